@@ -27,6 +27,10 @@ reduction and the on-device 6x6 / 3x3 solve.
 Timed region = exactly K steps from T0 = identity with conv_tol = 0 (never early-exits), bracketed by barrier +
 torch.cuda.synchronize(); MAX over ranks; rank 0 prints one JSON line.  `value` = correspondence pairs/s of the whole
 job (source points of all ranks x K / time); `icp_iterations_per_sec` = K / time is reported beside it.
+
+--dump-outputs DIR: after the timed steps, what the timed run computed in its last step as DIR/<name>.npy (float32 / float64, at
+most 64 MB; per-point arrays of clouds over 2^20 points: a fixed, seeded sample).  ICP: the transform, the loop's state (iterations,
+correspondences, last update norm) and the last search's correspondences; kmeans: centroids and labels; ransac: the inlier counts.
 """
 import argparse
 import ctypes as C
@@ -69,10 +73,35 @@ def parse():
     ap.add_argument("--no-extras", action="store_true", help="skip the cold-start / converging-trajectory measurements")
     ap.add_argument("--no-other-configs", action="store_true", help="default line only: skip the c2 / kmeans / ransac / c4_1gpu figures it carries as `other_configs`")
     ap.add_argument("--cpu-sample", type=int, default=2_000_000, help="source points of the CPU baseline sample")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all; arrays over one entry per point are a fixed, seeded sample of the points)")
     return ap.parse_args()
 
 
 TIMING_STRIDE = 4      # kernel timing inside the timed region: iterations 0-2 and every 4th one carry events
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 20  # per-point outputs of larger clouds: this many points, the same ones in every run of the same arguments
+
+
+def dump_sample(n, seed=0):
+    """Indices (ascending) of the points whose per-point outputs --dump-outputs writes: all of them up to DUMP_SAMPLE, else a seeded sample."""
+    if n <= DUMP_SAMPLE:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, DUMP_SAMPLE, replace=False))
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: {name: float32 / float64 array} -> dirname/<name>.npy"""
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    for k, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), (k, v.dtype)
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget"
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), v)
 
 
 def stratified_form_timing(ft, forms, timed):
@@ -331,6 +360,18 @@ def bench_icp(a, torch, rank, world, local_rank, emit=True):
         if strong:
             assert not ctx.slab_violation(), "a source point left its slab's halo: the partition had to be redone (not expected in the bench)"
     assert int(res.iterations) == a.steps, (res.iterations, a.steps)
+    if a.dump_outputs and rank == 0:
+        # what cilhip_icp_run hands its caller (the transform and the loop's state) and, one process, the correspondences of the last
+        # iteration's search (cilhip_get_nn, source order; no match = -1) -- read after the timed region, before anything else runs
+        outs = {"transform": np.array(res.T[:], np.float32).reshape(4, 4).T,
+                "state": np.array([res.iterations, res.last_ncorr, res.last_delta_norm], np.float64)}
+        if not sharded:
+            nn_idx, nn_d2 = ctx.get_nn()
+            sel = dump_sample(len(nn_idx))
+            nn = nn_idx[sel].astype(np.float64)
+            nn[nn_idx[sel] == 0xFFFFFFFF] = -1.0
+            outs.update(nn_source_index=sel.astype(np.float64), nn_target_index=nn, nn_sq_dist=nn_d2[sel])
+        dump_outputs(a.dump_outputs, outs)
     sf = None
     if sharded:
         # every rank's own figures of the timed region (sampled iterations: kernel_timing_stride), gathered for the line
@@ -667,7 +708,7 @@ def other_configs(a, torch, local_rank, budget_s=150.0):
             res[cfg] = {"skipped": f"wall-clock budget of {budget_s:.0f} s spent ({spent:.0f} s)"}
             continue
         b = copy.copy(a)
-        b.config, b.no_extras, b.no_cpu_baseline, b.n, b.metric = cfg, True, True, None, None
+        b.config, b.no_extras, b.no_cpu_baseline, b.n, b.metric, b.dump_outputs = cfg, True, True, None, None, None
         t0 = time.perf_counter()
         try:
             if cfg == "kmeans":
@@ -712,6 +753,8 @@ def bench_kmeans_sharded(a, torch, rank, world, local_rank):
     t1 = timed(1)                              # fixed costs (scale, labels) cancel in the difference
     tk = timed(a.steps + 1)
     assert km.getNumberOfPerformedIterations() == a.steps + 1
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"centroids": np.asarray(km.getClusterCentroids(), np.float32)})
     t = torch.tensor([tk - t1], dtype=torch.float64, device="cuda")
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
@@ -747,14 +790,21 @@ def bench_kmeans(a, torch, emit=True):
         torch.cuda.synchronize()
         return time.perf_counter() - t0, km
 
+    last = {}
+
     def per_step(kd=False):
         t1, _ = timed(1, kd)                  # fixed costs (centroid upload, label download) cancel in the difference
         tk, km = timed(a.steps + 1, kd)
         assert km.getNumberOfPerformedIterations() == a.steps + 1
+        last["km"] = km
         return tk - t1
 
     from cilantro_amd import clustering
     dt = per_step()                           # the default: the assignment pruned exactly (centroid grid, proof, fallbacks: kmeans.hip)
+    if a.dump_outputs:
+        sel = dump_sample(n)
+        dump_outputs(a.dump_outputs, {"centroids": np.asarray(last["km"].getClusterCentroids(), np.float32), "label_point_index": sel.astype(np.float64),
+                                      "labels": last["km"].getPointToClusterIndexMap()[sel].astype(np.float64)})
     clustering.set_pruning(False)
     try:
         KMeans3f(xd).cluster(c0, max_iter=1, tol=0.0)
@@ -848,6 +898,8 @@ def bench_ransac(a, torch, emit=True):
         torch.cuda.synchronize(); tks.append(time.perf_counter() - t0)
     t1, tk = min(t1s), min(tks)
     dt = tk - t1                                  # a.steps passes of 128 hypotheses
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"inlier_counts": cnt.astype(np.float64)})      # of the last timed call: every hypothesis it scored
     tests = float(n) * 128 * a.steps
     alg = 12.0 * n                                # one read of the points per 128-hypothesis pass
     rs_traffic, rs_note = config_traffic("ransac", {"n_points": n})

@@ -7,6 +7,8 @@ knn_golden.npz : outputs of the REFERENCE's own nanoflann 1.7.1 (oracle/_ref/lib
                  from /root/reference/include/cilantro/3rd_party/nanoflann/nanoflann.hpp) driven exactly as
                  cilantro drives it (core/kd_tree.hpp:63-109,162-170,283-291;
                  correspondence_search_kd_tree_utilities.hpp:7-51) on small seeded inputs.
+ref_nanoflann_golden.npz : the reference's nanoflann on the seeded inputs of the oracle tests that compare with it, and
+                 what it takes to rebuild the reference's frame_1.ply byte for byte (make_ref_nanoflann_fixture).
 icp_golden.npz : regression vectors of the ORACLE's ICP loop (the estimator half of the reference cannot be
                  run here -- Eigen3 is absent -- so these pin the oracle against itself over time and carry
                  the analytic ground truth T_true the recipe converges to).
@@ -122,6 +124,73 @@ def main_frame1():
     print(f"frames_full.npz: frame_1 {n1} points (+ normals), frame_2 {n2} points")
 
 
+def make_ref_nanoflann_fixture(out_path, ply="/root/reference/examples/test_clouds/frame_1.ply"):
+    """ref_nanoflann_golden.npz: what the REFERENCE's own nanoflann (oracle/_ref) answers on the seeded inputs of the tests in
+    tests/test_oracle_cpu.py that compare the oracle with it (the inputs are rebuilt there from the same seeds), and what
+    tests/test_ply_io.py needs to rebuild frame_1.ply byte for byte (its header, its colours -- points and normals are
+    frames_full.npz's -- and the file's SHA-256)."""
+    import hashlib
+
+    assert orc.ref_available(), "oracle/_ref missing: run `make -C oracle` where /root/reference exists"
+    out = {}
+    # test_oracle_kdtree_vs_live_reference
+    d = syn.make_pair(60000)
+    q = orc.transform_points(np.eye(4), d["src"])
+    for k, v in zip(("first", "second", "value"), orc.KDTree(d["dst"], use_ref=True).find_correspondences(q, d["max_sq_dist"], num_threads=2)):
+        out[f"live_{k}"] = v
+    # test_point_normal_feature_search_vs_reference_nanoflann
+    rng = np.random.default_rng(21)
+    n = 6000
+    dst = rng.random((n, 3)).astype(np.float32)
+    dn = rng.normal(size=(n, 3)); dn /= np.linalg.norm(dn, axis=1, keepdims=True); dn = dn.astype(np.float32)
+    src = (dst + rng.normal(size=(n, 3)).astype(np.float32) * np.float32(0.01))[rng.permutation(n)[:4000]]
+    sn = rng.normal(size=(len(src), 3)); sn /= np.linalg.norm(sn, axis=1, keepdims=True); sn = sn.astype(np.float32)
+    ang = 0.05
+    T = np.eye(4, dtype=np.float32)
+    T[:3, :3] = np.array([[np.cos(ang), -np.sin(ang), 0], [np.sin(ang), np.cos(ang), 0], [0, 0, 1]], np.float32)
+    T[:3, 3] = [0.01, -0.005, 0.002]
+    for i, w in enumerate((0.02, 0.3)):
+        dst6 = orc.point_normal_features(dst, dn, w)
+        q6 = orc.transform_features6(T, orc.point_normal_features(src, sn, w))
+        for j, max_sq in enumerate((0.05 ** 2, float("inf"))):
+            for k, v in zip(("first", "second", "value"), orc.find_correspondences_feat6(dst6, q6, max_sq, use_ref=True)):
+                out[f"feat6_{i}_{j}_{k}"] = v
+    # test_feat9_oracle_vs_reference_nanoflann_dim9
+    rng = np.random.default_rng(23)
+    n = 5000
+    dst = rng.random((n, 3)).astype(np.float32)
+    dn = rng.normal(size=(n, 3)); dn /= np.linalg.norm(dn, axis=1, keepdims=True); dn = dn.astype(np.float32)
+    dc = rng.random((n, 3)).astype(np.float32)
+    sel = rng.permutation(n)[:3000]
+    src = (dst + rng.normal(size=(n, 3)).astype(np.float32) * np.float32(0.01))[sel]
+    sn = dn[sel]
+    sc = np.clip(dc[sel] + rng.normal(0, 0.05, (len(sel), 3)), 0, 1).astype(np.float32)
+    for i, (wn, wc) in enumerate(((0.02, 0.03), (0.3, 0.1), (0.0, 0.2))):
+        d9 = orc.point_normal_color_features(dst, dn, dc, wn, wc)
+        q9 = orc.transform_features9(T, orc.point_normal_color_features(src, sn, sc, wn, wc))
+        for j, max_sq in enumerate((0.05 ** 2, float("inf"))):
+            for k, v in zip(("first", "second", "value"), orc.find_correspondences_feat9(d9, q9, max_sq, use_ref=True)):
+                out[f"feat9_{i}_{j}_{k}"] = v
+    # test_radius_search_oracle_vs_reference_nanoflann: per radius the reference's lists of all queries, one after another
+    rng = np.random.default_rng(31)
+    pts = rng.random((4000, 3)).astype(np.float32)
+    q = np.concatenate([pts[:50], rng.random((50, 3)).astype(np.float32) * 1.2 - 0.1])
+    tree = orc.KDTree(pts, use_ref=True)
+    for j, r2 in enumerate((0.0, 0.03 ** 2, 0.11 ** 2)):
+        lists = [orc.ref_radius_search(tree, q[i], r2) for i in range(len(q))]
+        out[f"radius_{j}_off"] = np.cumsum([0] + [len(ri) for ri, _ in lists]).astype(np.int64)
+        out[f"radius_{j}_idx"] = np.concatenate([np.asarray(ri, np.int64) for ri, _ in lists])
+        out[f"radius_{j}_d2"] = np.concatenate([np.asarray(rd, np.float32) for _, rd in lists])
+    # test_reads_the_references_test_cloud: frame_1.ply = header + 120111 x (float xyz, float normal, uchar rgb)
+    raw = open(ply, "rb").read()
+    h = raw.index(b"end_header\n") + len(b"end_header\n")
+    body = np.frombuffer(raw[h:], np.dtype([("p", "<f4", 3), ("n", "<f4", 3), ("c", "u1", 3)]))
+    out.update(frame1_ply_header=np.frombuffer(raw[:h], np.uint8), frame1_colors=np.ascontiguousarray(body["c"]),
+               frame1_sha256=np.frombuffer(hashlib.sha256(raw).digest(), np.uint8))
+    np.savez_compressed(out_path, **out)
+
+
 if __name__ == "__main__":
     main()
     main_frame1()
+    make_ref_nanoflann_fixture(os.path.join(HERE, "ref_nanoflann_golden.npz"))

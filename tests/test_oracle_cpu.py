@@ -1,5 +1,6 @@
 """CPU tests (-m "not gpu"): the oracle against the reference's golden vectors, known answers and
-independent numpy restatements.  No GPU, no /root/reference needed (golden fixtures are committed)."""
+independent numpy restatements.  No GPU and no reference tree needed: the reference's answers are committed fixtures
+(tests/golden/); where oracle/_ref is built, the tests compare with the reference live as well."""
 import os
 
 import numpy as np
@@ -13,6 +14,12 @@ GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 @pytest.fixture(scope="module")
 def knn_gold():
     return np.load(os.path.join(GOLD, "knn_golden.npz"))
+
+
+@pytest.fixture(scope="module")
+def ref_gold():
+    """the reference nanoflann's answers on the seeded inputs below (tests/golden/make_golden.py: make_ref_nanoflann_fixture)"""
+    return np.load(os.path.join(GOLD, "ref_nanoflann_golden.npz"))
 
 
 def test_kd_tree_example_known_answer(orc, knn_gold):
@@ -47,15 +54,17 @@ def test_oracle_kdtree_matches_reference_nanoflann_golden(orc, knn_gold, name):
         assert bi[kept][j] < di[j]                     # brute force = lowest index
 
 
-def test_oracle_kdtree_vs_live_reference(orc):
-    if not orc.ref_available():
-        pytest.skip("oracle/_ref not built (needs /root/reference at build time)")
+def test_oracle_kdtree_vs_live_reference(orc, ref_gold):
+    """against the reference's stored answers, and against the reference itself where oracle/_ref is built"""
     d = syn.make_pair(60000)
     q = orc.transform_points(np.eye(4), d["src"])
     a = orc.KDTree(d["dst"]).find_correspondences(q, d["max_sq_dist"])
-    b = orc.KDTree(d["dst"], use_ref=True).find_correspondences(q, d["max_sq_dist"], num_threads=2)
-    for x, y in zip(a, b):
-        assert np.array_equal(x, y)
+    for x, k in zip(a, ("first", "second", "value")):
+        assert np.array_equal(x, ref_gold[f"live_{k}"]), k
+    if orc.ref_available():
+        b = orc.KDTree(d["dst"], use_ref=True).find_correspondences(q, d["max_sq_dist"], num_threads=2)
+        for x, y in zip(a, b):
+            assert np.array_equal(x, y)
 
 
 def test_radius_is_strict_and_empty_inputs(orc):
@@ -292,12 +301,10 @@ def test_affine_estimator_known_answer(orc):
     assert np.abs(back - dst).max() < 5e-4 and r["iterations"] < 30
 
 
-def test_point_normal_feature_search_vs_reference_nanoflann(orc):
+def test_point_normal_feature_search_vs_reference_nanoflann(orc, ref_gold):
     """6-D point+normal features (common_transformable_feature_adaptors.hpp:60-161): the oracle's exhaustive search with
     the pinned DIM = 6 distance arithmetic against the reference's own nanoflann instantiated for DIM = 6 -- same indices,
-    bit-identical distances, same strict radius test."""
-    if not orc.ref_available():
-        pytest.skip("oracle/_ref not built")
+    bit-identical distances, same strict radius test (the reference's stored answers; where oracle/_ref is built, also live)."""
     rng = np.random.default_rng(21)
     n = 6000
     dst = rng.random((n, 3)).astype(np.float32)
@@ -308,26 +315,28 @@ def test_point_normal_feature_search_vs_reference_nanoflann(orc):
     T = np.eye(4, dtype=np.float32)
     T[:3, :3] = np.array([[np.cos(ang), -np.sin(ang), 0], [np.sin(ang), np.cos(ang), 0], [0, 0, 1]], np.float32)
     T[:3, 3] = [0.01, -0.005, 0.002]
-    for w in (0.02, 0.3):
+    for i, w in enumerate((0.02, 0.3)):
         dst6 = orc.point_normal_features(dst, dn, w)
         assert np.array_equal(dst6[:, :3], dst) and np.array_equal(dst6[:, 3:], np.float32(w) * dn)
         q6 = orc.transform_features6(T, orc.point_normal_features(src, sn, w))
         assert np.array_equal(q6[:, :3], orc.transform_points(T, src))
-        for max_sq in (0.05 ** 2, float("inf")):
+        for j, max_sq in enumerate((0.05 ** 2, float("inf"))):
             a1, a2, av = orc.find_correspondences_feat6(dst6, q6, max_sq)
-            b1, b2, bv = orc.find_correspondences_feat6(dst6, q6, max_sq, use_ref=True)
+            b1, b2, bv = (ref_gold[f"feat6_{i}_{j}_{k}"] for k in ("first", "second", "value"))
             assert np.array_equal(a2, b2) and np.array_equal(a1, b1) and np.array_equal(av, bv)
+            if orc.ref_available():
+                b1, b2, bv = orc.find_correspondences_feat6(dst6, q6, max_sq, use_ref=True)
+                assert np.array_equal(a2, b2) and np.array_equal(a1, b1) and np.array_equal(av, bv)
         # with a heavy normal weight the feature match differs from the plain nearest point for many queries
     p1, _, _ = orc.KDTree(dst).find_correspondences(q6[:, :3].copy(), float("inf"))
     assert np.mean(p1 != a1) > 0.2
 
 
-def test_feat9_oracle_vs_reference_nanoflann_dim9(orc):
+def test_feat9_oracle_vs_reference_nanoflann_dim9(orc, ref_gold):
     """PointNormalColorFeaturesAdaptor (common_transformable_feature_adaptors.hpp:255-343): the oracle's exhaustive 9-D search with
     nanoflann's DIM = 9 summation order (two groups of four, one tail term) against the reference's own nanoflann instantiated for
-    DIM = 9 -- indices and squared distances bit for bit; the transform moves points and normals, not colours."""
-    if not orc.ref_available():
-        pytest.skip("oracle/_ref not built")
+    DIM = 9 -- indices and squared distances bit for bit; the transform moves points and normals, not colours (the reference's
+    stored answers; where oracle/_ref is built, also live)."""
     rng = np.random.default_rng(23)
     n = 5000
     dst = rng.random((n, 3)).astype(np.float32)
@@ -341,39 +350,45 @@ def test_feat9_oracle_vs_reference_nanoflann_dim9(orc):
     T = np.eye(4, dtype=np.float32)
     T[:3, :3] = np.array([[np.cos(ang), -np.sin(ang), 0], [np.sin(ang), np.cos(ang), 0], [0, 0, 1]], np.float32)
     T[:3, 3] = [0.01, -0.005, 0.002]
-    for wn, wc in ((0.02, 0.03), (0.3, 0.1), (0.0, 0.2)):
+    for i, (wn, wc) in enumerate(((0.02, 0.03), (0.3, 0.1), (0.0, 0.2))):
         d9 = orc.point_normal_color_features(dst, dn, dc, wn, wc)
         assert np.array_equal(d9[:, :3], dst) and np.array_equal(d9[:, 3:6], np.float32(wn) * dn) and np.array_equal(d9[:, 6:], np.float32(wc) * dc)
         s9 = orc.point_normal_color_features(src, sn, sc, wn, wc)
         q9 = orc.transform_features9(T, s9)
         assert np.array_equal(q9[:, :3], orc.transform_points(T, src)) and np.array_equal(q9[:, 6:], s9[:, 6:])
         assert np.array_equal(q9[:, :6], orc.transform_features6(T, s9[:, :6].copy()))
-        for max_sq in (0.05 ** 2, float("inf")):
+        for j, max_sq in enumerate((0.05 ** 2, float("inf"))):
             a = orc.find_correspondences_feat9(d9, q9, max_sq)
-            b = orc.find_correspondences_feat9(d9, q9, max_sq, use_ref=True)
+            b = [ref_gold[f"feat9_{i}_{j}_{k}"] for k in ("first", "second", "value")]
             assert all(np.array_equal(x, y) for x, y in zip(a, b)) and len(a[0]) > 0
+            if orc.ref_available():
+                b = orc.find_correspondences_feat9(d9, q9, max_sq, use_ref=True)
+                assert all(np.array_equal(x, y) for x, y in zip(a, b))
     # the 9-D distance is not the 6-D one plus a colour term in a different order: DIM = 9 groups (d4, d5) with the colour's first two
     a6 = orc.find_correspondences_feat6(d9[:, :6].copy(), q9[:, :6].copy(), float("inf"))
     assert len(a6[0]) == len(a[0])
 
 
-def test_radius_search_oracle_vs_reference_nanoflann(orc):
+def test_radius_search_oracle_vs_reference_nanoflann(orc, ref_gold):
     """KDTree::radiusSearch (core/kd_tree.hpp:251-282): the exhaustive oracle against the reference's own nanoflann with
-    cilantro's RadiusSearchResultAdaptor -- same neighbour sets, bit-identical sorted distances, strict radius."""
-    if not orc.ref_available():
-        pytest.skip("oracle/_ref not built")
+    cilantro's RadiusSearchResultAdaptor -- same neighbour sets, bit-identical sorted distances, strict radius (the reference's
+    stored lists; where oracle/_ref is built, also live)."""
     rng = np.random.default_rng(31)
     pts = rng.random((4000, 3)).astype(np.float32)
     q = np.concatenate([pts[:50], rng.random((50, 3)).astype(np.float32) * 1.2 - 0.1])
-    tree = orc.KDTree(pts, use_ref=True)
-    for r2 in (0.0, 0.03 ** 2, 0.11 ** 2):
+    tree = orc.KDTree(pts, use_ref=True) if orc.ref_available() else None
+    for j, r2 in enumerate((0.0, 0.03 ** 2, 0.11 ** 2)):
         off, idx, d2 = orc.radius_search(pts, q, r2)
         assert off[0] == 0 and off[-1] == len(idx)
+        goff, gidx, gd2 = ref_gold[f"radius_{j}_off"], ref_gold[f"radius_{j}_idx"], ref_gold[f"radius_{j}_d2"]
         for i in range(len(q)):
-            ri, rd = orc.ref_radius_search(tree, q[i], r2)
             mine_i, mine_d = idx[off[i]:off[i + 1]], d2[off[i]:off[i + 1]]
-            assert np.array_equal(rd, mine_d)                      # sorted distances, bit for bit
-            assert np.array_equal(np.sort(ri), np.sort(mine_i))    # the same set (tie order is unspecified in the reference)
+            refs = [(gidx[goff[i]:goff[i + 1]], gd2[goff[i]:goff[i + 1]])]
+            if tree is not None:
+                refs.append(orc.ref_radius_search(tree, q[i], r2))
+            for ri, rd in refs:
+                assert np.array_equal(rd, mine_d)                      # sorted distances, bit for bit
+                assert np.array_equal(np.sort(ri), np.sort(mine_i))    # the same set (tie order is unspecified in the reference)
             assert np.all(mine_d < np.float32(r2)) if len(mine_d) else True
     # a query point that is a tree point sits in its own list at distance 0 (first)
     off, idx, d2 = orc.radius_search(pts, pts[:5], 0.05 ** 2)

@@ -55,11 +55,19 @@ def test_cpp_header_interoperates(tmp_path, hip_lib, orc):
     assert np.all(r["normals"][:, 2] == 1.0)
 
 
-def test_reads_the_references_test_cloud():
-    """examples/test_clouds/frame_1.ply (binary little endian, xyz + normals + uchar rgb): only where the reference is present"""
-    f = "/root/reference/examples/test_clouds/frame_1.ply"
-    if not os.path.exists(f):
-        pytest.skip("reference not present on this box")
+def test_reads_the_references_test_cloud(tmp_path):
+    """examples/test_clouds/frame_1.ply (binary little endian, xyz + normals + uchar rgb), rebuilt byte for byte from the committed
+    fixtures (its header and colours: ref_nanoflann_golden.npz, its points and normals: frames_full.npz) and checked by its SHA-256"""
+    import hashlib
+
+    gold = os.path.join(ROOT, "tests", "golden")
+    g, fr = np.load(os.path.join(gold, "ref_nanoflann_golden.npz")), np.load(os.path.join(gold, "frames_full.npz"))
+    body = np.zeros(len(g["frame1_colors"]), np.dtype([("p", "<f4", 3), ("n", "<f4", 3), ("c", "u1", 3)]))
+    body["p"], body["n"], body["c"] = fr["p1"], fr["n1"], g["frame1_colors"]
+    raw = g["frame1_ply_header"].tobytes() + body.tobytes()
+    assert hashlib.sha256(raw).digest() == g["frame1_sha256"].tobytes()
+    f = str(tmp_path / "frame_1.ply")
+    open(f, "wb").write(raw)
     r = read_ply(f)
     assert r["points"].shape == (120111, 3) and r["normals"].shape == (120111, 3) and r["colors"].shape == (120111, 3)
     ok = np.isfinite(r["normals"]).all(axis=1)
