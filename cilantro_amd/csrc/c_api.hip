@@ -489,6 +489,11 @@ int cilhip_get_option(cilhip_ctx* c, const char* key, double* value) {
 int cilhip_set_option(cilhip_ctx* c, const char* key, double value) {
   if (!c || !key) return CILHIP_ERR_INVALID;
   if (value != value) return fail(c, CILHIP_ERR_INVALID, "set_option: the value is not a number");
+  // every row's admissible range holds for every key (a mistyped "tiled" = 3 would otherwise run some other form); the rows
+  // below only add what a range cannot say (the discrete values of group_search, tie_rule, ...)
+  for (int i = 0; i < N_OPTIONS; ++i)
+    if (!strcmp(key, g_options[i].info.key) && !(value >= g_options[i].info.min_value && value <= g_options[i].info.max_value))
+      return fail(c, CILHIP_ERR_INVALID, "set_option: value outside the option's [min_value, max_value] (cilhip_option_info)");
   if (!strcmp(key, "fused")) { c->fused = value != 0.0; return CILHIP_OK; }
   // (a finished run's set that has not been searched again yet -- cilhip_get_last_matches_origin 2 -- would be filtered with the
   //  NEW values: a changed post-filter drops it; a set already in memory is what its search left, whatever is set afterwards)

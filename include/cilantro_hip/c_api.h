@@ -735,8 +735,9 @@ int cilhip_set_option(cilhip_ctx* ctx, const char* key, double value);
 /* The same options as a typed table: an enum a C caller can check at compile time, and per option its key, default, admissible
  * range and one line of documentation (the long form is the comment above).  cilhip_option_info(id) is valid for
  * 0 <= id < cilhip_option_count() == CILHIP_OPT_COUNT, in the enum's order (NULL otherwise); cilhip_set_option_id is
- * cilhip_set_option by id; cilhip_get_option reads the current value back.  tests/test_capi_symbols.py walks the table: every
- * option is documented, accepted with its default, readable, and named by at least one test. */
+ * cilhip_set_option by id; cilhip_get_option reads the current value back.  cilhip_set_option refuses (CILHIP_ERR_INVALID) a value
+ * outside [min_value, max_value] of its row.  tests/test_capi_symbols.py walks the table: every option is documented, accepted
+ * with its default, readable, refused outside its range, and named by at least one test. */
 typedef enum cilhip_option {
   CILHIP_OPT_FUSED = 0, CILHIP_OPT_INLIER_FRACTION, CILHIP_OPT_ONE_TO_ONE, CILHIP_OPT_TILED, CILHIP_OPT_WARM_START, CILHIP_OPT_WARM_FORECAST,
   CILHIP_OPT_FUSED_EPILOGUE, CILHIP_OPT_GROUP_SEARCH, CILHIP_OPT_TIE_RULE, CILHIP_OPT_WARM_EXTRA_FRACTION, CILHIP_OPT_PAIR_RECORDS,

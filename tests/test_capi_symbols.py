@@ -121,6 +121,14 @@ def test_every_option_takes_its_default_and_reads_back():
     for key, bad in (("tie_rule", 3), ("group_search", 5), ("search_direction", 7), ("kernel_timing_stride", 0), ("refined_occupancy_factor", 0.5), ("tiled", float("nan"))):
         with pytest.raises(capi.CilhipError):
             ctx.set_option(key, bad)
+    # one value outside every row's [min_value, max_value] (a mistyped "tiled" = 3 must not run some other form): refused by key and by
+    # id, and the option keeps its value
+    for o in capi.options():
+        bad = o["max"] + 1.0 if o["max"] < 1e30 else o["min"] - 1.0
+        for setter in (lambda v: ctx.set_option(o["key"], v), lambda v: ctx._ck(ctx._L.cilhip_set_option_id(ctx._h, o["id"], v))):
+            with pytest.raises(capi.CilhipError):
+                setter(bad)
+            assert ctx.get_option(o["key"]) == pytest.approx(o["default"]), (o["key"], bad)
     with pytest.raises(capi.CilhipError):
         ctx.get_option("no_such_option")
     ctx.close()

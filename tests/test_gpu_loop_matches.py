@@ -90,7 +90,8 @@ def _loop_matches(Context, D, N, S, r2, iters, metric=capi.METRIC_COMBINED, w_p2
     return _signed(idx), d2, T, ctx, int(res.last_ncorr)
 
 
-def _check_against_fresh_search_and_reference(Context, orc, name, D, N, S, r2, gi, gd, T, ncorr, sample_n, rng, allow_ties):
+def _check_against_fresh_search_and_reference(Context, orc, name, D, N, S, r2, gi, gd, T, ncorr, sample_n, rng, allow_ties, tree=None):
+    """tree: the kd-tree over D to compare with (built here when None; callers checking several runs on one target pass it)"""
     n = len(S)
     assert int(np.count_nonzero(gi >= 0)) == ncorr, name                  # last_ncorr counts exactly this set
     # (1) a fresh search by the search-only kernels under the same transform: every index, every d2 bit
@@ -110,7 +111,8 @@ def _check_against_fresh_search_and_reference(Context, orc, name, D, N, S, r2, g
     # (2) the reference's nanoflann over a sample of the queries at that transform
     sample = np.sort(rng.choice(n, min(sample_n, n), replace=False))
     q = orc.transform_points(T, S[sample])
-    tree = orc.KDTree(D, use_ref=orc.ref_available())
+    if tree is None:
+        tree = orc.KDTree(D, use_ref=orc.ref_available())
     o1, o2, ov = tree.find_correspondences(q, float(r2))
     oi = np.full(len(sample), -1, np.int64)
     od = np.zeros(len(sample), np.float32)
