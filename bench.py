@@ -31,6 +31,11 @@ job (source points of all ranks x K / time); `icp_iterations_per_sec` = K / time
 --dump-outputs DIR: after the timed steps, what the timed run computed in its last step as DIR/<name>.npy (float32 / float64, at
 most 64 MB; per-point arrays of clouds over 2^20 points: a fixed, seeded sample).  ICP: the transform, the loop's state (iterations,
 correspondences, last update norm) and the last search's correspondences; kmeans: centroids and labels; ransac: the inlier counts.
+
+A plain run does what the line's headline needs and no more: set-up, warm-up, the K timed steps, --dump-outputs, the line (its
+figures derived from the timed steps included).  --full adds, after the timed steps, everything that takes runs of its own: the
+CPU baseline, the device copy bandwidth beside the roofline, the cold-start / converging / independent-source / variant /
+multi-device legs and the other configurations (`other_configs`) of the default line, KMeans' exhaustive and kd-tree passes.
 """
 import argparse
 import ctypes as C
@@ -69,9 +74,12 @@ def parse():
     ap.add_argument("--selftest-spawn", action="store_true", help="(tests) exercise the self-launch path on CPU: gloo, one all-reduce, no GPU work")
     ap.add_argument("--n", type=int, default=None, help="override the number of target points (source scaled alike): quick runs only")
     ap.add_argument("--metric", choices=["p2plane", "p2p"], default=None, help="(compatibility) c3 sizes with another metric")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the cold-start / converging-trajectory measurements")
-    ap.add_argument("--no-other-configs", action="store_true", help="default line only: skip the c2 / kmeans / ransac / c4_1gpu figures it carries as `other_configs`")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure what takes runs of its own: the CPU baseline, the copy bandwidth, "
+                                                        "the legs beside the loop, `other_configs`, KMeans' exhaustive / kd-tree passes (off: the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="skip the source sort before the warm-up (the first run does it) and, --full, the cold-start / "
+                                                             "converging-trajectory measurements")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full, default line only: skip the c2 / kmeans / ransac / c4_1gpu figures it carries as `other_configs`")
     ap.add_argument("--cpu-sample", type=int, default=2_000_000, help="source points of the CPU baseline sample")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, "
@@ -438,7 +446,7 @@ def bench_icp(a, torch, rank, world, local_rank, emit=True):
             avg_ms = ft[dom][0] / ft[dom][1]
             ach = alg_bytes / (avg_ms * 1e-3) / 1e9
             roof = {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
-                    "measured_copy_bandwidth_GBps": copy_bandwidth(torch), "traffic": traffic, "traffic_note": traffic_note,
+                    "measured_copy_bandwidth_GBps": copy_bandwidth(torch) if a.full else None, "traffic": traffic, "traffic_note": traffic_note,
                     "kernel": kern, "form": dom, "avg_kernel_ms": avg_ms, "launches": n_form[dom], "timed_launches": ft[dom][1], "algorithmic_bytes_per_launch": alg_bytes,
                     "timing": "hipEvents attached to the kernels' own dispatch packets on the context's stream, inside the timed region: iterations 0-2 and "
                               f"every {TIMING_STRIDE}th one (an event between two dependent kernels idles the device for ~6 us, two per iteration are a tenth of a "
@@ -502,7 +510,7 @@ def bench_icp(a, torch, rank, world, local_rank, emit=True):
         }
         if sf is not None:
             out.update(sf)
-    if not sharded and not a.no_extras:
+    if not sharded and a.full and not a.no_extras:
         extras = {}
         # cost of a whole estimate() the way the reference's example calls it (15 iterations), sort included: what a caller sees
         cold = []
@@ -678,12 +686,12 @@ def bench_icp(a, torch, rank, world, local_rank, emit=True):
         except Exception as e:
             extras["multi_device_c_loop_one_shard"] = {"error": repr(e)}
         out.update(extras)
-    if rank == 0 and not sharded and not a.no_cpu_baseline:
+    if rank == 0 and not sharded and a.full and not a.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline_icp(d, metric, w_p2p, w_p2pl, min(a.cpu_sample, ns), T0)
         except Exception as e:  # the baseline is a report, never the product path
             out["cpu_baseline"] = {"error": repr(e)}
-    if rank == 0 and emit and not sharded and a.config == "c3" and not a.no_extras and not a.no_other_configs and a.n is None:
+    if rank == 0 and emit and not sharded and a.config == "c3" and a.full and not a.no_extras and not a.no_other_configs and a.n is None:
         out["other_configs"] = other_configs(a, torch, local_rank)
     if rank == 0 and emit:
         print(json.dumps(out))
@@ -695,9 +703,9 @@ def bench_icp(a, torch, rank, world, local_rank, emit=True):
 
 
 def other_configs(a, torch, local_rank, budget_s=150.0):
-    """The default line is the one the driver times; the other BASELINE configurations ride on it as `other_configs` -- ms_per_step and
-    roofline.frac each, measured by the very functions their own `--config` lines come from (`value`, `config`, `roofline` of the line
-    itself stay C3's).  A wall-clock budget keeps the default run inside a few minutes: what does not fit is named, not dropped silently."""
+    """--full: the other BASELINE configurations ride on the default line as `other_configs` -- ms_per_step and roofline.frac each,
+    measured by the very functions their own `--config` lines come from (`value`, `config`, `roofline` of the line itself stay C3's).
+    A wall-clock budget keeps the run inside a few minutes: what does not fit is named, not dropped silently."""
     import copy
     import gc
 
@@ -805,16 +813,17 @@ def bench_kmeans(a, torch, emit=True):
         sel = dump_sample(n)
         dump_outputs(a.dump_outputs, {"centroids": np.asarray(last["km"].getClusterCentroids(), np.float32), "label_point_index": sel.astype(np.float64),
                                       "labels": last["km"].getPointToClusterIndexMap()[sel].astype(np.float64)})
-    clustering.set_pruning(False)
-    try:
-        KMeans3f(xd).cluster(c0, max_iter=1, tol=0.0)
-        dt_ex = per_step()                    # the exhaustive pass of the same library (n * k distances): what round 4's line measured
-    finally:
-        clustering.set_pruning(True)
+    dt_ex = dt_kd = None
+    if a.full:
+        clustering.set_pruning(False)
+        try:
+            KMeans3f(xd).cluster(c0, max_iter=1, tol=0.0)
+            dt_ex = per_step()                # the exhaustive pass of the same library (n * k distances): what round 4's line measured
+        finally:
+            clustering.set_pruning(True)
     # ... and the reference's use_kd_tree branch (the mode its examples/kmeans.cpp runs): the same pruned pass with nanoflann's rounding, the
     # order tables of the tree over the centroids built in the iterations that meet exactly equidistant centroids
-    dt_kd = None
-    if emit:
+    if a.full and emit:
         try:
             KMeans3f(xd).cluster(c0, max_iter=1, tol=0.0, use_kd_tree=True)
             dt_kd = per_step(True)
@@ -845,10 +854,11 @@ def bench_kmeans(a, torch, emit=True):
                                     if (n == 50_000_000 and k == 1024) else None)},
            "kd_branch": ({"ms_per_step": dt_kd * 1e3 / a.steps, "note": "use_kd_tree = true (clustering/kmeans.hpp:86-94): labels equal the reference's tree search, exact ties included"}
                          if dt_kd is not None else None),
-           "exhaustive_pass": {"ms_per_step": dt_ex * 1e3 / a.steps, "distances_per_sec": evals / dt_ex, "kernel": "k_assign_accumulate",
-                               "roofline": {"bound": "valu", "achieved": flops_ex / dt_ex / 1e12, "peak": VALU_NOFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": flops_ex / dt_ex / 1e12 / VALU_NOFMA_PEAK_TFLOPS,
-                                            "note": "8 individually rounded f32 ops per distance (no FMA contraction: labels must match the reference bit for bit); peak = half of the 157.3 TFLOP/s FMA figure"}}}
-    if not a.no_cpu_baseline:
+           "exhaustive_pass": ({"ms_per_step": dt_ex * 1e3 / a.steps, "distances_per_sec": evals / dt_ex, "kernel": "k_assign_accumulate",
+                                "roofline": {"bound": "valu", "achieved": flops_ex / dt_ex / 1e12, "peak": VALU_NOFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": flops_ex / dt_ex / 1e12 / VALU_NOFMA_PEAK_TFLOPS,
+                                             "note": "8 individually rounded f32 ops per distance (no FMA contraction: labels must match the reference bit for bit); peak = half of the 157.3 TFLOP/s FMA figure"}}
+                               if dt_ex is not None else None)}
+    if a.full and not a.no_cpu_baseline:
         try:
             from oracle import oracle as orc
 
@@ -918,7 +928,7 @@ def bench_ransac(a, torch, emit=True):
                         # v_pk_*, 1.45 ns for single-operation f32 instructions), 1024 SIMDs
                         "issue_bound": {"ns_per_128_lane_tests": 6 * 2.0 + 2 * 1.45, "bound_ms_per_step": float(n) * 128 / 128.0 * (6 * 2.0 + 2 * 1.45) * 1e-6 / 1024.0,
                                         "frac": float(n) * 128 / 128.0 * (6 * 2.0 + 2 * 1.45) * 1e-6 / 1024.0 / (dt * 1e3 / a.steps)}}}
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         try:
             from oracle import oracle as orc
 

@@ -1,5 +1,6 @@
 """bench.py's launch contract (CPU): `python bench.py --gpus N` starts N ranks itself or fails loudly -- it never prints a
-1-GPU line for an N-GPU request (round-2 VERDICT, missing 1).  And (GPU) what --dump-outputs writes."""
+1-GPU line for an N-GPU request (round-2 VERDICT, missing 1).  And (GPU) what --dump-outputs writes and what a plain run leaves
+to --full."""
 import json
 import os
 import subprocess
@@ -72,3 +73,23 @@ def test_dump_outputs_writes_the_last_timed_step(tmp_path):
     for k in ("nn_source_index", "nn_target_index", "nn_sq_dist", "state"):
         assert np.array_equal(a[k], b[k]), k
     assert np.allclose(a["transform"], b["transform"], rtol=0.0, atol=1e-6)
+
+
+@pytest.mark.gpu
+def test_plain_run_leaves_the_runs_of_their_own_to_full():
+    """A plain run prints the headline line and no figure that takes a run of its own; --full adds them after the same timed steps"""
+    args = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--n", "200000"]
+    lines = []
+    for extra in ([], ["--full"]):
+        out = subprocess.run([sys.executable, BENCH] + args + extra, capture_output=True, text=True, timeout=600, env=_env())
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+        lines.append(json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]))
+    plain, full = lines
+    for r in (plain, full):
+        assert r["unit"] == "pairs/s" and r["higher_is_better"] and r["dtype"] == "f32 search / f64 accumulate+solve"
+        assert r["steps"] == 3 and r["ms_per_step"] > 0.0 and r["value"] == pytest.approx(200000 * 1e3 / r["ms_per_step"])
+    runs_of_their_own = ("icp_estimate_ms_15iter_cold", "without_warm_start", "converging_run", "independent_source", "variants",
+                         "multi_device_c_loop_one_shard", "cpu_baseline")
+    assert [k for k in runs_of_their_own if k in plain] == [] and plain["roofline"]["measured_copy_bandwidth_GBps"] is None
+    assert [k for k in runs_of_their_own if k not in full or (isinstance(full[k], dict) and "error" in full[k])] == []
+    assert full["roofline"]["measured_copy_bandwidth_GBps"] > 0.0 and full["cpu_baseline"]["value"] > 0.0

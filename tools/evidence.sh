@@ -9,13 +9,13 @@
 #   c5pmc    KMeans' pruned assignment under the SQ / LDS counter passes + every launch's duration
 #   regimes  the loop iteration by iteration (recipe / independent source / sensor frames / configs[3]'s shape), the real-cloud report,
 #            variants, search directions, the size sweep, the read-bandwidth probe, the tie-order build times
-#   full     the default line in full (extras + CPU baseline): the long one, last
+#   full     the default line in full (`bench.py --full`: extras + CPU baseline + other_configs): the long one, last
 #   lines    ONLY the bench lines again (default in full, c2, c4_1gpu, kmeans, ransac), no profiler: after `core` / `configs` of the same build
 #            were collected into profiles/ (tools/collect_profiles.sh), so that the lines quote the build's counter traffic
 cd /tmp && export TMPDIR=/tmp
 TAG=${1:-dev}; shift; SECTIONS=${*:-core configs regimes full}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/${TAG}final; mkdir -p $O; cd $R
-CMD="python bench.py --steps 20 --warmup 3 --no-extras --no-cpu-baseline"
+CMD="python bench.py --full --steps 20 --warmup 3 --no-extras --no-cpu-baseline"
 has() { [[ " $SECTIONS " == *" $1 "* ]]; }
 prune() { find $O -name "*.csv" -size +1M -delete; find $O -name "*.db" -delete; }
 if has core; then
@@ -39,20 +39,20 @@ if has search; then
 fi
 if has configs; then
   for cfg in c2 c4_1gpu; do
-    C2="python bench.py --config $cfg --steps 20 --warmup 3 --no-extras --no-cpu-baseline"
+    C2="python bench.py --full --config $cfg --steps 20 --warmup 3 --no-extras --no-cpu-baseline"
     timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$cfg -- $C2 > $O/bench_${cfg}_profiled.json 2> $O/trace_$cfg.log
     cp $O/trace_$cfg/*/*_kernel_stats.csv $O/config_${cfg}_kernel_stats.csv 2>/dev/null
   done
-  timeout 200 python bench.py --config c2 > $O/bench_c2.json 2> $O/bench_c2.err; cut -c1-300 $O/bench_c2.json
-  timeout 300 python bench.py --config c4_1gpu --steps 20 --warmup 3 --no-extras > $O/bench_c4_1gpu.json 2> $O/bench_c4.err; cut -c1-300 $O/bench_c4_1gpu.json
+  timeout 200 python bench.py --full --config c2 > $O/bench_c2.json 2> $O/bench_c2.err; cut -c1-300 $O/bench_c2.json
+  timeout 300 python bench.py --full --config c4_1gpu --steps 20 --warmup 3 --no-extras > $O/bench_c4_1gpu.json 2> $O/bench_c4.err; cut -c1-300 $O/bench_c4_1gpu.json
   for cfg in kmeans ransac; do
-    C2="python bench.py --config $cfg --no-cpu-baseline"
+    C2="python bench.py --full --config $cfg --no-cpu-baseline"
     timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$cfg -- $C2 > $O/bench_${cfg}_profiled.json 2> $O/trace_$cfg.log
     cp $O/trace_$cfg/*/*_kernel_stats.csv $O/config_${cfg}_kernel_stats.csv 2>/dev/null
   done
   # HBM traffic of every configuration's dominant kernel (the counters of `core`, per configuration): profiles/<tag>_traffic_<cfg>.json
   for cfg in c2 c4_1gpu; do
-    C2="python bench.py --config $cfg --steps 20 --warmup 3 --no-extras --no-cpu-baseline --no-other-configs"
+    C2="python bench.py --full --config $cfg --steps 20 --warmup 3 --no-extras --no-cpu-baseline --no-other-configs"
     mkdir -p $O/pmc_$cfg
     timeout 300 $C2 > $O/pmc_$cfg/bench_line.json 2> $O/pmc_$cfg/bench.err
     timeout 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_$cfg/fetch -- $C2 > $O/pmc_$cfg/fetch.log 2>&1
@@ -60,7 +60,7 @@ if has configs; then
     python tools/make_traffic_json.py $O/pmc_$cfg > $O/traffic_$cfg.json 2> $O/traffic_$cfg.err
   done
   for cfg in kmeans ransac; do
-    C2="python bench.py --config $cfg --no-cpu-baseline"
+    C2="python bench.py --full --config $cfg --no-cpu-baseline"
     mkdir -p $O/pmc_$cfg
     timeout 300 $C2 > $O/pmc_$cfg/bench_line.json 2> $O/pmc_$cfg/bench.err
     timeout 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_$cfg/fetch -- $C2 > $O/pmc_$cfg/fetch.log 2>&1
@@ -72,7 +72,7 @@ if has configs; then
 fi
 if has c5pmc; then
   # KMeans' pruned assignment: the SQ / LDS counter passes that name its limiter, and every launch's duration (the 1.3 - 3.4 ms spread)
-  KM="python bench.py --config kmeans --no-cpu-baseline"
+  KM="python bench.py --full --config kmeans --no-cpu-baseline"
   timeout 300 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --output-format csv -d $O/c5/sq -- $KM > $O/c5_sq.log 2>&1
   timeout 300 rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_WAIT_ANY SQ_INSTS_VMEM_RD --output-format csv -d $O/c5/sq2 -- $KM > $O/c5_sq2.log 2>&1
   python tools/pmc_summary.py $O/c5 k_assign > $O/config_c5_pmc_summary.txt 2>&1
@@ -107,13 +107,13 @@ if has regimes; then
   prune
 fi
 if has full; then
-  timeout 600 python bench.py > $O/bench_c3_full.json 2> $O/bench_c3_full.err; cut -c1-700 $O/bench_c3_full.json
+  timeout 600 python bench.py --full > $O/bench_c3_full.json 2> $O/bench_c3_full.err; cut -c1-700 $O/bench_c3_full.json
 fi
 if has lines; then
-  timeout 200 python bench.py --config c2 > $O/bench_c2.json 2> $O/bench_c2.err
-  timeout 300 python bench.py --config c4_1gpu --steps 20 --warmup 3 --no-extras > $O/bench_c4_1gpu.json 2> $O/bench_c4.err
-  timeout 300 python bench.py --config kmeans > $O/bench_kmeans_profiled.json 2> $O/bench_kmeans.err
-  timeout 300 python bench.py --config ransac > $O/bench_ransac_profiled.json 2> $O/bench_ransac.err
-  timeout 900 python bench.py > $O/bench_c3_full.json 2> $O/bench_c3_full.err
+  timeout 200 python bench.py --full --config c2 > $O/bench_c2.json 2> $O/bench_c2.err
+  timeout 300 python bench.py --full --config c4_1gpu --steps 20 --warmup 3 --no-extras > $O/bench_c4_1gpu.json 2> $O/bench_c4.err
+  timeout 300 python bench.py --full --config kmeans > $O/bench_kmeans_profiled.json 2> $O/bench_kmeans.err
+  timeout 300 python bench.py --full --config ransac > $O/bench_ransac_profiled.json 2> $O/bench_ransac.err
+  timeout 900 python bench.py --full > $O/bench_c3_full.json 2> $O/bench_c3_full.err
   cut -c1-200 $O/bench_c3_full.json
 fi

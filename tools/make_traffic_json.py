@@ -27,7 +27,7 @@ if subs and subs[0] == "--config":
                       "launches": len(c["FETCH_SIZE"]), "source_hash": bench.source_hash(bench.KERNEL_SOURCES[config]),
                       "workload": {k: cfg.get(k) for k in (("n_points", "k") if config == "kmeans" else ("n_points",))},
                       "algorithmic_bytes_per_launch": (line.get("roofline") or {}).get("algorithmic_bytes_per_launch"),
-                      "method": f"separate rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes of `python bench.py --config {config} --no-cpu-baseline`; HBM bytes = "
+                      "method": f"separate rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes of `python bench.py --full --config {config} --no-cpu-baseline`; HBM bytes = "
                                 "2 x FETCH_SIZE + WRITE_SIZE (profiles/r02_calibration.txt)"}, indent=1))
     sys.exit(0)
 line = json.loads(open(f"{d}/bench_line.json").read()) if os.path.exists(f"{d}/bench_line.json") else {}
@@ -61,6 +61,6 @@ print(json.dumps({"traffic_bytes_per_launch": tot, "kernels": per, "cold_forms":
                   "form": form, "kernel_patterns": list(subs),
                   "workload": {"n_target": cfg.get("n_target"), "n_source_per_gpu": cfg.get("n_source_per_gpu"),
                                "metric": "p2plane" if "point-to-plane" in cfg.get("workload", "") else ("p2p" if "point-to-point" in cfg.get("workload", "") else "combined")},
-                  "method": "separate rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes of `python bench.py --steps 20 --warmup 3 --no-extras --no-cpu-baseline`; "
+                  "method": "separate rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes of `python bench.py --full --steps 20 --warmup 3 --no-extras --no-cpu-baseline`; "
                             "HBM bytes = 2 x FETCH_SIZE + WRITE_SIZE (profiles/r02_calibration.txt: FETCH_SIZE reports half of the 128-B-line bytes for every read pattern, WRITE_SIZE is exact)"},
                  indent=1))

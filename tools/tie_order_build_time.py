@@ -2,7 +2,7 @@
 """Build time of the order tables behind option "tie_rule" (csrc/tie_build.hip: the permutation and splits of the index the reference
 builds, level by level on the device) at the benchmark's sizes: (a) a context's own build from its grid (cilhip_build_tie_order:
 everything on the device), (b) through cilhip_tie_order_create (host cloud in, host tables out: + upload and download).  The
-reference's own one-thread kd-tree build of the same clouds is on the bench lines (cpu_baseline.tree_build_s: 1.8 s at 10M, 21 s at
+reference's own one-thread kd-tree build of the same clouds is on the `bench.py --full` lines (cpu_baseline.tree_build_s: 1.8 s at 10M, 21 s at
 80M); round 5 built these tables on the host's 256 cores in 0.008 / 0.27 / 2.6 s (120k / 10M / 80M).
 usage: tie_order_build_time.py [sizes, default 1.2e5,1e6,1e7,8e7]"""
 import ctypes as C
