@@ -6,6 +6,9 @@
 //                                                                                     integer atomics (order-
 //                                                                                     independent => deterministic)
 //   empty clusters :134-176, new centroids :179-181, convergence :186-188           -> host, from k*(3+1) values
+// Non-finite coordinates have no fixed-point image: they stay out of max|x| (the scale) and of the integer sums (their point still
+// counts) and set a per-cluster, per-coordinate flag (NaN / +inf / -inf) instead; the host writes what the reference's IEEE sum of that
+// cluster gives -- NaN for a NaN or both infinities, else the infinity -- into that one coordinate and leaves every other alone.
 // The assignment is VALU-bound (n*k distance evaluations, no reuse to tile): two points per lane so the
 // distance math runs on packed f32 (v_pk_*), centroids come through the scalar cache (wave-uniform index).
 // d2 is (c-x).squaredNorm() with Eigen's 3-term redux pairing d0*d0 + (d1*d1 + d2*d2), no FMA contraction,
@@ -35,6 +38,7 @@ struct KmArgs {
   uint32_t* labels;        // [n] in: previous, out: new
   long long* sums;         // [k*4] fixed-point sums x,y,z and count
   unsigned int* changed;   // [1]
+  unsigned int* nonfinite; // [k] per cluster: KM_NF_* << 3d for a member whose coordinate d is NaN / +inf / -inf (kept out of `sums`)
   double scale;            // 2^S
   int accumulate;
   cilhip::TieDev tie;      // KD only: order tables of the reference's tree over THIS iteration's centroids, by centroid index (leaf_slot null: none)
@@ -43,6 +47,19 @@ struct KmArgs {
   uint2* tie_list;         // ... and (the pruned pass) LISTED: {point, its label before the pass}, so that only they are looked at again (k_fix_ties)
   uint32_t tie_cap;        // entries the list holds (more tied points than that: the pass runs again instead)
 };
+
+constexpr unsigned int KM_NF_NAN = 1u, KM_NF_PINF = 2u, KM_NF_NINF = 4u;
+
+// one point into its cluster's sums: finite coordinates as exact fixed-point integers (LDS), the others as a flag (global: rare)
+__device__ __forceinline__ void km_accumulate(long long* lsum, unsigned int* nonfinite, uint32_t b, float px, float py, float pz, double scale) {
+  const float p[3] = {px, py, pz};
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    if (fabsf(p[d]) < INFINITY) atomicAdd((unsigned long long*)&lsum[b * 4 + d], (unsigned long long)llrint((double)p[d] * scale));
+    else atomicOr(&nonfinite[b], (p[d] != p[d] ? KM_NF_NAN : (p[d] > 0.0f ? KM_NF_PINF : KM_NF_NINF)) << (3 * d));
+  }
+  atomicAdd((unsigned long long*)&lsum[b * 4 + 3], 1ull);
+}
 
 // KD: the distance the reference's kd-tree branch compares (use_kd_tree = true, kmeans.hpp:86-94: a KDTree over the centroids,
 // nanoflann's L2 metric) -- ((dx*dx) + (dy*dy)) + (dz*dz) -- instead of the brute-force branch's Eigen squaredNorm pairing
@@ -131,16 +148,8 @@ __global__ __launch_bounds__(KM_THREADS) void k_assign_accumulate(KmArgs a) {
     a.labels[i0] = b0;
     if (two) { changed += (a.labels[i1] != b1) ? 1u : 0u; a.labels[i1] = b1; }
     if (a.accumulate) {
-      atomicAdd((unsigned long long*)&lsum[b0 * 4 + 0], (unsigned long long)llrint((double)px.x * a.scale));
-      atomicAdd((unsigned long long*)&lsum[b0 * 4 + 1], (unsigned long long)llrint((double)py.x * a.scale));
-      atomicAdd((unsigned long long*)&lsum[b0 * 4 + 2], (unsigned long long)llrint((double)pz.x * a.scale));
-      atomicAdd((unsigned long long*)&lsum[b0 * 4 + 3], 1ull);
-      if (two) {
-        atomicAdd((unsigned long long*)&lsum[b1 * 4 + 0], (unsigned long long)llrint((double)px.y * a.scale));
-        atomicAdd((unsigned long long*)&lsum[b1 * 4 + 1], (unsigned long long)llrint((double)py.y * a.scale));
-        atomicAdd((unsigned long long*)&lsum[b1 * 4 + 2], (unsigned long long)llrint((double)pz.y * a.scale));
-        atomicAdd((unsigned long long*)&lsum[b1 * 4 + 3], 1ull);
-      }
+      km_accumulate(lsum, a.nonfinite, b0, px.x, py.x, pz.x, a.scale);
+      if (two) km_accumulate(lsum, a.nonfinite, b1, px.y, py.y, pz.y, a.scale);
     }
   }
   if (changed) atomicAdd(a.changed, changed);
@@ -199,12 +208,7 @@ __global__ __launch_bounds__(KM_THREADS) void k_assign_grid(KmArgs a, KmGrid gr,
     }
     changed += (a.labels[i] != b) ? 1u : 0u;
     a.labels[i] = b;
-    if (a.accumulate) {
-      atomicAdd((unsigned long long*)&lsum[b * 4 + 0], (unsigned long long)llrint((double)px * a.scale));
-      atomicAdd((unsigned long long*)&lsum[b * 4 + 1], (unsigned long long)llrint((double)py * a.scale));
-      atomicAdd((unsigned long long*)&lsum[b * 4 + 2], (unsigned long long)llrint((double)pz * a.scale));
-      atomicAdd((unsigned long long*)&lsum[b * 4 + 3], 1ull);
-    }
+    if (a.accumulate) km_accumulate(lsum, a.nonfinite, b, px, py, pz, a.scale);
   };
   // a point its 3x3x3 block did not prove (one in seventy): the 5x5x5 block, then -- whatever that does not prove, and every point with a
   // non-finite coordinate -- all k centroids: the definition.  (Queueing these per wave and searching them 64 at a time was measured
@@ -327,7 +331,7 @@ __global__ void k_fix_ties(KmArgs a, const uint2* __restrict__ list, uint32_t co
     const float d = (dx * dx + dy * dy) + dz * dz;
     if (d < bd) { bd = d; bj = j; }
   }
-  if (!(bd < INFINITY)) return;
+  if (!(bd < INFINITY)) return;      // (a tied point has a finite distance, so finite coordinates: no flag moves with it)
   uint32_t cur = bj;
   for (uint32_t j = 0; j < a.k; ++j) {
     const float dx = a.centroids[3 * j] - px, dy = a.centroids[3 * j + 1] - py, dz = a.centroids[3 * j + 2] - pz;
@@ -406,8 +410,10 @@ __global__ void k_farthest_member(const float* __restrict__ xyz, const uint32_t*
 
 __global__ void k_maxabs_bits(const float* __restrict__ v, size_t count, unsigned int* out) {
   unsigned int m = 0;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x)
-    m = max(m, __float_as_uint(fabsf(v[i])));
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x) {
+    const unsigned int b = __float_as_uint(fabsf(v[i]));
+    if (b < 0x7F800000u) m = max(m, b);      // (finite values only: a NaN or an infinity must not set the scale)
+  }
   for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned int)__shfl_down((int)m, off, 64));
   if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
 }
@@ -440,6 +446,7 @@ struct cilhip_kmeans_shard {
   uint32_t* d_lab = nullptr;
   long long* d_sums = nullptr;
   unsigned int* d_changed = nullptr;
+  unsigned int* d_nonfinite = nullptr;   // [kpad] flags of the last assign()
   unsigned long long* d_best = nullptr;
   float4* d_cs = nullptr;
   uint32_t* d_cstart = nullptr;
@@ -472,11 +479,13 @@ struct cilhip_kmeans_shard {
     KS_CK(hipMalloc(&d_lab, (n ? n : 1) * sizeof(uint32_t)));
     KS_CK(hipMalloc(&d_sums, kpad * 4 * sizeof(long long)));
     KS_CK(hipMalloc(&d_changed, 2 * sizeof(unsigned int)));      // [0] labels changed, [1] (kd branch) tied points met without tables
+    KS_CK(hipMalloc(&d_nonfinite, kpad * sizeof(unsigned int)));
+    KS_CK(hipMemsetAsync(d_nonfinite, 0, kpad * sizeof(unsigned int), s));
     KS_CK(hipMalloc(&d_best, sizeof(unsigned long long)));
     KS_CK(hipMemsetAsync(d_lab, 0, (n ? n : 1) * sizeof(uint32_t), s));   // point_to_cluster_index_map_.resize(n): zeros (:80)
     return CILHIP_OK;
   }
-  // max |coordinate| of the shard (f32; 0 for an empty one)
+  // max finite |coordinate| of the shard (f32; 0 for an empty one)
   int maxabs(float* out) {
     KS_CK(hipSetDevice(device));
     unsigned int hmax = 0;   // max |x| as f32 bits (non-negative floats order like unsigned ints)
@@ -495,9 +504,10 @@ struct cilhip_kmeans_shard {
     KS_CK(hipMemcpyAsync(d_c, cpad.data(), 3 * kpad * sizeof(float), hipMemcpyHostToDevice, s));
     KS_CK(hipMemsetAsync(d_changed, 0, sizeof(unsigned int), s));
     KS_CK(hipMemsetAsync(d_sums, 0, kpad * 4 * sizeof(long long), s));
+    KS_CK(hipMemsetAsync(d_nonfinite, 0, kpad * sizeof(unsigned int), s));      // (a pass that runs again sets the same flags again)
     if (n) {
       const int nblocks = (int)std::min<size_t>((n / 2 + KM_THREADS - 1) / KM_THREADS + 1, 1024);
-      KmArgs a{d_xyz, d_c, (uint32_t)n, (uint32_t)kpad, d_lab, d_sums, d_changed, scale, assign_only ? 0 : 1, {nullptr, nullptr, nullptr, 0}, nullptr, nullptr, 0u};
+      KmArgs a{d_xyz, d_c, (uint32_t)n, (uint32_t)kpad, d_lab, d_sums, d_changed, d_nonfinite, scale, assign_only ? 0 : 1, {nullptr, nullptr, nullptr, 0}, nullptr, nullptr, 0u};
       // The kd branch's choice among exactly equidistant centroids needs the order tables of the tree the reference builds over THIS
       // iteration's centroids (kmeans.hpp:87) -- about a millisecond, as much as the whole pruned pass.  So the pass first runs WITHOUT
       // them and counts the points whose best distance was met on two centroids (none on data without exact ties); only then the
@@ -592,6 +602,13 @@ struct cilhip_kmeans_shard {
     KS_CK(hipStreamSynchronize(s));
     return CILHIP_OK;
   }
+  // per cluster, the non-finite coordinates the last assign() met among its members (KM_NF_* << 3d)
+  int nonfinite(uint32_t* out) {
+    KS_CK(hipSetDevice(device));
+    KS_CK(hipMemcpyAsync(out, d_nonfinite, k * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+    KS_CK(hipStreamSynchronize(s));
+    return CILHIP_OK;
+  }
   int labels(uint32_t* out) {
     KS_CK(hipSetDevice(device));
     if (n) KS_CK(hipMemcpyAsync(out, d_lab, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -607,6 +624,7 @@ struct cilhip_kmeans_shard {
     if (d_lab) (void)hipFree(d_lab);
     if (d_sums) (void)hipFree(d_sums);
     if (d_changed) (void)hipFree(d_changed);
+    if (d_nonfinite) (void)hipFree(d_nonfinite);
     if (d_best) (void)hipFree(d_best);
     if (d_cs) (void)hipFree(d_cs);
     if (d_cstart) (void)hipFree(d_cstart);
@@ -642,6 +660,7 @@ int kmeans_impl(int device, const float* xyz, size_t n, int mem, float* centroid
   int rc = CILHIP_OK;
   std::vector<long long> hs(k * 4);
   std::vector<float> c_old(3 * k);
+  std::vector<uint32_t> nf(k);
   size_t iter = 0;
   cilhip_kmeans_shard sh;
 #define KM_RC(x) do { rc = (x); if (rc != CILHIP_OK) goto done; } while (0)
@@ -657,6 +676,7 @@ int kmeans_impl(int device, const float* xyz, size_t n, int mem, float* centroid
       KM_RC(sh.assign(centroids, scale, kd_order, assign_only, hs.data(), &changed));
       if (assign_only) break;
       if (changed == 0 && iter > 0) break;                                            // kmeans.hpp:122
+      KM_RC(sh.nonfinite(nf.data()));
       if (tol > 0.0f) std::memcpy(c_old.data(), centroids, 3 * k * sizeof(float));   // :123
       // empty clusters (:134-176), processed in ascending cluster index like the reference
       for (size_t i = 0; i < k; ++i) {
@@ -674,7 +694,11 @@ int kmeans_impl(int device, const float* xyz, size_t n, int mem, float* centroid
         hs[mx * 4 + 3]--; hs[i * 4 + 3]++;   // the reference does not add the point to cluster i's sum (:171-175)
       }
       for (size_t i = 0; i < k; ++i)                                                    // :179-181
-        for (int d = 0; d < 3; ++d) centroids[3 * i + d] = (float)((double)hs[i * 4 + d] / scale / (double)hs[i * 4 + 3]);
+        for (int d = 0; d < 3; ++d) {
+          const unsigned int f = (nf[i] >> (3 * d)) & 7u;      // a non-finite member: what the reference's IEEE sum gives
+          centroids[3 * i + d] = f == 0 ? (float)((double)hs[i * 4 + d] / scale / (double)hs[i * 4 + 3])
+                                 : ((f & KM_NF_NAN) || f == (KM_NF_PINF | KM_NF_NINF)) ? NAN : (f & KM_NF_PINF) ? INFINITY : -INFINITY;
+        }
       ++iter;
       if (tol > 0.0f) {                                                                  // :186-188
         float mxs = 0.0f;
@@ -739,6 +763,7 @@ int cilhip_kmeans_shard_move_point(cilhip_kmeans_shard* h, uint64_t global_index
   if (!h || !xyz_out || global_index < h->index_offset || global_index - h->index_offset >= h->n) return CILHIP_ERR_INVALID;
   return h->move_point((uint32_t)(global_index - h->index_offset), to_cluster, xyz_out);
 }
+int cilhip_kmeans_shard_nonfinite(cilhip_kmeans_shard* h, uint32_t* flags_out) { return (h && flags_out) ? h->nonfinite(flags_out) : CILHIP_ERR_INVALID; }
 int cilhip_kmeans_shard_labels(cilhip_kmeans_shard* h, uint32_t* labels_out) { return (h && (labels_out || h->n == 0)) ? h->labels(labels_out) : CILHIP_ERR_INVALID; }
 
 int cilhip_kmeans3f(int device, const float* xyz, size_t n, int mem, float* centroids, size_t k, size_t max_iter, float tol,

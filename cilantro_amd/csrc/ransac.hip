@@ -470,6 +470,8 @@ int cilhip_plane_ransac3f(int device, const float* xyz, size_t n, int mem, const
     }
     RS_CK(hipMemcpyAsync(&hs, b.st, sizeof hs, hipMemcpyDeviceToHost, b.s));
     RS_CK(hipStreamSynchronize(b.s));
+    // an empty cloud: the reference's loop runs once -- an empty sample, no inliers, 0 >= the clamped target -- and stops (ransac_base.hpp:103-114)
+    if (n == 0 && max_iter > 0) hs.iterations = 1;
     if (n > 0 && max_iter > 0) {
       RS_CK(hipEventElapsedTime(&ms, b.e0, b.e1));
       // the reference keeps residuals / inliers of the best hypothesis; with no accepted model they are empty

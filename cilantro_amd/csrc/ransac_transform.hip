@@ -419,6 +419,8 @@ int cilhip_transform_ransac3f(int device, const float* dst_xyz, const float* src
     }
     TR_CK(hipMemcpyAsync(&hs, b.st, sizeof hs, hipMemcpyDeviceToHost, b.s));
     TR_CK(hipStreamSynchronize(b.s));
+    // no pairs: the reference's loop runs once -- an empty sample, no inliers, 0 >= the clamped target -- and stops (ransac_base.hpp:103-114)
+    if (n == 0 && max_iter > 0) hs.iterations = 1;
     if (n > 0) {
       TR_CK(hipEventElapsedTime(&ms, b.e0, b.e1));
       if (residuals_out && b.residuals) TR_CK(hipMemcpy(residuals_out, b.residuals, n * sizeof(float), hipMemcpyDeviceToHost));

@@ -8,8 +8,8 @@ KMeans (clustering/kmeans.hpp:67-194).  One Lloyd iteration has exactly one exch
                     all-reduce(sum) of 4k + 1 int64                   (RCCL; k = 1024: 32 KB)
                     kmeans.hpp:122-188 on the summed values           (host, identical on every rank)
 
-The cluster sums are exact fixed-point integers (one scale for all shards), so the summed values do not depend on how the points
-were cut: centroids, labels and the iteration count are the single-device run's bit for bit.  The empty-cluster repair (:134-176)
+The cluster sums are exact fixed-point integers (one scale for all shards; non-finite coordinates travel as per-cluster flags
+instead, HipKMeansShard.nonfinite), so the summed values do not depend on how the points were cut: centroids, labels and the iteration count are the single-device run's bit for bit.  The empty-cluster repair (:134-176)
 adds two small collectives per empty cluster (MAX of a packed key, SUM of three coordinates); it is rare.
 
 RANSAC (model_estimation/ransac_base.hpp:81-115, ransac_hyperplane_estimator.hpp:47-55): the scoring pass -- H hypotheses
@@ -77,6 +77,13 @@ class HipKMeansShard:
         self._ck(self._L.cilhip_kmeans_shard_move_point(self._h, C.c_uint64(int(global_index)), int(to_cluster), p.ctypes.data), "cilhip_kmeans_shard_move_point")
         return p
 
+    def nonfinite(self):
+        """-> uint32 [k]: per cluster, the non-finite coordinates the last assign() met among this shard's members (kept out of the
+        sums): three bits per coordinate d (<< 3d): 1 a NaN, 2 a +inf, 4 a -inf"""
+        out = np.zeros(self.k, np.uint32)
+        self._ck(self._L.cilhip_kmeans_shard_nonfinite(self._h, out.ctypes.data), "cilhip_kmeans_shard_nonfinite")
+        return out
+
     def labels(self):
         out = np.zeros(max(self.n, 1), np.uint32)
         self._ck(self._L.cilhip_kmeans_shard_labels(self._h, out.ctypes.data), "cilhip_kmeans_shard_labels")
@@ -131,8 +138,12 @@ class ShardedKMeans3f:
         it = 0
         while it < int(max_iter):
             sums, changed = eng.assign(cent, S, use_kd_tree)
-            red = self._reduce(np.concatenate([sums.reshape(-1), np.array([changed], np.int64)]), "SUM")
-            hs, changed = red[:-1].reshape(k, 4).copy(), int(red[-1])
+            nf = eng.nonfinite() if hasattr(eng, "nonfinite") else np.zeros(k, np.uint32)
+            red = self._reduce(np.concatenate([sums.reshape(-1), np.array([changed, int(nf.any())], np.int64)]), "SUM")
+            hs, changed, any_nf = red[:-2].reshape(k, 4).copy(), int(red[-2]), int(red[-1])
+            if any_nf:      # (rare, and every rank sees the same count: the flags' OR as a sum of their bits)
+                bits = self._reduce(((nf[:, None].astype(np.int64) >> np.arange(9)) & 1).reshape(-1), "SUM").reshape(k, 9)
+                nf = ((bits > 0).astype(np.int64) << np.arange(9)).sum(axis=1).astype(np.uint32)
             if changed == 0 and it > 0:                                           # kmeans.hpp:122
                 break
             c_old = cent.copy()                                                   # :123
@@ -152,6 +163,11 @@ class ShardedKMeans3f:
                 hs[i, 3] += 1                                                     # the reference does not add the point to cluster i's sum (:171-175)
             with np.errstate(divide="ignore", invalid="ignore"):
                 cent = (hs[:, :3].astype(np.float64) / scale / hs[:, 3:4].astype(np.float64)).astype(np.float32)      # :179-181
+            for j in np.nonzero(nf)[0]:      # a non-finite member: what the reference's IEEE sum of that coordinate gives
+                for d in range(3):
+                    f = (int(nf[j]) >> (3 * d)) & 7
+                    if f:
+                        cent[j, d] = np.nan if (f & 1 or f == 6) else (np.inf if f & 2 else -np.inf)
             it += 1
             if tol > 0:                                                           # :186-188
                 d = cent - c_old

@@ -330,6 +330,11 @@ int cilhip_kmeans_shard_assign(cilhip_kmeans_shard* shard, const float* centroid
                                uint64_t* changed_out);
 int cilhip_kmeans_shard_farthest(cilhip_kmeans_shard* shard, uint32_t cluster, const float center[3], uint64_t* key_out);
 int cilhip_kmeans_shard_move_point(cilhip_kmeans_shard* shard, uint64_t global_index, uint32_t to_cluster, float xyz_out[3]);
+/* Non-finite coordinates have no fixed-point image: they are left out of cilhip_kmeans_shard_maxabs and of the sums (their point still
+ * counts).  flags_out[j] names what the last cilhip_kmeans_shard_assign met among cluster j's members of THIS shard, three bits per
+ * coordinate d (<< 3d): 1 a NaN, 2 a +inf, 4 a -inf; the bitwise OR over the shards is the run's.  Coordinate d of such a cluster's
+ * centroid is what the reference's IEEE sum gives: NaN for a NaN or both infinities, else the infinity. */
+int cilhip_kmeans_shard_nonfinite(cilhip_kmeans_shard* shard, uint32_t* flags_out /* [k] */);
 int cilhip_kmeans_shard_labels(cilhip_kmeans_shard* shard, uint32_t* labels_out);
 
 /* ---- next tier: PlaneRANSACEstimator3f ----------------------------------- */

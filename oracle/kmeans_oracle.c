@@ -47,8 +47,11 @@ size_t orc_kmeans_assign_kd(const float* x, size_t n, const float* c, size_t k, 
   orc_knn_batch(t, x, n, 1, INFINITY, idx, d2, cnt);
   size_t changed = 0;
   for (size_t i = 0; i < n; ++i) {
-    if (labels[i] != idx[i]) ++changed;
-    labels[i] = idx[i];
+    /* a non-finite point has no neighbour (the reference's nn is left as it was: undefined there); here label 0, the brute-force
+     * branch's chain of strict compares from (inf, 0) -- never a negative index into the sums */
+    const int64_t bi = idx[i] < 0 ? 0 : idx[i];
+    if (labels[i] != bi) ++changed;
+    labels[i] = bi;
   }
   free(idx); free(d2); free(cnt);
   orc_kdtree_free(t);
