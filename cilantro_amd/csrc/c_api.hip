@@ -409,7 +409,7 @@ void cilhip_destroy(cilhip_ctx* c) {
   delete c;
 }
 
-const char* cilhip_last_error(const cilhip_ctx* c) { return c ? c->err.c_str() : "null context"; }
+const char* cilhip_last_error(const cilhip_ctx* c) { return c ? c->err.c_str() : cilhip::stateless_last_error(); }
 
 int cilhip_set_stream(cilhip_ctx* c, void* s) {
   if (!c) return CILHIP_ERR_INVALID;

@@ -5,8 +5,8 @@
 //       -Wl,-rpath,$PWD/cilantro_amd/lib -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib
 //   ./rigid_icp cloud.ply
 //
-// Differences from the reference example are only the ones the missing pieces force: no visualizer, no voxel
-// down-sampling (not on the ICP path), a seeded uniform jitter instead of Eigen::Random.
+// Differences from the reference example are only the ones the missing pieces force: no visualizer, a seeded uniform
+// jitter instead of Eigen::Random.
 #include <cilantro_hip/icp.hpp>
 #include <cilantro_hip/point_cloud.hpp>
 
@@ -30,6 +30,7 @@ int main(int argc, char** argv) {
   PointCloud3f dst(argv[1]), src;
   if (!dst.hasNormals()) { std::printf("Input cloud is empty or does not have normals!\n"); return 0; }
 
+  dst.gridDownsample(0.005f);                                                   // reference example :27
   // distorted and transformed version of dst (reference example :29-62)
   src = dst;
   uint64_t seed = 44;

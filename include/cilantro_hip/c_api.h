@@ -433,6 +433,31 @@ int cilhip_normals_knn3f(int device, const float* xyz, size_t n, int mem, size_t
 int cilhip_normals_radius3f(int device, const float* xyz, size_t n, int mem, float radius_sq, const float* view_point,
                             float* normals_out, float* curvature_out);
 
+/* ---- voxel-grid downsampling ---------------------------------------------------------------------------------- */
+/* PointsGridDownsampler<float,3> and its siblings with normals / colours (core/grid_downsampler.hpp:8-340 over
+ * core/grid_accumulator.hpp:76-199 and core/common_accumulators.hpp:36-256): what PointCloud3f::gridDownsample
+ * (utilities/point_cloud.hpp:247-266) runs.  One averaged row per occupied cell of a cubic grid of edge bin_size:
+ *   cell of a point: floor(p * (1.0f / bin_size)) per axis, in f32 (grid_accumulator.hpp:79, :114-123);
+ *   a bin's sums: its members in ascending input index, one f32 add at a time, starting AS the first member
+ *   (common_accumulators.hpp:45-46, :68-72) -- the reference's order with parallel = false, or on one thread;
+ *   normals: if (dot(sum, n_i) < 0) sum -= n_i; else sum += n_i (:122-131), dot = x x' + (y y' + z z') without FMA;
+ *   rows: scale = 1.0f / (float)count; scale * pointSum, scale * colorSum, normalized(scale * normalSum)
+ *   (grid_downsampler.hpp:118-126); bins with fewer than min_points_in_bin members are left out (:27, :119).
+ * bin_order: 1 = lexicographic in (cell_x, cell_y, cell_z), x most significant (the reference's parallel = true:
+ * grid_accumulator.hpp:10-39, :180-184), 0 = first appearance, i.e. ascending lowest member index (parallel = false, :186-197).
+ * A point with a non-finite coordinate belongs to no bin and is counted nowhere; non-finite normals / colours go through
+ * the arithmetic as they are.  A finite point whose cell index lies outside [-2^20, 2^20) on some axis:
+ * CILHIP_ERR_UNSUPPORTED.  bin_size not finite and positive, n >= 2^32, unknown mem / bin_order, NULL xyz with n > 0:
+ * CILHIP_ERR_INVALID -- checked before the device is opened.  n == 0: CILHIP_OK, *n_out = 0, no device needed.
+ * mem says where ALL array arguments live (inputs and outputs).  normals_or_null / rgb_or_null: optional attributes, 3 floats
+ * per point; their outputs (and counts_out_or_null, members per row) are written when both the input and the output are
+ * given.  Outputs hold `capacity` rows; *n_out = the number of rows.  All outputs NULL and capacity == 0: only *n_out is
+ * set.  capacity < *n_out: CILHIP_ERR_INVALID, *n_out set, nothing written; capacity = n always suffices.  In every error
+ * case no output array is written; cilhip_last_error(NULL) names the rule the calling thread's last call broke. */
+int cilhip_grid_downsample3f(int device, const float* xyz, const float* normals_or_null, const float* rgb_or_null, size_t n, int mem,
+                             float bin_size, size_t min_points_in_bin, int bin_order, float* xyz_out, float* normals_out, float* rgb_out,
+                             uint32_t* counts_out_or_null, size_t capacity, size_t* n_out);
+
 /* ---- introspection (bench / tests) ----------------------------------------------------------- */
 typedef struct {
   int nx, ny, nz;        /* grid dims */

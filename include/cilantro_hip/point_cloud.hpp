@@ -7,8 +7,11 @@
 // uchar in the file and floats in [0,1] in memory (point_cloud.hpp:513, :535).  Reads ascii and
 // binary_little_endian files with any scalar property types; other elements (faces ...) are skipped.
 // The clouds feed the engine as non-owning views:  ConstPointsView(cloud.points), ConstPointsView(cloud.normals).
+//   utilities/point_cloud.hpp:247-290             gridDownsample / gridDownsampled (on the device: grid_downsampler.hpp); member
+//                                                 templates as in the reference, so a program that never calls them links without the library
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 #include <cstring>
 #include <fstream>
@@ -16,6 +19,8 @@
 #include <stdexcept>
 #include <string>
 #include <vector>
+
+#include "grid_downsampler.hpp"
 
 namespace cilantro_hip {
 
@@ -32,6 +37,30 @@ public:
   bool isEmpty() const { return points.empty(); }
   bool hasNormals() const { return size() > 0 && normals.size() == points.size(); }   // point_cloud.hpp:139-141
   bool hasColors() const { return size() > 0 && colors.size() == points.size(); }
+
+  // point_cloud.hpp:247-266: the variant follows from the attributes the cloud has
+  template <typename GridPointScalarT = std::ptrdiff_t>
+  PointCloud3f& gridDownsample(float bin_size, size_t min_points_in_bin = 1, bool parallel = true) {
+    PointCloud3f res = gridDownsampled<GridPointScalarT>(bin_size, min_points_in_bin, parallel);
+    points.swap(res.points); normals.swap(res.normals); colors.swap(res.colors);
+    return *this;
+  }
+
+  // point_cloud.hpp:268-290
+  template <typename GridPointScalarT = std::ptrdiff_t>
+  PointCloud3f gridDownsampled(float bin_size, size_t min_points_in_bin = 1, bool parallel = true) const {
+    PointCloud3f res;
+    const ConstPointsView p(points), n(normals), c(colors);
+    if (hasNormals() && hasColors())
+      PointsNormalsColorsGridDownsampler3f(p, n, c, bin_size, parallel).getDownsampledPointsNormalsColors(res.points, res.normals, res.colors, min_points_in_bin);
+    else if (hasNormals())
+      PointsNormalsGridDownsampler3f(p, n, bin_size, parallel).getDownsampledPointsNormals(res.points, res.normals, min_points_in_bin);
+    else if (hasColors())
+      PointsColorsGridDownsampler3f(p, c, bin_size, parallel).getDownsampledPointsColors(res.points, res.colors, min_points_in_bin);
+    else
+      PointsGridDownsampler3f(p, bin_size, parallel).getDownsampledPoints(res.points, min_points_in_bin);
+    return res;
+  }
 
   PointCloud3f& fromPLYFile(const std::string& file_name) {
     std::ifstream f(file_name, std::ios::binary);
