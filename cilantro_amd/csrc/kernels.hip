@@ -1543,7 +1543,7 @@ __global__ __launch_bounds__(ITER_THREADS, (METRIC == IM_NONE && SEARCH) ? 4 : 1
     uint32_t i0 = beg + threadIdx.x;
     const uint32_t last = end > beg ? end - 1u : 0u;
     const bool nrm_a = TR::plane || (TR::affine && a.grid.nrm != nullptr);      // (uniform)
-    float4 sa = a.src[min(i0, last)], sb = a.src[min(i0 + ITER_THREADS, last)];
+    float4 sa = stream_ld_xyz(a.src + min(i0, last)), sb = stream_ld_xyz(a.src + min(i0 + ITER_THREADS, last));
     uint32_t pa = a.nn_pos[min(i0, last)], pb = a.nn_pos[min(i0 + ITER_THREADS, last)];
     if (!(i0 < end)) pa = NONE_U32;
     if (!(i0 + ITER_THREADS < end)) pb = NONE_U32;
@@ -1566,8 +1566,8 @@ __global__ __launch_bounds__(ITER_THREADS, (METRIC == IM_NONE && SEARCH) ? 4 : 1
         __builtin_amdgcn_sched_barrier(0);
       }
       i0 += 2 * ITER_THREADS;
-      sa = a.src[min(i0, last)]; pa = a.nn_pos[min(i0, last)];
-      sb = a.src[min(i0 + ITER_THREADS, last)]; pb = a.nn_pos[min(i0 + ITER_THREADS, last)];
+      sa = stream_ld_xyz(a.src + min(i0, last)); pa = a.nn_pos[min(i0, last)];
+      sb = stream_ld_xyz(a.src + min(i0 + ITER_THREADS, last)); pb = a.nn_pos[min(i0 + ITER_THREADS, last)];
       __builtin_amdgcn_sched_barrier(0);
       if (!(i0 < end)) pa = NONE_U32;
       if (!(i0 + ITER_THREADS < end)) pb = NONE_U32;
@@ -1587,7 +1587,7 @@ __global__ __launch_bounds__(ITER_THREADS, (METRIC == IM_NONE && SEARCH) ? 4 : 1
   // queries and the search is one cell scan.  Lanes whose bound exceeds a.warm_far_sq (or that have none) are counted:
   // the host falls back to the tiled kernels when they are many.
   uint32_t inext = beg + threadIdx.x;
-  float4 s4n = inext < end ? a.src[inext] : make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 s4n = inext < end ? stream_ld_xyz(a.src + inext) : make_float4(0.f, 0.f, 0.f, 0.f);
   uint32_t wn = (a.warm_pos && inext < end) ? a.warm_pos[inext] : NONE_U32;
   uint32_t nfar = 0, nsmall = 0;
   const MotionRef mref = {st->motion_acc, st->motion_eps};
@@ -1600,7 +1600,7 @@ __global__ __launch_bounds__(ITER_THREADS, (METRIC == IM_NONE && SEARCH) ? 4 : 1
     float value = 0.0f;
     float4 p = make_float4(0.f, 0.f, 0.f, 0.f), nvp = p, snp = p;
     inext += ITER_THREADS;
-    if (inext < end) { s4n = a.src[inext]; if (a.warm_pos) wn = a.warm_pos[inext]; }
+    if (inext < end) { s4n = stream_ld_xyz(a.src + inext); if (a.warm_pos) wn = a.warm_pos[inext]; }
     float qx, qy, qz;
     transform_point(T, s4.x, s4.y, s4.z, qx, qy, qz);
     {

@@ -37,6 +37,29 @@ __device__ __forceinline__ float d2_pinned(float qx, float qy, float qz, float p
   return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
 }
 
+// ---- one-touch streams: loads with the non-temporal policy ------------------------------------------------------------------
+// What a kernel reads once per launch out of an array larger than the caches (the warm iteration's records, the sorted source)
+// is not found there again by anybody: a line allocated for it only evicts one that could be.  stream_ld() marks such a load
+// non-temporal (the `nt` bit of global_load) -- still a load the compiler counts in its vmcnt bookkeeping, so the waits of a
+// prefetch pipeline stay where they are.  The typed vector loads are one instruction per record like the struct loads they
+// replace (dwordx4 / dwordx3; the 12-byte record is only 4-byte aligned).  stream_ld_xyz(): the first three components of a
+// 16-byte record whose fourth the caller does not use (a sorted source point without its index, a normal) -- 12 bytes, as the
+// compiler narrows the plain load of such a record.  Measured: NOTEBOOK 2026-10-17, profiles/r07_read_bw_probe.txt.
+typedef float stream_f4 __attribute__((ext_vector_type(4)));
+typedef float stream_f3 __attribute__((ext_vector_type(3), aligned(4)));
+__device__ __forceinline__ float4 stream_ld(const float4* p) {
+  const stream_f4 v = __builtin_nontemporal_load(reinterpret_cast<const stream_f4*>(p));
+  return make_float4(v.x, v.y, v.z, v.w);
+}
+__device__ __forceinline__ F3 stream_ld(const F3* p) {
+  const stream_f3 v = __builtin_nontemporal_load(reinterpret_cast<const stream_f3*>(p));
+  return F3{v.x, v.y, v.z};
+}
+__device__ __forceinline__ float4 stream_ld_xyz(const float4* p) {
+  const F3 v = stream_ld(reinterpret_cast<const F3*>(p));
+  return make_float4(v.x, v.y, v.z, 0.f);
+}
+
 // ---- margin keys (IterArgs::nn_lb, the match records' fourth component) ------------------------------------
 // A search that has PROVEN its result for a query q also knows a lower bound on the distance from q to every target point but
 // the match: the second smallest squared distance it evaluated (every point of the searched block was evaluated) and the gap

@@ -466,7 +466,8 @@ __global__ __launch_bounds__(WARM_THREADS, 4) void k_warm(IterArgs a) {
     z_to_lds(shas, qx, qy, qz, pm, SYM ? sym_normal(nm, sn) : nm);
   };
   // What a round streams in.  REC 2: the 12-byte copy of the source point and the match record {point, margin key} {normal}
-  // -- 40 B per query (28 without normals), all of it coalesced, TWO rounds in flight per wave (sets A and B; vmcnt retires in
+  // -- 40 B per query (28 without normals), all of it coalesced and non-temporal (stream_ld: a 400 MB stream re-read every
+  // iteration must not allocate in a 256 MiB cache), TWO rounds in flight per wave (sets A and B; vmcnt retires in
   // order, so the wait for A leaves B's loads flying).  REC 1: the sorted source record, the stored position and the search's
   // margin key one round, the gathers through that position (old match, its normal, its table entry) the next: a three-stage
   // pipeline with one wait per round for loads that were issued a whole round earlier.
@@ -486,15 +487,15 @@ __global__ __launch_bounds__(WARM_THREADS, 4) void k_warm(IterArgs a) {
   //  position of its loads in the in-order vmcnt queue, merged over all paths into the loop)
   auto load2 = [&](uint32_t k, F3& sv, float4& rv, F3& nv, float4& snv) {
     __builtin_amdgcn_sched_barrier(0);
-    sv = a.warm_src3[k];
+    sv = stream_ld(a.warm_src3 + k);
     __builtin_amdgcn_sched_barrier(0);
-    rv = a.warm_rec[k];
+    rv = stream_ld(a.warm_rec + k);
     __builtin_amdgcn_sched_barrier(0);
-    if (NRM) nv = a.warm_rec_n[k];
+    if (NRM) nv = stream_ld(a.warm_rec_n + k);
     __builtin_amdgcn_sched_barrier(0);
-    if (SYM) { snv = a.src_nrm[k]; __builtin_amdgcn_sched_barrier(0); }
+    if (SYM) { snv = stream_ld_xyz(a.src_nrm + k); __builtin_amdgcn_sched_barrier(0); }
   };
-  auto load1 = [&](uint32_t k, F3& sv, uint32_t& wv, float& lv, float4& snv) { const float4 t4 = a.src[k]; sv = F3{t4.x, t4.y, t4.z}; wv = a.warm_pos[k]; lv = a.nn_lb[k]; if (SYM) snv = a.src_nrm[k]; };
+  auto load1 = [&](uint32_t k, F3& sv, uint32_t& wv, float& lv, float4& snv) { const float4 t4 = stream_ld_xyz(a.src + k); sv = F3{t4.x, t4.y, t4.z}; wv = a.warm_pos[k]; lv = a.nn_lb[k]; if (SYM) snv = stream_ld_xyz(a.src_nrm + k); };
   // (every load of the streaming loop is UNCONDITIONAL, from an index clamped into the chunk / a position clamped into the
   //  target: a load under a divergent branch may or may not have been issued as far as the compiler's vmcnt bookkeeping
   //  is concerned, and the waits it then inserts drain the younger prefetches as well)
@@ -607,7 +608,11 @@ __global__ __launch_bounds__(WARM_THREADS, 4) void k_warm(IterArgs a) {
     if (lane == 0 && qlisted != 0u) atomicAdd(a.unproven_cnt + 64u + ((vb * WARM_WAVES + (uint32_t)wave) & 63u), qlisted);   // listed queries: is the form paying?
   }
   if (AFF) {
-    aff_write_row<WARM_WAVES>(raw, wave, lane, acc, a.partials + (size_t)vb * AFF_ROW);
+    // (the wave index taken afresh: the address of the wave's tile formed from the copy of the prologue would be kept alive across the
+    //  whole kernel -- at 128 registers in scratch, the one spill of these instantiations)
+    uint32_t tid_now = threadIdx.x;
+    asm volatile("" : "+v"(tid_now));
+    aff_write_row<WARM_WAVES>(raw, (int)(tid_now >> 6), lane, acc, a.partials + (size_t)vb * AFF_ROW);
     return;
   }
   double* const db = reinterpret_cast<double*>(raw + wave * FUSED_WAVE_BYTES);
@@ -682,7 +687,7 @@ void launch_warm(const IterArgs& a, int metric, int rec, int nblocks, hipStream_
 
 // the 12-byte copy of the sorted source the record-reading warm kernel streams (once per sort of a source)
 __global__ void k_copy_src3(const float4* __restrict__ src, uint32_t ns, F3* __restrict__ out) {
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < ns; i += gridDim.x * blockDim.x) { const float4 v = src[i]; out[i] = F3{v.x, v.y, v.z}; }
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < ns; i += gridDim.x * blockDim.x) { const float4 v = stream_ld_xyz(src + i); out[i] = F3{v.x, v.y, v.z}; }
 }
 __global__ void k_interleave_pn(const float4* __restrict__ pts, const float4* __restrict__ nrm, uint32_t n, float4* __restrict__ pn) {
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) { pn[2 * (size_t)i] = pts[i]; pn[2 * (size_t)i + 1] = nrm[i]; }
