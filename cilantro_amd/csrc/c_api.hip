@@ -1,267 +1,34 @@
-// c_api.hip -- the C ABI of libcilantro_hip.so (declared in include/cilantro_hip/c_api.h).
+// c_api.hip -- the C ABI of libcilantro_hip.so (declared in include/cilantro_hip/c_api.h), but for the ICP loop drivers (icp_loop.hip).
 // Host-side orchestration only: owns device buffers + stream, enqueues the kernels of kernels.hip /
 // grid_build.hip.  No CPU compute fallback exists: without a usable HIP device every call fails.
-#include "../../include/cilantro_hip/c_api.h"
-
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
-#include <atomic>
 #include <chrono>
-#include <condition_variable>
-#include <mutex>
 #include <cmath>
 #include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <new>
-#include <string>
-#include <thread>
-#include <vector>
 
-#include "internal.hpp"
+#include "ctx.hpp"
 
-using namespace cilhip;
-
-// Device allocations of a target that SEVERAL contexts use (cilhip_share_target): freed when the last of them lets go.
-struct TargetShare { int refs = 0; std::vector<void*> allocs; };
-
-struct cilhip_ctx {
-  int device = 0;
-  TargetShare* tshare = nullptr;  // non-null: some of this context's target pointers belong to a share (target_ptr_free / release_target_share)
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;
-  std::string err;
-
-  // target
-  bool has_target = false;
-  GridDev grid{};
-  bool has_normals = false;
-  double grid_occ = 0.0;
-  size_t grid_cells = 0;
-  double build_ms = 0.0;
-  float dst_mean[3] = {0, 0, 0};
-  uint32_t index_offset = 0;      // global index of this shard's first target point (target-sharded runs)
-  bool partial_target = false;    // this context holds only PART of the cloud the reference would index (an index shard, a spatial slab: cilhip_set_shard_info
-                                  // with an offset or the whole cloud's mean): the order tables are the WHOLE cloud's -- loaded (cilhip_load_tie_order), never built here
-  uint32_t* d_inv_perm = nullptr; // [n_target] original local index -> sorted position (built on first use)
-
-  // source
-  bool has_source = false;
-  uint32_t ns = 0;
-  float* d_src_xyz = nullptr;     // original order (kept for re-sorting)
-  float4* d_src_sorted = nullptr; // sorted cube-major by target-grid cell under sort_T
-  SortWorkspace sort_ws;          // scratch + tile table of sort_source, kept between the sorts of a source (d_tiles / d_tile_center point into it)
-  uint32_t tile_aux_cap = 0;      // tiles d_tile_box / d_defer_mask are sized for
-  uint2* d_tiles = nullptr;       // [ntiles] query ranges of the LDS-tiled search kernel
-  float4* d_tile_center = nullptr;  // [ntiles] cube centre of each tile in source space
-  int* d_tile_box = nullptr;        // [8*ntiles] cell range of each tile's cube under the current transform (recomputed per search)
-  float tile_axes[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long* d_defer_mask = nullptr;  // [ntiles * 32] queries the tiles hand to the clean-up pass (bit masks, rewritten by every search)
-  uint32_t* d_defer_flag = nullptr;            // [1] "some tile deferred a query" (reset before, set by, every tiled search)
-  uint32_t* d_unproven = nullptr;              // [128] queries the tiles' first stage did not prove / the warm-started kernel listed (summed / zeroed by the epilogue)
-  bool warm_banned = false;                    // the warm-started form was seen not to pay on this cloud pair (too few queries settled by the table)
-  Feedback* h_feedback = nullptr;              // pinned, host-coherent: what the epilogue kernel publishes after every iteration (pacing, kernel form)
-  Feedback* d_feedback = nullptr;              // the device's address of it
-  unsigned int run_tag = 0;
-  bool far_mode = true;                        // tiled ICP loop: the source is far from alignment (many unproven octant searches): search and
-                                               // accumulate in two passes (the search's 3x3x3 pass settles them in LDS) instead of one
-  int last_fused_iters = 0, last_two_pass_iters = 0, last_warm_iters = 0;
-  int run_calls = 0;              // cilhip_icp_partial_sums calls since cilhip_icp_begin
-  bool run_warm_on = false;       // sharded runs: the loop has been seen to (nearly) stand still
-  unsigned int run_judged = 0;    // ... and the last published iteration whose count of searched queries has been judged
-  std::vector<unsigned char> iter_form;   // form of every timed search / one-pass launch of the last run (FORM_*), in launch order
-  std::vector<unsigned char> trace_form;  // form of every iteration enqueued by the last run, timed or not (cilhip_get_last_run_trace)
-  double form_ms[5] = {0, 0, 0, 0, 0};    // ... and the kernel time summed per form
-  int form_n[5] = {0, 0, 0, 0, 0};
-  int warm_start = 1;             // option "warm_start": 0 = never, 1 = when the device reports the source near alignment, 2 = from the second iteration on
-  uint32_t* d_dbg = nullptr;                   // [2] cilhip_debug_counters scratch
-  uint4* d_trace = nullptr;                    // [RUN_TRACE_CAP] per-iteration loop state of the last run, written by the epilogue (cilhip_get_last_run_trace)
-  uint32_t ntiles = 0;
-                                  // (round 3 experiment, exact, measured 17 % slower than two workgroups per CU: off)
-  int tiled = 1;                  // 0: per-lane global-memory search; 1: LDS-tiled search when the cloud is large enough; 2: always tiled
-  bool src_sorted = false;
-  float sort_T[16];
-  float src_mean[3] = {0, 0, 0};
-  float* d_src_nrm = nullptr;         // optional source normals, original order (4-cloud ctor => symmetric metric)
-  float4* d_src_nrm_sorted = nullptr;
-  uint32_t* d_nn_pos = nullptr;
-  float* d_nn_d2 = nullptr;
-  float4* d_warm_rec = nullptr;   // [ns] float4 + 2 x [ns] F3: match records {matched point, margin key} {normal} and the 12-byte source copy of the warm-started iterations
-  bool rec_valid = false;         // the records describe the last executed iteration's matches (inside a run)
-  bool src3_valid = false;        // the 12-byte source copy matches d_src_sorted (rewritten after a re-sort)
-  float* d_nn_lb = nullptr;       // [ns] margin keys the search-only tile kernel leaves next to nn_pos (IterArgs::nn_lb)
-  bool lb_fresh = false;          // ... and they belong to the search that left nn_pos (inside a run)
-  bool warm_forecast = true;      // option "warm_forecast": the cold kernels' count of the queries a warm-started iteration would have to search gates the form
-  // option "tie_rule": which of several EXACTLY equidistant nearest target points a correspondence names.  0 = the lowest target index;
-  // 1 = the one the reference's kd-tree traversal meets first, order tables built before the first search; 2 (default) = the same
-  // choice, the tables built when a search first MEETS a tie (that search / run is then executed again): a target that never ties never
-  // pays for a tree.  The device resolves ties inside its search kernels (TieDev, kernels.hip: tie_settle).
-  int tie_rule = 2;
-  uint2* d_tief_leaf_slot = nullptr;             // [grid.n] the order tables of the FEATURE tree (6-D / 9-D adaptors: points + weighted normals / colours), for the
-  uint4* d_tief_nodes = nullptr;                 // feature options they were built under (dropped with any of them); TieNode::info with four dimension bits
-  int tief_builds = 0;
-  uint2* d_tie_leaf_slot = nullptr;              // [grid.n] the order tables by sorted target position (null: not loaded)
-  uint4* d_tie_nodes = nullptr;
-  unsigned int* d_tie_counters = nullptr;        // [4] TieDev::counters
-  unsigned int* d_ticket = nullptr;              // [1] k_reduce_solve's ticket (zero between launches)
-  // option "group_search": the global-memory search with SEVERAL lanes per query (k_search_group: small clouds and sources far from
-  // alignment, where one lane per query leaves the chip idle behind chains of dependent trips).  -1 (default) = the ICP loop decides per
-  // iteration (cold iterations of clouds the tiles do not take: always for clouds below the warm-started form's floor, from the
-  // kernels' own forecast above it); 0 = never; 4 .. 64 = that many lanes in every global-memory search.
-  int group_lanes = -1;
-  double wait_us = 0.0;                          // time spent waiting for the device to publish loop state (wait_published), accumulated: not enqueue work
-  bool feat_warm = true;                         // option "feature_warm_start": the feature adaptors' forward search warm-started from the previous matches once the loop moves little (feat_warm.hip)
-  bool affine_device_loop = true;                // option "affine_device_loop": the affine classes' loop device-resident (one-pass moments on the matrix cores, 12-unknown
-                                                 // solve in the epilogue kernel) whenever nothing needs the stored set per iteration; 0 = the host-driven loop (A/B)
-  bool fused_epilogue = false;                   // option "fused_epilogue": stage-1 reduction + epilogue in ONE launch (the last of the 32 stage-1 blocks runs the
-                                                 // epilogue).  Bitwise the same results, measured SLOWER: 0.129 -> 0.136 ms per iteration at 10M, 0.037 -> 0.044 at 1M --
-                                                 // a device-scope fence costs more on this eight-L2 part than the kernel boundary it removes (NOTEBOOK.md): off
-  unsigned int tie_counters_host[4] = {0, 0, 0, 0};      // ... as read together with the loop state at the end of a run (read_state: one synchronisation for both)
-  bool tie_counters_fresh = false;
-  double tie_build_ms = 0.0;                     // host time of the last table build (tree + upload)
-  int tie_builds = 0;                            // table builds on this context (diagnostics)
-  // the reverse matches of FIRST_TO_SECOND / BOTH: the reference's tree is over the TRANSFORMED source, a new one per search -- once a
-  // reverse search has met exactly equidistant source points (or under tie_rule 1) that tree's order tables are built (on the device) before
-  // every reverse search (the loops then run host-driven, one search at a time)
-  bool rev_tie_aware = false;
-  uint2* d_rev_tie_leaf_slot = nullptr;          // [ns] by position in the source grid; valid for rev_tie_T only
-  uint4* d_rev_tie_nodes = nullptr;
-  size_t rev_tie_nodes_cap = 0;
-  bool rev_tie_valid = false;
-  float rev_tie_T[16];
-  int rev_tie_builds = 0;
-  float warm_extra = 0.0625f;     // option "warm_extra_fraction"
-  bool pair_records = true;       // option "pair_records": the streaming accumulation gathers a match's point and normal from one 32-byte record (GridDev::pn)
-  void* rank_comm = nullptr; int rank_comm_size = 0; double* d_rank_sums = nullptr;      // cilhip_rank_comm_*: this process' rank in an RCCL communicator
-  bool tile_records = true;       // option "tile_records": the accumulating tile kernel writes the warm-started form's match records itself
-  float warm_enter = 0.15f;       // option "warm_enter_fraction": the bar a run starts with, as a fraction of a grid cell
-  float warm_thresh = 0.0f;       // a run's bar for (re-)entering the warm-started form: the last update moved no source point by more than this
-  int warm_strikes = 0;           // warm iterations of the run that had to search a quarter of their queries
-  float src_center[3] = {0, 0, 0}, src_half[3] = {0, 0, 0};   // bounding box of the source (source coordinates): the epilogue's bound on how far a query moves per update
-  float* d_safe2 = nullptr;       // [grid.n] k_self_nn's table for the warm-started iteration; built with the target
-  int cw_point_kind = 0, cw_plane_kind = 0;     // correspondence weight evaluators (CW_*), combined metric
-  float cw_point_sigma = 1.0f, cw_plane_sigma = 1.0f;
-  cilhip_pair_weight_fn weight_fn = nullptr;    // a caller's own evaluators (cilhip_set_pair_weight_callback): the estimates call them on the host
-  void* weight_user = nullptr;
-  float* d_wtab = nullptr;        // [2 * wtab_cap] point / plane weights by stream position (CorrWeights::point_table / plane_table)
-  float* d_wtab_in = nullptr;     // [2 * wtab_cap] ... by original source index, as the host filled them
-  size_t wtab_cap = 0;
-  bool have_nn = false;           // nn_pos/nn_d2 hold the result of a search
-  bool d2_stale = false;          // ... but nn_d2 has not been formed yet (matches left by a loop whose kernels keep no distances: ensure_d2)
-  float nn_T[16];                 // transform used by that search
-  // after cilhip_icp_run the engine's correspondence set is the last executed iteration's (correspondence_search_kd_tree.hpp:231 through
-  // icp_base.hpp:32-38): either the loop's kernels left it in nn_pos (have_nn, origin 1) or it is searched again on demand under
-  // nn_T = the transform that iteration searched under (pending_matches, origin 2) -- the search is exact, so it is the same set
-  bool pending_matches = false;
-  float pending_max_sq = 0.0f;
-  int matches_origin = 0;         // cilhip_get_last_matches_origin
-
-  // loop state / scratch
-  IcpState* d_state = nullptr;
-  double* d_partials = nullptr;
-  int partial_blocks = 0;
-  double* d_stage = nullptr;      // [REDUCE_STAGE_DOUBLES] stage-1 rows of the cross-block reduction
-  double* d_sums = nullptr;       // [3 * SUMS_MAX] (the affine estimator reduces three passes before one copy to the host)
-  bool tile_acc_adaptive = true;  // choose one pass / two passes per iteration from the device's feedback (option "tile_accumulation" = 2: always one pass)
-  bool tile_acc = true;           // accumulate inside the LDS tiles of the search when the engine allows it (option "tile_accumulation", A/B)
-  bool fused = false;             // true: search+accumulate in one kernel; false: search kernel + streaming accumulate kernel (faster: the search runs at 2x the occupancy)
-  double cell_occupancy = 1.0;    // target points per grid cell (takes effect at the next set_target)
-  double refined_occupancy = 3.0; // option "refined_occupancy_factor": how much denser than that a REFINED grid (surface-like / clustered target) may stay
-  unsigned long long* d_count = nullptr;
-  uint32_t* d_out_idx = nullptr;  // [ns] original-order results
-  float* d_out_d2 = nullptr;
-
-  // engine post-filters (correspondence_search_kd_tree.hpp:224-225)
-  double inlier_fraction = 1.0;
-  bool one_to_one = false;
-  unsigned long long* d_keys = nullptr;    // [ns]
-  unsigned long long* d_own_order = nullptr;   // [ns] this shard's traversal keys of the current iteration (cilhip_icp_order_keys)
-  int tie_max_depth = 0;                   // depth of the loaded order tree (the traversal keys hold 58 levels)
-  void* d_sel_state = nullptr;
-  unsigned long long* d_winner = nullptr;  // [n_target]
-
-  // other search directions (correspondence_search_kd_tree.hpp:185-222): the correspondence set is a pair list
-  int search_dir = 0;             // 0 = SECOND_TO_FIRST (default), 1 = FIRST_TO_SECOND, 2 = BOTH
-  bool reciprocal = false;        // require_reciprocality_ (BOTH only)
-  int transform_mode = 0;         // 0 = rigid (Isometry), 1 = affine: which ICP instance family cilhip_icp_run mirrors
-  float normal_weight = 0.0f;     // > 0: the correspondence search runs on 6-D features (point, weight * v)
-  int feature_kind = 0;           // option "feature_kind": 0 = v = normals, following the transform (PointNormalFeaturesAdaptor);
-                                  // 1 = v = colours, untouched by it (PointColorFeaturesAdaptor; cilhip_set_color_features)
-  float *d_dst_rgb = nullptr, *d_src_rgb = nullptr;             // colour features, original order
-  float4 *d_dst_rgb_sorted = nullptr, *d_src_rgb_sorted = nullptr;
-  float4* d_src_rgb_grid = nullptr;      // the source's colours in the order of the source's own grid (9-D reverse search)
-  float color_weight = 0.0f;             // option "feature_color_weight" (feature_kind 2: the 9-D adaptor's colour weight)
-  bool dst_rgb_sorted_ok = false;
-  float src_nrm0[3] = {0, 0, 0};  // the first source normal (the affine feature adaptor's normal weight is |w n_0|, adaptors.hpp:113-114)
-  float feat_M[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};              // L^-T of the transform being searched under (affine adaptor)
-  bool symmetric = true;          // source normals, when set, also switch the combined metric to the symmetric objective
-  PairSet pairs;
-  GridDev src_grid{};             // grid over the source in SOURCE coordinates (built on the first FIRST_TO_SECOND / BOTH search of a source)
-  bool has_src_grid = false;
-  float* d_src_safe2 = nullptr;   // [ns] k_self_nn's table over the SOURCE grid: the margin test of the warm-started reverse search (k_reverse_warm)
-  bool reverse_warm = true;       // option "reverse_warm_start": the device-resident FIRST_TO_SECOND / BOTH loops start every reverse search but the first from the previous matches
-  uint32_t* d_grid_to_sorted = nullptr;   // [ns] source-grid position -> sorted source position (d_src_inv through the source grid's order): the fused reverse pass's duplicate test
-  uint32_t *d_rev_pos = nullptr, *d_src_inv = nullptr;   // list-free loops of those directions: reverse matches by target position; original -> sorted source position
-  float* d_rev_d2 = nullptr;
-  bool have_pairs = false;        // `pairs` holds the result of the last find_correspondences
-  IcpState* d_state_id = nullptr; // a state holding the identity transform (the reverse search transforms nothing)
-
-  // sharded-run state
-  cilhip_icp_params run_prm{};
-  bool run_active = false;
-  int guard_axis = -1;            // slab-sharded runs: see SolveArgs::guard_*
-  float guard_slack = 0.0f, guard_center[3] = {0, 0, 0}, guard_half[3] = {0, 0, 0}, guard_T[16] = {0};
-  float run_src_mean[3] = {0, 0, 0};
-
-  // timing
-  bool kernel_timing = false;
-  int timing_stride = 1;          // option "kernel_timing_stride": with kernel timing on, iterations 0..2 and every stride-th one carry events
-  std::vector<unsigned int> timed_iter;      // the iterations of the last run that did
-  std::vector<float> timed_ms;               // ... and the kernel time of each (cilhip_get_last_iteration_timing)
-  double last_loop_ms = 0.0, last_search_ms = 0.0, last_acc_ms = 0.0;
-  int last_search_launches = 0;
-  size_t run_nev = 0;             // sharded runs: hipEvents recorded by cilhip_icp_partial_sums since cilhip_icp_begin (3 per call)
-  std::vector<hipEvent_t> ev, ev_acc;
-  std::vector<hipEvent_t> ev_ar;  // ranked loop: event pairs around the sampled all-reduces since cilhip_icp_begin (cilhip_get_last_allreduce_timing)
-  size_t run_nar = 0;             // ... how many of them are recorded
-  double last_allreduce_ms = 0.0; int last_allreduce_n = 0;
-  double run_enqueue_us = 0.0; int run_enqueue_iters = 0;      // ranked loop: host time of its enqueue calls (the paced waits for the device's feedback word excluded)
-
-};
-
-#define CK(ctx, call)                                                                                   \
-  do {                                                                                                  \
-    hipError_t e_ = (call);                                                                             \
-    if (e_ != hipSuccess) {                                                                             \
-      (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                                   \
-      return CILHIP_ERR_HIP;                                                                            \
-    }                                                                                                   \
-  } while (0)
-
-static int fail(cilhip_ctx* c, int code, const char* msg) {
-  if (c) c->err = msg;
-  return code;
-}
-
-static const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
 // (multi.hip -- the C entry of the multi-device loops -- drives contexts through the public entry points; these two are all it reads of one)
 namespace cilhip {
 hipStream_t ctx_stream(const cilhip_ctx* c) { return c->stream; }
 double ctx_wait_us(const cilhip_ctx* c) { return c->wait_us; }
 }  // namespace cilhip
 
-// the stored correspondence set (matches or pair list) no longer describes anything a caller may read
+template <class T> static void dev_free(T*& p) {
+  if (p) { (void)hipFree(p); p = nullptr; }
+}
 static void drop_src_grid(cilhip_ctx* c) {
   if (c->has_src_grid) { free_grid(c->src_grid); c->has_src_grid = false; }
-  if (c->d_src_safe2) { (void)hipFree(c->d_src_safe2); c->d_src_safe2 = nullptr; }
-  if (c->d_grid_to_sorted) { (void)hipFree(c->d_grid_to_sorted); c->d_grid_to_sorted = nullptr; }
-  if (c->d_src_rgb_grid) { (void)hipFree(c->d_src_rgb_grid); c->d_src_rgb_grid = nullptr; }
+  dev_free(c->d_src_safe2);
+  dev_free(c->d_grid_to_sorted);
+  dev_free(c->d_src_rgb_grid);
 }
-static void drop_matches(cilhip_ctx* c) { c->have_nn = false; c->d2_stale = false; c->pending_matches = false; c->matches_origin = 0; }
 static void drop_rev_tie_tables(cilhip_ctx* c) {  // (they describe ONE source under ONE transform)
-  if (c->d_rev_tie_leaf_slot) { (void)hipFree(c->d_rev_tie_leaf_slot); c->d_rev_tie_leaf_slot = nullptr; }
-  if (c->d_rev_tie_nodes) { (void)hipFree(c->d_rev_tie_nodes); c->d_rev_tie_nodes = nullptr; }
+  dev_free(c->d_rev_tie_leaf_slot);
+  dev_free(c->d_rev_tie_nodes);
   c->rev_tie_nodes_cap = 0; c->rev_tie_valid = false; c->rev_tie_aware = false;
 }
 // a target-side allocation of this context: freed here unless it belongs to a share (then by whoever lets go of the share last)
@@ -279,8 +46,8 @@ static void release_target_share(cilhip_ctx* c) {
   c->tshare = nullptr;
 }
 static void drop_feat_tie_tables(cilhip_ctx* c) {      // (one target under one set of feature options; never shared)
-  if (c->d_tief_leaf_slot) { (void)hipFree(c->d_tief_leaf_slot); c->d_tief_leaf_slot = nullptr; }
-  if (c->d_tief_nodes) { (void)hipFree(c->d_tief_nodes); c->d_tief_nodes = nullptr; }
+  dev_free(c->d_tief_leaf_slot);
+  dev_free(c->d_tief_nodes);
 }
 static void drop_tie_tables(cilhip_ctx* c) {      // (they describe ONE target)
   target_ptr_free(c, c->d_tie_leaf_slot); c->d_tie_leaf_slot = nullptr;
@@ -300,7 +67,7 @@ static void release_target(cilhip_ctx* c) {
   release_target_share(c);
 }
 
-extern "C" {
+// (the entry points take their C linkage from their declarations in c_api.h)
 
 int cilhip_create(cilhip_ctx** out, int device) {
   if (!out) return CILHIP_ERR_INVALID;
@@ -329,48 +96,29 @@ int cilhip_create(cilhip_ctx** out, int device) {
   }
   if (hipMemset(c->d_state, 0, sizeof(IcpState)) != hipSuccess) { delete c; return CILHIP_ERR_HIP; }
   c->d_tie_counters = reinterpret_cast<unsigned int*>(reinterpret_cast<char*>(c->d_state) + offsetof(IcpState, tie_counters));      // (read with the state: read_state)
-  memcpy(c->sort_T, kIdentity, sizeof(kIdentity));
-  memcpy(c->nn_T, kIdentity, sizeof(kIdentity));
+  memcpy(c->sort_T, kIdentity16, sizeof(kIdentity16));
+  memcpy(c->nn_T, kIdentity16, sizeof(kIdentity16));
   *out = c;
   return CILHIP_OK;
 }
 
 static void free_source(cilhip_ctx* c) {
   drop_rev_tie_tables(c);
-  if (c->d_src_xyz) (void)hipFree(c->d_src_xyz);
-  if (c->d_src_sorted) (void)hipFree(c->d_src_sorted);
-  if (c->d_nn_pos) (void)hipFree(c->d_nn_pos);
-  if (c->d_nn_d2) (void)hipFree(c->d_nn_d2);
-  if (c->d_warm_rec) { (void)hipFree(c->d_warm_rec); c->d_warm_rec = nullptr; }
-  if (c->d_nn_lb) { (void)hipFree(c->d_nn_lb); c->d_nn_lb = nullptr; }
-  c->src3_valid = false; c->lb_fresh = false;
-  c->rec_valid = false;
-  if (c->d_out_idx) (void)hipFree(c->d_out_idx);
-  if (c->d_out_d2) (void)hipFree(c->d_out_d2);
+  dev_free(c->d_src_xyz); dev_free(c->d_src_sorted); dev_free(c->d_nn_pos); dev_free(c->d_nn_d2);
+  dev_free(c->d_warm_rec); dev_free(c->d_nn_lb);
+  c->src3_valid = false; c->lb_fresh = false; c->rec_valid = false;
+  dev_free(c->d_out_idx); dev_free(c->d_out_d2);
   free_sort_workspace(c->sort_ws);      // (owns d_tiles / d_tile_center)
-  c->tile_aux_cap = 0;
-  if (c->d_tile_box) (void)hipFree(c->d_tile_box);
-  if (c->d_src_nrm) (void)hipFree(c->d_src_nrm);
-  if (c->d_src_nrm_sorted) (void)hipFree(c->d_src_nrm_sorted);
-  c->d_src_nrm = nullptr; c->d_src_nrm_sorted = nullptr;
-  if (c->d_src_rgb) (void)hipFree(c->d_src_rgb);
-  if (c->d_src_rgb_sorted) (void)hipFree(c->d_src_rgb_sorted);
-  c->d_src_rgb = nullptr; c->d_src_rgb_sorted = nullptr;
-  if (c->d_defer_mask) (void)hipFree(c->d_defer_mask);
-  if (c->d_keys) (void)hipFree(c->d_keys);
-  c->d_keys = nullptr;
-  if (c->d_own_order) (void)hipFree(c->d_own_order);
-  c->d_own_order = nullptr;
-  c->d_tiles = nullptr; c->d_tile_center = nullptr; c->d_tile_box = nullptr; c->ntiles = 0; c->d_defer_mask = nullptr;
-  c->d_src_xyz = nullptr; c->d_src_sorted = nullptr; c->d_nn_pos = nullptr; c->d_nn_d2 = nullptr;
-  c->d_out_idx = nullptr; c->d_out_d2 = nullptr;
+  c->d_tiles = nullptr; c->d_tile_center = nullptr; c->ntiles = 0; c->tile_aux_cap = 0;
+  dev_free(c->d_tile_box); dev_free(c->d_defer_mask);
+  dev_free(c->d_src_nrm); dev_free(c->d_src_nrm_sorted); dev_free(c->d_src_rgb); dev_free(c->d_src_rgb_sorted);
+  dev_free(c->d_keys); dev_free(c->d_own_order);
   drop_src_grid(c);
-  if (c->d_src_inv) { (void)hipFree(c->d_src_inv); c->d_src_inv = nullptr; }
-  if (c->d_grid_to_sorted) { (void)hipFree(c->d_grid_to_sorted); c->d_grid_to_sorted = nullptr; }
+  dev_free(c->d_src_inv); dev_free(c->d_grid_to_sorted);
   c->has_source = false; c->src_sorted = false; drop_matches(c); c->ns = 0;
   c->have_pairs = false; c->pairs.count = 0;   // a pair list refers to the source / target it was found on
-  c->far_mode = true;
-  c->warm_banned = false;
+  c->policy.far_mode = true;
+  c->policy.warm_banned = false;
 }
 
 void cilhip_destroy(cilhip_ctx* c) {
@@ -380,27 +128,12 @@ void cilhip_destroy(cilhip_ctx* c) {
   (void)cilhip_rank_comm_destroy(c);
   free_source(c);
   release_target(c);
-  if (c->d_ticket) (void)hipFree(c->d_ticket);
-  if (c->d_wtab) (void)hipFree(c->d_wtab);
-  if (c->d_wtab_in) (void)hipFree(c->d_wtab_in);
-  if (c->d_dst_rgb) (void)hipFree(c->d_dst_rgb);
-  if (c->d_dst_rgb_sorted) (void)hipFree(c->d_dst_rgb_sorted);
-  if (c->d_state) (void)hipFree(c->d_state);
-  if (c->d_state_id) (void)hipFree(c->d_state_id);
   free_pairs(c->pairs);
-  if (c->d_partials) (void)hipFree(c->d_partials);
-  if (c->d_sel_state) (void)hipFree(c->d_sel_state);
-  if (c->d_winner) (void)hipFree(c->d_winner);
-  if (c->d_count) (void)hipFree(c->d_count);
-  if (c->d_dbg) (void)hipFree(c->d_dbg);
-  if (c->d_trace) (void)hipFree(c->d_trace);
-  if (c->d_defer_flag) (void)hipFree(c->d_defer_flag);
-  if (c->d_unproven) (void)hipFree(c->d_unproven);
-  if (c->d_rev_pos) (void)hipFree(c->d_rev_pos);
-  if (c->d_rev_d2) (void)hipFree(c->d_rev_d2);
+  dev_free(c->d_ticket); dev_free(c->d_wtab); dev_free(c->d_wtab_in); dev_free(c->d_dst_rgb); dev_free(c->d_dst_rgb_sorted);
+  dev_free(c->d_state); dev_free(c->d_state_id); dev_free(c->d_partials); dev_free(c->d_sel_state); dev_free(c->d_winner);
+  dev_free(c->d_count); dev_free(c->d_dbg); dev_free(c->d_trace); dev_free(c->d_defer_flag); dev_free(c->d_unproven);
+  dev_free(c->d_rev_pos); dev_free(c->d_rev_d2); dev_free(c->d_stage); dev_free(c->d_sums);
   if (c->h_feedback) (void)hipHostFree(c->h_feedback);
-  if (c->d_stage) (void)hipFree(c->d_stage);
-  if (c->d_sums) (void)hipFree(c->d_sums);
   for (auto e : c->ev) (void)hipEventDestroy(e);
   for (auto e : c->ev_acc) (void)hipEventDestroy(e);
   for (auto e : c->ev_ar) (void)hipEventDestroy(e);
@@ -639,7 +372,7 @@ int cilhip_get_last_run_trace(cilhip_ctx* c, int cap, int* n_out, unsigned int* 
     if (listed) listed[i] = tr[i].y;
     if (step) memcpy(&step[i], &tr[i].z, 4);
     if (delta) memcpy(&delta[i], &tr[i].w, 4);
-    if (form) form[i] = (size_t)i < c->trace_form.size() ? (int)(c->trace_form[i] & 0x7f) : -1;
+    if (form) form[i] = (size_t)i < c->trace_form.size() ? (int)(c->trace_form[i] & FORM_MASK) : -1;
   }
   *n_out = n;
   return CILHIP_OK;
@@ -678,9 +411,7 @@ int cilhip_set_target(cilhip_ctx* c, const float* xyz, const float* nrm, size_t 
   CK(c, hipSetDevice(c->device));
   auto t0 = std::chrono::steady_clock::now();
   release_target(c);      // (incl. the order tables, the nearest-other-point table: they describe ONE target; a shared target is only let go of)
-  if (c->d_winner) { (void)hipFree(c->d_winner); c->d_winner = nullptr; }
-  if (c->d_rev_pos) { (void)hipFree(c->d_rev_pos); c->d_rev_pos = nullptr; }
-  if (c->d_rev_d2) { (void)hipFree(c->d_rev_d2); c->d_rev_d2 = nullptr; }
+  dev_free(c->d_winner); dev_free(c->d_rev_pos); dev_free(c->d_rev_d2);
   float *d_xyz = nullptr, *d_nrm = nullptr;
   int rc = upload(c, xyz, 3 * n, mem, &d_xyz);
   if (rc) return rc;
@@ -692,10 +423,9 @@ int cilhip_set_target(cilhip_ctx* c, const float* xyz, const float* nrm, size_t 
   if (d_nrm) (void)hipFree(d_nrm);
   if (e != hipSuccess) { c->err = std::string("build_grid: ") + hipGetErrorString(e); return CILHIP_ERR_HIP; }
   c->grid = r.grid; c->grid_occ = r.avg_occupancy; c->grid_cells = r.n_cells;
-  c->warm_banned = false;
+  c->policy.warm_banned = false;
   c->dst_rgb_sorted_ok = false;
-  if (c->d_dst_rgb) { (void)hipFree(c->d_dst_rgb); c->d_dst_rgb = nullptr; }      // (colours belong to the target they were set for)
-  if (c->d_dst_rgb_sorted) { (void)hipFree(c->d_dst_rgb_sorted); c->d_dst_rgb_sorted = nullptr; }
+  dev_free(c->d_dst_rgb); dev_free(c->d_dst_rgb_sorted);      // (colours belong to the target they were set for)
   c->has_normals = (nrm != nullptr);
   for (int i = 0; i < 3; ++i) c->dst_mean[i] = (float)mean[i];
   c->partial_target = false;      // (a new target stands for itself until cilhip_set_shard_info says otherwise)
@@ -703,7 +433,7 @@ int cilhip_set_target(cilhip_ctx* c, const float* xyz, const float* nrm, size_t 
   c->src_sorted = false;  // source order is tied to the target grid
   drop_matches(c);
   c->have_pairs = false; c->pairs.count = 0;
-  c->far_mode = true;
+  c->policy.far_mode = true;
   c->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return CILHIP_OK;
 }
@@ -722,11 +452,8 @@ int cilhip_share_target(cilhip_ctx* c, cilhip_ctx* from) {
   CK(c, hipStreamSynchronize(from->stream));      // (whatever is still building the lender's tables)
   CK(c, hipStreamSynchronize(c->stream));
   release_target(c);
-  if (c->d_winner) { (void)hipFree(c->d_winner); c->d_winner = nullptr; }
-  if (c->d_rev_pos) { (void)hipFree(c->d_rev_pos); c->d_rev_pos = nullptr; }
-  if (c->d_rev_d2) { (void)hipFree(c->d_rev_d2); c->d_rev_d2 = nullptr; }
-  if (c->d_dst_rgb) { (void)hipFree(c->d_dst_rgb); c->d_dst_rgb = nullptr; }
-  if (c->d_dst_rgb_sorted) { (void)hipFree(c->d_dst_rgb_sorted); c->d_dst_rgb_sorted = nullptr; }
+  dev_free(c->d_winner); dev_free(c->d_rev_pos); dev_free(c->d_rev_d2);
+  dev_free(c->d_dst_rgb); dev_free(c->d_dst_rgb_sorted);
   c->dst_rgb_sorted_ok = false;
   // the lender's own allocations become the share's (its earlier share, if it has one, already holds the rest)
   if (!from->tshare) { from->tshare = new (std::nothrow) TargetShare(); if (!from->tshare) return fail(c, CILHIP_ERR_HIP, "share_target: out of memory"); from->tshare->refs = 1; }
@@ -742,11 +469,11 @@ int cilhip_share_target(cilhip_ctx* c, cilhip_ctx* from) {
   c->index_offset = from->index_offset; c->partial_target = from->partial_target;
   c->d_inv_perm = from->d_inv_perm; c->d_safe2 = from->d_safe2;
   c->d_tie_leaf_slot = from->d_tie_leaf_slot; c->d_tie_nodes = from->d_tie_nodes;
-  c->warm_banned = false;
+  c->policy.warm_banned = false;
   c->src_sorted = false;  // source order is tied to the target grid
   drop_matches(c);
   c->have_pairs = false; c->pairs.count = 0;
-  c->far_mode = true;
+  c->policy.far_mode = true;
   return CILHIP_OK;
 }
 
@@ -774,11 +501,8 @@ int cilhip_set_source(cilhip_ctx* c, const float* xyz, size_t n, int mem) {
     if (!(c->src_half[i] >= 0.0f) || !std::isfinite(c->src_center[i])) { c->src_center[i] = 0.0f; c->src_half[i] = 1.0e30f; }   // (non-finite coordinates: no bound)
   }
   const int nb = std::max(iter_num_blocks(c->ns), warm_num_blocks(c->ns));      // rows of partial sums: the streaming and the warm-started kernels
-  if (nb > c->partial_blocks) {
-    if (c->d_partials) (void)hipFree(c->d_partials);
-    CK(c, hipMalloc(&c->d_partials, (size_t)nb * SUMS_MAX * sizeof(double)));
-    c->partial_blocks = nb;
-  }
+  rc = ensure_partial_rows(c, (size_t)nb);
+  if (rc) return rc;
   c->has_source = true;
   return CILHIP_OK;
 }
@@ -787,8 +511,8 @@ int cilhip_set_source_normals(cilhip_ctx* c, const float* nrm, int mem) {
   if (!c) return CILHIP_ERR_INVALID;
   if (!c->has_source) return fail(c, CILHIP_ERR_INVALID, "set_source_normals: set_source first");
   CK(c, hipSetDevice(c->device));
-  if (c->d_src_nrm) { (void)hipFree(c->d_src_nrm); c->d_src_nrm = nullptr; }
-  if (c->d_src_nrm_sorted) { (void)hipFree(c->d_src_nrm_sorted); c->d_src_nrm_sorted = nullptr; }
+  dev_free(c->d_src_nrm);
+  dev_free(c->d_src_nrm_sorted);
   c->have_pairs = false; c->pairs.count = 0;
   drop_src_grid(c);      // (it carries the feature vectors of the reverse searches)
   if (!nrm) return CILHIP_OK;                              // back to the 3-cloud (non-symmetric) form
@@ -811,9 +535,9 @@ int cilhip_set_color_features(cilhip_ctx* c, const float* dst_rgb, const float* 
   if (!c->has_target || !c->has_source) return fail(c, CILHIP_ERR_INVALID, "set_color_features: set_target and set_source first");
   if (!dst_rgb || !src_rgb) return fail(c, CILHIP_ERR_INVALID, "set_color_features: both clouds' colours are needed");
   CK(c, hipSetDevice(c->device));
-  if (c->d_dst_rgb) { (void)hipFree(c->d_dst_rgb); c->d_dst_rgb = nullptr; }
-  if (c->d_src_rgb) { (void)hipFree(c->d_src_rgb); c->d_src_rgb = nullptr; }
-  if (c->d_src_rgb_sorted) { (void)hipFree(c->d_src_rgb_sorted); c->d_src_rgb_sorted = nullptr; }
+  dev_free(c->d_dst_rgb);
+  dev_free(c->d_src_rgb);
+  dev_free(c->d_src_rgb_sorted);
   int rc = upload(c, dst_rgb, 3 * (size_t)c->grid.n, mem, &c->d_dst_rgb);
   if (rc) return rc;
   rc = upload(c, src_rgb, 3 * (size_t)c->ns, mem, &c->d_src_rgb);
@@ -835,8 +559,19 @@ int cilhip_get_means(cilhip_ctx* c, float dm[3], float sm[3]) {
   return CILHIP_OK;
 }
 
+// The rows of partial sums the accumulating kernels write (SUMS_MAX doubles each): grown, never shrunk.  The pointer is null and the
+// count zero while the new block is being allocated, so a failed allocation leaves nothing stale behind.
+int cilhip::ensure_partial_rows(cilhip_ctx* c, size_t rows) {
+  if (rows <= (size_t)c->partial_blocks) return CILHIP_OK;
+  if (c->d_partials) (void)hipFree(c->d_partials);
+  c->d_partials = nullptr; c->partial_blocks = 0;
+  CK(c, hipMalloc(&c->d_partials, rows * SUMS_MAX * sizeof(double)));
+  c->partial_blocks = (int)rows;
+  return CILHIP_OK;
+}
+
 // Spatially sort the source under T (once; re-sorted only if the transform moved it by more than a few cells).
-static int ensure_sorted(cilhip_ctx* c, const float T[16]) {
+int cilhip::ensure_sorted(cilhip_ctx* c, const float T[16]) {
   if (!c->has_target || !c->has_source) return fail(c, CILHIP_ERR_INVALID, "set_target and set_source first");
   bool need = !c->src_sorted;
   if (!need) {
@@ -857,8 +592,8 @@ static int ensure_sorted(cilhip_ctx* c, const float T[16]) {
     hipError_t e = sort_source(c->d_src_xyz, c->ns, c->grid, T, c->d_src_sorted, c->stream, &c->d_tiles, &c->d_tile_center, c->tile_axes, &c->ntiles, &c->sort_ws);
     if (e != hipSuccess) { c->err = std::string("sort_source: ") + hipGetErrorString(e); return CILHIP_ERR_HIP; }
     if (c->ntiles + 1 > c->tile_aux_cap) {
-      if (c->d_tile_box) { (void)hipFree(c->d_tile_box); c->d_tile_box = nullptr; }
-      if (c->d_defer_mask) { (void)hipFree(c->d_defer_mask); c->d_defer_mask = nullptr; }
+      dev_free(c->d_tile_box);
+      dev_free(c->d_defer_mask);
       c->tile_aux_cap = 0;
       const uint32_t cap = c->ntiles + 1 + c->ntiles / 8;
       CK(c, hipMalloc(&c->d_defer_mask, (size_t)cap * 2 * (TILE_THREADS / 64) * sizeof(unsigned long long)));
@@ -868,17 +603,13 @@ static int ensure_sorted(cilhip_ctx* c, const float T[16]) {
     CK(c, hipMemsetAsync(c->d_defer_mask, 0, ((size_t)c->ntiles + 1) * 2 * (TILE_THREADS / 64) * sizeof(unsigned long long), c->stream));
     {   // the tiled search with in-tile accumulation leaves one row of partial sums per tile and per block of its clean-up pass
       const int rows = std::max(std::max(iter_num_blocks(c->ns), warm_num_blocks(c->ns)), tiled_partial_rows(c->ntiles));
-      if (rows > c->partial_blocks) {
-        if (c->d_partials) (void)hipFree(c->d_partials);
-        c->d_partials = nullptr; c->partial_blocks = 0;
-        CK(c, hipMalloc(&c->d_partials, (size_t)rows * SUMS_MAX * sizeof(double)));
-        c->partial_blocks = rows;
-      }
+      const int rc = ensure_partial_rows(c, (size_t)rows);
+      if (rc) return rc;
     }
     if (c->d_src_nrm) launch_gather_by_w(c->d_src_sorted, c->d_src_nrm, c->ns, c->d_src_nrm_sorted, c->stream);
     if (c->d_src_rgb) launch_gather_by_w(c->d_src_sorted, c->d_src_rgb, c->ns, c->d_src_rgb_sorted, c->stream);
-    if (c->d_src_inv) { (void)hipFree(c->d_src_inv); c->d_src_inv = nullptr; }
-    if (c->d_grid_to_sorted) { (void)hipFree(c->d_grid_to_sorted); c->d_grid_to_sorted = nullptr; }
+    dev_free(c->d_src_inv);
+    dev_free(c->d_grid_to_sorted);
     memcpy(c->sort_T, T, sizeof(c->sort_T));
     c->src_sorted = true;
     c->src3_valid = false; c->rec_valid = false; c->lb_fresh = false;     // (per sorted order)
@@ -893,58 +624,15 @@ int cilhip_prepare_source(cilhip_ctx* c, const float* T, int force, double* ms) 
   CK(c, hipStreamSynchronize(c->stream));
   const auto t0 = std::chrono::steady_clock::now();
   if (force) c->src_sorted = false;
-  const int rc = ensure_sorted(c, T ? T : kIdentity);
+  const int rc = ensure_sorted(c, T ? T : kIdentity16);
   if (rc) return rc;
   CK(c, hipStreamSynchronize(c->stream));
   if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return CILHIP_OK;
 }
 
-// The LDS-tiled kernel runs 1024-thread workgroups, two per CU: below ~2 full rounds of tiles on the
-// 256 CUs the per-lane kernel (8x more, smaller workgroups) balances better (measured: per-lane wins at 1M
-// points = 580 tiles, tiled wins from 2M = 1160 tiles on).
-// It also needs tiles that are reasonably full (a source much sparser than the target leaves most lanes of
-// a tile idle: 10M source points against an 80M-point target fill 14 % of the slots) and a target whose
-// local density fits the LDS budget of a tile's region (cube + halo + one cell of drift per axis);
-// otherwise every tile would be handed to the clean-up pass, which is the per-lane search done worse.
-static bool use_tiled(const cilhip_ctx* c) {
-  if (c->ns >= 0x80000000ull) return false;   // the clean-up list keeps a flag in bit 31 of a query index
-  if (c->tiled >= 2) return true;
-  if (c->tiled != 1 || c->ntiles < 600) return false;   // (measured: 729 tiles / 1M points already favour the tiles by 4 %, 2M by 27 %)
-  const double fill = (double)c->ns / ((double)c->ntiles * (double)TILE_QUERIES);
-  const double region_cells = (double)(CUBE_EDGE + 3) * (CUBE_EDGE + 3) * (CUBE_EDGE + 3);
-  const double density = c->grid_occ > 1.0 ? c->grid_occ - 1.0 : c->grid_occ;   // sum(count^2)/n = lambda + 1 for a Poisson cloud
-  return fill >= 0.45 && density * region_cells <= 0.92 * (double)TILE_CAP;
-}
-
-static bool filters_active(const cilhip_ctx* c) {
-  return (c->inlier_fraction > 0.0 && c->inlier_fraction < 1.0) || c->one_to_one;
-}
-
-// The ICP loop's first Gauss-Newton step is accumulated inside the LDS tiles of the search (one pass instead of a search
-// pass + a streaming accumulation pass) whenever the plain engine runs tiled: no post-filters (they act on the complete
-// match set), point features, the three-cloud metric (the symmetric objective reads source normals per pair), and not
-// the A/B option "fused" (per-lane kernel) or "tile_accumulation" = 0.
-// kernel forms of an iteration's search (+ accumulation): cilhip_get_last_form_timing
-enum { FORM_SEARCH = 0, FORM_TILE_ONE_PASS = 1, FORM_WARM_FIRST = 2, FORM_WARM = 3, FORM_LANE_FUSED = 4 };
-// The warm-started form (k_warm) pays while the queries move little between iterations: a query is settled without any search as
-// long as it has moved less than the MARGIN its last search left it (distance to the second nearest target point minus distance
-// to the nearest, capped by the searched block's faces -- a good fraction of the target's point spacing, whatever the source is).
-// The epilogue publishes how far any source point can have moved in the last update (IcpState::motion_step); a run enters the
-// form when that falls below warm_thresh (a fraction of a cell), and the kernel's own count of the queries it had to search
-// corrects the guess: a quarter of them searched = one iteration through the cold form (whose searches leave fresh margins)
-// and half the bar; three such falls and the run stays cold.
-static void warm_run_reset(cilhip_ctx* c) { c->warm_thresh = c->warm_enter * c->grid.cell; c->warm_strikes = 0; }
-// a warm iteration was seen to search `listed` of its queries: keep going?
-static bool warm_keeps_paying(cilhip_ctx* c, unsigned int listed) {
-  if ((unsigned long long)listed * 4ull <= (unsigned long long)c->ns) return true;
-  c->warm_thresh *= 0.5f;
-  if (++c->warm_strikes >= 3) c->warm_banned = true;
-  return false;
-}
-static bool warm_worthwhile(const cilhip_ctx* c, float step) { return step < c->warm_thresh; }
 // the matches records / margin keys / 12-byte source copy of the warm-started iterations: allocated by the first run that can use them
-static int ensure_warm_buffers(cilhip_ctx* c) {
+int cilhip::ensure_warm_buffers(cilhip_ctx* c) {
   const size_t cap = c->ns ? c->ns : 1;
   if (!c->d_warm_rec) { CK(c, hipMalloc(&c->d_warm_rec, cap * (sizeof(float4) + 2 * sizeof(F3)))); c->src3_valid = false; }
   if (!c->d_nn_lb) CK(c, hipMalloc(&c->d_nn_lb, cap * sizeof(float)));
@@ -956,21 +644,20 @@ static int ensure_warm_buffers(cilhip_ctx* c) {
 }
 // {point, normal} of every target position side by side (GridDev::pn), for the streaming accumulation's gathers: built by the first run
 // that streams over stored matches with a metric that reads normals (32 B per target point; without room for it the two arrays serve)
-static void ensure_pair_records(cilhip_ctx* c) {
+void cilhip::ensure_pair_records(cilhip_ctx* c) {
   if (c->grid.pn || !c->pair_records || !c->grid.nrm || !c->grid.n) return;
   float4* pn = nullptr;
   if (hipMalloc(&pn, (size_t)c->grid.n * 2 * sizeof(float4)) != hipSuccess) { (void)hipGetLastError(); return; }
   launch_interleave_pn(c->grid.pts, c->grid.nrm, c->grid.n, pn, c->stream);
   c->grid.pn = pn;
 }
-static void set_warm_args(const cilhip_ctx* c, IterArgs& wa) {
+void cilhip::set_warm_args(const cilhip_ctx* c, IterArgs& wa) {
   const size_t cap = c->ns ? c->ns : 1;
   wa.warm_extra = c->warm_extra;
   wa.warm_rec = c->d_warm_rec;
   wa.warm_rec_n = reinterpret_cast<F3*>(c->d_warm_rec + cap);
   wa.warm_src3 = wa.warm_rec_n + cap;
 }
-static bool weighted(const cilhip_ctx* c) { return c->weight_fn != nullptr || c->cw_point_kind != CW_UNITY || c->cw_plane_kind != CW_UNITY; }
 // The per-pair weights of the combined-metric classes (PointToPoint/PointToPlaneCorrWeightEvaluatorT of
 // icp_single_transform_combined_metric.hpp:11-14; the point-to-point class has none): evaluator(corr.value) times the
 // metric weight, in f32.  RBF coefficient as common_pair_evaluators.hpp:53.
@@ -985,39 +672,26 @@ static CorrWeights corr_weights_of(const cilhip_ctx* c, bool combined_metric, fl
   if (w.enabled && c->weight_fn) { w.point_table = c->d_wtab; w.plane_table = c->d_wtab + c->wtab_cap; }
   return w;
 }
-static CorrWeights corr_weights_of(const cilhip_ctx* c, const cilhip_icp_params* p) {
+CorrWeights cilhip::corr_weights_of(const cilhip_ctx* c, const cilhip_icp_params* p) {
   return corr_weights_of(c, p->metric == CILHIP_METRIC_COMBINED, p->w_p2p, p->w_p2pl);
 }
-// The warm-started iteration (k_warm) needs stored matches, unit weights and the first Gauss-Newton step's plain terms -- the
-// same engine conditions as the in-tile accumulation, but no tiles: it also serves clouds the tiles do not (a source much
-// sparser than the target: BASELINE configs[3]).
-// a feature adaptor is in force (6-D point+normal or point+colour, 9-D point+normal+colour): correspondences are compared by feature distance
-static bool feat6(const cilhip_ctx* c) { return c->normal_weight > 0.0f || (c->feature_kind == 2 && c->color_weight > 0.0f); }
-static bool warm_capable(const cilhip_ctx* c) {
-  // (the symmetric objective -- source normals set, option symmetric_metric on -- runs warm-started too: k_warm<., ., SYM> streams the source normals)
-  return c->warm_start && c->ns >= 65536 && !filters_active(c) && !weighted(c) && !feat6(c) && !c->fused;
-}
 // k_self_nn's nearest-other-point table (4 B per target point, 0.5 ms at 10M): built by the first warm-capable run on a target
-static int ensure_safe2(cilhip_ctx* c) {
+int cilhip::ensure_safe2(cilhip_ctx* c) {
   if (c->d_safe2) return CILHIP_OK;
   CK(c, hipMalloc(&c->d_safe2, (c->grid.n ? c->grid.n : 1) * sizeof(float)));
   launch_self_nn(c->grid, c->d_safe2, c->stream);
   return CILHIP_OK;
 }
-static bool tile_accumulation(const cilhip_ctx* c) {
-  return c->tile_acc && use_tiled(c) && !filters_active(c) && !weighted(c) && !feat6(c) && !(c->d_src_nrm && c->symmetric) && !c->fused;
-}
 
 // ---- option "tie_rule": the reference's order among exactly equidistant nearest points ------------------------------------------
-// Is the option in force for this context's searches?  The order is the reference's kd-tree over the TARGET POINTS: it covers the
+// When the option is in force for a context's searches: the order is the reference's kd-tree over the TARGET POINTS: it covers the
 // SECOND_TO_FIRST matches (also the forward half of BOTH) under rigid and affine transforms.  Feature adaptors search another
 // space (nanoflann's DIM = 6 / 9 tree: tie_feat_on below), the reverse matches of FIRST_TO_SECOND / BOTH a tree over the transformed
 // SOURCE that the reference rebuilds every iteration (rev_tie_aware); the feature adaptors' reverse searches keep the lowest index
 // (tie_rule 2) or are refused (tie_rule 1, the explicit request).  An
 // index shard of a target (cilhip_set_shard_info) notices and counts ties like any context, but never builds tables from its own points:
 // the order belongs to the WHOLE target's tree -- whoever owns the shards loads it (cilhip_load_tie_order with the global indices) and
-// runs the two-key protocol between them (cilhip_icp_order_keys).
-static bool tie_mode_on(const cilhip_ctx* c) { return c->tie_rule != 0 && !feat6(c); }
+// runs the two-key protocol between them (cilhip_icp_order_keys).  (The predicate itself: tie_mode_on, ctx.hpp.)
 // ... and over 6-D / 9-D features: the forward (SECOND_TO_FIRST) search of a whole target follows the reference's DIM = 6 / 9 tree
 // (its order tables: tie_order_build_device_features; tie_settle<true> / tie_before_nd on the device)
 static bool tie_feat_on(const cilhip_ctx* c) { return c->tie_rule != 0 && feat6(c) && c->search_dir == 0 && !c->partial_target && !c->index_offset; }
@@ -1062,33 +736,40 @@ static int load_tie_tables(cilhip_ctx* c, const uint32_t* leaf_by_index, const u
   for (size_t k = 0; k < n_nodes; ++k) c->tie_max_depth = std::max(c->tie_max_depth, (int)(nodes[k].info >> 3));
   return CILHIP_OK;
 }
-// The tables of THIS context's target, built on the device from the grid's own records (tie_build.hip).
+// The order tables of a tree over this context's target, built on the device (tie_build.hip): `build` fills leaf and slot by original
+// index and the nodes; the tables by sorted position go to *leaf_slot.  On failure the caller drops what *leaf_slot holds.
+template <class Build>
+static hipError_t build_target_order_tables(cilhip_ctx* c, uint2** leaf_slot, uint4** nodes, Build build) {
+  const uint32_t n = c->grid.n;
+  uint32_t *d_leaf = nullptr, *d_slot = nullptr;
+  uint4* d_nodes = nullptr;
+  hipError_t e = hipMalloc(&d_leaf, (n ? n : 1) * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMalloc(&d_slot, (n ? n : 1) * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMalloc(leaf_slot, (n ? n : 1) * sizeof(uint2));
+  if (e == hipSuccess) e = build(d_leaf, d_slot, &d_nodes);
+  if (e == hipSuccess && !d_nodes) e = hipMalloc(&d_nodes, sizeof(uint4));      // (an empty target)
+  if (e == hipSuccess && n) { launch_tie_tables_by_position(c->grid.pts, n, d_leaf, d_slot, *leaf_slot, c->stream); e = hipGetLastError(); }
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  dev_free(d_leaf); dev_free(d_slot);
+  if (e != hipSuccess) dev_free(d_nodes);
+  else *nodes = d_nodes;
+  return e;
+}
+// The tables of THIS context's target, from the grid's own records.
 static int build_tie_tables(cilhip_ctx* c) {
   if (c->d_tie_leaf_slot || !c->has_target) return CILHIP_OK;
   const auto t0 = std::chrono::steady_clock::now();
   CK(c, hipSetDevice(c->device));
-  const uint32_t n = c->grid.n;
   drop_tie_tables(c);
-  uint32_t *d_leaf = nullptr, *d_slot = nullptr;
-  uint4* d_nodes = nullptr;
   size_t n_nodes = 0;
   int depth = 0;
-  hipError_t e = hipMalloc(&d_leaf, (n ? n : 1) * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMalloc(&d_slot, (n ? n : 1) * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMalloc(&c->d_tie_leaf_slot, (n ? n : 1) * sizeof(uint2));
-  if (e == hipSuccess) e = tie_order_build_device(nullptr, c->grid.pts, n, c->stream, d_leaf, d_slot, &d_nodes, &n_nodes, &depth);
-  if (e == hipSuccess && !d_nodes) e = hipMalloc(&d_nodes, sizeof(uint4));      // (an empty target)
-  if (e == hipSuccess && n) { launch_tie_tables_by_position(c->grid.pts, n, d_leaf, d_slot, c->d_tie_leaf_slot, c->stream); e = hipGetLastError(); }
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (d_leaf) (void)hipFree(d_leaf);
-  if (d_slot) (void)hipFree(d_slot);
+  const hipError_t e = build_target_order_tables(c, &c->d_tie_leaf_slot, &c->d_tie_nodes, [&](uint32_t* leaf, uint32_t* slot, uint4** nodes) {
+    return tie_order_build_device(nullptr, c->grid.pts, c->grid.n, c->stream, leaf, slot, nodes, &n_nodes, &depth); });
   if (e != hipSuccess) {
-    if (d_nodes) (void)hipFree(d_nodes);
     drop_tie_tables(c);
     c->err = std::string("tie_rule: building the order tables: ") + hipGetErrorString(e);
     return CILHIP_ERR_HIP;
   }
-  c->d_tie_nodes = d_nodes;
   c->tie_max_depth = depth;
   c->tie_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   ++c->tie_builds;
@@ -1102,7 +783,7 @@ static int read_tie_counters(cilhip_ctx* c, unsigned int out[4]) {
 }
 // The reverse matches' order (FIRST_TO_SECOND / BOTH): what k_reverse_search is handed.  Without valid tables it counts the tied target
 // points (counters[3]) and keeps the lowest source index.
-static TieDev tie_dev_rev(const cilhip_ctx* c) {
+TieDev cilhip::tie_dev_rev(const cilhip_ctx* c) {
   TieDev t{};
   t.mode = tie_mode_on(c) ? 1 : 0;
   t.leaf_slot = (t.mode && c->rev_tie_valid) ? c->d_rev_tie_leaf_slot : nullptr;
@@ -1147,8 +828,6 @@ static int build_rev_tie_tables(cilhip_ctx* c, const float T[16]) {
   return CILHIP_OK;
 }
 // tie_rule 1: the tables before the first search; refusals of the explicit request (see tie_mode_on)
-static int ensure_feature_arrays(cilhip_ctx* c);
-static FeatSpec feat_spec_of(const cilhip_ctx* c);
 // The order tables of the tree the reference's feature adaptor searches (DIM = 6: points + weighted normals or colours; 9: + colours), for
 // this target under the CURRENT feature options, built on the device (tie_build.hip).
 static int build_feat_tie_tables(cilhip_ctx* c) {
@@ -1158,30 +837,18 @@ static int build_feat_tie_tables(cilhip_ctx* c) {
   const FeatSpec f = feat_spec_of(c);
   const int dim = c->feature_kind == 2 ? 9 : 6;
   if (!f.dst || (dim == 9 && !f.dst2)) return fail(c, CILHIP_ERR_INVALID, "tie_rule: the target's feature attributes (normals / colours) are not set");
-  const uint32_t n = c->grid.n;
-  uint32_t *d_leaf = nullptr, *d_slot = nullptr;
-  uint4* d_nodes = nullptr;
   size_t n_nodes = 0;
-  hipError_t e = hipMalloc(&d_leaf, (n ? n : 1) * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMalloc(&d_slot, (n ? n : 1) * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMalloc(&c->d_tief_leaf_slot, (n ? n : 1) * sizeof(uint2));
-  if (e == hipSuccess) e = tie_order_build_device_features(dim, c->grid.pts, f.dst, f.w, f.dst2, f.w2, n, c->stream, d_leaf, d_slot, &d_nodes, &n_nodes, nullptr);
-  if (e == hipSuccess && !d_nodes) e = hipMalloc(&d_nodes, sizeof(uint4));
-  if (e == hipSuccess && n) { launch_tie_tables_by_position(c->grid.pts, n, d_leaf, d_slot, c->d_tief_leaf_slot, c->stream); e = hipGetLastError(); }
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (d_leaf) (void)hipFree(d_leaf);
-  if (d_slot) (void)hipFree(d_slot);
+  const hipError_t e = build_target_order_tables(c, &c->d_tief_leaf_slot, &c->d_tief_nodes, [&](uint32_t* leaf, uint32_t* slot, uint4** nodes) {
+    return tie_order_build_device_features(dim, c->grid.pts, f.dst, f.w, f.dst2, f.w2, c->grid.n, c->stream, leaf, slot, nodes, &n_nodes, nullptr); });
   if (e != hipSuccess) {
-    if (d_nodes) (void)hipFree(d_nodes);
     drop_feat_tie_tables(c);
     c->err = std::string("tie_rule: building the feature tree's order tables: ") + hipGetErrorString(e);
     return CILHIP_ERR_HIP;
   }
-  c->d_tief_nodes = d_nodes;
   ++c->tief_builds;
   return CILHIP_OK;
 }
-static int tie_prepare(cilhip_ctx* c, const char* what) {
+int cilhip::tie_prepare(cilhip_ctx* c, const char* what) {
   c->tie_counters_fresh = false;      // (a new search / run: whatever the host holds of the counters is history)
   if (c->tie_rule == 1 && ((feat6(c) && !tie_feat_on(c)) || (!feat6(c) && c->partial_target && !c->d_tie_leaf_slot))) {
     c->err = std::string(what) + ": tie_rule = 1 covers the SECOND_TO_FIRST search (point features: every direction) on a whole target, or on shards of a point-feature target with the whole target's order loaded (tie_rule = 2 applies the reference's order where it is defined)";
@@ -1194,7 +861,7 @@ static int tie_prepare(cilhip_ctx* c, const char* what) {
   return CILHIP_OK;
 }
 // After a search / run: did it meet ties without tables (tie_rule 2)?  Then the tables are built and *again says: run it once more.
-static int tie_check_pending(cilhip_ctx* c, bool* again) {
+int cilhip::tie_check_pending(cilhip_ctx* c, bool* again) {
   *again = false;
   if (tie_feat_on(c)) {      // a feature search: its forward matches counted tied queries while the feature tree's tables were not there
     if (c->d_tief_leaf_slot || !c->ns || !c->grid.n) return CILHIP_OK;
@@ -1233,7 +900,7 @@ static int tie_check_pending(cilhip_ctx* c, bool* again) {
 }
 
 // filterCorrespondencesFraction then filterCorrespondencesOneToOne on the stored matches
-static int apply_filters(cilhip_ctx* c) {
+int cilhip::apply_filters(cilhip_ctx* c) {
   if (!filters_active(c) || c->ns == 0) return CILHIP_OK;
   if (c->inlier_fraction > 0.0 && c->inlier_fraction < 1.0) {
     if (!c->d_keys) CK(c, hipMalloc(&c->d_keys, (size_t)c->ns * sizeof(unsigned long long)));
@@ -1251,7 +918,7 @@ static int apply_filters(cilhip_ctx* c) {
 // The 6-D feature search's inputs: vectors (normals or colours), weight, and how the source's part follows the transform being
 // searched under (FeatSpec::mode; M = L^-T of that transform is refreshed by cilhip_find_correspondences -- the affine loops are
 // host-driven, the device-resident loops are rigid).
-static FeatSpec feat_spec_of(const cilhip_ctx* c) {
+FeatSpec cilhip::feat_spec_of(const cilhip_ctx* c) {
   FeatSpec f{};
   f.w = c->normal_weight;
   f.enabled = feat6(c) ? 1 : 0;
@@ -1265,7 +932,7 @@ static FeatSpec feat_spec_of(const cilhip_ctx* c) {
   return f;
 }
 // sorted copy of the target's colour features (gathered by the sorted records' original indices), built on first use
-static int ensure_feature_arrays(cilhip_ctx* c) {
+int cilhip::ensure_feature_arrays(cilhip_ctx* c) {
   if (c->feature_kind == 0) return CILHIP_OK;
   if (!c->d_dst_rgb || !c->d_src_rgb) return fail(c, CILHIP_ERR_INVALID, "colour features: cilhip_set_color_features first");
   if (!c->dst_rgb_sorted_ok) {
@@ -1276,7 +943,7 @@ static int ensure_feature_arrays(cilhip_ctx* c) {
   return CILHIP_OK;
 }
 
-static IterArgs make_iter_args(cilhip_ctx* c, float max_sq) {
+IterArgs cilhip::make_iter_args(cilhip_ctx* c, float max_sq) {
   IterArgs a{};
   a.grid = c->grid;
   a.src = c->d_src_sorted;
@@ -1302,7 +969,7 @@ static IterArgs make_iter_args(cilhip_ctx* c, float max_sq) {
 
 // The SECOND_TO_FIRST search under the transform held by c->d_state: LDS-tiled or per-lane kernel for point features, the
 // 6-D feature search when a normal weight is set.
-static int launch_search(cilhip_ctx* c, const IterArgs& a, int lanes = -1 /* -1: the option's own value when it names a lane count */) {
+int cilhip::launch_search(cilhip_ctx* c, const IterArgs& a, int lanes) {
   if (lanes < 0) lanes = c->group_lanes > 0 ? c->group_lanes : 0;
   if (feat6(c)) {
     if (c->feature_kind != 1 && (!c->has_normals || !c->d_src_nrm)) return fail(c, CILHIP_ERR_INVALID, "point+normal features need target and source normals");
@@ -1340,7 +1007,7 @@ static int ensure_src_grid(cilhip_ctx* c) {
   return CILHIP_OK;
 }
 
-static int ensure_reverse_buffers(cilhip_ctx* c) {
+int cilhip::ensure_reverse_buffers(cilhip_ctx* c) {
   const int rc = ensure_src_grid(c);
   if (rc) return rc;
   if (!c->d_rev_pos) {
@@ -1362,11 +1029,11 @@ static int ensure_reverse_buffers(cilhip_ctx* c) {
   return CILHIP_OK;
 }
 
-static int run_pair_search(cilhip_ctx* c, const IterArgs& a, float max_sq, const float T_host[16]) {
+int cilhip::run_pair_search(cilhip_ctx* c, const IterArgs& a, float max_sq, const float T_host[16]) {
   if (!c->d_state_id) {
     CK(c, hipMalloc(&c->d_state_id, sizeof(IcpState)));
     const float zero[3] = {0, 0, 0};
-    launch_init_state(c->d_state_id, kIdentity, zero, c->stream);
+    launch_init_state(c->d_state_id, kIdentity16, zero, c->stream);
   }
   if (c->search_dir == 2 && c->ns && c->grid.n) {   // forward half of BOTH: the usual search, no filters yet
     const int src_rc = launch_search(c, a);
@@ -1467,7 +1134,6 @@ static int scatter_to_original(cilhip_ctx* c) {
 // The correspondence set of the last executed iteration of cilhip_icp_run, when the loop's kernels did not leave it in memory
 // (post-filters, pair-list directions, feature search, forms that store no matches): searched again under the transform that
 // iteration searched under.  The search is exact and deterministic: the same set.
-static int ensure_d2(cilhip_ctx* c);
 static int materialize_pending(cilhip_ctx* c) {
   if (!c->pending_matches) return ensure_d2(c);      // (matches a loop left in place: their distances are formed now, if not yet)
   float T[16];
@@ -1792,12 +1458,8 @@ static int accumulate_stored(cilhip_ctx* c, int metric, const double innerL[9], 
   const int nb = iter_num_blocks(a.ns);
   for (int i = 0; i < SUMS_MAX; ++i) sums[i] = 0.0;
   if (a.ns == 0) return CILHIP_OK;
-  if (nb > c->partial_blocks) {
-    if (c->d_partials) (void)hipFree(c->d_partials);
-    c->d_partials = nullptr; c->partial_blocks = 0;
-    CK(c, hipMalloc(&c->d_partials, (size_t)nb * SUMS_MAX * sizeof(double)));
-    c->partial_blocks = nb;
-  }
+  const int grc = ensure_partial_rows(c, (size_t)nb);
+  if (grc) return grc;
   a.partials = c->d_partials;
   launch_iter(a, metric, false, false, nb, c->stream);
   launch_reduce_partials(c->d_partials, nb, c->d_stage, c->d_sums, c->stream);
@@ -1831,7 +1493,7 @@ int cilhip_estimate_combined(cilhip_ctx* c, float w_p2p, float w_p2pl, size_t ma
   CK(c, hipSetDevice(c->device));
   { const int wrc = prepare_pair_weights(c); if (wrc) return wrc; }
   double L[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0};
-  memcpy(dT, kIdentity, sizeof(kIdentity));
+  memcpy(dT, kIdentity16, sizeof(kIdentity16));
   if (converged) *converged = 0;
   if (AtA_out) for (int i = 0; i < 36; ++i) AtA_out[i] = 0.0;
   if (Atb_out) for (int i = 0; i < 6; ++i) Atb_out[i] = 0.0;
@@ -1918,7 +1580,7 @@ int cilhip_estimate_combined_two_sets(cilhip_ctx* cp, cilhip_ctx* cl, float w_p2
   if (cp->ns != cl->ns || cp->grid.n != cl->grid.n) return fail(cp, CILHIP_ERR_INVALID, "estimate (two sets): the two engines hold different clouds");
   { int wrc = prepare_pair_weights(cp); if (wrc) return wrc; if (cl != cp) { wrc = prepare_pair_weights(cl); if (wrc) { cp->err = cl->err; return wrc; } } }
   double L[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0};
-  memcpy(dT, kIdentity, sizeof(kIdentity));
+  memcpy(dT, kIdentity16, sizeof(kIdentity16));
   if (converged) *converged = 0;
   bool wp = w_p2p > 0.0f, wl = w_p2pl > 0.0f;
   if (!wp && !wl) return CILHIP_OK;                      // transform_estimation.hpp:264-272
@@ -1962,7 +1624,7 @@ int cilhip_icp_run_two_sets(cilhip_ctx* cp, float max_sq_point, cilhip_ctx* cl, 
   if (cp->transform_mode != 0 || cl->transform_mode != 0) return fail(cp, CILHIP_ERR_UNSUPPORTED, "icp_run (two sets): rigid transforms");
   if (cp->search_dir != 0 || cl->search_dir != 0) return fail(cp, CILHIP_ERR_UNSUPPORTED, "icp_run (two sets): SECOND_TO_FIRST engines");
   float T[16];
-  memcpy(T, T0 ? T0 : kIdentity, sizeof(T));
+  memcpy(T, T0 ? T0 : kIdentity16, sizeof(T));
   memcpy(out->T, T, sizeof(T));
   out->iterations = 0; out->last_delta_norm = INFINITY; out->last_ncorr = 0;
   for (size_t it = 0; it < p->max_iter; ++it) {
@@ -1986,9 +1648,6 @@ int cilhip_icp_run_two_sets(cilhip_ctx* cp, float max_sq_point, cilhip_ctx* cl, 
   return CILHIP_OK;
 }
 
-static hipEvent_t get_event(cilhip_ctx* c, size_t i);
-static hipEvent_t get_acc_event(cilhip_ctx* c, size_t i);
-
 // ---- affine variants: SimpleCombinedMetricAffineICP3f / SimplePointToPointMetricAffineICP3f ---------------------------
 // Moments of the 12-unknown normal equations over the stored correspondences (matches or pair list), three streaming
 // passes on the device, one copy to the host.
@@ -2003,12 +1662,8 @@ static int affine_accumulate(cilhip_ctx* c, bool centered, bool plane, double su
   a.no_centering = centered ? 0 : 1;
   if (a.ns == 0) return CILHIP_OK;
   const int nb = iter_num_blocks(a.ns);
-  if (nb > c->partial_blocks) {
-    if (c->d_partials) (void)hipFree(c->d_partials);
-    c->d_partials = nullptr; c->partial_blocks = 0;
-    CK(c, hipMalloc(&c->d_partials, (size_t)nb * SUMS_MAX * sizeof(double)));
-    c->partial_blocks = nb;
-  }
+  const int grc = ensure_partial_rows(c, (size_t)nb);
+  if (grc) return grc;
   a.partials = c->d_partials;
   const int passes[3] = {IM_AFF0, IM_AFF1, IM_AFF2};
   const int np = plane ? 3 : 1;
@@ -2028,7 +1683,7 @@ int cilhip_estimate_affine(cilhip_ctx* c, float w_p2p, float w_p2pl, int centere
   { const int prc = materialize_pending(c); if (prc) return prc; }
   if (!c->have_nn && !c->have_pairs) return fail(c, CILHIP_ERR_INVALID, "estimate: run find_correspondences first");
   CK(c, hipSetDevice(c->device));
-  memcpy(dT, kIdentity, sizeof(kIdentity));
+  memcpy(dT, kIdentity16, sizeof(kIdentity16));
   if (ok) *ok = 0;
   if (n_corr) *n_corr = 0;
   if (AtA_out) for (int i = 0; i < 144; ++i) AtA_out[i] = 0.0;
@@ -2067,12 +1722,12 @@ int cilhip_estimate_affine(cilhip_ctx* c, float w_p2p, float w_p2pl, int centere
 
 // icp_base.hpp:68-87 with the affine updateEstimate() (icp_single_transform_point_to_point_metric.hpp:46-65,
 // icp_single_transform_combined_metric.hpp:173-217 without the rotation() polish): host-driven, one 12x12 solve per iteration.
-static int icp_run_affine(cilhip_ctx* c, const cilhip_icp_params* p, const float* T0, cilhip_icp_result* out) {
+int cilhip::icp_run_affine(cilhip_ctx* c, const cilhip_icp_params* p, const float* T0, cilhip_icp_result* out) {
   float T[16];
-  memcpy(T, T0 ? T0 : kIdentity, sizeof(T));
+  memcpy(T, T0 ? T0 : kIdentity16, sizeof(T));
   float delta = INFINITY;
   size_t it = 0, ncorr = 0;
-  hipEvent_t e_beg = get_event(c, 0), e_end = get_event(c, 1);
+  hipEvent_t e_beg = event_at(c->ev, 0), e_end = event_at(c->ev, 1);
   CK(c, hipEventRecord(e_beg, c->stream));
   while (it < p->max_iter) {
     int rc = cilhip_find_correspondences(c, T, p->max_sq_dist, nullptr);
@@ -2123,809 +1778,6 @@ void cilhip_icp_default_params(cilhip_icp_params* p) {
   p->max_iter = 15; p->conv_tol = 1e-5f;
   p->max_opt_iter = 1; p->opt_conv_tol = 1e-5f;
   p->max_sq_dist = 0.01f * 0.01f;
-}
-
-// What the accumulation kernels sum for one ICP instance.  A plane term without target normals is the reference's
-// "dst_p.cols() != dst_n.cols()" case (transform_estimation.hpp:264-272: identity, false): the kernels must then never
-// touch grid.nrm (it is null) -- they count the correspondences only (IM_POINT's slot 0) and the epilogue's identity
-// branch (k_solve: has_p2pl && !has_normals) does the rest.
-static int iter_metric_of(const cilhip_ctx* c, const cilhip_icp_params* p) {
-  if (p->metric == CILHIP_METRIC_POINT_TO_POINT) return IM_KABSCH;
-  const bool wp = p->w_p2p > 0.0f, wl = p->w_p2pl > 0.0f;
-  if (wl && !c->has_normals) return IM_POINT;
-  if (wp && wl) return IM_BOTH;
-  if (wl) return IM_PLANE;
-  if (wp) return IM_POINT;
-  return IM_PLANE;  // no terms: sums unused, the epilogue takes the identity branch
-}
-
-static SolveArgs make_solve_args(cilhip_ctx* c, const cilhip_icp_params* p, int im, const float src_mean[3]) {
-  SolveArgs sa{};
-  sa.state = c->d_state;
-  sa.partials = c->d_partials;
-  sa.nblocks = iter_num_blocks(c->ns);
-  sa.reduced = nullptr;
-  sa.metric = im;
-  sa.w_p2p = p->w_p2p; sa.w_p2pl = p->w_p2pl;
-  if (p->metric == CILHIP_METRIC_COMBINED && weighted(c)) {   // the metric weights are inside the per-pair weights already
-    sa.w_p2p = p->w_p2p > 0.0f ? 1.0f : 0.0f; sa.w_p2pl = p->w_p2pl > 0.0f ? 1.0f : 0.0f;
-    sa.point_weighted = 1;
-  }
-  sa.conv_tol = p->conv_tol; sa.opt_conv_tol = p->opt_conv_tol;
-  for (int i = 0; i < 3; ++i) { sa.dst_mean[i] = c->dst_mean[i]; sa.src_mean[i] = src_mean[i]; }
-  sa.gn_last_step = 1;
-  sa.has_normals = c->has_normals ? 1 : 0;
-  sa.unproven_cnt = c->d_unproven;
-  sa.guard_axis = c->guard_axis; sa.guard_slack = c->guard_slack;
-  for (int i = 0; i < 3; ++i) { sa.guard_center[i] = c->guard_center[i]; sa.guard_half[i] = c->guard_half[i]; }
-  for (int i = 0; i < 16; ++i) sa.guard_T[i] = c->guard_T[i];
-  for (int i = 0; i < 3; ++i) { sa.src_center[i] = c->src_center[i]; sa.src_half[i] = c->src_half[i]; }
-  sa.trace = c->d_trace;
-  return sa;
-}
-
-static hipEvent_t get_acc_event(cilhip_ctx* c, size_t i) {
-  while (c->ev_acc.size() <= i) { hipEvent_t e; (void)hipEventCreate(&e); c->ev_acc.push_back(e); }
-  return c->ev_acc[i];
-}
-
-static hipEvent_t get_event(cilhip_ctx* c, size_t i) {
-  while (c->ev.size() <= i) { hipEvent_t e; (void)hipEventCreate(&e); c->ev.push_back(e); }
-  return c->ev[i];
-}
-
-// What the run's epilogues have published (Feedback): a consistent snapshot of the LATEST published iteration.
-struct FbView { bool done; unsigned int iterations, unproven, listed; float delta, prev_delta, step; };
-// Waits until iteration `need` of the current run (or its convergence) has been published.  patience_s: how long to spin;
-// returns 0 and fills *v, or 1 when nothing came in that time.
-static int wait_published(cilhip_ctx* c, unsigned int need, double patience_s, FbView* v) {
-  const volatile Feedback* fb = c->h_feedback;
-  const auto t0 = std::chrono::steady_clock::now();
-  struct Acc { cilhip_ctx* c; std::chrono::steady_clock::time_point t; ~Acc() { c->wait_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t).count(); } } acc{c, t0};
-  for (unsigned spins = 0;; ++spins) {
-    const unsigned long long lt = fb->latest;
-    if ((unsigned int)(lt >> 32) == c->run_tag) {
-      const bool done = (lt & 0x80000000ull) != 0ull;
-      const unsigned int iters = (unsigned int)lt & 0x7fffffffu;
-      if (done || iters >= need) {
-        // the slot of the latest published iteration: the device's next write goes to another slot (the host is at most two
-        // iterations ahead), so this read cannot be torn; its commit word is checked all the same
-        const volatile FeedbackSlot* sl = &fb->slot[iters & 3u];
-        v->done = done; v->iterations = iters;
-        v->unproven = sl->unproven; v->listed = sl->listed; v->delta = sl->delta; v->prev_delta = sl->prev_delta; v->step = iters ? sl->step : INFINITY;
-        if (iters == 0u || sl->commit == (((unsigned long long)c->run_tag << 32) | iters)) return 0;
-      }
-    }
-    cpu_relax(spins);
-    if ((spins & 1023u) == 1023u && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > patience_s) return 1;
-  }
-}
-// ... with the long-stall handling of cilhip_icp_run: nothing for 30 s -- a caller-owned stream may have long work of its own
-// queued ahead of this run -- wait for the stream (that also surfaces a device fault); everything enqueued has then run and
-// must have been published
-static int wait_published_or_sync(cilhip_ctx* c, unsigned int need, FbView* v) {
-  if (wait_published(c, need, 30.0, v) == 0) return CILHIP_OK;
-  CK(c, hipStreamSynchronize(c->stream));
-  if (wait_published(c, need, 0.01, v) == 0) return CILHIP_OK;
-  return fail(c, CILHIP_ERR_HIP, "icp_run: the device stopped publishing its loop state");
-}
-
-static int read_state(cilhip_ctx* c, cilhip_icp_result* out, float* Tprev = nullptr) {
-  IcpState hs;
-  CK(c, hipMemcpyAsync(&hs, c->d_state, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
-  CK(c, hipStreamSynchronize(c->stream));
-  memcpy(c->tie_counters_host, hs.tie_counters, sizeof(c->tie_counters_host));
-  c->tie_counters_fresh = true;
-  memcpy(out->T, hs.T, sizeof(hs.T));
-  if (Tprev) memcpy(Tprev, hs.Tprev, sizeof(hs.Tprev));
-  out->iterations = (size_t)hs.iterations;
-  out->last_delta_norm = hs.delta;
-  out->last_ncorr = (size_t)hs.ncorr;
-  return CILHIP_OK;
-}
-
-// What the engine's getCorrespondences() refers to after a run: the set of the last executed iteration, found under Tprev
-// (correspondence_search_kd_tree.hpp:231 keeps it; icp_base.hpp:32-38 hands the engine out).  stored: the loop's kernels left
-// it in nn_pos (the squared distances are formed again with the search's pinned arithmetic); pairs: c->pairs holds it;
-// otherwise it is searched again when somebody asks (materialize_pending).
-static void finish_run_matches(cilhip_ctx* c, const cilhip_icp_params* p, size_t iterations, const float Tprev[16], bool stored, bool pairs) {
-  drop_matches(c); c->have_pairs = false;
-  if (iterations == 0) return;
-  memcpy(c->nn_T, Tprev, sizeof(c->nn_T));
-  if (pairs) { c->have_pairs = true; c->matches_origin = 1; return; }
-  if (stored && c->ns) {
-    // (the squared distances of the stored matches are formed when somebody asks for them -- ensure_d2: a pass over the source that
-    //  a caller who only wants the transform does not pay, 80 us at 10M)
-    c->have_nn = true; c->d2_stale = true; c->matches_origin = 1;
-  } else {
-    c->pending_matches = true; c->pending_max_sq = p->max_sq_dist; c->matches_origin = 2;
-  }
-}
-
-static int icp_run_once(cilhip_ctx* c, const cilhip_icp_params* p, const float* T0, cilhip_icp_result* out);
-int cilhip_icp_run(cilhip_ctx* c, const cilhip_icp_params* p, const float* T0, cilhip_icp_result* out) {
-  if (!c || !p || !out) return CILHIP_ERR_INVALID;
-  if (p->metric != CILHIP_METRIC_POINT_TO_POINT && p->metric != CILHIP_METRIC_COMBINED) return fail(c, CILHIP_ERR_INVALID, "icp_run: bad metric");
-  CK(c, hipSetDevice(c->device));
-  int rc = tie_prepare(c, "icp_run");
-  if (rc) return rc;
-  rc = icp_run_once(c, p, T0, out);
-  if (rc) return rc;
-  // tie_rule 2: some search of the run met exactly equidistant nearest points and the reference's order tables were not there: they
-  // are now (built once per target) -- the run is executed again, from T0, with the ties resolved inside its kernels
-  bool again = false;
-  rc = tie_check_pending(c, &again);
-  if (rc) return rc;
-  return again ? icp_run_once(c, p, T0, out) : CILHIP_OK;
-}
-static int icp_run_once(cilhip_ctx* c, const cilhip_icp_params* p, const float* T0, cilhip_icp_result* out) {
-  if (c->weight_fn && p->metric == CILHIP_METRIC_COMBINED && c->transform_mode == 0) {
-    // a caller's own weight evaluators run on the host: the reference's loop step by step (search, estimate over the stored set with
-    // the callback's weights, rotation() polish + compose), the combiner's loop with one engine in both roles
-    if (c->search_dir != 0) return fail(c, CILHIP_ERR_UNSUPPORTED, "a pair-weight callback runs with SECOND_TO_FIRST searches (rigid loop); estimate from pair lists through cilhip_estimate_combined");
-    c->last_loop_ms = 0.0; c->last_search_ms = 0.0; c->last_acc_ms = 0.0; c->last_search_launches = 0;
-    return cilhip_icp_run_two_sets(c, p->max_sq_dist, c, p->max_sq_dist, p, T0, out);
-  }
-  // The affine classes: their loop runs device-resident like the rigid one -- search-only kernels + one streaming pass of moments
-  // (k_acc_affine) while the source is far from alignment, search + moments in the warm-started kernel afterwards, the 12-unknown solve
-  // and the f32 compose in k_solve_affine -- unless something asks for the stored set per iteration (post-filters, per-pair weights,
-  // other directions, feature adaptors): those keep the host-driven loop (icp_run_affine: three passes + a host solve per iteration).
-  const bool affine = c->transform_mode == 1;
-  if (affine) {
-    if (c->index_offset) return fail(c, CILHIP_ERR_UNSUPPORTED, "the affine variants are not available on target shards");
-    const bool device_loop = c->affine_device_loop && c->ns != 0 && c->grid.n != 0 && c->search_dir == 0 && !filters_active(c) && !weighted(c) && !feat6(c) && !c->fused &&
-                             !(c->d_src_nrm && c->symmetric) && c->guard_axis < 0;
-    if (!device_loop) return icp_run_affine(c, p, T0, out);
-  }
-  const float* Ti = T0 ? T0 : kIdentity;
-  int rc = ensure_sorted(c, Ti);
-  if (rc) return rc;
-  const bool affine_combined = affine && p->metric == CILHIP_METRIC_COMBINED;
-  const int im = !affine ? iter_metric_of(c, p) : (affine_combined && p->w_p2pl > 0.0f && c->has_normals) ? IM_AFFC : IM_AFFP;
-  const bool gn = (im != IM_KABSCH) && !affine;
-  // max_optimization_iterations == 0 (combined metric): the estimator's loop body never runs -- one accumulation pass still counts
-  // the correspondences (the "no usable terms" test, transform_estimation.hpp:264-272), the epilogue skips the solve
-  const bool zero_steps = gn && p->max_opt_iter == 0;
-  const size_t opt_steps = gn ? (p->max_opt_iter ? p->max_opt_iter : 1) : 1;
-  ++c->run_tag;
-  launch_init_state(c->d_state, Ti, c->src_mean, c->stream, c->d_feedback, c->run_tag, c->src_center, c->src_half, c->d_tie_counters);
-  if (gn && c->ns >= 65536) ensure_pair_records(c);
-  IterArgs a = make_iter_args(c, p->max_sq_dist);
-  if (!c->pair_records) a.grid.pn = nullptr;
-  a.cw = corr_weights_of(c, p);
-  SolveArgs sa = make_solve_args(c, p, im, c->src_mean);
-  sa.feedback = c->d_feedback; sa.run_tag = c->run_tag;
-  sa.gn_zero_steps = zero_steps ? 1 : 0;
-  const int nb = sa.nblocks;
-  const int nb_aff = affine ? affine_acc_blocks(c->ns) : 0;
-  if (affine) {
-    a.no_centering = affine_combined ? 0 : 1;
-    sa.affine_centered = affine_combined ? 1 : 0;
-    if (!affine_combined) { sa.w_p2p = 1.0f; sa.w_p2pl = 0.0f; }      // the point-to-point class: unit point terms of the raw coordinates
-    // rows of AFF_ROW doubles: the streaming pass's or the warm-started kernel's
-    const size_t rows = (size_t)std::max(nb_aff, warm_num_blocks(c->ns));
-    const size_t need = (rows * AFF_ROW + SUMS_MAX - 1) / SUMS_MAX;
-    if (need > (size_t)c->partial_blocks) {
-      if (c->d_partials) (void)hipFree(c->d_partials);
-      c->d_partials = nullptr; c->partial_blocks = 0;
-      CK(c, hipMalloc(&c->d_partials, need * SUMS_MAX * sizeof(double)));
-      c->partial_blocks = (int)need;
-      a.partials = c->d_partials; a.tile_partials = c->d_partials;
-      sa.partials = c->d_partials;
-    }
-  }
-  if (c->ns == 0) {  // no source points: the epilogue runs on all-zero sums (identity step)
-    CK(c, hipMemsetAsync(c->d_sums, 0, SUMS_MAX * sizeof(double), c->stream));
-    sa.nblocks = 0;
-    sa.reduced = c->d_sums;
-  }
-  if (c->search_dir != 0) {
-    // FIRST_TO_SECOND / BOTH: the correspondence set is a pair list rebuilt every iteration (a grid over the transformed
-    // source, like the reference's per-iteration kd-tree); host-driven loop, the accumulation kernels stream over the pairs
-    if (c->index_offset) return fail(c, CILHIP_ERR_UNSUPPORTED, "search directions other than SECOND_TO_FIRST are not available on target shards");
-    if (feat6(c)) { rc = ensure_feature_arrays(c); if (rc) return rc; a.feat = feat_spec_of(c); }
-    // (a weight evaluator over FEATURE distances reads them per pair: those loops go through the pair list below)
-    const bool feat_weights = feat6(c) && a.cw.enabled;
-    hipEvent_t e_beg = get_event(c, 0), e_end = get_event(c, 1);
-    CK(c, hipEventRecord(e_beg, c->stream));
-    // Without post-filters the loop needs the SUMS over the correspondence set, not the sorted list: the reverse matches are
-    // found through the inverse of the (rigid) transform against a grid over the source built once, and accumulated where
-    // they are found (BOTH: forward pass + the reverse matches that are not reciprocal duplicates; reciprocal: the
-    // duplicates alone) -- no per-iteration index, no sort, no host round trip: every iteration is enqueued back to back.
-    bool t0_rigid = true;
-    for (int i = 0; i < 3 && t0_rigid; ++i)
-      for (int j = 0; j < 3; ++j) {
-        const double dot = (double)Ti[i * 4] * Ti[j * 4] + (double)Ti[i * 4 + 1] * Ti[j * 4 + 1] + (double)Ti[i * 4 + 2] * Ti[j * 4 + 2];
-        if (std::fabs(dot - (i == j ? 1.0 : 0.0)) > 1e-5) t0_rigid = false;
-      }
-    if (!filters_active(c) && !(c->d_src_nrm && c->symmetric) && t0_rigid && c->ns && c->grid.n && !feat_weights && !(c->rev_tie_aware && tie_mode_on(c))) {
-      rc = ensure_reverse_buffers(c);
-      if (rc) return rc;
-      FeatSpec rf = a.feat;
-      rf.src = c->src_grid.nrm;
-      if (rf.dst2) rf.src2 = c->d_src_rgb_grid;
-      if (feat6(c) && (!rf.src || !rf.dst || (rf.dst2 && !rf.src2))) return fail(c, CILHIP_ERR_INVALID, "feature search: both clouds' feature vectors are needed");
-      const int nb_f = iter_num_blocks(c->ns), nb_r = iter_num_blocks(c->grid.n);
-      // BOTH: the forward half runs warm-started from its third iteration on (search + accumulation in k_warm, like the plain loop's
-      // steady state: exact whatever the source's distance, and these loops have no cheaper forward form to go back to)
-      const bool fwd_wcap = c->search_dir == 2 && warm_capable(c);
-      if (fwd_wcap) { rc = ensure_safe2(c); if (rc) return rc; rc = ensure_warm_buffers(c); if (rc) return rc; }
-      const int nb_w = fwd_wcap ? warm_num_blocks(c->ns) : 0;
-      const int nb_fmax = std::max(nb_f, nb_w);
-      // the warm-started reverse search accumulates the first step's sums itself (one pass over the target; per-pair weights keep the separate pass)
-      const bool rev_fusable = c->reverse_warm && !feat6(c) && !a.cw.enabled && c->d_src_safe2 != nullptr;
-      const int nb_rw = rev_fusable ? reverse_warm_blocks(c->grid.n) : 0;
-      const int nb_rmax = std::max(nb_r, nb_rw);
-      if (nb_fmax + nb_rmax > c->partial_blocks) {
-        if (c->d_partials) (void)hipFree(c->d_partials);
-        c->d_partials = nullptr; c->partial_blocks = 0;
-        CK(c, hipMalloc(&c->d_partials, (size_t)(nb_fmax + nb_rmax) * SUMS_MAX * sizeof(double)));
-        c->partial_blocks = nb_fmax + nb_rmax;
-      }
-      const bool both_union = c->search_dir == 2 && !c->reciprocal;
-      const int rmode = c->search_dir == 1 ? 1 : (c->reciprocal ? 3 : 2);
-      // rows: the reverse matches' first, the forward half's (streaming pass or warm-started kernel) right behind them
-      IterArgs ar = a;
-      ar.partials = c->d_partials;
-      a.nn_d2 = nullptr;
-      c->rec_valid = false; c->lb_fresh = false;
-      warm_run_reset(c);
-      c->last_fused_iters = c->last_two_pass_iters = c->last_warm_iters = 0;
-      for (size_t it = 0; it < p->max_iter; ++it) {
-        bool fwd_warm = false;
-        const bool rev_fused = rev_fusable && it >= 1;      // (this iteration's reverse search starts from the previous matches and accumulates)
-        for (size_t st = 0; st < opt_steps; ++st) {
-          a.skip_if_inner_done = ar.skip_if_inner_done = (st > 0);
-          const int rev_rows = (rev_fused && st == 0) ? nb_rw : nb_r;
-          a.partials = c->d_partials + (size_t)rev_rows * SUMS_MAX; a.tile_partials = a.partials;
-          if (st == 0) {
-            if (c->search_dir == 2) {
-              fwd_warm = fwd_wcap && it >= 2;
-              if (fwd_warm) {
-                IterArgs wa = a;
-                wa.warm_pos = c->d_nn_pos;
-                wa.safe2 = c->d_safe2;
-                wa.warm_far_sq = 0.25f * c->grid.cell * c->grid.cell;
-                set_warm_args(c, wa);
-                wa.nn_lb = c->d_nn_lb; wa.lb_valid = c->lb_fresh ? 1 : 0;
-                launch_warm(wa, im, c->rec_valid ? 2 : 1, nb_w, c->stream);
-                c->rec_valid = true; c->lb_fresh = false;
-                ++c->last_warm_iters;
-              } else {
-                IterArgs sa2 = a;
-                if (fwd_wcap) { sa2.nn_lb = c->d_nn_lb; c->lb_fresh = true; }      // (the margin keys the first warm-started iteration starts from)
-                c->rec_valid = false;
-                const int src_rc = launch_search(c, sa2);
-                if (src_rc) return src_rc;
-              }
-            }
-            // (from the second iteration on d_rev_pos holds the previous reverse matches: the search starts from them)
-            const float* warm_tab = (it >= 1 && c->reverse_warm && !feat6(c)) ? c->d_src_safe2 : nullptr;
-            RevFused rfu{};
-            rfu.metric = im; rfu.mode = rmode; rfu.fwd_pos = c->d_nn_pos; rfu.src_inv = c->d_src_inv; rfu.grid_to_sorted = c->d_grid_to_sorted; rfu.partials = c->d_partials;
-            for (int k = 0; k < 3; ++k) rfu.dst_mean[k] = a.dst_mean[k];
-            { const TieDev rt = tie_dev_rev(c); launch_reverse_search_rigid(c->grid, c->src_grid, c->d_state, p->max_sq_dist, c->d_rev_pos, c->d_rev_d2, c->stream, feat6(c) ? &rf : nullptr, &rt, warm_tab, rev_fused ? &rfu : nullptr); }
-          }
-          const bool fwd_in_kernel = fwd_warm && st == 0;      // (the warm-started kernel accumulated the first step's terms itself)
-          if (both_union && !fwd_in_kernel) launch_iter(a, im, false, false, nb_f, c->stream);
-          if (!(rev_fused && st == 0)) launch_acc_reverse(ar, im, c->src_grid.pts, c->d_rev_pos, c->grid.n, rmode, c->d_nn_pos, c->d_src_inv, nb_r, c->stream);
-          sa.gn_last_step = (st + 1 == opt_steps);
-          const int rows_total = rev_rows + (both_union ? (fwd_in_kernel ? nb_w : nb_f) : 0);
-          const int rows = launch_reduce_stage1(c->d_partials, rows_total, c->d_stage, c->stream);
-          sa.partials = rows ? c->d_stage : c->d_partials;
-          sa.nblocks = rows ? rows : rows_total;
-          sa.reduced = nullptr;
-          launch_solve(sa, c->stream);
-        }
-        if (p->max_iter > 64 && (it + 1) % 32 == 0 && it + 1 < p->max_iter) {     // (long runs: stop enqueueing once converged)
-          int done = 0;
-          CK(c, hipMemcpyAsync(&done, reinterpret_cast<const char*>(c->d_state) + offsetof(IcpState, done), sizeof(int), hipMemcpyDeviceToHost, c->stream));
-          CK(c, hipStreamSynchronize(c->stream));
-          if (done) break;
-        }
-      }
-      CK(c, hipEventRecord(e_end, c->stream));
-      CK(c, hipGetLastError());
-      float Tprev[16];
-      rc = read_state(c, out, Tprev);
-      if (rc) return rc;
-      finish_run_matches(c, p, out->iterations, Tprev, false, false);      // (nothing was listed: searched again on demand)
-      float ms = 0.f;
-      CK(c, hipEventElapsedTime(&ms, e_beg, e_end));
-      c->last_loop_ms = ms; c->last_search_ms = 0.0; c->last_acc_ms = 0.0; c->last_search_launches = 0;
-      return CILHIP_OK;
-    }
-    for (size_t it = 0; it < p->max_iter; ++it) {
-      rc = run_pair_search(c, a, p->max_sq_dist, it == 0 ? Ti : out->T);
-      if (rc) return rc;
-      IterArgs pa = a;
-      pa.nn_d2 = c->pairs.d2;  // (per pair: corr.value -- the 6-D distance under a feature adaptor -- for the weight evaluators)
-      pa.src = c->pairs.src_view; pa.src_nrm = (c->d_src_nrm && c->symmetric) ? c->pairs.nrm_view : nullptr; pa.ns = c->pairs.count; pa.nn_pos = c->pairs.posd;
-      const int pnb = iter_num_blocks(pa.ns);
-      if (pnb > c->partial_blocks) {
-        if (c->d_partials) (void)hipFree(c->d_partials);
-        c->d_partials = nullptr; c->partial_blocks = 0;
-        CK(c, hipMalloc(&c->d_partials, (size_t)pnb * SUMS_MAX * sizeof(double)));
-        c->partial_blocks = pnb;
-      }
-      pa.partials = c->d_partials;
-      for (size_t st = 0; st < opt_steps; ++st) {
-        pa.skip_if_inner_done = (st > 0);
-        sa.gn_last_step = (st + 1 == opt_steps);
-        if (pa.ns) {
-          launch_iter(pa, im, false, false, pnb, c->stream);
-          const int rows = launch_reduce_stage1(c->d_partials, pnb, c->d_stage, c->stream);
-          sa.partials = rows ? c->d_stage : c->d_partials;
-          sa.nblocks = rows ? rows : pnb;
-          sa.reduced = nullptr;
-        } else {
-          CK(c, hipMemsetAsync(c->d_sums, 0, SUMS_MAX * sizeof(double), c->stream));
-          sa.nblocks = 0;
-          sa.reduced = c->d_sums;
-        }
-        launch_solve(sa, c->stream);
-      }
-      rc = read_state(c, out);
-      if (rc) return rc;
-      if (out->last_delta_norm < p->conv_tol) break;   // the device sets `done` by the same test (icp_base.hpp:83)
-    }
-    CK(c, hipEventRecord(e_end, c->stream));
-    CK(c, hipGetLastError());
-    float Tprev[16];
-    rc = read_state(c, out, Tprev);
-    if (rc) return rc;
-    finish_run_matches(c, p, out->iterations, Tprev, false, out->iterations > 0);      // c->pairs: the last iteration's list
-    float ms = 0.f;
-    CK(c, hipEventElapsedTime(&ms, e_beg, e_end));
-    c->last_loop_ms = ms; c->last_search_ms = 0.0; c->last_acc_ms = 0.0; c->last_search_launches = 0;
-    return CILHIP_OK;
-  }
-  if (feat6(c)) { rc = ensure_feature_arrays(c); if (rc) return rc; a.feat = feat_spec_of(c); }
-  if (!filters_active(c) && !(a.cw.enabled && feat6(c))) a.nn_d2 = nullptr;   // nobody reads the distances inside the loop: 4 B per query less to write
-                                                                              // (a weight evaluator over the 6-D feature distance does)
-  const bool tile_acc = tile_accumulation(c) && !affine;      // (the tiles accumulate the rigid classes' terms only)
-  const bool timing = c->kernel_timing && p->max_iter <= 4096;
-  hipEvent_t e_beg = get_event(c, 0), e_end = get_event(c, 1);
-  CK(c, hipEventRecord(e_beg, c->stream));
-  size_t nev = 2, nacc = 0;
-  int launches = 0;
-  // Tiled runs are PACED: the host stays at most two iterations ahead of the device and looks at the loop state of
-  // iteration it - 2 before it enqueues iteration it (a pinned copy + an event per iteration; the device never waits: an
-  // iteration takes hundreds of microseconds, the look a few).  That buys (1) no launches after convergence and (2) the
-  // choice of the kernel FORM per iteration: while the octant stage leaves many queries unproven (source far from
-  // alignment: first iterations of a registration) the search runs with its in-LDS 3x3x3 second pass and a separate
-  // streaming accumulation; once nearly all are proven, search + accumulation run as one pass inside the tiles.
-  const bool wcap = warm_capable(c);
-  if (wcap) { rc = ensure_safe2(c); if (rc) return rc; rc = ensure_warm_buffers(c); if (rc) return rc; }
-  // the feature adaptors' searches warm-started from the previous matches (feat_warm.hip): once the published step is within reach,
-  // while the kernel's own count of the queries it had to search says that it pays
-  // (from 400 000 source points up: below, the look at the published state before every enqueue costs what the form saves -- measured 200k: +5 %, 1M: -23 %)
-  const bool fwcap = feat6(c) && c->feat_warm && c->warm_start != 0 && c->ns >= 400000 && !filters_active(c) && !c->fused && !affine;
-  if (fwcap) {
-    rc = ensure_safe2(c); if (rc) return rc;
-    const int rows = feat_warm_blocks(c->ns);
-    if (rows > c->partial_blocks) {
-      if (c->d_partials) (void)hipFree(c->d_partials);
-      c->d_partials = nullptr; c->partial_blocks = 0;
-      CK(c, hipMalloc(&c->d_partials, (size_t)rows * SUMS_MAX * sizeof(double)));
-      c->partial_blocks = rows;
-      a.partials = c->d_partials; a.tile_partials = c->d_partials; sa.partials = c->d_partials;
-    }
-  }
-  bool feat_warm_now = false;
-  unsigned int feat_judged = 0;
-  const bool paced = ((tile_acc || wcap) && c->ns && p->max_iter > 2 && c->tile_acc_adaptive) || (fwcap && p->max_iter > 2);
-  if (tile_acc && !c->tile_acc_adaptive) c->far_mode = false;
-  c->last_fused_iters = c->last_two_pass_iters = c->last_warm_iters = 0;
-  c->rec_valid = false; c->lb_fresh = false;
-  warm_run_reset(c);
-  c->iter_form.clear(); c->trace_form.clear(); c->timed_iter.clear();
-  for (int k = 0; k < 5; ++k) { c->form_ms[k] = 0.0; c->form_n[k] = 0; }
-  // The cooperative search (several lanes per query) for the cold iterations of clouds the tiles do not take: lanes so that the
-  // queries fill the machine; below the warm-started form's floor always (nothing is lost: no margin keys are wanted there), above it
-  // while the cold kernels' forecast says that most queries are far from settled (their margins would not survive the next step) and
-  // the loop is not yet within reach of the warm-started form -- whose entry needs the keys only the one-lane search leaves.
-  const int glanes = c->group_lanes > 0 ? c->group_lanes
-                     : (c->group_lanes < 0 && !use_tiled(c) && !feat6(c) && !c->fused) ? (c->ns <= 400000u ? 16 : c->ns <= 1500000u ? 8 : 0) : 0;
-  bool group_now = glanes != 0 && (c->group_lanes > 0 || !wcap);
-  size_t next_probe = 0, probe_gap = 8;
-  bool warm_on = false;       // the loop has been seen to move little: iterations run warm-started until one of them has to search too many of its queries
-  unsigned int judged = 0;    // the last published iteration whose listed count has been judged
-  bool all_stored = true;     // every iteration enqueued left its matches in nn_pos (finish_run_matches)
-  bool prev_stored = false;   // ... the previous one did
-  for (size_t it = 0; it < p->max_iter; ++it) {
-    if (paced && it == 1 && wcap && c->warm_start == 1 && !c->warm_banned && !c->trace_form.empty() && (c->trace_form[0] & 0x80)) {
-      // The SECOND iteration can already run warm-started when the first one moved the source by a small fraction of a cell (a
-      // source that starts aligned: tracking, a refinement pass) and its kernels' own forecast agrees: worth one look at the
-      // first iteration's result before the second is enqueued (the device idles for the host's reaction once per run; a cold
-      // iteration costs three times a warm one).
-      FbView fv;
-      rc = wait_published_or_sync(c, 1u, &fv);
-      if (rc) return rc;
-      if (fv.done) break;
-      if ((c->trace_form[0] & 0x7f) <= FORM_TILE_ONE_PASS) c->far_mode = (unsigned long long)fv.unproven * 16ull > (unsigned long long)c->ns;
-      const bool forecast_ok = !c->warm_forecast || (unsigned long long)fv.listed * 8ull <= (unsigned long long)c->ns;
-      if (glanes && c->group_lanes < 0 && fv.iterations == 1u) group_now = (unsigned long long)fv.listed * 2ull > (unsigned long long)c->ns;
-      warm_on = fv.iterations == 1u && forecast_ok && !group_now && warm_worthwhile(c, fv.step);
-    }
-    if (paced && it >= 2) {
-      // wait (briefly, if at all) until iteration it - 2 has been published
-      FbView fv;
-      rc = wait_published_or_sync(c, (unsigned int)(it - 1), &fv);
-      if (rc) return rc;
-      if (fv.done) break;
-      if (fwcap && !c->warm_banned) {
-        // (a warm-started feature search reports the queries it had to search in full: more than a quarter of them = a cold tile search's price)
-        const bool was_fw = fv.iterations >= 1 && fv.iterations <= c->trace_form.size() && (c->trace_form[fv.iterations - 1] & 0x7f) == FORM_WARM;
-        if (was_fw && fv.iterations > feat_judged) { feat_judged = fv.iterations; if (!warm_keeps_paying(c, fv.listed)) feat_warm_now = false; }
-        else if (!feat_warm_now) feat_warm_now = warm_worthwhile(c, fv.step);
-      }
-      // the form of the COLD iterations (one pass / two passes), from the last cold iteration's count of queries its octant stage
-      // left open (a warm-started iteration counts something else there: the queries its own search took to the shells)
-      if (fv.iterations >= 1 && fv.iterations <= c->trace_form.size() && (c->trace_form[fv.iterations - 1] & 0x7f) <= FORM_TILE_ONE_PASS)
-        c->far_mode = (unsigned long long)fv.unproven * 16ull > (unsigned long long)c->ns;
-      // what the published iteration's `listed` count means: a warm-started iteration reports the queries it had to search, a
-      // cold iteration whose kernels leave margins (bit 7 of its form) the queries a warm-started iteration after it would have to
-      auto form_of = [&](const FbView& f) -> int { return (f.iterations >= 1 && f.iterations <= c->trace_form.size()) ? (int)c->trace_form[f.iterations - 1] : -1; };
-      auto is_warm = [&](const FbView& f) { const int fo = form_of(f); return fo >= 0 && ((fo & 0x7f) == FORM_WARM || (fo & 0x7f) == FORM_WARM_FIRST); };
-      if (glanes && c->group_lanes < 0 && wcap) {
-        // a cold iteration that counted (bit 7 of its form): its forecast decides (every eighth iteration of a stretch of cooperative
-        // searches is such a one: below)
-        const int fo = form_of(fv);
-        if (fo >= 0 && (fo & 0x80)) group_now = (unsigned long long)fv.listed * 2ull > (unsigned long long)c->ns;
-      }
-      // (a published iteration is judged once: the same one can be the latest at two consecutive looks)
-      bool fell = false;
-      if (wcap && warm_on && c->warm_start == 1 && fv.iterations > judged && is_warm(fv)) {
-        judged = fv.iterations;
-        if (!warm_keeps_paying(c, fv.listed)) { warm_on = false; fell = true; }
-      }
-      if (wcap && c->warm_start == 1 && !warm_on && !fell && !c->warm_banned && fv.step < 8.0f * c->warm_thresh) {
-        // Candidate for the warm-started form (below).  Decided on the step the loop made LAST -- it is the distance between
-        // the queries the margins were left for and the queries about to be searched -- so wait for iteration it - 1 itself
-        // (a bubble of some tens of microseconds, only while this decision is pending and the loop is within reach of it).
-        rc = wait_published_or_sync(c, (unsigned int)it, &fv);
-        if (rc) return rc;
-        if (fv.done) break;
-        if (is_warm(fv)) {
-          if (fv.iterations > judged && fv.listed != 0u) { judged = fv.iterations; fell = !warm_keeps_paying(c, fv.listed); }
-          if (!fell && !c->warm_banned) warm_on = warm_worthwhile(c, fv.step);
-        } else {
-          // the cold iteration's own forecast: enter only if at most an eighth of the queries would have to be searched
-          // (never out of a stretch of cooperative searches: they leave no keys; its next one-lane iteration's forecast ends the stretch first)
-          const int fo = form_of(fv);
-          const bool forecast_ok = !c->warm_forecast || !(fo >= 0 && (fo & 0x80)) || (unsigned long long)fv.listed * 8ull <= (unsigned long long)c->ns;
-          warm_on = forecast_ok && !(glanes && c->group_lanes < 0 && group_now) && warm_worthwhile(c, fv.step);
-        }
-      }
-    }
-    const bool one_pass = tile_acc && !c->far_mode;
-    // Third form, from the second iteration on: search + accumulation WARM-STARTED from the previous iteration's matches and
-    // the margins their searches left (kept by the forms above) -- no tile to stage at all.  Same matches, same sums up to
-    // the order of the f64 additions.
-    const bool warm = wcap && it >= 1 && (c->warm_start == 2 || (paced && warm_on));
-    const bool single = one_pass || warm;        // search + accumulation in one kernel
-    bool warm_first = false;
-    bool stored_now = true;    // this iteration leaves its matches in nn_pos
-    bool counted = false;      // a cold iteration whose kernels count the queries a warm-started iteration after it would have to search
-    bool feat_warm_it = false; // this iteration's feature search ran warm-started
-    bool feat_fused_it = false; // ... and accumulated the first step's sums itself
-    // (kernel timing on: does THIS iteration carry events?  Every event between dependent kernels idles the device for ~6 us --
-    //  two per iteration are a tenth of a warm-started iteration at 10M -- so a caller may ask for a sample: option kernel_timing_stride)
-    const bool timing_it = timing && (c->timing_stride <= 1 || it < 3 || it % (size_t)c->timing_stride == 0);
-    for (size_t st = 0; st < opt_steps; ++st) {
-      a.skip_if_inner_done = (st > 0);
-      // (the one-kernel forms are timed through their own dispatch packets: no event packets between dependent kernels)
-      const bool lane_fused = c->fused && !filters_active(c) && !feat6(c);
-      const bool ext_ev = timing_it && st == 0 && c->ns && !lane_fused && (warm || one_pass);
-      if (timing_it && st == 0 && !ext_ev) CK(c, hipEventRecord(get_event(c, nev++), c->stream));
-      if (ext_ev) { hipEvent_t e0 = get_event(c, nev), e1 = get_event(c, nev + 1); set_launch_events(e0, e1); nev += 2; }
-      if (c->ns) {
-        if (st == 0 && c->fused && !filters_active(c) && !feat6(c)) {
-          launch_iter(a, im, true, gn && opt_steps > 1, nb, c->stream);
-          all_stored = all_stored && gn && opt_steps > 1;
-          stored_now = gn && opt_steps > 1;
-        } else if (st == 0 && warm) {
-          IterArgs wa = a;
-          wa.warm_pos = c->d_nn_pos;
-          wa.safe2 = c->d_safe2;
-          wa.warm_far_sq = 0.25f * c->grid.cell * c->grid.cell;
-          // the first warm iteration after the search-only forms gathers through the stored positions, takes the margin keys
-          // those searches left (nn_lb) and writes a match record per query; after a tile iteration with the accumulation
-          // inside -- which writes the records itself -- and from then on, the records are streamed instead
-          set_warm_args(c, wa);
-          wa.nn_lb = c->d_nn_lb; wa.lb_valid = c->lb_fresh ? 1 : 0;
-          warm_first = !c->rec_valid;
-          launch_warm(wa, im, c->rec_valid ? 2 : 1, warm_num_blocks(c->ns), c->stream);
-          c->rec_valid = true; c->lb_fresh = false;
-        } else if (st == 0 && one_pass) {
-          // search + accumulation of the first Gauss-Newton step inside the LDS tiles (one pass; the matches are only
-          // stored when further Gauss-Newton steps will stream over them or the next iteration may start from them)
-          IterArgs fa = a;
-          fa.store_matches = (opt_steps > 1 || c->warm_start) ? 1 : 0;
-          fa.partials = c->d_partials + (size_t)c->ntiles * SUMS_MAX;
-          // ... and from the second iteration on the tile leaves the match records of the warm-started form (not the first: a
-          // registration's first step is its largest, its margins would be spent at once)
-          const bool recs = wcap && it >= 1 && c->tile_records && fa.store_matches;
-          if (recs) set_warm_args(c, fa);
-          launch_search_tiled(fa, im, c->d_tiles, c->d_tile_center, c->d_tile_box, c->ntiles, c->stream);
-          c->rec_valid = recs; c->lb_fresh = false;
-          counted = recs;
-          all_stored = all_stored && fa.store_matches != 0;
-          stored_now = fa.store_matches != 0;
-        } else if (st == 0) {
-          c->rec_valid = false;
-          // (search-only form of the tiles: the margin keys of its searches next to the matches)
-          IterArgs sa2 = a;
-          // (above the warm-started form's floor a stretch of cooperative searches is interrupted by a one-lane search now and then -- after
-          //  8 iterations, then 16, 32 ...: it leaves the margin keys and the forecast the loop's decisions, this form or that, the
-          //  warm-started one, are taken from)
-          const bool probe = c->group_lanes < 0 && wcap && it >= next_probe;
-          if (probe) { next_probe = it + probe_gap; probe_gap *= 2; }
-          const int lanes_it = (group_now && !probe && !use_tiled(c) && !feat6(c)) ? glanes : 0;
-          const bool keys = wcap && !feat6(c) && !lanes_it;
-          if (keys) sa2.nn_lb = c->d_nn_lb;
-          c->lb_fresh = keys;
-          counted = keys;
-          // (the cooperative form: the previous iteration's matches, when it left them in nn_pos, bound every query's search)
-          if (lanes_it && it >= 1 && prev_stored) sa2.warm_pos = c->d_nn_pos;
-          feat_warm_it = fwcap && feat_warm_now && it >= 1 && prev_stored && !c->warm_banned;
-          // (... with the sums in the same pass when the terms are the three-cloud metric's own: no source normals in the objective, no per-pair weights)
-          feat_fused_it = feat_warm_it && !(c->d_src_nrm && c->symmetric) && !a.cw.enabled;
-          if (feat_warm_it) { sa2.safe2 = c->d_safe2; sa2.partials = c->d_partials; launch_feat_warm(sa2, feat_fused_it ? im : (int)IM_NONE, c->stream); ++c->last_warm_iters; }
-          else { const int src_rc = launch_search(c, sa2, lanes_it); if (src_rc) return src_rc; }
-          { const int frc = apply_filters(c); if (frc) return frc; }
-          if (timing_it) { CK(c, hipEventRecord(get_event(c, nev++), c->stream)); CK(c, hipEventRecord(get_acc_event(c, nacc++), c->stream)); }
-          if (affine) launch_acc_affine(a, im, nb_aff, c->stream);            // streaming accumulation kernel
-          else if (!feat_fused_it) launch_iter(a, im, false, false, nb, c->stream);
-        } else {
-          launch_iter(a, im, false, false, nb, c->stream);
-        }
-      }
-      if (timing_it && st == 0) {
-        // (two events per iteration around the search / one-pass kernels; a two-pass iteration adds a pair around its
-        //  streaming accumulation, kept in a list of its own)
-        if (ext_ev) {}
-        else if (single || (c->fused && !filters_active(c) && !feat6(c)) || !c->ns) CK(c, hipEventRecord(get_event(c, nev++), c->stream));
-        else CK(c, hipEventRecord(get_acc_event(c, nacc++), c->stream));
-        ++launches; c->timed_iter.push_back((unsigned int)it);
-      }
-      if (st == 0) { if (single) ++c->last_fused_iters; else ++c->last_two_pass_iters; if (warm) ++c->last_warm_iters; }
-      if (st == 0) {
-        const unsigned char form = (unsigned char)(warm ? (warm_first ? FORM_WARM_FIRST : FORM_WARM) : feat_warm_it ? FORM_WARM : one_pass ? FORM_TILE_ONE_PASS
-                                                   : (c->fused && !filters_active(c) && !feat6(c)) ? FORM_LANE_FUSED : FORM_SEARCH);
-        if (timing_it) c->iter_form.push_back(form);
-        c->trace_form.push_back((unsigned char)(form | (counted ? 0x80 : 0)));
-      }
-      sa.gn_last_step = (st + 1 == opt_steps);
-      if (c->ns) {
-        const int prows = (st == 0 && warm) ? warm_num_blocks(c->ns) : (st == 0 && one_pass) ? tiled_partial_rows(c->ntiles) : (st == 0 && feat_fused_it) ? feat_warm_blocks(c->ns)
-                          : affine ? nb_aff : nb;
-        if (affine) launch_reduce_and_solve_affine(c->d_partials, prows, c->d_stage, sa, c->stream);
-        else launch_reduce_and_solve(c->d_partials, prows, c->d_stage, c->fused_epilogue ? c->d_ticket : nullptr, sa, c->stream);
-      } else {
-        launch_solve(sa, c->stream);
-      }
-    }
-    prev_stored = stored_now && c->ns != 0;
-    // Long runs ("iterate until converged" with a large max_iter): the kernels of a converged run return at once, but
-    // the post-filter / reduction launches do not look at the flag, so look at it from the host now and then and stop
-    // enqueueing.  Short runs (the reference's default is 15) stay free of host round trips.
-    if (!paced && p->max_iter > 64 && (it + 1) % 32 == 0 && it + 1 < p->max_iter) {
-      int done = 0;
-      CK(c, hipMemcpyAsync(&done, reinterpret_cast<const char*>(c->d_state) + offsetof(IcpState, done), sizeof(int), hipMemcpyDeviceToHost, c->stream));
-      CK(c, hipStreamSynchronize(c->stream));
-      if (done) break;
-    }
-  }
-  CK(c, hipEventRecord(e_end, c->stream));
-  CK(c, hipGetLastError());
-  float Tprev[16];
-  rc = read_state(c, out, Tprev);
-  if (rc) return rc;
-  finish_run_matches(c, p, out->iterations, Tprev, all_stored && !filters_active(c) && !feat6(c), false);
-  float ms = 0.f;
-  CK(c, hipEventElapsedTime(&ms, e_beg, e_end));
-#ifdef CILHIP_EXP_PHASE_CLOCKS
-  cilhip::debug_dump_phase_clocks();
-#endif
-  c->last_loop_ms = ms;
-  c->last_search_ms = 0.0; c->last_search_launches = 0;
-  if (timing) {
-    // only iterations that actually executed (not the early-exit launches after convergence)
-    size_t executed = 0;
-    while (executed < c->timed_iter.size() && executed < (size_t)launches && (size_t)c->timed_iter[executed] < out->iterations) ++executed;
-    c->last_acc_ms = 0.0;
-    c->timed_ms.assign(executed, 0.0f);
-    for (size_t k = 0; k < executed; ++k) {
-      float m = 0.f;
-      CK(c, hipEventElapsedTime(&m, c->ev[2 + 2 * k], c->ev[3 + 2 * k]));
-      c->timed_ms[k] = m;
-      c->last_search_ms += m;
-      if (k < c->iter_form.size()) { c->form_ms[c->iter_form[k]] += m; ++c->form_n[c->iter_form[k]]; }
-    }
-    for (size_t k = 0; k + 1 < nacc; k += 2) {      // (two-pass iterations; those enqueued past convergence measure ~0)
-      float m = 0.f;
-      CK(c, hipEventElapsedTime(&m, c->ev_acc[k], c->ev_acc[k + 1]));
-      c->last_acc_ms += m;
-    }
-    c->last_search_launches = (int)executed;
-  }
-  return CILHIP_OK;
-}
-
-int cilhip_icp_begin(cilhip_ctx* c, const cilhip_icp_params* p, const float* T0, const float* gmean) {
-  if (!c || !p) return CILHIP_ERR_INVALID;
-  CK(c, hipSetDevice(c->device));
-  if (p->metric == CILHIP_METRIC_COMBINED && p->max_opt_iter != 1) return fail(c, CILHIP_ERR_UNSUPPORTED, "sharded runs support max_opt_iter == 1");
-  if (filters_active(c)) return fail(c, CILHIP_ERR_UNSUPPORTED, "inlier_fraction / one_to_one are global filters: not available in sharded runs");
-  if (c->weight_fn && p->metric == CILHIP_METRIC_COMBINED)
-    return fail(c, CILHIP_ERR_UNSUPPORTED, "a pair-weight callback is evaluated on the host, per estimate: not available in sharded runs (the stock evaluators are)");
-  { const int trc = tie_prepare(c, "icp_begin"); if (trc) return trc; }
-  if (c->search_dir != 0) return fail(c, CILHIP_ERR_UNSUPPORTED, "search directions other than SECOND_TO_FIRST are not available in sharded runs");
-  if (feat6(c) || c->transform_mode != 0) return fail(c, CILHIP_ERR_UNSUPPORTED, "point+normal features and the affine variants are not available in sharded runs");
-  const float* Ti = T0 ? T0 : kIdentity;
-  int rc = ensure_sorted(c, Ti);
-  if (rc) return rc;
-  c->run_prm = *p;
-  for (int i = 0; i < 3; ++i) c->run_src_mean[i] = gmean ? gmean[i] : c->src_mean[i];
-  ++c->run_tag;
-  launch_init_state(c->d_state, Ti, c->run_src_mean, c->stream, c->d_feedback, c->run_tag, c->src_center, c->src_half, c->d_tie_counters);     // (the epilogue publishes the loop state: see cilhip_icp_partial_sums)
-  CK(c, hipGetLastError());
-  c->run_active = true;
-  c->run_nev = 0; c->run_nar = 0; c->last_allreduce_ms = 0.0; c->last_allreduce_n = 0;
-  c->run_enqueue_us = 0.0; c->run_enqueue_iters = 0;
-  c->run_calls = 0;
-  c->run_warm_on = false; c->run_judged = 0;
-  c->rec_valid = false; c->lb_fresh = false;
-  warm_run_reset(c);
-  if (warm_capable(c) && !(c->d_src_nrm && c->symmetric)) { rc = ensure_safe2(c); if (rc) return rc; rc = ensure_warm_buffers(c); if (rc) return rc; }
-  c->iter_form.clear(); c->trace_form.clear();
-  for (int k = 0; k < 5; ++k) { c->form_ms[k] = 0.0; c->form_n[k] = 0; }
-  c->last_fused_iters = c->last_two_pass_iters = c->last_warm_iters = 0;    // counted per cilhip_icp_partial_sums call (cilhip_get_last_run_forms)
-  return CILHIP_OK;
-}
-
-// sums_dev != null: the 48 sums of this iteration's search + accumulation (cilhip_icp_partial_sums).  rows_dev != null instead: RANK_ROWS
-// rows that still have to be folded -- the stage-1 reduction with a FIXED number of groups, whatever form the iteration took and
-// however many blocks this rank has -- for the ranked loop, which all-reduces those (12 KB instead of 384 B: both latency-bound) and
-// lets the epilogue fold them as it does in cilhip_icp_run: one kernel and one gap less per iteration.
-constexpr int RANK_ROWS = 32;
-static int partial_sums_core(cilhip_ctx* c, double* sums_dev, double* rows_dev) {
-  if (!c->run_active) return fail(c, CILHIP_ERR_INVALID, "icp_begin first");
-  CK(c, hipSetDevice(c->device));
-  const int im = iter_metric_of(c, &c->run_prm);
-  IterArgs a = make_iter_args(c, c->run_prm.max_sq_dist);
-  a.cw = corr_weights_of(c, &c->run_prm);
-  const int nb = iter_num_blocks(c->ns);
-  int prows = nb;
-  unsigned char form_now = FORM_LANE_FUSED;      // (the form this iteration takes: what its published counts will mean)
-  if (c->ns && c->grid.n) {      // (a shard without target points -- a slab beyond the target's extent -- has nothing to match: zero sums)
-    if (c->fused) {
-      launch_iter(a, im, true, false, nb, c->stream);
-    } else {
-      a.nn_d2 = nullptr;   // no post-filters in sharded runs: nobody reads the squared distances (as in cilhip_icp_run)
-      const bool timing = c->kernel_timing && c->run_nev + 3 <= 3 * 4096 &&
-                          (c->timing_stride <= 1 || c->run_calls < 3 || c->run_calls % c->timing_stride == 0);      // (a sample of the iterations: option kernel_timing_stride)
-      const size_t e = 2 + c->run_nev;
-      if (timing) CK(c, hipEventRecord(get_event(c, e), c->stream));
-      // Warm-started form (see cilhip_icp_run): from the second call on, when the latest loop state this run's epilogues have
-      // published (a bounded wait for iteration run_calls - 2) says the source is near alignment.  Ranks may differ in their choice: the sums are
-      // the same up to the order of the f64 additions.
-      bool warm = false;
-      const bool wcap = warm_capable(c) && !(c->d_src_nrm && c->symmetric);      // (the sharded building blocks: the symmetric objective stays with the streaming pass)
-      if (wcap && c->run_calls >= 1) {
-        warm = c->warm_start == 2;
-        if (!warm && c->run_calls >= 2) {
-          // paced like cilhip_icp_run: at most two iterations ahead of the device (which never waits: an iteration takes
-          // hundreds of microseconds), so that the loop state looked at is at least that of iteration run_calls - 2; a brief
-          // wait at most (5 s without news: the cold form)
-          FbView fv;
-          if (wait_published(c, (unsigned int)(c->run_calls - 1), 5.0, &fv) == 0) {
-            // (what a published iteration's counts mean depends on the form it ran in: as in cilhip_icp_run)
-            auto form_of = [&](const FbView& f) -> int { return (f.iterations >= 1 && f.iterations <= c->trace_form.size()) ? (int)c->trace_form[f.iterations - 1] : -1; };
-            auto is_warm = [&](const FbView& f) { const int fo = form_of(f); return fo >= 0 && ((fo & 0x7f) == FORM_WARM || (fo & 0x7f) == FORM_WARM_FIRST); };
-            if (form_of(fv) >= 0 && (form_of(fv) & 0x7f) <= FORM_TILE_ONE_PASS) c->far_mode = (unsigned long long)fv.unproven * 16ull > (unsigned long long)c->ns;
-            bool fell = false;
-            if (c->run_warm_on && fv.iterations > c->run_judged && is_warm(fv)) {
-              c->run_judged = fv.iterations;
-              if (!warm_keeps_paying(c, fv.listed)) { c->run_warm_on = false; fell = true; }
-            }
-            if (!c->run_warm_on && !fell && !c->warm_banned && fv.step < 8.0f * c->warm_thresh) {
-              // candidate for the warm-started form: decided on the step the loop made LAST -- wait for iteration run_calls - 1
-              // itself (its epilogue has been enqueued by the caller's previous apply; a bubble of some tens of microseconds, only
-              // while this decision is pending and the loop is within reach of it), then as cilhip_icp_run decides
-              FbView f2;
-              if (wait_published(c, (unsigned int)c->run_calls, 5.0, &f2) == 0) {
-                fv = f2;
-                if (is_warm(fv)) {
-                  if (fv.iterations > c->run_judged && fv.listed != 0u) { c->run_judged = fv.iterations; fell = !warm_keeps_paying(c, fv.listed); }
-                  if (!fell && !c->warm_banned) c->run_warm_on = warm_worthwhile(c, fv.step);
-                } else {
-                  const int fo = form_of(fv);
-                  const bool forecast_ok = !c->warm_forecast || !(fo >= 0 && (fo & 0x80)) || (unsigned long long)fv.listed * 8ull <= (unsigned long long)c->ns;
-                  c->run_warm_on = forecast_ok && warm_worthwhile(c, fv.step);
-                }
-              }
-            }
-            warm = c->run_warm_on;
-          }
-        }
-      }
-      if (warm) {
-        IterArgs wa = a;
-        wa.nn_pos = c->d_nn_pos;
-        wa.warm_pos = c->d_nn_pos;
-        wa.safe2 = c->d_safe2;
-        wa.warm_far_sq = 0.25f * c->grid.cell * c->grid.cell;
-        set_warm_args(c, wa);
-        wa.nn_lb = c->d_nn_lb; wa.lb_valid = c->lb_fresh ? 1 : 0;
-        if (timing) c->iter_form.push_back((unsigned char)(c->rec_valid ? FORM_WARM : FORM_WARM_FIRST));
-        form_now = (unsigned char)(c->rec_valid ? FORM_WARM : FORM_WARM_FIRST);
-        launch_warm(wa, im, c->rec_valid ? 2 : 1, warm_num_blocks(c->ns), c->stream);
-        prows = warm_num_blocks(c->ns);
-        c->rec_valid = true; c->lb_fresh = false;
-        if (timing) CK(c, hipEventRecord(get_event(c, e + 1), c->stream));
-        ++c->last_fused_iters; ++c->last_warm_iters;
-      } else if (tile_accumulation(c)) {
-        if (timing) c->iter_form.push_back((unsigned char)FORM_TILE_ONE_PASS);
-        IterArgs fa = a;
-        fa.store_matches = c->warm_start ? 1 : 0;
-        fa.partials = c->d_partials + (size_t)c->ntiles * SUMS_MAX;
-        const bool recs = wcap && c->run_calls >= 1 && c->tile_records && fa.store_matches;
-        if (recs) set_warm_args(c, fa);
-        launch_search_tiled(fa, im, c->d_tiles, c->d_tile_center, c->d_tile_box, c->ntiles, c->stream);
-        c->rec_valid = recs; c->lb_fresh = false;
-        form_now = (unsigned char)(FORM_TILE_ONE_PASS | (recs ? 0x80 : 0));
-        if (timing) CK(c, hipEventRecord(get_event(c, e + 1), c->stream));
-        prows = tiled_partial_rows(c->ntiles);
-        ++c->last_fused_iters;
-      } else {
-        c->rec_valid = false;
-        if (timing) c->iter_form.push_back((unsigned char)FORM_SEARCH);
-        ++c->last_two_pass_iters;
-        IterArgs sa2 = a;
-        const bool keys = wcap;
-        if (keys) sa2.nn_lb = c->d_nn_lb;
-        c->lb_fresh = keys;
-        form_now = (unsigned char)(FORM_SEARCH | (keys ? 0x80 : 0));
-        if (use_tiled(c)) launch_search_tiled(sa2, IM_NONE, c->d_tiles, c->d_tile_center, c->d_tile_box, c->ntiles, c->stream);
-        else launch_iter(sa2, IM_NONE, true, true, nb, c->stream);
-        if (timing) CK(c, hipEventRecord(get_event(c, e + 1), c->stream));
-        launch_iter(a, im, false, false, nb, c->stream);
-      }
-      if (timing) { CK(c, hipEventRecord(get_event(c, e + 2), c->stream)); c->run_nev += 3; }
-    }
-    if (sums_dev) launch_reduce_partials(c->d_partials, prows, c->d_stage, sums_dev, c->stream);
-    else launch_reduce_stage1_groups(c->d_partials, prows, rows_dev, RANK_ROWS, c->stream);
-  } else if (sums_dev) {
-    CK(c, hipMemsetAsync(sums_dev, 0, SUMS_MAX * sizeof(double), c->stream));
-  } else {
-    CK(c, hipMemsetAsync(rows_dev, 0, (size_t)RANK_ROWS * SUMS_MAX * sizeof(double), c->stream));
-  }
-  c->trace_form.push_back(form_now);
-  ++c->run_calls;
-  CK(c, hipGetLastError());
-  return CILHIP_OK;
-}
-
-int cilhip_icp_partial_sums(cilhip_ctx* c, double* sums_dev) {
-  if (!c || !sums_dev) return CILHIP_ERR_INVALID;
-  return partial_sums_core(c, sums_dev, nullptr);
-}
-
-int cilhip_icp_apply_sums(cilhip_ctx* c, const double* sums_dev) {
-  if (!c || !sums_dev) return CILHIP_ERR_INVALID;
-  if (!c->run_active) return fail(c, CILHIP_ERR_INVALID, "icp_begin first");
-  CK(c, hipSetDevice(c->device));
-  const int im = iter_metric_of(c, &c->run_prm);
-  SolveArgs sa = make_solve_args(c, &c->run_prm, im, c->run_src_mean);
-  sa.feedback = c->d_feedback; sa.run_tag = c->run_tag;
-  sa.nblocks = 0;
-  sa.reduced = sums_dev;
-  launch_solve(sa, c->stream);
-  CK(c, hipGetLastError());
-  return CILHIP_OK;
 }
 
 int cilhip_set_shard_info(cilhip_ctx* c, uint64_t target_index_offset, const float* dst_mean, const float* src_mean) {
@@ -2990,6 +1842,24 @@ int cilhip_icp_partial_keys(cilhip_ctx* c, uint64_t* keys_dev) {
   return CILHIP_OK;
 }
 
+// the sums over the matches a key exchange has just selected into nn_pos / nn_d2 (select: enqueues that selection)
+template <class Select>
+static int sums_of_selected(cilhip_ctx* c, double* sums_dev, Select select) {
+  const int im = iter_metric_of(c, &c->run_prm);
+  IterArgs a = make_iter_args(c, c->run_prm.max_sq_dist);
+  a.cw = corr_weights_of(c, &c->run_prm);
+  const int nb = iter_num_blocks(c->ns);
+  if (c->ns && c->grid.n) {
+    select();
+    launch_iter(a, im, false, false, nb, c->stream);
+    launch_reduce_partials(c->d_partials, nb, c->d_stage, sums_dev, c->stream);
+  } else {
+    CK(c, hipMemsetAsync(sums_dev, 0, SUMS_MAX * sizeof(double), c->stream));
+  }
+  CK(c, hipGetLastError());
+  return CILHIP_OK;
+}
+
 int cilhip_icp_sums_from_keys(cilhip_ctx* c, const uint64_t* keys_dev, double* sums_dev) {
   if (!c || !keys_dev || !sums_dev) return CILHIP_ERR_INVALID;
   if (!c->run_active) return fail(c, CILHIP_ERR_INVALID, "icp_begin first");
@@ -2998,21 +1868,10 @@ int cilhip_icp_sums_from_keys(cilhip_ctx* c, const uint64_t* keys_dev, double* s
     CK(c, hipMalloc(&c->d_inv_perm, (c->grid.n ? c->grid.n : 1) * sizeof(uint32_t)));
     launch_inv_perm(c->grid.pts, c->grid.n, c->d_inv_perm, c->stream);
   }
-  const int im = iter_metric_of(c, &c->run_prm);
-  IterArgs a = make_iter_args(c, c->run_prm.max_sq_dist);
-  a.cw = corr_weights_of(c, &c->run_prm);
-  const int nb = iter_num_blocks(c->ns);
-  if (c->ns && c->grid.n) {
+  return sums_of_selected(c, sums_dev, [&] {
     launch_keys_to_pos(c->d_src_sorted, reinterpret_cast<const unsigned long long*>(keys_dev), c->d_inv_perm, c->ns,
                        c->index_offset, c->grid.n, c->d_nn_pos, c->d_nn_d2, c->stream,
-                       (tie_mode_on(c) && !c->d_tie_leaf_slot) ? c->d_tie_counters : nullptr);
-    launch_iter(a, im, false, false, nb, c->stream);
-    launch_reduce_partials(c->d_partials, nb, c->d_stage, sums_dev, c->stream);
-  } else {
-    CK(c, hipMemsetAsync(sums_dev, 0, SUMS_MAX * sizeof(double), c->stream));
-  }
-  CK(c, hipGetLastError());
-  return CILHIP_OK;
+                       (tie_mode_on(c) && !c->d_tie_leaf_slot) ? c->d_tie_counters : nullptr); });
 }
 
 // The reference's tie order across target shards (extract.hip: tie_rank): after the MIN all-reduce of cilhip_icp_partial_keys' keys,
@@ -3041,48 +1900,9 @@ int cilhip_icp_sums_from_ordered_keys(cilhip_ctx* c, const uint64_t* win_keys_de
   if (!c->run_active) return fail(c, CILHIP_ERR_INVALID, "icp_begin first");
   if (!c->d_own_order) return fail(c, CILHIP_ERR_INVALID, "icp_sums_from_ordered_keys: cilhip_icp_order_keys first");
   CK(c, hipSetDevice(c->device));
-  const int im = iter_metric_of(c, &c->run_prm);
-  IterArgs a = make_iter_args(c, c->run_prm.max_sq_dist);
-  a.cw = corr_weights_of(c, &c->run_prm);
-  const int nb = iter_num_blocks(c->ns);
-  if (c->ns && c->grid.n) {
+  return sums_of_selected(c, sums_dev, [&] {
     launch_select_ordered(c->d_src_sorted, c->d_own_order, reinterpret_cast<const unsigned long long*>(order_keys_dev),
-                          reinterpret_cast<const unsigned long long*>(win_keys_dev), c->ns, c->d_nn_pos, c->d_nn_d2, c->stream);
-    launch_iter(a, im, false, false, nb, c->stream);
-    launch_reduce_partials(c->d_partials, nb, c->d_stage, sums_dev, c->stream);
-  } else {
-    CK(c, hipMemsetAsync(sums_dev, 0, SUMS_MAX * sizeof(double), c->stream));
-  }
-  CK(c, hipGetLastError());
-  return CILHIP_OK;
-}
-
-int cilhip_icp_state(cilhip_ctx* c, cilhip_icp_result* out) {
-  if (!c || !out) return CILHIP_ERR_INVALID;
-  CK(c, hipSetDevice(c->device));
-  const int rc = read_state(c, out);   // (synchronises the stream)
-  if (rc == CILHIP_OK && c->run_nar) {
-    double ms = 0.0;
-    for (size_t k = 0; k + 2 <= c->run_nar; k += 2) { float a = 0.f; CK(c, hipEventElapsedTime(&a, c->ev_ar[k], c->ev_ar[k + 1])); ms += a; }
-    c->last_allreduce_ms = ms; c->last_allreduce_n = (int)(c->run_nar / 2);
-    c->run_nar = 0;
-  }
-  if (rc == CILHIP_OK && c->run_nev) {
-    // kernel timing of a sharded run: search / accumulation time summed over the cilhip_icp_partial_sums calls since
-    // cilhip_icp_begin (read with cilhip_get_last_timing / cilhip_get_last_timing2)
-    double sm = 0.0, am = 0.0;
-    for (size_t k = 0; k + 3 <= c->run_nev; k += 3) {
-      float a = 0.f, b = 0.f;
-      CK(c, hipEventElapsedTime(&a, get_event(c, 2 + k), get_event(c, 2 + k + 1)));
-      CK(c, hipEventElapsedTime(&b, get_event(c, 2 + k + 1), get_event(c, 2 + k + 2)));
-      sm += a; am += b;
-      if (k / 3 < c->iter_form.size()) { c->form_ms[c->iter_form[k / 3]] += a; ++c->form_n[c->iter_form[k / 3]]; }
-    }
-    c->last_search_ms = sm; c->last_acc_ms = am; c->last_search_launches = (int)(c->run_nev / 3);
-    c->last_loop_ms = 0.0;
-    c->run_nev = 0;
-  }
-  return rc;
+                          reinterpret_cast<const unsigned long long*>(win_keys_dev), c->ns, c->d_nn_pos, c->d_nn_d2, c->stream); });
 }
 
 int cilhip_compute_residuals(cilhip_ctx* c, int metric, float w_p2p, float w_p2pl, const float T[16], float* out, int mem) {
@@ -3133,113 +1953,3 @@ int cilhip_get_last_timing(cilhip_ctx* c, double* loop_ms, double* search_ms, in
   if (launches) *launches = c->last_search_launches;
   return CILHIP_OK;
 }
-
-}  // extern "C"
-
-#include "rccl_api.hpp"
-
-// =====================================================================================================================
-// One process PER device (torchrun, MPI): this process' context as one rank of an RCCL communicator, and the sharded loop's
-// inner triple -- partial sums, all-reduce of the 48 f64, epilogue -- run for a number of iterations inside ONE call: per
-// iteration the host enqueues a handful of launches and one ncclAllReduce on the context's stream instead of going through three
-// foreign-function calls and a framework collective (measured with one rank: 0.169 -> see DESIGN.md section 8).  The id travels
-// by whatever the launcher already has (torch.distributed broadcast, MPI_Bcast, a file).
-namespace { RcclApi g_rank_rccl; }
-
-extern "C" {
-
-int cilhip_rank_comm_unique_id(unsigned char id_out[128]) {
-  if (!id_out) return CILHIP_ERR_INVALID;
-  if (!g_rank_rccl.load()) return CILHIP_ERR_UNSUPPORTED;
-  RcclApi::UniqueId u;
-  if (g_rank_rccl.GetUniqueId(&u) != 0) return CILHIP_ERR_HIP;
-  memcpy(id_out, u.internal, sizeof(u.internal));
-  return CILHIP_OK;
-}
-
-// Everything of cilhip_rank_comm_init that can fail on ONE rank alone -- opening librccl, the buffer of the rows -- done beforehand, so
-// that the ranks can agree (one MIN over whatever channel the launcher has) to enter the collective ncclCommInitRank only when every
-// one of them will get through: a rank that bailed out before the collective would leave its peers waiting inside it.
-int cilhip_rank_comm_prepare(cilhip_ctx* c) {
-  if (!c) return CILHIP_ERR_INVALID;
-  if (!g_rank_rccl.load()) return fail(c, CILHIP_ERR_UNSUPPORTED, "rank_comm_prepare: librccl.so.1 could not be opened");
-  CK(c, hipSetDevice(c->device));
-  if (!c->d_rank_sums && hipMalloc(&c->d_rank_sums, (size_t)RANK_ROWS * SUMS_MAX * sizeof(double)) != hipSuccess)
-    return fail(c, CILHIP_ERR_HIP, "rank_comm_prepare: out of device memory");
-  return CILHIP_OK;
-}
-
-int cilhip_rank_comm_init(cilhip_ctx* c, const unsigned char id[128], int nranks, int rank) {
-  if (!c || !id || nranks < 1 || rank < 0 || rank >= nranks) return CILHIP_ERR_INVALID;
-  if (c->rank_comm) return fail(c, CILHIP_ERR_INVALID, "rank_comm_init: the context already holds a communicator");
-  if (!g_rank_rccl.load()) return fail(c, CILHIP_ERR_UNSUPPORTED, "rank_comm_init: librccl.so.1 could not be opened");
-  CK(c, hipSetDevice(c->device));
-  RcclApi::UniqueId u;
-  memcpy(u.internal, id, sizeof(u.internal));
-  rccl_comm_t comm = nullptr;
-  if (g_rank_rccl.CommInitRank(&comm, nranks, u, rank) != 0 || !comm) return fail(c, CILHIP_ERR_HIP, "ncclCommInitRank failed");
-  if (!c->d_rank_sums && hipMalloc(&c->d_rank_sums, (size_t)RANK_ROWS * SUMS_MAX * sizeof(double)) != hipSuccess) {
-    (void)g_rank_rccl.CommDestroy(comm);
-    return fail(c, CILHIP_ERR_HIP, "rank_comm_init: out of device memory");
-  }
-  c->rank_comm = comm; c->rank_comm_size = nranks;
-  return CILHIP_OK;
-}
-
-int cilhip_rank_comm_destroy(cilhip_ctx* c) {
-  if (!c) return CILHIP_ERR_INVALID;
-  if (c->rank_comm) { (void)hipStreamSynchronize(c->stream); (void)g_rank_rccl.CommDestroy(c->rank_comm); c->rank_comm = nullptr; c->rank_comm_size = 0; }
-  if (c->d_rank_sums) { (void)hipFree(c->d_rank_sums); c->d_rank_sums = nullptr; }
-  return CILHIP_OK;
-}
-
-int cilhip_get_last_allreduce_timing(cilhip_ctx* c, double* total_ms, int* timed) {
-  if (!c) return CILHIP_ERR_INVALID;
-  if (total_ms) *total_ms = c->last_allreduce_ms;
-  if (timed) *timed = c->last_allreduce_n;
-  return CILHIP_OK;
-}
-
-int cilhip_get_last_host_enqueue_time(cilhip_ctx* c, double* us_per_iteration) {
-  if (!c || !us_per_iteration) return CILHIP_ERR_INVALID;
-  *us_per_iteration = c->run_enqueue_iters ? c->run_enqueue_us / c->run_enqueue_iters : 0.0;
-  return CILHIP_OK;
-}
-
-int cilhip_icp_iterate_ranked(cilhip_ctx* c, int iterations) {
-  if (!c || iterations < 0) return CILHIP_ERR_INVALID;
-  if (!c->rank_comm) return fail(c, CILHIP_ERR_INVALID, "icp_iterate_ranked: cilhip_rank_comm_init first");
-  if (!c->run_active) return fail(c, CILHIP_ERR_INVALID, "icp_begin first");
-  CK(c, hipSetDevice(c->device));
-  const int im = iter_metric_of(c, &c->run_prm);
-  const auto t_call = std::chrono::steady_clock::now();
-  const double wait0 = c->wait_us;
-  struct Acc { cilhip_ctx* c; std::chrono::steady_clock::time_point t; double w0; int n;
-               ~Acc() { c->run_enqueue_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t).count() - (c->wait_us - w0); c->run_enqueue_iters += n; } } acc{c, t_call, wait0, iterations};
-  for (int k = 0; k < iterations; ++k) {
-    // this rank's RANK_ROWS rows of partial sums -> summed over the ranks, row by row -> folded by the epilogue (the same values on
-    // every rank: identical transforms and decisions everywhere)
-    // (with kernel timing on, the iterations that carry kernel events also time their collective: what the all-reduce costs per
-    //  iteration ON THE STREAM -- launch of RCCL's kernel, the exchange over xGMI, the wait for the slowest rank -- is the figure a
-    //  scaling curve has to be read against; cilhip_get_last_allreduce_timing)
-    const bool time_ar = c->kernel_timing && c->run_nar + 2 <= 2 * 4096 &&
-                         (c->timing_stride <= 1 || c->run_calls < 3 || c->run_calls % c->timing_stride == 0);
-    const int rc = partial_sums_core(c, nullptr, c->d_rank_sums);
-    if (rc) return rc;
-    if (time_ar) {
-      while (c->ev_ar.size() < c->run_nar + 2) { hipEvent_t e; CK(c, hipEventCreate(&e)); c->ev_ar.push_back(e); }
-      CK(c, hipEventRecord(c->ev_ar[c->run_nar], c->stream));
-    }
-    if (g_rank_rccl.AllReduce(c->d_rank_sums, c->d_rank_sums, (size_t)RANK_ROWS * SUMS_MAX, RCCL_DOUBLE, RCCL_SUM, c->rank_comm, c->stream) != 0)
-      return fail(c, CILHIP_ERR_HIP, "ncclAllReduce failed");
-    if (time_ar) { CK(c, hipEventRecord(c->ev_ar[c->run_nar + 1], c->stream)); c->run_nar += 2; }
-    SolveArgs sa = make_solve_args(c, &c->run_prm, im, c->run_src_mean);
-    sa.feedback = c->d_feedback; sa.run_tag = c->run_tag;
-    sa.partials = c->d_rank_sums; sa.nblocks = RANK_ROWS; sa.reduced = nullptr;
-    launch_solve(sa, c->stream);
-    CK(c, hipGetLastError());
-  }
-  return CILHIP_OK;
-}
-
-}  // extern "C"

@@ -1,0 +1,304 @@
+// ctx.hpp -- the context behind the C ABI (struct cilhip_ctx) and what the two host-only translation units share: c_api.hip (entry
+// points, buffers, single searches and estimates) and icp_loop.hip (the ICP loop drivers).  No kernel translation unit includes it.
+#pragma once
+
+#include "../../include/cilantro_hip/c_api.h"
+
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "internal.hpp"
+#include "loop_policy.hpp"
+
+using namespace cilhip;
+
+// Device allocations of a target that SEVERAL contexts use (cilhip_share_target): freed when the last of them lets go.
+struct TargetShare { int refs = 0; std::vector<void*> allocs; };
+
+struct cilhip_ctx {
+  int device = 0;
+  TargetShare* tshare = nullptr;  // non-null: some of this context's target pointers belong to a share (target_ptr_free / release_target_share)
+  hipStream_t own_stream = nullptr;
+  hipStream_t stream = nullptr;
+  std::string err;
+
+  // target
+  bool has_target = false;
+  GridDev grid{};
+  bool has_normals = false;
+  double grid_occ = 0.0;
+  size_t grid_cells = 0;
+  double build_ms = 0.0;
+  float dst_mean[3] = {0, 0, 0};
+  uint32_t index_offset = 0;      // global index of this shard's first target point (target-sharded runs)
+  bool partial_target = false;    // this context holds only PART of the cloud the reference would index (an index shard, a spatial slab: cilhip_set_shard_info
+                                  // with an offset or the whole cloud's mean): the order tables are the WHOLE cloud's -- loaded (cilhip_load_tie_order), never built here
+  uint32_t* d_inv_perm = nullptr; // [n_target] original local index -> sorted position (built on first use)
+
+  // source
+  bool has_source = false;
+  uint32_t ns = 0;
+  float* d_src_xyz = nullptr;     // original order (kept for re-sorting)
+  float4* d_src_sorted = nullptr; // sorted cube-major by target-grid cell under sort_T
+  SortWorkspace sort_ws;          // scratch + tile table of sort_source, kept between the sorts of a source (d_tiles / d_tile_center point into it)
+  uint32_t tile_aux_cap = 0;      // tiles d_tile_box / d_defer_mask are sized for
+  uint2* d_tiles = nullptr;       // [ntiles] query ranges of the LDS-tiled search kernel
+  float4* d_tile_center = nullptr;  // [ntiles] cube centre of each tile in source space
+  int* d_tile_box = nullptr;        // [8*ntiles] cell range of each tile's cube under the current transform (recomputed per search)
+  float tile_axes[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  unsigned long long* d_defer_mask = nullptr;  // [ntiles * 32] queries the tiles hand to the clean-up pass (bit masks, rewritten by every search)
+  uint32_t* d_defer_flag = nullptr;            // [1] "some tile deferred a query" (reset before, set by, every tiled search)
+  uint32_t* d_unproven = nullptr;              // [128] queries the tiles' first stage did not prove / the warm-started kernel listed (summed / zeroed by the epilogue)
+  LoopPolicy policy;                           // the form an ICP iteration takes: warm_banned / far_mode belong to the cloud pair, the rest to one run (loop_policy.hpp)
+  Feedback* h_feedback = nullptr;              // pinned, host-coherent: what the epilogue kernel publishes after every iteration (pacing, kernel form)
+  Feedback* d_feedback = nullptr;              // the device's address of it
+  unsigned int run_tag = 0;
+  int last_fused_iters = 0, last_two_pass_iters = 0, last_warm_iters = 0;
+  int run_calls = 0;              // cilhip_icp_partial_sums calls since cilhip_icp_begin
+  std::vector<unsigned char> iter_form;   // form of every timed search / one-pass launch of the last run (FORM_*), in launch order
+  std::vector<unsigned char> trace_form;  // form of every iteration enqueued by the last run, timed or not (cilhip_get_last_run_trace)
+  double form_ms[5] = {0, 0, 0, 0, 0};    // ... and the kernel time summed per form
+  int form_n[5] = {0, 0, 0, 0, 0};
+  int warm_start = 1;             // option "warm_start": 0 = never, 1 = when the device reports the source near alignment, 2 = from the second iteration on
+  uint32_t* d_dbg = nullptr;                   // [2] cilhip_debug_counters scratch
+  uint4* d_trace = nullptr;                    // [RUN_TRACE_CAP] per-iteration loop state of the last run, written by the epilogue (cilhip_get_last_run_trace)
+  uint32_t ntiles = 0;
+  int tiled = 1;                  // 0: per-lane global-memory search; 1: LDS-tiled search when the cloud is large enough; 2: always tiled
+  bool src_sorted = false;
+  float sort_T[16];
+  float src_mean[3] = {0, 0, 0};
+  float* d_src_nrm = nullptr;         // optional source normals, original order (4-cloud ctor => symmetric metric)
+  float4* d_src_nrm_sorted = nullptr;
+  uint32_t* d_nn_pos = nullptr;
+  float* d_nn_d2 = nullptr;
+  float4* d_warm_rec = nullptr;   // [ns] float4 + 2 x [ns] F3: match records {matched point, margin key} {normal} and the 12-byte source copy of the warm-started iterations
+  bool rec_valid = false;         // the records describe the last executed iteration's matches (inside a run)
+  bool src3_valid = false;        // the 12-byte source copy matches d_src_sorted (rewritten after a re-sort)
+  float* d_nn_lb = nullptr;       // [ns] margin keys the search-only tile kernel leaves next to nn_pos (IterArgs::nn_lb)
+  bool lb_fresh = false;          // ... and they belong to the search that left nn_pos (inside a run)
+  bool warm_forecast = true;      // option "warm_forecast": the cold kernels' count of the queries a warm-started iteration would have to search gates the form
+  // option "tie_rule": which of several EXACTLY equidistant nearest target points a correspondence names.  0 = the lowest target index;
+  // 1 = the one the reference's kd-tree traversal meets first, order tables built before the first search; 2 (default) = the same
+  // choice, the tables built when a search first MEETS a tie (that search / run is then executed again): a target that never ties never
+  // pays for a tree.  The device resolves ties inside its search kernels (TieDev, kernels.hip: tie_settle).
+  int tie_rule = 2;
+  uint2* d_tief_leaf_slot = nullptr;             // [grid.n] the order tables of the FEATURE tree (6-D / 9-D adaptors: points + weighted normals / colours), for the
+  uint4* d_tief_nodes = nullptr;                 // feature options they were built under (dropped with any of them); TieNode::info with four dimension bits
+  int tief_builds = 0;
+  uint2* d_tie_leaf_slot = nullptr;              // [grid.n] the order tables by sorted target position (null: not loaded)
+  uint4* d_tie_nodes = nullptr;
+  unsigned int* d_tie_counters = nullptr;        // [4] TieDev::counters
+  unsigned int* d_ticket = nullptr;              // [1] k_reduce_solve's ticket (zero between launches)
+  // option "group_search": the global-memory search with SEVERAL lanes per query (k_search_group: small clouds and sources far from
+  // alignment, where one lane per query leaves the chip idle behind chains of dependent trips).  -1 (default) = the ICP loop decides per
+  // iteration (cold iterations of clouds the tiles do not take: always for clouds below the warm-started form's floor, from the
+  // kernels' own forecast above it); 0 = never; 4 .. 64 = that many lanes in every global-memory search.
+  int group_lanes = -1;
+  double wait_us = 0.0;                          // time spent waiting for the device to publish loop state (wait_published), accumulated: not enqueue work
+  bool feat_warm = true;                         // option "feature_warm_start": the feature adaptors' forward search warm-started from the previous matches once the loop moves little (feat_warm.hip)
+  bool affine_device_loop = true;                // option "affine_device_loop": the affine classes' loop device-resident (one-pass moments on the matrix cores, 12-unknown
+                                                 // solve in the epilogue kernel) whenever nothing needs the stored set per iteration; 0 = the host-driven loop (A/B)
+  bool fused_epilogue = false;                   // option "fused_epilogue": stage-1 reduction + epilogue in ONE launch (the last of the 32 stage-1 blocks runs the
+                                                 // epilogue).  Bitwise the same results, measured SLOWER: 0.129 -> 0.136 ms per iteration at 10M, 0.037 -> 0.044 at 1M --
+                                                 // a device-scope fence costs more on this eight-L2 part than the kernel boundary it removes (NOTEBOOK.md): off
+  unsigned int tie_counters_host[4] = {0, 0, 0, 0};      // ... as read together with the loop state at the end of a run (read_state: one synchronisation for both)
+  bool tie_counters_fresh = false;
+  double tie_build_ms = 0.0;                     // host time of the last table build (tree + upload)
+  int tie_builds = 0;                            // table builds on this context (diagnostics)
+  // the reverse matches of FIRST_TO_SECOND / BOTH: the reference's tree is over the TRANSFORMED source, a new one per search -- once a
+  // reverse search has met exactly equidistant source points (or under tie_rule 1) that tree's order tables are built (on the device) before
+  // every reverse search (the loops then run host-driven, one search at a time)
+  bool rev_tie_aware = false;
+  uint2* d_rev_tie_leaf_slot = nullptr;          // [ns] by position in the source grid; valid for rev_tie_T only
+  uint4* d_rev_tie_nodes = nullptr;
+  size_t rev_tie_nodes_cap = 0;
+  bool rev_tie_valid = false;
+  float rev_tie_T[16];
+  int rev_tie_builds = 0;
+  float warm_extra = 0.0625f;     // option "warm_extra_fraction"
+  bool pair_records = true;       // option "pair_records": the streaming accumulation gathers a match's point and normal from one 32-byte record (GridDev::pn)
+  void* rank_comm = nullptr; int rank_comm_size = 0; double* d_rank_sums = nullptr;      // cilhip_rank_comm_*: this process' rank in an RCCL communicator
+  bool tile_records = true;       // option "tile_records": the accumulating tile kernel writes the warm-started form's match records itself
+  float warm_enter = 0.15f;       // option "warm_enter_fraction": the bar a run starts with, as a fraction of a grid cell
+  float src_center[3] = {0, 0, 0}, src_half[3] = {0, 0, 0};   // bounding box of the source (source coordinates): the epilogue's bound on how far a query moves per update
+  float* d_safe2 = nullptr;       // [grid.n] k_self_nn's table for the warm-started iteration; built with the target
+  int cw_point_kind = 0, cw_plane_kind = 0;     // correspondence weight evaluators (CW_*), combined metric
+  float cw_point_sigma = 1.0f, cw_plane_sigma = 1.0f;
+  cilhip_pair_weight_fn weight_fn = nullptr;    // a caller's own evaluators (cilhip_set_pair_weight_callback): the estimates call them on the host
+  void* weight_user = nullptr;
+  float* d_wtab = nullptr;        // [2 * wtab_cap] point / plane weights by stream position (CorrWeights::point_table / plane_table)
+  float* d_wtab_in = nullptr;     // [2 * wtab_cap] ... by original source index, as the host filled them
+  size_t wtab_cap = 0;
+  bool have_nn = false;           // nn_pos/nn_d2 hold the result of a search
+  bool d2_stale = false;          // ... but nn_d2 has not been formed yet (matches left by a loop whose kernels keep no distances: ensure_d2)
+  float nn_T[16];                 // transform used by that search
+  // after cilhip_icp_run the engine's correspondence set is the last executed iteration's (correspondence_search_kd_tree.hpp:231 through
+  // icp_base.hpp:32-38): either the loop's kernels left it in nn_pos (have_nn, origin 1) or it is searched again on demand under
+  // nn_T = the transform that iteration searched under (pending_matches, origin 2) -- the search is exact, so it is the same set
+  bool pending_matches = false;
+  float pending_max_sq = 0.0f;
+  int matches_origin = 0;         // cilhip_get_last_matches_origin
+
+  // loop state / scratch
+  IcpState* d_state = nullptr;
+  double* d_partials = nullptr;
+  int partial_blocks = 0;
+  double* d_stage = nullptr;      // [REDUCE_STAGE_DOUBLES] stage-1 rows of the cross-block reduction
+  double* d_sums = nullptr;       // [3 * SUMS_MAX] (the affine estimator reduces three passes before one copy to the host)
+  bool tile_acc_adaptive = true;  // choose one pass / two passes per iteration from the device's feedback (option "tile_accumulation" = 2: always one pass)
+  bool tile_acc = true;           // accumulate inside the LDS tiles of the search when the engine allows it (option "tile_accumulation", A/B)
+  bool fused = false;             // true: search+accumulate in one kernel; false: search kernel + streaming accumulate kernel (faster: the search runs at 2x the occupancy)
+  double cell_occupancy = 1.0;    // target points per grid cell (takes effect at the next set_target)
+  double refined_occupancy = 3.0; // option "refined_occupancy_factor": how much denser than that a REFINED grid (surface-like / clustered target) may stay
+  unsigned long long* d_count = nullptr;
+  uint32_t* d_out_idx = nullptr;  // [ns] original-order results
+  float* d_out_d2 = nullptr;
+
+  // engine post-filters (correspondence_search_kd_tree.hpp:224-225)
+  double inlier_fraction = 1.0;
+  bool one_to_one = false;
+  unsigned long long* d_keys = nullptr;    // [ns]
+  unsigned long long* d_own_order = nullptr;   // [ns] this shard's traversal keys of the current iteration (cilhip_icp_order_keys)
+  int tie_max_depth = 0;                   // depth of the loaded order tree (the traversal keys hold 58 levels)
+  void* d_sel_state = nullptr;
+  unsigned long long* d_winner = nullptr;  // [n_target]
+
+  // other search directions (correspondence_search_kd_tree.hpp:185-222): the correspondence set is a pair list
+  int search_dir = 0;             // 0 = SECOND_TO_FIRST (default), 1 = FIRST_TO_SECOND, 2 = BOTH
+  bool reciprocal = false;        // require_reciprocality_ (BOTH only)
+  int transform_mode = 0;         // 0 = rigid (Isometry), 1 = affine: which ICP instance family cilhip_icp_run mirrors
+  float normal_weight = 0.0f;     // > 0: the correspondence search runs on 6-D features (point, weight * v)
+  int feature_kind = 0;           // option "feature_kind": 0 = v = normals, following the transform (PointNormalFeaturesAdaptor);
+                                  // 1 = v = colours, untouched by it (PointColorFeaturesAdaptor; cilhip_set_color_features)
+  float *d_dst_rgb = nullptr, *d_src_rgb = nullptr;             // colour features, original order
+  float4 *d_dst_rgb_sorted = nullptr, *d_src_rgb_sorted = nullptr;
+  float4* d_src_rgb_grid = nullptr;      // the source's colours in the order of the source's own grid (9-D reverse search)
+  float color_weight = 0.0f;             // option "feature_color_weight" (feature_kind 2: the 9-D adaptor's colour weight)
+  bool dst_rgb_sorted_ok = false;
+  float src_nrm0[3] = {0, 0, 0};  // the first source normal (the affine feature adaptor's normal weight is |w n_0|, adaptors.hpp:113-114)
+  float feat_M[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};              // L^-T of the transform being searched under (affine adaptor)
+  bool symmetric = true;          // source normals, when set, also switch the combined metric to the symmetric objective
+  PairSet pairs;
+  GridDev src_grid{};             // grid over the source in SOURCE coordinates (built on the first FIRST_TO_SECOND / BOTH search of a source)
+  bool has_src_grid = false;
+  float* d_src_safe2 = nullptr;   // [ns] k_self_nn's table over the SOURCE grid: the margin test of the warm-started reverse search (k_reverse_warm)
+  bool reverse_warm = true;       // option "reverse_warm_start": the device-resident FIRST_TO_SECOND / BOTH loops start every reverse search but the first from the previous matches
+  uint32_t* d_grid_to_sorted = nullptr;   // [ns] source-grid position -> sorted source position (d_src_inv through the source grid's order): the fused reverse pass's duplicate test
+  uint32_t *d_rev_pos = nullptr, *d_src_inv = nullptr;   // list-free loops of those directions: reverse matches by target position; original -> sorted source position
+  float* d_rev_d2 = nullptr;
+  bool have_pairs = false;        // `pairs` holds the result of the last find_correspondences
+  IcpState* d_state_id = nullptr; // a state holding the identity transform (the reverse search transforms nothing)
+
+  // sharded-run state
+  cilhip_icp_params run_prm{};
+  bool run_active = false;
+  int guard_axis = -1;            // slab-sharded runs: see SolveArgs::guard_*
+  float guard_slack = 0.0f, guard_center[3] = {0, 0, 0}, guard_half[3] = {0, 0, 0}, guard_T[16] = {0};
+  float run_src_mean[3] = {0, 0, 0};
+
+  // timing
+  bool kernel_timing = false;
+  int timing_stride = 1;          // option "kernel_timing_stride": with kernel timing on, iterations 0..2 and every stride-th one carry events
+  std::vector<unsigned int> timed_iter;      // the iterations of the last run that did
+  std::vector<float> timed_ms;               // ... and the kernel time of each (cilhip_get_last_iteration_timing)
+  double last_loop_ms = 0.0, last_search_ms = 0.0, last_acc_ms = 0.0;
+  int last_search_launches = 0;
+  size_t run_nev = 0;             // sharded runs: hipEvents recorded by cilhip_icp_partial_sums since cilhip_icp_begin (3 per call)
+  std::vector<hipEvent_t> ev, ev_acc;
+  std::vector<hipEvent_t> ev_ar;  // ranked loop: event pairs around the sampled all-reduces since cilhip_icp_begin (cilhip_get_last_allreduce_timing)
+  size_t run_nar = 0;             // ... how many of them are recorded
+  double last_allreduce_ms = 0.0; int last_allreduce_n = 0;
+  double run_enqueue_us = 0.0; int run_enqueue_iters = 0;      // ranked loop: host time of its enqueue calls (the paced waits for the device's feedback word excluded)
+};
+
+#define CK(ctx, call)                                                                                   \
+  do {                                                                                                  \
+    hipError_t e_ = (call);                                                                             \
+    if (e_ != hipSuccess) {                                                                             \
+      (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                                   \
+      return CILHIP_ERR_HIP;                                                                            \
+    }                                                                                                   \
+  } while (0)
+
+namespace cilhip {
+inline int fail(cilhip_ctx* c, int code, const char* msg) {
+  if (c) c->err = msg;
+  return code;
+}
+
+// The LDS-tiled kernel runs 1024-thread workgroups, two per CU: below ~2 full rounds of tiles on the
+// 256 CUs the per-lane kernel (8x more, smaller workgroups) balances better (measured: per-lane wins at 1M
+// points = 580 tiles, tiled wins from 2M = 1160 tiles on).
+// It also needs tiles that are reasonably full (a source much sparser than the target leaves most lanes of
+// a tile idle: 10M source points against an 80M-point target fill 14 % of the slots) and a target whose
+// local density fits the LDS budget of a tile's region (cube + halo + one cell of drift per axis);
+// otherwise every tile would be handed to the clean-up pass, which is the per-lane search done worse.
+inline bool use_tiled(const cilhip_ctx* c) {
+  if (c->ns >= 0x80000000ull) return false;   // the clean-up list keeps a flag in bit 31 of a query index
+  if (c->tiled >= 2) return true;
+  if (c->tiled != 1 || c->ntiles < 600) return false;   // (measured: 729 tiles / 1M points already favour the tiles by 4 %, 2M by 27 %)
+  const double fill = (double)c->ns / ((double)c->ntiles * (double)TILE_QUERIES);
+  const double region_cells = (double)(CUBE_EDGE + 3) * (CUBE_EDGE + 3) * (CUBE_EDGE + 3);
+  const double density = c->grid_occ > 1.0 ? c->grid_occ - 1.0 : c->grid_occ;   // sum(count^2)/n = lambda + 1 for a Poisson cloud
+  return fill >= 0.45 && density * region_cells <= 0.92 * (double)TILE_CAP;
+}
+
+inline bool filters_active(const cilhip_ctx* c) {
+  return (c->inlier_fraction > 0.0 && c->inlier_fraction < 1.0) || c->one_to_one;
+}
+
+inline bool weighted(const cilhip_ctx* c) { return c->weight_fn != nullptr || c->cw_point_kind != CW_UNITY || c->cw_plane_kind != CW_UNITY; }
+// a feature adaptor is in force (6-D point+normal or point+colour, 9-D point+normal+colour): correspondences are compared by feature distance
+inline bool feat6(const cilhip_ctx* c) { return c->normal_weight > 0.0f || (c->feature_kind == 2 && c->color_weight > 0.0f); }
+// The warm-started iteration (k_warm) needs stored matches, unit weights and the first Gauss-Newton step's plain terms -- the
+// same engine conditions as the in-tile accumulation, but no tiles: it also serves clouds the tiles do not (a source much
+// sparser than the target: BASELINE configs[3]).
+inline bool warm_capable(const cilhip_ctx* c) {
+  // (the symmetric objective -- source normals set, option symmetric_metric on -- runs warm-started too: k_warm<., ., SYM> streams the source normals)
+  return c->warm_start && c->ns >= 65536 && !filters_active(c) && !weighted(c) && !feat6(c) && !c->fused;
+}
+
+// The ICP loop's first Gauss-Newton step is accumulated inside the LDS tiles of the search (one pass instead of a search
+// pass + a streaming accumulation pass) whenever the plain engine runs tiled: no post-filters (they act on the complete
+// match set), point features, the three-cloud metric (the symmetric objective reads source normals per pair), and not
+// the A/B option "fused" (per-lane kernel) or "tile_accumulation" = 0.
+inline bool tile_accumulation(const cilhip_ctx* c) {
+  return c->tile_acc && use_tiled(c) && !filters_active(c) && !weighted(c) && !feat6(c) && !(c->d_src_nrm && c->symmetric) && !c->fused;
+}
+
+// option "tie_rule" is in force for this context's point searches (c_api.hip: the order tables)
+inline bool tie_mode_on(const cilhip_ctx* c) { return c->tie_rule != 0 && !feat6(c); }
+
+// c->fused is honoured as ONE per-lane search+accumulate kernel only by the plain engine (post-filters and feature adaptors need the stored set)
+inline bool lane_fused(const cilhip_ctx* c) { return c->fused && !filters_active(c) && !feat6(c); }
+// the stored correspondence set (matches or pair list) no longer describes anything a caller may read
+inline void drop_matches(cilhip_ctx* c) { c->have_nn = false; c->d2_stale = false; c->pending_matches = false; c->matches_origin = 0; }
+// event i of a list that grows on demand (c->ev: run / kernel events, c->ev_acc: the two-pass iterations' accumulation)
+inline hipEvent_t event_at(std::vector<hipEvent_t>& v, size_t i) {
+  while (v.size() <= i) { hipEvent_t e; (void)hipEventCreate(&e); v.push_back(e); }
+  return v[i];
+}
+
+// ---- helpers of c_api.hip the loop drivers call (iter_metric_of: the other way round)
+int ensure_sorted(cilhip_ctx* c, const float T[16]);
+int ensure_partial_rows(cilhip_ctx* c, size_t rows);      // d_partials holds at least `rows` rows of SUMS_MAX doubles (callers re-read c->d_partials)
+int ensure_warm_buffers(cilhip_ctx* c);
+void ensure_pair_records(cilhip_ctx* c);
+int ensure_safe2(cilhip_ctx* c);
+int ensure_feature_arrays(cilhip_ctx* c);
+int ensure_reverse_buffers(cilhip_ctx* c);
+void set_warm_args(const cilhip_ctx* c, IterArgs& wa);
+CorrWeights corr_weights_of(const cilhip_ctx* c, const cilhip_icp_params* p);
+FeatSpec feat_spec_of(const cilhip_ctx* c);
+TieDev tie_dev_rev(const cilhip_ctx* c);
+int tie_prepare(cilhip_ctx* c, const char* what);
+int tie_check_pending(cilhip_ctx* c, bool* again);
+int apply_filters(cilhip_ctx* c);
+IterArgs make_iter_args(cilhip_ctx* c, float max_sq);
+int launch_search(cilhip_ctx* c, const IterArgs& a, int lanes = -1 /* -1: the option's own value when it names a lane count */);
+int run_pair_search(cilhip_ctx* c, const IterArgs& a, float max_sq, const float T_host[16]);
+int icp_run_affine(cilhip_ctx* c, const cilhip_icp_params* p, const float* T0, cilhip_icp_result* out);
+int iter_metric_of(const cilhip_ctx* c, const cilhip_icp_params* p);      // (icp_loop.hip)
+}  // namespace cilhip

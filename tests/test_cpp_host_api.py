@@ -49,3 +49,13 @@ def test_solve_fast_paths_on_host(hip_lib, orc):
         subprocess.check_call(["bash", os.path.join(ROOT, "tests", "cpp", "build.sh")])
     out = subprocess.run([binp], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and "ALL OK" in out.stdout, out.stdout + out.stderr
+
+
+def test_loop_policy_on_host(hip_lib, orc):
+    """cilantro_amd/csrc/loop_policy.hpp decides the kernel form of every ICP iteration (cilhip_icp_run and the sharded runs
+    share it): its integer and strict-inequality rules at their boundaries, compiled with the host compiler -- no GPU needed."""
+    binp = os.path.join(ROOT, "tests", "cpp", "bin", "test_loop_policy")
+    if not os.path.exists(binp):
+        subprocess.check_call(["bash", os.path.join(ROOT, "tests", "cpp", "build.sh")])
+    out = subprocess.run([binp], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "ALL OK" in out.stdout, out.stdout + out.stderr
