@@ -425,7 +425,11 @@ int cilhip_radius_search3f(int device, const float* ref_xyz, size_t n_ref, const
  * fewer than 3 neighbours => NaN.  view_point: 3 floats; if all finite the normal is flipped to point towards it
  * (:326-330), NULL / non-finite: sign left as the eigen-solver gives it (as in the reference).
  * normals_out: HOST 3*n, curvature_out: HOST n or NULL.  f32 per-term arithmetic, f64 accumulation and f64 Jacobi
- * eigen-solve in place of Eigen's f32 SelfAdjointEigenSolver. */
+ * eigen-solve in place of Eigen's f32 SelfAdjointEigenSolver: the mean is summed in f64 and rounded to f32, the centred
+ * terms and their products are f32 (one rounding each), sums and eigen-solve f64, results rounded to f32.
+ * A neighbourhood of >= 3 copies of ONE point (zero covariance): the normal is finite and unit -- (0, 0, 1), flipped by the
+ * view-point rule like any other --, the curvature is 0 / 0 = NaN (as the reference's eigenvalues()[0] / eigenvalues().sum()).
+ * Every row is inside the a-priori bound of DESIGN.md section 6.9 around the f64 PCA of the same list (tests/test_gpu_normals.py). */
 int cilhip_normals_knn3f(int device, const float* xyz, size_t n, int mem, size_t k, float max_sq_dist, const float* view_point,
                          float* normals_out, float* curvature_out);
 /* ...Radius (core/normal_estimation.hpp:120-162, RadiusNeighborhoodSpecification): every point with d2 < radius_sq

@@ -639,6 +639,7 @@ def transform_ransac(dst, src, samples, thresh, target_inliers, max_iter=None, r
 # ---- k-NN batch + NormalEstimation (core/kd_tree.hpp kNNSearch, core/normal_estimation.hpp) -------------
 def knn_batch(tree, queries, k, radius_sq=np.inf):
     """tree: oracle.KDTree (restatement, not the _ref one) -> (idx int64 [nq,k] -1 padded, d2 [nq,k], counts)"""
+    assert 1 <= k <= 64, "orc_knn_batch lists at most 64 neighbours per query"
     q = _c(queries).reshape(-1, 3)
     idx = np.zeros((len(q), k), np.int64); d2 = np.zeros((len(q), k), np.float32); cnt = np.zeros(len(q), np.uint32)
     lib().orc_knn_batch(tree.h, q, len(q), k, np.float32(radius_sq), idx.reshape(-1), d2.reshape(-1), cnt)
