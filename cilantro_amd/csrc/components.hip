@@ -1,0 +1,534 @@
+// components.hip -- connected-component segmentation on the device: cilantro's ConnectedComponentExtraction3f
+// (clustering/connected_component_extraction.hpp:162-265 over core/common_pair_evaluators.hpp:84-259 and
+// clustering/clustering_base.hpp:7-18), the consumer of the radius search in the reference's
+// examples/connected_component_extraction.cpp.
+//
+// The contract (DESIGN.md section 11 has it in full; every rule cites the reference lines it restates):
+//   graph     i ~ j (i != j) iff d2(i, j) < radius_sq (strict; d2 = ((dx*dx)+(dy*dy))+(dz*dz), knn.hip's d2_pinned) and the
+//             similarity clauses hold                                                   connected_component_extraction.hpp:201-204
+//   clauses   distance: d2 < max_distance                                               common_pair_evaluators.hpp:100, :159, :185, :243
+//             colours:  |c_i - c_j|^2 < fl(color_thresh * color_thresh); |v|^2 = x*x + (y*y + z*z)      :136-141
+//             normals:  angle = (float)acos((double)dot), dot = x*x' + (y*y' + z*z'); max_angle >= 0: angle <| max_angle, otherwise
+//                       min(angle, (float)M_PI - angle) <| -max_angle; <| is <= for NormalsProximityEvaluator alone (:119-121) and <
+//                       in the combined classes (:162-164, :213-215, :247-249): angle_inclusive.  dot > 1 -> NaN -> not similar.
+//   output    the connected components (only those holding a seed when a seed list is given), members in ascending index, kept iff
+//             min <= size <= max (:246-261), ordered by size descending, equal sizes by lowest member ascending;
+//             labels[i] = rank of i's segment, or the number of kept segments                clustering_base.hpp:10-11
+//   a point is never its own neighbour and an exact duplicate always is one; a point with a non-finite coordinate has no neighbours;
+//   a finite radius_sq <= 0 makes every point a singleton.
+//
+// The reference runs a serial stack flood fill per seed.  Here: a lock-free union-find over the uniform grid of grid_build.hip, no
+// neighbour list is ever written.
+//   k_cc_hook      one lane per point in grid-cell order (neighbouring lanes of a wave scan the same cells); scans the cells the ball
+//                  overlaps (the bounds of knn.hip's k_radius_pca) and, for every candidate with a SMALLER original index inside the
+//                  radius that is not already under the same root and passes the clauses, unites the two.  parent[] is over ORIGINAL
+//                  indices; a link is atomicCAS(&parent[hi], hi, lo) with hi > lo, made only on a true root.
+//   k_cc_flatten   a launch of its own: root[i] = find(i).  The larger root always goes under the smaller one, so a component's root
+//                  is its lowest original index whatever order the atomics landed in: the result is reproducible.
+//   the rest       seed marks, sizes (integer atomics, one per distinct root of a wave), keep flags, rocPRIM radix sort of
+//                  (~size, root) -> ranks, labels, and a stable rocPRIM sort of the point indices by label -> the member lists.
+// Memory model: inside k_cc_hook a load of parent[] may be stale; a stale value is the entry's former value,
+// i.e. the point itself or a former parent, and either is an ancestor-or-self in the same component, with parent[x] <= x always: find
+// may stop early but never leaves the component and always terminates; a link succeeds only through a device-scope CAS that sees the
+// entry still naming itself.  Path halving only ever replaces a non-root's parent by one of its ancestors.
+#include <hip/hip_runtime.h>
+
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "../../include/cilantro_hip/c_api.h"
+#include "internal.hpp"
+
+namespace cilhip {
+
+namespace {
+
+constexpr int CC_THREADS = 256;
+
+struct CcClauses {
+  float radius_sq;
+  int use_distance; float max_distance;
+  int use_normals; float max_angle; int angle_inclusive;
+  int use_colors; float color_thr2;      // fl(color_thresh * color_thresh), formed once on the host
+};
+
+// ---- union-find over original indices ---------------------------------------------------------------------------------------
+// CILHIP_CC_PLAIN_FIND: plain loads in find (may be served from a stale L1 / another XCD's L2 line); default: relaxed agent-scope
+// atomic loads.  CILHIP_CC_NO_HALVING: find without path halving.  (dev A/B builds: NOTEBOOK.md has what was kept and why.)
+__device__ __forceinline__ uint32_t cc_load(const uint32_t* p) {
+#ifdef CILHIP_CC_PLAIN_FIND
+  return *p;
+#else
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#endif
+}
+__device__ __forceinline__ uint32_t cc_find(uint32_t* parent, uint32_t x) {
+  uint32_t p = cc_load(parent + x);
+  while (p != x) {
+    const uint32_t gp = cc_load(parent + p);
+#ifndef CILHIP_CC_NO_HALVING
+    if (gp != p) __hip_atomic_store(parent + x, gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // x is not a root and never becomes one again
+#endif
+    x = p; p = gp;
+  }
+  return x;
+}
+// -> the root both end under, as far as this lane knows
+__device__ __forceinline__ uint32_t cc_unite(uint32_t* parent, uint32_t a, uint32_t b) {
+  for (;;) {
+    a = cc_find(parent, a); b = cc_find(parent, b);
+    if (a == b) return a;
+    const uint32_t hi = max(a, b), lo = min(a, b);
+    const uint32_t old = atomicCAS(parent + hi, hi, lo);
+    if (old == hi) return lo;
+    a = old; b = lo;      // hi had a parent already (the find stopped on a stale value, or another lane linked it first): go on from there
+  }
+}
+
+// the cells a ball can touch (never fewer): knn.hip ball_cells
+__device__ __forceinline__ void cc_ball_cells(const GridDev& g, float qx, float qy, float qz, float radius_sq, int& x0, int& x1, int& y0, int& y1, int& z0, int& z1) {
+  const float r = sqrtf(radius_sq) * 1.000001f + g.margin;
+  const float BIG = 1.0e9f;
+  x0 = max((int)floorf(fminf(fmaxf((qx - r - g.ox) * g.inv_cell, -BIG), BIG)), 0); x1 = min((int)floorf(fminf(fmaxf((qx + r - g.ox) * g.inv_cell, -BIG), BIG)), g.nx - 1);
+  y0 = max((int)floorf(fminf(fmaxf((qy - r - g.oy) * g.inv_cell, -BIG), BIG)), 0); y1 = min((int)floorf(fminf(fmaxf((qy + r - g.oy) * g.inv_cell, -BIG), BIG)), g.ny - 1);
+  z0 = max((int)floorf(fminf(fmaxf((qz - r - g.oz) * g.inv_cell, -BIG), BIG)), 0); z1 = min((int)floorf(fminf(fmaxf((qz + r - g.oz) * g.inv_cell, -BIG), BIG)), g.nz - 1);
+}
+__device__ __forceinline__ float cc_d2(float qx, float qy, float qz, float px, float py, float pz) {      // knn.hip d2_pinned
+  const float dx = __fsub_rn(qx, px), dy = __fsub_rn(qy, py), dz = __fsub_rn(qz, pz);
+  return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+}
+// x x' + (y y' + z z'), every operation rounded (grid_downsample.hip gd_dot)
+__device__ __forceinline__ float cc_dot(const F3& a, const F3& b) { return __fadd_rn(__fmul_rn(a.x, b.x), __fadd_rn(__fmul_rn(a.y, b.y), __fmul_rn(a.z, b.z))); }
+
+// the evaluator classes' operator() (common_pair_evaluators.hpp:100, :116-123, :139-141, :158-166, :184-187, :209-217, :242-251)
+__device__ __forceinline__ bool cc_similar(const CcClauses& c, const F3* __restrict__ nrm, const F3* __restrict__ rgb, uint32_t i, uint32_t j, float d2) {
+  if (c.use_distance && !(d2 < c.max_distance)) return false;
+  if (c.use_colors) {
+    const F3 a = rgb[i], b = rgb[j];
+    const F3 d{__fsub_rn(a.x, b.x), __fsub_rn(a.y, b.y), __fsub_rn(a.z, b.z)};
+    if (!(cc_dot(d, d) < c.color_thr2)) return false;
+  }
+  if (c.use_normals) {
+    const float angle = (float)acos((double)cc_dot(nrm[i], nrm[j]));      // NaN for a dot product above 1: every test below is then false
+    float v = angle, lim = c.max_angle;
+    if (!(c.max_angle >= 0.0f)) {
+      const float other = __fsub_rn((float)M_PI, angle);
+      v = other < angle ? other : angle;      // std::min
+      lim = -c.max_angle;
+    }
+    return c.angle_inclusive ? v <= lim : v < lim;
+  }
+  return true;
+}
+
+__global__ __launch_bounds__(CC_THREADS) void k_cc_init(uint32_t* __restrict__ a, size_t n) {      // a[i] = i: every point its own root
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) a[i] = (uint32_t)i;
+}
+
+// points with a non-finite coordinate become (NaN, NaN, NaN): such a record sits in the grid's first (empty) cell, is inside nobody's
+// radius (its d2 is NaN) and searches nothing itself; an infinite coordinate never reaches the grid's bounding box
+__global__ __launch_bounds__(CC_THREADS) void k_cc_clean(const F3* __restrict__ xyz, size_t n, F3* __restrict__ out, unsigned int* n_finite) {
+  unsigned int cnt = 0;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    F3 p = xyz[i];
+    if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) ++cnt;
+    else p = F3{NAN, NAN, NAN};
+    out[i] = p;
+  }
+  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
+  if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(n_finite, cnt);
+}
+
+__global__ __launch_bounds__(CC_THREADS) void k_cc_hook(GridDev g, CcClauses c, const F3* __restrict__ nrm, const F3* __restrict__ rgb, uint32_t* parent) {
+  const size_t pos = (size_t)blockIdx.x * CC_THREADS + threadIdx.x;
+  if (pos >= g.n) return;
+  const float4 q = g.pts[pos];
+  const uint32_t i = __float_as_uint(q.w);
+  if (!(fabsf(q.x) < INFINITY && fabsf(q.y) < INFINITY && fabsf(q.z) < INFINITY)) return;      // (false for NaN too)
+  int x0, x1, y0, y1, z0, z1;
+  cc_ball_cells(g, q.x, q.y, q.z, c.radius_sq, x0, x1, y0, y1, z0, z1);
+  if (x0 > x1) return;
+  uint32_t ri = i;      // an ancestor of i (its root when last looked at)
+  for (int z = z0; z <= z1; ++z)
+    for (int y = y0; y <= y1; ++y) {
+      const uint32_t row = ((uint32_t)z * (uint32_t)g.ny + (uint32_t)y) * (uint32_t)g.nx;
+      const uint32_t beg = g.cell_start[row + x0], end = g.cell_start[row + x1 + 1];
+      for (uint32_t k = beg; k < end; ++k) {
+        const float4 p = g.pts[k];
+        const uint32_t j = __float_as_uint(p.w);
+        if (j >= i) continue;      // every undirected edge once, from its larger end (and never the point itself)
+        const float d2 = cc_d2(q.x, q.y, q.z, p.x, p.y, p.z);
+        if (!(d2 < c.radius_sq)) continue;
+        ri = cc_find(parent, ri);
+        if (cc_find(parent, j) == ri) continue;      // already one component: no clause arithmetic, no gathers
+        if (!cc_similar(c, nrm, rgb, i, j, d2)) continue;
+        ri = cc_unite(parent, ri, j);
+      }
+    }
+}
+
+// the "given neighbours" overloads (connected_component_extraction.hpp:20-160): CSR lists instead of a search.  One lane per list.
+__global__ __launch_bounds__(CC_THREADS) void k_cc_hook_lists(const unsigned long long* __restrict__ offsets, const uint32_t* __restrict__ idx, const unsigned char* __restrict__ keep,
+                                                              unsigned long long n_entries, uint32_t n, unsigned int skip_first, uint32_t* parent) {
+  const size_t i = (size_t)blockIdx.x * CC_THREADS + threadIdx.x;
+  if (i >= n) return;
+  const unsigned long long end = min(offsets[i + 1], n_entries);      // (never past the arrays, whatever the offsets say)
+  const unsigned long long beg = min(offsets[i] + skip_first, end);
+  uint32_t ri = (uint32_t)i;
+  for (unsigned long long e = beg; e < end; ++e) {
+    if (keep && !keep[e]) continue;
+    const uint32_t j = idx[e];
+    if (j >= n || j == (uint32_t)i) continue;      // (the NONE padding of k-NN lists ends here)
+    ri = cc_unite(parent, ri, j);
+  }
+}
+
+__global__ __launch_bounds__(CC_THREADS) void k_cc_flatten(const uint32_t* __restrict__ parent, uint32_t* __restrict__ root, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    uint32_t x = (uint32_t)i, p = parent[x];
+    while (p != x) { x = p; p = parent[x]; }
+    root[i] = x;
+  }
+}
+
+__global__ __launch_bounds__(CC_THREADS) void k_cc_mark_seeds(const uint32_t* __restrict__ root, const uint32_t* __restrict__ seeds, size_t n_seeds, uint32_t* __restrict__ seeded) {
+  for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < n_seeds; k += (size_t)gridDim.x * blockDim.x) seeded[root[seeds[k]]] = 1u;
+}
+
+// count[r] = members of root r.  One atomic per distinct root of a wave (a cloud that is one component would otherwise send
+// every lane's add to the same word).
+__global__ __launch_bounds__(CC_THREADS) void k_cc_sizes(const uint32_t* __restrict__ root, size_t n, uint32_t* __restrict__ count) {
+  const unsigned lane = threadIdx.x & 63u;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t base = (size_t)blockIdx.x * blockDim.x; base < n; base += stride) {      // (wave-uniform trip count)
+    const size_t i = base + threadIdx.x;
+    const bool active = i < n;
+    const uint32_t r = active ? root[i] : 0u;
+    unsigned long long todo = __ballot(active);
+    while (todo) {
+      const int leader = __ffsll((long long)todo) - 1;
+      const uint32_t r0 = (uint32_t)__shfl((int)r, leader, 64);
+      const unsigned long long same = __ballot(active && r == r0) & todo;
+      if ((int)lane == leader) atomicAdd(count + r0, (uint32_t)__popcll(same));
+      todo &= ~same;
+    }
+  }
+}
+
+// key of a kept root: (~size << 32) | root -- ascending keys = size descending, equal sizes by lowest member; everything else: all ones
+__global__ __launch_bounds__(CC_THREADS) void k_cc_keys(const uint32_t* __restrict__ root, const uint32_t* __restrict__ count, const uint32_t* __restrict__ seeded, size_t n,
+                                                        unsigned long long min_size, unsigned long long max_size, unsigned long long* __restrict__ keys, unsigned int* n_kept) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t base = (size_t)blockIdx.x * blockDim.x; base < n; base += stride) {
+    const size_t i = base + threadIdx.x;
+    bool kept = false;
+    if (i < n) {
+      const uint32_t sz = count[i];
+      kept = root[i] == (uint32_t)i && (!seeded || seeded[i]) && sz >= min_size && sz <= max_size;
+      keys[i] = kept ? (((unsigned long long)(~sz) << 32) | (unsigned long long)i) : ~0ull;
+    }
+    const unsigned long long b = __ballot(kept);
+    if ((threadIdx.x & 63u) == 0 && b) atomicAdd(n_kept, (unsigned int)__popcll(b));
+  }
+}
+
+__global__ __launch_bounds__(CC_THREADS) void k_cc_rank(const unsigned long long* __restrict__ keys_sorted, uint32_t n_kept, uint32_t* __restrict__ rank) {
+  for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < n_kept; p += (size_t)gridDim.x * blockDim.x) rank[(uint32_t)keys_sorted[p]] = (uint32_t)p;
+}
+
+// rank[] holds NONE for everything that is not a kept root
+__global__ __launch_bounds__(CC_THREADS) void k_cc_labels(const uint32_t* __restrict__ root, const uint32_t* __restrict__ rank, uint32_t n_kept, size_t n, uint32_t* __restrict__ labels) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const uint32_t r = rank[root[i]];
+    labels[i] = r == NONE_U32 ? n_kept : r;
+  }
+}
+
+// offsets[k] = first sorted position of label k; offsets[n_kept] (preset to n) = the first unlabelled point's
+__global__ __launch_bounds__(CC_THREADS) void k_cc_offsets(const uint32_t* __restrict__ labels_sorted, size_t n, uint32_t* __restrict__ offsets) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const uint32_t l = labels_sorted[i];
+    if (i == 0 || labels_sorted[i - 1] != l) offsets[l] = (uint32_t)i;
+  }
+}
+
+inline int cc_blocks(size_t n) { return (int)std::min<size_t>((n + CC_THREADS - 1) / CC_THREADS, 2048) + (n == 0); }
+unsigned cc_bits(uint32_t v) {      // bits that hold 0 .. v
+  unsigned b = 1;
+  while (b < 32 && (1ull << b) <= (unsigned long long)v) ++b;
+  return b;
+}
+
+// device allocations of one call: freed on every way out
+struct CcPool {
+  std::vector<void*> p;
+  ~CcPool() { for (void* q : p) (void)hipFree(q); }
+  template <typename T>
+  hipError_t get(T** out, size_t bytes) {
+    void* q = nullptr;
+    hipError_t e = hipMalloc(&q, bytes ? bytes : 16);
+    if (e == hipSuccess) p.push_back(q);
+    *out = static_cast<T*>(q);
+    return e;
+  }
+};
+struct CcStream {
+  hipStream_t s = nullptr;
+  ~CcStream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
+};
+struct CcGrid {
+  GridBuildResult gr{};
+  bool have = false;
+  ~CcGrid() { if (have) free_grid(gr.grid); }
+};
+
+#define CC_CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_stateless_error(std::string("connected_components: ") + #x + ": " + hipGetErrorString(e_)); return CILHIP_ERR_HIP; } } while (0)
+
+struct CcOut {
+  int mem;
+  size_t n;
+  unsigned long long min_size, max_size;
+  const uint32_t* seeds;      // host array, or null: every point is a seed
+  size_t n_seeds;
+  uint32_t *labels, *offsets, *members;      // where `mem` says; offsets / members may be null
+  size_t* n_segments;
+};
+
+// everything after the hook step: parent[] (device, over original indices) -> the caller's outputs
+int cc_finish(const CcOut& o, CcPool& pool, hipStream_t s, uint32_t* parent) {
+  const size_t n = o.n;
+  const dim3 grid(cc_blocks(n)), block(CC_THREADS);
+  uint32_t *root = nullptr, *count = nullptr, *seeded = nullptr, *rank = nullptr;
+  unsigned long long *keys = nullptr, *keys_sorted = nullptr;
+  unsigned int* n_kept_d = nullptr;
+  CC_CK(pool.get(&root, n * sizeof(uint32_t)));
+  CC_CK(pool.get(&count, n * sizeof(uint32_t)));
+  CC_CK(pool.get(&keys, n * sizeof(unsigned long long)));
+  CC_CK(pool.get(&keys_sorted, n * sizeof(unsigned long long)));
+  CC_CK(pool.get(&n_kept_d, sizeof(unsigned int)));
+  hipLaunchKernelGGL(k_cc_flatten, grid, block, 0, s, (const uint32_t*)parent, root, n);
+  if (o.seeds) {
+    uint32_t* d_seeds = nullptr;
+    CC_CK(pool.get(&seeded, n * sizeof(uint32_t)));
+    CC_CK(pool.get(&d_seeds, o.n_seeds * sizeof(uint32_t)));
+    CC_CK(hipMemsetAsync(seeded, 0, n * sizeof(uint32_t), s));
+    if (o.n_seeds) {
+      CC_CK(hipMemcpyAsync(d_seeds, o.seeds, o.n_seeds * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+      hipLaunchKernelGGL(k_cc_mark_seeds, dim3(cc_blocks(o.n_seeds)), block, 0, s, (const uint32_t*)root, (const uint32_t*)d_seeds, o.n_seeds, seeded);
+    }
+  }
+  CC_CK(hipMemsetAsync(count, 0, n * sizeof(uint32_t), s));
+  CC_CK(hipMemsetAsync(n_kept_d, 0, sizeof(unsigned int), s));
+  hipLaunchKernelGGL(k_cc_sizes, grid, block, 0, s, (const uint32_t*)root, n, count);
+  hipLaunchKernelGGL(k_cc_keys, grid, block, 0, s, (const uint32_t*)root, (const uint32_t*)count, (const uint32_t*)seeded, n, o.min_size, o.max_size, keys, n_kept_d);
+  CC_CK(hipGetLastError());
+  {
+    size_t tmp_bytes = 0;
+    void* tmp = nullptr;
+    CC_CK(rocprim::radix_sort_keys(nullptr, tmp_bytes, keys, keys_sorted, n, 0u, 64u, s));
+    CC_CK(pool.get(&tmp, tmp_bytes));
+    CC_CK(rocprim::radix_sort_keys(tmp, tmp_bytes, keys, keys_sorted, n, 0u, 64u, s));
+  }
+  unsigned int n_kept = 0;      // the one host round trip of the chain
+  CC_CK(hipMemcpyAsync(&n_kept, n_kept_d, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+  CC_CK(hipStreamSynchronize(s));
+  rank = count;      // (the sizes are in the keys now)
+  CC_CK(hipMemsetAsync(rank, 0xFF, n * sizeof(uint32_t), s));
+  hipLaunchKernelGGL(k_cc_rank, dim3(cc_blocks(n_kept)), block, 0, s, (const unsigned long long*)keys_sorted, (uint32_t)n_kept, rank);
+  const bool host = o.mem == CILHIP_MEM_HOST;
+  uint32_t* d_labels = o.labels;
+  if (host) CC_CK(pool.get(&d_labels, n * sizeof(uint32_t)));
+  hipLaunchKernelGGL(k_cc_labels, grid, block, 0, s, (const uint32_t*)root, (const uint32_t*)rank, (uint32_t)n_kept, n, d_labels);
+  CC_CK(hipGetLastError());
+  if (host) CC_CK(hipMemcpyAsync(o.labels, d_labels, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  if (o.offsets || o.members) {
+    // a stable sort of the point indices by label: every segment's members in ascending index, the unlabelled points behind them
+    uint32_t *iota = root, *lab_sorted = reinterpret_cast<uint32_t*>(keys), *d_members = o.members, *d_offsets = o.offsets;      // (roots and unsorted keys are done with)
+    if (host || !d_members) CC_CK(pool.get(&d_members, n * sizeof(uint32_t)));
+    if (host || !d_offsets) CC_CK(pool.get(&d_offsets, ((size_t)n_kept + 1) * sizeof(uint32_t)));
+    hipLaunchKernelGGL(k_cc_init, grid, block, 0, s, iota, n);
+    size_t tmp_bytes = 0;
+    void* tmp = nullptr;
+    const unsigned bits = cc_bits(n_kept);
+    CC_CK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_labels, lab_sorted, iota, d_members, n, 0u, bits, s));
+    CC_CK(pool.get(&tmp, tmp_bytes));
+    CC_CK(rocprim::radix_sort_pairs(tmp, tmp_bytes, d_labels, lab_sorted, iota, d_members, n, 0u, bits, s));
+    const uint32_t n32 = (uint32_t)n;
+    CC_CK(hipMemcpyAsync(d_offsets + n_kept, &n32, sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_cc_offsets, grid, block, 0, s, (const uint32_t*)lab_sorted, n, d_offsets);
+    CC_CK(hipGetLastError());
+    if (host && o.offsets) CC_CK(hipMemcpyAsync(o.offsets, d_offsets, ((size_t)n_kept + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (host && o.members) CC_CK(hipMemcpyAsync(o.members, d_members, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  }
+  CC_CK(hipStreamSynchronize(s));
+  *o.n_segments = n_kept;
+  return CILHIP_OK;
+}
+
+int cc_open(int device, CcStream& st) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
+    set_stateless_error("connected_components: no such HIP device (the segmentation runs on the device: there is no CPU path)");
+    return CILHIP_ERR_NO_DEVICE;
+  }
+  CC_CK(hipSetDevice(device));
+  CC_CK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+  return CILHIP_OK;
+}
+
+int cc_run_fused(int device, const float* xyz, const float* nrm, const float* rgb, const CcClauses& cl, const CcOut& o) {
+  CcPool pool;
+  CcGrid grid;
+  CcStream st;      // (declared last: the stream is drained and destroyed before anything is freed)
+  if (int rc = cc_open(device, st)) return rc;
+  hipStream_t s = st.s;
+  const size_t n = o.n;
+  const F3* d_in[3] = {nullptr, nullptr, nullptr};
+  const float* src[3] = {xyz, cl.use_normals ? nrm : nullptr, cl.use_colors ? rgb : nullptr};
+  for (int k = 0; k < 3; ++k) {
+    if (!src[k]) continue;
+    if (o.mem == CILHIP_MEM_DEVICE) { d_in[k] = reinterpret_cast<const F3*>(src[k]); continue; }
+    F3* d = nullptr;
+    CC_CK(pool.get(&d, n * sizeof(F3)));
+    CC_CK(hipMemcpyAsync(d, src[k], n * sizeof(F3), hipMemcpyHostToDevice, s));
+    d_in[k] = d;
+  }
+  uint32_t* parent = nullptr;
+  CC_CK(pool.get(&parent, n * sizeof(uint32_t)));
+  hipLaunchKernelGGL(k_cc_init, dim3(cc_blocks(n)), dim3(CC_THREADS), 0, s, parent, n);
+  if (cl.radius_sq > 0.0f) {
+    F3* clean = nullptr;
+    unsigned int *d_fin = nullptr, n_finite = 0;
+    CC_CK(pool.get(&clean, n * sizeof(F3)));
+    CC_CK(pool.get(&d_fin, sizeof(unsigned int)));
+    CC_CK(hipMemsetAsync(d_fin, 0, sizeof(unsigned int), s));
+    hipLaunchKernelGGL(k_cc_clean, dim3(cc_blocks(n)), dim3(CC_THREADS), 0, s, d_in[0], n, clean, d_fin);
+    CC_CK(hipMemcpyAsync(&n_finite, d_fin, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+    CC_CK(hipStreamSynchronize(s));
+    if (n_finite > 1) {      // (otherwise nobody has a neighbour)
+      double mean[3];
+      CC_CK(build_grid(reinterpret_cast<const float*>(clean), nullptr, (uint32_t)n, s, &grid.gr, mean, 2.0));      // the radius search's grid
+      grid.have = true;
+      hipLaunchKernelGGL(k_cc_hook, dim3((unsigned)((n + CC_THREADS - 1) / CC_THREADS)), dim3(CC_THREADS), 0, s, grid.gr.grid, cl, d_in[1], d_in[2], parent);
+      CC_CK(hipGetLastError());
+    }
+  }
+  return cc_finish(o, pool, s, parent);
+}
+
+int cc_run_lists(int device, const uint64_t* offsets, const uint32_t* idx, const unsigned char* keep, size_t n_entries, int skip_first, const CcOut& o) {
+  CcPool pool;
+  CcStream st;
+  if (int rc = cc_open(device, st)) return rc;
+  hipStream_t s = st.s;
+  const size_t n = o.n;
+  const unsigned long long* d_off = reinterpret_cast<const unsigned long long*>(offsets);
+  const uint32_t* d_idx = idx;
+  const unsigned char* d_keep = keep;
+  if (o.mem == CILHIP_MEM_HOST) {
+    unsigned long long* a = nullptr; uint32_t* b = nullptr; unsigned char* c = nullptr;
+    CC_CK(pool.get(&a, (n + 1) * sizeof(unsigned long long)));
+    CC_CK(hipMemcpyAsync(a, offsets, (n + 1) * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+    CC_CK(pool.get(&b, n_entries * sizeof(uint32_t)));
+    if (n_entries) CC_CK(hipMemcpyAsync(b, idx, n_entries * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    if (keep) {
+      CC_CK(pool.get(&c, n_entries));
+      if (n_entries) CC_CK(hipMemcpyAsync(c, keep, n_entries, hipMemcpyHostToDevice, s));
+    }
+    d_off = a; d_idx = b; d_keep = c;
+  }
+  uint32_t* parent = nullptr;
+  CC_CK(pool.get(&parent, n * sizeof(uint32_t)));
+  hipLaunchKernelGGL(k_cc_init, dim3(cc_blocks(n)), dim3(CC_THREADS), 0, s, parent, n);
+  hipLaunchKernelGGL(k_cc_hook_lists, dim3((unsigned)((n + CC_THREADS - 1) / CC_THREADS)), dim3(CC_THREADS), 0, s, d_off, d_idx, d_keep, (unsigned long long)n_entries, (uint32_t)n,
+                     skip_first ? 1u : 0u, parent);
+  CC_CK(hipGetLastError());
+  return cc_finish(o, pool, s, parent);
+}
+
+int cc_refuse(const char* why) { set_stateless_error(std::string("connected_components: ") + why); return (int)CILHIP_ERR_INVALID; }
+
+// the argument rules both entries share; they hold on a machine without a device too.  0: go on, 1: answered (n == 0), < 0: refused
+int cc_check_common(size_t n, int mem, const uint32_t* seeds, size_t n_seeds, uint32_t* labels, size_t* n_segments) {
+  if (!n_segments) return cc_refuse("n_segments_out is null");
+  if ((unsigned long long)n >= (1ull << 32)) return cc_refuse("n must be below 2^32");
+  if (mem != CILHIP_MEM_HOST && mem != CILHIP_MEM_DEVICE) return cc_refuse("mem: CILHIP_MEM_HOST or CILHIP_MEM_DEVICE");
+  if (n && !labels) return cc_refuse("labels_out is null");
+  if (n_seeds && !seeds) return cc_refuse("n_seeds > 0 without a seed array");
+  for (size_t k = 0; k < n_seeds; ++k)
+    if (seeds[k] >= n) return cc_refuse("a seed index is not below n");
+  return 0;
+}
+
+}  // namespace
+
+}  // namespace cilhip
+
+extern "C" void cilhip_cc_default_params(cilhip_cc_params* p) {
+  if (!p) return;
+  *p = cilhip_cc_params{};
+  p->min_segment_size = 1;
+  p->max_segment_size = (size_t)-1;
+}
+
+extern "C" int cilhip_connected_components3f(int device, const float* xyz, const float* normals_or_null, const float* rgb_or_null, size_t n, int mem, const cilhip_cc_params* params,
+                                             const uint32_t* seeds_or_null, size_t n_seeds, uint32_t* labels_out, uint32_t* offsets_out_or_null, uint32_t* members_out_or_null,
+                                             size_t* n_segments_out) {
+  using namespace cilhip;
+  if (!params) return cc_refuse("params is null");
+  if (int rc = cc_check_common(n, mem, seeds_or_null, n_seeds, labels_out, n_segments_out)) return rc;
+  if (!std::isfinite(params->radius_sq)) return cc_refuse("radius_sq must be finite");
+  if (params->use_normals && !normals_or_null) return cc_refuse("a normals clause without the normals array");
+  if (params->use_colors && !rgb_or_null) return cc_refuse("a colours clause without the colours array");
+  if (n && !xyz) return cc_refuse("points is null");
+  set_stateless_error("");
+  if (n == 0) {      // (without touching a device)
+    *n_segments_out = 0;
+    if (offsets_out_or_null && mem == CILHIP_MEM_HOST) offsets_out_or_null[0] = 0;
+    return CILHIP_OK;
+  }
+  CcClauses cl{};
+  cl.radius_sq = params->radius_sq;
+  cl.use_distance = params->use_distance != 0; cl.max_distance = params->max_distance;
+  cl.use_normals = params->use_normals != 0; cl.max_angle = params->max_angle; cl.angle_inclusive = params->angle_inclusive != 0;
+  cl.use_colors = params->use_colors != 0; cl.color_thr2 = params->color_thresh * params->color_thresh;
+  const CcOut o{mem, n, (unsigned long long)params->min_segment_size, (unsigned long long)params->max_segment_size, seeds_or_null, n_seeds,
+                labels_out, offsets_out_or_null, members_out_or_null, n_segments_out};
+  try {
+    return cc_run_fused(device, xyz, normals_or_null, rgb_or_null, cl, o);
+  } catch (...) {      // (out of host memory: never across the C boundary)
+    set_stateless_error("connected_components: out of host memory");
+    return CILHIP_ERR_HIP;
+  }
+}
+
+extern "C" int cilhip_connected_components_lists(int device, size_t n, const uint64_t* offsets, const uint32_t* idx, const unsigned char* keep_or_null, size_t n_entries,
+                                                 int skip_first, int symmetric, int mem, size_t min_segment_size, size_t max_segment_size, const uint32_t* seeds_or_null,
+                                                 size_t n_seeds, uint32_t* labels_out, uint32_t* offsets_out_or_null, uint32_t* members_out_or_null, size_t* n_segments_out) {
+  using namespace cilhip;
+  if (int rc = cc_check_common(n, mem, seeds_or_null, n_seeds, labels_out, n_segments_out)) return rc;
+  if (n && !offsets) return cc_refuse("offsets is null");
+  if (n_entries && !idx) return cc_refuse("idx is null");
+  if (seeds_or_null && !symmetric) {
+    set_stateless_error("connected_components: a seed list over directed lists (the reference's result then depends on its traversal order): pass symmetric lists or no seeds");
+    return CILHIP_ERR_UNSUPPORTED;
+  }
+  set_stateless_error("");
+  if (n == 0) {
+    *n_segments_out = 0;
+    if (offsets_out_or_null && mem == CILHIP_MEM_HOST) offsets_out_or_null[0] = 0;
+    return CILHIP_OK;
+  }
+  const CcOut o{mem, n, (unsigned long long)min_segment_size, (unsigned long long)max_segment_size, seeds_or_null, n_seeds, labels_out, offsets_out_or_null, members_out_or_null,
+                n_segments_out};
+  try {
+    return cc_run_lists(device, offsets, idx, keep_or_null, n_entries, skip_first, o);
+  } catch (...) {
+    set_stateless_error("connected_components: out of host memory");
+    return CILHIP_ERR_HIP;
+  }
+}

@@ -476,6 +476,7 @@ int gd_run(const GdCall& c, int device) {
 }  // namespace
 
 const char* stateless_last_error() { return g_gd_err.empty() ? "null context" : g_gd_err.c_str(); }
+void set_stateless_error(const std::string& what) { g_gd_err = what; }
 
 }  // namespace cilhip
 

@@ -498,6 +498,7 @@ hipError_t mean3_device(const float* d_xyz, uint32_t n, hipStream_t s, double me
 
 // grid_downsample.hip: what the calling thread's last stateless call refused, for cilhip_last_error(NULL) ("null context" when nothing)
 const char* stateless_last_error();
+void set_stateless_error(const std::string& what);      // (components.hip: the same slot; "" clears it)
 
 // c_api.hip <-> multi.hip
 hipStream_t ctx_stream(const ::cilhip_ctx* c);

@@ -462,6 +462,63 @@ int cilhip_grid_downsample3f(int device, const float* xyz, const float* normals_
                              float bin_size, size_t min_points_in_bin, int bin_order, float* xyz_out, float* normals_out, float* rgb_out,
                              uint32_t* counts_out_or_null, size_t capacity, size_t* n_out);
 
+/* ---- connected-component segmentation ------------------------------------------------------------------------- */
+/* ConnectedComponentExtraction<float,3>::segment with a RadiusNeighborhoodSpecification
+ * (clustering/connected_component_extraction.hpp:162-265, :394-422) and the proximity evaluators of
+ * core/common_pair_evaluators.hpp:84-259; labels as clustering/clustering_base.hpp:7-18.  DESIGN.md section 11 is the long form.
+ *   Graph: points i != j are joined iff d2(i, j) < radius_sq (strict; d2 = ((dx*dx)+(dy*dy))+(dz*dz) in f32, the engine's pinned
+ *   form) and every selected clause holds (connected_component_extraction.hpp:201-204).  Both conditions are symmetric: the
+ *   result does not depend on any traversal order.
+ *   Clauses (selected independently; the reference's eight evaluator classes are their combinations, AlwaysTrueEvaluator is none):
+ *     use_distance: d2 < max_distance                                                        (:100, :159, :185, :243)
+ *     use_colors:   |c_i - c_j|^2 < color_thresh * color_thresh (the product formed once in f32; differences in f32;
+ *                   |v|^2 = x*x + (y*y + z*z), every operation rounded, no FMA)              (:136-141)
+ *     use_normals:  dot = x*x' + (y*y' + z*z') (same rounding; not checked against a compiled reference, Eigen being absent where
+ *                   this was written); angle = (float)acos((double)dot); max_angle >= 0: angle <| max_angle, otherwise
+ *                   min(angle, (float)M_PI - angle) <| -max_angle, the subtraction in f32.  <| is <= when angle_inclusive != 0
+ *                   (NormalsProximityEvaluator, :119-121) and < otherwise (every combined evaluator, :162-164, :213-215,
+ *                   :247-249).  A dot product that rounds above 1 gives acos = NaN: the pair is NOT similar, as in the reference
+ *                   (two identical, slightly over-long normals are not joined; nothing is clamped).
+ *   Output: the connected components -- with a seed list only those that contain a seed -- each with its members in ascending
+ *   index; kept iff min_segment_size <= size <= max_segment_size (:246-261: a segment past the maximum is dropped whole);
+ *   ordered by size, descending, equal sizes by lowest member index ascending (the reference leaves equal sizes to std::sort; this
+ *   is what a stable sort of its list gives with all seeds).  labels_out[i] = the rank of i's segment, or *n_segments_out for a
+ *   point in no kept segment (clustering_base.hpp:10-11).  offsets_out_or_null[0 .. *n_segments_out] / members_out_or_null: the
+ *   segments as CSR lists; members_out[offsets_out[*n_segments_out] .. n) are the unlabelled points, ascending.
+ *   Deviations: the reference skips the first entry of every neighbour list, taking it for the point itself (:202); here a point
+ *   is never its own neighbour and an exact duplicate always is one (identical on clouds without duplicates).  A point with a
+ *   non-finite coordinate has no neighbours: a component of size 1.  A finite radius_sq <= 0: every point is a singleton.
+ * mem says where xyz / normals / rgb and the three output arrays live; seeds_or_null is always a HOST array (NULL: every point
+ * is a seed; non-NULL with n_seeds == 0: no segment), n_segments_out a host word.  Output sizes that always suffice: labels n,
+ * offsets n + 1, members n.
+ * CILHIP_ERR_INVALID, before the device is opened, nothing written, cilhip_last_error(NULL) naming the rule: a normals or
+ * colours clause without its array; a seed index >= n; n >= 2^32; unknown mem; radius_sq not finite; NULL params / xyz / labels
+ * / n_segments_out.  n == 0: CILHIP_OK, zero segments, no device needed. */
+typedef struct cilhip_cc_params {
+  float radius_sq;
+  int use_distance; float max_distance;
+  int use_normals; float max_angle; int angle_inclusive;
+  int use_colors; float color_thresh;
+  size_t min_segment_size, max_segment_size;
+} cilhip_cc_params;
+/* no clause, radius_sq = 0, min_segment_size = 1, max_segment_size = SIZE_MAX (:168-169) */
+void cilhip_cc_default_params(cilhip_cc_params* params);
+int cilhip_connected_components3f(int device, const float* xyz, const float* normals_or_null, const float* rgb_or_null, size_t n, int mem,
+                                  const cilhip_cc_params* params, const uint32_t* seeds_or_null, size_t n_seeds, uint32_t* labels_out,
+                                  uint32_t* offsets_out_or_null, uint32_t* members_out_or_null, size_t* n_segments_out);
+/* The "given neighbours" overloads (connected_component_extraction.hpp:20-160) over CSR lists: list i is
+ * idx[offsets[i] .. offsets[i + 1]) (offsets: n + 1 words, as cilhip_radius_search3f returns them; rows of cilhip_knn3f: offsets[i]
+ * = i * k), n_entries the length of idx (nothing past it is read; entries >= n, the k-NN rows' padding among them, are no
+ * neighbours).  keep_or_null: one byte per entry, 0 = the caller's own evaluator refused the pair.  skip_first != 0 drops entry 0
+ * of every list, as :55 does.  Lists may be directed (k-NN lists are): the result is the WEAKLY connected components -- what the
+ * reference computes with all seeds, where every edge either spreads a label or records a merge.  With a seed list the reference's
+ * result over directed lists depends on its traversal order: symmetric == 0 together with seeds_or_null is CILHIP_ERR_UNSUPPORTED.
+ * Everything after the edges (sizes, limits, order, labels, outputs, seeds, mem, errors) is shared with the entry above. */
+int cilhip_connected_components_lists(int device, size_t n, const uint64_t* offsets, const uint32_t* idx, const unsigned char* keep_or_null,
+                                      size_t n_entries, int skip_first, int symmetric, int mem, size_t min_segment_size, size_t max_segment_size,
+                                      const uint32_t* seeds_or_null, size_t n_seeds, uint32_t* labels_out, uint32_t* offsets_out_or_null,
+                                      uint32_t* members_out_or_null, size_t* n_segments_out);
+
 /* ---- introspection (bench / tests) ----------------------------------------------------------- */
 typedef struct {
   int nx, ny, nz;        /* grid dims */

@@ -7,10 +7,12 @@
 // uchar in the file and floats in [0,1] in memory (point_cloud.hpp:513, :535).  Reads ascii and
 // binary_little_endian files with any scalar property types; other elements (faces ...) are skipped.
 // The clouds feed the engine as non-owning views:  ConstPointsView(cloud.points), ConstPointsView(cloud.normals).
+//   utilities/point_cloud.hpp:201-245             removeInvalidPoints / Normals / Colors / Data: host compaction, in the order the reference's remove() (:154-198) leaves
 //   utilities/point_cloud.hpp:247-290             gridDownsample / gridDownsampled (on the device: grid_downsampler.hpp); member
 //                                                 templates as in the reference, so a program that never calls them links without the library
 #pragma once
 
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
@@ -37,6 +39,12 @@ public:
   bool isEmpty() const { return points.empty(); }
   bool hasNormals() const { return size() > 0 && normals.size() == points.size(); }   // point_cloud.hpp:139-141
   bool hasColors() const { return size() > 0 && colors.size() == points.size(); }
+
+  // point_cloud.hpp:201-245: rows with a non-finite entry in the named attribute(s) leave the cloud, from every attribute it has
+  PointCloud3f& removeInvalidPoints() { return removeRows(true, false, false); }
+  PointCloud3f& removeInvalidNormals() { return hasNormals() ? removeRows(false, true, false) : *this; }
+  PointCloud3f& removeInvalidColors() { return hasColors() ? removeRows(false, false, true) : *this; }
+  PointCloud3f& removeInvalidData() { return removeRows(true, hasNormals(), hasColors()); }
 
   // point_cloud.hpp:247-266: the variant follows from the attributes the cloud has
   template <typename GridPointScalarT = std::ptrdiff_t>
@@ -180,6 +188,36 @@ public:
   }
 
 private:
+  static bool finite3(const std::vector<float>& v, size_t i) { return std::isfinite(v[3 * i]) && std::isfinite(v[3 * i + 1]) && std::isfinite(v[3 * i + 2]); }
+  PointCloud3f& removeRows(bool by_points, bool by_normals, bool by_colors) {
+    const bool has_n = hasNormals(), has_c = hasColors();
+    const size_t n = size();
+    std::vector<char> bad(n, 0);
+    size_t n_bad = 0;
+    for (size_t i = 0; i < n; ++i) {
+      bad[i] = (by_points && !finite3(points, i)) || (by_normals && !finite3(normals, i)) || (by_colors && !finite3(colors, i));
+      n_bad += bad[i];
+    }
+    if (n_bad == 0) return *this;
+    if (n_bad == n) { points.clear(); normals.clear(); colors.clear(); return *this; }
+    // as remove() does (:164-186): every hole, in ascending order, takes the last row that stays; the rest keeps its place
+    size_t last = n - 1;
+    while (bad[last]) --last;
+    for (size_t i = 0; i < last; ++i) {
+      if (!bad[i]) continue;
+      for (int k = 0; k < 3; ++k) {
+        points[3 * i + k] = points[3 * last + k];
+        if (has_n) normals[3 * i + k] = normals[3 * last + k];
+        if (has_c) colors[3 * i + k] = colors[3 * last + k];
+      }
+      --last;
+      while (i < last && bad[last]) --last;
+    }
+    points.resize(3 * (last + 1));
+    if (has_n) normals.resize(3 * (last + 1));
+    if (has_c) colors.resize(3 * (last + 1));
+    return *this;
+  }
   static std::string strip(const std::string& s) {
     size_t a = 0, b = s.size();
     while (a < b && (s[a] == ' ' || s[a] == '\t' || s[a] == '\r')) ++a;
