@@ -156,7 +156,8 @@ __device__ __forceinline__ void reverse_search_point(const GridDev& sg, const fl
     const float gy = fmaxf(fmaxf(sg.oy - sy, sy - (sg.oy + (float)sg.ny * sg.cell)) - sg.margin, 0.0f);
     const float gz = fmaxf(fmaxf(sg.oz - sz, sz - (sg.oz + (float)sg.nz * sg.cell)) - sg.margin, 0.0f);
     const float lb = mapped_bound(sqrtf(gx * gx + gy * gy + gz * gz), iv);
-    if (lb * lb * KS >= max_sq) { rev_pos[jd] = NONE_U32; rev_d2[jd] = max_sq; return; }
+    // (a target point with a non-finite coordinate, or a transform with one: T^-1 p is not a place, nothing to find)
+    if (!query_is_finite(sx, sy, sz) || lb * lb * KS >= max_sq) { rev_pos[jd] = NONE_U32; rev_d2[jd] = max_sq; return; }
   }
   int s = max(0, max(max(-cx, cx - (sg.nx - 1)), max(max(-cy, cy - (sg.ny - 1)), max(-cz, cz - (sg.nz - 1)))));   // first shell that reaches the grid
   for (;; ++s) {

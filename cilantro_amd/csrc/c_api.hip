@@ -421,6 +421,7 @@ int cilhip_set_target(cilhip_ctx* c, const float* xyz, const float* nrm, size_t 
   hipError_t e = build_grid(d_xyz, d_nrm, (uint32_t)n, c->stream, &r, mean, c->cell_occupancy, c->refined_occupancy);
   (void)hipFree(d_xyz);
   if (d_nrm) (void)hipFree(d_nrm);
+  if (e == GRID_RANGE_ERROR) { c->err = std::string("set_target: ") + kGridRangeMessage; return CILHIP_ERR_UNSUPPORTED; }
   if (e != hipSuccess) { c->err = std::string("build_grid: ") + hipGetErrorString(e); return CILHIP_ERR_HIP; }
   c->grid = r.grid; c->grid_occ = r.avg_occupancy; c->grid_cells = r.n_cells;
   c->policy.warm_banned = false;
@@ -997,6 +998,7 @@ static int ensure_src_grid(cilhip_ctx* c) {
     // (its per-point attribute = the feature vectors a 6-D reverse search compares by: normals or colours)
     const float* attr = c->feature_kind == 1 ? c->d_src_rgb : c->d_src_nrm;
     const hipError_t eg = build_grid(c->d_src_xyz, attr, c->ns, c->stream, &r, mean, 1.0);
+    if (eg == GRID_RANGE_ERROR) { c->err = std::string("source grid: ") + kGridRangeMessage; return CILHIP_ERR_UNSUPPORTED; }
     if (eg != hipSuccess) { c->err = std::string("build_grid (source): ") + hipGetErrorString(eg); return CILHIP_ERR_HIP; }
     c->src_grid = r.grid; c->has_src_grid = true;
   }
@@ -1050,6 +1052,7 @@ int cilhip::run_pair_search(cilhip_ctx* c, const IterArgs& a, float max_sq, cons
   const hipError_t e = find_pairs(rf, c->grid, c->src_grid, c->d_src_xyz, (c->d_src_nrm && c->symmetric) ? c->d_src_nrm : nullptr, c->d_src_sorted, c->ns, c->d_state,
                                   c->d_state_id, T_host, max_sq, c->search_dir, c->reciprocal, c->inlier_fraction, c->one_to_one, c->d_nn_pos, c->d_nn_d2,
                                   c->pairs, c->stream, &rt);
+  if (e == GRID_RANGE_ERROR) { c->err = std::string("find_pairs (grid over the transformed source): ") + kGridRangeMessage; return CILHIP_ERR_UNSUPPORTED; }
   if (e != hipSuccess) { c->err = std::string("find_pairs: ") + hipGetErrorString(e); return CILHIP_ERR_HIP; }
   return CILHIP_OK;
 }

@@ -21,6 +21,7 @@
 #include <cmath>
 #include <vector>
 
+#include "grid_policy.hpp"
 #include "internal.hpp"
 
 namespace cilhip {
@@ -29,7 +30,8 @@ namespace cilhip {
 
 constexpr int RB = 1024;  // reduction blocks
 
-// per-block min/max (f32) and sum (f64) of xyz
+// per-block min/max (f32) over the FINITE coordinates and sum (f64) of all of them: the box is what the grid is laid over (a depth
+// sensor's NaN / +-inf points have no cell), the mean stays the IEEE one (NaN or inf for such a cloud, as the reference's dst_mean_)
 __global__ __launch_bounds__(256) void k_bbox_sum(const float* __restrict__ xyz, uint32_t n, float* bmin, float* bmax, double* bsum) {
   float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
   double sm[3] = {0, 0, 0};
@@ -39,7 +41,8 @@ __global__ __launch_bounds__(256) void k_bbox_sum(const float* __restrict__ xyz,
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const float v = xyz[3 * (size_t)i + c];
-      mn[c] = fminf(mn[c], v); mx[c] = fmaxf(mx[c], v); sm[c] += (double)v;
+      if (fabsf(v) < INFINITY) { mn[c] = fminf(mn[c], v); mx[c] = fmaxf(mx[c], v); }
+      sm[c] += (double)v;
     }
   }
   __shared__ float smn[4][3], smx[4][3];
@@ -92,10 +95,11 @@ hipError_t mean3_device(const float* d_xyz, uint32_t n, hipStream_t s, double me
   return e;
 }
 
+// A point with a non-finite coordinate has no cell: key g.nx * g.ny * g.nz, one past the last cell.  It sorts behind every cell's points
+// (its record keeps its index at the tail of GridDev::pts) and no cell range holds it, so no search ever meets it as a candidate.
 __device__ __forceinline__ uint32_t cell_of(const GridDev& g, float x, float y, float z) {
-  int cx = (int)floorf(fminf(fmaxf((x - g.ox) * g.inv_cell, -1.0f), 1.0e9f));
-  int cy = (int)floorf(fminf(fmaxf((y - g.oy) * g.inv_cell, -1.0f), 1.0e9f));
-  int cz = (int)floorf(fminf(fmaxf((z - g.oz) * g.inv_cell, -1.0f), 1.0e9f));
+  if (!(fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY)) return (uint32_t)g.nx * (uint32_t)g.ny * (uint32_t)g.nz;
+  int cx = grid_cell_coord(x, g.ox, g.inv_cell), cy = grid_cell_coord(y, g.oy, g.inv_cell), cz = grid_cell_coord(z, g.oz, g.inv_cell);
   cx = min(max(cx, 0), g.nx - 1); cy = min(max(cy, 0), g.ny - 1); cz = min(max(cz, 0), g.nz - 1);
   return ((uint32_t)cz * (uint32_t)g.ny + (uint32_t)cy) * (uint32_t)g.nx + (uint32_t)cx;
 }
@@ -134,9 +138,9 @@ __global__ void k_cell_start(const uint32_t* __restrict__ keys_sorted, uint32_t 
 __global__ void k_run_starts(const uint32_t* __restrict__ keys_sorted, uint32_t n, uint32_t ncells, uint32_t* cell_start) {
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     const uint32_t k = keys_sorted[i];
-    if (i == 0 || keys_sorted[i - 1] != k) cell_start[k] = i;
+    if (i == 0 || keys_sorted[i - 1] != k) cell_start[k] = i;      // (key ncells: the points without a cell -- the table ends where they begin)
   }
-  if (blockIdx.x == 0 && threadIdx.x == 0) cell_start[ncells] = n;
+  if (blockIdx.x == 0 && threadIdx.x == 0 && (n == 0 || keys_sorted[n - 1] != ncells)) cell_start[ncells] = n;
 }
 static inline int grid_blocks(uint32_t n);
 static hipError_t cell_start_table(const uint32_t* keys_sorted, uint32_t n, uint32_t ncells, uint32_t* cell_start, hipStream_t s) {
@@ -192,29 +196,14 @@ static unsigned bits_for(uint32_t ncells) {
   return b;
 }
 
-static void set_dims(GridDev& g, const float lo[3], const float hi[3], double cell) {
-  const int MAXD = 2048;
-  const double MAXCELLS = 67108864.0;  // 2^26
-  double ext[3] = {(double)hi[0] - lo[0], (double)hi[1] - lo[1], (double)hi[2] - lo[2]};
-  double maxext = std::max(ext[0], std::max(ext[1], ext[2]));
-  if (!(maxext > 0.0) || !std::isfinite(maxext)) maxext = 1.0;
-  if (!(cell > 0.0) || !std::isfinite(cell)) cell = maxext;
-  cell = std::max(cell, maxext / (MAXD - 1));
-  // GRID_PAD layers of (empty) cells around the data: every cell that can hold a target point (and the first layer
-  // around them) has all 26 neighbours inside the grid, so the fast search path needs no boundary cases (queries in
-  // the outermost layer or beyond take the generic path).
-  for (;;) {
-    double nxd = std::floor(ext[0] / cell) + 1 + 2 * GRID_PAD, nyd = std::floor(ext[1] / cell) + 1 + 2 * GRID_PAD, nzd = std::floor(ext[2] / cell) + 1 + 2 * GRID_PAD;
-    if (nxd * nyd * nzd <= MAXCELLS && nxd <= MAXD && nyd <= MAXD && nzd <= MAXD) {
-      g.nx = (int)nxd; g.ny = (int)nyd; g.nz = (int)nzd;
-      break;
-    }
-    cell *= 1.1;
-  }
-  g.cell = (float)cell;
-  g.ox = lo[0] - (float)GRID_PAD * g.cell; g.oy = lo[1] - (float)GRID_PAD * g.cell; g.oz = lo[2] - (float)GRID_PAD * g.cell;
-  g.inv_cell = 1.0f / g.cell;
-  g.margin = g.cell * (1.0f / 512.0f);
+// grid_policy.hpp decides the shape; false: the cloud's coordinates leave the range an f32 grid can index (GRID_POLICY_RANGE)
+static bool set_dims(GridDev& g, const float lo[3], const float hi[3], double cell) {
+  GridShape sh{};
+  if (grid_set_dims(sh, lo, hi, cell) != GRID_POLICY_OK) return false;
+  g.nx = sh.nx; g.ny = sh.ny; g.nz = sh.nz;
+  g.cell = sh.cell; g.inv_cell = sh.inv_cell; g.margin = sh.margin;
+  g.ox = sh.ox; g.oy = sh.oy; g.oz = sh.oz;
+  return true;
 }
 
 hipError_t build_grid(const float* d_xyz, const float* d_nrm, uint32_t n, hipStream_t s, GridBuildResult* out, double mean_out[3],
@@ -225,7 +214,7 @@ hipError_t build_grid(const float* d_xyz, const float* d_nrm, uint32_t n, hipStr
   if (n == 0) {
     // empty target: a minimal grid of empty cells; every search returns "none" (kd_tree_utilities.hpp:16-19)
     const float z3[3] = {0, 0, 0};
-    set_dims(g, z3, z3, 1.0);
+    (void)set_dims(g, z3, z3, 1.0);
     const size_t nc = (size_t)g.nx * g.ny * g.nz;
     uint32_t* cs = nullptr;
     HIP_TRY(hipMalloc(&cs, (nc + 1) * sizeof(uint32_t)));
@@ -238,14 +227,14 @@ hipError_t build_grid(const float* d_xyz, const float* d_nrm, uint32_t n, hipStr
     return hipSuccess;
   }
   float lo[3], hi[3];
-  HIP_TRY(bbox_mean(d_xyz, n, s, lo, hi, mean_out));
-  double ext[3] = {(double)hi[0] - lo[0], (double)hi[1] - lo[1], (double)hi[2] - lo[2]};
-  const double maxext = std::max(ext[0], std::max(ext[1], ext[2]));
-  // volume with degenerate extents floored so planar / linear clouds still get a sane first guess
-  double vol = 1.0;
-  for (int c = 0; c < 3; ++c) vol *= std::max(ext[c], maxext * 1e-3);
+  {
+    float lo_raw[3], hi_raw[3];
+    HIP_TRY(bbox_mean(d_xyz, n, s, lo_raw, hi_raw, mean_out));
+    grid_clean_box(lo_raw, hi_raw, lo, hi);      // an axis without a finite coordinate: extent 0 at origin 0
+  }
   const double TARGET = target_occupancy > 0.0 ? target_occupancy : 1.0;  // points per cell for a volumetric cloud
-  double cell = std::cbrt(vol * TARGET / (double)n);
+  double cell = grid_first_cell(lo, hi, n, TARGET);
+  if (!set_dims(g, lo, hi, cell)) return GRID_RANGE_ERROR;      // (before anything is allocated)
 
   uint32_t *k_in = nullptr, *k_out = nullptr, *v_in = nullptr, *v_out = nullptr, *cs = nullptr;
   double* d_occ = nullptr;
@@ -255,12 +244,12 @@ hipError_t build_grid(const float* d_xyz, const float* d_nrm, uint32_t n, hipStr
   double occ = 0.0;
   size_t ncells = 0;
   for (int attempt = 0; attempt < 8; ++attempt) {
-    set_dims(g, lo, hi, cell);
+    (void)set_dims(g, lo, hi, cell);      // (cannot fail where the first guess did not: the range test does not depend on a smaller cell)
     ncells = (size_t)g.nx * g.ny * g.nz;
     if (cs) { (void)hipFree(cs); cs = nullptr; }
     HIP_TRY(hipMalloc(&cs, (ncells + 1) * sizeof(uint32_t)));
     hipLaunchKernelGGL(k_cell_keys, dim3(grid_blocks(n)), dim3(256), 0, s, d_xyz, n, g, k_in, v_in);
-    HIP_TRY(sort_pairs(k_in, k_out, v_in, v_out, n, bits_for((uint32_t)ncells), s));
+    HIP_TRY(sort_pairs(k_in, k_out, v_in, v_out, n, bits_for((uint32_t)ncells + 1u), s));      // (+ 1: the key of the points without a cell)
     HIP_TRY(cell_start_table(k_out, n, (uint32_t)ncells, cs, s));
     HIP_TRY(hipMemsetAsync(d_occ, 0, sizeof(double), s));
     hipLaunchKernelGGL(k_occupancy, dim3(grid_blocks((uint32_t)ncells)), dim3(256), 0, s, cs, (uint32_t)ncells, d_occ);
@@ -277,7 +266,7 @@ hipError_t build_grid(const float* d_xyz, const float* d_nrm, uint32_t n, hipStr
     const double shrink = std::min(0.85, std::max(0.3, std::pow(2.0 * TARGET * RF / occ, 1.0 / 2.5)));
     const double new_cell = (double)g.cell * shrink;
     GridDev probe = g;
-    set_dims(probe, lo, hi, new_cell);
+    if (!set_dims(probe, lo, hi, new_cell)) break;
     if (probe.cell >= g.cell * 0.97f) break;  // dims / cell-count caps reached: keep the current grid
     cell = new_cell;
   }
@@ -306,9 +295,7 @@ void free_grid(GridDev& g) {
 // the LDS-tiled search kernel: the octant blocks of a cube's queries fit a (CUBE_EDGE+2..3)^3-cell region that
 // one workgroup stages in LDS once.
 __device__ __forceinline__ uint32_t cube_key_of(const GridDev& g, float x, float y, float z) {
-  int cx = (int)floorf(fminf(fmaxf((x - g.ox) * g.inv_cell, -1.0f), 1.0e9f));
-  int cy = (int)floorf(fminf(fmaxf((y - g.oy) * g.inv_cell, -1.0f), 1.0e9f));
-  int cz = (int)floorf(fminf(fmaxf((z - g.oz) * g.inv_cell, -1.0f), 1.0e9f));
+  int cx = grid_cell_coord(x, g.ox, g.inv_cell), cy = grid_cell_coord(y, g.oy, g.inv_cell), cz = grid_cell_coord(z, g.oz, g.inv_cell);
   // cubes tile the DATA cells GRID_PAD..n-1-GRID_PAD (the outer layers hold no target points): shift by the padding,
   // so a cloud registered onto itself fills whole cubes; queries in the low outer layers join cube 0
   cx = min(max(cx - GRID_PAD, 0), g.nx - 1 - GRID_PAD); cy = min(max(cy - GRID_PAD, 0), g.ny - 1 - GRID_PAD); cz = min(max(cz - GRID_PAD, 0), g.nz - 1 - GRID_PAD);

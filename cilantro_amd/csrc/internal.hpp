@@ -7,6 +7,7 @@
 #include <string>
 #include <thread>
 
+#include "grid_policy.hpp"
 #include "solve.hpp"
 
 struct cilhip_ctx;      // (c_api.h: the opaque context)
@@ -19,10 +20,7 @@ constexpr uint32_t NONE_U32 = 0xFFFFFFFFu;
 #endif
 // LDS-tiled search: queries are grouped by cubes of CUBE_EDGE^3 target-grid cells
 constexpr int CUBE_EDGE = CILHIP_CUBE_EDGE;
-// Layers of empty cells around the data's bounding box.  Two: queries up to one cell outside the data (source points
-// that noise / the current transform pushed just past the target's bounding box) still have all 26 neighbour cells
-// inside the grid and stay on the fast search path.
-constexpr int GRID_PAD = 2;
+// (GRID_PAD, the layers of empty cells around the data's bounding box: grid_policy.hpp)
 #ifndef CILHIP_TILE_THREADS
 #define CILHIP_TILE_THREADS 1024
 #endif
@@ -480,6 +478,11 @@ struct GridBuildResult {
 // arrays and the cell table (freed by free_grid).  Returns hipSuccess or an error.
 // refined_factor: a cloud whose density-based first guess leaves far too many points per cell (a surface, clusters) is refined until
 // the expected own-cell population is at most 3 x target x refined_factor (1: as dense a grid as for a volumetric cloud).
+// GRID_RANGE_ERROR: a finite cloud whose coordinates leave the range an f32 grid can index (grid_policy.hpp: GRID_POLICY_RANGE; nothing
+// was allocated) -- the C entry points report CILHIP_ERR_UNSUPPORTED with kGridRangeMessage, not a HIP failure.
+// Points with a non-finite coordinate keep their records at the tail of GridDev::pts (behind cell_start[n_cells]) and are in no cell.
+constexpr hipError_t GRID_RANGE_ERROR = hipErrorInvalidPitchValue;      // (a value none of build_grid's runtime calls returns)
+constexpr const char* kGridRangeMessage = "the cloud's finite coordinates span more than a single-precision grid can index (|coordinate| + 4 * extent must stay below FLT_MAX)";
 hipError_t build_grid(const float* d_xyz, const float* d_nrm, uint32_t n, hipStream_t s,
                       GridBuildResult* out, double mean_out[3], double target_occupancy, double refined_factor = 1.0);
 void free_grid(GridDev& g);

@@ -859,7 +859,7 @@ __global__ __launch_bounds__(TILE_THREADS, CILHIP_TILE_WAVES_PER_SIMD) void k_se
         const float gx = axis_gap(oq[u].qx, g.ox, g.ox + (float)g.nx * g.cell, g.margin);
         const float gy = axis_gap(oq[u].qy, g.oy, g.oy + (float)g.ny * g.cell, g.margin);
         const float gz = axis_gap(oq[u].qz, g.oz, g.oz + (float)g.nz * g.cell, g.margin);
-        defer = (gx * gx + gy * gy + gz * gz) * KSHRINK < a.max_sq;
+        defer = query_is_finite(oq[u].qx, oq[u].qy, oq[u].qz) && (gx * gx + gy * gy + gz * gz) * KSHRINK < a.max_sq;      // (a NaN query's gaps read 0: it finds nothing, no clean-up)
         const float ggap = __fsqrt_rn((gx * gx + gy * gy + gz * gz) * KSHRINK) * 0.999999f;      // every target point lies inside the grid
         if (LB && ACC == IM_NONE) mkey = margin_key(false, INFINITY, ggap, mref);
         if (LB && ACC != IM_NONE) mq = margin_q15(false, INFINITY, ggap, mref, g.inv_cell);

@@ -426,7 +426,11 @@ int knn_impl(int device, const float* ref_xyz, size_t n_ref, const float* query_
     }
     double mean[3];
     // ~k/4 points per cell: the k-th neighbour then normally lies inside the 3x3x3 block of cells
-    KN_CK(build_grid(d_ref, nullptr, (uint32_t)n_ref, s, &gr, mean, std::max(1.0, (double)k / 4.0)));   // (radius-only: 1 point per cell)
+    {
+      const hipError_t eg = build_grid(d_ref, nullptr, (uint32_t)n_ref, s, &gr, mean, std::max(1.0, (double)k / 4.0));
+      if (eg == GRID_RANGE_ERROR) { set_stateless_error(std::string("grid: ") + kGridRangeMessage); rc = CILHIP_ERR_UNSUPPORTED; goto done; }
+      KN_CK(eg);
+    }   // (radius-only: 1 point per cell)
     have_grid = true;
     // queries in target-grid cell order (identity transform)
     KN_CK(hipMalloc(&d_qs, n_query * sizeof(float4)));
@@ -616,7 +620,11 @@ int radius_impl(int device, const float* ref_xyz, size_t n_ref, const float* que
       }
     }
     double mean[3];
-    KN_CK(build_grid(d_ref, nullptr, (uint32_t)n_ref, s, &gr, mean, 2.0));
+    {
+      const hipError_t eg = build_grid(d_ref, nullptr, (uint32_t)n_ref, s, &gr, mean, 2.0);
+      if (eg == GRID_RANGE_ERROR) { set_stateless_error(std::string("grid: ") + kGridRangeMessage); rc = CILHIP_ERR_UNSUPPORTED; goto done; }
+      KN_CK(eg);
+    }
     have_grid = true;
     KN_CK(hipMalloc(&d_qs, n_query * sizeof(float4)));
     {

@@ -115,6 +115,13 @@ __device__ __forceinline__ void nn_take(NN& best, unsigned long long k, uint32_t
 __device__ __forceinline__ float axis_gap(float q, float lo, float hi, float margin) {
   return fmaxf(fmaxf(lo - q, q - hi) - margin, 0.0f);
 }
+// A query with a NaN or infinite coordinate finds nothing: its squared distance to every point is NaN or inf, never < max_sq.
+// Every search leaves before it forms a bound from such a coordinate (a NaN gap reads 0 in axis_gap: the clamped cell
+// coordinate +-1e9 would otherwise make the first "shell" the whole grid).  Such a query's cell is never inside the grid,
+// so the test sits on the searches' cold branches.
+__device__ __forceinline__ bool query_is_finite(float qx, float qy, float qz) {
+  return fabsf(qx) < INFINITY && fabsf(qy) < INFINITY && fabsf(qz) < INFINITY;   // (false for NaN too)
+}
 
 // Batched candidate scan: 4 independent 16-byte loads in flight per trip (indices clamped to the
 // last element of the range: re-evaluating a candidate never changes the result), so a wave pays
@@ -391,6 +398,7 @@ __device__ __forceinline__ void nn_search_from(const GridDev& g, float qx, float
   const bool inside = (cx >= 0) & (cx < g.nx) & (cy >= 0) & (cy < g.ny) & (cz >= 0) & (cz < g.nz);
   int s_shells = 2;      // (ONE call site of the shell search for both ways into it: it is inlined, and the kernels that hold this search live on their registers)
   if (!inside) {
+    if (!query_is_finite(qx, qy, qz)) return;
     // query farther than the radius from the whole grid: nothing to find
     const float gx = axis_gap(qx, g.ox, g.ox + (float)g.nx * g.cell, g.margin);
     const float gy = axis_gap(qy, g.oy, g.oy + (float)g.ny * g.cell, g.margin);
@@ -522,6 +530,7 @@ __device__ __forceinline__ void nn_search_lb(const GridDev& g, float qx, float q
   const int cx = (int)floorf(fx), cy = (int)floorf(fy), cz = (int)floorf(fz);
   const bool inside = (cx >= 0) & (cx < g.nx) & (cy >= 0) & (cy < g.ny) & (cz >= 0) & (cz < g.nz);
   if (!inside) {
+    if (!query_is_finite(qx, qy, qz)) return;      // (no match, no bound kept: *lb_out = 0)
     const float gx = axis_gap(qx, g.ox, g.ox + (float)g.nx * g.cell, g.margin);
     const float gy = axis_gap(qy, g.oy, g.oy + (float)g.ny * g.cell, g.margin);
     const float gz = axis_gap(qz, g.oz, g.oz + (float)g.nz * g.cell, g.margin);
@@ -645,7 +654,8 @@ __device__ __forceinline__ void nn_search_group(const GridDev& g, float qx, floa
     const float gx = axis_gap(qx, g.ox, g.ox + (float)g.nx * g.cell, g.margin);
     const float gy = axis_gap(qy, g.oy, g.oy + (float)g.ny * g.cell, g.margin);
     const float gz = axis_gap(qz, g.oz, g.oz + (float)g.nz * g.cell, g.margin);
-    if ((gx * gx + gy * gy + gz * gz) * KSHRINK >= max_sq) return;
+    // (a NaN coordinate reads as gap 0 in axis_gap: multiplied by zero it stays NaN, and the sum is not < max_sq -- nor is anything < a NaN radius; group-uniform: one query per group)
+    if (!((gx * gx + gy * gy + gz * gz) * KSHRINK + (qx * 0.0f + qy * 0.0f + qz * 0.0f) < max_sq)) return;
   }
   // first block size that reaches the grid at all
   int s = max(s_start, max(max(-cx, cx - (g.nx - 1)), max(max(-cy, cy - (g.ny - 1)), max(-cz, cz - (g.nz - 1)))));

@@ -62,12 +62,33 @@ const char* cilhip_last_error(const cilhip_ctx* ctx);
 int cilhip_set_stream(cilhip_ctx* ctx, void* hip_stream);
 int cilhip_synchronize(cilhip_ctx* ctx);
 
+/* ---- Non-finite points ------------------------------------------------------------------------
+ * Depth sensors produce NaN and +-inf points; every search entry point accepts them, in the indexed cloud and among the queries
+ * (cilhip_set_target, cilhip_set_source / cilhip_find_correspondences in all three search directions, cilhip_knn3f,
+ * cilhip_normals_*, cilhip_radius_search3f):
+ *   - a point with ANY non-finite coordinate keeps its index, is never returned as a neighbour and, as a query, finds nothing
+ *     (cilhip_get_nn: 0xFFFFFFFF; k-NN / radius lists: count 0, padding only; normals: a NaN row);
+ *   - every other point and query gets exactly what the same call returns on the clouds with those rows removed, indices
+ *     mapped back.  This is the brute force with IEEE comparisons -- a NaN or infinite squared distance is never
+ *     < max_sq_dist, also when max_sq_dist is INFINITY -- and what nanoflann's dist < worstDist does with such a point;
+ *   - the grid's bounding box is taken over the finite coordinates only; a cloud without a single finite point behaves as an
+ *     empty index (every search returns none, n is unchanged);
+ *   - a transform with a NaN or infinite entry makes every query non-finite: zero correspondences, CILHIP_OK;
+ *   - cilhip_get_means keeps returning the IEEE mean (NaN or inf), as the reference's dst_mean_ / src_mean_ would;
+ *   - WHICH of several exactly equidistant points is named is not defined on a cloud that holds non-finite points (the
+ *     reference's tree over NaN coordinates is not meaningful either).
+ * A FINITE cloud whose coordinates leave the range a single-precision grid can index (|coordinate| + 4 * extent must stay
+ * below FLT_MAX: coordinates near +-3.4e38) is refused: CILHIP_ERR_UNSUPPORTED with a message, never a wrong grid.
+ * Not covered: the ICP loops on such clouds (the combined metric's means are NaN in the reference too) and the 6-D / 9-D
+ * feature searches with non-finite normals or colours.  DESIGN.md, "Non-finite points". */
 /* ---- clouds ---------------------------------------------------------------------------------- */
 /* Target ("first"/dst) cloud + optional normals.  Builds the uniform-grid index on the GPU.
  * Replaces: KDTree ctor core/kd_tree.hpp:162-170 -> nanoflann buildIndex
  * (3rd_party/nanoflann/nanoflann.hpp:1661-1687), lazily triggered at
  * correspondence_search/correspondence_search_kd_tree.hpp:202-203; and the dst_mean_ of
- * registration/icp_single_transform_combined_metric.hpp:51-54. */
+ * registration/icp_single_transform_combined_metric.hpp:51-54.
+ * Points with a non-finite coordinate are kept (their indices stay) but are in no cell: "Non-finite points" above.  A finite cloud
+ * beyond the range of a single-precision grid: CILHIP_ERR_UNSUPPORTED. */
 int cilhip_set_target(cilhip_ctx* ctx, const float* xyz, const float* normals_or_null, size_t n,
                       int mem);
 /* Source ("second"/src) cloud.  Replaces the PointFeaturesAdaptor src_feat_
@@ -112,7 +133,9 @@ int cilhip_share_target(cilhip_ctx* ctx, cilhip_ctx* from);
  *   d2 < max_sq_dist, strict (correspondence_search_kd_tree_utilities.hpp:26-33; nanoflann.hpp:1901).
  * Ties on d2 (several target points at EXACTLY the smallest distance) name the point the reference's kd-tree traversal meets first
  * (option "tie_rule" = 2, the default; 0: the lowest dst index).
- * Results stay on the device; n_found (optional) forces a sync and returns the count. */
+ * Results stay on the device; n_found (optional) forces a sync and returns the count.
+ * Source or target points with a non-finite coordinate, or such an entry in T, match nothing ("Non-finite points" above); the same holds
+ * for the grid over the source that search directions FIRST_TO_SECOND / BOTH build. */
 int cilhip_find_correspondences(cilhip_ctx* ctx, const float T[16], float max_sq_dist,
                                 size_t* n_found_or_null);
 /* Per-source raw result of the last search, in ORIGINAL source order: nn_idx[i] = dst index or
@@ -406,7 +429,9 @@ int cilhip_transform_fit3f(int device, const float* dst_xyz, const float* src_xy
  * (csrc/tie_build.hip, on the device) the first time a call needs them, and searches again with them -- a cloud without exact ties never pays.
  * cilhip_knn_set_tie_rule (process-wide; also cilhip_normals_knn3f): 2 = that (default), 1 = tables built up front, 0 = lowest
  * index among equal distances (a brute-force argsort's order).  tests/test_gpu_parity.py: the reference's sensor frames and
- * lattices, index for index against the reference's own nanoflann knnSearch. */
+ * lattices, index for index against the reference's own nanoflann knnSearch.
+ * Reference points with a non-finite coordinate are in no list -- no entry at distance inf appears, also with max_sq_dist = INFINITY --,
+ * such queries get count 0 and padding only ("Non-finite points" above). */
 int cilhip_knn_set_tie_rule(int rule);
 int cilhip_knn3f(int device, const float* ref_xyz, size_t n_ref, const float* query_xyz, size_t n_query, int mem, size_t k,
                  float max_sq_dist, uint32_t* idx_out, float* d2_out, uint32_t* counts_out);
@@ -415,7 +440,8 @@ int cilhip_knn3f(int device, const float* ref_xyz, size_t n_ref, const float* qu
  * reference leaves them as std::sort does).  query_xyz == NULL: the target points are the queries.
  * offsets_out: HOST n_query + 1 -- list of query i = [offsets[i], offsets[i+1]); *total_out_or_null = offsets[n_query].
  * idx_out / d2_out: HOST `capacity` entries (d2_out may be NULL); when capacity < total (or idx_out == NULL) only the
- * offsets and the total are produced -- call again with enough room.  radius_sq must be finite. */
+ * offsets and the total are produced -- call again with enough room.  radius_sq must be finite.
+ * Reference points with a non-finite coordinate are in no list, such queries own empty lists ("Non-finite points" above). */
 int cilhip_radius_search3f(int device, const float* ref_xyz, size_t n_ref, const float* query_xyz, size_t n_query, int mem,
                            float radius_sq, uint64_t* offsets_out, uint32_t* idx_out, float* d2_out, size_t capacity,
                            size_t* total_out_or_null);

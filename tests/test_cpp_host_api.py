@@ -59,3 +59,15 @@ def test_loop_policy_on_host(hip_lib, orc):
         subprocess.check_call(["bash", os.path.join(ROOT, "tests", "cpp", "build.sh")])
     out = subprocess.run([binp], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and "ALL OK" in out.stdout, out.stdout + out.stderr
+
+
+def test_grid_policy_on_host(hip_lib, orc):
+    """cilantro_amd/csrc/grid_policy.hpp shapes the grid of every search (build_grid): on boxes at the edges of the f32 range,
+    degenerate, inverted, infinite and NaN it returns within a bounded number of growth steps, keeps the dimension caps, leaves
+    finite normal f32 parameters and puts every coordinate of the box into a data cell -- or refuses; compiled with the host
+    compiler, no GPU needed."""
+    binp = os.path.join(ROOT, "tests", "cpp", "bin", "test_grid_policy")
+    if not os.path.exists(binp):
+        subprocess.check_call(["bash", os.path.join(ROOT, "tests", "cpp", "build.sh")])
+    out = subprocess.run([binp], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "ALL OK" in out.stdout, out.stdout + out.stderr
