@@ -496,35 +496,18 @@ void launch_transform_original_host_T(const float* d_src_xyz, uint32_t ns, const
 }
 
 
-void free_pairs(PairSet& p) {
-  uint32_t** u[] = {&p.first, &p.second, &p.posd, &p.poss, &p.first2, &p.second2, &p.posd2, &p.poss2};
-  for (auto q : u) { if (*q) (void)hipFree(*q); *q = nullptr; }
-  if (p.d2) (void)hipFree(p.d2);
-  if (p.d2b) (void)hipFree(p.d2b);
-  if (p.src_view) (void)hipFree(p.src_view);
-  if (p.nrm_view) (void)hipFree(p.nrm_view);
-  p.d2 = p.d2b = nullptr; p.src_view = p.nrm_view = nullptr;
-  p.cap = 0; p.count = 0;
-  for (void*& w : p.ws) { if (w) (void)hipFree(w); w = nullptr; }
-  p.ws_cand = 0; p.ws_tmp_bytes = 0; p.ws_nd = 0; p.ws_ns = 0;
-}
-
 static hipError_t ensure_pairs(PairSet& p, size_t cap, bool with_normals) {
   if (cap <= p.cap && (!with_normals || p.nrm_view)) return hipSuccess;
-  void* keep_ws[PairSet::WS_COUNT];
-  for (int k = 0; k < PairSet::WS_COUNT; ++k) { keep_ws[k] = p.ws[k]; p.ws[k] = nullptr; }   // (free_pairs would drop the workspace too)
-  const size_t wc = p.ws_cand, wt = p.ws_tmp_bytes, wnd = p.ws_nd, wns = p.ws_ns;
-  free_pairs(p);
-  for (int k = 0; k < PairSet::WS_COUNT; ++k) p.ws[k] = keep_ws[k];
-  p.ws_cand = wc; p.ws_tmp_bytes = wt; p.ws_nd = wnd; p.ws_ns = wns;
-  const size_t c = cap ? cap : 1;
-  uint32_t** u[] = {&p.first, &p.second, &p.posd, &p.poss, &p.first2, &p.second2, &p.posd2, &p.poss2};
-  for (auto q : u) HIP_TRY(hipMalloc(q, c * sizeof(uint32_t)));
-  HIP_TRY(hipMalloc(&p.d2, c * sizeof(float)));
-  HIP_TRY(hipMalloc(&p.d2b, c * sizeof(float)));
-  HIP_TRY(hipMalloc(&p.src_view, c * sizeof(float4)));
-  if (with_normals) HIP_TRY(hipMalloc(&p.nrm_view, c * sizeof(float4)));
-  p.cap = c;
+  p.cap = 0; p.count = 0;
+  DevBuf<uint32_t>* u[] = {&p.first, &p.second, &p.posd, &p.poss, &p.first2, &p.second2, &p.posd2, &p.poss2};
+  for (auto q : u) q->reset();      // (everything goes before anything comes: the old and the new set never coexist)
+  p.d2.reset(); p.d2b.reset(); p.src_view.reset(); p.nrm_view.reset();
+  for (auto q : u) HIP_TRY(q->alloc(cap));
+  HIP_TRY(p.d2.alloc(cap));
+  HIP_TRY(p.d2b.alloc(cap));
+  HIP_TRY(p.src_view.alloc(cap));
+  if (with_normals) HIP_TRY(p.nrm_view.alloc(cap));
+  p.cap = cap ? cap : 1;
   return hipSuccess;
 }
 
@@ -534,35 +517,28 @@ static hipError_t ensure_ws(PairSet& p, size_t ncand, size_t nd, size_t ns, size
   enum { REV_POS, REV_D2, KEYS_IN, KEYS_OUT, SLOTS_IN, SLOTS_OUT, C_POSD, C_POSS, C_D2, FLAGS, OFFS, WINNER, SEL_KEYS, SEL_STATE, TMP };
   if (ncand > p.ws_cand) {
     const int cand_slots[] = {KEYS_IN, KEYS_OUT, SLOTS_IN, SLOTS_OUT, C_POSD, C_POSS, C_D2, FLAGS, OFFS, SEL_KEYS};
-    for (int k : cand_slots) { if (p.ws[k]) (void)hipFree(p.ws[k]); p.ws[k] = nullptr; }
+    for (int k : cand_slots) p.ws[k].reset();
+    p.ws_cand = 0;
     const size_t c = ncand;
-    HIP_TRY(hipMalloc(&p.ws[KEYS_IN], c * 8)); HIP_TRY(hipMalloc(&p.ws[KEYS_OUT], c * 8)); HIP_TRY(hipMalloc(&p.ws[SEL_KEYS], c * 8));
-    HIP_TRY(hipMalloc(&p.ws[SLOTS_IN], c * 4)); HIP_TRY(hipMalloc(&p.ws[SLOTS_OUT], c * 4));
-    HIP_TRY(hipMalloc(&p.ws[C_POSD], c * 4)); HIP_TRY(hipMalloc(&p.ws[C_POSS], c * 4)); HIP_TRY(hipMalloc(&p.ws[C_D2], c * 4));
-    HIP_TRY(hipMalloc(&p.ws[FLAGS], c * 4)); HIP_TRY(hipMalloc(&p.ws[OFFS], c * 4));
-    if (!p.ws[SEL_STATE]) HIP_TRY(hipMalloc(&p.ws[SEL_STATE], filter_state_bytes()));
+    HIP_TRY(p.ws[KEYS_IN].alloc(c * 8)); HIP_TRY(p.ws[KEYS_OUT].alloc(c * 8)); HIP_TRY(p.ws[SEL_KEYS].alloc(c * 8));
+    HIP_TRY(p.ws[SLOTS_IN].alloc(c * 4)); HIP_TRY(p.ws[SLOTS_OUT].alloc(c * 4));
+    HIP_TRY(p.ws[C_POSD].alloc(c * 4)); HIP_TRY(p.ws[C_POSS].alloc(c * 4)); HIP_TRY(p.ws[C_D2].alloc(c * 4));
+    HIP_TRY(p.ws[FLAGS].alloc(c * 4)); HIP_TRY(p.ws[OFFS].alloc(c * 4));
+    if (!p.ws[SEL_STATE]) HIP_TRY(p.ws[SEL_STATE].alloc(filter_state_bytes()));
     p.ws_cand = ncand;
   }
   // (sized by the clouds, not by the candidates: a FIRST_TO_SECOND search -- nd candidates -- after a BOTH search of a smaller target
   //  -- nd' + ns' >= nd candidates -- keeps the candidate arrays and still needs longer per-target arrays)
-  if (nd > p.ws_nd || !p.ws[REV_POS]) {
-    for (int k : {REV_POS, REV_D2}) { if (p.ws[k]) (void)hipFree(p.ws[k]); p.ws[k] = nullptr; }
-    HIP_TRY(hipMalloc(&p.ws[REV_POS], (nd ? nd : 1) * 4)); HIP_TRY(hipMalloc(&p.ws[REV_D2], (nd ? nd : 1) * 4));
+  if (nd > p.ws_nd || !p.ws[REV_POS] || !p.ws[REV_D2]) {
+    p.ws[REV_POS].reset(); p.ws[REV_D2].reset();
+    HIP_TRY(p.ws[REV_POS].alloc(nd * 4)); HIP_TRY(p.ws[REV_D2].alloc(nd * 4));
     p.ws_nd = nd;
   }
   if (ns > p.ws_ns || !p.ws[WINNER]) {
-    if (p.ws[WINNER]) (void)hipFree(p.ws[WINNER]);
-    p.ws[WINNER] = nullptr;
-    HIP_TRY(hipMalloc(&p.ws[WINNER], (ns ? ns : 1) * 8));
+    HIP_TRY(p.ws[WINNER].alloc(ns * 8));
     p.ws_ns = ns;
   }
-  if (tmp_bytes > p.ws_tmp_bytes) {
-    if (p.ws[TMP]) (void)hipFree(p.ws[TMP]);
-    p.ws[TMP] = nullptr;
-    HIP_TRY(hipMalloc(&p.ws[TMP], tmp_bytes));
-    p.ws_tmp_bytes = tmp_bytes;
-  }
-  return hipSuccess;
+  return p.ws[TMP].ensure(tmp_bytes);
 }
 
 // exclusive scan of flags into offs; the total comes back to the host (one synchronisation: the next launches are sized by it)
@@ -605,11 +581,11 @@ hipError_t find_pairs(const FeatSpec& feat, const GridDev& g, const GridDev& sgr
   size_t sort_bytes = 0;
   HIP_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, ncand, 0u, end_bit, s));
   HIP_TRY(ensure_ws(out, ncand, nd, ns, sort_bytes ? sort_bytes : 16));
-  uint32_t* rev_pos = (uint32_t*)out.ws[REV_POS]; float* rev_d2 = (float*)out.ws[REV_D2];
-  unsigned long long *keys_in = (unsigned long long*)out.ws[KEYS_IN], *keys_out = (unsigned long long*)out.ws[KEYS_OUT];
-  uint32_t *slots_in = (uint32_t*)out.ws[SLOTS_IN], *slots_out = (uint32_t*)out.ws[SLOTS_OUT], *c_posd = (uint32_t*)out.ws[C_POSD], *c_poss = (uint32_t*)out.ws[C_POSS];
-  float* c_d2 = (float*)out.ws[C_D2];
-  uint32_t *flags = (uint32_t*)out.ws[FLAGS], *offs = (uint32_t*)out.ws[OFFS];
+  uint32_t* rev_pos = (uint32_t*)out.ws[REV_POS].get(); float* rev_d2 = (float*)out.ws[REV_D2].get();
+  unsigned long long *keys_in = (unsigned long long*)out.ws[KEYS_IN].get(), *keys_out = (unsigned long long*)out.ws[KEYS_OUT].get();
+  uint32_t *slots_in = (uint32_t*)out.ws[SLOTS_IN].get(), *slots_out = (uint32_t*)out.ws[SLOTS_OUT].get(), *c_posd = (uint32_t*)out.ws[C_POSD].get(), *c_poss = (uint32_t*)out.ws[C_POSS].get();
+  float* c_d2 = (float*)out.ws[C_D2].get();
+  uint32_t *flags = (uint32_t*)out.ws[FLAGS].get(), *offs = (uint32_t*)out.ws[OFFS].get();
 
   // 1. reverse search: the target points (in their grid order) against the source
   InvArgs iv{};
@@ -641,7 +617,7 @@ hipError_t find_pairs(const FeatSpec& feat, const GridDev& g, const GridDev& sgr
       through_inverse = sgrid.pts != nullptr;
     }
   }
-  float* d_q = nullptr;
+  DevBuf<float> d_q;
   GridBuildResult qg{};
   bool have_grid = false;
   hipError_t e = hipSuccess;
@@ -652,8 +628,8 @@ hipError_t find_pairs(const FeatSpec& feat, const GridDev& g, const GridDev& sgr
       else hipLaunchKernelGGL(k_reverse_search<false>, dim3(iter_num_blocks(nd)), dim3(256), 0, s, sgrid, g.pts, nd, state, iv, max_sq, rev_pos, rev_d2, feat, rev_tie ? *rev_tie : TieDev{});
     } else {
       if (feat.enabled) { e = hipErrorNotSupported; break; }      // (a feature search under a (nearly) singular transform: not implemented)
-      if ((e = hipMalloc(&d_q, 3 * (size_t)ns * sizeof(float))) != hipSuccess) break;
-      hipLaunchKernelGGL(k_transform_original, dim3(nblk(ns)), dim3(256), 0, s, d_src_xyz, ns, state, d_q);
+      if ((e = d_q.alloc(3 * (size_t)ns)) != hipSuccess) break;
+      hipLaunchKernelGGL(k_transform_original, dim3(nblk(ns)), dim3(256), 0, s, d_src_xyz, ns, state, d_q.get());
       double mean[3];
       if ((e = build_grid(d_q, nullptr, ns, s, &qg, mean, 1.0)) != hipSuccess) break;
       have_grid = true;
@@ -677,7 +653,7 @@ hipError_t find_pairs(const FeatSpec& feat, const GridDev& g, const GridDev& sgr
                        out.first, out.second, out.posd, out.poss, out.d2);
     // 4. post-filters on the pair list (correspondence_search_kd_tree.hpp:224-225)
     if (m > 0 && inlier_fraction > 0.0 && inlier_fraction < 1.0) {
-      launch_select_fraction(out.d2, m, inlier_fraction, (unsigned long long*)out.ws[SEL_KEYS], out.ws[SEL_STATE], flags, s);
+      launch_select_fraction(out.d2, m, inlier_fraction, (unsigned long long*)out.ws[SEL_KEYS].get(), out.ws[SEL_STATE], flags, s);
       uint32_t m2 = 0;
       if ((e = scan_flags_ws(out, flags, offs, m, &m2, s)) != hipSuccess) break;
       hipLaunchKernelGGL(k_compact_pairs, dim3(nblk(m)), dim3(256), 0, s, flags, offs, m, out.first, out.second, out.posd, out.poss, out.d2, out.first2,
@@ -687,7 +663,7 @@ hipError_t find_pairs(const FeatSpec& feat, const GridDev& g, const GridDev& sgr
       m = m2;
     }
     if (m > 0 && one_to_one && direction == 1) {
-      unsigned long long* winner = (unsigned long long*)out.ws[WINNER];
+      unsigned long long* winner = (unsigned long long*)out.ws[WINNER].get();
       if ((e = hipMemsetAsync(winner, 0xFF, (size_t)ns * 8, s)) != hipSuccess) break;
       hipLaunchKernelGGL(k_o2o_min_pairs, dim3(nblk(m)), dim3(256), 0, s, out.first, out.poss, out.d2, m, winner);
       hipLaunchKernelGGL(k_o2o_flags_pairs, dim3(nblk(m)), dim3(256), 0, s, out.first, out.poss, out.d2, m, winner, flags);
@@ -703,11 +679,9 @@ hipError_t find_pairs(const FeatSpec& feat, const GridDev& g, const GridDev& sgr
     if (m > 0)
       hipLaunchKernelGGL(k_gather_pair_view, dim3(nblk(m)), dim3(256), 0, s, d_src_xyz, d_src_nrm, out.poss, m, out.src_view,
                          d_src_nrm ? out.nrm_view : (float4*)nullptr);
-    if (have_grid) e = hipStreamSynchronize(s);      // (the one-off grid is freed below)
+    if (have_grid) e = hipStreamSynchronize(s);      // (the one-off grid goes with this frame)
     out.count = m;
   } while (0);
-  if (have_grid) free_grid(qg.grid);
-  if (d_q) (void)hipFree(d_q);
   return e;
 }
 

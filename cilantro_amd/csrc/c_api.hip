@@ -17,54 +17,23 @@ hipStream_t ctx_stream(const cilhip_ctx* c) { return c->stream; }
 double ctx_wait_us(const cilhip_ctx* c) { return c->wait_us; }
 }  // namespace cilhip
 
-template <class T> static void dev_free(T*& p) {
-  if (p) { (void)hipFree(p); p = nullptr; }
-}
+// ---- what a context lets go of, and when (ctx.hpp: the groups).  A shared target array is only let go of: its last holder frees it.
 static void drop_src_grid(cilhip_ctx* c) {
-  if (c->has_src_grid) { free_grid(c->src_grid); c->has_src_grid = false; }
-  dev_free(c->d_src_safe2);
-  dev_free(c->d_grid_to_sorted);
-  dev_free(c->d_src_rgb_grid);
-}
-static void drop_rev_tie_tables(cilhip_ctx* c) {  // (they describe ONE source under ONE transform)
-  dev_free(c->d_rev_tie_leaf_slot);
-  dev_free(c->d_rev_tie_nodes);
-  c->rev_tie_nodes_cap = 0; c->rev_tie_valid = false; c->rev_tie_aware = false;
-}
-// a target-side allocation of this context: freed here unless it belongs to a share (then by whoever lets go of the share last)
-static void target_ptr_free(cilhip_ctx* c, const void* p) {
-  if (!p) return;
-  if (c->tshare && std::find(c->tshare->allocs.begin(), c->tshare->allocs.end(), p) != c->tshare->allocs.end()) return;
-  (void)hipFree(const_cast<void*>(p));
-}
-static void release_target_share(cilhip_ctx* c) {
-  if (!c->tshare) return;
-  if (--c->tshare->refs == 0) {
-    for (void* p : c->tshare->allocs) (void)hipFree(p);
-    delete c->tshare;
-  }
-  c->tshare = nullptr;
+  static_cast<SrcGridBufs&>(*c) = SrcGridBufs{};
+  c->src_grid = GridDev{}; c->has_src_grid = false;
 }
 static void drop_feat_tie_tables(cilhip_ctx* c) {      // (one target under one set of feature options; never shared)
-  dev_free(c->d_tief_leaf_slot);
-  dev_free(c->d_tief_nodes);
+  c->d_tief_leaf_slot.reset(); c->d_tief_nodes.reset();
 }
 static void drop_tie_tables(cilhip_ctx* c) {      // (they describe ONE target)
-  target_ptr_free(c, c->d_tie_leaf_slot); c->d_tie_leaf_slot = nullptr;
-  target_ptr_free(c, c->d_tie_nodes); c->d_tie_nodes = nullptr;
+  c->d_tie_leaf_slot.reset(); c->d_tie_nodes.reset();
 }
-// everything a context holds of its target (its own allocations are freed, shared ones only let go of)
+// everything a context holds of its target: grid arrays, the tables built on top of them, the per-target buffers of the filters and
+// the reverse searches, the colours that were set for it
 static void release_target(cilhip_ctx* c) {
-  if (c->has_target) {
-    target_ptr_free(c, c->grid.pts); target_ptr_free(c, c->grid.nrm); target_ptr_free(c, c->grid.pn); target_ptr_free(c, c->grid.cell_start);
-    c->grid.pts = nullptr; c->grid.nrm = nullptr; c->grid.pn = nullptr; c->grid.cell_start = nullptr;
-    c->has_target = false;
-  }
-  target_ptr_free(c, c->d_inv_perm); c->d_inv_perm = nullptr;
-  target_ptr_free(c, c->d_safe2); c->d_safe2 = nullptr;
-  drop_tie_tables(c);
-  drop_feat_tie_tables(c);
-  release_target_share(c);
+  static_cast<TargetBufs&>(*c) = TargetBufs{};
+  c->grid.pts = nullptr; c->grid.nrm = nullptr; c->grid.pn = nullptr; c->grid.cell_start = nullptr;
+  c->has_target = false; c->dst_rgb_sorted_ok = false;
 }
 
 // (the entry points take their C linkage from their declarations in c_api.h)
@@ -78,24 +47,24 @@ int cilhip_create(cilhip_ctx** out, int device) {
   cilhip_ctx* c = new (std::nothrow) cilhip_ctx();
   if (!c) return CILHIP_ERR_HIP;
   c->device = device;
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) {
+  if (hipSetDevice(device) != hipSuccess || c->own_stream.create() != hipSuccess) {
     delete c;
     return CILHIP_ERR_HIP;
   }
   c->stream = c->own_stream;
-  if (hipMalloc(&c->d_state, sizeof(IcpState)) != hipSuccess || hipMalloc(&c->d_count, sizeof(unsigned long long)) != hipSuccess ||
-      hipMalloc(&c->d_defer_flag, sizeof(uint32_t)) != hipSuccess || hipMemset(c->d_defer_flag, 0, sizeof(uint32_t)) != hipSuccess ||
-      hipMalloc(&c->d_unproven, 128 * sizeof(uint32_t)) != hipSuccess || hipMemset(c->d_unproven, 0, 128 * sizeof(uint32_t)) != hipSuccess ||
-      hipMalloc(&c->d_ticket, sizeof(unsigned int)) != hipSuccess || hipMemset(c->d_ticket, 0, sizeof(unsigned int)) != hipSuccess ||
+  if (c->d_state.alloc(1) != hipSuccess || c->d_count.alloc(1) != hipSuccess ||
+      c->d_defer_flag.alloc(1) != hipSuccess || hipMemset(c->d_defer_flag, 0, sizeof(uint32_t)) != hipSuccess ||
+      c->d_unproven.alloc(128) != hipSuccess || hipMemset(c->d_unproven, 0, 128 * sizeof(uint32_t)) != hipSuccess ||
+      c->d_ticket.alloc(1) != hipSuccess || hipMemset(c->d_ticket, 0, sizeof(unsigned int)) != hipSuccess ||
       hipHostMalloc(&c->h_feedback, sizeof(Feedback), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
       hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_feedback), c->h_feedback, 0) != hipSuccess ||
-      hipMalloc(&c->d_trace, RUN_TRACE_CAP * sizeof(uint4)) != hipSuccess || hipMemset(c->d_trace, 0, RUN_TRACE_CAP * sizeof(uint4)) != hipSuccess ||
-      hipMalloc(&c->d_stage, REDUCE_STAGE_DOUBLES * sizeof(double)) != hipSuccess || hipMalloc(&c->d_sums, 3 * SUMS_MAX * sizeof(double)) != hipSuccess) {
+      c->d_trace.alloc(RUN_TRACE_CAP) != hipSuccess || hipMemset(c->d_trace, 0, RUN_TRACE_CAP * sizeof(uint4)) != hipSuccess ||
+      c->d_stage.alloc(REDUCE_STAGE_DOUBLES) != hipSuccess || c->d_sums.alloc(3 * SUMS_MAX) != hipSuccess) {
     delete c;
     return CILHIP_ERR_HIP;
   }
   if (hipMemset(c->d_state, 0, sizeof(IcpState)) != hipSuccess) { delete c; return CILHIP_ERR_HIP; }
-  c->d_tie_counters = reinterpret_cast<unsigned int*>(reinterpret_cast<char*>(c->d_state) + offsetof(IcpState, tie_counters));      // (read with the state: read_state)
+  c->d_tie_counters = reinterpret_cast<unsigned int*>(reinterpret_cast<char*>(c->d_state.get()) + offsetof(IcpState, tie_counters));      // (read with the state: read_state)
   memcpy(c->sort_T, kIdentity16, sizeof(kIdentity16));
   memcpy(c->nn_T, kIdentity16, sizeof(kIdentity16));
   *out = c;
@@ -103,18 +72,11 @@ int cilhip_create(cilhip_ctx** out, int device) {
 }
 
 static void free_source(cilhip_ctx* c) {
-  drop_rev_tie_tables(c);
-  dev_free(c->d_src_xyz); dev_free(c->d_src_sorted); dev_free(c->d_nn_pos); dev_free(c->d_nn_d2);
-  dev_free(c->d_warm_rec); dev_free(c->d_nn_lb);
+  static_cast<SourceBufs&>(*c) = SourceBufs{};      // (d_tiles / d_tile_center pointed into its sort_ws)
+  c->src_grid = GridDev{}; c->has_src_grid = false;
+  c->rev_tie_valid = false; c->rev_tie_aware = false;      // (the reverse order tables described this source under one transform)
   c->src3_valid = false; c->lb_fresh = false; c->rec_valid = false;
-  dev_free(c->d_out_idx); dev_free(c->d_out_d2);
-  free_sort_workspace(c->sort_ws);      // (owns d_tiles / d_tile_center)
-  c->d_tiles = nullptr; c->d_tile_center = nullptr; c->ntiles = 0; c->tile_aux_cap = 0;
-  dev_free(c->d_tile_box); dev_free(c->d_defer_mask);
-  dev_free(c->d_src_nrm); dev_free(c->d_src_nrm_sorted); dev_free(c->d_src_rgb); dev_free(c->d_src_rgb_sorted);
-  dev_free(c->d_keys); dev_free(c->d_own_order);
-  drop_src_grid(c);
-  dev_free(c->d_src_inv); dev_free(c->d_grid_to_sorted);
+  c->d_tiles = nullptr; c->d_tile_center = nullptr; c->ntiles = 0;
   c->has_source = false; c->src_sorted = false; drop_matches(c); c->ns = 0;
   c->have_pairs = false; c->pairs.count = 0;   // a pair list refers to the source / target it was found on
   c->policy.far_mode = true;
@@ -126,20 +88,7 @@ void cilhip_destroy(cilhip_ctx* c) {
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
   (void)cilhip_rank_comm_destroy(c);
-  free_source(c);
-  release_target(c);
-  free_pairs(c->pairs);
-  dev_free(c->d_ticket); dev_free(c->d_wtab); dev_free(c->d_wtab_in); dev_free(c->d_dst_rgb); dev_free(c->d_dst_rgb_sorted);
-  dev_free(c->d_state); dev_free(c->d_state_id); dev_free(c->d_partials); dev_free(c->d_sel_state); dev_free(c->d_winner);
-  dev_free(c->d_count); dev_free(c->d_dbg); dev_free(c->d_trace); dev_free(c->d_defer_flag); dev_free(c->d_unproven);
-  dev_free(c->d_rev_pos); dev_free(c->d_rev_d2); dev_free(c->d_stage); dev_free(c->d_sums);
-  if (c->h_feedback) (void)hipHostFree(c->h_feedback);
-  for (auto e : c->ev) (void)hipEventDestroy(e);
-  for (auto e : c->ev_acc) (void)hipEventDestroy(e);
-  for (auto e : c->ev_ar) (void)hipEventDestroy(e);
-
-  if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-  delete c;
+  delete c;      // (every buffer is a member; the context's own stream is the last thing to go: ctx.hpp)
 }
 
 const char* cilhip_last_error(const cilhip_ctx* c) { return c ? c->err.c_str() : cilhip::stateless_last_error(); }
@@ -326,13 +275,20 @@ int cilhip_debug_counters(cilhip_ctx* c, uint32_t out[2]) {
   out[0] = out[1] = 0;
   if (!c->d_defer_mask || !c->ntiles) return CILHIP_OK;
   CK(c, hipSetDevice(c->device));
-  if (!c->d_dbg) CK(c, hipMalloc(&c->d_dbg, 2 * sizeof(uint32_t)));
+  if (!c->d_dbg) CK(c, c->d_dbg.alloc(2));
   launch_count_deferred(c->d_defer_mask, c->ntiles, c->d_dbg, c->stream);
   CK(c, hipMemcpyAsync(out, c->d_dbg, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   CK(c, hipStreamSynchronize(c->stream));
 #ifdef CILHIP_EXP_PHASE_CLOCKS
   cilhip::debug_dump_phase_clocks();
 #endif
+  return CILHIP_OK;
+}
+
+int cilhip_debug_live_allocations(unsigned long long out[2]) {
+  if (!out) return CILHIP_ERR_INVALID;
+  out[0] = dev_mem_live().count.load(std::memory_order_relaxed);
+  out[1] = dev_mem_live().bytes.load(std::memory_order_relaxed);
   return CILHIP_OK;
 }
 
@@ -397,11 +353,10 @@ int cilhip_enable_kernel_timing(cilhip_ctx* c, int on) {
   return CILHIP_OK;
 }
 
-static int upload(cilhip_ctx* c, const float* src, size_t count, int mem, float** d_out) {
-  *d_out = nullptr;
-  CK(c, hipMalloc(d_out, (count ? count : 1) * sizeof(float)));
+static int upload(cilhip_ctx* c, const float* src, size_t count, int mem, DevBuf<float>& d_out) {
+  CK(c, d_out.alloc(count));
   if (count)
-    CK(c, hipMemcpyAsync(*d_out, src, count * sizeof(float), mem == CILHIP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+    CK(c, hipMemcpyAsync(d_out, src, count * sizeof(float), mem == CILHIP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
   return CILHIP_OK;
 }
 
@@ -410,23 +365,19 @@ int cilhip_set_target(cilhip_ctx* c, const float* xyz, const float* nrm, size_t 
   if ((n && !xyz) || n >= 0xFFFFFFF0ull) return fail(c, CILHIP_ERR_INVALID, "set_target: bad cloud (null or >= 2^32-16 points)");
   CK(c, hipSetDevice(c->device));
   auto t0 = std::chrono::steady_clock::now();
-  release_target(c);      // (incl. the order tables, the nearest-other-point table: they describe ONE target; a shared target is only let go of)
-  dev_free(c->d_winner); dev_free(c->d_rev_pos); dev_free(c->d_rev_d2);
-  float *d_xyz = nullptr, *d_nrm = nullptr;
-  int rc = upload(c, xyz, 3 * n, mem, &d_xyz);
+  release_target(c);      // (incl. the order tables, the nearest-other-point table, the colours: they describe ONE target; a shared target is only let go of)
+  DevBuf<float> d_xyz, d_nrm;
+  int rc = upload(c, xyz, 3 * n, mem, d_xyz);
   if (rc) return rc;
-  if (nrm) { rc = upload(c, nrm, 3 * n, mem, &d_nrm); if (rc) { (void)hipFree(d_xyz); return rc; } }
+  if (nrm) { rc = upload(c, nrm, 3 * n, mem, d_nrm); if (rc) return rc; }
   GridBuildResult r{};
   double mean[3];
   hipError_t e = build_grid(d_xyz, d_nrm, (uint32_t)n, c->stream, &r, mean, c->cell_occupancy, c->refined_occupancy);
-  (void)hipFree(d_xyz);
-  if (d_nrm) (void)hipFree(d_nrm);
+  d_xyz.reset(); d_nrm.reset();
   if (e == GRID_RANGE_ERROR) { c->err = std::string("set_target: ") + kGridRangeMessage; return CILHIP_ERR_UNSUPPORTED; }
   if (e != hipSuccess) { c->err = std::string("build_grid: ") + hipGetErrorString(e); return CILHIP_ERR_HIP; }
-  c->grid = r.grid; c->grid_occ = r.avg_occupancy; c->grid_cells = r.n_cells;
+  c->grid = r.grid; c->grid_store = std::move(r.store); c->grid_occ = r.avg_occupancy; c->grid_cells = r.n_cells;
   c->policy.warm_banned = false;
-  c->dst_rgb_sorted_ok = false;
-  dev_free(c->d_dst_rgb); dev_free(c->d_dst_rgb_sorted);      // (colours belong to the target they were set for)
   c->has_normals = (nrm != nullptr);
   for (int i = 0; i < 3; ++i) c->dst_mean[i] = (float)mean[i];
   c->partial_target = false;      // (a new target stands for itself until cilhip_set_shard_info says otherwise)
@@ -442,9 +393,9 @@ int cilhip_set_target(cilhip_ctx* c, const float* xyz, const float* nrm, size_t 
 // CorrespondenceSearchKDTree::getFirstSearchTree / setFirstSearchTree (correspondence_search_kd_tree.hpp:273-296): a second engine
 // takes the index another one built instead of building its own.  Here: `c` takes `from`'s target as it stands -- the sorted
 // points and normals, the cell table, and whatever has been built on top of them by now (the paired point+normal records, the
-// nearest-other-point table, the order tables of the reference's tree, the index -> position map) -- without copying a byte.  The
-// allocations move into a reference-counted share: either context may be destroyed or given another target first, the memory goes
-// when the last user lets go.  What one of them builds LATER (tables a run finds it needs) is its own.
+// nearest-other-point table, the order tables of the reference's tree, the index -> position map) -- without copying a byte.  Every
+// one of those arrays is reference-counted by itself (SharedBuf): either context may be destroyed or given another target first, an
+// array goes when its last holder lets go.  What one of them builds LATER (tables a run finds it needs) is its own.
 int cilhip_share_target(cilhip_ctx* c, cilhip_ctx* from) {
   if (!c || !from || c == from) return CILHIP_ERR_INVALID;
   if (!from->has_target) return fail(c, CILHIP_ERR_INVALID, "share_target: the other context has no target");
@@ -453,18 +404,7 @@ int cilhip_share_target(cilhip_ctx* c, cilhip_ctx* from) {
   CK(c, hipStreamSynchronize(from->stream));      // (whatever is still building the lender's tables)
   CK(c, hipStreamSynchronize(c->stream));
   release_target(c);
-  dev_free(c->d_winner); dev_free(c->d_rev_pos); dev_free(c->d_rev_d2);
-  dev_free(c->d_dst_rgb); dev_free(c->d_dst_rgb_sorted);
-  c->dst_rgb_sorted_ok = false;
-  // the lender's own allocations become the share's (its earlier share, if it has one, already holds the rest)
-  if (!from->tshare) { from->tshare = new (std::nothrow) TargetShare(); if (!from->tshare) return fail(c, CILHIP_ERR_HIP, "share_target: out of memory"); from->tshare->refs = 1; }
-  TargetShare* sh = from->tshare;
-  const void* ptrs[] = {from->grid.pts, from->grid.nrm, from->grid.pn, from->grid.cell_start, from->d_inv_perm, from->d_safe2, from->d_tie_leaf_slot, from->d_tie_nodes};
-  for (const void* p : ptrs)
-    if (p && std::find(sh->allocs.begin(), sh->allocs.end(), p) == sh->allocs.end()) sh->allocs.push_back(const_cast<void*>(p));
-  ++sh->refs;
-  c->tshare = sh;
-  c->grid = from->grid; c->has_target = true; c->has_normals = from->has_normals;
+  c->grid = from->grid; c->grid_store = from->grid_store; c->has_target = true; c->has_normals = from->has_normals;
   c->grid_occ = from->grid_occ; c->grid_cells = from->grid_cells; c->build_ms = 0.0;
   for (int i = 0; i < 3; ++i) c->dst_mean[i] = from->dst_mean[i];
   c->index_offset = from->index_offset; c->partial_target = from->partial_target;
@@ -483,12 +423,11 @@ int cilhip_set_source(cilhip_ctx* c, const float* xyz, size_t n, int mem) {
   if ((n && !xyz) || n >= 0xFFFFFFF0ull) return fail(c, CILHIP_ERR_INVALID, "set_source: bad cloud");
   CK(c, hipSetDevice(c->device));
   free_source(c);
-  int rc = upload(c, xyz, 3 * n, mem, &c->d_src_xyz);
+  int rc = upload(c, xyz, 3 * n, mem, c->d_src_xyz);
   if (rc) return rc;
-  const size_t cap = n ? n : 1;
-  CK(c, hipMalloc(&c->d_src_sorted, cap * sizeof(float4)));
-  CK(c, hipMalloc(&c->d_nn_pos, cap * sizeof(uint32_t)));
-  CK(c, hipMalloc(&c->d_nn_d2, cap * sizeof(float)));
+  CK(c, c->d_src_sorted.alloc(n));
+  CK(c, c->d_nn_pos.alloc(n));
+  CK(c, c->d_nn_d2.alloc(n));
   c->ns = (uint32_t)n;
   double mean[3];
   float lo[3], hi[3];
@@ -512,19 +451,19 @@ int cilhip_set_source_normals(cilhip_ctx* c, const float* nrm, int mem) {
   if (!c) return CILHIP_ERR_INVALID;
   if (!c->has_source) return fail(c, CILHIP_ERR_INVALID, "set_source_normals: set_source first");
   CK(c, hipSetDevice(c->device));
-  dev_free(c->d_src_nrm);
-  dev_free(c->d_src_nrm_sorted);
+  c->d_src_nrm.reset();
+  c->d_src_nrm_sorted.reset();
   c->have_pairs = false; c->pairs.count = 0;
   drop_src_grid(c);      // (it carries the feature vectors of the reverse searches)
   if (!nrm) return CILHIP_OK;                              // back to the 3-cloud (non-symmetric) form
-  int rc = upload(c, nrm, 3 * (size_t)c->ns, mem, &c->d_src_nrm);
+  int rc = upload(c, nrm, 3 * (size_t)c->ns, mem, c->d_src_nrm);
   if (rc) return rc;
   c->src_nrm0[0] = c->src_nrm0[1] = c->src_nrm0[2] = 0.0f;
   if (c->ns) {
     CK(c, hipMemcpyAsync(c->src_nrm0, c->d_src_nrm, 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     CK(c, hipStreamSynchronize(c->stream));
   }
-  CK(c, hipMalloc(&c->d_src_nrm_sorted, (c->ns ? c->ns : 1) * sizeof(float4)));
+  CK(c, c->d_src_nrm_sorted.alloc(c->ns));
   c->src_sorted = false;                                   // the sorted copy is (re)built with the next sort
   drop_matches(c);
   c->have_pairs = false; c->pairs.count = 0;
@@ -536,14 +475,14 @@ int cilhip_set_color_features(cilhip_ctx* c, const float* dst_rgb, const float* 
   if (!c->has_target || !c->has_source) return fail(c, CILHIP_ERR_INVALID, "set_color_features: set_target and set_source first");
   if (!dst_rgb || !src_rgb) return fail(c, CILHIP_ERR_INVALID, "set_color_features: both clouds' colours are needed");
   CK(c, hipSetDevice(c->device));
-  dev_free(c->d_dst_rgb);
-  dev_free(c->d_src_rgb);
-  dev_free(c->d_src_rgb_sorted);
-  int rc = upload(c, dst_rgb, 3 * (size_t)c->grid.n, mem, &c->d_dst_rgb);
+  c->d_dst_rgb.reset();
+  c->d_src_rgb.reset();
+  c->d_src_rgb_sorted.reset();
+  int rc = upload(c, dst_rgb, 3 * (size_t)c->grid.n, mem, c->d_dst_rgb);
   if (rc) return rc;
-  rc = upload(c, src_rgb, 3 * (size_t)c->ns, mem, &c->d_src_rgb);
+  rc = upload(c, src_rgb, 3 * (size_t)c->ns, mem, c->d_src_rgb);
   if (rc) return rc;
-  CK(c, hipMalloc(&c->d_src_rgb_sorted, (c->ns ? c->ns : 1) * sizeof(float4)));
+  CK(c, c->d_src_rgb_sorted.alloc(c->ns));
   c->dst_rgb_sorted_ok = false;
   c->src_sorted = false;                                   // the source's sorted copy is (re)built with the next sort
   drop_src_grid(c);      // (it carries the features of the reverse searches)
@@ -560,14 +499,10 @@ int cilhip_get_means(cilhip_ctx* c, float dm[3], float sm[3]) {
   return CILHIP_OK;
 }
 
-// The rows of partial sums the accumulating kernels write (SUMS_MAX doubles each): grown, never shrunk.  The pointer is null and the
-// count zero while the new block is being allocated, so a failed allocation leaves nothing stale behind.
+// The rows of partial sums the accumulating kernels write (SUMS_MAX doubles each): grown, never shrunk (DevBuf::ensure: a failed
+// allocation leaves nothing stale behind).
 int cilhip::ensure_partial_rows(cilhip_ctx* c, size_t rows) {
-  if (rows <= (size_t)c->partial_blocks) return CILHIP_OK;
-  if (c->d_partials) (void)hipFree(c->d_partials);
-  c->d_partials = nullptr; c->partial_blocks = 0;
-  CK(c, hipMalloc(&c->d_partials, rows * SUMS_MAX * sizeof(double)));
-  c->partial_blocks = (int)rows;
+  CK(c, c->d_partials.ensure(rows * SUMS_MAX));
   return CILHIP_OK;
 }
 
@@ -590,16 +525,14 @@ int cilhip::ensure_sorted(cilhip_ctx* c, const float T[16]) {
   if (need) {
     // (scratch, tile table and the per-tile arrays are kept between the sorts of a source: a re-sort costs its kernels only)
     c->d_tiles = nullptr; c->d_tile_center = nullptr; c->ntiles = 0;
-    hipError_t e = sort_source(c->d_src_xyz, c->ns, c->grid, T, c->d_src_sorted, c->stream, &c->d_tiles, &c->d_tile_center, c->tile_axes, &c->ntiles, &c->sort_ws);
+    hipError_t e = sort_source(c->d_src_xyz, c->ns, c->grid, T, c->d_src_sorted, c->stream, &c->d_tiles, &c->d_tile_center, c->tile_axes, &c->ntiles, c->sort_ws);
     if (e != hipSuccess) { c->err = std::string("sort_source: ") + hipGetErrorString(e); return CILHIP_ERR_HIP; }
-    if (c->ntiles + 1 > c->tile_aux_cap) {
-      dev_free(c->d_tile_box);
-      dev_free(c->d_defer_mask);
-      c->tile_aux_cap = 0;
-      const uint32_t cap = c->ntiles + 1 + c->ntiles / 8;
-      CK(c, hipMalloc(&c->d_defer_mask, (size_t)cap * 2 * (TILE_THREADS / 64) * sizeof(unsigned long long)));
-      CK(c, hipMalloc(&c->d_tile_box, (size_t)cap * 8 * sizeof(int)));
-      c->tile_aux_cap = cap;
+    if (((size_t)c->ntiles + 1) * 8 > c->d_tile_box.capacity() || !c->d_defer_mask) {      // (sized together, with room to grow)
+      c->d_tile_box.reset();
+      c->d_defer_mask.reset();
+      const size_t cap = (size_t)c->ntiles + 1 + c->ntiles / 8;
+      CK(c, c->d_defer_mask.alloc(cap * 2 * (TILE_THREADS / 64)));
+      CK(c, c->d_tile_box.alloc(cap * 8));
     }
     CK(c, hipMemsetAsync(c->d_defer_mask, 0, ((size_t)c->ntiles + 1) * 2 * (TILE_THREADS / 64) * sizeof(unsigned long long), c->stream));
     {   // the tiled search with in-tile accumulation leaves one row of partial sums per tile and per block of its clean-up pass
@@ -609,8 +542,8 @@ int cilhip::ensure_sorted(cilhip_ctx* c, const float T[16]) {
     }
     if (c->d_src_nrm) launch_gather_by_w(c->d_src_sorted, c->d_src_nrm, c->ns, c->d_src_nrm_sorted, c->stream);
     if (c->d_src_rgb) launch_gather_by_w(c->d_src_sorted, c->d_src_rgb, c->ns, c->d_src_rgb_sorted, c->stream);
-    dev_free(c->d_src_inv);
-    dev_free(c->d_grid_to_sorted);
+    c->d_src_inv.reset();
+    c->d_grid_to_sorted.reset();
     memcpy(c->sort_T, T, sizeof(c->sort_T));
     c->src_sorted = true;
     c->src3_valid = false; c->rec_valid = false; c->lb_fresh = false;     // (per sorted order)
@@ -635,8 +568,8 @@ int cilhip_prepare_source(cilhip_ctx* c, const float* T, int force, double* ms) 
 // the matches records / margin keys / 12-byte source copy of the warm-started iterations: allocated by the first run that can use them
 int cilhip::ensure_warm_buffers(cilhip_ctx* c) {
   const size_t cap = c->ns ? c->ns : 1;
-  if (!c->d_warm_rec) { CK(c, hipMalloc(&c->d_warm_rec, cap * (sizeof(float4) + 2 * sizeof(F3)))); c->src3_valid = false; }
-  if (!c->d_nn_lb) CK(c, hipMalloc(&c->d_nn_lb, cap * sizeof(float)));
+  if (!c->d_warm_rec) { CK(c, c->d_warm_rec.alloc((cap * (sizeof(float4) + 2 * sizeof(F3)) + sizeof(float4) - 1) / sizeof(float4))); c->src3_valid = false; }      // (one allocation, three views: set_warm_args)
+  if (!c->d_nn_lb) CK(c, c->d_nn_lb.alloc(cap));
   if (!c->src3_valid) {
     launch_copy_src3(c->d_src_sorted, c->ns, reinterpret_cast<F3*>(c->d_warm_rec + cap) + cap, c->stream);
     c->src3_valid = true;
@@ -647,10 +580,9 @@ int cilhip::ensure_warm_buffers(cilhip_ctx* c) {
 // that streams over stored matches with a metric that reads normals (32 B per target point; without room for it the two arrays serve)
 void cilhip::ensure_pair_records(cilhip_ctx* c) {
   if (c->grid.pn || !c->pair_records || !c->grid.nrm || !c->grid.n) return;
-  float4* pn = nullptr;
-  if (hipMalloc(&pn, (size_t)c->grid.n * 2 * sizeof(float4)) != hipSuccess) { (void)hipGetLastError(); return; }
-  launch_interleave_pn(c->grid.pts, c->grid.nrm, c->grid.n, pn, c->stream);
-  c->grid.pn = pn;
+  if (c->grid_store.pn.alloc((size_t)c->grid.n * 2) != hipSuccess) { (void)hipGetLastError(); return; }      // (without room for it the two arrays serve)
+  launch_interleave_pn(c->grid.pts, c->grid.nrm, c->grid.n, c->grid_store.pn, c->stream);
+  c->grid.pn = c->grid_store.pn;
 }
 void cilhip::set_warm_args(const cilhip_ctx* c, IterArgs& wa) {
   const size_t cap = c->ns ? c->ns : 1;
@@ -670,7 +602,7 @@ static CorrWeights corr_weights_of(const cilhip_ctx* c, bool combined_metric, fl
   w.plane_coeff = -0.5f / (c->cw_plane_sigma * c->cw_plane_sigma);
   w.w_p2p = w_p2p; w.w_p2pl = w_p2pl;
   // (a caller's own evaluators: prepare_pair_weights() has put the weights of the stored correspondences into the tables)
-  if (w.enabled && c->weight_fn) { w.point_table = c->d_wtab; w.plane_table = c->d_wtab + c->wtab_cap; }
+  if (w.enabled && c->weight_fn) { w.point_table = c->d_wtab; w.plane_table = c->d_wtab + c->d_wtab.capacity() / 2; }
   return w;
 }
 CorrWeights cilhip::corr_weights_of(const cilhip_ctx* c, const cilhip_icp_params* p) {
@@ -679,7 +611,7 @@ CorrWeights cilhip::corr_weights_of(const cilhip_ctx* c, const cilhip_icp_params
 // k_self_nn's nearest-other-point table (4 B per target point, 0.5 ms at 10M): built by the first warm-capable run on a target
 int cilhip::ensure_safe2(cilhip_ctx* c) {
   if (c->d_safe2) return CILHIP_OK;
-  CK(c, hipMalloc(&c->d_safe2, (c->grid.n ? c->grid.n : 1) * sizeof(float)));
+  CK(c, c->d_safe2.alloc(c->grid.n));
   launch_self_nn(c->grid, c->d_safe2, c->stream);
   return CILHIP_OK;
 }
@@ -717,12 +649,12 @@ static int load_tie_tables(cilhip_ctx* c, const uint32_t* leaf_by_index, const u
   CK(c, hipSetDevice(c->device));
   drop_tie_tables(c);
   const size_t n = c->grid.n;
-  uint32_t *d_leaf = nullptr, *d_slot = nullptr;
+  DevBuf<uint32_t> d_leaf, d_slot;
   // (d_tie_leaf_slot != null is the "tables loaded" flag: nothing may be left half set when an allocation fails)
-  hipError_t e = hipMalloc(&c->d_tie_leaf_slot, (n ? n : 1) * sizeof(uint2));
-  if (e == hipSuccess) e = hipMalloc(&c->d_tie_nodes, (n_nodes ? n_nodes : 1) * sizeof(uint4));
-  if (e == hipSuccess) e = hipMalloc(&d_leaf, (n ? n : 1) * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMalloc(&d_slot, (n ? n : 1) * sizeof(uint32_t));
+  hipError_t e = c->d_tie_leaf_slot.alloc(n);
+  if (e == hipSuccess) e = c->d_tie_nodes.alloc(n_nodes);
+  if (e == hipSuccess) e = d_leaf.alloc(n);
+  if (e == hipSuccess) e = d_slot.alloc(n);
   if (e == hipSuccess && n) {
     e = hipMemcpyAsync(d_leaf, leaf_by_index, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_slot, slot_by_index, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
@@ -730,8 +662,6 @@ static int load_tie_tables(cilhip_ctx* c, const uint32_t* leaf_by_index, const u
     if (e == hipSuccess) { launch_tie_tables_by_position(c->grid.pts, c->grid.n, d_leaf, d_slot, c->d_tie_leaf_slot, c->stream); e = hipGetLastError(); }
   }
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      // (the host arrays and the two staging buffers live on this frame)
-  if (d_leaf) (void)hipFree(d_leaf);
-  if (d_slot) (void)hipFree(d_slot);
   if (e != hipSuccess) { drop_tie_tables(c); c->err = std::string("tie_rule: loading the order tables: ") + hipGetErrorString(e); return CILHIP_ERR_HIP; }
   c->tie_max_depth = 0;
   for (size_t k = 0; k < n_nodes; ++k) c->tie_max_depth = std::max(c->tie_max_depth, (int)(nodes[k].info >> 3));
@@ -740,20 +670,18 @@ static int load_tie_tables(cilhip_ctx* c, const uint32_t* leaf_by_index, const u
 // The order tables of a tree over this context's target, built on the device (tie_build.hip): `build` fills leaf and slot by original
 // index and the nodes; the tables by sorted position go to *leaf_slot.  On failure the caller drops what *leaf_slot holds.
 template <class Build>
-static hipError_t build_target_order_tables(cilhip_ctx* c, uint2** leaf_slot, uint4** nodes, Build build) {
+static hipError_t build_target_order_tables(cilhip_ctx* c, SharedBuf<uint2>& leaf_slot, SharedBuf<uint4>& nodes, Build build) {
   const uint32_t n = c->grid.n;
-  uint32_t *d_leaf = nullptr, *d_slot = nullptr;
-  uint4* d_nodes = nullptr;
-  hipError_t e = hipMalloc(&d_leaf, (n ? n : 1) * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMalloc(&d_slot, (n ? n : 1) * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMalloc(leaf_slot, (n ? n : 1) * sizeof(uint2));
-  if (e == hipSuccess) e = build(d_leaf, d_slot, &d_nodes);
-  if (e == hipSuccess && !d_nodes) e = hipMalloc(&d_nodes, sizeof(uint4));      // (an empty target)
-  if (e == hipSuccess && n) { launch_tie_tables_by_position(c->grid.pts, n, d_leaf, d_slot, *leaf_slot, c->stream); e = hipGetLastError(); }
+  DevBuf<uint32_t> d_leaf, d_slot;
+  DevBuf<uint4> d_nodes;
+  hipError_t e = d_leaf.alloc(n);
+  if (e == hipSuccess) e = d_slot.alloc(n);
+  if (e == hipSuccess) e = leaf_slot.alloc(n);
+  if (e == hipSuccess) e = build(d_leaf.get(), d_slot.get(), &d_nodes);
+  if (e == hipSuccess && !d_nodes) e = d_nodes.alloc(1);      // (an empty target)
+  if (e == hipSuccess && n) { launch_tie_tables_by_position(c->grid.pts, n, d_leaf, d_slot, leaf_slot, c->stream); e = hipGetLastError(); }
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  dev_free(d_leaf); dev_free(d_slot);
-  if (e != hipSuccess) dev_free(d_nodes);
-  else *nodes = d_nodes;
+  if (e == hipSuccess) e = nodes.adopt(std::move(d_nodes));
   return e;
 }
 // The tables of THIS context's target, from the grid's own records.
@@ -764,7 +692,7 @@ static int build_tie_tables(cilhip_ctx* c) {
   drop_tie_tables(c);
   size_t n_nodes = 0;
   int depth = 0;
-  const hipError_t e = build_target_order_tables(c, &c->d_tie_leaf_slot, &c->d_tie_nodes, [&](uint32_t* leaf, uint32_t* slot, uint4** nodes) {
+  const hipError_t e = build_target_order_tables(c, c->d_tie_leaf_slot, c->d_tie_nodes, [&](uint32_t* leaf, uint32_t* slot, DevBuf<uint4>* nodes) {
     return tie_order_build_device(nullptr, c->grid.pts, c->grid.n, c->stream, leaf, slot, nodes, &n_nodes, &depth); });
   if (e != hipSuccess) {
     drop_tie_tables(c);
@@ -801,27 +729,22 @@ static int build_rev_tie_tables(cilhip_ctx* c, const float T[16]) {
   const uint32_t n = c->ns;
   if (!c->has_src_grid || n == 0) return CILHIP_OK;
   CK(c, hipSetDevice(c->device));
-  float* d_q = nullptr;
-  uint32_t *d_leaf = nullptr, *d_slot = nullptr;
-  uint4* d_nodes = nullptr;
+  DevBuf<float> d_q;
+  DevBuf<uint32_t> d_leaf, d_slot;
+  DevBuf<uint4> d_nodes;
   size_t n_nodes = 0;
-  hipError_t e = hipMalloc(&d_q, (size_t)n * 3 * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&d_leaf, (size_t)n * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMalloc(&d_slot, (size_t)n * sizeof(uint32_t));
-  if (e == hipSuccess && !c->d_rev_tie_leaf_slot) e = hipMalloc(&c->d_rev_tie_leaf_slot, (size_t)n * sizeof(uint2));
+  hipError_t e = d_q.alloc((size_t)n * 3);
+  if (e == hipSuccess) e = d_leaf.alloc(n);
+  if (e == hipSuccess) e = d_slot.alloc(n);
+  if (e == hipSuccess && !c->d_rev_tie_leaf_slot) e = c->d_rev_tie_leaf_slot.alloc(n);
   if (e == hipSuccess) { launch_transform_original_host_T(c->d_src_xyz, n, T, d_q, c->stream); e = hipGetLastError(); }      // q = fl(T s), the engine's pinned expression
   if (e == hipSuccess) e = tie_order_build_device(d_q, nullptr, n, c->stream, d_leaf, d_slot, &d_nodes, &n_nodes, nullptr);
   if (e == hipSuccess) {
-    if (c->d_rev_tie_nodes) (void)hipFree(c->d_rev_tie_nodes);
-    c->d_rev_tie_nodes = d_nodes; c->rev_tie_nodes_cap = n_nodes; d_nodes = nullptr;
+    c->d_rev_tie_nodes = std::move(d_nodes);
     launch_tie_tables_by_position(c->src_grid.pts, n, d_leaf, d_slot, c->d_rev_tie_leaf_slot, c->stream);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (d_q) (void)hipFree(d_q);
-  if (d_leaf) (void)hipFree(d_leaf);
-  if (d_slot) (void)hipFree(d_slot);
-  if (d_nodes) (void)hipFree(d_nodes);
   if (e != hipSuccess) { c->err = std::string("tie_rule: the transformed source's order tables: ") + hipGetErrorString(e); return CILHIP_ERR_HIP; }
   memcpy(c->rev_tie_T, T, sizeof(c->rev_tie_T));
   c->rev_tie_valid = true;
@@ -839,7 +762,7 @@ static int build_feat_tie_tables(cilhip_ctx* c) {
   const int dim = c->feature_kind == 2 ? 9 : 6;
   if (!f.dst || (dim == 9 && !f.dst2)) return fail(c, CILHIP_ERR_INVALID, "tie_rule: the target's feature attributes (normals / colours) are not set");
   size_t n_nodes = 0;
-  const hipError_t e = build_target_order_tables(c, &c->d_tief_leaf_slot, &c->d_tief_nodes, [&](uint32_t* leaf, uint32_t* slot, uint4** nodes) {
+  const hipError_t e = build_target_order_tables(c, c->d_tief_leaf_slot, c->d_tief_nodes, [&](uint32_t* leaf, uint32_t* slot, DevBuf<uint4>* nodes) {
     return tie_order_build_device_features(dim, c->grid.pts, f.dst, f.w, f.dst2, f.w2, c->grid.n, c->stream, leaf, slot, nodes, &n_nodes, nullptr); });
   if (e != hipSuccess) {
     drop_feat_tie_tables(c);
@@ -904,12 +827,12 @@ int cilhip::tie_check_pending(cilhip_ctx* c, bool* again) {
 int cilhip::apply_filters(cilhip_ctx* c) {
   if (!filters_active(c) || c->ns == 0) return CILHIP_OK;
   if (c->inlier_fraction > 0.0 && c->inlier_fraction < 1.0) {
-    if (!c->d_keys) CK(c, hipMalloc(&c->d_keys, (size_t)c->ns * sizeof(unsigned long long)));
-    if (!c->d_sel_state) CK(c, hipMalloc(&c->d_sel_state, filter_state_bytes()));
+    if (!c->d_keys) CK(c, c->d_keys.alloc(c->ns));
+    if (!c->d_sel_state) CK(c, c->d_sel_state.alloc(filter_state_bytes()));
     launch_filter_fraction(c->d_src_sorted, c->d_nn_pos, c->d_nn_d2, c->ns, c->inlier_fraction, c->d_keys, c->d_sel_state, c->stream);
   }
   if (c->one_to_one && c->grid.n) {
-    if (!c->d_winner) CK(c, hipMalloc(&c->d_winner, (size_t)c->grid.n * sizeof(unsigned long long)));
+    if (!c->d_winner) CK(c, c->d_winner.alloc(c->grid.n));
     launch_filter_one_to_one(c->d_src_sorted, c->d_nn_pos, c->d_nn_d2, c->ns, c->d_winner, c->grid.n, c->stream);
   }
   CK(c, hipGetLastError());
@@ -937,7 +860,7 @@ int cilhip::ensure_feature_arrays(cilhip_ctx* c) {
   if (c->feature_kind == 0) return CILHIP_OK;
   if (!c->d_dst_rgb || !c->d_src_rgb) return fail(c, CILHIP_ERR_INVALID, "colour features: cilhip_set_color_features first");
   if (!c->dst_rgb_sorted_ok) {
-    if (!c->d_dst_rgb_sorted) CK(c, hipMalloc(&c->d_dst_rgb_sorted, (c->grid.n ? c->grid.n : 1) * sizeof(float4)));
+    if (!c->d_dst_rgb_sorted) CK(c, c->d_dst_rgb_sorted.alloc(c->grid.n));
     launch_gather_by_w(c->grid.pts, c->d_dst_rgb, c->grid.n, c->d_dst_rgb_sorted, c->stream);
     c->dst_rgb_sorted_ok = true;
   }
@@ -1000,10 +923,10 @@ static int ensure_src_grid(cilhip_ctx* c) {
     const hipError_t eg = build_grid(c->d_src_xyz, attr, c->ns, c->stream, &r, mean, 1.0);
     if (eg == GRID_RANGE_ERROR) { c->err = std::string("source grid: ") + kGridRangeMessage; return CILHIP_ERR_UNSUPPORTED; }
     if (eg != hipSuccess) { c->err = std::string("build_grid (source): ") + hipGetErrorString(eg); return CILHIP_ERR_HIP; }
-    c->src_grid = r.grid; c->has_src_grid = true;
+    c->src_grid = r.grid; c->src_grid_store = std::move(r.store); c->has_src_grid = true;
   }
   if (c->has_src_grid && c->feature_kind == 2 && c->d_src_rgb && !c->d_src_rgb_grid) {      // 9-D: the colours in the same order
-    CK(c, hipMalloc(&c->d_src_rgb_grid, (c->ns ? c->ns : 1) * sizeof(float4)));
+    CK(c, c->d_src_rgb_grid.alloc(c->ns));
     launch_gather_by_w(c->src_grid.pts, c->d_src_rgb, c->ns, c->d_src_rgb_grid, c->stream);
   }
   return CILHIP_OK;
@@ -1013,19 +936,19 @@ int cilhip::ensure_reverse_buffers(cilhip_ctx* c) {
   const int rc = ensure_src_grid(c);
   if (rc) return rc;
   if (!c->d_rev_pos) {
-    CK(c, hipMalloc(&c->d_rev_pos, (c->grid.n ? c->grid.n : 1) * sizeof(uint32_t)));
-    CK(c, hipMalloc(&c->d_rev_d2, (c->grid.n ? c->grid.n : 1) * sizeof(float)));
+    CK(c, c->d_rev_pos.alloc(c->grid.n));
+    CK(c, c->d_rev_d2.alloc(c->grid.n));
   }
   if (!c->d_src_safe2 && c->has_src_grid && c->reverse_warm) {      // (lives and dies with the source grid: drop_src_grid)
-    CK(c, hipMalloc(&c->d_src_safe2, (c->ns ? c->ns : 1) * sizeof(float)));
+    CK(c, c->d_src_safe2.alloc(c->ns));
     launch_self_nn(c->src_grid, c->d_src_safe2, c->stream);
   }
   if (!c->d_src_inv) {      // original source index -> position in the cube-sorted source (the forward matches are stored by that)
-    CK(c, hipMalloc(&c->d_src_inv, (c->ns ? c->ns : 1) * sizeof(uint32_t)));
+    CK(c, c->d_src_inv.alloc(c->ns));
     launch_inv_perm(c->d_src_sorted, c->ns, c->d_src_inv, c->stream);
   }
   if (!c->d_grid_to_sorted && c->has_src_grid) {
-    CK(c, hipMalloc(&c->d_grid_to_sorted, (c->ns ? c->ns : 1) * sizeof(uint32_t)));
+    CK(c, c->d_grid_to_sorted.alloc(c->ns));
     launch_grid_to_sorted(c->src_grid.pts, c->ns, c->d_src_inv, c->d_grid_to_sorted, c->stream);
   }
   return CILHIP_OK;
@@ -1033,7 +956,7 @@ int cilhip::ensure_reverse_buffers(cilhip_ctx* c) {
 
 int cilhip::run_pair_search(cilhip_ctx* c, const IterArgs& a, float max_sq, const float T_host[16]) {
   if (!c->d_state_id) {
-    CK(c, hipMalloc(&c->d_state_id, sizeof(IcpState)));
+    CK(c, c->d_state_id.alloc(1));
     const float zero[3] = {0, 0, 0};
     launch_init_state(c->d_state_id, kIdentity16, zero, c->stream);
   }
@@ -1127,8 +1050,8 @@ static int ensure_d2(cilhip_ctx* c) {
 static int scatter_to_original(cilhip_ctx* c) {
   { const int drc = ensure_d2(c); if (drc) return drc; }
   const size_t cap = c->ns ? c->ns : 1;
-  if (!c->d_out_idx) CK(c, hipMalloc(&c->d_out_idx, cap * sizeof(uint32_t)));
-  if (!c->d_out_d2) CK(c, hipMalloc(&c->d_out_d2, cap * sizeof(float)));
+  if (!c->d_out_idx) CK(c, c->d_out_idx.alloc(cap));
+  if (!c->d_out_d2) CK(c, c->d_out_d2.alloc(cap));
   launch_scatter_nn(c->d_src_sorted, c->grid.pts, c->d_nn_pos, c->d_nn_d2, c->ns, c->d_out_idx, c->d_out_d2, c->stream);
   CK(c, hipGetLastError());
   return CILHIP_OK;
@@ -1145,13 +1068,12 @@ static int materialize_pending(cilhip_ctx* c) {
   c->pending_matches = false;
   // (the search runs through the context's loop state: the finished run's state -- what cilhip_icp_state and
   //  cilhip_get_slab_violation_state report -- is put back afterwards)
-  IcpState* keep = nullptr;
-  CK(c, hipMalloc(&keep, sizeof(IcpState)));
+  DevBuf<IcpState> keep;
+  CK(c, keep.alloc(1));
   hipError_t e = hipMemcpyAsync(keep, c->d_state, sizeof(IcpState), hipMemcpyDeviceToDevice, c->stream);
   int rc = e == hipSuccess ? cilhip_find_correspondences(c, T, r, nullptr) : CILHIP_ERR_HIP;
   if (e == hipSuccess) e = hipMemcpyAsync(c->d_state, keep, sizeof(IcpState), hipMemcpyDeviceToDevice, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(keep);
   if (e != hipSuccess && rc == CILHIP_OK) { c->err = std::string("materialize_pending: ") + hipGetErrorString(e); rc = CILHIP_ERR_HIP; }
   if (rc == CILHIP_OK) c->matches_origin = 2;
   return rc;
@@ -1191,11 +1113,11 @@ int cilhip_tie_order_create(const float* xyz, size_t n, cilhip_tie_order** out) 
   int ndev = 0, dev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipGetDevice(&dev) != hipSuccess) return CILHIP_ERR_NO_DEVICE;      // (built on the device: no CPU fallback)
   cilhip_tie_order* o = nullptr;
-  float* d_xyz = nullptr;
-  uint32_t *d_leaf = nullptr, *d_slot = nullptr;
-  uint4* d_nodes = nullptr;
+  DevBuf<float> d_xyz;
+  DevBuf<uint32_t> d_leaf, d_slot;
+  DevBuf<uint4> d_nodes;
   size_t n_nodes = 0;
-  hipStream_t s = nullptr;
+  StreamGuard s;      // (declared last: drained and destroyed before the buffers go)
   hipError_t e = hipSuccess;
   int rc = CILHIP_OK;
   try {
@@ -1203,10 +1125,10 @@ int cilhip_tie_order_create(const float* xyz, size_t n, cilhip_tie_order** out) 
     o->n = (uint32_t)n;
     o->leaf.assign(n, 0u); o->slot.assign(n, 0u);
     if (n) {
-      e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-      if (e == hipSuccess) e = hipMalloc(&d_xyz, n * 3 * sizeof(float));
-      if (e == hipSuccess) e = hipMalloc(&d_leaf, n * sizeof(uint32_t));
-      if (e == hipSuccess) e = hipMalloc(&d_slot, n * sizeof(uint32_t));
+      e = s.create();
+      if (e == hipSuccess) e = d_xyz.alloc(n * 3);
+      if (e == hipSuccess) e = d_leaf.alloc(n);
+      if (e == hipSuccess) e = d_slot.alloc(n);
       if (e == hipSuccess) e = hipMemcpyAsync(d_xyz, xyz, n * 3 * sizeof(float), hipMemcpyHostToDevice, s);
       if (e == hipSuccess) e = tie_order_build_device(d_xyz, nullptr, (uint32_t)n, s, d_leaf, d_slot, &d_nodes, &n_nodes, &o->max_depth);
       if (e == hipSuccess) { o->nodes.resize(n_nodes); e = hipMemcpyAsync(o->nodes.data(), d_nodes, n_nodes * sizeof(uint4), hipMemcpyDeviceToHost, s); }
@@ -1215,11 +1137,6 @@ int cilhip_tie_order_create(const float* xyz, size_t n, cilhip_tie_order** out) 
       if (e == hipSuccess) e = hipStreamSynchronize(s);
     }
   } catch (...) { rc = CILHIP_ERR_HIP; }      // (out of host memory: never across the C boundary)
-  if (d_xyz) (void)hipFree(d_xyz);
-  if (d_leaf) (void)hipFree(d_leaf);
-  if (d_slot) (void)hipFree(d_slot);
-  if (d_nodes) (void)hipFree(d_nodes);
-  if (s) (void)hipStreamDestroy(s);
   if (e != hipSuccess) rc = CILHIP_ERR_HIP;
   if (rc != CILHIP_OK) { delete o; return rc; }
   *out = o;
@@ -1393,15 +1310,13 @@ static int prepare_pair_weights(cilhip_ctx* c) {
 static int prepare_pair_weights_impl(cilhip_ctx* c) {
   const bool pairs = c->have_pairs;
   const size_t slots = pairs ? c->pairs.count : c->ns;      // stream positions
-  if (slots > c->wtab_cap || !c->d_wtab) {
-    if (c->d_wtab) (void)hipFree(c->d_wtab);
-    if (c->d_wtab_in) (void)hipFree(c->d_wtab_in);
-    c->d_wtab = c->d_wtab_in = nullptr; c->wtab_cap = 0;
+  if (2 * slots > c->d_wtab.capacity() || !c->d_wtab || !c->d_wtab_in) {
+    c->d_wtab.reset(); c->d_wtab_in.reset();
     const size_t cap = slots ? slots : 1;
-    CK(c, hipMalloc(&c->d_wtab, 2 * cap * sizeof(float)));
-    CK(c, hipMalloc(&c->d_wtab_in, 2 * cap * sizeof(float)));
-    c->wtab_cap = cap;
+    CK(c, c->d_wtab.alloc(2 * cap));
+    CK(c, c->d_wtab_in.alloc(2 * cap));
   }
+  const size_t half = c->d_wtab.capacity() / 2;      // the plane weights' table follows the point weights' (corr_weights_of)
   if (slots == 0) return CILHIP_OK;
   std::vector<uint64_t> i1(slots), i2(slots);
   std::vector<float> val(slots), wq(slots, 0.0f), wl(slots, 0.0f);
@@ -1425,15 +1340,15 @@ static int prepare_pair_weights_impl(cilhip_ctx* c) {
   if (cnt) c->weight_fn(c->weight_user, i1.data(), i2.data(), val.data(), cnt, wq.data(), wl.data());
   if (pairs) {
     CK(c, hipMemcpyAsync(c->d_wtab, wq.data(), slots * 4, hipMemcpyHostToDevice, c->stream));
-    CK(c, hipMemcpyAsync(c->d_wtab + c->wtab_cap, wl.data(), slots * 4, hipMemcpyHostToDevice, c->stream));
+    CK(c, hipMemcpyAsync(c->d_wtab + half, wl.data(), slots * 4, hipMemcpyHostToDevice, c->stream));
   } else {
     // by original source index (unmatched: 0, never read), then into the sorted order the pass streams over
     std::vector<float> oq(slots, 0.0f), ol(slots, 0.0f);
     for (size_t k = 0; k < cnt; ++k) { oq[i2[k]] = wq[k]; ol[i2[k]] = wl[k]; }
     CK(c, hipMemcpyAsync(c->d_wtab_in, oq.data(), slots * 4, hipMemcpyHostToDevice, c->stream));
-    CK(c, hipMemcpyAsync(c->d_wtab_in + c->wtab_cap, ol.data(), slots * 4, hipMemcpyHostToDevice, c->stream));
+    CK(c, hipMemcpyAsync(c->d_wtab_in + half, ol.data(), slots * 4, hipMemcpyHostToDevice, c->stream));
     launch_gather1_by_w(c->d_src_sorted, c->d_wtab_in, (uint32_t)slots, c->d_wtab, c->stream);
-    launch_gather1_by_w(c->d_src_sorted, c->d_wtab_in + c->wtab_cap, (uint32_t)slots, c->d_wtab + c->wtab_cap, c->stream);
+    launch_gather1_by_w(c->d_src_sorted, c->d_wtab_in + half, (uint32_t)slots, c->d_wtab + half, c->stream);
   }
   CK(c, hipStreamSynchronize(c->stream));      // (the host vectors go out of scope)
   return CILHIP_OK;
@@ -1807,7 +1722,7 @@ int cilhip_get_slab_violation(cilhip_ctx* c, int* out) {
   if (!c || !out) return CILHIP_ERR_INVALID;
   CK(c, hipSetDevice(c->device));
   int v = 0;
-  CK(c, hipMemcpyAsync(&v, reinterpret_cast<const char*>(c->d_state) + offsetof(IcpState, slab_violation), sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  CK(c, hipMemcpyAsync(&v, reinterpret_cast<const char*>(c->d_state.get()) + offsetof(IcpState, slab_violation), sizeof(int), hipMemcpyDeviceToHost, c->stream));
   CK(c, hipStreamSynchronize(c->stream));
   *out = v;
   return CILHIP_OK;
@@ -1868,7 +1783,7 @@ int cilhip_icp_sums_from_keys(cilhip_ctx* c, const uint64_t* keys_dev, double* s
   if (!c->run_active) return fail(c, CILHIP_ERR_INVALID, "icp_begin first");
   CK(c, hipSetDevice(c->device));
   if (!c->d_inv_perm) {
-    CK(c, hipMalloc(&c->d_inv_perm, (c->grid.n ? c->grid.n : 1) * sizeof(uint32_t)));
+    CK(c, c->d_inv_perm.alloc(c->grid.n));
     launch_inv_perm(c->grid.pts, c->grid.n, c->d_inv_perm, c->stream);
   }
   return sums_of_selected(c, sums_dev, [&] {
@@ -1890,7 +1805,7 @@ int cilhip_icp_order_keys(cilhip_ctx* c, const uint64_t* win_keys_dev, uint64_t*
   if (!c->d_tie_leaf_slot) return fail(c, CILHIP_ERR_INVALID, "icp_order_keys: load the whole target's tie order first (cilhip_load_tie_order)");
   if (c->tie_max_depth > 58) return fail(c, CILHIP_ERR_UNSUPPORTED, "icp_order_keys: the order tree is deeper than the 58 levels a traversal key holds");
   CK(c, hipSetDevice(c->device));
-  if (!c->d_own_order) CK(c, hipMalloc(&c->d_own_order, (c->ns ? c->ns : 1) * sizeof(unsigned long long)));
+  if (!c->d_own_order) CK(c, c->d_own_order.alloc(c->ns));
   TieDev t = tie_dev_of(c);
   launch_order_keys(c->d_src_sorted, c->d_state, reinterpret_cast<const unsigned long long*>(win_keys_dev), c->d_nn_pos, c->d_nn_d2, c->ns, t,
                     c->d_own_order, reinterpret_cast<unsigned long long*>(order_keys_dev), c->stream);
@@ -1919,20 +1834,20 @@ int cilhip_compute_residuals(cilhip_ctx* c, int metric, float w_p2p, float w_p2p
   if (rc) return rc;
   launch_init_state(c->d_state, T, c->src_mean, c->stream, nullptr, 0, nullptr, nullptr, c->d_tie_counters);
   IterArgs a = make_iter_args(c, 3.402823466e+38f);
-  float* d_out = out;
-  if (mem != CILHIP_MEM_DEVICE) CK(c, hipMalloc(&d_out, (c->ns ? c->ns : 1) * sizeof(float)));
+  DevBuf<float> staging;      // (host output: the residuals are formed on the device first)
+  if (mem != CILHIP_MEM_DEVICE) CK(c, staging.alloc(c->ns));
+  float* d_out = mem != CILHIP_MEM_DEVICE ? staging.get() : out;
   launch_residuals(a, metric, w_p2p, w_p2pl, d_out, c->stream);
   CK(c, hipGetLastError());
   if (metric != 0) {      // (the point-to-plane term reads the matched point's normal: which of two equidistant points matters)
     bool again = false;
     rc = tie_check_pending(c, &again);
-    if (rc) { if (mem != CILHIP_MEM_DEVICE) (void)hipFree(d_out); return rc; }
+    if (rc) return rc;
     if (again) { a = make_iter_args(c, 3.402823466e+38f); launch_residuals(a, metric, w_p2p, w_p2pl, d_out, c->stream); CK(c, hipGetLastError()); }
   }
   if (mem != CILHIP_MEM_DEVICE) {
     if (c->ns) CK(c, hipMemcpyAsync(out, d_out, (size_t)c->ns * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     CK(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(d_out);
   }
   return CILHIP_OK;
 }

@@ -263,29 +263,6 @@ unsigned cc_bits(uint32_t v) {      // bits that hold 0 .. v
   return b;
 }
 
-// device allocations of one call: freed on every way out
-struct CcPool {
-  std::vector<void*> p;
-  ~CcPool() { for (void* q : p) (void)hipFree(q); }
-  template <typename T>
-  hipError_t get(T** out, size_t bytes) {
-    void* q = nullptr;
-    hipError_t e = hipMalloc(&q, bytes ? bytes : 16);
-    if (e == hipSuccess) p.push_back(q);
-    *out = static_cast<T*>(q);
-    return e;
-  }
-};
-struct CcStream {
-  hipStream_t s = nullptr;
-  ~CcStream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
-};
-struct CcGrid {
-  GridBuildResult gr{};
-  bool have = false;
-  ~CcGrid() { if (have) free_grid(gr.grid); }
-};
-
 #define CC_CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_stateless_error(std::string("connected_components: ") + #x + ": " + hipGetErrorString(e_)); return CILHIP_ERR_HIP; } } while (0)
 
 struct CcOut {
@@ -299,22 +276,22 @@ struct CcOut {
 };
 
 // everything after the hook step: parent[] (device, over original indices) -> the caller's outputs
-int cc_finish(const CcOut& o, CcPool& pool, hipStream_t s, uint32_t* parent) {
+int cc_finish(const CcOut& o, DevPool& pool, hipStream_t s, uint32_t* parent) {
   const size_t n = o.n;
   const dim3 grid(cc_blocks(n)), block(CC_THREADS);
   uint32_t *root = nullptr, *count = nullptr, *seeded = nullptr, *rank = nullptr;
   unsigned long long *keys = nullptr, *keys_sorted = nullptr;
   unsigned int* n_kept_d = nullptr;
-  CC_CK(pool.get(&root, n * sizeof(uint32_t)));
-  CC_CK(pool.get(&count, n * sizeof(uint32_t)));
-  CC_CK(pool.get(&keys, n * sizeof(unsigned long long)));
-  CC_CK(pool.get(&keys_sorted, n * sizeof(unsigned long long)));
-  CC_CK(pool.get(&n_kept_d, sizeof(unsigned int)));
+  CC_CK(pool.bytes(&root, n * sizeof(uint32_t)));
+  CC_CK(pool.bytes(&count, n * sizeof(uint32_t)));
+  CC_CK(pool.bytes(&keys, n * sizeof(unsigned long long)));
+  CC_CK(pool.bytes(&keys_sorted, n * sizeof(unsigned long long)));
+  CC_CK(pool.bytes(&n_kept_d, sizeof(unsigned int)));
   hipLaunchKernelGGL(k_cc_flatten, grid, block, 0, s, (const uint32_t*)parent, root, n);
   if (o.seeds) {
     uint32_t* d_seeds = nullptr;
-    CC_CK(pool.get(&seeded, n * sizeof(uint32_t)));
-    CC_CK(pool.get(&d_seeds, o.n_seeds * sizeof(uint32_t)));
+    CC_CK(pool.bytes(&seeded, n * sizeof(uint32_t)));
+    CC_CK(pool.bytes(&d_seeds, o.n_seeds * sizeof(uint32_t)));
     CC_CK(hipMemsetAsync(seeded, 0, n * sizeof(uint32_t), s));
     if (o.n_seeds) {
       CC_CK(hipMemcpyAsync(d_seeds, o.seeds, o.n_seeds * sizeof(uint32_t), hipMemcpyHostToDevice, s));
@@ -330,7 +307,7 @@ int cc_finish(const CcOut& o, CcPool& pool, hipStream_t s, uint32_t* parent) {
     size_t tmp_bytes = 0;
     void* tmp = nullptr;
     CC_CK(rocprim::radix_sort_keys(nullptr, tmp_bytes, keys, keys_sorted, n, 0u, 64u, s));
-    CC_CK(pool.get(&tmp, tmp_bytes));
+    CC_CK(pool.bytes(&tmp, tmp_bytes));
     CC_CK(rocprim::radix_sort_keys(tmp, tmp_bytes, keys, keys_sorted, n, 0u, 64u, s));
   }
   unsigned int n_kept = 0;      // the one host round trip of the chain
@@ -341,21 +318,21 @@ int cc_finish(const CcOut& o, CcPool& pool, hipStream_t s, uint32_t* parent) {
   hipLaunchKernelGGL(k_cc_rank, dim3(cc_blocks(n_kept)), block, 0, s, (const unsigned long long*)keys_sorted, (uint32_t)n_kept, rank);
   const bool host = o.mem == CILHIP_MEM_HOST;
   uint32_t* d_labels = o.labels;
-  if (host) CC_CK(pool.get(&d_labels, n * sizeof(uint32_t)));
+  if (host) CC_CK(pool.bytes(&d_labels, n * sizeof(uint32_t)));
   hipLaunchKernelGGL(k_cc_labels, grid, block, 0, s, (const uint32_t*)root, (const uint32_t*)rank, (uint32_t)n_kept, n, d_labels);
   CC_CK(hipGetLastError());
   if (host) CC_CK(hipMemcpyAsync(o.labels, d_labels, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   if (o.offsets || o.members) {
     // a stable sort of the point indices by label: every segment's members in ascending index, the unlabelled points behind them
     uint32_t *iota = root, *lab_sorted = reinterpret_cast<uint32_t*>(keys), *d_members = o.members, *d_offsets = o.offsets;      // (roots and unsorted keys are done with)
-    if (host || !d_members) CC_CK(pool.get(&d_members, n * sizeof(uint32_t)));
-    if (host || !d_offsets) CC_CK(pool.get(&d_offsets, ((size_t)n_kept + 1) * sizeof(uint32_t)));
+    if (host || !d_members) CC_CK(pool.bytes(&d_members, n * sizeof(uint32_t)));
+    if (host || !d_offsets) CC_CK(pool.bytes(&d_offsets, ((size_t)n_kept + 1) * sizeof(uint32_t)));
     hipLaunchKernelGGL(k_cc_init, grid, block, 0, s, iota, n);
     size_t tmp_bytes = 0;
     void* tmp = nullptr;
     const unsigned bits = cc_bits(n_kept);
     CC_CK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_labels, lab_sorted, iota, d_members, n, 0u, bits, s));
-    CC_CK(pool.get(&tmp, tmp_bytes));
+    CC_CK(pool.bytes(&tmp, tmp_bytes));
     CC_CK(rocprim::radix_sort_pairs(tmp, tmp_bytes, d_labels, lab_sorted, iota, d_members, n, 0u, bits, s));
     const uint32_t n32 = (uint32_t)n;
     CC_CK(hipMemcpyAsync(d_offsets + n_kept, &n32, sizeof(uint32_t), hipMemcpyHostToDevice, s));
@@ -369,21 +346,21 @@ int cc_finish(const CcOut& o, CcPool& pool, hipStream_t s, uint32_t* parent) {
   return CILHIP_OK;
 }
 
-int cc_open(int device, CcStream& st) {
+int cc_open(int device, StreamGuard& st) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
     set_stateless_error("connected_components: no such HIP device (the segmentation runs on the device: there is no CPU path)");
     return CILHIP_ERR_NO_DEVICE;
   }
   CC_CK(hipSetDevice(device));
-  CC_CK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+  CC_CK(st.create());
   return CILHIP_OK;
 }
 
 int cc_run_fused(int device, const float* xyz, const float* nrm, const float* rgb, const CcClauses& cl, const CcOut& o) {
-  CcPool pool;
-  CcGrid grid;
-  CcStream st;      // (declared last: the stream is drained and destroyed before anything is freed)
+  DevPool pool;
+  GridBuildResult grid{};      // the radius search's grid
+  StreamGuard st;      // (declared last: the stream is drained and destroyed before anything is freed)
   if (int rc = cc_open(device, st)) return rc;
   hipStream_t s = st.s;
   const size_t n = o.n;
@@ -393,27 +370,26 @@ int cc_run_fused(int device, const float* xyz, const float* nrm, const float* rg
     if (!src[k]) continue;
     if (o.mem == CILHIP_MEM_DEVICE) { d_in[k] = reinterpret_cast<const F3*>(src[k]); continue; }
     F3* d = nullptr;
-    CC_CK(pool.get(&d, n * sizeof(F3)));
+    CC_CK(pool.bytes(&d, n * sizeof(F3)));
     CC_CK(hipMemcpyAsync(d, src[k], n * sizeof(F3), hipMemcpyHostToDevice, s));
     d_in[k] = d;
   }
   uint32_t* parent = nullptr;
-  CC_CK(pool.get(&parent, n * sizeof(uint32_t)));
+  CC_CK(pool.bytes(&parent, n * sizeof(uint32_t)));
   hipLaunchKernelGGL(k_cc_init, dim3(cc_blocks(n)), dim3(CC_THREADS), 0, s, parent, n);
   if (cl.radius_sq > 0.0f) {
     F3* clean = nullptr;
     unsigned int *d_fin = nullptr, n_finite = 0;
-    CC_CK(pool.get(&clean, n * sizeof(F3)));
-    CC_CK(pool.get(&d_fin, sizeof(unsigned int)));
+    CC_CK(pool.bytes(&clean, n * sizeof(F3)));
+    CC_CK(pool.bytes(&d_fin, sizeof(unsigned int)));
     CC_CK(hipMemsetAsync(d_fin, 0, sizeof(unsigned int), s));
     hipLaunchKernelGGL(k_cc_clean, dim3(cc_blocks(n)), dim3(CC_THREADS), 0, s, d_in[0], n, clean, d_fin);
     CC_CK(hipMemcpyAsync(&n_finite, d_fin, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
     CC_CK(hipStreamSynchronize(s));
     if (n_finite > 1) {      // (otherwise nobody has a neighbour)
       double mean[3];
-      CC_CK(build_grid(reinterpret_cast<const float*>(clean), nullptr, (uint32_t)n, s, &grid.gr, mean, 2.0));      // the radius search's grid
-      grid.have = true;
-      hipLaunchKernelGGL(k_cc_hook, dim3((unsigned)((n + CC_THREADS - 1) / CC_THREADS)), dim3(CC_THREADS), 0, s, grid.gr.grid, cl, d_in[1], d_in[2], parent);
+      CC_CK(build_grid(reinterpret_cast<const float*>(clean), nullptr, (uint32_t)n, s, &grid, mean, 2.0));
+      hipLaunchKernelGGL(k_cc_hook, dim3((unsigned)((n + CC_THREADS - 1) / CC_THREADS)), dim3(CC_THREADS), 0, s, grid.grid, cl, d_in[1], d_in[2], parent);
       CC_CK(hipGetLastError());
     }
   }
@@ -421,8 +397,8 @@ int cc_run_fused(int device, const float* xyz, const float* nrm, const float* rg
 }
 
 int cc_run_lists(int device, const uint64_t* offsets, const uint32_t* idx, const unsigned char* keep, size_t n_entries, int skip_first, const CcOut& o) {
-  CcPool pool;
-  CcStream st;
+  DevPool pool;
+  StreamGuard st;
   if (int rc = cc_open(device, st)) return rc;
   hipStream_t s = st.s;
   const size_t n = o.n;
@@ -431,18 +407,18 @@ int cc_run_lists(int device, const uint64_t* offsets, const uint32_t* idx, const
   const unsigned char* d_keep = keep;
   if (o.mem == CILHIP_MEM_HOST) {
     unsigned long long* a = nullptr; uint32_t* b = nullptr; unsigned char* c = nullptr;
-    CC_CK(pool.get(&a, (n + 1) * sizeof(unsigned long long)));
+    CC_CK(pool.bytes(&a, (n + 1) * sizeof(unsigned long long)));
     CC_CK(hipMemcpyAsync(a, offsets, (n + 1) * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
-    CC_CK(pool.get(&b, n_entries * sizeof(uint32_t)));
+    CC_CK(pool.bytes(&b, n_entries * sizeof(uint32_t)));
     if (n_entries) CC_CK(hipMemcpyAsync(b, idx, n_entries * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     if (keep) {
-      CC_CK(pool.get(&c, n_entries));
+      CC_CK(pool.bytes(&c, n_entries));
       if (n_entries) CC_CK(hipMemcpyAsync(c, keep, n_entries, hipMemcpyHostToDevice, s));
     }
     d_off = a; d_idx = b; d_keep = c;
   }
   uint32_t* parent = nullptr;
-  CC_CK(pool.get(&parent, n * sizeof(uint32_t)));
+  CC_CK(pool.bytes(&parent, n * sizeof(uint32_t)));
   hipLaunchKernelGGL(k_cc_init, dim3(cc_blocks(n)), dim3(CC_THREADS), 0, s, parent, n);
   hipLaunchKernelGGL(k_cc_hook_lists, dim3((unsigned)((n + CC_THREADS - 1) / CC_THREADS)), dim3(CC_THREADS), 0, s, d_off, d_idx, d_keep, (unsigned long long)n_entries, (uint32_t)n,
                      skip_first ? 1u : 0u, parent);

@@ -14,13 +14,59 @@
 
 using namespace cilhip;
 
-// Device allocations of a target that SEVERAL contexts use (cilhip_share_target): freed when the last of them lets go.
-struct TargetShare { int refs = 0; std::vector<void*> allocs; };
+// What a context owns on the device, grouped by the event that releases it: a group is let go of by assigning an empty one
+// (c_api.hip: release_target, free_source, drop_src_grid).  Everything else the context owns lives as long as it does.
+// (declared first, destroyed last: the context's own stream outlives every buffer its work used)
+struct CtxStream { StreamGuard own_stream; };
+// ... of the TARGET.  Shareable members are what cilhip_share_target hands to a borrower, buffer by buffer.
+struct TargetBufs {
+  GridStore grid_store;           // the arrays cilhip_ctx::grid views
+  SharedBuf<uint32_t> d_inv_perm;  // [n_target] original local index -> sorted position (built on first use)
+  SharedBuf<uint2> d_tief_leaf_slot;  // [grid.n] the order tables of the FEATURE tree (6-D / 9-D adaptors: points + weighted normals / colours), for the
+  SharedBuf<uint4> d_tief_nodes;  // feature options they were built under (dropped with any of them); TieNode::info with four dimension bits
+  SharedBuf<uint2> d_tie_leaf_slot;  // [grid.n] the order tables by sorted target position (null: not loaded)
+  SharedBuf<uint4> d_tie_nodes;
+  SharedBuf<float> d_safe2;  // [grid.n] k_self_nn's table for the warm-started iteration; built with the target
+  DevBuf<unsigned long long> d_winner;  // [n_target]
+  DevBuf<float> d_dst_rgb;        // colour features, original order (they belong to the target they were set for)
+  DevBuf<float4> d_dst_rgb_sorted;
+  DevBuf<uint32_t> d_rev_pos;     // list-free loops of FIRST_TO_SECOND / BOTH: reverse matches by target position
+  DevBuf<float> d_rev_d2;
+};
+// ... of the SOURCE's own grid (FIRST_TO_SECOND / BOTH) and what is laid out in its order
+struct SrcGridBufs {
+  GridStore src_grid_store;       // the arrays cilhip_ctx::src_grid views
+  DevBuf<float4> d_src_rgb_grid;  // the source's colours in the order of the source's own grid (9-D reverse search)
+  DevBuf<float> d_src_safe2;  // [ns] k_self_nn's table over the SOURCE grid: the margin test of the warm-started reverse search (k_reverse_warm)
+  DevBuf<uint32_t> d_grid_to_sorted;  // [ns] source-grid position -> sorted source position (d_src_inv through the source grid's order): the fused reverse pass's duplicate test
+};
+// ... of the SOURCE
+struct SourceBufs : SrcGridBufs {
+  DevBuf<float> d_src_xyz;  // original order (kept for re-sorting)
+  DevBuf<float4> d_src_sorted;  // sorted cube-major by target-grid cell under sort_T
+  SortWorkspace sort_ws;          // scratch + tile table of sort_source, kept between the sorts of a source (d_tiles / d_tile_center point into it)
+  DevBuf<int> d_tile_box;  // [8*ntiles] cell range of each tile's cube under the current transform (recomputed per search)
+  DevBuf<unsigned long long> d_defer_mask;  // [ntiles * 32] queries the tiles hand to the clean-up pass (bit masks, rewritten by every search)
+  DevBuf<float> d_src_nrm;  // optional source normals, original order (4-cloud ctor => symmetric metric)
+  DevBuf<float4> d_src_nrm_sorted;
+  DevBuf<uint32_t> d_nn_pos;
+  DevBuf<float> d_nn_d2;
+  DevBuf<float4> d_warm_rec;  // [ns] float4 + 2 x [ns] F3: match records {matched point, margin key} {normal} and the 12-byte source copy of the warm-started iterations
+  DevBuf<float> d_nn_lb;  // [ns] margin keys the search-only tile kernel leaves next to nn_pos (IterArgs::nn_lb)
+  DevBuf<uint2> d_rev_tie_leaf_slot;  // [ns] by position in the source grid; valid for rev_tie_T only
+  DevBuf<uint4> d_rev_tie_nodes;
+  DevBuf<uint32_t> d_out_idx;  // [ns] original-order results
+  DevBuf<float> d_out_d2;
+  DevBuf<unsigned long long> d_keys;  // [ns]
+  DevBuf<unsigned long long> d_own_order;  // [ns] this shard's traversal keys of the current iteration (cilhip_icp_order_keys)
+  DevBuf<float> d_src_rgb;
+  DevBuf<float4> d_src_rgb_sorted;
+  DevBuf<uint32_t> d_src_inv;     // ... original -> sorted source position (per sorted order)
+};
 
-struct cilhip_ctx {
+struct cilhip_ctx : CtxStream, TargetBufs, SourceBufs {
+  ~cilhip_ctx();                  // (below: events and the pinned feedback block)
   int device = 0;
-  TargetShare* tshare = nullptr;  // non-null: some of this context's target pointers belong to a share (target_ptr_free / release_target_share)
-  hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
   std::string err;
 
@@ -35,22 +81,15 @@ struct cilhip_ctx {
   uint32_t index_offset = 0;      // global index of this shard's first target point (target-sharded runs)
   bool partial_target = false;    // this context holds only PART of the cloud the reference would index (an index shard, a spatial slab: cilhip_set_shard_info
                                   // with an offset or the whole cloud's mean): the order tables are the WHOLE cloud's -- loaded (cilhip_load_tie_order), never built here
-  uint32_t* d_inv_perm = nullptr; // [n_target] original local index -> sorted position (built on first use)
 
   // source
   bool has_source = false;
   uint32_t ns = 0;
-  float* d_src_xyz = nullptr;     // original order (kept for re-sorting)
-  float4* d_src_sorted = nullptr; // sorted cube-major by target-grid cell under sort_T
-  SortWorkspace sort_ws;          // scratch + tile table of sort_source, kept between the sorts of a source (d_tiles / d_tile_center point into it)
-  uint32_t tile_aux_cap = 0;      // tiles d_tile_box / d_defer_mask are sized for
   uint2* d_tiles = nullptr;       // [ntiles] query ranges of the LDS-tiled search kernel
   float4* d_tile_center = nullptr;  // [ntiles] cube centre of each tile in source space
-  int* d_tile_box = nullptr;        // [8*ntiles] cell range of each tile's cube under the current transform (recomputed per search)
   float tile_axes[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long* d_defer_mask = nullptr;  // [ntiles * 32] queries the tiles hand to the clean-up pass (bit masks, rewritten by every search)
-  uint32_t* d_defer_flag = nullptr;            // [1] "some tile deferred a query" (reset before, set by, every tiled search)
-  uint32_t* d_unproven = nullptr;              // [128] queries the tiles' first stage did not prove / the warm-started kernel listed (summed / zeroed by the epilogue)
+  DevBuf<uint32_t> d_defer_flag;            // [1] "some tile deferred a query" (reset before, set by, every tiled search)
+  DevBuf<uint32_t> d_unproven;              // [128] queries the tiles' first stage did not prove / the warm-started kernel listed (summed / zeroed by the epilogue)
   LoopPolicy policy;                           // the form an ICP iteration takes: warm_banned / far_mode belong to the cloud pair, the rest to one run (loop_policy.hpp)
   Feedback* h_feedback = nullptr;              // pinned, host-coherent: what the epilogue kernel publishes after every iteration (pacing, kernel form)
   Feedback* d_feedback = nullptr;              // the device's address of it
@@ -62,21 +101,15 @@ struct cilhip_ctx {
   double form_ms[5] = {0, 0, 0, 0, 0};    // ... and the kernel time summed per form
   int form_n[5] = {0, 0, 0, 0, 0};
   int warm_start = 1;             // option "warm_start": 0 = never, 1 = when the device reports the source near alignment, 2 = from the second iteration on
-  uint32_t* d_dbg = nullptr;                   // [2] cilhip_debug_counters scratch
-  uint4* d_trace = nullptr;                    // [RUN_TRACE_CAP] per-iteration loop state of the last run, written by the epilogue (cilhip_get_last_run_trace)
+  DevBuf<uint32_t> d_dbg;                   // [2] cilhip_debug_counters scratch
+  DevBuf<uint4> d_trace;                    // [RUN_TRACE_CAP] per-iteration loop state of the last run, written by the epilogue (cilhip_get_last_run_trace)
   uint32_t ntiles = 0;
   int tiled = 1;                  // 0: per-lane global-memory search; 1: LDS-tiled search when the cloud is large enough; 2: always tiled
   bool src_sorted = false;
   float sort_T[16];
   float src_mean[3] = {0, 0, 0};
-  float* d_src_nrm = nullptr;         // optional source normals, original order (4-cloud ctor => symmetric metric)
-  float4* d_src_nrm_sorted = nullptr;
-  uint32_t* d_nn_pos = nullptr;
-  float* d_nn_d2 = nullptr;
-  float4* d_warm_rec = nullptr;   // [ns] float4 + 2 x [ns] F3: match records {matched point, margin key} {normal} and the 12-byte source copy of the warm-started iterations
   bool rec_valid = false;         // the records describe the last executed iteration's matches (inside a run)
   bool src3_valid = false;        // the 12-byte source copy matches d_src_sorted (rewritten after a re-sort)
-  float* d_nn_lb = nullptr;       // [ns] margin keys the search-only tile kernel leaves next to nn_pos (IterArgs::nn_lb)
   bool lb_fresh = false;          // ... and they belong to the search that left nn_pos (inside a run)
   bool warm_forecast = true;      // option "warm_forecast": the cold kernels' count of the queries a warm-started iteration would have to search gates the form
   // option "tie_rule": which of several EXACTLY equidistant nearest target points a correspondence names.  0 = the lowest target index;
@@ -84,13 +117,9 @@ struct cilhip_ctx {
   // choice, the tables built when a search first MEETS a tie (that search / run is then executed again): a target that never ties never
   // pays for a tree.  The device resolves ties inside its search kernels (TieDev, kernels.hip: tie_settle).
   int tie_rule = 2;
-  uint2* d_tief_leaf_slot = nullptr;             // [grid.n] the order tables of the FEATURE tree (6-D / 9-D adaptors: points + weighted normals / colours), for the
-  uint4* d_tief_nodes = nullptr;                 // feature options they were built under (dropped with any of them); TieNode::info with four dimension bits
   int tief_builds = 0;
-  uint2* d_tie_leaf_slot = nullptr;              // [grid.n] the order tables by sorted target position (null: not loaded)
-  uint4* d_tie_nodes = nullptr;
   unsigned int* d_tie_counters = nullptr;        // [4] TieDev::counters
-  unsigned int* d_ticket = nullptr;              // [1] k_reduce_solve's ticket (zero between launches)
+  DevBuf<unsigned int> d_ticket;              // [1] k_reduce_solve's ticket (zero between launches)
   // option "group_search": the global-memory search with SEVERAL lanes per query (k_search_group: small clouds and sources far from
   // alignment, where one lane per query leaves the chip idle behind chains of dependent trips).  -1 (default) = the ICP loop decides per
   // iteration (cold iterations of clouds the tiles do not take: always for clouds below the warm-started form's floor, from the
@@ -111,26 +140,21 @@ struct cilhip_ctx {
   // reverse search has met exactly equidistant source points (or under tie_rule 1) that tree's order tables are built (on the device) before
   // every reverse search (the loops then run host-driven, one search at a time)
   bool rev_tie_aware = false;
-  uint2* d_rev_tie_leaf_slot = nullptr;          // [ns] by position in the source grid; valid for rev_tie_T only
-  uint4* d_rev_tie_nodes = nullptr;
-  size_t rev_tie_nodes_cap = 0;
   bool rev_tie_valid = false;
   float rev_tie_T[16];
   int rev_tie_builds = 0;
   float warm_extra = 0.0625f;     // option "warm_extra_fraction"
   bool pair_records = true;       // option "pair_records": the streaming accumulation gathers a match's point and normal from one 32-byte record (GridDev::pn)
-  void* rank_comm = nullptr; int rank_comm_size = 0; double* d_rank_sums = nullptr;      // cilhip_rank_comm_*: this process' rank in an RCCL communicator
+  void* rank_comm = nullptr; int rank_comm_size = 0; DevBuf<double> d_rank_sums;      // cilhip_rank_comm_*: this process' rank in an RCCL communicator
   bool tile_records = true;       // option "tile_records": the accumulating tile kernel writes the warm-started form's match records itself
   float warm_enter = 0.15f;       // option "warm_enter_fraction": the bar a run starts with, as a fraction of a grid cell
   float src_center[3] = {0, 0, 0}, src_half[3] = {0, 0, 0};   // bounding box of the source (source coordinates): the epilogue's bound on how far a query moves per update
-  float* d_safe2 = nullptr;       // [grid.n] k_self_nn's table for the warm-started iteration; built with the target
   int cw_point_kind = 0, cw_plane_kind = 0;     // correspondence weight evaluators (CW_*), combined metric
   float cw_point_sigma = 1.0f, cw_plane_sigma = 1.0f;
   cilhip_pair_weight_fn weight_fn = nullptr;    // a caller's own evaluators (cilhip_set_pair_weight_callback): the estimates call them on the host
   void* weight_user = nullptr;
-  float* d_wtab = nullptr;        // [2 * wtab_cap] point / plane weights by stream position (CorrWeights::point_table / plane_table)
-  float* d_wtab_in = nullptr;     // [2 * wtab_cap] ... by original source index, as the host filled them
-  size_t wtab_cap = 0;
+  DevBuf<float> d_wtab;           // [2 * cap]: capacity() / 2 entries per table;  point / plane weights by stream position (CorrWeights::point_table / plane_table)
+  DevBuf<float> d_wtab_in;        // [2 * cap] ... by original source index, as the host filled them
   bool have_nn = false;           // nn_pos/nn_d2 hold the result of a search
   bool d2_stale = false;          // ... but nn_d2 has not been formed yet (matches left by a loop whose kernels keep no distances: ensure_d2)
   float nn_T[16];                 // transform used by that search
@@ -142,28 +166,22 @@ struct cilhip_ctx {
   int matches_origin = 0;         // cilhip_get_last_matches_origin
 
   // loop state / scratch
-  IcpState* d_state = nullptr;
-  double* d_partials = nullptr;
-  int partial_blocks = 0;
-  double* d_stage = nullptr;      // [REDUCE_STAGE_DOUBLES] stage-1 rows of the cross-block reduction
-  double* d_sums = nullptr;       // [3 * SUMS_MAX] (the affine estimator reduces three passes before one copy to the host)
+  DevBuf<IcpState> d_state;
+  DevBuf<double> d_partials;      // rows of SUMS_MAX doubles (ensure_partial_rows)
+  DevBuf<double> d_stage;      // [REDUCE_STAGE_DOUBLES] stage-1 rows of the cross-block reduction
+  DevBuf<double> d_sums;       // [3 * SUMS_MAX] (the affine estimator reduces three passes before one copy to the host)
   bool tile_acc_adaptive = true;  // choose one pass / two passes per iteration from the device's feedback (option "tile_accumulation" = 2: always one pass)
   bool tile_acc = true;           // accumulate inside the LDS tiles of the search when the engine allows it (option "tile_accumulation", A/B)
   bool fused = false;             // true: search+accumulate in one kernel; false: search kernel + streaming accumulate kernel (faster: the search runs at 2x the occupancy)
   double cell_occupancy = 1.0;    // target points per grid cell (takes effect at the next set_target)
   double refined_occupancy = 3.0; // option "refined_occupancy_factor": how much denser than that a REFINED grid (surface-like / clustered target) may stay
-  unsigned long long* d_count = nullptr;
-  uint32_t* d_out_idx = nullptr;  // [ns] original-order results
-  float* d_out_d2 = nullptr;
+  DevBuf<unsigned long long> d_count;
 
   // engine post-filters (correspondence_search_kd_tree.hpp:224-225)
   double inlier_fraction = 1.0;
   bool one_to_one = false;
-  unsigned long long* d_keys = nullptr;    // [ns]
-  unsigned long long* d_own_order = nullptr;   // [ns] this shard's traversal keys of the current iteration (cilhip_icp_order_keys)
   int tie_max_depth = 0;                   // depth of the loaded order tree (the traversal keys hold 58 levels)
-  void* d_sel_state = nullptr;
-  unsigned long long* d_winner = nullptr;  // [n_target]
+  DevBuf<unsigned char> d_sel_state;
 
   // other search directions (correspondence_search_kd_tree.hpp:185-222): the correspondence set is a pair list
   int search_dir = 0;             // 0 = SECOND_TO_FIRST (default), 1 = FIRST_TO_SECOND, 2 = BOTH
@@ -172,9 +190,6 @@ struct cilhip_ctx {
   float normal_weight = 0.0f;     // > 0: the correspondence search runs on 6-D features (point, weight * v)
   int feature_kind = 0;           // option "feature_kind": 0 = v = normals, following the transform (PointNormalFeaturesAdaptor);
                                   // 1 = v = colours, untouched by it (PointColorFeaturesAdaptor; cilhip_set_color_features)
-  float *d_dst_rgb = nullptr, *d_src_rgb = nullptr;             // colour features, original order
-  float4 *d_dst_rgb_sorted = nullptr, *d_src_rgb_sorted = nullptr;
-  float4* d_src_rgb_grid = nullptr;      // the source's colours in the order of the source's own grid (9-D reverse search)
   float color_weight = 0.0f;             // option "feature_color_weight" (feature_kind 2: the 9-D adaptor's colour weight)
   bool dst_rgb_sorted_ok = false;
   float src_nrm0[3] = {0, 0, 0};  // the first source normal (the affine feature adaptor's normal weight is |w n_0|, adaptors.hpp:113-114)
@@ -183,13 +198,9 @@ struct cilhip_ctx {
   PairSet pairs;
   GridDev src_grid{};             // grid over the source in SOURCE coordinates (built on the first FIRST_TO_SECOND / BOTH search of a source)
   bool has_src_grid = false;
-  float* d_src_safe2 = nullptr;   // [ns] k_self_nn's table over the SOURCE grid: the margin test of the warm-started reverse search (k_reverse_warm)
   bool reverse_warm = true;       // option "reverse_warm_start": the device-resident FIRST_TO_SECOND / BOTH loops start every reverse search but the first from the previous matches
-  uint32_t* d_grid_to_sorted = nullptr;   // [ns] source-grid position -> sorted source position (d_src_inv through the source grid's order): the fused reverse pass's duplicate test
-  uint32_t *d_rev_pos = nullptr, *d_src_inv = nullptr;   // list-free loops of those directions: reverse matches by target position; original -> sorted source position
-  float* d_rev_d2 = nullptr;
   bool have_pairs = false;        // `pairs` holds the result of the last find_correspondences
-  IcpState* d_state_id = nullptr; // a state holding the identity transform (the reverse search transforms nothing)
+  DevBuf<IcpState> d_state_id; // a state holding the identity transform (the reverse search transforms nothing)
 
   // sharded-run state
   cilhip_icp_params run_prm{};
@@ -212,6 +223,13 @@ struct cilhip_ctx {
   double last_allreduce_ms = 0.0; int last_allreduce_n = 0;
   double run_enqueue_us = 0.0; int run_enqueue_iters = 0;      // ranked loop: host time of its enqueue calls (the paced waits for the device's feedback word excluded)
 };
+
+inline cilhip_ctx::~cilhip_ctx() {
+  if (h_feedback) (void)hipHostFree(h_feedback);
+  for (auto e : ev) (void)hipEventDestroy(e);
+  for (auto e : ev_acc) (void)hipEventDestroy(e);
+  for (auto e : ev_ar) (void)hipEventDestroy(e);
+}
 
 #define CK(ctx, call)                                                                                   \
   do {                                                                                                  \

@@ -66,17 +66,16 @@ __global__ __launch_bounds__(256) void k_bbox_sum(const float* __restrict__ xyz,
 }
 
 static hipError_t bbox_mean(const float* d_xyz, uint32_t n, hipStream_t s, float lo[3], float hi[3], double mean[3]) {
-  float *d_min = nullptr, *d_max = nullptr; double* d_sum = nullptr;
-  HIP_TRY(hipMalloc(&d_min, RB * 3 * sizeof(float)));
-  HIP_TRY(hipMalloc(&d_max, RB * 3 * sizeof(float)));
-  HIP_TRY(hipMalloc(&d_sum, RB * 3 * sizeof(double)));
-  hipLaunchKernelGGL(k_bbox_sum, dim3(RB), dim3(256), 0, s, d_xyz, n, d_min, d_max, d_sum);
+  DevBuf<float> d_min, d_max; DevBuf<double> d_sum;
+  HIP_TRY(d_min.alloc(RB * 3));
+  HIP_TRY(d_max.alloc(RB * 3));
+  HIP_TRY(d_sum.alloc(RB * 3));
+  hipLaunchKernelGGL(k_bbox_sum, dim3(RB), dim3(256), 0, s, d_xyz, n, d_min.get(), d_max.get(), d_sum.get());
   std::vector<float> hmin(RB * 3), hmax(RB * 3); std::vector<double> hsum(RB * 3);
   HIP_TRY(hipMemcpyAsync(hmin.data(), d_min, RB * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(hmax.data(), d_max, RB * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(hsum.data(), d_sum, RB * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  (void)hipFree(d_min); (void)hipFree(d_max); (void)hipFree(d_sum);
   for (int c = 0; c < 3; ++c) { lo[c] = INFINITY; hi[c] = -INFINITY; mean[c] = 0.0; }
   for (int b = 0; b < RB; ++b)
     for (int c = 0; c < 3; ++c) {
@@ -149,11 +148,10 @@ static hipError_t cell_start_table(const uint32_t* keys_sorted, uint32_t n, uint
   auto rit = rocprim::make_reverse_iterator(cell_start + (size_t)ncells + 1);
   size_t tmp_bytes = 0;
   HIP_TRY(rocprim::inclusive_scan(nullptr, tmp_bytes, rit, rit, (size_t)ncells + 1, rocprim::minimum<uint32_t>(), s));
-  void* tmp = nullptr;
-  HIP_TRY(hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 16));
-  hipError_t e = rocprim::inclusive_scan(tmp, tmp_bytes, rit, rit, (size_t)ncells + 1, rocprim::minimum<uint32_t>(), s);
+  DevBuf<unsigned char> tmp;
+  HIP_TRY(tmp.alloc(tmp_bytes));
+  hipError_t e = rocprim::inclusive_scan(tmp.get(), tmp_bytes, rit, rit, (size_t)ncells + 1, rocprim::minimum<uint32_t>(), s);
   hipError_t e2 = hipStreamSynchronize(s);
-  (void)hipFree(tmp);
   return e != hipSuccess ? e : e2;
 }
 
@@ -182,11 +180,10 @@ static inline int grid_blocks(uint32_t n) { return (int)std::min<uint32_t>((n + 
 static hipError_t sort_pairs(uint32_t* k_in, uint32_t* k_out, uint32_t* v_in, uint32_t* v_out, uint32_t n, unsigned bits, hipStream_t s) {
   size_t tmp_bytes = 0;
   HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, k_in, k_out, v_in, v_out, (size_t)n, 0u, bits, s));
-  void* tmp = nullptr;
-  HIP_TRY(hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 16));
-  hipError_t e = rocprim::radix_sort_pairs(tmp, tmp_bytes, k_in, k_out, v_in, v_out, (size_t)n, 0u, bits, s);
+  DevBuf<unsigned char> tmp;
+  HIP_TRY(tmp.alloc(tmp_bytes));
+  hipError_t e = rocprim::radix_sort_pairs(tmp.get(), tmp_bytes, k_in, k_out, v_in, v_out, (size_t)n, 0u, bits, s);
   hipError_t e2 = hipStreamSynchronize(s);
-  (void)hipFree(tmp);
   return e != hipSuccess ? e : e2;
 }
 
@@ -210,19 +207,18 @@ hipError_t build_grid(const float* d_xyz, const float* d_nrm, uint32_t n, hipStr
                       double target_occupancy, double refined_factor) {
   GridDev g{};
   g.n = n; g.pts = nullptr; g.nrm = nullptr; g.pn = nullptr; g.cell_start = nullptr;
+  GridStore st;      // (handed to *out on success only)
   out->avg_occupancy = 0.0;
   if (n == 0) {
     // empty target: a minimal grid of empty cells; every search returns "none" (kd_tree_utilities.hpp:16-19)
     const float z3[3] = {0, 0, 0};
     (void)set_dims(g, z3, z3, 1.0);
     const size_t nc = (size_t)g.nx * g.ny * g.nz;
-    uint32_t* cs = nullptr;
-    HIP_TRY(hipMalloc(&cs, (nc + 1) * sizeof(uint32_t)));
-    HIP_TRY(hipMemsetAsync(cs, 0, (nc + 1) * sizeof(uint32_t), s));
-    float4* dummy = nullptr;
-    HIP_TRY(hipMalloc(&dummy, sizeof(float4)));
-    g.cell_start = cs; g.pts = dummy;
-    out->grid = g; out->n_cells = nc;
+    HIP_TRY(st.cell_start.alloc(nc + 1));
+    HIP_TRY(hipMemsetAsync(st.cell_start, 0, (nc + 1) * sizeof(uint32_t), s));
+    HIP_TRY(st.pts.alloc(1));
+    g.cell_start = st.cell_start; g.pts = st.pts;
+    out->grid = g; out->store = std::move(st); out->n_cells = nc;
     mean_out[0] = mean_out[1] = mean_out[2] = 0.0;
     return hipSuccess;
   }
@@ -236,23 +232,23 @@ hipError_t build_grid(const float* d_xyz, const float* d_nrm, uint32_t n, hipStr
   double cell = grid_first_cell(lo, hi, n, TARGET);
   if (!set_dims(g, lo, hi, cell)) return GRID_RANGE_ERROR;      // (before anything is allocated)
 
-  uint32_t *k_in = nullptr, *k_out = nullptr, *v_in = nullptr, *v_out = nullptr, *cs = nullptr;
-  double* d_occ = nullptr;
-  HIP_TRY(hipMalloc(&k_in, (size_t)n * 4)); HIP_TRY(hipMalloc(&k_out, (size_t)n * 4));
-  HIP_TRY(hipMalloc(&v_in, (size_t)n * 4)); HIP_TRY(hipMalloc(&v_out, (size_t)n * 4));
-  HIP_TRY(hipMalloc(&d_occ, sizeof(double)));
+  DevBuf<uint32_t> k_in, k_out, v_in, v_out;
+  DevBuf<double> d_occ;
+  HIP_TRY(k_in.alloc(n)); HIP_TRY(k_out.alloc(n));
+  HIP_TRY(v_in.alloc(n)); HIP_TRY(v_out.alloc(n));
+  HIP_TRY(d_occ.alloc(1));
   double occ = 0.0;
   size_t ncells = 0;
   for (int attempt = 0; attempt < 8; ++attempt) {
     (void)set_dims(g, lo, hi, cell);      // (cannot fail where the first guess did not: the range test does not depend on a smaller cell)
     ncells = (size_t)g.nx * g.ny * g.nz;
-    if (cs) { (void)hipFree(cs); cs = nullptr; }
-    HIP_TRY(hipMalloc(&cs, (ncells + 1) * sizeof(uint32_t)));
-    hipLaunchKernelGGL(k_cell_keys, dim3(grid_blocks(n)), dim3(256), 0, s, d_xyz, n, g, k_in, v_in);
+    HIP_TRY(st.cell_start.alloc(ncells + 1));
+    uint32_t* const cs = st.cell_start;
+    hipLaunchKernelGGL(k_cell_keys, dim3(grid_blocks(n)), dim3(256), 0, s, d_xyz, n, g, k_in.get(), v_in.get());
     HIP_TRY(sort_pairs(k_in, k_out, v_in, v_out, n, bits_for((uint32_t)ncells + 1u), s));      // (+ 1: the key of the points without a cell)
     HIP_TRY(cell_start_table(k_out, n, (uint32_t)ncells, cs, s));
     HIP_TRY(hipMemsetAsync(d_occ, 0, sizeof(double), s));
-    hipLaunchKernelGGL(k_occupancy, dim3(grid_blocks((uint32_t)ncells)), dim3(256), 0, s, cs, (uint32_t)ncells, d_occ);
+    hipLaunchKernelGGL(k_occupancy, dim3(grid_blocks((uint32_t)ncells)), dim3(256), 0, s, cs, (uint32_t)ncells, d_occ.get());
     HIP_TRY(hipMemcpyAsync(&occ, d_occ, sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     occ /= (double)n;
@@ -270,23 +266,13 @@ hipError_t build_grid(const float* d_xyz, const float* d_nrm, uint32_t n, hipStr
     if (probe.cell >= g.cell * 0.97f) break;  // dims / cell-count caps reached: keep the current grid
     cell = new_cell;
   }
-  float4 *pts = nullptr, *nrm = nullptr;
-  HIP_TRY(hipMalloc(&pts, (size_t)n * sizeof(float4)));
-  if (d_nrm) HIP_TRY(hipMalloc(&nrm, (size_t)n * sizeof(float4)));
-  hipLaunchKernelGGL(k_gather, dim3(grid_blocks(n)), dim3(256), 0, s, d_xyz, d_nrm, v_out, n, pts, nrm);
+  HIP_TRY(st.pts.alloc(n));
+  if (d_nrm) HIP_TRY(st.nrm.alloc(n));
+  hipLaunchKernelGGL(k_gather, dim3(grid_blocks(n)), dim3(256), 0, s, d_xyz, d_nrm, (const uint32_t*)v_out.get(), n, st.pts.get(), st.nrm.get());
   HIP_TRY(hipStreamSynchronize(s));
-  (void)hipFree(k_in); (void)hipFree(k_out); (void)hipFree(v_in); (void)hipFree(v_out); (void)hipFree(d_occ);
-  g.pts = pts; g.nrm = nrm; g.cell_start = cs;
-  out->grid = g; out->avg_occupancy = occ; out->n_cells = ncells;
+  g.pts = st.pts; g.nrm = st.nrm; g.cell_start = st.cell_start;
+  out->grid = g; out->store = std::move(st); out->avg_occupancy = occ; out->n_cells = ncells;
   return hipSuccess;
-}
-
-void free_grid(GridDev& g) {
-  if (g.pts) (void)hipFree((void*)g.pts);
-  if (g.nrm) (void)hipFree((void*)g.nrm);
-  if (g.pn) (void)hipFree((void*)g.pn);
-  if (g.cell_start) (void)hipFree((void*)g.cell_start);
-  g.pts = nullptr; g.nrm = nullptr; g.pn = nullptr; g.cell_start = nullptr;
 }
 
 // ---- source ordering + tiles ------------------------------------------------------------------------
@@ -349,9 +335,9 @@ __global__ void k_emit_tiles(const uint32_t* __restrict__ cube_start, const uint
 
 // ws (optional): scratch and tile-table storage kept between calls -- a registration loop re-sorts the same source for every new
 // initial transform, and the dozen hipMalloc / hipFree of a stand-alone call cost more than its kernels (1.7 -> 0.8 ms at 10M).
-// With ws the tile table lives in ws (valid until the next call with it); without, the caller frees *d_tiles_out / *d_tile_center_out.
+// The tile table lives in ws (valid until the next call with it); everything stays on the stream.
 hipError_t sort_source(const float* d_xyz, uint32_t n, const GridDev& g, const float T[16], float4* d_out, hipStream_t s,
-                       uint2** d_tiles_out, float4** d_tile_center_out, float tile_axes_out[9], uint32_t* ntiles_out, SortWorkspace* ws) {
+                       uint2** d_tiles_out, float4** d_tile_center_out, float tile_axes_out[9], uint32_t* ntiles_out, SortWorkspace& ws) {
   *d_tiles_out = nullptr; *d_tile_center_out = nullptr; *ntiles_out = 0;
   // inverse of the (affine) sort transform, in double; a singular linear part leaves a zero box (every query
   // then takes the clean-up pass: slow, still exact)
@@ -384,16 +370,9 @@ hipError_t sort_source(const float* d_xyz, uint32_t n, const GridDev& g, const f
   auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const size_t arr = up((size_t)n * 4), carr = up(((size_t)ncubes + 1) * 4);
   const size_t need = 4 * arr + 3 * carr + up(sort_tmp ? sort_tmp : 16) + up(scan_tmp ? scan_tmp : 16);
-  SortWorkspace local;
-  SortWorkspace* w = ws ? ws : &local;
   hipError_t e = hipSuccess;
-  if (w->scratch_bytes < need) {
-    if (w->scratch) (void)hipFree(w->scratch);
-    w->scratch = nullptr; w->scratch_bytes = 0;
-    if ((e = hipMalloc(&w->scratch, need)) != hipSuccess) return e;
-    w->scratch_bytes = need;
-  }
-  char* base = static_cast<char*>(w->scratch);
+  if ((e = ws.scratch.ensure(need)) != hipSuccess) return e;
+  char* base = reinterpret_cast<char*>(ws.scratch.get());
   uint32_t *k_in = reinterpret_cast<uint32_t*>(base), *k_out = reinterpret_cast<uint32_t*>(base + arr), *v_in = reinterpret_cast<uint32_t*>(base + 2 * arr),
            *v_out = reinterpret_cast<uint32_t*>(base + 3 * arr);
   uint32_t *cube_start = reinterpret_cast<uint32_t*>(base + 4 * arr), *tcount = reinterpret_cast<uint32_t*>(base + 4 * arr + carr),
@@ -402,8 +381,6 @@ hipError_t sort_source(const float* d_xyz, uint32_t n, const GridDev& g, const f
   void* tmp_scan = base + 4 * arr + 3 * carr + up(sort_tmp ? sort_tmp : 16);
   Tf tf;
   for (int i = 0; i < 16; ++i) tf.m[i] = T[i];
-  uint2* tiles = nullptr;
-  float4* centers = nullptr;
   do {
     hipLaunchKernelGGL(k_cube_keys_tf, dim3(grid_blocks(n)), dim3(256), 0, s, d_xyz, n, g, tf, k_in, v_in);
     if ((e = rocprim::radix_sort_pairs(tmp_sort, sort_tmp, k_in, k_out, v_in, v_out, (size_t)n, 0u, bits, s)) != hipSuccess) break;
@@ -417,42 +394,18 @@ hipError_t sort_source(const float* d_xyz, uint32_t n, const GridDev& g, const f
     uint32_t ntiles = 0;
     if ((e = hipMemcpyAsync(&ntiles, toff + ncubes, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) break;
     if ((e = hipStreamSynchronize(s)) != hipSuccess) break;
-    if (ws) {
-      if (ws->tile_cap < ntiles + 1) {
-        if (ws->tiles) (void)hipFree(ws->tiles);
-        if (ws->centers) (void)hipFree(ws->centers);
-        ws->tiles = nullptr; ws->centers = nullptr; ws->tile_cap = 0;
-        const uint32_t cap = ntiles + 1 + ntiles / 8;
-        if ((e = hipMalloc(&ws->tiles, (size_t)cap * sizeof(uint2))) != hipSuccess) break;
-        if ((e = hipMalloc(&ws->centers, (size_t)cap * sizeof(float4))) != hipSuccess) break;
-        ws->tile_cap = cap;
-      }
-      tiles = ws->tiles; centers = ws->centers;
-    } else {
-      if ((e = hipMalloc(&tiles, ((size_t)ntiles + 1) * sizeof(uint2))) != hipSuccess) break;
-      if ((e = hipMalloc(&centers, ((size_t)ntiles + 1) * sizeof(float4))) != hipSuccess) break;
+    if (ws.tiles.capacity() < (size_t)ntiles + 1 || ws.centers.capacity() < (size_t)ntiles + 1) {
+      ws.tiles.reset(); ws.centers.reset();
+      const size_t cap = (size_t)ntiles + 1 + ntiles / 8;
+      if ((e = ws.tiles.alloc(cap)) != hipSuccess) break;
+      if ((e = ws.centers.alloc(cap)) != hipSuccess) break;
     }
-    hipLaunchKernelGGL(k_emit_tiles, dim3(grid_blocks(ncubes)), dim3(256), 0, s, cube_start, toff, ncubes, g, tinv, tiles, centers);
-    e = ws ? hipGetLastError() : hipStreamSynchronize(s);      // (with ws everything stays on the stream)
-    *d_tiles_out = tiles; *d_tile_center_out = centers; *ntiles_out = ntiles;
+    hipLaunchKernelGGL(k_emit_tiles, dim3(grid_blocks(ncubes)), dim3(256), 0, s, cube_start, toff, ncubes, g, tinv, ws.tiles.get(), ws.centers.get());
+    e = hipGetLastError();
+    *d_tiles_out = ws.tiles; *d_tile_center_out = ws.centers; *ntiles_out = ntiles;
   } while (0);
-  if (!ws) {
-    (void)hipStreamSynchronize(s);
-    if (local.scratch) (void)hipFree(local.scratch);
-    if (e != hipSuccess) {
-      if (tiles) (void)hipFree(tiles);
-      if (centers) (void)hipFree(centers);
-    }
-  }
   if (e != hipSuccess) { *d_tiles_out = nullptr; *d_tile_center_out = nullptr; *ntiles_out = 0; }
   return e;
-}
-
-void free_sort_workspace(SortWorkspace& ws) {
-  if (ws.scratch) (void)hipFree(ws.scratch);
-  if (ws.tiles) (void)hipFree(ws.tiles);
-  if (ws.centers) (void)hipFree(ws.centers);
-  ws = SortWorkspace();
 }
 
 }  // namespace cilhip

@@ -281,20 +281,6 @@ unsigned gd_bits(int range) {      // bits that hold 0 .. range
   return b;
 }
 
-// device allocations of one call: freed on every way out
-struct GdPool {
-  std::vector<void*> p;
-  ~GdPool() { for (void* q : p) (void)hipFree(q); }
-  template <typename T>
-  hipError_t get(T** out, size_t bytes) {
-    void* q = nullptr;
-    hipError_t e = hipMalloc(&q, bytes ? bytes : 16);
-    if (e == hipSuccess) p.push_back(q);
-    *out = static_cast<T*>(q);
-    return e;
-  }
-};
-
 #define GD_CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { g_gd_err = std::string("grid_downsample: ") + #x + ": " + hipGetErrorString(e_); return CILHIP_ERR_HIP; } } while (0)
 
 struct GdCall {
@@ -311,18 +297,18 @@ struct GdCall {
 };
 
 template <typename KeyT>
-int gd_sort_and_fold(const GdCall& c, GdPool& pool, hipStream_t s, const F3* d_xyz, const F3* d_nrm, const F3* d_rgb, const GdPack& pk, unsigned end_bit, size_t m) {
+int gd_sort_and_fold(const GdCall& c, DevPool& pool, hipStream_t s, const F3* d_xyz, const F3* d_nrm, const F3* d_rgb, const GdPack& pk, unsigned end_bit, size_t m) {
   const size_t n = c.n;
   KeyT *k_in = nullptr, *k_out = nullptr;
   uint32_t *v_in = nullptr, *v_out = nullptr;
-  GD_CK(pool.get(&k_in, n * sizeof(KeyT))); GD_CK(pool.get(&k_out, n * sizeof(KeyT)));
-  GD_CK(pool.get(&v_in, (n + 1) * sizeof(uint32_t))); GD_CK(pool.get(&v_out, n * sizeof(uint32_t)));
+  GD_CK(pool.bytes(&k_in, n * sizeof(KeyT))); GD_CK(pool.bytes(&k_out, n * sizeof(KeyT)));
+  GD_CK(pool.bytes(&v_in, (n + 1) * sizeof(uint32_t))); GD_CK(pool.bytes(&v_out, n * sizeof(uint32_t)));
   hipLaunchKernelGGL((k_gd_keys<KeyT>), dim3(gd_blocks(n)), dim3(256), 0, s, d_xyz, n, pk, k_in, v_in);
   {
     size_t tmp_bytes = 0;
     void* tmp = nullptr;
     GD_CK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, k_in, k_out, v_in, v_out, n, 0u, end_bit, s));
-    GD_CK(pool.get(&tmp, tmp_bytes));
+    GD_CK(pool.bytes(&tmp, tmp_bytes));
     GD_CK(rocprim::radix_sort_pairs(tmp, tmp_bytes, k_in, k_out, v_in, v_out, n, 0u, end_bit, s));
   }
   // the first m sorted positions are the points that have a bin
@@ -335,15 +321,15 @@ int gd_sort_and_fold(const GdCall& c, GdPool& pool, hipStream_t s, const F3* d_x
     GD_CK(rocprim::inclusive_scan(nullptr, b1, bin_of, bin_of, m, rocprim::plus<uint32_t>(), s));
     GD_CK(rocprim::exclusive_scan(nullptr, b2, bin_of, bin_of, 0u, n + 1, rocprim::plus<uint32_t>(), s));
     scan_bytes = std::max(b1, b2);
-    GD_CK(pool.get(&scan_tmp, scan_bytes));
+    GD_CK(pool.bytes(&scan_tmp, scan_bytes));
   }
   GD_CK(rocprim::inclusive_scan(scan_tmp, scan_bytes, bin_of, bin_of, m, rocprim::plus<uint32_t>(), s));
   uint32_t nbins = 0;
   GD_CK(hipMemcpyAsync(&nbins, bin_of + (m - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   GD_CK(hipStreamSynchronize(s));
   uint32_t *start = nullptr, *slot = nullptr;
-  GD_CK(pool.get(&start, ((size_t)nbins + 1) * sizeof(uint32_t)));
-  GD_CK(pool.get(&slot, ((size_t)nbins + 1) * sizeof(uint32_t)));
+  GD_CK(pool.bytes(&start, ((size_t)nbins + 1) * sizeof(uint32_t)));
+  GD_CK(pool.bytes(&slot, ((size_t)nbins + 1) * sizeof(uint32_t)));
   hipLaunchKernelGGL(k_gd_starts, dim3(gd_blocks(m)), dim3(256), 0, s, (const uint32_t*)bin_of, m, nbins, start);
   const uint32_t min_pts = (uint32_t)std::min<size_t>(c.min_pts, 0xFFFFFFFFull);      // (no bin has 2^32 members: anything above refuses them all)
   uint32_t rows = 0;
@@ -368,25 +354,25 @@ int gd_sort_and_fold(const GdCall& c, GdPool& pool, hipStream_t s, const F3* d_x
 
   const bool has_n = d_nrm && c.nrm_out, has_c = d_rgb && c.rgb_out;
   F3 *gp = nullptr, *gn = nullptr, *gc = nullptr;
-  GD_CK(pool.get(&gp, m * sizeof(F3)));
-  if (has_n) GD_CK(pool.get(&gn, m * sizeof(F3)));
-  if (has_c) GD_CK(pool.get(&gc, m * sizeof(F3)));
+  GD_CK(pool.bytes(&gp, m * sizeof(F3)));
+  if (has_n) GD_CK(pool.bytes(&gn, m * sizeof(F3)));
+  if (has_c) GD_CK(pool.bytes(&gc, m * sizeof(F3)));
   hipLaunchKernelGGL(k_gd_gather, dim3(gd_blocks(m)), dim3(256), 0, s, d_xyz, has_n ? d_nrm : (const F3*)nullptr, has_c ? d_rgb : (const F3*)nullptr,
                      (const uint32_t*)v_out, m, gp, gn, gc);
   GdFold a{};
   a.start = start; a.slot = slot; a.gp = gp; a.gn = gn; a.gc = gc; a.nbins = nbins; a.min_pts = min_pts;
   uint32_t* n_long = nullptr;
   // a bin that goes to the wave form has more than GD_WAVE_MIN members: there are fewer than m / GD_WAVE_MIN of them
-  GD_CK(pool.get(&a.long_list, (m / GD_WAVE_MIN + 1) * sizeof(uint32_t)));
-  GD_CK(pool.get(&n_long, sizeof(uint32_t)));
+  GD_CK(pool.bytes(&a.long_list, (m / GD_WAVE_MIN + 1) * sizeof(uint32_t)));
+  GD_CK(pool.bytes(&n_long, sizeof(uint32_t)));
   GD_CK(hipMemsetAsync(n_long, 0, sizeof(uint32_t), s));
   a.n_long = n_long;
   const bool host = c.mem == CILHIP_MEM_HOST;
   if (host) {
-    if (c.xyz_out) GD_CK(pool.get(&a.out_p, (size_t)rows * sizeof(F3)));
-    if (has_n) GD_CK(pool.get(&a.out_n, (size_t)rows * sizeof(F3)));
-    if (has_c) GD_CK(pool.get(&a.out_c, (size_t)rows * sizeof(F3)));
-    if (c.cnt_out) GD_CK(pool.get(&a.out_cnt, (size_t)rows * sizeof(uint32_t)));
+    if (c.xyz_out) GD_CK(pool.bytes(&a.out_p, (size_t)rows * sizeof(F3)));
+    if (has_n) GD_CK(pool.bytes(&a.out_n, (size_t)rows * sizeof(F3)));
+    if (has_c) GD_CK(pool.bytes(&a.out_c, (size_t)rows * sizeof(F3)));
+    if (c.cnt_out) GD_CK(pool.bytes(&a.out_cnt, (size_t)rows * sizeof(uint32_t)));
   } else {
     a.out_p = reinterpret_cast<F3*>(c.xyz_out);
     a.out_n = has_n ? reinterpret_cast<F3*>(c.nrm_out) : nullptr;
@@ -418,11 +404,6 @@ int gd_sort_and_fold(const GdCall& c, GdPool& pool, hipStream_t s, const F3* d_x
   return CILHIP_OK;
 }
 
-struct GdStream {
-  hipStream_t s = nullptr;
-  ~GdStream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
-};
-
 int gd_run(const GdCall& c, int device) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
@@ -430,9 +411,9 @@ int gd_run(const GdCall& c, int device) {
     return CILHIP_ERR_NO_DEVICE;
   }
   GD_CK(hipSetDevice(device));
-  GdPool pool;
-  GdStream st;      // (declared after the pool: the stream is drained and destroyed before anything is freed)
-  GD_CK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+  DevPool pool;
+  StreamGuard st;      // (declared after the pool: the stream is drained and destroyed before anything is freed)
+  GD_CK(st.create());
   hipStream_t s = st.s;
   const size_t n = c.n;
   const F3 *d_xyz = nullptr, *d_nrm = nullptr, *d_rgb = nullptr;
@@ -444,7 +425,7 @@ int gd_run(const GdCall& c, int device) {
     for (int k = 0; k < 3; ++k) {
       if (!src[k]) continue;
       F3* d = nullptr;
-      GD_CK(pool.get(&d, n * sizeof(F3)));
+      GD_CK(pool.bytes(&d, n * sizeof(F3)));
       GD_CK(hipMemcpyAsync(d, src[k], n * sizeof(F3), hipMemcpyHostToDevice, s));
       *dst[k] = d;
     }
@@ -453,7 +434,7 @@ int gd_run(const GdCall& c, int device) {
   GdRange h{};
   for (int a = 0; a < 3; ++a) { h.mn[a] = INT_MAX; h.mx[a] = INT_MIN; }
   GdRange* d_range = nullptr;
-  GD_CK(pool.get(&d_range, sizeof(GdRange)));
+  GD_CK(pool.bytes(&d_range, sizeof(GdRange)));
   GD_CK(hipMemcpyAsync(d_range, &h, sizeof(GdRange), hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_gd_range, dim3(std::min(gd_blocks(n), 2048)), dim3(256), 0, s, d_xyz, n, inv, d_range);
   GD_CK(hipMemcpyAsync(&h, d_range, sizeof(GdRange), hipMemcpyDeviceToHost, s));

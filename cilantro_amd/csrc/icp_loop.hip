@@ -176,7 +176,7 @@ static int stop_when_done(cilhip_ctx* c, size_t it, size_t max_iter, bool* stop)
   *stop = false;
   if (!(max_iter > 64 && (it + 1) % 32 == 0 && it + 1 < max_iter)) return CILHIP_OK;
   int done = 0;
-  CK(c, hipMemcpyAsync(&done, reinterpret_cast<const char*>(c->d_state) + offsetof(IcpState, done), sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  CK(c, hipMemcpyAsync(&done, reinterpret_cast<const char*>(c->d_state.get()) + offsetof(IcpState, done), sizeof(int), hipMemcpyDeviceToHost, c->stream));
   CK(c, hipStreamSynchronize(c->stream));
   *stop = done != 0;
   return CILHIP_OK;
@@ -852,7 +852,7 @@ int cilhip_rank_comm_prepare(cilhip_ctx* c) {
   if (!c) return CILHIP_ERR_INVALID;
   if (!g_rank_rccl.load()) return fail(c, CILHIP_ERR_UNSUPPORTED, "rank_comm_prepare: librccl.so.1 could not be opened");
   CK(c, hipSetDevice(c->device));
-  if (!c->d_rank_sums && hipMalloc(&c->d_rank_sums, (size_t)RANK_ROWS * SUMS_MAX * sizeof(double)) != hipSuccess)
+  if (!c->d_rank_sums && c->d_rank_sums.alloc((size_t)RANK_ROWS * SUMS_MAX) != hipSuccess)
     return fail(c, CILHIP_ERR_HIP, "rank_comm_prepare: out of device memory");
   return CILHIP_OK;
 }
@@ -866,7 +866,7 @@ int cilhip_rank_comm_init(cilhip_ctx* c, const unsigned char id[128], int nranks
   memcpy(u.internal, id, sizeof(u.internal));
   rccl_comm_t comm = nullptr;
   if (g_rank_rccl.CommInitRank(&comm, nranks, u, rank) != 0 || !comm) return fail(c, CILHIP_ERR_HIP, "ncclCommInitRank failed");
-  if (!c->d_rank_sums && hipMalloc(&c->d_rank_sums, (size_t)RANK_ROWS * SUMS_MAX * sizeof(double)) != hipSuccess) {
+  if (!c->d_rank_sums && c->d_rank_sums.alloc((size_t)RANK_ROWS * SUMS_MAX) != hipSuccess) {
     (void)g_rank_rccl.CommDestroy(comm);
     return fail(c, CILHIP_ERR_HIP, "rank_comm_init: out of device memory");
   }
@@ -877,7 +877,7 @@ int cilhip_rank_comm_init(cilhip_ctx* c, const unsigned char id[128], int nranks
 int cilhip_rank_comm_destroy(cilhip_ctx* c) {
   if (!c) return CILHIP_ERR_INVALID;
   if (c->rank_comm) { (void)hipStreamSynchronize(c->stream); (void)g_rank_rccl.CommDestroy(c->rank_comm); c->rank_comm = nullptr; c->rank_comm_size = 0; }
-  if (c->d_rank_sums) { (void)hipFree(c->d_rank_sums); c->d_rank_sums = nullptr; }
+  c->d_rank_sums.reset();
   return CILHIP_OK;
 }
 

@@ -7,6 +7,7 @@
 #include <string>
 #include <thread>
 
+#include "device_mem.hpp"
 #include "grid_policy.hpp"
 #include "solve.hpp"
 
@@ -404,14 +405,14 @@ struct TieNode {          // 16 bytes: one load on the device
 // planeSplit, leaf size 10), level by level on the device.  Input: d_xyz -- the cloud in its ORIGINAL order, 3 floats per point -- or
 // d_sorted -- {x, y, z, bits(original index)} records in any order (exactly one non-null).  Output by ORIGINAL index: the leaf node of
 // every point and its slot in the reference's permutation (device arrays [n] the caller provides); *d_nodes_out: the TieNode
-// records (hipMalloc'ed: the caller frees), breadth-first ids.
+// records, breadth-first ids.
 extern int g_knn_tie_rule;      // knn.hip: cilhip_knn_set_tie_rule (k-NN lists and the KMeans kd branch)
 hipError_t tie_order_build_device(const float* d_xyz, const float4* d_sorted, uint32_t n, hipStream_t s, uint32_t* d_leaf_by_index, uint32_t* d_slot_by_index,
-                                  uint4** d_nodes_out, size_t* n_nodes_out, int* max_depth_out);
+                                  DevBuf<uint4>* d_nodes_out, size_t* n_nodes_out, int* max_depth_out);
 // ... and of the tree a feature adaptor's search walks (DIM = 6 / 9: points + w1 * att1 [+ w2 * att2], attributes by sorted position);
 // TieNode::info there = (depth << 5) | (split dimension << 1) | second child (tie_before_nd)
 hipError_t tie_order_build_device_features(int dim, const float4* d_sorted, const float4* att1, float w1, const float4* att2, float w2, uint32_t n, hipStream_t s,
-                                           uint32_t* d_leaf_by_index, uint32_t* d_slot_by_index, uint4** d_nodes_out, size_t* n_nodes_out, int* max_depth_out);
+                                           uint32_t* d_leaf_by_index, uint32_t* d_slot_by_index, DevBuf<uint4>* d_nodes_out, size_t* n_nodes_out, int* max_depth_out);
 void launch_tie_tables_by_position(const float4* dst_sorted, uint32_t n, const uint32_t* leaf_by_index, const uint32_t* slot_by_index, uint2* leaf_slot, hipStream_t s);
 void launch_count_ties(const GridDev& g, const float4* src_sorted, uint32_t ns, const float T[16], float max_sq, unsigned long long* out, hipStream_t s);
 // squared distances of the stored matches under T, formed again with the search's pinned arithmetic (bit-identical to what the
@@ -434,20 +435,19 @@ void launch_select_fraction(const float* d2, uint32_t n, double fraction, unsign
 
 // bidir.hip -- search directions FIRST_TO_SECOND / BOTH: the correspondence set as a device pair list
 struct PairSet {
-  uint32_t *first = nullptr, *second = nullptr;   // ORIGINAL target / source indices, ascending (first, second)
-  uint32_t *posd = nullptr, *poss = nullptr;      // sorted-target / sorted-source positions of the same pairs
-  float* d2 = nullptr;
-  uint32_t *first2 = nullptr, *second2 = nullptr, *posd2 = nullptr, *poss2 = nullptr;   // ping-pong buffers of the post-filters
-  float* d2b = nullptr;
-  float4 *src_view = nullptr, *nrm_view = nullptr;   // sorted-source records (and normals) gathered per pair: what the accumulation streams over
-  size_t cap = 0;
+  DevBuf<uint32_t> first, second;   // ORIGINAL target / source indices, ascending (first, second)
+  DevBuf<uint32_t> posd, poss;      // sorted-target / sorted-source positions of the same pairs
+  DevBuf<float> d2;
+  DevBuf<uint32_t> first2, second2, posd2, poss2;   // ping-pong buffers of the post-filters
+  DevBuf<float> d2b;
+  DevBuf<float4> src_view, nrm_view;   // sorted-source records (and normals) gathered per pair: what the accumulation streams over
+  size_t cap = 0;                   // pairs all of the arrays above hold (0 while they are being replaced)
   uint32_t count = 0;
   // workspace of find_pairs (reverse matches, sort keys / slots, flags, scan temporaries ...): allocated once per size
   static constexpr int WS_COUNT = 15;
-  void* ws[WS_COUNT] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  size_t ws_cand = 0, ws_tmp_bytes = 0, ws_nd = 0, ws_ns = 0;      // what the workspace was sized for: candidates, scan scratch, target / source points
+  DevBuf<unsigned char> ws[WS_COUNT];
+  size_t ws_cand = 0, ws_nd = 0, ws_ns = 0;      // what the workspace was sized for: candidates, target / source points
 };
-void free_pairs(PairSet& p);
 // the reverse search of those directions alone (every target point against the source, through the inverse of the state's
 // rigid transform computed on the device): rev_pos / rev_d2 [nd] by target sorted position
 // feat (optional, w > 0): the reverse matches are the nearest 6-D FEATURES (feat->src in the source grid's order, feat->dst by target position)
@@ -469,13 +469,20 @@ hipError_t find_pairs(const FeatSpec& feat, const GridDev& g, const GridDev& src
                       PairSet& out, hipStream_t s, const TieDev* rev_tie = nullptr);
 
 // grid_build.hip
+// The arrays a GridDev views (pts, nrm, pn, cell_start), owned beside it.  Shareable per array: cilhip_share_target hands a built target's
+// arrays to a second context; what either builds later (pn) is its own.
+struct GridStore {
+  SharedBuf<float4> pts, nrm, pn;
+  SharedBuf<uint32_t> cell_start;
+};
 struct GridBuildResult {
   GridDev grid;
+  GridStore store;      // owns what `grid` points to
   double avg_occupancy;
   size_t n_cells;
 };
 // Builds the grid for n points (device xyz, optional device normals).  Allocates the sorted
-// arrays and the cell table (freed by free_grid).  Returns hipSuccess or an error.
+// arrays and the cell table (out->store).  Returns hipSuccess or an error.
 // refined_factor: a cloud whose density-based first guess leaves far too many points per cell (a surface, clusters) is refined until
 // the expected own-cell population is at most 3 x target x refined_factor (1: as dense a grid as for a volumetric cloud).
 // GRID_RANGE_ERROR: a finite cloud whose coordinates leave the range an f32 grid can index (grid_policy.hpp: GRID_POLICY_RANGE; nothing
@@ -485,18 +492,17 @@ constexpr hipError_t GRID_RANGE_ERROR = hipErrorInvalidPitchValue;      // (a va
 constexpr const char* kGridRangeMessage = "the cloud's finite coordinates span more than a single-precision grid can index (|coordinate| + 4 * extent must stay below FLT_MAX)";
 hipError_t build_grid(const float* d_xyz, const float* d_nrm, uint32_t n, hipStream_t s,
                       GridBuildResult* out, double mean_out[3], double target_occupancy, double refined_factor = 1.0);
-void free_grid(GridDev& g);
 // Sorts the source by the target-grid cell of T*s; writes {x,y,z,orig} records.  d_out preallocated [n].
 // Also emits the tile table of the LDS-tiled search kernel: tiles[t] = [begin,end) of <= TILE_QUERIES sorted
-// queries that share one 4x4x4-cell cube (caller frees *d_tiles_out with hipFree).
-struct SortWorkspace {      // scratch + tile-table storage a caller keeps between sort_source calls (free_sort_workspace)
-  void* scratch = nullptr; size_t scratch_bytes = 0;
-  uint2* tiles = nullptr; float4* centers = nullptr; uint32_t tile_cap = 0;
+// queries that share one 4x4x4-cell cube; it lives in ws (valid until the next call with it).
+struct SortWorkspace {      // scratch + tile-table storage a caller keeps between sort_source calls
+  DevBuf<unsigned char> scratch;
+  DevBuf<uint2> tiles;
+  DevBuf<float4> centers;
 };
 hipError_t sort_source(const float* d_xyz, uint32_t n, const GridDev& g, const float T[16], float4* d_out,
                        hipStream_t s, uint2** d_tiles_out, float4** d_tile_center_out, float tile_axes_out[9], uint32_t* ntiles_out,
-                       SortWorkspace* ws = nullptr);
-void free_sort_workspace(SortWorkspace& ws);
+                       SortWorkspace& ws);
 hipError_t mean3_device(const float* d_xyz, uint32_t n, hipStream_t s, double mean_out[3], float* lo_out = nullptr, float* hi_out = nullptr);
 
 // grid_downsample.hip: what the calling thread's last stateless call refused, for cilhip_last_error(NULL) ("null context" when nothing)

@@ -437,24 +437,25 @@ static bool g_kmeans_prune = [] { const char* e = getenv("CILHIP_KMEANS_PRUNE");
 // all-reduced sums -- and with them the centroids and every later assignment -- are the single-device run's bit for bit.
 struct cilhip_kmeans_shard {
   int device = 0;
-  hipStream_t s = nullptr;
-  float* d_xyz = nullptr;
-  bool own_xyz = false;
+  const float* d_xyz = nullptr;     // the caller's device cloud, or own_xyz
+  cilhip::DevBuf<float> own_xyz;
   size_t n = 0, k = 0, kpad = 0;
   uint64_t index_offset = 0;        // global index of this shard's point 0 (the empty-cluster repair's tie rule: lowest GLOBAL index)
-  float* d_c = nullptr;
-  uint32_t* d_lab = nullptr;
-  long long* d_sums = nullptr;
-  unsigned int* d_changed = nullptr;
-  unsigned int* d_nonfinite = nullptr;   // [kpad] flags of the last assign()
-  unsigned long long* d_best = nullptr;
-  float4* d_cs = nullptr;
-  uint32_t* d_cstart = nullptr;
-  uint32_t* d_tleaf = nullptr;      // kd branch: order tables of the reference's tree over the centroids (leaf, slot by centroid index)
-  uint2* d_tls = nullptr;
-  uint4* d_tnodes = nullptr;
-  uint32_t* d_lab_prev = nullptr;   // kd branch: the labels before a pass (put back when the pass has to run again with the tables)
-  uint2* d_tie_list = nullptr;      // kd branch, pruned pass: the tied points {index, label before the pass}
+  cilhip::DevBuf<float> d_c;
+  cilhip::DevBuf<uint32_t> d_lab;
+  cilhip::DevBuf<long long> d_sums;
+  cilhip::DevBuf<unsigned int> d_changed;
+  cilhip::DevBuf<unsigned int> d_nonfinite;   // [kpad] flags of the last assign()
+  cilhip::DevBuf<unsigned long long> d_best;
+  cilhip::DevBuf<float4> d_cs;
+  cilhip::DevBuf<uint32_t> d_cstart;
+  cilhip::DevBuf<uint32_t> d_tleaf;      // kd branch: order tables of the reference's tree over the centroids (leaf, slot by centroid index)
+  cilhip::DevBuf<uint2> d_tls;
+  cilhip::DevBuf<uint4> d_tnodes;
+  cilhip::DevBuf<uint32_t> d_lab_prev;   // kd branch: the labels before a pass (put back when the pass has to run again with the tables)
+  cilhip::DevBuf<uint2> d_tie_list;      // kd branch, pruned pass: the tied points {index, label before the pass}
+  cilhip::StreamGuard s;            // (after the buffers: drained and destroyed before they are freed)
+  ~cilhip_kmeans_shard() { (void)hipSetDevice(device); }
   int tie_table_builds = 0;         // passes that met exact ties (diagnostics)
   std::vector<float4> cs_host;
   std::vector<uint32_t> cstart_host;
@@ -467,21 +468,21 @@ struct cilhip_kmeans_shard {
     cpad.assign(3 * kpad, INFINITY);                              // device copy padded with +inf centroids
 #define KS_CK(x) do { if ((x) != hipSuccess) return CILHIP_ERR_HIP; } while (0)
     KS_CK(hipSetDevice(device));
-    KS_CK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    KS_CK(s.create());
     if (mem == CILHIP_MEM_DEVICE) {
-      d_xyz = const_cast<float*>(xyz);
+      d_xyz = xyz;
     } else {
-      KS_CK(hipMalloc(&d_xyz, (n ? 3 * n : 1) * sizeof(float)));
-      own_xyz = true;
-      if (n) KS_CK(hipMemcpyAsync(d_xyz, xyz, 3 * n * sizeof(float), hipMemcpyHostToDevice, s));
+      KS_CK(own_xyz.alloc(3 * n));
+      d_xyz = own_xyz;
+      if (n) KS_CK(hipMemcpyAsync(own_xyz, xyz, 3 * n * sizeof(float), hipMemcpyHostToDevice, s));
     }
-    KS_CK(hipMalloc(&d_c, 3 * kpad * sizeof(float)));
-    KS_CK(hipMalloc(&d_lab, (n ? n : 1) * sizeof(uint32_t)));
-    KS_CK(hipMalloc(&d_sums, kpad * 4 * sizeof(long long)));
-    KS_CK(hipMalloc(&d_changed, 2 * sizeof(unsigned int)));      // [0] labels changed, [1] (kd branch) tied points met without tables
-    KS_CK(hipMalloc(&d_nonfinite, kpad * sizeof(unsigned int)));
+    KS_CK(d_c.alloc(3 * kpad));
+    KS_CK(d_lab.alloc(n ? n : 1));
+    KS_CK(d_sums.alloc(kpad * 4));
+    KS_CK(d_changed.alloc(2));      // [0] labels changed, [1] (kd branch) tied points met without tables
+    KS_CK(d_nonfinite.alloc(kpad));
     KS_CK(hipMemsetAsync(d_nonfinite, 0, kpad * sizeof(unsigned int), s));
-    KS_CK(hipMalloc(&d_best, sizeof(unsigned long long)));
+    KS_CK(d_best.alloc(1));
     KS_CK(hipMemsetAsync(d_lab, 0, (n ? n : 1) * sizeof(uint32_t), s));   // point_to_cluster_index_map_.resize(n): zeros (:80)
     return CILHIP_OK;
   }
@@ -516,11 +517,11 @@ struct cilhip_kmeans_shard {
       if (kd_order) for (size_t t = 0; t < 3 * k; ++t) finite = finite && std::isfinite(centroids[t]);
       const bool ties_matter = kd_order && cilhip::g_knn_tie_rule != 0 && k > 1 && finite;
       if (ties_matter) {
-        if (!d_lab_prev) KS_CK(hipMalloc(&d_lab_prev, n * sizeof(uint32_t)));
+        if (!d_lab_prev) KS_CK(d_lab_prev.alloc(n));
         KS_CK(hipMemcpyAsync(d_lab_prev, d_lab, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
         KS_CK(hipMemsetAsync(d_changed + 1, 0, sizeof(unsigned int), s));
         a.tie_count = d_changed + 1;
-        if (!d_tie_list) KS_CK(hipMalloc(&d_tie_list, (size_t)KM_TIE_LIST * sizeof(uint2)));
+        if (!d_tie_list) KS_CK(d_tie_list.alloc(KM_TIE_LIST));
         a.tie_list = d_tie_list; a.tie_cap = KM_TIE_LIST;
       }
       KmGrid gr{};
@@ -528,7 +529,7 @@ struct cilhip_kmeans_shard {
       const size_t ncell1 = pruned ? (size_t)gr.g * gr.g * gr.g + 1 : 0;
       if (pruned) {
         // the grid of THIS iteration's centroids: sorted list + cell table, 20 KB
-        if (!d_cs) { KS_CK(hipMalloc(&d_cs, (kpad + 8) * sizeof(float4))); KS_CK(hipMalloc(&d_cstart, (16 * 16 * 16 + 1) * sizeof(uint32_t))); }
+        if (!d_cs || !d_cstart) { KS_CK(d_cs.alloc(kpad + 8)); KS_CK(d_cstart.alloc(16 * 16 * 16 + 1)); }
         KS_CK(hipMemcpyAsync(d_cs, cs_host.data(), (kpad + 8) * sizeof(float4), hipMemcpyHostToDevice, s));
         KS_CK(hipMemcpyAsync(d_cstart, cstart_host.data(), ncell1 * sizeof(uint32_t), hipMemcpyHostToDevice, s));
       }
@@ -549,8 +550,7 @@ struct cilhip_kmeans_shard {
         KS_CK(hipMemcpyAsync(&tied, d_changed + 1, sizeof(tied), hipMemcpyDeviceToHost, s));
         KS_CK(hipStreamSynchronize(s));
         if (tied != 0) {
-          if (!d_tleaf) { KS_CK(hipMalloc(&d_tleaf, 2 * kpad * sizeof(uint32_t))); KS_CK(hipMalloc(&d_tls, kpad * sizeof(uint2))); }
-          if (d_tnodes) { (void)hipFree(d_tnodes); d_tnodes = nullptr; }
+          if (!d_tleaf || !d_tls) { KS_CK(d_tleaf.alloc(2 * kpad)); KS_CK(d_tls.alloc(kpad)); }
           size_t nn = 0; int depth = 0;
           KS_CK(cilhip::tie_order_build_device(d_c, nullptr, (uint32_t)k, s, d_tleaf, d_tleaf + kpad, &d_tnodes, &nn, &depth));
           hipLaunchKernelGGL(k_zip_tables, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, s, (const uint32_t*)d_tleaf, (const uint32_t*)(d_tleaf + kpad), d_tls, (uint32_t)k);
@@ -616,26 +616,6 @@ struct cilhip_kmeans_shard {
     return CILHIP_OK;
   }
 #undef KS_CK
-  void release() {
-    (void)hipSetDevice(device);
-    if (s) (void)hipStreamSynchronize(s);
-    if (own_xyz && d_xyz) (void)hipFree(d_xyz);
-    if (d_c) (void)hipFree(d_c);
-    if (d_lab) (void)hipFree(d_lab);
-    if (d_sums) (void)hipFree(d_sums);
-    if (d_changed) (void)hipFree(d_changed);
-    if (d_nonfinite) (void)hipFree(d_nonfinite);
-    if (d_best) (void)hipFree(d_best);
-    if (d_cs) (void)hipFree(d_cs);
-    if (d_cstart) (void)hipFree(d_cstart);
-    if (d_tleaf) (void)hipFree(d_tleaf);
-    if (d_tls) (void)hipFree(d_tls);
-    if (d_tnodes) (void)hipFree(d_tnodes);
-    if (d_lab_prev) (void)hipFree(d_lab_prev);
-    if (d_tie_list) (void)hipFree(d_tie_list);
-    if (s) (void)hipStreamDestroy(s);
-    d_xyz = nullptr; s = nullptr;
-  }
 };
 
 namespace {
@@ -657,14 +637,13 @@ int kmeans_impl(int device, const float* xyz, size_t n, int mem, float* centroid
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return CILHIP_ERR_NO_DEVICE;
   if (device < 0 || device >= ndev) return CILHIP_ERR_INVALID;
-  int rc = CILHIP_OK;
   std::vector<long long> hs(k * 4);
   std::vector<float> c_old(3 * k);
   std::vector<uint32_t> nf(k);
   size_t iter = 0;
   cilhip_kmeans_shard sh;
-#define KM_RC(x) do { rc = (x); if (rc != CILHIP_OK) goto done; } while (0)
-  {
+#define KM_RC(x) do { const int rc_ = (x); if (rc_ != CILHIP_OK) return rc_; } while (0)
+  const int rc = [&]() -> int {
     KM_RC(sh.init(device, xyz, n, mem, k, 0));
     float fmax = 0.0f;
     KM_RC(sh.maxabs(&fmax));
@@ -711,11 +690,10 @@ int kmeans_impl(int device, const float* xyz, size_t n, int mem, float* centroid
       }
     }
     if (labels_out) KM_RC(sh.labels(labels_out));
-  }
-done:
+    return CILHIP_OK;
+  }();
 #undef KM_RC
   if (iterations_out) *iterations_out = iter;
-  sh.release();
   return rc;
 }
 
@@ -736,11 +714,11 @@ int cilhip_kmeans_shard_create(int device, const float* xyz, size_t n, int mem, 
   if (!h) return CILHIP_ERR_HIP;
   int rc = CILHIP_ERR_HIP;
   try { rc = h->init(device, xyz, n, mem, k, index_offset); } catch (...) { rc = CILHIP_ERR_HIP; }
-  if (rc != CILHIP_OK) { h->release(); delete h; return rc; }
+  if (rc != CILHIP_OK) { delete h; return rc; }
   *out = h;
   return CILHIP_OK;
 }
-void cilhip_kmeans_shard_destroy(cilhip_kmeans_shard* h) { if (h) { h->release(); delete h; } }
+void cilhip_kmeans_shard_destroy(cilhip_kmeans_shard* h) { delete h; }
 int cilhip_kmeans_shard_maxabs(cilhip_kmeans_shard* h, float* maxabs_out) { return (h && maxabs_out) ? h->maxabs(maxabs_out) : CILHIP_ERR_INVALID; }
 int cilhip_kmeans_scale_exponent(double maxabs_all, size_t n_all) { return kmeans_scale_exponent(maxabs_all, n_all); }
 int cilhip_kmeans_shard_assign(cilhip_kmeans_shard* h, const float* centroids, int scale_exponent, int use_kd_tree, int64_t* sums_out, uint64_t* changed_out) {

@@ -371,13 +371,7 @@ __global__ __launch_bounds__(KNN_THREADS) void k_radius_pca(KnnArgs a) {
 }
 
 
-#define KN_CK(x)               \
-  do {                         \
-    if ((x) != hipSuccess) {   \
-      rc = CILHIP_ERR_HIP;     \
-      goto done;               \
-    }                          \
-  } while (0)
+#define KN_CK(x) do { if ((x) != hipSuccess) return CILHIP_ERR_HIP; } while (0)
 
 int knn_impl(int device, const float* ref_xyz, size_t n_ref, const float* query_xyz, size_t n_query, int mem, size_t k, float max_sq_dist,
              uint32_t* idx_out, float* d2_out, uint32_t* cnt_out, bool do_pca, const float* view_point, float* normals_out,
@@ -388,39 +382,36 @@ int knn_impl(int device, const float* ref_xyz, size_t n_ref, const float* query_
   if (!(max_sq_dist > 0.0f)) max_sq_dist = 0.0f;   // NaN / negative radius: nothing is inside
   const bool self = query_xyz == nullptr;
   if (self) n_query = n_ref;
-  int rc = CILHIP_OK;
-  hipStream_t s = nullptr;
+  DevPool pool;      // every device allocation of this call (a caller's device clouds are only read)
   float *d_ref = nullptr, *d_q = nullptr, *d_d2 = nullptr, *d_nrm = nullptr, *d_curv = nullptr;
-  bool own_ref = false, own_q = false;
   float4* d_qs = nullptr;
   uint2* d_tiles = nullptr;
   float4* d_tc = nullptr;
   uint32_t *d_idx = nullptr, *d_cnt = nullptr;
   unsigned int* d_tiecnt = nullptr;
   uint2* d_tie_ls = nullptr;
-  uint4* d_tie_nodes = nullptr;
+  DevBuf<uint4> d_tie_nodes;
   uint32_t *d_tie_leaf = nullptr, *d_tie_slot = nullptr;
   GridBuildResult gr{};
-  bool have_grid = false;
+  SortWorkspace sort_ws;
+  StreamGuard s;      // (declared last: drained and destroyed before anything is freed)
   {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CILHIP_ERR_NO_DEVICE;
     KN_CK(hipSetDevice(device));
     if (n_query == 0) return CILHIP_OK;
-    KN_CK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    KN_CK(s.create());
     if (mem == CILHIP_MEM_DEVICE) {
       d_ref = const_cast<float*>(ref_xyz);
       d_q = self ? d_ref : const_cast<float*>(query_xyz);
     } else {
       if (n_ref) {
-        own_ref = true;
-        KN_CK(hipMalloc(&d_ref, 3 * n_ref * sizeof(float)));
+        KN_CK(pool.get(&d_ref, 3 * n_ref));
         KN_CK(hipMemcpyAsync(d_ref, ref_xyz, 3 * n_ref * sizeof(float), hipMemcpyHostToDevice, s));
       }
       if (self) d_q = d_ref;
       else {
-        own_q = true;
-        KN_CK(hipMalloc(&d_q, 3 * n_query * sizeof(float)));
+        KN_CK(pool.get(&d_q, 3 * n_query));
         KN_CK(hipMemcpyAsync(d_q, query_xyz, 3 * n_query * sizeof(float), hipMemcpyHostToDevice, s));
       }
     }
@@ -428,28 +419,29 @@ int knn_impl(int device, const float* ref_xyz, size_t n_ref, const float* query_
     // ~k/4 points per cell: the k-th neighbour then normally lies inside the 3x3x3 block of cells
     {
       const hipError_t eg = build_grid(d_ref, nullptr, (uint32_t)n_ref, s, &gr, mean, std::max(1.0, (double)k / 4.0));
-      if (eg == GRID_RANGE_ERROR) { set_stateless_error(std::string("grid: ") + kGridRangeMessage); rc = CILHIP_ERR_UNSUPPORTED; goto done; }
+      if (eg == GRID_RANGE_ERROR) { set_stateless_error(std::string("grid: ") + kGridRangeMessage); return CILHIP_ERR_UNSUPPORTED; }
       KN_CK(eg);
     }   // (radius-only: 1 point per cell)
-    have_grid = true;
     // queries in target-grid cell order (identity transform)
-    KN_CK(hipMalloc(&d_qs, n_query * sizeof(float4)));
+    KN_CK(pool.get(&d_qs, n_query));
     {
       const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
       float axes[9];
       uint32_t nt = 0;
-      KN_CK(sort_source(d_q, (uint32_t)n_query, gr.grid, I, d_qs, s, &d_tiles, &d_tc, axes, &nt));
+      KN_CK(sort_source(d_q, (uint32_t)n_query, gr.grid, I, d_qs, s, &d_tiles, &d_tc, axes, &nt, sort_ws));
+      KN_CK(hipStreamSynchronize(s));
+      sort_ws = SortWorkspace{};      // (only the sorted queries are used)
     }
     KnnArgs a{};
     a.g = gr.grid; a.queries = d_qs; a.nq = (uint32_t)n_query; a.k = (uint32_t)k; a.radius_sq = max_sq_dist;
-    if (idx_out) { KN_CK(hipMalloc(&d_idx, n_query * k * sizeof(uint32_t))); a.out_idx = d_idx; }
-    if (idx_out && d2_out) { KN_CK(hipMalloc(&d_d2, n_query * k * sizeof(float))); a.out_d2 = d_d2; }
-    if (cnt_out) { KN_CK(hipMalloc(&d_cnt, n_query * sizeof(uint32_t))); a.out_cnt = d_cnt; }
+    if (idx_out) { KN_CK(pool.get(&d_idx, n_query * k)); a.out_idx = d_idx; }
+    if (idx_out && d2_out) { KN_CK(pool.get(&d_d2, n_query * k)); a.out_d2 = d_d2; }
+    if (cnt_out) { KN_CK(pool.get(&d_cnt, n_query)); a.out_cnt = d_cnt; }
     a.do_pca = do_pca ? 1 : 0;
     if (do_pca) {
-      KN_CK(hipMalloc(&d_nrm, 3 * n_query * sizeof(float)));
+      KN_CK(pool.get(&d_nrm, 3 * n_query));
       a.ref_xyz = d_ref; a.normals = d_nrm;
-      if (curvature_out) { KN_CK(hipMalloc(&d_curv, n_query * sizeof(float))); a.curvature = d_curv; }
+      if (curvature_out) { KN_CK(pool.get(&d_curv, n_query)); a.curvature = d_curv; }
       a.use_vp = 0;
       if (view_point && std::isfinite(view_point[0]) && std::isfinite(view_point[1]) && std::isfinite(view_point[2])) {   // normal_estimation.hpp:366
         a.use_vp = 1;
@@ -463,7 +455,7 @@ int knn_impl(int device, const float* ref_xyz, size_t n_ref, const float* query_
       // again; rule 1 -- tables first; rule 0 -- the keys' own order (lowest index)
       const int rule = g_knn_tie_rule;
       a.tie = TieDev{}; a.tie.mode = rule != 0 ? 1 : 0; a.by_pos = 0;
-      if (rule != 0) { KN_CK(hipMalloc(&d_tiecnt, sizeof(unsigned int))); KN_CK(hipMemsetAsync(d_tiecnt, 0, sizeof(unsigned int), s)); a.tie_count = d_tiecnt; }
+      if (rule != 0) { KN_CK(pool.get(&d_tiecnt, 1)); KN_CK(hipMemsetAsync(d_tiecnt, 0, sizeof(unsigned int), s)); a.tie_count = d_tiecnt; }
       for (int pass = 0; pass < 2; ++pass) {
         bool need_tables = rule == 1 && pass == 0;
         if (!need_tables) {
@@ -480,9 +472,9 @@ int knn_impl(int device, const float* ref_xyz, size_t n_ref, const float* query_
           // the order tables of the tree the reference builds over the searched cloud (nanoflann 1.7.1, leaf size 10: core/kd_tree.hpp:162-170),
           // built on the device (tie_build.hip)
           size_t nn = 0;
-          KN_CK(hipMalloc(&d_tie_ls, n_ref * sizeof(uint2)));
-          KN_CK(hipMalloc(&d_tie_leaf, n_ref * sizeof(uint32_t)));
-          KN_CK(hipMalloc(&d_tie_slot, n_ref * sizeof(uint32_t)));
+          KN_CK(pool.get(&d_tie_ls, n_ref));
+          KN_CK(pool.get(&d_tie_leaf, n_ref));
+          KN_CK(pool.get(&d_tie_slot, n_ref));
           KN_CK(tie_order_build_device(d_ref, nullptr, (uint32_t)n_ref, s, d_tie_leaf, d_tie_slot, &d_tie_nodes, &nn, nullptr));
           launch_tie_tables_by_position(gr.grid.pts, gr.grid.n, d_tie_leaf, d_tie_slot, d_tie_ls, s);
           KN_CK(hipGetLastError());
@@ -498,25 +490,7 @@ int knn_impl(int device, const float* ref_xyz, size_t n_ref, const float* query_
     if (do_pca && curvature_out) KN_CK(hipMemcpyAsync(curvature_out, d_curv, n_query * sizeof(float), hipMemcpyDeviceToHost, s));
     KN_CK(hipStreamSynchronize(s));
   }
-done:
-  if (have_grid) free_grid(gr.grid);
-  if (own_ref && d_ref) (void)hipFree(d_ref);
-  if (own_q && d_q) (void)hipFree(d_q);
-  if (d_qs) (void)hipFree(d_qs);
-  if (d_tiles) (void)hipFree(d_tiles);
-  if (d_tc) (void)hipFree(d_tc);
-  if (d_idx) (void)hipFree(d_idx);
-  if (d_d2) (void)hipFree(d_d2);
-  if (d_cnt) (void)hipFree(d_cnt);
-  if (d_nrm) (void)hipFree(d_nrm);
-  if (d_curv) (void)hipFree(d_curv);
-  if (d_tiecnt) (void)hipFree(d_tiecnt);
-  if (d_tie_ls) (void)hipFree(d_tie_ls);
-  if (d_tie_nodes) (void)hipFree(d_tie_nodes);
-  if (d_tie_leaf) (void)hipFree(d_tie_leaf);
-  if (d_tie_slot) (void)hipFree(d_tie_slot);
-  if (s) (void)hipStreamDestroy(s);
-  return rc;
+  return CILHIP_OK;
 }
 
 
@@ -584,86 +558,84 @@ int radius_impl(int device, const float* ref_xyz, size_t n_ref, const float* que
   const bool self = query_xyz == nullptr;
   if (self) n_query = n_ref;
   if (total_out) *total_out = 0;
-  int rc = CILHIP_OK;
-  hipStream_t s = nullptr;
+  DevPool pool;
   float *d_ref = nullptr, *d_q = nullptr, *d_d2 = nullptr;
-  bool own_ref = false, own_q = false;
   float4* d_qs = nullptr;
   uint2* d_tiles = nullptr;
   float4* d_tc = nullptr;
   unsigned long long *d_cnt = nullptr, *d_keys = nullptr, *d_keys2 = nullptr;
   uint32_t *d_off32 = nullptr, *d_idx = nullptr;
-  void* d_tmp = nullptr;
   GridBuildResult gr{};
-  bool have_grid = false;
+  SortWorkspace sort_ws;
+  StreamGuard s;      // (declared last: drained and destroyed before anything is freed)
   {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CILHIP_ERR_NO_DEVICE;
     KN_CK(hipSetDevice(device));
     offsets_out[0] = 0;
     if (n_query == 0) return CILHIP_OK;
-    KN_CK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    KN_CK(s.create());
     if (mem == CILHIP_MEM_DEVICE) {
       d_ref = const_cast<float*>(ref_xyz);
       d_q = self ? d_ref : const_cast<float*>(query_xyz);
     } else {
       if (n_ref) {
-        own_ref = true;
-        KN_CK(hipMalloc(&d_ref, 3 * n_ref * sizeof(float)));
+        KN_CK(pool.get(&d_ref, 3 * n_ref));
         KN_CK(hipMemcpyAsync(d_ref, ref_xyz, 3 * n_ref * sizeof(float), hipMemcpyHostToDevice, s));
       }
       if (self) d_q = d_ref;
       else {
-        own_q = true;
-        KN_CK(hipMalloc(&d_q, 3 * n_query * sizeof(float)));
+        KN_CK(pool.get(&d_q, 3 * n_query));
         KN_CK(hipMemcpyAsync(d_q, query_xyz, 3 * n_query * sizeof(float), hipMemcpyHostToDevice, s));
       }
     }
     double mean[3];
     {
       const hipError_t eg = build_grid(d_ref, nullptr, (uint32_t)n_ref, s, &gr, mean, 2.0);
-      if (eg == GRID_RANGE_ERROR) { set_stateless_error(std::string("grid: ") + kGridRangeMessage); rc = CILHIP_ERR_UNSUPPORTED; goto done; }
+      if (eg == GRID_RANGE_ERROR) { set_stateless_error(std::string("grid: ") + kGridRangeMessage); return CILHIP_ERR_UNSUPPORTED; }
       KN_CK(eg);
     }
-    have_grid = true;
-    KN_CK(hipMalloc(&d_qs, n_query * sizeof(float4)));
+    KN_CK(pool.get(&d_qs, n_query));
     {
       const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
       float axes[9];
       uint32_t nt = 0;
-      KN_CK(sort_source(d_q, (uint32_t)n_query, gr.grid, I, d_qs, s, &d_tiles, &d_tc, axes, &nt));
+      KN_CK(sort_source(d_q, (uint32_t)n_query, gr.grid, I, d_qs, s, &d_tiles, &d_tc, axes, &nt, sort_ws));
+      KN_CK(hipStreamSynchronize(s));
+      sort_ws = SortWorkspace{};      // (only the sorted queries are used)
     }
     const unsigned nblk = (unsigned)((n_query + KNN_THREADS - 1) / KNN_THREADS);
-    KN_CK(hipMalloc(&d_cnt, (n_query + 1) * sizeof(unsigned long long)));
+    KN_CK(pool.get(&d_cnt, n_query + 1));
     KN_CK(hipMemsetAsync(d_cnt, 0, (n_query + 1) * sizeof(unsigned long long), s));
     hipLaunchKernelGGL((k_radius_lists<false>), dim3(nblk), dim3(KNN_THREADS), 0, s, gr.grid, (const float4*)d_qs, (uint32_t)n_query, radius_sq, d_cnt,
                        (unsigned long long*)nullptr);
     {  // counts -> offsets (exclusive scan over n_query + 1 entries: the last one is the total), in place
       size_t tmp_bytes = 0;
       KN_CK(rocprim::exclusive_scan(nullptr, tmp_bytes, d_cnt, d_cnt, 0ull, n_query + 1, rocprim::plus<unsigned long long>(), s));
-      KN_CK(hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 8));
-      KN_CK(rocprim::exclusive_scan(d_tmp, tmp_bytes, d_cnt, d_cnt, 0ull, n_query + 1, rocprim::plus<unsigned long long>(), s));
-      (void)hipFree(d_tmp); d_tmp = nullptr;
+      DevBuf<unsigned char> d_tmp;
+      KN_CK(d_tmp.alloc(tmp_bytes));
+      KN_CK(rocprim::exclusive_scan(d_tmp.get(), tmp_bytes, d_cnt, d_cnt, 0ull, n_query + 1, rocprim::plus<unsigned long long>(), s));
     }
     KN_CK(hipMemcpyAsync(offsets_out, d_cnt, (n_query + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     KN_CK(hipStreamSynchronize(s));
     const size_t total = (size_t)offsets_out[n_query];
     if (total_out) *total_out = total;
     if (idx_out && capacity >= total && total > 0) {
-      if (total > 0xFFFFFFF0ull) { rc = CILHIP_ERR_UNSUPPORTED; goto done; }   // one segmented sort call takes 32-bit sizes
-      KN_CK(hipMalloc(&d_keys, total * sizeof(unsigned long long)));
-      KN_CK(hipMalloc(&d_keys2, total * sizeof(unsigned long long)));
+      if (total > 0xFFFFFFF0ull) return CILHIP_ERR_UNSUPPORTED;   // one segmented sort call takes 32-bit sizes
+      KN_CK(pool.get(&d_keys, total));
+      KN_CK(pool.get(&d_keys2, total));
       hipLaunchKernelGGL((k_radius_lists<true>), dim3(nblk), dim3(KNN_THREADS), 0, s, gr.grid, (const float4*)d_qs, (uint32_t)n_query, radius_sq, d_cnt, d_keys);
-      KN_CK(hipMalloc(&d_off32, (n_query + 1) * sizeof(uint32_t)));
+      KN_CK(pool.get(&d_off32, n_query + 1));
       hipLaunchKernelGGL(k_offsets32, dim3(256), dim3(256), 0, s, (const unsigned long long*)d_cnt, (uint32_t)(n_query + 1), d_off32);
       {
         size_t tmp_bytes = 0;
         KN_CK(rocprim::segmented_radix_sort_keys(nullptr, tmp_bytes, d_keys, d_keys2, (unsigned int)total, (unsigned int)n_query, d_off32, d_off32 + 1, 0, 64, s));
-        KN_CK(hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 8));
+        void* d_tmp = nullptr;
+        KN_CK(pool.bytes(&d_tmp, tmp_bytes));
         KN_CK(rocprim::segmented_radix_sort_keys(d_tmp, tmp_bytes, d_keys, d_keys2, (unsigned int)total, (unsigned int)n_query, d_off32, d_off32 + 1, 0, 64, s));
       }
-      KN_CK(hipMalloc(&d_idx, total * sizeof(uint32_t)));
-      if (d2_out) KN_CK(hipMalloc(&d_d2, total * sizeof(float)));
+      KN_CK(pool.get(&d_idx, total));
+      if (d2_out) KN_CK(pool.get(&d_d2, total));
       hipLaunchKernelGGL(k_unpack_radius, dim3(2048), dim3(256), 0, s, (const unsigned long long*)d_keys2, total, d_idx, d_d2);
       KN_CK(hipGetLastError());
       KN_CK(hipMemcpyAsync(idx_out, d_idx, total * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -671,22 +643,7 @@ int radius_impl(int device, const float* ref_xyz, size_t n_ref, const float* que
       KN_CK(hipStreamSynchronize(s));
     }
   }
-done:
-  if (have_grid) free_grid(gr.grid);
-  if (own_ref && d_ref) (void)hipFree(d_ref);
-  if (own_q && d_q) (void)hipFree(d_q);
-  if (d_qs) (void)hipFree(d_qs);
-  if (d_tiles) (void)hipFree(d_tiles);
-  if (d_tc) (void)hipFree(d_tc);
-  if (d_cnt) (void)hipFree(d_cnt);
-  if (d_keys) (void)hipFree(d_keys);
-  if (d_keys2) (void)hipFree(d_keys2);
-  if (d_off32) (void)hipFree(d_off32);
-  if (d_idx) (void)hipFree(d_idx);
-  if (d_d2) (void)hipFree(d_d2);
-  if (d_tmp) (void)hipFree(d_tmp);
-  if (s) (void)hipStreamDestroy(s);
-  return rc;
+  return CILHIP_OK;
 }
 
 }  // namespace

@@ -56,6 +56,8 @@ struct cilhip_multi {
   int n = 0;
   std::vector<int> dev;
   std::vector<cilhip_ctx*> ctx;
+  DevPool mem;                     // owns d_sums / d_bufs: as long as the handle
+  DevPool key_mem;                 // owns d_keys / d_okeys / d_kbufs: as long as the partition (multi_free_keys)
   std::vector<double*> d_sums;
   bool distinct = true;            // all ordinals different: RCCL; otherwise the same-device reduction
   RcclApi rccl;
@@ -95,13 +97,8 @@ struct cilhip_multi {
 static int mfail(cilhip_multi* m, int code, const std::string& msg) { if (m) m->err = msg; return code; }
 static int multi_upload_fwd(cilhip_multi* m);
 static void multi_free_keys(cilhip_multi* m) {
-  for (size_t r = 0; r < m->d_keys.size(); ++r) {
-    (void)hipSetDevice(m->dev[r]);
-    if (m->d_keys[r]) (void)hipFree(m->d_keys[r]);
-    if (m->d_okeys[r]) (void)hipFree(m->d_okeys[r]);
-  }
-  m->d_keys.clear(); m->d_okeys.clear();
-  if (m->d_kbufs) { (void)hipSetDevice(m->dev[0]); (void)hipFree(m->d_kbufs); m->d_kbufs = nullptr; }
+  m->key_mem.clear();
+  m->d_keys.clear(); m->d_okeys.clear(); m->d_kbufs = nullptr;
 }
 #define MCK(m, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return mfail((m), CILHIP_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
 #define MCTX(m, r, call) do { const int rc_ = (call); if (rc_ != CILHIP_OK) return mfail((m), rc_, std::string(#call) + ": " + cilhip_last_error((m)->ctx[r])); } while (0)
@@ -123,7 +120,7 @@ int cilhip_multi_create(cilhip_multi** out, const int* devices, int ndev) {
   int rc = CILHIP_OK;
   for (int r = 0; r < ndev && rc == CILHIP_OK; ++r) {
     rc = cilhip_create(&m->ctx[r], devices[r]);
-    if (rc == CILHIP_OK && (hipSetDevice(devices[r]) != hipSuccess || hipMalloc(&m->d_sums[r], SUMS_MAX * sizeof(double)) != hipSuccess)) rc = CILHIP_ERR_HIP;
+    if (rc == CILHIP_OK && (hipSetDevice(devices[r]) != hipSuccess || m->mem.get(&m->d_sums[r], SUMS_MAX) != hipSuccess)) rc = CILHIP_ERR_HIP;
   }
   // (CILHIP_MULTI_FORCE_RCCL=1: a single shard goes through RCCL too -- a communicator of one rank: what a one-GPU box can check of that path)
   const bool force_rccl = ndev == 1 && getenv("CILHIP_MULTI_FORCE_RCCL") != nullptr && atoi(getenv("CILHIP_MULTI_FORCE_RCCL")) != 0;
@@ -136,7 +133,7 @@ int cilhip_multi_create(cilhip_multi** out, const int* devices, int ndev) {
       }
     } else {
       for (int r = 1; r < ndev; ++r) if (devices[r] != devices[0]) rc = CILHIP_ERR_UNSUPPORTED;   // (repeated ordinals: all shards on one device)
-      if (rc == CILHIP_OK && (hipSetDevice(devices[0]) != hipSuccess || hipMalloc(&m->d_bufs, ndev * sizeof(double*)) != hipSuccess ||
+      if (rc == CILHIP_OK && (hipSetDevice(devices[0]) != hipSuccess || m->mem.get(&m->d_bufs, ndev) != hipSuccess ||
                               hipMemcpy(m->d_bufs, m->d_sums.data(), ndev * sizeof(double*), hipMemcpyHostToDevice) != hipSuccess))
         rc = CILHIP_ERR_HIP;
       for (int r = 0; r < ndev && rc == CILHIP_OK; ++r) { hipEvent_t e; if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) rc = CILHIP_ERR_HIP; else m->ev.push_back(e); }
@@ -151,11 +148,8 @@ void cilhip_multi_destroy(cilhip_multi* m) {
   if (!m) return;
   for (size_t r = 0; r < m->comms.size(); ++r) if (m->comms[r] && m->rccl.CommDestroy) (void)m->rccl.CommDestroy(m->comms[r]);
   for (int r = 0; r < m->n; ++r) {
-    if (m->d_sums[r]) { (void)hipSetDevice(m->dev[r]); (void)hipFree(m->d_sums[r]); }
     if (m->ctx[r]) cilhip_destroy(m->ctx[r]);
   }
-  if (m->d_bufs) (void)hipFree(m->d_bufs);
-  multi_free_keys(m);
   for (hipEvent_t e : m->ev) (void)hipEventDestroy(e);
   cilhip_tie_order_destroy(m->order);
   delete m;
@@ -227,15 +221,15 @@ static int multi_upload(cilhip_multi* m) {
       MCTX(m, r, cilhip_set_shard_info(m->ctx[r], lo, m->gdm, m->gsm));
       MCTX(m, r, cilhip_set_slab_guard(m->ctx[r], -1, 0.0f, nullptr, nullptr, nullptr));
       MCK(m, hipSetDevice(m->dev[r]));
-      MCK(m, hipMalloc(&m->d_keys[r], (m->ns ? m->ns : 1) * sizeof(unsigned long long)));
-      MCK(m, hipMalloc(&m->d_okeys[r], (m->ns ? m->ns : 1) * sizeof(unsigned long long)));
+      MCK(m, m->key_mem.get(&m->d_keys[r], m->ns));
+      MCK(m, m->key_mem.get(&m->d_okeys[r], m->ns));
       m->n_dst_local[r] = hi - lo; m->n_src_local[r] = m->ns;
     }
     if (!m->distinct && n > 1) {
       std::vector<unsigned long long*> both(m->d_keys);
       both.insert(both.end(), m->d_okeys.begin(), m->d_okeys.end());
       MCK(m, hipSetDevice(m->dev[0]));
-      MCK(m, hipMalloc(&m->d_kbufs, both.size() * sizeof(unsigned long long*)));
+      MCK(m, m->key_mem.get(&m->d_kbufs, both.size()));
       MCK(m, hipMemcpy(m->d_kbufs, both.data(), both.size() * sizeof(unsigned long long*), hipMemcpyHostToDevice));
     }
     return CILHIP_OK;

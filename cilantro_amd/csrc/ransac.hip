@@ -16,6 +16,7 @@
 // the same plane.  Model fit: f32 per-term arithmetic, f64 accumulation in a fixed order (bitwise
 // reproducible), f64 Jacobi eigen-solve (solve.hpp) in place of Eigen's f32 SelfAdjointEigenSolver.
 #include "../../include/cilantro_hip/c_api.h"
+#include "device_mem.hpp"
 #include "solve.hpp"
 
 #include <hip/hip_runtime.h>
@@ -313,13 +314,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_write_final(const float* __restr
   }
 }
 
-#define RS_CK(x)                          \
-  do {                                    \
-    if ((x) != hipSuccess) {              \
-      rc = CILHIP_ERR_HIP;                \
-      goto done;                          \
-    }                                     \
-  } while (0)
+#define RS_CK(x) do { if ((x) != hipSuccess) return CILHIP_ERR_HIP; } while (0)
 
 inline uint64_t splitmix64(uint64_t& s) {
   uint64_t z = (s += 0x9E3779B97F4A7C15ull);
@@ -332,9 +327,10 @@ inline uint64_t bounded(uint64_t& s, uint64_t bound) {   // uniform in [0, bound
   return (uint64_t)(((unsigned __int128)splitmix64(s) * bound) >> 64);
 }
 
+// what one call holds on the device: views into the pool's allocations (xyz: or the caller's device cloud), released at scope exit
 struct Buffers {
+  cilhip::DevPool pool;
   float* xyz = nullptr;
-  bool own_xyz = false;
   uint32_t* samples = nullptr;
   float4* planes = nullptr;
   uint32_t* partial = nullptr;
@@ -344,23 +340,8 @@ struct Buffers {
   float* residuals = nullptr;
   uint32_t* inliers = nullptr;
   uint32_t* counts = nullptr;
-  hipStream_t s = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  void release() {
-    if (own_xyz && xyz) (void)hipFree(xyz);
-    if (samples) (void)hipFree(samples);
-    if (planes) (void)hipFree(planes);
-    if (partial) (void)hipFree(partial);
-    if (dpartial) (void)hipFree(dpartial);
-    if (chunk_counts) (void)hipFree(chunk_counts);
-    if (st) (void)hipFree(st);
-    if (residuals) (void)hipFree(residuals);
-    if (inliers) (void)hipFree(inliers);
-    if (counts) (void)hipFree(counts);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (s) (void)hipStreamDestroy(s);
-  }
+  cilhip::EventGuard e0, e1;
+  cilhip::StreamGuard s;      // (last: drained and destroyed before the events and the allocations go)
 };
 
 // blocks of the scoring pass: the kernel alternates vector arithmetic with scalar population counts, so it wants many waves per SIMD
@@ -382,7 +363,6 @@ int cilhip_plane_ransac3f(int device, const float* xyz, size_t n, int mem, const
                           float max_residual, size_t target_inliers, size_t max_iter, int re_estimate,
                           cilhip_plane_model* out, float* residuals_out, uint32_t* inliers_out) {
   if (!out || (!xyz && n) || n > 0xFFFFFFF0ull || max_iter > 0x0FFFFFFFull) return CILHIP_ERR_INVALID;
-  int rc = CILHIP_OK;
   Buffers b;
   RansacState hs;
   std::memset(&hs, 0, sizeof hs);
@@ -390,21 +370,20 @@ int cilhip_plane_ransac3f(int device, const float* xyz, size_t n, int mem, const
   const uint32_t sample_size = n < 3 ? (uint32_t)n : 3u;          // ransac_base.hpp:67
   if (target_inliers > n) target_inliers = n;                     // :68
   float ms = 0.0f;
-  {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CILHIP_ERR_NO_DEVICE;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CILHIP_ERR_NO_DEVICE;
+  const int rc = [&]() -> int {      // (whatever it returns, `out` is filled from hs below)
     RS_CK(hipSetDevice(device));
-    RS_CK(hipStreamCreateWithFlags(&b.s, hipStreamNonBlocking));
-    RS_CK(hipEventCreate(&b.e0));
-    RS_CK(hipEventCreate(&b.e1));
-    RS_CK(hipMalloc(&b.st, sizeof(RansacState)));
+    RS_CK(b.s.create());
+    RS_CK(b.e0.create());
+    RS_CK(b.e1.create());
+    RS_CK(b.pool.get(&b.st, 1));
     RS_CK(hipMemcpyAsync(b.st, &hs, sizeof hs, hipMemcpyHostToDevice, b.s));
     if (n > 0 && max_iter > 0) {
       if (mem == CILHIP_MEM_DEVICE) {
         b.xyz = const_cast<float*>(xyz);
       } else {
-        b.own_xyz = true;
-        RS_CK(hipMalloc(&b.xyz, 3 * n * sizeof(float)));
+        RS_CK(b.pool.get(&b.xyz, 3 * n));
         RS_CK(hipMemcpyAsync(b.xyz, xyz, 3 * n * sizeof(float), hipMemcpyHostToDevice, b.s));
       }
       // the random samples (ransac_base.hpp:83-91): 3 distinct indices per iteration; drawn on the host
@@ -428,15 +407,15 @@ int cilhip_plane_ransac3f(int device, const float* xyz, size_t n, int mem, const
         samples = hsamp.data();
       } else {
         for (size_t i = 0; i < 3 * max_iter; ++i)
-          if ((i % 3) < sample_size && samples[i] >= n) { rc = CILHIP_ERR_INVALID; goto done; }
+          if ((i % 3) < sample_size && samples[i] >= n) return CILHIP_ERR_INVALID;
       }
       const size_t mpad = (max_iter + RS_ROUND - 1) / RS_ROUND * RS_ROUND;
       const int nb = score_blocks(n);
-      RS_CK(hipMalloc(&b.samples, 3 * max_iter * sizeof(uint32_t)));
-      RS_CK(hipMalloc(&b.planes, mpad * sizeof(float4)));
-      RS_CK(hipMalloc(&b.partial, (size_t)nb * RS_ROUND * sizeof(uint32_t)));
-      RS_CK(hipMalloc(&b.dpartial, (size_t)RS_MAX_BLOCKS * 8 * sizeof(double)));
-      RS_CK(hipMalloc(&b.chunk_counts, RS_MAX_BLOCKS * sizeof(uint32_t)));
+      RS_CK(b.pool.get(&b.samples, 3 * max_iter));
+      RS_CK(b.pool.get(&b.planes, mpad));
+      RS_CK(b.pool.get(&b.partial, (size_t)nb * RS_ROUND));
+      RS_CK(b.pool.get(&b.dpartial, (size_t)RS_MAX_BLOCKS * 8));
+      RS_CK(b.pool.get(&b.chunk_counts, RS_MAX_BLOCKS));
       RS_CK(hipMemcpyAsync(b.samples, samples, 3 * max_iter * sizeof(uint32_t), hipMemcpyHostToDevice, b.s));
       RS_CK(hipEventRecord(b.e0, b.s));
       hipLaunchKernelGGL(k_models, dim3((unsigned)((mpad + 127) / 128)), dim3(128), 0, b.s, b.xyz, b.samples, sample_size,
@@ -460,8 +439,8 @@ int cilhip_plane_ransac3f(int device, const float* xyz, size_t n, int mem, const
       const int cb = (int)((n + chunk - 1) / chunk);
       hipLaunchKernelGGL(k_chunk_counts, dim3(cb), dim3(RS_THREADS), 0, b.s, b.xyz, (uint32_t)n, chunk, max_residual, b.st, b.chunk_counts);
       hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(64), 0, b.s, b.chunk_counts, cb, b.st);
-      if (residuals_out) RS_CK(hipMalloc(&b.residuals, n * sizeof(float)));
-      if (inliers_out) RS_CK(hipMalloc(&b.inliers, n * sizeof(uint32_t)));
+      if (residuals_out) RS_CK(b.pool.get(&b.residuals, n));
+      if (inliers_out) RS_CK(b.pool.get(&b.inliers, n));
       if (residuals_out || inliers_out)
         hipLaunchKernelGGL(k_write_final, dim3(cb), dim3(RS_THREADS), 0, b.s, b.xyz, (uint32_t)n, chunk, max_residual, b.st,
                            b.chunk_counts, b.residuals, b.inliers);
@@ -481,15 +460,14 @@ int cilhip_plane_ransac3f(int device, const float* xyz, size_t n, int mem, const
         RS_CK(hipMemcpy(inliers_out, b.inliers, (size_t)hs.n_inliers * sizeof(uint32_t), hipMemcpyDeviceToHost));
       (void)any;
     }
-  }
-done:
+    return CILHIP_OK;
+  }();
   for (int d = 0; d < 3; ++d) out->normal[d] = hs.best[d];
   out->offset = hs.best[3];
   out->iterations = hs.iterations;
   out->n_inliers = hs.n_inliers;
   out->target_reached = hs.n_inliers >= target_inliers ? 1 : 0;   // ransac_base.hpp:172
   out->device_ms = (double)ms;
-  b.release();
   return rc;
 }
 
@@ -497,28 +475,26 @@ int cilhip_plane_score3f(int device, const float* xyz, size_t n, int mem, const 
                          uint32_t* counts_out) {
   if ((!xyz && n) || (!planes && m) || (!counts_out && m) || n > 0xFFFFFFF0ull) return CILHIP_ERR_INVALID;
   if (m == 0) return CILHIP_OK;
-  int rc = CILHIP_OK;
   Buffers b;
   {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CILHIP_ERR_NO_DEVICE;
     RS_CK(hipSetDevice(device));
-    RS_CK(hipStreamCreateWithFlags(&b.s, hipStreamNonBlocking));
-    if (n == 0) { std::memset(counts_out, 0, m * sizeof(uint32_t)); goto done; }
+    RS_CK(b.s.create());
+    if (n == 0) { std::memset(counts_out, 0, m * sizeof(uint32_t)); return CILHIP_OK; }
     if (mem == CILHIP_MEM_DEVICE) {
       b.xyz = const_cast<float*>(xyz);
     } else {
-      b.own_xyz = true;
-      RS_CK(hipMalloc(&b.xyz, 3 * n * sizeof(float)));
+      RS_CK(b.pool.get(&b.xyz, 3 * n));
       RS_CK(hipMemcpyAsync(b.xyz, xyz, 3 * n * sizeof(float), hipMemcpyHostToDevice, b.s));
     }
     const size_t mpad = (m + RS_ROUND - 1) / RS_ROUND * RS_ROUND;
     const int nb = score_blocks(n);
     std::vector<float> hp(4 * mpad, NAN);
     std::memcpy(hp.data(), planes, 4 * m * sizeof(float));
-    RS_CK(hipMalloc(&b.planes, mpad * sizeof(float4)));
-    RS_CK(hipMalloc(&b.partial, (size_t)nb * RS_ROUND * sizeof(uint32_t)));
-    RS_CK(hipMalloc(&b.counts, mpad * sizeof(uint32_t)));
+    RS_CK(b.pool.get(&b.planes, mpad));
+    RS_CK(b.pool.get(&b.partial, (size_t)nb * RS_ROUND));
+    RS_CK(b.pool.get(&b.counts, mpad));
     RS_CK(hipMemcpyAsync(b.planes, hp.data(), 4 * mpad * sizeof(float), hipMemcpyHostToDevice, b.s));
     for (size_t r0 = 0; r0 < m; r0 += RS_ROUND) {
       const uint32_t mm = (uint32_t)(m - r0 < RS_ROUND ? m - r0 : RS_ROUND);
@@ -531,34 +507,30 @@ int cilhip_plane_score3f(int device, const float* xyz, size_t n, int mem, const 
     RS_CK(hipMemcpyAsync(counts_out, b.counts, m * sizeof(uint32_t), hipMemcpyDeviceToHost, b.s));
     RS_CK(hipStreamSynchronize(b.s));
   }
-done:
-  b.release();
-  return rc;
+  return CILHIP_OK;
 }
 
 int cilhip_plane_fit3f(int device, const float* xyz, size_t n, int mem, float plane_out[4]) {
   if (!plane_out || (!xyz && n) || n > 0xFFFFFFF0ull) return CILHIP_ERR_INVALID;
-  int rc = CILHIP_OK;
   Buffers b;
   RansacState hs;
   std::memset(&hs, 0, sizeof hs);
   for (int d = 0; d < 4; ++d) hs.best[d] = NAN;
-  {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CILHIP_ERR_NO_DEVICE;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CILHIP_ERR_NO_DEVICE;
+  const int rc = [&]() -> int {      // (whatever it returns, plane_out is filled from hs below)
     RS_CK(hipSetDevice(device));
     if (n >= 2) {
-      RS_CK(hipStreamCreateWithFlags(&b.s, hipStreamNonBlocking));
-      RS_CK(hipMalloc(&b.st, sizeof(RansacState)));
+      RS_CK(b.s.create());
+      RS_CK(b.pool.get(&b.st, 1));
       RS_CK(hipMemcpyAsync(b.st, &hs, sizeof hs, hipMemcpyHostToDevice, b.s));
       if (mem == CILHIP_MEM_DEVICE) {
         b.xyz = const_cast<float*>(xyz);
       } else {
-        b.own_xyz = true;
-        RS_CK(hipMalloc(&b.xyz, 3 * n * sizeof(float)));
+        RS_CK(b.pool.get(&b.xyz, 3 * n));
         RS_CK(hipMemcpyAsync(b.xyz, xyz, 3 * n * sizeof(float), hipMemcpyHostToDevice, b.s));
       }
-      RS_CK(hipMalloc(&b.dpartial, (size_t)RS_MAX_BLOCKS * 8 * sizeof(double)));
+      RS_CK(b.pool.get(&b.dpartial, (size_t)RS_MAX_BLOCKS * 8));
       const int mb = (int)std::min<size_t>((n + RS_THREADS - 1) / RS_THREADS, RS_MAX_BLOCKS);
       hipLaunchKernelGGL(k_moments<0>, dim3(mb), dim3(RS_THREADS), 0, b.s, b.xyz, (uint32_t)n, 0.0f, 1, b.st, b.dpartial);
       hipLaunchKernelGGL(k_moments_finish<0>, dim3(1), dim3(64), 0, b.s, b.dpartial, mb, b.st);
@@ -568,10 +540,9 @@ int cilhip_plane_fit3f(int device, const float* xyz, size_t n, int mem, float pl
       RS_CK(hipMemcpyAsync(&hs, b.st, sizeof hs, hipMemcpyDeviceToHost, b.s));
       RS_CK(hipStreamSynchronize(b.s));
     }
-  }
-done:
+    return CILHIP_OK;
+  }();
   for (int d = 0; d < 4; ++d) plane_out[d] = hs.best[d];
-  b.release();
   return rc;
 }
 

@@ -19,6 +19,7 @@
 // moments (products of f32 coordinates are exact in f64), f64 SVD -- Eigen's JacobiSVD<Matrix3f> round-off is "parity
 // unpinned" (Eigen is absent from the build container), as for every estimator of this engine.
 #include "../../include/cilantro_hip/c_api.h"
+#include "device_mem.hpp"
 #include "solve.hpp"
 
 #include <hip/hip_runtime.h>
@@ -244,13 +245,7 @@ __global__ __launch_bounds__(TR_THREADS) void k_twrite_final(const float* __rest
   }
 }
 
-#define TR_CK(x)                          \
-  do {                                    \
-    if ((x) != hipSuccess) {              \
-      rc = CILHIP_ERR_HIP;                \
-      goto done;                          \
-    }                                     \
-  } while (0)
+#define TR_CK(x) do { if ((x) != hipSuccess) return CILHIP_ERR_HIP; } while (0)
 
 inline uint64_t splitmix64(uint64_t& s) {
   uint64_t z = (s += 0x9E3779B97F4A7C15ull);
@@ -274,9 +269,10 @@ inline float sq_threshold(float thr) {
   return x;
 }
 
+// what one call holds on the device: views into the pool's allocations (dst / src: or the caller's device clouds), released at scope exit
 struct TBuffers {
+  cilhip::DevPool pool;
   float *dst = nullptr, *src = nullptr;
-  bool own = false;
   uint32_t* samples = nullptr;
   float* models = nullptr;
   uint32_t* partial = nullptr;
@@ -286,30 +282,13 @@ struct TBuffers {
   float* residuals = nullptr;
   uint32_t* inliers = nullptr;
   uint32_t* counts = nullptr;
-  hipStream_t s = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  void release() {
-    if (own && dst) (void)hipFree(dst);
-    if (own && src) (void)hipFree(src);
-    if (samples) (void)hipFree(samples);
-    if (models) (void)hipFree(models);
-    if (partial) (void)hipFree(partial);
-    if (dpartial) (void)hipFree(dpartial);
-    if (chunk_counts) (void)hipFree(chunk_counts);
-    if (st) (void)hipFree(st);
-    if (residuals) (void)hipFree(residuals);
-    if (inliers) (void)hipFree(inliers);
-    if (counts) (void)hipFree(counts);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (s) (void)hipStreamDestroy(s);
-  }
+  cilhip::EventGuard e0, e1;
+  cilhip::StreamGuard s;      // (last: drained and destroyed before the events and the allocations go)
   hipError_t upload(const float* d, const float* sc, size_t n, int mem) {
     if (mem == CILHIP_MEM_DEVICE) { dst = const_cast<float*>(d); src = const_cast<float*>(sc); return hipSuccess; }
-    own = true;
-    hipError_t e = hipMalloc(&dst, 3 * n * sizeof(float));
+    hipError_t e = pool.get(&dst, 3 * n);
     if (e != hipSuccess) return e;
-    e = hipMalloc(&src, 3 * n * sizeof(float));
+    e = pool.get(&src, 3 * n);
     if (e != hipSuccess) return e;
     e = hipMemcpyAsync(dst, d, 3 * n * sizeof(float), hipMemcpyHostToDevice, s);
     if (e != hipSuccess) return e;
@@ -337,7 +316,6 @@ int cilhip_transform_ransac3f(int device, const float* dst_xyz, const float* src
                               float max_residual, size_t target_inliers, size_t max_iter, int re_estimate, cilhip_transform_model* out,
                               float* residuals_out, uint32_t* inliers_out) {
   if (!out || ((!dst_xyz || !src_xyz) && n) || n > 0xFFFFFFF0ull || max_iter > 0x0FFFFFFFull) return CILHIP_ERR_INVALID;
-  int rc = CILHIP_OK;
   TBuffers b;
   TState hs;
   std::memset(&hs, 0, sizeof hs);
@@ -346,14 +324,14 @@ int cilhip_transform_ransac3f(int device, const float* dst_xyz, const float* src
   if (target_inliers > n) target_inliers = n;                     // :68
   const float thr_sq = sq_threshold(max_residual);
   float ms = 0.0f;
-  {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CILHIP_ERR_NO_DEVICE;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CILHIP_ERR_NO_DEVICE;
+  const int rc = [&]() -> int {      // (whatever it returns, `out` is filled from hs below)
     TR_CK(hipSetDevice(device));
-    TR_CK(hipStreamCreateWithFlags(&b.s, hipStreamNonBlocking));
-    TR_CK(hipEventCreate(&b.e0));
-    TR_CK(hipEventCreate(&b.e1));
-    TR_CK(hipMalloc(&b.st, sizeof(TState)));
+    TR_CK(b.s.create());
+    TR_CK(b.e0.create());
+    TR_CK(b.e1.create());
+    TR_CK(b.pool.get(&b.st, 1));
     TR_CK(hipMemcpyAsync(b.st, &hs, sizeof hs, hipMemcpyHostToDevice, b.s));
     if (n > 0) {
       TR_CK(b.upload(dst_xyz, src_xyz, n, mem));
@@ -377,15 +355,15 @@ int cilhip_transform_ransac3f(int device, const float* dst_xyz, const float* src
         samples = hsamp.data();
       } else if (samples) {
         for (size_t i = 0; i < 3 * max_iter; ++i)
-          if ((i % 3) < sample_size && samples[i] >= n) { rc = CILHIP_ERR_INVALID; goto done; }
+          if ((i % 3) < sample_size && samples[i] >= n) return CILHIP_ERR_INVALID;
       }
       const size_t mpad = ((max_iter ? max_iter : 1) + TR_ROUND - 1) / TR_ROUND * TR_ROUND;
       const int nb = tscore_blocks(n);
-      TR_CK(hipMalloc(&b.samples, 3 * (max_iter ? max_iter : 1) * sizeof(uint32_t)));
-      TR_CK(hipMalloc(&b.models, mpad * 12 * sizeof(float)));
-      TR_CK(hipMalloc(&b.partial, (size_t)nb * TR_ROUND * sizeof(uint32_t)));
-      TR_CK(hipMalloc(&b.dpartial, (size_t)TR_MAX_BLOCKS * 16 * sizeof(double)));
-      TR_CK(hipMalloc(&b.chunk_counts, TR_MAX_BLOCKS * sizeof(uint32_t)));
+      TR_CK(b.pool.get(&b.samples, 3 * (max_iter ? max_iter : 1)));
+      TR_CK(b.pool.get(&b.models, mpad * 12));
+      TR_CK(b.pool.get(&b.partial, (size_t)nb * TR_ROUND));
+      TR_CK(b.pool.get(&b.dpartial, (size_t)TR_MAX_BLOCKS * 16));
+      TR_CK(b.pool.get(&b.chunk_counts, TR_MAX_BLOCKS));
       if (max_iter) TR_CK(hipMemcpy(b.samples, samples, 3 * max_iter * sizeof(uint32_t), hipMemcpyHostToDevice));      // (blocking: `samples` may be a local vector)
       TR_CK(hipEventRecord(b.e0, b.s));
       if (max_iter)
@@ -409,8 +387,8 @@ int cilhip_transform_ransac3f(int device, const float* dst_xyz, const float* src
       }
       hipLaunchKernelGGL(k_tchunk_counts, dim3(cb), dim3(TR_THREADS), 0, b.s, b.dst, b.src, (uint32_t)n, chunk, thr_sq, b.st, b.chunk_counts);
       hipLaunchKernelGGL(k_tscan_counts, dim3(1), dim3(64), 0, b.s, b.chunk_counts, cb, b.st);
-      if (residuals_out) TR_CK(hipMalloc(&b.residuals, n * sizeof(float)));
-      if (inliers_out) TR_CK(hipMalloc(&b.inliers, n * sizeof(uint32_t)));
+      if (residuals_out) TR_CK(b.pool.get(&b.residuals, n));
+      if (inliers_out) TR_CK(b.pool.get(&b.inliers, n));
       if (residuals_out || inliers_out)
         hipLaunchKernelGGL(k_twrite_final, dim3(cb), dim3(TR_THREADS), 0, b.s, b.dst, b.src, (uint32_t)n, chunk, thr_sq, b.st, b.chunk_counts,
                            b.residuals, b.inliers);
@@ -427,15 +405,14 @@ int cilhip_transform_ransac3f(int device, const float* dst_xyz, const float* src
       if (inliers_out && b.inliers && hs.n_inliers)
         TR_CK(hipMemcpy(inliers_out, b.inliers, (size_t)hs.n_inliers * sizeof(uint32_t), hipMemcpyDeviceToHost));
     }
-  }
-done:
+    return CILHIP_OK;
+  }();
   pack_model(hs.best, out->T);
   out->iterations = hs.iterations;
   out->n_inliers = hs.n_inliers;
   out->have_model = hs.have_model;
   out->target_reached = hs.n_inliers >= target_inliers ? 1 : 0;   // ransac_base.hpp:172
   out->device_ms = (double)ms;
-  b.release();
   return rc;
 }
 
@@ -443,15 +420,14 @@ int cilhip_transform_score3f(int device, const float* dst_xyz, const float* src_
                              float max_residual, uint32_t* counts_out) {
   if (((!dst_xyz || !src_xyz) && n) || (!transforms && m) || (!counts_out && m) || n > 0xFFFFFFF0ull) return CILHIP_ERR_INVALID;
   if (m == 0) return CILHIP_OK;
-  int rc = CILHIP_OK;
   TBuffers b;
   const float thr_sq = sq_threshold(max_residual);
   {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CILHIP_ERR_NO_DEVICE;
     TR_CK(hipSetDevice(device));
-    TR_CK(hipStreamCreateWithFlags(&b.s, hipStreamNonBlocking));
-    if (n == 0) { std::memset(counts_out, 0, m * sizeof(uint32_t)); goto done; }
+    TR_CK(b.s.create());
+    if (n == 0) { std::memset(counts_out, 0, m * sizeof(uint32_t)); return CILHIP_OK; }
     TR_CK(b.upload(dst_xyz, src_xyz, n, mem));
     const size_t mpad = (m + TR_ROUND - 1) / TR_ROUND * TR_ROUND;
     const int nb = tscore_blocks(n);
@@ -460,9 +436,9 @@ int cilhip_transform_score3f(int device, const float* dst_xyz, const float* src_
       const float* T = transforms + 16 * h;
       for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) hm[12 * h + r * 3 + c] = T[c * 4 + r]; hm[12 * h + 9 + r] = T[12 + r]; }
     }
-    TR_CK(hipMalloc(&b.models, mpad * 12 * sizeof(float)));
-    TR_CK(hipMalloc(&b.partial, (size_t)nb * TR_ROUND * sizeof(uint32_t)));
-    TR_CK(hipMalloc(&b.counts, mpad * sizeof(uint32_t)));
+    TR_CK(b.pool.get(&b.models, mpad * 12));
+    TR_CK(b.pool.get(&b.partial, (size_t)nb * TR_ROUND));
+    TR_CK(b.pool.get(&b.counts, mpad));
     TR_CK(hipMemcpyAsync(b.models, hm.data(), 12 * mpad * sizeof(float), hipMemcpyHostToDevice, b.s));
     for (size_t r0 = 0; r0 < m; r0 += TR_ROUND) {
       const uint32_t mm = (uint32_t)(m - r0 < TR_ROUND ? m - r0 : TR_ROUND);
@@ -475,28 +451,25 @@ int cilhip_transform_score3f(int device, const float* dst_xyz, const float* src_
     TR_CK(hipMemcpyAsync(counts_out, b.counts, m * sizeof(uint32_t), hipMemcpyDeviceToHost, b.s));
     TR_CK(hipStreamSynchronize(b.s));
   }
-done:
-  b.release();
-  return rc;
+  return CILHIP_OK;
 }
 
 int cilhip_transform_fit3f(int device, const float* dst_xyz, const float* src_xyz, size_t n, int mem, float T_out[16]) {
   if (!T_out || ((!dst_xyz || !src_xyz) && n) || n > 0xFFFFFFF0ull) return CILHIP_ERR_INVALID;
-  int rc = CILHIP_OK;
   TBuffers b;
   TState hs;
   std::memset(&hs, 0, sizeof hs);
   hs.best[0] = hs.best[4] = hs.best[8] = 1.0f;
-  {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CILHIP_ERR_NO_DEVICE;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CILHIP_ERR_NO_DEVICE;
+  const int rc = [&]() -> int {      // (whatever it returns, T_out is filled from hs below)
     TR_CK(hipSetDevice(device));
     if (n > 0) {
-      TR_CK(hipStreamCreateWithFlags(&b.s, hipStreamNonBlocking));
-      TR_CK(hipMalloc(&b.st, sizeof(TState)));
+      TR_CK(b.s.create());
+      TR_CK(b.pool.get(&b.st, 1));
       TR_CK(hipMemcpyAsync(b.st, &hs, sizeof hs, hipMemcpyHostToDevice, b.s));
       TR_CK(b.upload(dst_xyz, src_xyz, n, mem));
-      TR_CK(hipMalloc(&b.dpartial, (size_t)TR_MAX_BLOCKS * 16 * sizeof(double)));
+      TR_CK(b.pool.get(&b.dpartial, (size_t)TR_MAX_BLOCKS * 16));
       const int mb = (int)std::min<size_t>((n + TR_THREADS - 1) / TR_THREADS, TR_MAX_BLOCKS);
       hipLaunchKernelGGL(k_tmoments, dim3(mb), dim3(TR_THREADS), 0, b.s, b.dst, b.src, (uint32_t)n, 0.0f, 1, b.st, b.dpartial);
       hipLaunchKernelGGL(k_tmoments_finish, dim3(1), dim3(64), 0, b.s, b.dpartial, mb, b.st);
@@ -504,10 +477,9 @@ int cilhip_transform_fit3f(int device, const float* dst_xyz, const float* src_xy
       TR_CK(hipMemcpyAsync(&hs, b.st, sizeof hs, hipMemcpyDeviceToHost, b.s));
       TR_CK(hipStreamSynchronize(b.s));
     }
-  }
-done:
+    return CILHIP_OK;
+  }();
   pack_model(hs.best, T_out);
-  b.release();
   return rc;
 }
 

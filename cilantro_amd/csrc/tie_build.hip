@@ -536,12 +536,13 @@ __global__ __launch_bounds__(SMALL_T) void k_build_small(const float* xyz, const
   if (t == 0) { w.out[0] = s_nodes; w.out[1] = depth; }
 }
 
+#define TB_TRY(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
+
 // the build of a cloud of at most SMALL_N points: one allocation, one launch, one read-back
-hipError_t build_small(const float* d_xyz, const float4* d_sorted, uint32_t n, hipStream_t s, uint32_t* d_leaf_by_index, uint32_t* d_slot_by_index, uint4** d_nodes_out,
+hipError_t build_small(const float* d_xyz, const float4* d_sorted, uint32_t n, hipStream_t s, uint32_t* d_leaf_by_index, uint32_t* d_slot_by_index, DevBuf<uint4>* d_nodes_out,
                        size_t* n_nodes_out, int* max_depth_out) {
-  hipError_t e = hipSuccess;
-  void* ws = nullptr;
-  uint4* nodes = nullptr;
+  DevBuf<unsigned char> ws;
+  DevBuf<uint4> nodes;
   const size_t node_cap = 2 * (size_t)n + 2;      // (every split leaves both children non-empty: at most 2n - 1 nodes)
   size_t off = 0;
   auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
@@ -550,39 +551,32 @@ hipError_t build_small(const float* d_xyz, const float4* d_sorted, uint32_t n, h
                o_iscan = take((2 * (size_t)SMALL_ACT + 2) * 4), o_cmm = take((2 * (size_t)SMALL_ACT + 2) * sizeof(MM<3>)), o_act0 = take((size_t)SMALL_ACT * sizeof(Act<3>)),
                o_act1 = take((size_t)SMALL_ACT * sizeof(Act<3>)), o_out = take(16);
   uint32_t h_out[2] = {0, 0};
-  do {
-    if ((e = hipMalloc(&ws, off)) != hipSuccess) break;
-    if ((e = hipMalloc(&nodes, node_cap * sizeof(uint4))) != hipSuccess) break;
-    unsigned char* b = static_cast<unsigned char*>(ws);
-    SmallWs w{(Rec<3>*)(b + o_recA), (Rec<3>*)(b + o_recB), (uint32_t*)(b + o_node), (uint32_t*)(b + o_flags), (uint32_t*)(b + o_S), (uint32_t*)(b + o_posF), (uint32_t*)(b + o_posU),
-              (uint32_t*)(b + o_int), (uint32_t*)(b + o_iscan), (MM<3>*)(b + o_cmm), (Act<3>*)(b + o_act0), (Act<3>*)(b + o_act1), (uint32_t*)(b + o_out)};
-    hipLaunchKernelGGL(k_build_small, dim3(1), dim3(SMALL_T), 0, s, d_xyz, d_sorted, n, w, nodes, (uint32_t)node_cap, d_leaf_by_index, d_slot_by_index);
-    if ((e = hipGetLastError()) != hipSuccess) break;
-    if ((e = hipMemcpyAsync(h_out, w.out, 8, hipMemcpyDeviceToHost, s)) != hipSuccess) break;
-    if ((e = hipStreamSynchronize(s)) != hipSuccess) break;
-    if (h_out[1] > 200u) { e = hipErrorUnknown; break; }
-    *d_nodes_out = nodes; nodes = nullptr;
-    *n_nodes_out = h_out[0];
-    if (max_depth_out) *max_depth_out = (int)h_out[1];
-  } while (0);
-  if (ws) (void)hipFree(ws);
-  if (nodes) (void)hipFree(nodes);
-  return e;
+  TB_TRY(ws.alloc(off));
+  TB_TRY(nodes.alloc(node_cap));
+  unsigned char* b = ws;
+  SmallWs w{(Rec<3>*)(b + o_recA), (Rec<3>*)(b + o_recB), (uint32_t*)(b + o_node), (uint32_t*)(b + o_flags), (uint32_t*)(b + o_S), (uint32_t*)(b + o_posF), (uint32_t*)(b + o_posU),
+            (uint32_t*)(b + o_int), (uint32_t*)(b + o_iscan), (MM<3>*)(b + o_cmm), (Act<3>*)(b + o_act0), (Act<3>*)(b + o_act1), (uint32_t*)(b + o_out)};
+  hipLaunchKernelGGL(k_build_small, dim3(1), dim3(SMALL_T), 0, s, d_xyz, d_sorted, n, w, nodes.get(), (uint32_t)node_cap, d_leaf_by_index, d_slot_by_index);
+  TB_TRY(hipGetLastError());
+  TB_TRY(hipMemcpyAsync(h_out, w.out, 8, hipMemcpyDeviceToHost, s));
+  TB_TRY(hipStreamSynchronize(s));
+  if (h_out[1] > 200u) return hipErrorUnknown;
+  *d_nodes_out = std::move(nodes);
+  *n_nodes_out = h_out[0];
+  if (max_depth_out) *max_depth_out = (int)h_out[1];
+  return hipSuccess;
 }
-
-#define TB_TRY(x) do { e = (x); if (e != hipSuccess) goto done; } while (0)
 
 // The build.  Records come from d_xyz (DIM = 3: the cloud in its ORIGINAL order) or from d_sorted (+ the feature parts att1 / att2 by the
 // same positions, weighted): back to the original order first -- the reference's vAcc_ starts as 0 .. n-1.
 template <int DIM>
 hipError_t build_impl(const float* d_xyz, const float4* d_sorted, const float4* att1, float w1, const float4* att2, float w2, uint32_t n, hipStream_t s,
-                      uint32_t* d_leaf_by_index, uint32_t* d_slot_by_index, uint4** d_nodes_out, size_t* n_nodes_out, int* max_depth_out) {
+                      uint32_t* d_leaf_by_index, uint32_t* d_slot_by_index, DevBuf<uint4>* d_nodes_out, size_t* n_nodes_out, int* max_depth_out) {
   typedef Rec<DIM> R;
   typedef MM<DIM> M;
   typedef Act<DIM> A;
-  *d_nodes_out = nullptr; *n_nodes_out = 0; if (max_depth_out) *max_depth_out = 0;
+  d_nodes_out->reset(); *n_nodes_out = 0; if (max_depth_out) *max_depth_out = 0;
   if (n == 0) return hipSuccess;
-  hipError_t e = hipSuccess;
   const unsigned gp = (unsigned)std::min<size_t>(((size_t)n + TB) / TB, 65535u * 4u);
   // active nodes of a level hold more than LEAF_MAX points each; a level's children: twice that; all nodes: bounded by 2n (leaves of one
   // point), in practice ~0.3 n -- the node array grows by doubling when a level does not fit
@@ -593,8 +587,9 @@ hipError_t build_impl(const float* d_xyz, const float4* d_sorted, const float4* 
   uint32_t *counts = nullptr, *nruns = nullptr;
   M *agg = nullptr, *child_mm = nullptr;
   A *act0 = nullptr, *act1 = nullptr;
-  uint4* nodes = nullptr;
-  void *tmp = nullptr, *ws = nullptr;
+  DevBuf<uint4> nodes;
+  DevBuf<unsigned char> ws;
+  void* tmp = nullptr;
   size_t tmp_bytes = 0;
   uint32_t h_counts[2] = {0, 0};
   int depth = 0;
@@ -617,17 +612,17 @@ hipError_t build_impl(const float* d_xyz, const float4* d_sorted, const float4* 
                    o_agg = take(run_cap * sizeof(M)), o_cmm = take((2 * (size_t)act_cap + 2) * sizeof(M)), o_int = take((2 * (size_t)act_cap + 2) * 4),
                    o_iscan = take((2 * (size_t)act_cap + 2) * 4), o_counts = take(16), o_nruns = take(4), o_act0 = take((size_t)act_cap * sizeof(A)),
                    o_act1 = take((size_t)act_cap * sizeof(A)), o_tmp = take(tmp_bytes ? tmp_bytes : 16);
-      TB_TRY(hipMalloc(&ws, off));
-      unsigned char* b = static_cast<unsigned char*>(ws);
+      TB_TRY(ws.alloc(off));
+      unsigned char* b = ws;
       recA = (R*)(b + o_recA); recB = (R*)(b + o_recB); node_of = (uint32_t*)(b + o_node); flags = (uint32_t*)(b + o_flags); S = (uint32_t*)(b + o_S);
       posF = (uint32_t*)(b + o_posF); posU = (uint32_t*)(b + o_posU); keys = (uint32_t*)(b + o_keys); uk = (uint32_t*)(b + o_uk); agg = (M*)(b + o_agg);
       child_mm = (M*)(b + o_cmm); internal = (uint32_t*)(b + o_int); iscan = (uint32_t*)(b + o_iscan); counts = (uint32_t*)(b + o_counts); nruns = (uint32_t*)(b + o_nruns);
       act0 = (A*)(b + o_act0); act1 = (A*)(b + o_act1); tmp = b + o_tmp;
     }
-    TB_TRY(hipMalloc(&nodes, node_cap * sizeof(uint4)));
+    TB_TRY(nodes.alloc(node_cap));
     if (d_sorted) hipLaunchKernelGGL((k_init_recs_from_sorted<DIM>), dim3(gp), dim3(TB), 0, s, d_sorted, att1, w1, att2, w2, n, recA, node_of);
     else if (DIM == 3) hipLaunchKernelGGL(k_init_recs, dim3(gp), dim3(TB), 0, s, d_xyz, n, reinterpret_cast<Rec<3>*>(recA), node_of);
-    else { e = hipErrorInvalidValue; goto done; }
+    else return hipErrorInvalidValue;
     // the root's box: one run of key 0
     TB_TRY(hipMemsetAsync(keys, 0, (size_t)n * 4, s));
     {
@@ -645,11 +640,11 @@ hipError_t build_impl(const float* d_xyz, const float4* d_sorted, const float4* 
       const uint32_t na = h_counts[0];
       if ((size_t)h_counts[1] + 2 * (size_t)na > node_cap) {      // the node array grows (degenerate clouds: many tiny leaves)
         const size_t ncap = std::max(node_cap * 2, (size_t)h_counts[1] + 2 * (size_t)na + 64);
-        uint4* nn = nullptr;
-        TB_TRY(hipMalloc(&nn, ncap * sizeof(uint4)));
+        DevBuf<uint4> nn;
+        TB_TRY(nn.alloc(ncap));
         TB_TRY(hipMemcpyAsync(nn, nodes, (size_t)h_counts[1] * sizeof(uint4), hipMemcpyDeviceToDevice, s));
         TB_TRY(hipStreamSynchronize(s));
-        (void)hipFree(nodes); nodes = nn; node_cap = ncap;
+        nodes = std::move(nn); node_cap = ncap;
       }
       const unsigned ga = (na + TB) / TB + 1;
       hipLaunchKernelGGL((k_decide<DIM>), dim3(ga), dim3(TB), 0, s, cur, (const uint32_t*)cnt_cur);
@@ -687,29 +682,26 @@ hipError_t build_impl(const float* d_xyz, const float4* d_sorted, const float4* 
       TB_TRY(hipStreamSynchronize(s));
       std::swap(cur, nxt); std::swap(cnt_cur, cnt_nxt);
       ++depth;
-      if (depth > 200) { e = hipErrorUnknown; goto done; }      // (cannot happen: every split leaves both children non-empty)
+      if (depth > 200) return hipErrorUnknown;      // (cannot happen: every split leaves both children non-empty)
     }
     TB_TRY(hipGetLastError());
     TB_TRY(hipStreamSynchronize(s));
-    *d_nodes_out = nodes; nodes = nullptr;
+    *d_nodes_out = std::move(nodes);
     *n_nodes_out = h_counts[1];
     if (max_depth_out) *max_depth_out = depth;
   }
-done:
-  if (ws) (void)hipFree(ws);
-  if (nodes) (void)hipFree(nodes);
-  return e;
+  return hipSuccess;
 }
 
 }  // namespace
 
 // d_xyz: the cloud in its ORIGINAL order (3 floats per point), or d_sorted: {x, y, z, bits(original index)} records in any order (one
-// of the two).  d_leaf_by_index / d_slot_by_index: [n], by ORIGINAL index.  *d_nodes_out: the TieNode records (hipMalloc'ed here, the
-// caller frees), *n_nodes_out how many; *max_depth_out the deepest node's depth.
+// of the two).  d_leaf_by_index / d_slot_by_index: [n], by ORIGINAL index.  *d_nodes_out: the TieNode records,
+// *n_nodes_out how many; *max_depth_out the deepest node's depth.
 hipError_t tie_order_build_device(const float* d_xyz, const float4* d_sorted, uint32_t n, hipStream_t s, uint32_t* d_leaf_by_index, uint32_t* d_slot_by_index,
-                                  uint4** d_nodes_out, size_t* n_nodes_out, int* max_depth_out) {
+                                  DevBuf<uint4>* d_nodes_out, size_t* n_nodes_out, int* max_depth_out) {
   if (n != 0 && n <= SMALL_N && (d_xyz != nullptr) != (d_sorted != nullptr)) {      // one workgroup: a launch instead of twenty per level
-    *d_nodes_out = nullptr; *n_nodes_out = 0; if (max_depth_out) *max_depth_out = 0;
+    d_nodes_out->reset(); *n_nodes_out = 0; if (max_depth_out) *max_depth_out = 0;
     return build_small(d_xyz, d_sorted, n, s, d_leaf_by_index, d_slot_by_index, d_nodes_out, n_nodes_out, max_depth_out);
   }
   return build_impl<3>(d_xyz, d_sorted, nullptr, 0.0f, nullptr, 0.0f, n, s, d_leaf_by_index, d_slot_by_index, d_nodes_out, n_nodes_out, max_depth_out);
@@ -717,7 +709,7 @@ hipError_t tie_order_build_device(const float* d_xyz, const float4* d_sorted, ui
 // The tree of a feature adaptor's search: records (p, w1 * att1[, w2 * att2]) from the grid's sorted points and the attributes at the same
 // positions; dim = 6 or 9.  Node records carry the split dimension in four bits: TieNode::info = (depth << 5) | (dimension << 1) | second child.
 hipError_t tie_order_build_device_features(int dim, const float4* d_sorted, const float4* att1, float w1, const float4* att2, float w2, uint32_t n, hipStream_t s,
-                                           uint32_t* d_leaf_by_index, uint32_t* d_slot_by_index, uint4** d_nodes_out, size_t* n_nodes_out, int* max_depth_out) {
+                                           uint32_t* d_leaf_by_index, uint32_t* d_slot_by_index, DevBuf<uint4>* d_nodes_out, size_t* n_nodes_out, int* max_depth_out) {
   if (dim == 6) return build_impl<6>(nullptr, d_sorted, att1, w1, nullptr, 0.0f, n, s, d_leaf_by_index, d_slot_by_index, d_nodes_out, n_nodes_out, max_depth_out);
   if (dim == 9) return build_impl<9>(nullptr, d_sorted, att1, w1, att2, w2, n, s, d_leaf_by_index, d_slot_by_index, d_nodes_out, n_nodes_out, max_depth_out);
   return hipErrorInvalidValue;

@@ -883,6 +883,10 @@ int cilhip_get_last_timing2(cilhip_ctx* ctx, double* search_ms, double* accumula
 /* Tiled search bookkeeping of the most recent search launch: out[0] = queries, out[1] = whole tiles that were
  * handed to the global-memory clean-up pass (syncs). */
 int cilhip_debug_counters(cilhip_ctx* ctx, uint32_t out[2]);
+/* Stateless: out[0] = device allocations the library holds in this process right now (all contexts, handles and calls in flight),
+ * out[1] = their bytes.  Every allocation and free of the library goes through one pair of functions that keeps the two counts, so
+ * "nothing leaked" can be checked exactly, without reading the device's free memory (which other processes move). */
+int cilhip_debug_live_allocations(unsigned long long out[2]);
 
 #ifdef __cplusplus
 }

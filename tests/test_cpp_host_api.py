@@ -71,3 +71,14 @@ def test_grid_policy_on_host(hip_lib, orc):
         subprocess.check_call(["bash", os.path.join(ROOT, "tests", "cpp", "build.sh")])
     out = subprocess.run([binp], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and "ALL OK" in out.stdout, out.stdout + out.stderr
+
+
+def test_device_mem_on_host(hip_lib, orc):
+    """cilantro_amd/csrc/device_mem.hpp owns every device allocation of the library: its owners (single buffer, shared buffer,
+    per-call pool) over a counting allocator backed by malloc that can fail a chosen request -- growth, failure, moves, every
+    release order of three sharers, early returns; live count and bytes back at their start after each case.  Host compiler, no GPU."""
+    binp = os.path.join(ROOT, "tests", "cpp", "bin", "test_device_mem")
+    if not os.path.exists(binp):
+        subprocess.check_call(["bash", os.path.join(ROOT, "tests", "cpp", "build.sh")])
+    out = subprocess.run([binp], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "ALL OK" in out.stdout, out.stdout + out.stderr
