@@ -10,6 +10,7 @@
 #include <new>
 
 #include "ctx.hpp"
+#include "stateless.hpp"
 
 // (multi.hip -- the C entry of the multi-device loops -- drives contexts through the public entry points; these two are all it reads of one)
 namespace cilhip {

@@ -42,6 +42,7 @@
 
 #include "../../include/cilantro_hip/c_api.h"
 #include "internal.hpp"
+#include "stateless.hpp"
 
 namespace cilhip {
 
@@ -263,8 +264,6 @@ unsigned cc_bits(uint32_t v) {      // bits that hold 0 .. v
   return b;
 }
 
-#define CC_CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_stateless_error(std::string("connected_components: ") + #x + ": " + hipGetErrorString(e_)); return CILHIP_ERR_HIP; } } while (0)
-
 struct CcOut {
   int mem;
   size_t n;
@@ -282,78 +281,67 @@ int cc_finish(const CcOut& o, DevPool& pool, hipStream_t s, uint32_t* parent) {
   uint32_t *root = nullptr, *count = nullptr, *seeded = nullptr, *rank = nullptr;
   unsigned long long *keys = nullptr, *keys_sorted = nullptr;
   unsigned int* n_kept_d = nullptr;
-  CC_CK(pool.bytes(&root, n * sizeof(uint32_t)));
-  CC_CK(pool.bytes(&count, n * sizeof(uint32_t)));
-  CC_CK(pool.bytes(&keys, n * sizeof(unsigned long long)));
-  CC_CK(pool.bytes(&keys_sorted, n * sizeof(unsigned long long)));
-  CC_CK(pool.bytes(&n_kept_d, sizeof(unsigned int)));
+  ST_CK("connected_components", pool.bytes(&root, n * sizeof(uint32_t)));
+  ST_CK("connected_components", pool.bytes(&count, n * sizeof(uint32_t)));
+  ST_CK("connected_components", pool.bytes(&keys, n * sizeof(unsigned long long)));
+  ST_CK("connected_components", pool.bytes(&keys_sorted, n * sizeof(unsigned long long)));
+  ST_CK("connected_components", pool.bytes(&n_kept_d, sizeof(unsigned int)));
   hipLaunchKernelGGL(k_cc_flatten, grid, block, 0, s, (const uint32_t*)parent, root, n);
   if (o.seeds) {
     uint32_t* d_seeds = nullptr;
-    CC_CK(pool.bytes(&seeded, n * sizeof(uint32_t)));
-    CC_CK(pool.bytes(&d_seeds, o.n_seeds * sizeof(uint32_t)));
-    CC_CK(hipMemsetAsync(seeded, 0, n * sizeof(uint32_t), s));
+    ST_CK("connected_components", pool.bytes(&seeded, n * sizeof(uint32_t)));
+    ST_CK("connected_components", pool.bytes(&d_seeds, o.n_seeds * sizeof(uint32_t)));
+    ST_CK("connected_components", hipMemsetAsync(seeded, 0, n * sizeof(uint32_t), s));
     if (o.n_seeds) {
-      CC_CK(hipMemcpyAsync(d_seeds, o.seeds, o.n_seeds * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+      ST_CK("connected_components", hipMemcpyAsync(d_seeds, o.seeds, o.n_seeds * sizeof(uint32_t), hipMemcpyHostToDevice, s));
       hipLaunchKernelGGL(k_cc_mark_seeds, dim3(cc_blocks(o.n_seeds)), block, 0, s, (const uint32_t*)root, (const uint32_t*)d_seeds, o.n_seeds, seeded);
     }
   }
-  CC_CK(hipMemsetAsync(count, 0, n * sizeof(uint32_t), s));
-  CC_CK(hipMemsetAsync(n_kept_d, 0, sizeof(unsigned int), s));
+  ST_CK("connected_components", hipMemsetAsync(count, 0, n * sizeof(uint32_t), s));
+  ST_CK("connected_components", hipMemsetAsync(n_kept_d, 0, sizeof(unsigned int), s));
   hipLaunchKernelGGL(k_cc_sizes, grid, block, 0, s, (const uint32_t*)root, n, count);
   hipLaunchKernelGGL(k_cc_keys, grid, block, 0, s, (const uint32_t*)root, (const uint32_t*)count, (const uint32_t*)seeded, n, o.min_size, o.max_size, keys, n_kept_d);
-  CC_CK(hipGetLastError());
+  ST_CK("connected_components", hipGetLastError());
   {
     size_t tmp_bytes = 0;
     void* tmp = nullptr;
-    CC_CK(rocprim::radix_sort_keys(nullptr, tmp_bytes, keys, keys_sorted, n, 0u, 64u, s));
-    CC_CK(pool.bytes(&tmp, tmp_bytes));
-    CC_CK(rocprim::radix_sort_keys(tmp, tmp_bytes, keys, keys_sorted, n, 0u, 64u, s));
+    ST_CK("connected_components", rocprim::radix_sort_keys(nullptr, tmp_bytes, keys, keys_sorted, n, 0u, 64u, s));
+    ST_CK("connected_components", pool.bytes(&tmp, tmp_bytes));
+    ST_CK("connected_components", rocprim::radix_sort_keys(tmp, tmp_bytes, keys, keys_sorted, n, 0u, 64u, s));
   }
   unsigned int n_kept = 0;      // the one host round trip of the chain
-  CC_CK(hipMemcpyAsync(&n_kept, n_kept_d, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
-  CC_CK(hipStreamSynchronize(s));
+  ST_CK("connected_components", hipMemcpyAsync(&n_kept, n_kept_d, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+  ST_CK("connected_components", hipStreamSynchronize(s));
   rank = count;      // (the sizes are in the keys now)
-  CC_CK(hipMemsetAsync(rank, 0xFF, n * sizeof(uint32_t), s));
+  ST_CK("connected_components", hipMemsetAsync(rank, 0xFF, n * sizeof(uint32_t), s));
   hipLaunchKernelGGL(k_cc_rank, dim3(cc_blocks(n_kept)), block, 0, s, (const unsigned long long*)keys_sorted, (uint32_t)n_kept, rank);
   const bool host = o.mem == CILHIP_MEM_HOST;
   uint32_t* d_labels = o.labels;
-  if (host) CC_CK(pool.bytes(&d_labels, n * sizeof(uint32_t)));
+  if (host) ST_CK("connected_components", pool.bytes(&d_labels, n * sizeof(uint32_t)));
   hipLaunchKernelGGL(k_cc_labels, grid, block, 0, s, (const uint32_t*)root, (const uint32_t*)rank, (uint32_t)n_kept, n, d_labels);
-  CC_CK(hipGetLastError());
-  if (host) CC_CK(hipMemcpyAsync(o.labels, d_labels, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  ST_CK("connected_components", hipGetLastError());
+  if (host) ST_CK("connected_components", hipMemcpyAsync(o.labels, d_labels, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   if (o.offsets || o.members) {
     // a stable sort of the point indices by label: every segment's members in ascending index, the unlabelled points behind them
     uint32_t *iota = root, *lab_sorted = reinterpret_cast<uint32_t*>(keys), *d_members = o.members, *d_offsets = o.offsets;      // (roots and unsorted keys are done with)
-    if (host || !d_members) CC_CK(pool.bytes(&d_members, n * sizeof(uint32_t)));
-    if (host || !d_offsets) CC_CK(pool.bytes(&d_offsets, ((size_t)n_kept + 1) * sizeof(uint32_t)));
+    if (host || !d_members) ST_CK("connected_components", pool.bytes(&d_members, n * sizeof(uint32_t)));
+    if (host || !d_offsets) ST_CK("connected_components", pool.bytes(&d_offsets, ((size_t)n_kept + 1) * sizeof(uint32_t)));
     hipLaunchKernelGGL(k_cc_init, grid, block, 0, s, iota, n);
     size_t tmp_bytes = 0;
     void* tmp = nullptr;
     const unsigned bits = cc_bits(n_kept);
-    CC_CK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_labels, lab_sorted, iota, d_members, n, 0u, bits, s));
-    CC_CK(pool.bytes(&tmp, tmp_bytes));
-    CC_CK(rocprim::radix_sort_pairs(tmp, tmp_bytes, d_labels, lab_sorted, iota, d_members, n, 0u, bits, s));
+    ST_CK("connected_components", rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_labels, lab_sorted, iota, d_members, n, 0u, bits, s));
+    ST_CK("connected_components", pool.bytes(&tmp, tmp_bytes));
+    ST_CK("connected_components", rocprim::radix_sort_pairs(tmp, tmp_bytes, d_labels, lab_sorted, iota, d_members, n, 0u, bits, s));
     const uint32_t n32 = (uint32_t)n;
-    CC_CK(hipMemcpyAsync(d_offsets + n_kept, &n32, sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    ST_CK("connected_components", hipMemcpyAsync(d_offsets + n_kept, &n32, sizeof(uint32_t), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_cc_offsets, grid, block, 0, s, (const uint32_t*)lab_sorted, n, d_offsets);
-    CC_CK(hipGetLastError());
-    if (host && o.offsets) CC_CK(hipMemcpyAsync(o.offsets, d_offsets, ((size_t)n_kept + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    if (host && o.members) CC_CK(hipMemcpyAsync(o.members, d_members, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    ST_CK("connected_components", hipGetLastError());
+    if (host && o.offsets) ST_CK("connected_components", hipMemcpyAsync(o.offsets, d_offsets, ((size_t)n_kept + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (host && o.members) ST_CK("connected_components", hipMemcpyAsync(o.members, d_members, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   }
-  CC_CK(hipStreamSynchronize(s));
+  ST_CK("connected_components", hipStreamSynchronize(s));
   *o.n_segments = n_kept;
-  return CILHIP_OK;
-}
-
-int cc_open(int device, StreamGuard& st) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-    set_stateless_error("connected_components: no such HIP device (the segmentation runs on the device: there is no CPU path)");
-    return CILHIP_ERR_NO_DEVICE;
-  }
-  CC_CK(hipSetDevice(device));
-  CC_CK(st.create());
   return CILHIP_OK;
 }
 
@@ -361,36 +349,31 @@ int cc_run_fused(int device, const float* xyz, const float* nrm, const float* rg
   DevPool pool;
   GridBuildResult grid{};      // the radius search's grid
   StreamGuard st;      // (declared last: the stream is drained and destroyed before anything is freed)
-  if (int rc = cc_open(device, st)) return rc;
+  if (const int open = st_open("connected_components", device)) return open;
+  ST_CK("connected_components", st.create());
   hipStream_t s = st.s;
   const size_t n = o.n;
   const F3* d_in[3] = {nullptr, nullptr, nullptr};
   const float* src[3] = {xyz, cl.use_normals ? nrm : nullptr, cl.use_colors ? rgb : nullptr};
-  for (int k = 0; k < 3; ++k) {
-    if (!src[k]) continue;
-    if (o.mem == CILHIP_MEM_DEVICE) { d_in[k] = reinterpret_cast<const F3*>(src[k]); continue; }
-    F3* d = nullptr;
-    CC_CK(pool.bytes(&d, n * sizeof(F3)));
-    CC_CK(hipMemcpyAsync(d, src[k], n * sizeof(F3), hipMemcpyHostToDevice, s));
-    d_in[k] = d;
-  }
+  for (int k = 0; k < 3; ++k)
+    if (src[k]) ST_CK("connected_components", st_stage(pool, s, o.mem, src[k], n, &d_in[k]));
   uint32_t* parent = nullptr;
-  CC_CK(pool.bytes(&parent, n * sizeof(uint32_t)));
+  ST_CK("connected_components", pool.bytes(&parent, n * sizeof(uint32_t)));
   hipLaunchKernelGGL(k_cc_init, dim3(cc_blocks(n)), dim3(CC_THREADS), 0, s, parent, n);
   if (cl.radius_sq > 0.0f) {
     F3* clean = nullptr;
     unsigned int *d_fin = nullptr, n_finite = 0;
-    CC_CK(pool.bytes(&clean, n * sizeof(F3)));
-    CC_CK(pool.bytes(&d_fin, sizeof(unsigned int)));
-    CC_CK(hipMemsetAsync(d_fin, 0, sizeof(unsigned int), s));
+    ST_CK("connected_components", pool.bytes(&clean, n * sizeof(F3)));
+    ST_CK("connected_components", pool.bytes(&d_fin, sizeof(unsigned int)));
+    ST_CK("connected_components", hipMemsetAsync(d_fin, 0, sizeof(unsigned int), s));
     hipLaunchKernelGGL(k_cc_clean, dim3(cc_blocks(n)), dim3(CC_THREADS), 0, s, d_in[0], n, clean, d_fin);
-    CC_CK(hipMemcpyAsync(&n_finite, d_fin, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
-    CC_CK(hipStreamSynchronize(s));
+    ST_CK("connected_components", hipMemcpyAsync(&n_finite, d_fin, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+    ST_CK("connected_components", hipStreamSynchronize(s));
     if (n_finite > 1) {      // (otherwise nobody has a neighbour)
       double mean[3];
-      CC_CK(build_grid(reinterpret_cast<const float*>(clean), nullptr, (uint32_t)n, s, &grid, mean, 2.0));
+      ST_CK("connected_components", build_grid(reinterpret_cast<const float*>(clean), nullptr, (uint32_t)n, s, &grid, mean, 2.0));
       hipLaunchKernelGGL(k_cc_hook, dim3((unsigned)((n + CC_THREADS - 1) / CC_THREADS)), dim3(CC_THREADS), 0, s, grid.grid, cl, d_in[1], d_in[2], parent);
-      CC_CK(hipGetLastError());
+      ST_CK("connected_components", hipGetLastError());
     }
   }
   return cc_finish(o, pool, s, parent);
@@ -399,7 +382,8 @@ int cc_run_fused(int device, const float* xyz, const float* nrm, const float* rg
 int cc_run_lists(int device, const uint64_t* offsets, const uint32_t* idx, const unsigned char* keep, size_t n_entries, int skip_first, const CcOut& o) {
   DevPool pool;
   StreamGuard st;
-  if (int rc = cc_open(device, st)) return rc;
+  if (const int open = st_open("connected_components", device)) return open;
+  ST_CK("connected_components", st.create());
   hipStream_t s = st.s;
   const size_t n = o.n;
   const unsigned long long* d_off = reinterpret_cast<const unsigned long long*>(offsets);
@@ -407,26 +391,26 @@ int cc_run_lists(int device, const uint64_t* offsets, const uint32_t* idx, const
   const unsigned char* d_keep = keep;
   if (o.mem == CILHIP_MEM_HOST) {
     unsigned long long* a = nullptr; uint32_t* b = nullptr; unsigned char* c = nullptr;
-    CC_CK(pool.bytes(&a, (n + 1) * sizeof(unsigned long long)));
-    CC_CK(hipMemcpyAsync(a, offsets, (n + 1) * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
-    CC_CK(pool.bytes(&b, n_entries * sizeof(uint32_t)));
-    if (n_entries) CC_CK(hipMemcpyAsync(b, idx, n_entries * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    ST_CK("connected_components", pool.bytes(&a, (n + 1) * sizeof(unsigned long long)));
+    ST_CK("connected_components", hipMemcpyAsync(a, offsets, (n + 1) * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+    ST_CK("connected_components", pool.bytes(&b, n_entries * sizeof(uint32_t)));
+    if (n_entries) ST_CK("connected_components", hipMemcpyAsync(b, idx, n_entries * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     if (keep) {
-      CC_CK(pool.bytes(&c, n_entries));
-      if (n_entries) CC_CK(hipMemcpyAsync(c, keep, n_entries, hipMemcpyHostToDevice, s));
+      ST_CK("connected_components", pool.bytes(&c, n_entries));
+      if (n_entries) ST_CK("connected_components", hipMemcpyAsync(c, keep, n_entries, hipMemcpyHostToDevice, s));
     }
     d_off = a; d_idx = b; d_keep = c;
   }
   uint32_t* parent = nullptr;
-  CC_CK(pool.bytes(&parent, n * sizeof(uint32_t)));
+  ST_CK("connected_components", pool.bytes(&parent, n * sizeof(uint32_t)));
   hipLaunchKernelGGL(k_cc_init, dim3(cc_blocks(n)), dim3(CC_THREADS), 0, s, parent, n);
   hipLaunchKernelGGL(k_cc_hook_lists, dim3((unsigned)((n + CC_THREADS - 1) / CC_THREADS)), dim3(CC_THREADS), 0, s, d_off, d_idx, d_keep, (unsigned long long)n_entries, (uint32_t)n,
                      skip_first ? 1u : 0u, parent);
-  CC_CK(hipGetLastError());
+  ST_CK("connected_components", hipGetLastError());
   return cc_finish(o, pool, s, parent);
 }
 
-int cc_refuse(const char* why) { set_stateless_error(std::string("connected_components: ") + why); return (int)CILHIP_ERR_INVALID; }
+int cc_refuse(const char* why) { return st_fail(CILHIP_ERR_INVALID, "connected_components", why); }
 
 // the argument rules both entries share; they hold on a machine without a device too.  0: go on, 1: answered (n == 0), < 0: refused
 int cc_check_common(size_t n, int mem, const uint32_t* seeds, size_t n_seeds, uint32_t* labels, size_t* n_segments) {
@@ -461,7 +445,7 @@ extern "C" int cilhip_connected_components3f(int device, const float* xyz, const
   if (params->use_normals && !normals_or_null) return cc_refuse("a normals clause without the normals array");
   if (params->use_colors && !rgb_or_null) return cc_refuse("a colours clause without the colours array");
   if (n && !xyz) return cc_refuse("points is null");
-  set_stateless_error("");
+  st_clear();
   if (n == 0) {      // (without touching a device)
     *n_segments_out = 0;
     if (offsets_out_or_null && mem == CILHIP_MEM_HOST) offsets_out_or_null[0] = 0;
@@ -477,8 +461,7 @@ extern "C" int cilhip_connected_components3f(int device, const float* xyz, const
   try {
     return cc_run_fused(device, xyz, normals_or_null, rgb_or_null, cl, o);
   } catch (...) {      // (out of host memory: never across the C boundary)
-    set_stateless_error("connected_components: out of host memory");
-    return CILHIP_ERR_HIP;
+    return st_fail(CILHIP_ERR_HIP, "connected_components", "out of host memory");
   }
 }
 
@@ -490,10 +473,9 @@ extern "C" int cilhip_connected_components_lists(int device, size_t n, const uin
   if (n && !offsets) return cc_refuse("offsets is null");
   if (n_entries && !idx) return cc_refuse("idx is null");
   if (seeds_or_null && !symmetric) {
-    set_stateless_error("connected_components: a seed list over directed lists (the reference's result then depends on its traversal order): pass symmetric lists or no seeds");
-    return CILHIP_ERR_UNSUPPORTED;
+    return st_fail(CILHIP_ERR_UNSUPPORTED, "connected_components", "a seed list over directed lists (the reference's result then depends on its traversal order): pass symmetric lists or no seeds");
   }
-  set_stateless_error("");
+  st_clear();
   if (n == 0) {
     *n_segments_out = 0;
     if (offsets_out_or_null && mem == CILHIP_MEM_HOST) offsets_out_or_null[0] = 0;
@@ -504,7 +486,6 @@ extern "C" int cilhip_connected_components_lists(int device, size_t n, const uin
   try {
     return cc_run_lists(device, offsets, idx, keep_or_null, n_entries, skip_first, o);
   } catch (...) {
-    set_stateless_error("connected_components: out of host memory");
-    return CILHIP_ERR_HIP;
+    return st_fail(CILHIP_ERR_HIP, "connected_components", "out of host memory");
   }
 }

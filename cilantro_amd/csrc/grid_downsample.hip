@@ -35,12 +35,11 @@
 
 #include "../../include/cilantro_hip/c_api.h"
 #include "internal.hpp"
+#include "stateless.hpp"
 
 namespace cilhip {
 
 namespace {
-
-thread_local std::string g_gd_err;      // what the last stateless call of this thread refused (cilhip_last_error(NULL))
 
 constexpr int GD_CELL_LIMIT = 1 << 20;       // accepted cells: [-2^20, 2^20) per axis
 constexpr uint32_t GD_WAVE_MIN = 64;         // bins with MORE members than this are folded by a whole wave
@@ -281,8 +280,6 @@ unsigned gd_bits(int range) {      // bits that hold 0 .. range
   return b;
 }
 
-#define GD_CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { g_gd_err = std::string("grid_downsample: ") + #x + ": " + hipGetErrorString(e_); return CILHIP_ERR_HIP; } } while (0)
-
 struct GdCall {
   const float *xyz, *nrm, *rgb;
   size_t n;
@@ -301,15 +298,15 @@ int gd_sort_and_fold(const GdCall& c, DevPool& pool, hipStream_t s, const F3* d_
   const size_t n = c.n;
   KeyT *k_in = nullptr, *k_out = nullptr;
   uint32_t *v_in = nullptr, *v_out = nullptr;
-  GD_CK(pool.bytes(&k_in, n * sizeof(KeyT))); GD_CK(pool.bytes(&k_out, n * sizeof(KeyT)));
-  GD_CK(pool.bytes(&v_in, (n + 1) * sizeof(uint32_t))); GD_CK(pool.bytes(&v_out, n * sizeof(uint32_t)));
+  ST_CK("grid_downsample", pool.bytes(&k_in, n * sizeof(KeyT))); ST_CK("grid_downsample", pool.bytes(&k_out, n * sizeof(KeyT)));
+  ST_CK("grid_downsample", pool.bytes(&v_in, (n + 1) * sizeof(uint32_t))); ST_CK("grid_downsample", pool.bytes(&v_out, n * sizeof(uint32_t)));
   hipLaunchKernelGGL((k_gd_keys<KeyT>), dim3(gd_blocks(n)), dim3(256), 0, s, d_xyz, n, pk, k_in, v_in);
   {
     size_t tmp_bytes = 0;
     void* tmp = nullptr;
-    GD_CK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, k_in, k_out, v_in, v_out, n, 0u, end_bit, s));
-    GD_CK(pool.bytes(&tmp, tmp_bytes));
-    GD_CK(rocprim::radix_sort_pairs(tmp, tmp_bytes, k_in, k_out, v_in, v_out, n, 0u, end_bit, s));
+    ST_CK("grid_downsample", rocprim::radix_sort_pairs(nullptr, tmp_bytes, k_in, k_out, v_in, v_out, n, 0u, end_bit, s));
+    ST_CK("grid_downsample", pool.bytes(&tmp, tmp_bytes));
+    ST_CK("grid_downsample", rocprim::radix_sort_pairs(tmp, tmp_bytes, k_in, k_out, v_in, v_out, n, 0u, end_bit, s));
   }
   // the first m sorted positions are the points that have a bin
   uint32_t* bin_of = reinterpret_cast<uint32_t*>(k_in);      // (the unsorted keys are done with)
@@ -318,61 +315,61 @@ int gd_sort_and_fold(const GdCall& c, DevPool& pool, hipStream_t s, const F3* d_
   size_t scan_bytes = 0;
   {
     size_t b1 = 0, b2 = 0;
-    GD_CK(rocprim::inclusive_scan(nullptr, b1, bin_of, bin_of, m, rocprim::plus<uint32_t>(), s));
-    GD_CK(rocprim::exclusive_scan(nullptr, b2, bin_of, bin_of, 0u, n + 1, rocprim::plus<uint32_t>(), s));
+    ST_CK("grid_downsample", rocprim::inclusive_scan(nullptr, b1, bin_of, bin_of, m, rocprim::plus<uint32_t>(), s));
+    ST_CK("grid_downsample", rocprim::exclusive_scan(nullptr, b2, bin_of, bin_of, 0u, n + 1, rocprim::plus<uint32_t>(), s));
     scan_bytes = std::max(b1, b2);
-    GD_CK(pool.bytes(&scan_tmp, scan_bytes));
+    ST_CK("grid_downsample", pool.bytes(&scan_tmp, scan_bytes));
   }
-  GD_CK(rocprim::inclusive_scan(scan_tmp, scan_bytes, bin_of, bin_of, m, rocprim::plus<uint32_t>(), s));
+  ST_CK("grid_downsample", rocprim::inclusive_scan(scan_tmp, scan_bytes, bin_of, bin_of, m, rocprim::plus<uint32_t>(), s));
   uint32_t nbins = 0;
-  GD_CK(hipMemcpyAsync(&nbins, bin_of + (m - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  GD_CK(hipStreamSynchronize(s));
+  ST_CK("grid_downsample", hipMemcpyAsync(&nbins, bin_of + (m - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  ST_CK("grid_downsample", hipStreamSynchronize(s));
   uint32_t *start = nullptr, *slot = nullptr;
-  GD_CK(pool.bytes(&start, ((size_t)nbins + 1) * sizeof(uint32_t)));
-  GD_CK(pool.bytes(&slot, ((size_t)nbins + 1) * sizeof(uint32_t)));
+  ST_CK("grid_downsample", pool.bytes(&start, ((size_t)nbins + 1) * sizeof(uint32_t)));
+  ST_CK("grid_downsample", pool.bytes(&slot, ((size_t)nbins + 1) * sizeof(uint32_t)));
   hipLaunchKernelGGL(k_gd_starts, dim3(gd_blocks(m)), dim3(256), 0, s, (const uint32_t*)bin_of, m, nbins, start);
   const uint32_t min_pts = (uint32_t)std::min<size_t>(c.min_pts, 0xFFFFFFFFull);      // (no bin has 2^32 members: anything above refuses them all)
   uint32_t rows = 0;
   if (c.bin_order == 1) {
     hipLaunchKernelGGL(k_gd_keep, dim3(gd_blocks((size_t)nbins + 1)), dim3(256), 0, s, (const uint32_t*)start, nbins, min_pts, slot);
-    GD_CK(rocprim::exclusive_scan(scan_tmp, scan_bytes, slot, slot, 0u, (size_t)nbins + 1, rocprim::plus<uint32_t>(), s));
-    GD_CK(hipMemcpyAsync(&rows, slot + nbins, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    ST_CK("grid_downsample", rocprim::exclusive_scan(scan_tmp, scan_bytes, slot, slot, 0u, (size_t)nbins + 1, rocprim::plus<uint32_t>(), s));
+    ST_CK("grid_downsample", hipMemcpyAsync(&rows, slot + nbins, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   } else {
     uint32_t* mark = v_in;      // (the unsorted indices are done with; n + 1 entries)
-    GD_CK(hipMemsetAsync(mark, 0, (n + 1) * sizeof(uint32_t), s));
+    ST_CK("grid_downsample", hipMemsetAsync(mark, 0, (n + 1) * sizeof(uint32_t), s));
     hipLaunchKernelGGL(k_gd_mark, dim3(gd_blocks(nbins)), dim3(256), 0, s, (const uint32_t*)start, (const uint32_t*)v_out, nbins, min_pts, mark);
-    GD_CK(rocprim::exclusive_scan(scan_tmp, scan_bytes, mark, mark, 0u, n + 1, rocprim::plus<uint32_t>(), s));
+    ST_CK("grid_downsample", rocprim::exclusive_scan(scan_tmp, scan_bytes, mark, mark, 0u, n + 1, rocprim::plus<uint32_t>(), s));
     hipLaunchKernelGGL(k_gd_slots, dim3(gd_blocks(nbins)), dim3(256), 0, s, (const uint32_t*)start, (const uint32_t*)v_out, nbins, (const uint32_t*)mark, slot);
-    GD_CK(hipMemcpyAsync(&rows, mark + n, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    ST_CK("grid_downsample", hipMemcpyAsync(&rows, mark + n, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   }
-  GD_CK(hipStreamSynchronize(s));
+  ST_CK("grid_downsample", hipStreamSynchronize(s));
   *c.n_out = rows;
   const bool want = c.xyz_out || c.nrm_out || c.rgb_out || c.cnt_out;
   if (!want && c.capacity == 0) return CILHIP_OK;      // the counting call
-  if (rows > c.capacity) { g_gd_err = "grid_downsample: capacity is smaller than the number of bins (*n_out has it; capacity = n always suffices)"; return CILHIP_ERR_INVALID; }
+  if (rows > c.capacity) return st_fail(CILHIP_ERR_INVALID, "grid_downsample", "capacity is smaller than the number of bins (*n_out has it; capacity = n always suffices)");
   if (rows == 0 || !want) return CILHIP_OK;
 
   const bool has_n = d_nrm && c.nrm_out, has_c = d_rgb && c.rgb_out;
   F3 *gp = nullptr, *gn = nullptr, *gc = nullptr;
-  GD_CK(pool.bytes(&gp, m * sizeof(F3)));
-  if (has_n) GD_CK(pool.bytes(&gn, m * sizeof(F3)));
-  if (has_c) GD_CK(pool.bytes(&gc, m * sizeof(F3)));
+  ST_CK("grid_downsample", pool.bytes(&gp, m * sizeof(F3)));
+  if (has_n) ST_CK("grid_downsample", pool.bytes(&gn, m * sizeof(F3)));
+  if (has_c) ST_CK("grid_downsample", pool.bytes(&gc, m * sizeof(F3)));
   hipLaunchKernelGGL(k_gd_gather, dim3(gd_blocks(m)), dim3(256), 0, s, d_xyz, has_n ? d_nrm : (const F3*)nullptr, has_c ? d_rgb : (const F3*)nullptr,
                      (const uint32_t*)v_out, m, gp, gn, gc);
   GdFold a{};
   a.start = start; a.slot = slot; a.gp = gp; a.gn = gn; a.gc = gc; a.nbins = nbins; a.min_pts = min_pts;
   uint32_t* n_long = nullptr;
   // a bin that goes to the wave form has more than GD_WAVE_MIN members: there are fewer than m / GD_WAVE_MIN of them
-  GD_CK(pool.bytes(&a.long_list, (m / GD_WAVE_MIN + 1) * sizeof(uint32_t)));
-  GD_CK(pool.bytes(&n_long, sizeof(uint32_t)));
-  GD_CK(hipMemsetAsync(n_long, 0, sizeof(uint32_t), s));
+  ST_CK("grid_downsample", pool.bytes(&a.long_list, (m / GD_WAVE_MIN + 1) * sizeof(uint32_t)));
+  ST_CK("grid_downsample", pool.bytes(&n_long, sizeof(uint32_t)));
+  ST_CK("grid_downsample", hipMemsetAsync(n_long, 0, sizeof(uint32_t), s));
   a.n_long = n_long;
   const bool host = c.mem == CILHIP_MEM_HOST;
   if (host) {
-    if (c.xyz_out) GD_CK(pool.bytes(&a.out_p, (size_t)rows * sizeof(F3)));
-    if (has_n) GD_CK(pool.bytes(&a.out_n, (size_t)rows * sizeof(F3)));
-    if (has_c) GD_CK(pool.bytes(&a.out_c, (size_t)rows * sizeof(F3)));
-    if (c.cnt_out) GD_CK(pool.bytes(&a.out_cnt, (size_t)rows * sizeof(uint32_t)));
+    if (c.xyz_out) ST_CK("grid_downsample", pool.bytes(&a.out_p, (size_t)rows * sizeof(F3)));
+    if (has_n) ST_CK("grid_downsample", pool.bytes(&a.out_n, (size_t)rows * sizeof(F3)));
+    if (has_c) ST_CK("grid_downsample", pool.bytes(&a.out_c, (size_t)rows * sizeof(F3)));
+    if (c.cnt_out) ST_CK("grid_downsample", pool.bytes(&a.out_cnt, (size_t)rows * sizeof(uint32_t)));
   } else {
     a.out_p = reinterpret_cast<F3*>(c.xyz_out);
     a.out_n = has_n ? reinterpret_cast<F3*>(c.nrm_out) : nullptr;
@@ -393,56 +390,39 @@ int gd_sort_and_fold(const GdCall& c, DevPool& pool, hipStream_t s, const F3* d_
     hipLaunchKernelGGL((k_gd_fold_lane<false, false>), lane_grid, dim3(256), 0, s, a);
     hipLaunchKernelGGL((k_gd_fold_wave<false, false>), wave_grid, dim3(256), 0, s, a);
   }
-  GD_CK(hipGetLastError());
+  ST_CK("grid_downsample", hipGetLastError());
   if (host) {
-    if (a.out_p) GD_CK(hipMemcpyAsync(c.xyz_out, a.out_p, (size_t)rows * sizeof(F3), hipMemcpyDeviceToHost, s));
-    if (a.out_n) GD_CK(hipMemcpyAsync(c.nrm_out, a.out_n, (size_t)rows * sizeof(F3), hipMemcpyDeviceToHost, s));
-    if (a.out_c) GD_CK(hipMemcpyAsync(c.rgb_out, a.out_c, (size_t)rows * sizeof(F3), hipMemcpyDeviceToHost, s));
-    if (a.out_cnt) GD_CK(hipMemcpyAsync(c.cnt_out, a.out_cnt, (size_t)rows * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (a.out_p) ST_CK("grid_downsample", hipMemcpyAsync(c.xyz_out, a.out_p, (size_t)rows * sizeof(F3), hipMemcpyDeviceToHost, s));
+    if (a.out_n) ST_CK("grid_downsample", hipMemcpyAsync(c.nrm_out, a.out_n, (size_t)rows * sizeof(F3), hipMemcpyDeviceToHost, s));
+    if (a.out_c) ST_CK("grid_downsample", hipMemcpyAsync(c.rgb_out, a.out_c, (size_t)rows * sizeof(F3), hipMemcpyDeviceToHost, s));
+    if (a.out_cnt) ST_CK("grid_downsample", hipMemcpyAsync(c.cnt_out, a.out_cnt, (size_t)rows * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   }
-  GD_CK(hipStreamSynchronize(s));
+  ST_CK("grid_downsample", hipStreamSynchronize(s));
   return CILHIP_OK;
 }
 
 int gd_run(const GdCall& c, int device) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-    g_gd_err = "grid_downsample: no such HIP device (the downsampler runs on the device: there is no CPU path)";
-    return CILHIP_ERR_NO_DEVICE;
-  }
-  GD_CK(hipSetDevice(device));
+  if (const int open = st_open("grid_downsample", device)) return open;
   DevPool pool;
   StreamGuard st;      // (declared after the pool: the stream is drained and destroyed before anything is freed)
-  GD_CK(st.create());
+  ST_CK("grid_downsample", st.create());
   hipStream_t s = st.s;
   const size_t n = c.n;
   const F3 *d_xyz = nullptr, *d_nrm = nullptr, *d_rgb = nullptr;
-  if (c.mem == CILHIP_MEM_DEVICE) {
-    d_xyz = reinterpret_cast<const F3*>(c.xyz); d_nrm = reinterpret_cast<const F3*>(c.nrm); d_rgb = reinterpret_cast<const F3*>(c.rgb);
-  } else {
-    const float* src[3] = {c.xyz, c.nrm, c.rgb};
-    const F3** dst[3] = {&d_xyz, &d_nrm, &d_rgb};
-    for (int k = 0; k < 3; ++k) {
-      if (!src[k]) continue;
-      F3* d = nullptr;
-      GD_CK(pool.bytes(&d, n * sizeof(F3)));
-      GD_CK(hipMemcpyAsync(d, src[k], n * sizeof(F3), hipMemcpyHostToDevice, s));
-      *dst[k] = d;
-    }
-  }
+  ST_CK("grid_downsample", st_stage(pool, s, c.mem, c.xyz, n, &d_xyz));
+  if (c.nrm) ST_CK("grid_downsample", st_stage(pool, s, c.mem, c.nrm, n, &d_nrm));
+  if (c.rgb) ST_CK("grid_downsample", st_stage(pool, s, c.mem, c.rgb, n, &d_rgb));
   const float inv = 1.0f / c.bin_size;      // grid_accumulator.hpp:79 (cwiseInverse, f32)
   GdRange h{};
   for (int a = 0; a < 3; ++a) { h.mn[a] = INT_MAX; h.mx[a] = INT_MIN; }
   GdRange* d_range = nullptr;
-  GD_CK(pool.bytes(&d_range, sizeof(GdRange)));
-  GD_CK(hipMemcpyAsync(d_range, &h, sizeof(GdRange), hipMemcpyHostToDevice, s));
+  ST_CK("grid_downsample", pool.bytes(&d_range, sizeof(GdRange)));
+  ST_CK("grid_downsample", hipMemcpyAsync(d_range, &h, sizeof(GdRange), hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_gd_range, dim3(std::min(gd_blocks(n), 2048)), dim3(256), 0, s, d_xyz, n, inv, d_range);
-  GD_CK(hipMemcpyAsync(&h, d_range, sizeof(GdRange), hipMemcpyDeviceToHost, s));
-  GD_CK(hipStreamSynchronize(s));
-  if (h.err) {
-    g_gd_err = "grid_downsample: a finite point lies in a cell outside [-2^20, 2^20) on some axis (three cell indices must fit one 64-bit sort key): use a larger bin_size or move the cloud towards the origin";
-    return CILHIP_ERR_UNSUPPORTED;
-  }
+  ST_CK("grid_downsample", hipMemcpyAsync(&h, d_range, sizeof(GdRange), hipMemcpyDeviceToHost, s));
+  ST_CK("grid_downsample", hipStreamSynchronize(s));
+  if (h.err)
+    return st_fail(CILHIP_ERR_UNSUPPORTED, "grid_downsample", "a finite point lies in a cell outside [-2^20, 2^20) on some axis (three cell indices must fit one 64-bit sort key): use a larger bin_size or move the cloud towards the origin");
   const size_t m = (size_t)h.n_valid;
   if (m == 0) { *c.n_out = 0; return CILHIP_OK; }      // nothing but non-finite points
   const unsigned bx = gd_bits(h.mx[0] - h.mn[0]), by = gd_bits(h.mx[1] - h.mn[1]), bz = gd_bits(h.mx[2] - h.mn[2]);
@@ -456,9 +436,6 @@ int gd_run(const GdCall& c, int device) {
 
 }  // namespace
 
-const char* stateless_last_error() { return g_gd_err.empty() ? "null context" : g_gd_err.c_str(); }
-void set_stateless_error(const std::string& what) { g_gd_err = what; }
-
 }  // namespace cilhip
 
 extern "C" int cilhip_grid_downsample3f(int device, const float* xyz, const float* normals_or_null, const float* rgb_or_null, size_t n, int mem, float bin_size,
@@ -466,20 +443,19 @@ extern "C" int cilhip_grid_downsample3f(int device, const float* xyz, const floa
                                         size_t capacity, size_t* n_out) {
   using namespace cilhip;
   // argument rules first: they hold on a machine without a device too
-  auto refuse = [](const char* why) { g_gd_err = std::string("grid_downsample: ") + why; return (int)CILHIP_ERR_INVALID; };
+  auto refuse = [](const char* why) { return st_fail(CILHIP_ERR_INVALID, "grid_downsample", why); };
   if (!n_out) return refuse("n_out is null");
   if (!(bin_size > 0.0f) || !std::isfinite(bin_size)) return refuse("bin_size must be a finite positive number");
   if ((unsigned long long)n >= (1ull << 32)) return refuse("n must be below 2^32");
   if (mem != CILHIP_MEM_HOST && mem != CILHIP_MEM_DEVICE) return refuse("mem: CILHIP_MEM_HOST or CILHIP_MEM_DEVICE");
   if (bin_order != 0 && bin_order != 1) return refuse("bin_order: 0 = first appearance, 1 = lexicographic");
   if (n && !xyz) return refuse("points is null");
-  g_gd_err.clear();
+  st_clear();
   if (n == 0) { *n_out = 0; return CILHIP_OK; }      // (without touching a device)
   GdCall c{xyz, normals_or_null, rgb_or_null, n, mem, bin_size, min_points_in_bin, bin_order, xyz_out, normals_out, rgb_out, counts_out_or_null, capacity, n_out};
   try {
     return gd_run(c, device);
   } catch (...) {      // (out of host memory: never across the C boundary)
-    g_gd_err = "grid_downsample: out of host memory";
-    return CILHIP_ERR_HIP;
+    return st_fail(CILHIP_ERR_HIP, "grid_downsample", "out of host memory");
   }
 }

@@ -505,10 +505,6 @@ hipError_t sort_source(const float* d_xyz, uint32_t n, const GridDev& g, const f
                        SortWorkspace& ws);
 hipError_t mean3_device(const float* d_xyz, uint32_t n, hipStream_t s, double mean_out[3], float* lo_out = nullptr, float* hi_out = nullptr);
 
-// grid_downsample.hip: what the calling thread's last stateless call refused, for cilhip_last_error(NULL) ("null context" when nothing)
-const char* stateless_last_error();
-void set_stateless_error(const std::string& what);      // (components.hip: the same slot; "" clears it)
-
 // c_api.hip <-> multi.hip
 hipStream_t ctx_stream(const ::cilhip_ctx* c);
 double ctx_wait_us(const ::cilhip_ctx* c);      // microseconds this context's host loop has spent waiting for published loop state

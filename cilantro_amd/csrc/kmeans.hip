@@ -15,6 +15,7 @@
 // so labels are bit-identical to the reference given identical centroids.
 #include "../../include/cilantro_hip/c_api.h"
 #include "internal.hpp"
+#include "stateless.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -466,46 +467,44 @@ struct cilhip_kmeans_shard {
     float4 pad4; pad4.x = pad4.y = pad4.z = INFINITY; { const uint32_t none = 0xFFFFFFFFu; std::memcpy(&pad4.w, &none, 4); }
     cs_host.assign(kpad + 8, pad4);
     cpad.assign(3 * kpad, INFINITY);                              // device copy padded with +inf centroids
-#define KS_CK(x) do { if ((x) != hipSuccess) return CILHIP_ERR_HIP; } while (0)
-    KS_CK(hipSetDevice(device));
-    KS_CK(s.create());
+    ST_CK("kmeans", s.create());      // (the caller has opened `dev`: st_open)
     if (mem == CILHIP_MEM_DEVICE) {
       d_xyz = xyz;
     } else {
-      KS_CK(own_xyz.alloc(3 * n));
+      ST_CK("kmeans", own_xyz.alloc(3 * n));
       d_xyz = own_xyz;
-      if (n) KS_CK(hipMemcpyAsync(own_xyz, xyz, 3 * n * sizeof(float), hipMemcpyHostToDevice, s));
+      if (n) ST_CK("kmeans", hipMemcpyAsync(own_xyz, xyz, 3 * n * sizeof(float), hipMemcpyHostToDevice, s));
     }
-    KS_CK(d_c.alloc(3 * kpad));
-    KS_CK(d_lab.alloc(n ? n : 1));
-    KS_CK(d_sums.alloc(kpad * 4));
-    KS_CK(d_changed.alloc(2));      // [0] labels changed, [1] (kd branch) tied points met without tables
-    KS_CK(d_nonfinite.alloc(kpad));
-    KS_CK(hipMemsetAsync(d_nonfinite, 0, kpad * sizeof(unsigned int), s));
-    KS_CK(d_best.alloc(1));
-    KS_CK(hipMemsetAsync(d_lab, 0, (n ? n : 1) * sizeof(uint32_t), s));   // point_to_cluster_index_map_.resize(n): zeros (:80)
+    ST_CK("kmeans", d_c.alloc(3 * kpad));
+    ST_CK("kmeans", d_lab.alloc(n ? n : 1));
+    ST_CK("kmeans", d_sums.alloc(kpad * 4));
+    ST_CK("kmeans", d_changed.alloc(2));      // [0] labels changed, [1] (kd branch) tied points met without tables
+    ST_CK("kmeans", d_nonfinite.alloc(kpad));
+    ST_CK("kmeans", hipMemsetAsync(d_nonfinite, 0, kpad * sizeof(unsigned int), s));
+    ST_CK("kmeans", d_best.alloc(1));
+    ST_CK("kmeans", hipMemsetAsync(d_lab, 0, (n ? n : 1) * sizeof(uint32_t), s));   // point_to_cluster_index_map_.resize(n): zeros (:80)
     return CILHIP_OK;
   }
   // max finite |coordinate| of the shard (f32; 0 for an empty one)
   int maxabs(float* out) {
-    KS_CK(hipSetDevice(device));
+    ST_CK("kmeans", hipSetDevice(device));
     unsigned int hmax = 0;   // max |x| as f32 bits (non-negative floats order like unsigned ints)
-    KS_CK(hipMemsetAsync(d_changed, 0, sizeof(unsigned int), s));
+    ST_CK("kmeans", hipMemsetAsync(d_changed, 0, sizeof(unsigned int), s));
     if (n) hipLaunchKernelGGL(k_maxabs_bits, dim3(1024), dim3(256), 0, s, d_xyz, 3 * n, d_changed);
-    KS_CK(hipMemcpyAsync(&hmax, d_changed, sizeof(hmax), hipMemcpyDeviceToHost, s));
-    KS_CK(hipStreamSynchronize(s));
+    ST_CK("kmeans", hipMemcpyAsync(&hmax, d_changed, sizeof(hmax), hipMemcpyDeviceToHost, s));
+    ST_CK("kmeans", hipStreamSynchronize(s));
     std::memcpy(out, &hmax, sizeof(float));
     return CILHIP_OK;
   }
   // one assignment pass over the shard under `centroids` (kmeans.hpp:95-119 / :86-94): labels updated in place, the shard's exact
   // fixed-point sums {x, y, z, count} per cluster (scale 2^S) and the number of labels that changed
   int assign(const float* centroids, double scale, bool kd_order, bool assign_only, long long* sums_out, unsigned int* changed_out) {
-    KS_CK(hipSetDevice(device));
+    ST_CK("kmeans", hipSetDevice(device));
     std::memcpy(cpad.data(), centroids, 3 * k * sizeof(float));
-    KS_CK(hipMemcpyAsync(d_c, cpad.data(), 3 * kpad * sizeof(float), hipMemcpyHostToDevice, s));
-    KS_CK(hipMemsetAsync(d_changed, 0, sizeof(unsigned int), s));
-    KS_CK(hipMemsetAsync(d_sums, 0, kpad * 4 * sizeof(long long), s));
-    KS_CK(hipMemsetAsync(d_nonfinite, 0, kpad * sizeof(unsigned int), s));      // (a pass that runs again sets the same flags again)
+    ST_CK("kmeans", hipMemcpyAsync(d_c, cpad.data(), 3 * kpad * sizeof(float), hipMemcpyHostToDevice, s));
+    ST_CK("kmeans", hipMemsetAsync(d_changed, 0, sizeof(unsigned int), s));
+    ST_CK("kmeans", hipMemsetAsync(d_sums, 0, kpad * 4 * sizeof(long long), s));
+    ST_CK("kmeans", hipMemsetAsync(d_nonfinite, 0, kpad * sizeof(unsigned int), s));      // (a pass that runs again sets the same flags again)
     if (n) {
       const int nblocks = (int)std::min<size_t>((n / 2 + KM_THREADS - 1) / KM_THREADS + 1, 1024);
       KmArgs a{d_xyz, d_c, (uint32_t)n, (uint32_t)kpad, d_lab, d_sums, d_changed, d_nonfinite, scale, assign_only ? 0 : 1, {nullptr, nullptr, nullptr, 0}, nullptr, nullptr, 0u};
@@ -517,11 +516,11 @@ struct cilhip_kmeans_shard {
       if (kd_order) for (size_t t = 0; t < 3 * k; ++t) finite = finite && std::isfinite(centroids[t]);
       const bool ties_matter = kd_order && cilhip::g_knn_tie_rule != 0 && k > 1 && finite;
       if (ties_matter) {
-        if (!d_lab_prev) KS_CK(d_lab_prev.alloc(n));
-        KS_CK(hipMemcpyAsync(d_lab_prev, d_lab, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-        KS_CK(hipMemsetAsync(d_changed + 1, 0, sizeof(unsigned int), s));
+        if (!d_lab_prev) ST_CK("kmeans", d_lab_prev.alloc(n));
+        ST_CK("kmeans", hipMemcpyAsync(d_lab_prev, d_lab, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+        ST_CK("kmeans", hipMemsetAsync(d_changed + 1, 0, sizeof(unsigned int), s));
         a.tie_count = d_changed + 1;
-        if (!d_tie_list) KS_CK(d_tie_list.alloc(KM_TIE_LIST));
+        if (!d_tie_list) ST_CK("kmeans", d_tie_list.alloc(KM_TIE_LIST));
         a.tie_list = d_tie_list; a.tie_cap = KM_TIE_LIST;
       }
       KmGrid gr{};
@@ -529,9 +528,9 @@ struct cilhip_kmeans_shard {
       const size_t ncell1 = pruned ? (size_t)gr.g * gr.g * gr.g + 1 : 0;
       if (pruned) {
         // the grid of THIS iteration's centroids: sorted list + cell table, 20 KB
-        if (!d_cs || !d_cstart) { KS_CK(d_cs.alloc(kpad + 8)); KS_CK(d_cstart.alloc(16 * 16 * 16 + 1)); }
-        KS_CK(hipMemcpyAsync(d_cs, cs_host.data(), (kpad + 8) * sizeof(float4), hipMemcpyHostToDevice, s));
-        KS_CK(hipMemcpyAsync(d_cstart, cstart_host.data(), ncell1 * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        if (!d_cs || !d_cstart) { ST_CK("kmeans", d_cs.alloc(kpad + 8)); ST_CK("kmeans", d_cstart.alloc(16 * 16 * 16 + 1)); }
+        ST_CK("kmeans", hipMemcpyAsync(d_cs, cs_host.data(), (kpad + 8) * sizeof(float4), hipMemcpyHostToDevice, s));
+        ST_CK("kmeans", hipMemcpyAsync(d_cstart, cstart_host.data(), ncell1 * sizeof(uint32_t), hipMemcpyHostToDevice, s));
       }
       auto pass = [&]() {
         if (pruned) {
@@ -544,15 +543,15 @@ struct cilhip_kmeans_shard {
         else hipLaunchKernelGGL(k_assign_accumulate<false>, dim3(nblocks), dim3(KM_THREADS), assign_only ? 0 : kpad * 4 * sizeof(long long), s, a);
       };
       pass();
-      KS_CK(hipGetLastError());
+      ST_CK("kmeans", hipGetLastError());
       if (ties_matter) {
         unsigned int tied = 0;
-        KS_CK(hipMemcpyAsync(&tied, d_changed + 1, sizeof(tied), hipMemcpyDeviceToHost, s));
-        KS_CK(hipStreamSynchronize(s));
+        ST_CK("kmeans", hipMemcpyAsync(&tied, d_changed + 1, sizeof(tied), hipMemcpyDeviceToHost, s));
+        ST_CK("kmeans", hipStreamSynchronize(s));
         if (tied != 0) {
-          if (!d_tleaf || !d_tls) { KS_CK(d_tleaf.alloc(2 * kpad)); KS_CK(d_tls.alloc(kpad)); }
+          if (!d_tleaf || !d_tls) { ST_CK("kmeans", d_tleaf.alloc(2 * kpad)); ST_CK("kmeans", d_tls.alloc(kpad)); }
           size_t nn = 0; int depth = 0;
-          KS_CK(cilhip::tie_order_build_device(d_c, nullptr, (uint32_t)k, s, d_tleaf, d_tleaf + kpad, &d_tnodes, &nn, &depth));
+          ST_CK("kmeans", cilhip::tie_order_build_device(d_c, nullptr, (uint32_t)k, s, d_tleaf, d_tleaf + kpad, &d_tnodes, &nn, &depth));
           hipLaunchKernelGGL(k_zip_tables, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, s, (const uint32_t*)d_tleaf, (const uint32_t*)(d_tleaf + kpad), d_tls, (uint32_t)k);
           a.tie.leaf_slot = d_tls; a.tie.nodes = d_tnodes; a.tie.mode = 1; a.tie_count = nullptr;
           ++tie_table_builds;
@@ -560,32 +559,32 @@ struct cilhip_kmeans_shard {
             // the pruned pass listed its tied points: only they are looked at again
             hipLaunchKernelGGL(k_fix_ties, dim3((tied + 255u) / 256u), dim3(256), 0, s, a, (const uint2*)d_tie_list, (uint32_t)tied);
           } else {
-            KS_CK(hipMemcpyAsync(d_lab, d_lab_prev, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-            KS_CK(hipMemsetAsync(d_changed, 0, sizeof(unsigned int), s));
-            KS_CK(hipMemsetAsync(d_sums, 0, kpad * 4 * sizeof(long long), s));
+            ST_CK("kmeans", hipMemcpyAsync(d_lab, d_lab_prev, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+            ST_CK("kmeans", hipMemsetAsync(d_changed, 0, sizeof(unsigned int), s));
+            ST_CK("kmeans", hipMemsetAsync(d_sums, 0, kpad * 4 * sizeof(long long), s));
             pass();
           }
-          KS_CK(hipGetLastError());
+          ST_CK("kmeans", hipGetLastError());
         }
       }
     }
     if (assign_only) return CILHIP_OK;
     unsigned int changed = 0;
-    KS_CK(hipMemcpyAsync(&changed, d_changed, sizeof(changed), hipMemcpyDeviceToHost, s));
-    KS_CK(hipMemcpyAsync(sums_out, d_sums, k * 4 * sizeof(long long), hipMemcpyDeviceToHost, s));
-    KS_CK(hipStreamSynchronize(s));
+    ST_CK("kmeans", hipMemcpyAsync(&changed, d_changed, sizeof(changed), hipMemcpyDeviceToHost, s));
+    ST_CK("kmeans", hipMemcpyAsync(sums_out, d_sums, k * 4 * sizeof(long long), hipMemcpyDeviceToHost, s));
+    ST_CK("kmeans", hipStreamSynchronize(s));
     *changed_out = changed;
     return CILHIP_OK;
   }
   // farthest member of `cluster` from `center` among the shard's points: key = (bits(d) << 32) | (0xFFFFFFFF - GLOBAL index), 0 = no
   // member; the maximum over shards names the point the reference's sweep keeps (ties: lowest index)
   int farthest(uint32_t cluster, const float center[3], unsigned long long* key_out) {
-    KS_CK(hipSetDevice(device));
-    KS_CK(hipMemsetAsync(d_best, 0, sizeof(unsigned long long), s));
+    ST_CK("kmeans", hipSetDevice(device));
+    ST_CK("kmeans", hipMemsetAsync(d_best, 0, sizeof(unsigned long long), s));
     if (n) hipLaunchKernelGGL(k_farthest_member, dim3(1024), dim3(256), 0, s, d_xyz, d_lab, (uint32_t)n, cluster, center[0], center[1], center[2], d_best);
     unsigned long long best = 0;
-    KS_CK(hipMemcpyAsync(&best, d_best, sizeof(best), hipMemcpyDeviceToHost, s));
-    KS_CK(hipStreamSynchronize(s));
+    ST_CK("kmeans", hipMemcpyAsync(&best, d_best, sizeof(best), hipMemcpyDeviceToHost, s));
+    ST_CK("kmeans", hipStreamSynchronize(s));
     if (best) {      // local -> global index
       const uint32_t li = 0xFFFFFFFFu - (uint32_t)(best & 0xFFFFFFFFull);
       best = (best & 0xFFFFFFFF00000000ull) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)(index_offset + li));
@@ -596,26 +595,25 @@ struct cilhip_kmeans_shard {
   // the point with LOCAL index li moves to `cluster`; its coordinates
   int move_point(uint32_t li, uint32_t cluster, float p[3]) {
     if (li >= n) return CILHIP_ERR_INVALID;
-    KS_CK(hipSetDevice(device));
+    ST_CK("kmeans", hipSetDevice(device));
     hipLaunchKernelGGL(k_set_label, dim3(1), dim3(64), 0, s, d_lab, li, cluster);
-    KS_CK(hipMemcpyAsync(p, d_xyz + 3 * (size_t)li, 3 * sizeof(float), hipMemcpyDeviceToHost, s));
-    KS_CK(hipStreamSynchronize(s));
+    ST_CK("kmeans", hipMemcpyAsync(p, d_xyz + 3 * (size_t)li, 3 * sizeof(float), hipMemcpyDeviceToHost, s));
+    ST_CK("kmeans", hipStreamSynchronize(s));
     return CILHIP_OK;
   }
   // per cluster, the non-finite coordinates the last assign() met among its members (KM_NF_* << 3d)
   int nonfinite(uint32_t* out) {
-    KS_CK(hipSetDevice(device));
-    KS_CK(hipMemcpyAsync(out, d_nonfinite, k * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
-    KS_CK(hipStreamSynchronize(s));
+    ST_CK("kmeans", hipSetDevice(device));
+    ST_CK("kmeans", hipMemcpyAsync(out, d_nonfinite, k * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+    ST_CK("kmeans", hipStreamSynchronize(s));
     return CILHIP_OK;
   }
   int labels(uint32_t* out) {
-    KS_CK(hipSetDevice(device));
-    if (n) KS_CK(hipMemcpyAsync(out, d_lab, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    KS_CK(hipStreamSynchronize(s));
+    ST_CK("kmeans", hipSetDevice(device));
+    if (n) ST_CK("kmeans", hipMemcpyAsync(out, d_lab, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    ST_CK("kmeans", hipStreamSynchronize(s));
     return CILHIP_OK;
   }
-#undef KS_CK
 };
 
 namespace {
@@ -632,11 +630,10 @@ int kmeans_scale_exponent(double maxabs, size_t n) {
 
 int kmeans_impl(int device, const float* xyz, size_t n, int mem, float* centroids, size_t k, size_t max_iter, float tol,
                 uint32_t* labels_out, size_t* iterations_out, bool assign_only, bool kd_order = false) {
-  if (!xyz || !centroids || k == 0 || n == 0 || n >= 0xFFFFFFF0ull) return CILHIP_ERR_INVALID;
-  if (k > KM_MAX_K) return CILHIP_ERR_UNSUPPORTED;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return CILHIP_ERR_NO_DEVICE;
-  if (device < 0 || device >= ndev) return CILHIP_ERR_INVALID;
+  if (!xyz || !centroids || k == 0 || n == 0 || n >= 0xFFFFFFF0ull) return cilhip::st_fail(CILHIP_ERR_INVALID, "kmeans", cilhip::kBadArguments);
+  if (k > KM_MAX_K) return cilhip::st_fail(CILHIP_ERR_UNSUPPORTED, "kmeans", "k is above 2048");
+  cilhip::st_clear();
+  if (const int open = cilhip::st_open("kmeans", device, CILHIP_ERR_INVALID)) return open;
   std::vector<long long> hs(k * 4);
   std::vector<float> c_old(3 * k);
   std::vector<uint32_t> nf(k);
@@ -704,14 +701,13 @@ extern "C" {
 int cilhip_kmeans_set_pruning(int on) { g_kmeans_prune = on != 0; return CILHIP_OK; }
 
 int cilhip_kmeans_shard_create(int device, const float* xyz, size_t n, int mem, size_t k, uint64_t index_offset, cilhip_kmeans_shard** out) {
-  if (!out || (!xyz && n) || k == 0 || n >= 0xFFFFFFF0ull) return CILHIP_ERR_INVALID;
+  if (!out || (!xyz && n) || k == 0 || n >= 0xFFFFFFF0ull) return cilhip::st_fail(CILHIP_ERR_INVALID, "kmeans", cilhip::kBadArguments);
   *out = nullptr;
-  if (k > KM_MAX_K) return CILHIP_ERR_UNSUPPORTED;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return CILHIP_ERR_NO_DEVICE;
-  if (device < 0 || device >= ndev) return CILHIP_ERR_INVALID;
+  if (k > KM_MAX_K) return cilhip::st_fail(CILHIP_ERR_UNSUPPORTED, "kmeans", "k is above 2048");
+  cilhip::st_clear();
+  if (const int open = cilhip::st_open("kmeans", device, CILHIP_ERR_INVALID)) return open;
   cilhip_kmeans_shard* h = new (std::nothrow) cilhip_kmeans_shard();
-  if (!h) return CILHIP_ERR_HIP;
+  if (!h) return cilhip::st_fail(CILHIP_ERR_HIP, "kmeans", "out of host memory");
   int rc = CILHIP_ERR_HIP;
   try { rc = h->init(device, xyz, n, mem, k, index_offset); } catch (...) { rc = CILHIP_ERR_HIP; }
   if (rc != CILHIP_OK) { delete h; return rc; }

@@ -21,6 +21,7 @@
 // Queries are processed in target-grid cell order (neighbouring lanes scan the same cells).
 #include "../../include/cilantro_hip/c_api.h"
 #include "internal.hpp"
+#include "stateless.hpp"
 
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_scan.hpp>
@@ -371,14 +372,13 @@ __global__ __launch_bounds__(KNN_THREADS) void k_radius_pca(KnnArgs a) {
 }
 
 
-#define KN_CK(x) do { if ((x) != hipSuccess) return CILHIP_ERR_HIP; } while (0)
-
 int knn_impl(int device, const float* ref_xyz, size_t n_ref, const float* query_xyz, size_t n_query, int mem, size_t k, float max_sq_dist,
              uint32_t* idx_out, float* d2_out, uint32_t* cnt_out, bool do_pca, const float* view_point, float* normals_out,
              float* curvature_out) {
   const bool radius_only = do_pca && k == 0;   // unbounded neighbourhood: moments only, no list
-  if ((!ref_xyz && n_ref) || (k == 0 && !radius_only) || k > (size_t)KNN_MAX_K || n_ref > 0xFFFFFFF0ull || n_query > 0xFFFFFFF0ull) return CILHIP_ERR_INVALID;
-  if (radius_only && !std::isfinite(max_sq_dist)) return CILHIP_ERR_INVALID;
+  if ((!ref_xyz && n_ref) || (k == 0 && !radius_only) || k > (size_t)KNN_MAX_K || n_ref > 0xFFFFFFF0ull || n_query > 0xFFFFFFF0ull) return st_fail(CILHIP_ERR_INVALID, "knn", kBadArguments);
+  if (radius_only && !std::isfinite(max_sq_dist)) return st_fail(CILHIP_ERR_INVALID, "knn", "radius_sq must be finite");
+  st_clear();
   if (!(max_sq_dist > 0.0f)) max_sq_dist = 0.0f;   // NaN / negative radius: nothing is inside
   const bool self = query_xyz == nullptr;
   if (self) n_query = n_ref;
@@ -396,52 +396,39 @@ int knn_impl(int device, const float* ref_xyz, size_t n_ref, const float* query_
   SortWorkspace sort_ws;
   StreamGuard s;      // (declared last: drained and destroyed before anything is freed)
   {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CILHIP_ERR_NO_DEVICE;
-    KN_CK(hipSetDevice(device));
+    if (const int open = st_open("knn", device)) return open;
     if (n_query == 0) return CILHIP_OK;
-    KN_CK(s.create());
-    if (mem == CILHIP_MEM_DEVICE) {
-      d_ref = const_cast<float*>(ref_xyz);
-      d_q = self ? d_ref : const_cast<float*>(query_xyz);
-    } else {
-      if (n_ref) {
-        KN_CK(pool.get(&d_ref, 3 * n_ref));
-        KN_CK(hipMemcpyAsync(d_ref, ref_xyz, 3 * n_ref * sizeof(float), hipMemcpyHostToDevice, s));
-      }
-      if (self) d_q = d_ref;
-      else {
-        KN_CK(pool.get(&d_q, 3 * n_query));
-        KN_CK(hipMemcpyAsync(d_q, query_xyz, 3 * n_query * sizeof(float), hipMemcpyHostToDevice, s));
-      }
-    }
+    ST_CK("knn", s.create());
+    if (n_ref || mem == CILHIP_MEM_DEVICE) ST_CK("knn", st_stage(pool, s, mem, ref_xyz, 3 * n_ref, &d_ref));      // (an empty host cloud: no block)
+    if (self) d_q = d_ref;
+    else ST_CK("knn", st_stage(pool, s, mem, query_xyz, 3 * n_query, &d_q));
     double mean[3];
     // ~k/4 points per cell: the k-th neighbour then normally lies inside the 3x3x3 block of cells
     {
       const hipError_t eg = build_grid(d_ref, nullptr, (uint32_t)n_ref, s, &gr, mean, std::max(1.0, (double)k / 4.0));
-      if (eg == GRID_RANGE_ERROR) { set_stateless_error(std::string("grid: ") + kGridRangeMessage); return CILHIP_ERR_UNSUPPORTED; }
-      KN_CK(eg);
+      if (eg == GRID_RANGE_ERROR) return st_fail(CILHIP_ERR_UNSUPPORTED, "grid", kGridRangeMessage);
+      ST_CK("knn", eg);
     }   // (radius-only: 1 point per cell)
     // queries in target-grid cell order (identity transform)
-    KN_CK(pool.get(&d_qs, n_query));
+    ST_CK("knn", pool.get(&d_qs, n_query));
     {
       const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
       float axes[9];
       uint32_t nt = 0;
-      KN_CK(sort_source(d_q, (uint32_t)n_query, gr.grid, I, d_qs, s, &d_tiles, &d_tc, axes, &nt, sort_ws));
-      KN_CK(hipStreamSynchronize(s));
+      ST_CK("knn", sort_source(d_q, (uint32_t)n_query, gr.grid, I, d_qs, s, &d_tiles, &d_tc, axes, &nt, sort_ws));
+      ST_CK("knn", hipStreamSynchronize(s));
       sort_ws = SortWorkspace{};      // (only the sorted queries are used)
     }
     KnnArgs a{};
     a.g = gr.grid; a.queries = d_qs; a.nq = (uint32_t)n_query; a.k = (uint32_t)k; a.radius_sq = max_sq_dist;
-    if (idx_out) { KN_CK(pool.get(&d_idx, n_query * k)); a.out_idx = d_idx; }
-    if (idx_out && d2_out) { KN_CK(pool.get(&d_d2, n_query * k)); a.out_d2 = d_d2; }
-    if (cnt_out) { KN_CK(pool.get(&d_cnt, n_query)); a.out_cnt = d_cnt; }
+    if (idx_out) { ST_CK("knn", pool.get(&d_idx, n_query * k)); a.out_idx = d_idx; }
+    if (idx_out && d2_out) { ST_CK("knn", pool.get(&d_d2, n_query * k)); a.out_d2 = d_d2; }
+    if (cnt_out) { ST_CK("knn", pool.get(&d_cnt, n_query)); a.out_cnt = d_cnt; }
     a.do_pca = do_pca ? 1 : 0;
     if (do_pca) {
-      KN_CK(pool.get(&d_nrm, 3 * n_query));
+      ST_CK("knn", pool.get(&d_nrm, 3 * n_query));
       a.ref_xyz = d_ref; a.normals = d_nrm;
-      if (curvature_out) { KN_CK(pool.get(&d_curv, n_query)); a.curvature = d_curv; }
+      if (curvature_out) { ST_CK("knn", pool.get(&d_curv, n_query)); a.curvature = d_curv; }
       a.use_vp = 0;
       if (view_point && std::isfinite(view_point[0]) && std::isfinite(view_point[1]) && std::isfinite(view_point[2])) {   // normal_estimation.hpp:366
         a.use_vp = 1;
@@ -455,16 +442,16 @@ int knn_impl(int device, const float* ref_xyz, size_t n_ref, const float* query_
       // again; rule 1 -- tables first; rule 0 -- the keys' own order (lowest index)
       const int rule = g_knn_tie_rule;
       a.tie = TieDev{}; a.tie.mode = rule != 0 ? 1 : 0; a.by_pos = 0;
-      if (rule != 0) { KN_CK(pool.get(&d_tiecnt, 1)); KN_CK(hipMemsetAsync(d_tiecnt, 0, sizeof(unsigned int), s)); a.tie_count = d_tiecnt; }
+      if (rule != 0) { ST_CK("knn", pool.get(&d_tiecnt, 1)); ST_CK("knn", hipMemsetAsync(d_tiecnt, 0, sizeof(unsigned int), s)); a.tie_count = d_tiecnt; }
       for (int pass = 0; pass < 2; ++pass) {
         bool need_tables = rule == 1 && pass == 0;
         if (!need_tables) {
           hipLaunchKernelGGL(k_knn, dim3((unsigned)((n_query + KNN_THREADS - 1) / KNN_THREADS)), dim3(KNN_THREADS), k * KNN_THREADS * sizeof(unsigned long long), s, a);
-          KN_CK(hipGetLastError());
+          ST_CK("knn", hipGetLastError());
           if (rule != 2 || pass == 1 || a.tie.leaf_slot != nullptr) break;
           unsigned int tied = 0;
-          KN_CK(hipMemcpyAsync(&tied, d_tiecnt, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
-          KN_CK(hipStreamSynchronize(s));
+          ST_CK("knn", hipMemcpyAsync(&tied, d_tiecnt, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+          ST_CK("knn", hipStreamSynchronize(s));
           if (tied == 0) break;
           need_tables = true;
         }
@@ -472,23 +459,23 @@ int knn_impl(int device, const float* ref_xyz, size_t n_ref, const float* query_
           // the order tables of the tree the reference builds over the searched cloud (nanoflann 1.7.1, leaf size 10: core/kd_tree.hpp:162-170),
           // built on the device (tie_build.hip)
           size_t nn = 0;
-          KN_CK(pool.get(&d_tie_ls, n_ref));
-          KN_CK(pool.get(&d_tie_leaf, n_ref));
-          KN_CK(pool.get(&d_tie_slot, n_ref));
-          KN_CK(tie_order_build_device(d_ref, nullptr, (uint32_t)n_ref, s, d_tie_leaf, d_tie_slot, &d_tie_nodes, &nn, nullptr));
+          ST_CK("knn", pool.get(&d_tie_ls, n_ref));
+          ST_CK("knn", pool.get(&d_tie_leaf, n_ref));
+          ST_CK("knn", pool.get(&d_tie_slot, n_ref));
+          ST_CK("knn", tie_order_build_device(d_ref, nullptr, (uint32_t)n_ref, s, d_tie_leaf, d_tie_slot, &d_tie_nodes, &nn, nullptr));
           launch_tie_tables_by_position(gr.grid.pts, gr.grid.n, d_tie_leaf, d_tie_slot, d_tie_ls, s);
-          KN_CK(hipGetLastError());
+          ST_CK("knn", hipGetLastError());
           a.tie.leaf_slot = d_tie_ls; a.tie.nodes = d_tie_nodes; a.by_pos = 1;
         }
       }
     }
-    KN_CK(hipGetLastError());
-    if (idx_out) KN_CK(hipMemcpyAsync(idx_out, d_idx, n_query * k * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    if (idx_out && d2_out) KN_CK(hipMemcpyAsync(d2_out, d_d2, n_query * k * sizeof(float), hipMemcpyDeviceToHost, s));
-    if (cnt_out) KN_CK(hipMemcpyAsync(cnt_out, d_cnt, n_query * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    if (do_pca) KN_CK(hipMemcpyAsync(normals_out, d_nrm, 3 * n_query * sizeof(float), hipMemcpyDeviceToHost, s));
-    if (do_pca && curvature_out) KN_CK(hipMemcpyAsync(curvature_out, d_curv, n_query * sizeof(float), hipMemcpyDeviceToHost, s));
-    KN_CK(hipStreamSynchronize(s));
+    ST_CK("knn", hipGetLastError());
+    if (idx_out) ST_CK("knn", hipMemcpyAsync(idx_out, d_idx, n_query * k * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (idx_out && d2_out) ST_CK("knn", hipMemcpyAsync(d2_out, d_d2, n_query * k * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (cnt_out) ST_CK("knn", hipMemcpyAsync(cnt_out, d_cnt, n_query * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (do_pca) ST_CK("knn", hipMemcpyAsync(normals_out, d_nrm, 3 * n_query * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (do_pca && curvature_out) ST_CK("knn", hipMemcpyAsync(curvature_out, d_curv, n_query * sizeof(float), hipMemcpyDeviceToHost, s));
+    ST_CK("knn", hipStreamSynchronize(s));
   }
   return CILHIP_OK;
 }
@@ -553,7 +540,8 @@ __global__ void k_offsets32(const unsigned long long* __restrict__ off64, uint32
 
 int radius_impl(int device, const float* ref_xyz, size_t n_ref, const float* query_xyz, size_t n_query, int mem, float radius_sq,
                 uint64_t* offsets_out, uint32_t* idx_out, float* d2_out, size_t capacity, size_t* total_out) {
-  if ((!ref_xyz && n_ref) || !offsets_out || n_ref > 0xFFFFFFF0ull || n_query > 0xFFFFFFF0ull || !std::isfinite(radius_sq)) return CILHIP_ERR_INVALID;
+  if ((!ref_xyz && n_ref) || !offsets_out || n_ref > 0xFFFFFFF0ull || n_query > 0xFFFFFFF0ull || !std::isfinite(radius_sq)) return st_fail(CILHIP_ERR_INVALID, "radius_search", kBadArguments);
+  st_clear();
   if (!(radius_sq > 0.0f)) radius_sq = 0.0f;
   const bool self = query_xyz == nullptr;
   if (self) n_query = n_ref;
@@ -569,78 +557,65 @@ int radius_impl(int device, const float* ref_xyz, size_t n_ref, const float* que
   SortWorkspace sort_ws;
   StreamGuard s;      // (declared last: drained and destroyed before anything is freed)
   {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CILHIP_ERR_NO_DEVICE;
-    KN_CK(hipSetDevice(device));
+    if (const int open = st_open("radius_search", device)) return open;
     offsets_out[0] = 0;
     if (n_query == 0) return CILHIP_OK;
-    KN_CK(s.create());
-    if (mem == CILHIP_MEM_DEVICE) {
-      d_ref = const_cast<float*>(ref_xyz);
-      d_q = self ? d_ref : const_cast<float*>(query_xyz);
-    } else {
-      if (n_ref) {
-        KN_CK(pool.get(&d_ref, 3 * n_ref));
-        KN_CK(hipMemcpyAsync(d_ref, ref_xyz, 3 * n_ref * sizeof(float), hipMemcpyHostToDevice, s));
-      }
-      if (self) d_q = d_ref;
-      else {
-        KN_CK(pool.get(&d_q, 3 * n_query));
-        KN_CK(hipMemcpyAsync(d_q, query_xyz, 3 * n_query * sizeof(float), hipMemcpyHostToDevice, s));
-      }
-    }
+    ST_CK("radius_search", s.create());
+    if (n_ref || mem == CILHIP_MEM_DEVICE) ST_CK("radius_search", st_stage(pool, s, mem, ref_xyz, 3 * n_ref, &d_ref));      // (an empty host cloud: no block)
+    if (self) d_q = d_ref;
+    else ST_CK("radius_search", st_stage(pool, s, mem, query_xyz, 3 * n_query, &d_q));
     double mean[3];
     {
       const hipError_t eg = build_grid(d_ref, nullptr, (uint32_t)n_ref, s, &gr, mean, 2.0);
-      if (eg == GRID_RANGE_ERROR) { set_stateless_error(std::string("grid: ") + kGridRangeMessage); return CILHIP_ERR_UNSUPPORTED; }
-      KN_CK(eg);
+      if (eg == GRID_RANGE_ERROR) return st_fail(CILHIP_ERR_UNSUPPORTED, "grid", kGridRangeMessage);
+      ST_CK("radius_search", eg);
     }
-    KN_CK(pool.get(&d_qs, n_query));
+    ST_CK("radius_search", pool.get(&d_qs, n_query));
     {
       const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
       float axes[9];
       uint32_t nt = 0;
-      KN_CK(sort_source(d_q, (uint32_t)n_query, gr.grid, I, d_qs, s, &d_tiles, &d_tc, axes, &nt, sort_ws));
-      KN_CK(hipStreamSynchronize(s));
+      ST_CK("radius_search", sort_source(d_q, (uint32_t)n_query, gr.grid, I, d_qs, s, &d_tiles, &d_tc, axes, &nt, sort_ws));
+      ST_CK("radius_search", hipStreamSynchronize(s));
       sort_ws = SortWorkspace{};      // (only the sorted queries are used)
     }
     const unsigned nblk = (unsigned)((n_query + KNN_THREADS - 1) / KNN_THREADS);
-    KN_CK(pool.get(&d_cnt, n_query + 1));
-    KN_CK(hipMemsetAsync(d_cnt, 0, (n_query + 1) * sizeof(unsigned long long), s));
+    ST_CK("radius_search", pool.get(&d_cnt, n_query + 1));
+    ST_CK("radius_search", hipMemsetAsync(d_cnt, 0, (n_query + 1) * sizeof(unsigned long long), s));
     hipLaunchKernelGGL((k_radius_lists<false>), dim3(nblk), dim3(KNN_THREADS), 0, s, gr.grid, (const float4*)d_qs, (uint32_t)n_query, radius_sq, d_cnt,
                        (unsigned long long*)nullptr);
     {  // counts -> offsets (exclusive scan over n_query + 1 entries: the last one is the total), in place
       size_t tmp_bytes = 0;
-      KN_CK(rocprim::exclusive_scan(nullptr, tmp_bytes, d_cnt, d_cnt, 0ull, n_query + 1, rocprim::plus<unsigned long long>(), s));
+      ST_CK("radius_search", rocprim::exclusive_scan(nullptr, tmp_bytes, d_cnt, d_cnt, 0ull, n_query + 1, rocprim::plus<unsigned long long>(), s));
       DevBuf<unsigned char> d_tmp;
-      KN_CK(d_tmp.alloc(tmp_bytes));
-      KN_CK(rocprim::exclusive_scan(d_tmp.get(), tmp_bytes, d_cnt, d_cnt, 0ull, n_query + 1, rocprim::plus<unsigned long long>(), s));
+      ST_CK("radius_search", d_tmp.alloc(tmp_bytes));
+      ST_CK("radius_search", rocprim::exclusive_scan(d_tmp.get(), tmp_bytes, d_cnt, d_cnt, 0ull, n_query + 1, rocprim::plus<unsigned long long>(), s));
     }
-    KN_CK(hipMemcpyAsync(offsets_out, d_cnt, (n_query + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    KN_CK(hipStreamSynchronize(s));
+    ST_CK("radius_search", hipMemcpyAsync(offsets_out, d_cnt, (n_query + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    ST_CK("radius_search", hipStreamSynchronize(s));
     const size_t total = (size_t)offsets_out[n_query];
     if (total_out) *total_out = total;
     if (idx_out && capacity >= total && total > 0) {
-      if (total > 0xFFFFFFF0ull) return CILHIP_ERR_UNSUPPORTED;   // one segmented sort call takes 32-bit sizes
-      KN_CK(pool.get(&d_keys, total));
-      KN_CK(pool.get(&d_keys2, total));
+      if (total > 0xFFFFFFF0ull) return st_fail(CILHIP_ERR_UNSUPPORTED, "radius_search", "the lists hold more than 2^32 - 16 entries together");   // one segmented sort call takes 32-bit sizes
+      ST_CK("radius_search", pool.get(&d_keys, total));
+      ST_CK("radius_search", pool.get(&d_keys2, total));
       hipLaunchKernelGGL((k_radius_lists<true>), dim3(nblk), dim3(KNN_THREADS), 0, s, gr.grid, (const float4*)d_qs, (uint32_t)n_query, radius_sq, d_cnt, d_keys);
-      KN_CK(pool.get(&d_off32, n_query + 1));
+      ST_CK("radius_search", pool.get(&d_off32, n_query + 1));
       hipLaunchKernelGGL(k_offsets32, dim3(256), dim3(256), 0, s, (const unsigned long long*)d_cnt, (uint32_t)(n_query + 1), d_off32);
       {
         size_t tmp_bytes = 0;
-        KN_CK(rocprim::segmented_radix_sort_keys(nullptr, tmp_bytes, d_keys, d_keys2, (unsigned int)total, (unsigned int)n_query, d_off32, d_off32 + 1, 0, 64, s));
+        ST_CK("radius_search", rocprim::segmented_radix_sort_keys(nullptr, tmp_bytes, d_keys, d_keys2, (unsigned int)total, (unsigned int)n_query, d_off32, d_off32 + 1, 0, 64, s));
         void* d_tmp = nullptr;
-        KN_CK(pool.bytes(&d_tmp, tmp_bytes));
-        KN_CK(rocprim::segmented_radix_sort_keys(d_tmp, tmp_bytes, d_keys, d_keys2, (unsigned int)total, (unsigned int)n_query, d_off32, d_off32 + 1, 0, 64, s));
+        ST_CK("radius_search", pool.bytes(&d_tmp, tmp_bytes));
+        ST_CK("radius_search", rocprim::segmented_radix_sort_keys(d_tmp, tmp_bytes, d_keys, d_keys2, (unsigned int)total, (unsigned int)n_query, d_off32, d_off32 + 1, 0, 64, s));
       }
-      KN_CK(pool.get(&d_idx, total));
-      if (d2_out) KN_CK(pool.get(&d_d2, total));
+      ST_CK("radius_search", pool.get(&d_idx, total));
+      if (d2_out) ST_CK("radius_search", pool.get(&d_d2, total));
       hipLaunchKernelGGL(k_unpack_radius, dim3(2048), dim3(256), 0, s, (const unsigned long long*)d_keys2, total, d_idx, d_d2);
-      KN_CK(hipGetLastError());
-      KN_CK(hipMemcpyAsync(idx_out, d_idx, total * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-      if (d2_out) KN_CK(hipMemcpyAsync(d2_out, d_d2, total * sizeof(float), hipMemcpyDeviceToHost, s));
-      KN_CK(hipStreamSynchronize(s));
+      ST_CK("radius_search", hipGetLastError());
+      ST_CK("radius_search", hipMemcpyAsync(idx_out, d_idx, total * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+      if (d2_out) ST_CK("radius_search", hipMemcpyAsync(d2_out, d_d2, total * sizeof(float), hipMemcpyDeviceToHost, s));
+      ST_CK("radius_search", hipStreamSynchronize(s));
     }
   }
   return CILHIP_OK;
@@ -664,20 +639,20 @@ int cilhip_knn_set_tie_rule(int rule) {
 
 int cilhip_knn3f(int device, const float* ref_xyz, size_t n_ref, const float* query_xyz, size_t n_query, int mem, size_t k,
                  float max_sq_dist, uint32_t* idx_out, float* d2_out, uint32_t* counts_out) {
-  if (!idx_out && !counts_out) return CILHIP_ERR_INVALID;
+  if (!idx_out && !counts_out) return cilhip::st_fail(CILHIP_ERR_INVALID, "knn", "idx_out and counts_out are both null");
   return cilhip::knn_impl(device, ref_xyz, n_ref, query_xyz, n_query, mem, k, max_sq_dist, idx_out, d2_out, counts_out, false, nullptr, nullptr,
                           nullptr);
 }
 
 int cilhip_normals_radius3f(int device, const float* xyz, size_t n, int mem, float radius_sq, const float* view_point, float* normals_out,
                             float* curvature_out) {
-  if (!normals_out && n) return CILHIP_ERR_INVALID;
+  if (!normals_out && n) return cilhip::st_fail(CILHIP_ERR_INVALID, "knn", "normals_out is null");
   return cilhip::knn_impl(device, xyz, n, nullptr, n, mem, 0, radius_sq, nullptr, nullptr, nullptr, true, view_point, normals_out, curvature_out);
 }
 
 int cilhip_normals_knn3f(int device, const float* xyz, size_t n, int mem, size_t k, float max_sq_dist, const float* view_point,
                          float* normals_out, float* curvature_out) {
-  if (!normals_out && n) return CILHIP_ERR_INVALID;
+  if (!normals_out && n) return cilhip::st_fail(CILHIP_ERR_INVALID, "knn", "normals_out is null");
   return cilhip::knn_impl(device, xyz, n, nullptr, n, mem, k, max_sq_dist, nullptr, nullptr, nullptr, true, view_point, normals_out, curvature_out);
 }
 

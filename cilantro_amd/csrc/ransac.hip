@@ -16,8 +16,9 @@
 // the same plane.  Model fit: f32 per-term arithmetic, f64 accumulation in a fixed order (bitwise
 // reproducible), f64 Jacobi eigen-solve (solve.hpp) in place of Eigen's f32 SelfAdjointEigenSolver.
 #include "../../include/cilantro_hip/c_api.h"
-#include "device_mem.hpp"
+#include "ransac_sampling.hpp"
 #include "solve.hpp"
+#include "stateless.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -26,6 +27,8 @@
 #include <vector>
 
 namespace {
+
+using namespace cilhip;
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr int RS_THREADS = 256;
@@ -314,19 +317,6 @@ __global__ __launch_bounds__(RS_THREADS) void k_write_final(const float* __restr
   }
 }
 
-#define RS_CK(x) do { if ((x) != hipSuccess) return CILHIP_ERR_HIP; } while (0)
-
-inline uint64_t splitmix64(uint64_t& s) {
-  uint64_t z = (s += 0x9E3779B97F4A7C15ull);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-inline uint64_t bounded(uint64_t& s, uint64_t bound) {   // uniform in [0, bound) (128-bit multiply, bias < 2^-32)
-  return (uint64_t)(((unsigned __int128)splitmix64(s) * bound) >> 64);
-}
-
 // what one call holds on the device: views into the pool's allocations (xyz: or the caller's device cloud), released at scope exit
 struct Buffers {
   cilhip::DevPool pool;
@@ -362,7 +352,8 @@ extern "C" {
 int cilhip_plane_ransac3f(int device, const float* xyz, size_t n, int mem, const uint32_t* samples, uint64_t seed,
                           float max_residual, size_t target_inliers, size_t max_iter, int re_estimate,
                           cilhip_plane_model* out, float* residuals_out, uint32_t* inliers_out) {
-  if (!out || (!xyz && n) || n > 0xFFFFFFF0ull || max_iter > 0x0FFFFFFFull) return CILHIP_ERR_INVALID;
+  if (!out || (!xyz && n) || n > 0xFFFFFFF0ull || max_iter > 0x0FFFFFFFull) return st_fail(CILHIP_ERR_INVALID, "plane_ransac", kBadArguments);
+  st_clear();
   Buffers b;
   RansacState hs;
   std::memset(&hs, 0, sizeof hs);
@@ -370,54 +361,35 @@ int cilhip_plane_ransac3f(int device, const float* xyz, size_t n, int mem, const
   const uint32_t sample_size = n < 3 ? (uint32_t)n : 3u;          // ransac_base.hpp:67
   if (target_inliers > n) target_inliers = n;                     // :68
   float ms = 0.0f;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CILHIP_ERR_NO_DEVICE;
+  const int open = st_open("plane_ransac", device);
+  if (open == CILHIP_ERR_NO_DEVICE) return open;
   const int rc = [&]() -> int {      // (whatever it returns, `out` is filled from hs below)
-    RS_CK(hipSetDevice(device));
-    RS_CK(b.s.create());
-    RS_CK(b.e0.create());
-    RS_CK(b.e1.create());
-    RS_CK(b.pool.get(&b.st, 1));
-    RS_CK(hipMemcpyAsync(b.st, &hs, sizeof hs, hipMemcpyHostToDevice, b.s));
+    if (open != CILHIP_OK) return open;
+    ST_CK("plane_ransac", b.s.create());
+    ST_CK("plane_ransac", b.e0.create());
+    ST_CK("plane_ransac", b.e1.create());
+    ST_CK("plane_ransac", b.pool.get(&b.st, 1));
+    ST_CK("plane_ransac", hipMemcpyAsync(b.st, &hs, sizeof hs, hipMemcpyHostToDevice, b.s));
     if (n > 0 && max_iter > 0) {
-      if (mem == CILHIP_MEM_DEVICE) {
-        b.xyz = const_cast<float*>(xyz);
-      } else {
-        RS_CK(b.pool.get(&b.xyz, 3 * n));
-        RS_CK(hipMemcpyAsync(b.xyz, xyz, 3 * n * sizeof(float), hipMemcpyHostToDevice, b.s));
-      }
+      ST_CK("plane_ransac", st_stage(b.pool, b.s, mem, xyz, 3 * n, &b.xyz));
       // the random samples (ransac_base.hpp:83-91): 3 distinct indices per iteration; drawn on the host
       std::vector<uint32_t> hsamp;
       if (!samples) {
         hsamp.resize(3 * max_iter);
-        uint64_t st = seed;
-        for (size_t it = 0; it < max_iter; ++it) {
-          uint32_t pick[3] = {0, 0, 0};
-          for (uint32_t i = 0; i < sample_size; ++i) {
-            uint32_t v = (uint32_t)bounded(st, n - i);   // i-th draw among the n-i indices not picked yet
-            uint32_t srt[3];
-            for (uint32_t a = 0; a < i; ++a) srt[a] = pick[a];
-            for (uint32_t a = 0; a + 1 < i; ++a)
-              if (srt[a] > srt[a + 1]) { const uint32_t t = srt[a]; srt[a] = srt[a + 1]; srt[a + 1] = t; }
-            for (uint32_t a = 0; a < i; ++a) v += v >= srt[a] ? 1u : 0u;
-            pick[i] = v;
-          }
-          for (int i = 0; i < 3; ++i) hsamp[3 * it + i] = pick[i];
-        }
+        draw_samples(seed, n, sample_size, max_iter, hsamp.data());
         samples = hsamp.data();
-      } else {
-        for (size_t i = 0; i < 3 * max_iter; ++i)
-          if ((i % 3) < sample_size && samples[i] >= n) return CILHIP_ERR_INVALID;
+      } else if (!samples_in_range(samples, n, sample_size, max_iter)) {
+        return st_fail(CILHIP_ERR_INVALID, "plane_ransac", "a sample index is not below n");
       }
       const size_t mpad = (max_iter + RS_ROUND - 1) / RS_ROUND * RS_ROUND;
       const int nb = score_blocks(n);
-      RS_CK(b.pool.get(&b.samples, 3 * max_iter));
-      RS_CK(b.pool.get(&b.planes, mpad));
-      RS_CK(b.pool.get(&b.partial, (size_t)nb * RS_ROUND));
-      RS_CK(b.pool.get(&b.dpartial, (size_t)RS_MAX_BLOCKS * 8));
-      RS_CK(b.pool.get(&b.chunk_counts, RS_MAX_BLOCKS));
-      RS_CK(hipMemcpyAsync(b.samples, samples, 3 * max_iter * sizeof(uint32_t), hipMemcpyHostToDevice, b.s));
-      RS_CK(hipEventRecord(b.e0, b.s));
+      ST_CK("plane_ransac", b.pool.get(&b.samples, 3 * max_iter));
+      ST_CK("plane_ransac", b.pool.get(&b.planes, mpad));
+      ST_CK("plane_ransac", b.pool.get(&b.partial, (size_t)nb * RS_ROUND));
+      ST_CK("plane_ransac", b.pool.get(&b.dpartial, (size_t)RS_MAX_BLOCKS * 8));
+      ST_CK("plane_ransac", b.pool.get(&b.chunk_counts, RS_MAX_BLOCKS));
+      ST_CK("plane_ransac", hipMemcpyAsync(b.samples, samples, 3 * max_iter * sizeof(uint32_t), hipMemcpyHostToDevice, b.s));
+      ST_CK("plane_ransac", hipEventRecord(b.e0, b.s));
       hipLaunchKernelGGL(k_models, dim3((unsigned)((mpad + 127) / 128)), dim3(128), 0, b.s, b.xyz, b.samples, sample_size,
                          (uint32_t)max_iter, (uint32_t)mpad, b.planes);
       for (size_t r0 = 0; r0 < max_iter; r0 += RS_ROUND) {
@@ -439,26 +411,24 @@ int cilhip_plane_ransac3f(int device, const float* xyz, size_t n, int mem, const
       const int cb = (int)((n + chunk - 1) / chunk);
       hipLaunchKernelGGL(k_chunk_counts, dim3(cb), dim3(RS_THREADS), 0, b.s, b.xyz, (uint32_t)n, chunk, max_residual, b.st, b.chunk_counts);
       hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(64), 0, b.s, b.chunk_counts, cb, b.st);
-      if (residuals_out) RS_CK(b.pool.get(&b.residuals, n));
-      if (inliers_out) RS_CK(b.pool.get(&b.inliers, n));
+      if (residuals_out) ST_CK("plane_ransac", b.pool.get(&b.residuals, n));
+      if (inliers_out) ST_CK("plane_ransac", b.pool.get(&b.inliers, n));
       if (residuals_out || inliers_out)
         hipLaunchKernelGGL(k_write_final, dim3(cb), dim3(RS_THREADS), 0, b.s, b.xyz, (uint32_t)n, chunk, max_residual, b.st,
                            b.chunk_counts, b.residuals, b.inliers);
-      RS_CK(hipEventRecord(b.e1, b.s));
-      RS_CK(hipGetLastError());
+      ST_CK("plane_ransac", hipEventRecord(b.e1, b.s));
+      ST_CK("plane_ransac", hipGetLastError());
     }
-    RS_CK(hipMemcpyAsync(&hs, b.st, sizeof hs, hipMemcpyDeviceToHost, b.s));
-    RS_CK(hipStreamSynchronize(b.s));
+    ST_CK("plane_ransac", hipMemcpyAsync(&hs, b.st, sizeof hs, hipMemcpyDeviceToHost, b.s));
+    ST_CK("plane_ransac", hipStreamSynchronize(b.s));
     // an empty cloud: the reference's loop runs once -- an empty sample, no inliers, 0 >= the clamped target -- and stops (ransac_base.hpp:103-114)
     if (n == 0 && max_iter > 0) hs.iterations = 1;
     if (n > 0 && max_iter > 0) {
-      RS_CK(hipEventElapsedTime(&ms, b.e0, b.e1));
+      ST_CK("plane_ransac", hipEventElapsedTime(&ms, b.e0, b.e1));
       // the reference keeps residuals / inliers of the best hypothesis; with no accepted model they are empty
-      const bool any = hs.have_model != 0;
-      if (residuals_out && b.residuals) RS_CK(hipMemcpy(residuals_out, b.residuals, n * sizeof(float), hipMemcpyDeviceToHost));
+      if (residuals_out && b.residuals) ST_CK("plane_ransac", hipMemcpy(residuals_out, b.residuals, n * sizeof(float), hipMemcpyDeviceToHost));
       if (inliers_out && b.inliers && hs.n_inliers)
-        RS_CK(hipMemcpy(inliers_out, b.inliers, (size_t)hs.n_inliers * sizeof(uint32_t), hipMemcpyDeviceToHost));
-      (void)any;
+        ST_CK("plane_ransac", hipMemcpy(inliers_out, b.inliers, (size_t)hs.n_inliers * sizeof(uint32_t), hipMemcpyDeviceToHost));
     }
     return CILHIP_OK;
   }();
@@ -473,29 +443,23 @@ int cilhip_plane_ransac3f(int device, const float* xyz, size_t n, int mem, const
 
 int cilhip_plane_score3f(int device, const float* xyz, size_t n, int mem, const float* planes, size_t m, float max_residual,
                          uint32_t* counts_out) {
-  if ((!xyz && n) || (!planes && m) || (!counts_out && m) || n > 0xFFFFFFF0ull) return CILHIP_ERR_INVALID;
+  if ((!xyz && n) || (!planes && m) || (!counts_out && m) || n > 0xFFFFFFF0ull) return st_fail(CILHIP_ERR_INVALID, "plane_ransac", kBadArguments);
+  st_clear();
   if (m == 0) return CILHIP_OK;
   Buffers b;
   {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CILHIP_ERR_NO_DEVICE;
-    RS_CK(hipSetDevice(device));
-    RS_CK(b.s.create());
+    if (const int open = st_open("plane_ransac", device)) return open;
+    ST_CK("plane_ransac", b.s.create());
     if (n == 0) { std::memset(counts_out, 0, m * sizeof(uint32_t)); return CILHIP_OK; }
-    if (mem == CILHIP_MEM_DEVICE) {
-      b.xyz = const_cast<float*>(xyz);
-    } else {
-      RS_CK(b.pool.get(&b.xyz, 3 * n));
-      RS_CK(hipMemcpyAsync(b.xyz, xyz, 3 * n * sizeof(float), hipMemcpyHostToDevice, b.s));
-    }
+    ST_CK("plane_ransac", st_stage(b.pool, b.s, mem, xyz, 3 * n, &b.xyz));
     const size_t mpad = (m + RS_ROUND - 1) / RS_ROUND * RS_ROUND;
     const int nb = score_blocks(n);
     std::vector<float> hp(4 * mpad, NAN);
     std::memcpy(hp.data(), planes, 4 * m * sizeof(float));
-    RS_CK(b.pool.get(&b.planes, mpad));
-    RS_CK(b.pool.get(&b.partial, (size_t)nb * RS_ROUND));
-    RS_CK(b.pool.get(&b.counts, mpad));
-    RS_CK(hipMemcpyAsync(b.planes, hp.data(), 4 * mpad * sizeof(float), hipMemcpyHostToDevice, b.s));
+    ST_CK("plane_ransac", b.pool.get(&b.planes, mpad));
+    ST_CK("plane_ransac", b.pool.get(&b.partial, (size_t)nb * RS_ROUND));
+    ST_CK("plane_ransac", b.pool.get(&b.counts, mpad));
+    ST_CK("plane_ransac", hipMemcpyAsync(b.planes, hp.data(), 4 * mpad * sizeof(float), hipMemcpyHostToDevice, b.s));
     for (size_t r0 = 0; r0 < m; r0 += RS_ROUND) {
       const uint32_t mm = (uint32_t)(m - r0 < RS_ROUND ? m - r0 : RS_ROUND);
       hipLaunchKernelGGL(k_score, dim3(nb), dim3(RS_THREADS), 0, b.s, b.xyz, (uint32_t)n, (const float*)(b.planes + r0), (mm + 3u) & ~3u,
@@ -503,42 +467,38 @@ int cilhip_plane_score3f(int device, const float* xyz, size_t n, int mem, const 
       hipLaunchKernelGGL(k_pick, dim3(1), dim3(RS_ROUND * PICK_GROUPS), 0, b.s, b.partial, nb, b.planes + r0, mm, 0u, 0u, (RansacState*)nullptr,
                          b.counts + r0);
     }
-    RS_CK(hipGetLastError());
-    RS_CK(hipMemcpyAsync(counts_out, b.counts, m * sizeof(uint32_t), hipMemcpyDeviceToHost, b.s));
-    RS_CK(hipStreamSynchronize(b.s));
+    ST_CK("plane_ransac", hipGetLastError());
+    ST_CK("plane_ransac", hipMemcpyAsync(counts_out, b.counts, m * sizeof(uint32_t), hipMemcpyDeviceToHost, b.s));
+    ST_CK("plane_ransac", hipStreamSynchronize(b.s));
   }
   return CILHIP_OK;
 }
 
 int cilhip_plane_fit3f(int device, const float* xyz, size_t n, int mem, float plane_out[4]) {
-  if (!plane_out || (!xyz && n) || n > 0xFFFFFFF0ull) return CILHIP_ERR_INVALID;
+  if (!plane_out || (!xyz && n) || n > 0xFFFFFFF0ull) return st_fail(CILHIP_ERR_INVALID, "plane_ransac", kBadArguments);
+  st_clear();
   Buffers b;
   RansacState hs;
   std::memset(&hs, 0, sizeof hs);
   for (int d = 0; d < 4; ++d) hs.best[d] = NAN;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CILHIP_ERR_NO_DEVICE;
+  const int open = st_open("plane_ransac", device);
+  if (open == CILHIP_ERR_NO_DEVICE) return open;
   const int rc = [&]() -> int {      // (whatever it returns, plane_out is filled from hs below)
-    RS_CK(hipSetDevice(device));
+    if (open != CILHIP_OK) return open;
     if (n >= 2) {
-      RS_CK(b.s.create());
-      RS_CK(b.pool.get(&b.st, 1));
-      RS_CK(hipMemcpyAsync(b.st, &hs, sizeof hs, hipMemcpyHostToDevice, b.s));
-      if (mem == CILHIP_MEM_DEVICE) {
-        b.xyz = const_cast<float*>(xyz);
-      } else {
-        RS_CK(b.pool.get(&b.xyz, 3 * n));
-        RS_CK(hipMemcpyAsync(b.xyz, xyz, 3 * n * sizeof(float), hipMemcpyHostToDevice, b.s));
-      }
-      RS_CK(b.pool.get(&b.dpartial, (size_t)RS_MAX_BLOCKS * 8));
+      ST_CK("plane_ransac", b.s.create());
+      ST_CK("plane_ransac", b.pool.get(&b.st, 1));
+      ST_CK("plane_ransac", hipMemcpyAsync(b.st, &hs, sizeof hs, hipMemcpyHostToDevice, b.s));
+      ST_CK("plane_ransac", st_stage(b.pool, b.s, mem, xyz, 3 * n, &b.xyz));
+      ST_CK("plane_ransac", b.pool.get(&b.dpartial, (size_t)RS_MAX_BLOCKS * 8));
       const int mb = (int)std::min<size_t>((n + RS_THREADS - 1) / RS_THREADS, RS_MAX_BLOCKS);
       hipLaunchKernelGGL(k_moments<0>, dim3(mb), dim3(RS_THREADS), 0, b.s, b.xyz, (uint32_t)n, 0.0f, 1, b.st, b.dpartial);
       hipLaunchKernelGGL(k_moments_finish<0>, dim3(1), dim3(64), 0, b.s, b.dpartial, mb, b.st);
       hipLaunchKernelGGL(k_moments<1>, dim3(mb), dim3(RS_THREADS), 0, b.s, b.xyz, (uint32_t)n, 0.0f, 1, b.st, b.dpartial);
       hipLaunchKernelGGL(k_moments_finish<1>, dim3(1), dim3(64), 0, b.s, b.dpartial, mb, b.st);
-      RS_CK(hipGetLastError());
-      RS_CK(hipMemcpyAsync(&hs, b.st, sizeof hs, hipMemcpyDeviceToHost, b.s));
-      RS_CK(hipStreamSynchronize(b.s));
+      ST_CK("plane_ransac", hipGetLastError());
+      ST_CK("plane_ransac", hipMemcpyAsync(&hs, b.st, sizeof hs, hipMemcpyDeviceToHost, b.s));
+      ST_CK("plane_ransac", hipStreamSynchronize(b.s));
     }
     return CILHIP_OK;
   }();

@@ -19,8 +19,9 @@
 // moments (products of f32 coordinates are exact in f64), f64 SVD -- Eigen's JacobiSVD<Matrix3f> round-off is "parity
 // unpinned" (Eigen is absent from the build container), as for every estimator of this engine.
 #include "../../include/cilantro_hip/c_api.h"
-#include "device_mem.hpp"
+#include "ransac_sampling.hpp"
 #include "solve.hpp"
+#include "stateless.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -29,6 +30,8 @@
 #include <vector>
 
 namespace {
+
+using namespace cilhip;
 
 constexpr int TR_THREADS = 256;
 constexpr int TR_PAIRS = 4;       // pairs per lane held in registers
@@ -245,16 +248,6 @@ __global__ __launch_bounds__(TR_THREADS) void k_twrite_final(const float* __rest
   }
 }
 
-#define TR_CK(x) do { if ((x) != hipSuccess) return CILHIP_ERR_HIP; } while (0)
-
-inline uint64_t splitmix64(uint64_t& s) {
-  uint64_t z = (s += 0x9E3779B97F4A7C15ull);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-inline uint64_t bounded(uint64_t& s, uint64_t bound) { return (uint64_t)(((unsigned __int128)splitmix64(s) * bound) >> 64); }
-
 // the largest f32 x with sqrtf(x) <= thr (sqrtf is correctly rounded and monotonic): `norm <= thr` <=> `squaredNorm <= x`
 inline float sq_threshold(float thr) {
   if (!(thr >= 0.0f)) return -1.0f;                        // nothing is an inlier (NaN / negative threshold)
@@ -285,14 +278,8 @@ struct TBuffers {
   cilhip::EventGuard e0, e1;
   cilhip::StreamGuard s;      // (last: drained and destroyed before the events and the allocations go)
   hipError_t upload(const float* d, const float* sc, size_t n, int mem) {
-    if (mem == CILHIP_MEM_DEVICE) { dst = const_cast<float*>(d); src = const_cast<float*>(sc); return hipSuccess; }
-    hipError_t e = pool.get(&dst, 3 * n);
-    if (e != hipSuccess) return e;
-    e = pool.get(&src, 3 * n);
-    if (e != hipSuccess) return e;
-    e = hipMemcpyAsync(dst, d, 3 * n * sizeof(float), hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return e;
-    return hipMemcpyAsync(src, sc, 3 * n * sizeof(float), hipMemcpyHostToDevice, s);
+    const hipError_t e = st_stage(pool, s, mem, d, 3 * n, &dst);
+    return e != hipSuccess ? e : st_stage(pool, s, mem, sc, 3 * n, &src);
   }
 };
 
@@ -315,7 +302,8 @@ extern "C" {
 int cilhip_transform_ransac3f(int device, const float* dst_xyz, const float* src_xyz, size_t n, int mem, const uint32_t* samples, uint64_t seed,
                               float max_residual, size_t target_inliers, size_t max_iter, int re_estimate, cilhip_transform_model* out,
                               float* residuals_out, uint32_t* inliers_out) {
-  if (!out || ((!dst_xyz || !src_xyz) && n) || n > 0xFFFFFFF0ull || max_iter > 0x0FFFFFFFull) return CILHIP_ERR_INVALID;
+  if (!out || ((!dst_xyz || !src_xyz) && n) || n > 0xFFFFFFF0ull || max_iter > 0x0FFFFFFFull) return st_fail(CILHIP_ERR_INVALID, "transform_ransac", kBadArguments);
+  st_clear();
   TBuffers b;
   TState hs;
   std::memset(&hs, 0, sizeof hs);
@@ -324,48 +312,34 @@ int cilhip_transform_ransac3f(int device, const float* dst_xyz, const float* src
   if (target_inliers > n) target_inliers = n;                     // :68
   const float thr_sq = sq_threshold(max_residual);
   float ms = 0.0f;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CILHIP_ERR_NO_DEVICE;
+  const int open = st_open("transform_ransac", device);
+  if (open == CILHIP_ERR_NO_DEVICE) return open;
   const int rc = [&]() -> int {      // (whatever it returns, `out` is filled from hs below)
-    TR_CK(hipSetDevice(device));
-    TR_CK(b.s.create());
-    TR_CK(b.e0.create());
-    TR_CK(b.e1.create());
-    TR_CK(b.pool.get(&b.st, 1));
-    TR_CK(hipMemcpyAsync(b.st, &hs, sizeof hs, hipMemcpyHostToDevice, b.s));
+    if (open != CILHIP_OK) return open;
+    ST_CK("transform_ransac", b.s.create());
+    ST_CK("transform_ransac", b.e0.create());
+    ST_CK("transform_ransac", b.e1.create());
+    ST_CK("transform_ransac", b.pool.get(&b.st, 1));
+    ST_CK("transform_ransac", hipMemcpyAsync(b.st, &hs, sizeof hs, hipMemcpyHostToDevice, b.s));
     if (n > 0) {
-      TR_CK(b.upload(dst_xyz, src_xyz, n, mem));
+      ST_CK("transform_ransac", b.upload(dst_xyz, src_xyz, n, mem));
       std::vector<uint32_t> hsamp;
       if (!samples && max_iter) {      // the random samples (ransac_base.hpp:83-91): distinct indices per iteration, drawn on the host
         hsamp.resize(3 * max_iter);
-        uint64_t st = seed;
-        for (size_t it = 0; it < max_iter; ++it) {
-          uint32_t pick[3] = {0, 0, 0};
-          for (uint32_t i = 0; i < sample_size; ++i) {
-            uint32_t v = (uint32_t)bounded(st, n - i);
-            uint32_t srt[3];
-            for (uint32_t a = 0; a < i; ++a) srt[a] = pick[a];
-            for (uint32_t a = 0; a + 1 < i; ++a)
-              if (srt[a] > srt[a + 1]) { const uint32_t t = srt[a]; srt[a] = srt[a + 1]; srt[a + 1] = t; }
-            for (uint32_t a = 0; a < i; ++a) v += v >= srt[a] ? 1u : 0u;
-            pick[i] = v;
-          }
-          for (int i = 0; i < 3; ++i) hsamp[3 * it + i] = pick[i];
-        }
+        draw_samples(seed, n, sample_size, max_iter, hsamp.data());
         samples = hsamp.data();
-      } else if (samples) {
-        for (size_t i = 0; i < 3 * max_iter; ++i)
-          if ((i % 3) < sample_size && samples[i] >= n) return CILHIP_ERR_INVALID;
+      } else if (samples && !samples_in_range(samples, n, sample_size, max_iter)) {
+        return st_fail(CILHIP_ERR_INVALID, "transform_ransac", "a sample index is not below n");
       }
       const size_t mpad = ((max_iter ? max_iter : 1) + TR_ROUND - 1) / TR_ROUND * TR_ROUND;
       const int nb = tscore_blocks(n);
-      TR_CK(b.pool.get(&b.samples, 3 * (max_iter ? max_iter : 1)));
-      TR_CK(b.pool.get(&b.models, mpad * 12));
-      TR_CK(b.pool.get(&b.partial, (size_t)nb * TR_ROUND));
-      TR_CK(b.pool.get(&b.dpartial, (size_t)TR_MAX_BLOCKS * 16));
-      TR_CK(b.pool.get(&b.chunk_counts, TR_MAX_BLOCKS));
-      if (max_iter) TR_CK(hipMemcpy(b.samples, samples, 3 * max_iter * sizeof(uint32_t), hipMemcpyHostToDevice));      // (blocking: `samples` may be a local vector)
-      TR_CK(hipEventRecord(b.e0, b.s));
+      ST_CK("transform_ransac", b.pool.get(&b.samples, 3 * (max_iter ? max_iter : 1)));
+      ST_CK("transform_ransac", b.pool.get(&b.models, mpad * 12));
+      ST_CK("transform_ransac", b.pool.get(&b.partial, (size_t)nb * TR_ROUND));
+      ST_CK("transform_ransac", b.pool.get(&b.dpartial, (size_t)TR_MAX_BLOCKS * 16));
+      ST_CK("transform_ransac", b.pool.get(&b.chunk_counts, TR_MAX_BLOCKS));
+      if (max_iter) ST_CK("transform_ransac", hipMemcpy(b.samples, samples, 3 * max_iter * sizeof(uint32_t), hipMemcpyHostToDevice));      // (blocking: `samples` may be a local vector)
+      ST_CK("transform_ransac", hipEventRecord(b.e0, b.s));
       if (max_iter)
         hipLaunchKernelGGL(k_tmodels, dim3((unsigned)((mpad + 127) / 128)), dim3(128), 0, b.s, b.dst, b.src, b.samples, sample_size, (uint32_t)max_iter,
                            (uint32_t)mpad, b.models);
@@ -387,23 +361,23 @@ int cilhip_transform_ransac3f(int device, const float* dst_xyz, const float* src
       }
       hipLaunchKernelGGL(k_tchunk_counts, dim3(cb), dim3(TR_THREADS), 0, b.s, b.dst, b.src, (uint32_t)n, chunk, thr_sq, b.st, b.chunk_counts);
       hipLaunchKernelGGL(k_tscan_counts, dim3(1), dim3(64), 0, b.s, b.chunk_counts, cb, b.st);
-      if (residuals_out) TR_CK(b.pool.get(&b.residuals, n));
-      if (inliers_out) TR_CK(b.pool.get(&b.inliers, n));
+      if (residuals_out) ST_CK("transform_ransac", b.pool.get(&b.residuals, n));
+      if (inliers_out) ST_CK("transform_ransac", b.pool.get(&b.inliers, n));
       if (residuals_out || inliers_out)
         hipLaunchKernelGGL(k_twrite_final, dim3(cb), dim3(TR_THREADS), 0, b.s, b.dst, b.src, (uint32_t)n, chunk, thr_sq, b.st, b.chunk_counts,
                            b.residuals, b.inliers);
-      TR_CK(hipEventRecord(b.e1, b.s));
-      TR_CK(hipGetLastError());
+      ST_CK("transform_ransac", hipEventRecord(b.e1, b.s));
+      ST_CK("transform_ransac", hipGetLastError());
     }
-    TR_CK(hipMemcpyAsync(&hs, b.st, sizeof hs, hipMemcpyDeviceToHost, b.s));
-    TR_CK(hipStreamSynchronize(b.s));
+    ST_CK("transform_ransac", hipMemcpyAsync(&hs, b.st, sizeof hs, hipMemcpyDeviceToHost, b.s));
+    ST_CK("transform_ransac", hipStreamSynchronize(b.s));
     // no pairs: the reference's loop runs once -- an empty sample, no inliers, 0 >= the clamped target -- and stops (ransac_base.hpp:103-114)
     if (n == 0 && max_iter > 0) hs.iterations = 1;
     if (n > 0) {
-      TR_CK(hipEventElapsedTime(&ms, b.e0, b.e1));
-      if (residuals_out && b.residuals) TR_CK(hipMemcpy(residuals_out, b.residuals, n * sizeof(float), hipMemcpyDeviceToHost));
+      ST_CK("transform_ransac", hipEventElapsedTime(&ms, b.e0, b.e1));
+      if (residuals_out && b.residuals) ST_CK("transform_ransac", hipMemcpy(residuals_out, b.residuals, n * sizeof(float), hipMemcpyDeviceToHost));
       if (inliers_out && b.inliers && hs.n_inliers)
-        TR_CK(hipMemcpy(inliers_out, b.inliers, (size_t)hs.n_inliers * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        ST_CK("transform_ransac", hipMemcpy(inliers_out, b.inliers, (size_t)hs.n_inliers * sizeof(uint32_t), hipMemcpyDeviceToHost));
     }
     return CILHIP_OK;
   }();
@@ -418,17 +392,16 @@ int cilhip_transform_ransac3f(int device, const float* dst_xyz, const float* src
 
 int cilhip_transform_score3f(int device, const float* dst_xyz, const float* src_xyz, size_t n, int mem, const float* transforms, size_t m,
                              float max_residual, uint32_t* counts_out) {
-  if (((!dst_xyz || !src_xyz) && n) || (!transforms && m) || (!counts_out && m) || n > 0xFFFFFFF0ull) return CILHIP_ERR_INVALID;
+  if (((!dst_xyz || !src_xyz) && n) || (!transforms && m) || (!counts_out && m) || n > 0xFFFFFFF0ull) return st_fail(CILHIP_ERR_INVALID, "transform_ransac", kBadArguments);
+  st_clear();
   if (m == 0) return CILHIP_OK;
   TBuffers b;
   const float thr_sq = sq_threshold(max_residual);
   {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CILHIP_ERR_NO_DEVICE;
-    TR_CK(hipSetDevice(device));
-    TR_CK(b.s.create());
+    if (const int open = st_open("transform_ransac", device)) return open;
+    ST_CK("transform_ransac", b.s.create());
     if (n == 0) { std::memset(counts_out, 0, m * sizeof(uint32_t)); return CILHIP_OK; }
-    TR_CK(b.upload(dst_xyz, src_xyz, n, mem));
+    ST_CK("transform_ransac", b.upload(dst_xyz, src_xyz, n, mem));
     const size_t mpad = (m + TR_ROUND - 1) / TR_ROUND * TR_ROUND;
     const int nb = tscore_blocks(n);
     std::vector<float> hm(12 * mpad, NAN);
@@ -436,10 +409,10 @@ int cilhip_transform_score3f(int device, const float* dst_xyz, const float* src_
       const float* T = transforms + 16 * h;
       for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) hm[12 * h + r * 3 + c] = T[c * 4 + r]; hm[12 * h + 9 + r] = T[12 + r]; }
     }
-    TR_CK(b.pool.get(&b.models, mpad * 12));
-    TR_CK(b.pool.get(&b.partial, (size_t)nb * TR_ROUND));
-    TR_CK(b.pool.get(&b.counts, mpad));
-    TR_CK(hipMemcpyAsync(b.models, hm.data(), 12 * mpad * sizeof(float), hipMemcpyHostToDevice, b.s));
+    ST_CK("transform_ransac", b.pool.get(&b.models, mpad * 12));
+    ST_CK("transform_ransac", b.pool.get(&b.partial, (size_t)nb * TR_ROUND));
+    ST_CK("transform_ransac", b.pool.get(&b.counts, mpad));
+    ST_CK("transform_ransac", hipMemcpyAsync(b.models, hm.data(), 12 * mpad * sizeof(float), hipMemcpyHostToDevice, b.s));
     for (size_t r0 = 0; r0 < m; r0 += TR_ROUND) {
       const uint32_t mm = (uint32_t)(m - r0 < TR_ROUND ? m - r0 : TR_ROUND);
       hipLaunchKernelGGL(k_tscore, dim3(nb), dim3(TR_THREADS), 0, b.s, b.dst, b.src, (uint32_t)n, (const float*)(b.models + 12 * r0), mm, thr_sq,
@@ -447,35 +420,36 @@ int cilhip_transform_score3f(int device, const float* dst_xyz, const float* src_
       hipLaunchKernelGGL(k_tpick, dim3(1), dim3(TR_ROUND), 0, b.s, b.partial, nb, (const float*)(b.models + 12 * r0), mm, 0u, 0u, (TState*)nullptr,
                          b.counts + r0);
     }
-    TR_CK(hipGetLastError());
-    TR_CK(hipMemcpyAsync(counts_out, b.counts, m * sizeof(uint32_t), hipMemcpyDeviceToHost, b.s));
-    TR_CK(hipStreamSynchronize(b.s));
+    ST_CK("transform_ransac", hipGetLastError());
+    ST_CK("transform_ransac", hipMemcpyAsync(counts_out, b.counts, m * sizeof(uint32_t), hipMemcpyDeviceToHost, b.s));
+    ST_CK("transform_ransac", hipStreamSynchronize(b.s));
   }
   return CILHIP_OK;
 }
 
 int cilhip_transform_fit3f(int device, const float* dst_xyz, const float* src_xyz, size_t n, int mem, float T_out[16]) {
-  if (!T_out || ((!dst_xyz || !src_xyz) && n) || n > 0xFFFFFFF0ull) return CILHIP_ERR_INVALID;
+  if (!T_out || ((!dst_xyz || !src_xyz) && n) || n > 0xFFFFFFF0ull) return st_fail(CILHIP_ERR_INVALID, "transform_ransac", kBadArguments);
+  st_clear();
   TBuffers b;
   TState hs;
   std::memset(&hs, 0, sizeof hs);
   hs.best[0] = hs.best[4] = hs.best[8] = 1.0f;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CILHIP_ERR_NO_DEVICE;
+  const int open = st_open("transform_ransac", device);
+  if (open == CILHIP_ERR_NO_DEVICE) return open;
   const int rc = [&]() -> int {      // (whatever it returns, T_out is filled from hs below)
-    TR_CK(hipSetDevice(device));
+    if (open != CILHIP_OK) return open;
     if (n > 0) {
-      TR_CK(b.s.create());
-      TR_CK(b.pool.get(&b.st, 1));
-      TR_CK(hipMemcpyAsync(b.st, &hs, sizeof hs, hipMemcpyHostToDevice, b.s));
-      TR_CK(b.upload(dst_xyz, src_xyz, n, mem));
-      TR_CK(b.pool.get(&b.dpartial, (size_t)TR_MAX_BLOCKS * 16));
+      ST_CK("transform_ransac", b.s.create());
+      ST_CK("transform_ransac", b.pool.get(&b.st, 1));
+      ST_CK("transform_ransac", hipMemcpyAsync(b.st, &hs, sizeof hs, hipMemcpyHostToDevice, b.s));
+      ST_CK("transform_ransac", b.upload(dst_xyz, src_xyz, n, mem));
+      ST_CK("transform_ransac", b.pool.get(&b.dpartial, (size_t)TR_MAX_BLOCKS * 16));
       const int mb = (int)std::min<size_t>((n + TR_THREADS - 1) / TR_THREADS, TR_MAX_BLOCKS);
       hipLaunchKernelGGL(k_tmoments, dim3(mb), dim3(TR_THREADS), 0, b.s, b.dst, b.src, (uint32_t)n, 0.0f, 1, b.st, b.dpartial);
       hipLaunchKernelGGL(k_tmoments_finish, dim3(1), dim3(64), 0, b.s, b.dpartial, mb, b.st);
-      TR_CK(hipGetLastError());
-      TR_CK(hipMemcpyAsync(&hs, b.st, sizeof hs, hipMemcpyDeviceToHost, b.s));
-      TR_CK(hipStreamSynchronize(b.s));
+      ST_CK("transform_ransac", hipGetLastError());
+      ST_CK("transform_ransac", hipMemcpyAsync(&hs, b.st, sizeof hs, hipMemcpyDeviceToHost, b.s));
+      ST_CK("transform_ransac", hipStreamSynchronize(b.s));
     }
     return CILHIP_OK;
   }();

@@ -54,6 +54,8 @@ enum {
 /* device: HIP device ordinal.  Owns one stream, all device buffers, the target grid index. */
 int cilhip_create(cilhip_ctx** out, int device);
 void cilhip_destroy(cilhip_ctx* ctx);
+/* ctx == NULL names the calling thread's last failed stateless call (the entries that take `int device` instead of a context), of any
+ * family; "null context" when the last such call passed its argument rules and did not fail. */
 const char* cilhip_last_error(const cilhip_ctx* ctx);
 /* Run all work on a caller-owned hipStream_t (e.g. torch's current stream) instead of the
  * context's own; pass NULL to go back.  The caller keeps the stream alive.  NULL never means the legacy default

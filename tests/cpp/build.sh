@@ -16,6 +16,8 @@ g++ -O2 -std=c++17 -Wall -ffp-contract=off "$HERE/test_loop_policy.cpp" -o "$HER
 g++ -O2 -std=c++17 -Wall -ffp-contract=off "$HERE/test_grid_policy.cpp" -o "$HERE/bin/test_grid_policy"
 # host-only check of the owners of device allocations (csrc/device_mem.hpp over a counting malloc allocator: plain C++, no HIP)
 g++ -O2 -std=c++17 -Wall -ffp-contract=off "$HERE/test_device_mem.cpp" -o "$HERE/bin/test_device_mem"
+# host-only check of the RANSAC estimators' sampler (csrc/ransac_sampling.hpp: plain C++, no HIP) against a copy of the loop it replaced
+g++ -O2 -std=c++17 -Wall -ffp-contract=off "$HERE/test_ransac_sampling.cpp" -o "$HERE/bin/test_ransac_sampling"
 # tests/cpp/tie_order_host.hpp (the host restatement of the reference's index build: the cross-check of csrc/tie_build.hip) as a host library
 g++ -O2 -std=c++17 -ffp-contract=off -shared -fPIC -pthread "$HERE/tie_order_shim.cpp" -o "$HERE/bin/libtie_order_shim.so"
 # host-only PLY round-trip helper (no GPU library needed)

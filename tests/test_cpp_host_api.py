@@ -82,3 +82,15 @@ def test_device_mem_on_host(hip_lib, orc):
         subprocess.check_call(["bash", os.path.join(ROOT, "tests", "cpp", "build.sh")])
     out = subprocess.run([binp], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and "ALL OK" in out.stdout, out.stdout + out.stderr
+
+
+def test_ransac_sampling_on_host(hip_lib, orc):
+    """cilantro_amd/csrc/ransac_sampling.hpp draws the samples of both RANSAC estimators and checks a caller's: bit for bit against
+    a literal copy of the loop the two estimator files used to carry, over cloud sizes 1 .. 0xFFFFFFF0, a few hundred seeds and 1, 7
+    and 128 iterations -- distinct indices below n, zeros behind a short sample, exactly the arrays with an index in use >= n
+    refused.  Host compiler, no GPU."""
+    binp = os.path.join(ROOT, "tests", "cpp", "bin", "test_ransac_sampling")
+    if not os.path.exists(binp):
+        subprocess.check_call(["bash", os.path.join(ROOT, "tests", "cpp", "build.sh")])
+    out = subprocess.run([binp], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "ALL OK" in out.stdout, out.stdout + out.stderr
