@@ -28,6 +28,7 @@ SYMBOLS = [
     "cilhip_icp_sums_from_keys", "cilhip_icp_order_keys", "cilhip_icp_sums_from_ordered_keys", "cilhip_debug_counters", "cilhip_debug_live_allocations", "cilhip_kmeans3f", "cilhip_kmeans3f_assign", "cilhip_kmeans3f_ex", "cilhip_kmeans3f_assign_ex", "cilhip_kmeans_shard_create", "cilhip_kmeans_shard_destroy", "cilhip_kmeans_shard_maxabs", "cilhip_kmeans_scale_exponent", "cilhip_kmeans_shard_assign", "cilhip_kmeans_shard_farthest", "cilhip_kmeans_shard_move_point", "cilhip_kmeans_shard_nonfinite", "cilhip_kmeans_shard_labels",
     "cilhip_plane_ransac3f", "cilhip_plane_score3f", "cilhip_plane_fit3f", "cilhip_transform_ransac3f", "cilhip_transform_score3f", "cilhip_transform_fit3f", "cilhip_knn3f", "cilhip_knn_set_tie_rule", "cilhip_normals_knn3f", "cilhip_normals_radius3f", "cilhip_radius_search3f", "cilhip_grid_downsample3f",
     "cilhip_cc_default_params", "cilhip_connected_components3f", "cilhip_connected_components_lists",
+    "cilhip_ms_default_params", "cilhip_mean_shift3f", "cilhip_ms_last_stats",
 ]
 
 
@@ -87,6 +88,17 @@ class CcParams(C.Structure):
         ("radius_sq", C.c_float), ("use_distance", C.c_int), ("max_distance", C.c_float), ("use_normals", C.c_int), ("max_angle", C.c_float),
         ("angle_inclusive", C.c_int), ("use_colors", C.c_int), ("color_thresh", C.c_float), ("min_segment_size", C.c_size_t), ("max_segment_size", C.c_size_t),
     ]
+
+
+class MsParams(C.Structure):
+    _fields_ = [
+        ("kernel_radius", C.c_float), ("max_iter", C.c_size_t), ("cluster_tol", C.c_float), ("convergence_tol", C.c_float), ("kernel_kind", C.c_int),
+        ("kernel_sigma", C.c_float), ("form", C.c_int),
+    ]
+
+
+class MsStats(C.Structure):
+    _fields_ = [("form_used", C.c_int), ("est_ball", C.c_double), ("shift_ms", C.c_double), ("group_ms", C.c_double), ("passes", C.c_size_t), ("rounds", C.c_size_t)]
 
 
 _lib = None
@@ -186,6 +198,10 @@ def load():
     L.cilhip_connected_components3f.argtypes = [C.c_int, f32p, f32p, f32p, C.c_size_t, C.c_int, C.POINTER(CcParams), vp, C.c_size_t, vp, vp, vp, C.POINTER(C.c_size_t)]
     L.cilhip_connected_components_lists.argtypes = [C.c_int, C.c_size_t, vp, vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp, vp, vp,
                                                     C.POINTER(C.c_size_t)]
+    L.cilhip_ms_default_params.argtypes = [C.POINTER(MsParams)]
+    L.cilhip_ms_default_params.restype = None
+    L.cilhip_mean_shift3f.argtypes = [C.c_int, f32p, C.c_size_t, f32p, C.c_size_t, C.c_int, C.POINTER(MsParams), vp, vp, vp, vp, vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.cilhip_ms_last_stats.argtypes = [C.POINTER(MsStats)]
     L.cilhip_icp_sums_from_keys.argtypes = [vp, vp, f64p]
     L.cilhip_icp_order_keys.argtypes = [vp, vp, vp]
     L.cilhip_icp_sums_from_ordered_keys.argtypes = [vp, vp, vp, f64p]
@@ -232,7 +248,7 @@ def load():
     L.cilhip_get_slab_violation_state.argtypes = [vp, C.POINTER(C.c_int), vp]
     for name in SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
-        if name not in ("cilhip_destroy", "cilhip_last_error", "cilhip_icp_default_params", "cilhip_option_info", "cilhip_cc_default_params"):
+        if name not in ("cilhip_destroy", "cilhip_last_error", "cilhip_icp_default_params", "cilhip_option_info", "cilhip_cc_default_params", "cilhip_ms_default_params"):
             fn.restype = C.c_int
     _lib = L
     return L

@@ -1,6 +1,6 @@
-"""Python mirrors of cilantro's KMeans3f (clustering/kmeans.hpp) and ConnectedComponentExtraction3f
-(clustering/connected_component_extraction.hpp; second half of this file) on top of the C ABI (cilhip_kmeans3f,
-cilhip_connected_components3f).
+"""Python mirrors of cilantro's KMeans3f (clustering/kmeans.hpp), ConnectedComponentExtraction3f
+(clustering/connected_component_extraction.hpp; second part of this file) and MeanShift3f (clustering/mean_shift.hpp; last part) on top
+of the C ABI (cilhip_kmeans3f, cilhip_connected_components3f, cilhip_mean_shift3f).
 
     km = KMeans3f(points)
     km.cluster(initial_centroids, max_iter=100, tol=eps)      # kmeans.hpp:24-30
@@ -322,3 +322,118 @@ class ConnectedComponentExtraction3f:
 
     def getUnlabeledPointIndices(self):
         return self._members[int(self._offsets[-1]):]
+
+
+# ---- MeanShift3f (clustering/mean_shift.hpp) ------------------------------------------------------------------------------------
+# The contract is stated in include/cilantro_hip/c_api.h (cilhip_mean_shift3f) and DESIGN.md section 13.  numpy arrays in -> numpy arrays
+# out; device tensors in -> device tensors out.  There is no CPU path.
+class UnityWeightEvaluator:
+    """common_pair_evaluators.hpp:30-43"""
+
+    kind, sigma = 0, 1.0
+
+
+class IdentityWeightEvaluator(UnityWeightEvaluator):
+    """:14-27 -- the weight is the squared distance"""
+
+    kind = 1
+
+
+class RBFKernelWeightEvaluator(UnityWeightEvaluator):
+    """:46-80 -- exp(-0.5 / sigma^2 * squared distance)"""
+
+    kind = 2
+
+    def __init__(self, sigma=1.0):
+        self.sigma = float(sigma)
+
+
+def mean_shift(points, kernel_radius, max_iter, cluster_tol, convergence_tol=float(np.finfo(np.float32).eps), evaluator=None, seeds=None, form=0, device=0):
+    """cilhip_mean_shift3f -> dict(shifted[ns, 3], labels[ns], modes[k, 3], offsets[k + 1], members[ns], iterations, stats): cluster c is
+    members[offsets[c]:offsets[c + 1]]; seeds=None: every point is a seed"""
+    L = capi.load()
+    ev = evaluator if evaluator is not None else UnityWeightEvaluator()
+    p, n, mem, keep_p = _as_cloud(points)
+    sp, ns, keep_s = None, n, None
+    if seeds is not None:
+        sp, ns, smem, keep_s = _as_cloud(seeds)
+        if smem != mem:
+            raise ValueError("points and seeds must live in the same memory space")
+        if ns == 0:
+            sp = (np.zeros((1, 3), np.float32) if mem == capi.MEM_HOST else keep_s.new_zeros((1, 3)))
+            keep_s = sp
+            sp = sp.ctypes.data if mem == capi.MEM_HOST else sp.data_ptr()      # (an empty list is still a list: a non-null pointer)
+    prm = capi.MsParams()
+    L.cilhip_ms_default_params(C.byref(prm))
+    prm.kernel_radius, prm.max_iter, prm.cluster_tol, prm.convergence_tol = kernel_radius, int(max_iter), cluster_tol, convergence_tol
+    prm.kernel_kind, prm.kernel_sigma, prm.form = int(ev.kind), float(ev.sigma), int(form)
+    on_device = mem == capi.MEM_DEVICE
+    if on_device:
+        import torch
+
+        dev = keep_p.device
+        if dev.index is not None:
+            device = dev.index
+        torch.cuda.synchronize(dev)      # the call runs on a stream of its own: the inputs must be complete
+        shifted, modes = torch.empty((ns, 3), dtype=torch.float32, device=dev), torch.empty((ns, 3), dtype=torch.float32, device=dev)
+        labels, offsets, members = (torch.empty(k, dtype=torch.int32, device=dev) for k in (ns, ns + 1, ns))
+        addr = [t.data_ptr() for t in (shifted, labels, modes, offsets, members)]
+    else:
+        shifted, modes = np.empty((ns, 3), np.float32), np.empty((ns, 3), np.float32)
+        labels, offsets, members = (np.empty(k, np.uint32) for k in (ns, ns + 1, ns))
+        addr = [a.ctypes.data for a in (shifted, labels, modes, offsets, members)]
+    nc, iters = C.c_size_t(0), C.c_size_t(0)
+    rc = L.cilhip_mean_shift3f(int(device), p, n, sp, ns if seeds is not None else 0, mem, C.byref(prm), addr[0], addr[1], addr[2], addr[3], addr[4], C.byref(nc), C.byref(iters))
+    if rc != capi.OK:
+        raise capi.CilhipError(rc, "cilhip_mean_shift3f: " + L.cilhip_last_error(None).decode())
+    if ns == 0:
+        offsets[:1] = 0
+    st = capi.MsStats()
+    L.cilhip_ms_last_stats(C.byref(st))
+    stats = {"form_used": st.form_used, "est_ball": st.est_ball, "shift_ms": st.shift_ms, "group_ms": st.group_ms, "passes": st.passes, "rounds": st.rounds} if ns else {}
+    lab, off, mem_ = _cc_result([labels, offsets, members], nc.value, on_device)
+    return {"shifted": shifted, "labels": lab, "modes": modes[: nc.value], "offsets": off, "members": mem_, "iterations": int(iters.value), "stats": stats}
+
+
+class MeanShift3f:
+    """mean_shift.hpp:12-140 with the ClusteringBase accessors (clustering_base.hpp:60-97)
+
+        ms = MeanShift3f(points)
+        ms.cluster(2.0, 5000, 0.2, 1e-7, UnityWeightEvaluator())               # :118-124 -- every point is a seed
+        ms.cluster(seeds, kernel_radius, max_iter, cluster_tol, convergence_tol, evaluator)      # :38-115
+    A tree handed to the reference's second constructor is "the same points" here."""
+
+    def __init__(self, points, device=0):
+        self._points = points
+        self._device = device
+        self._r = None
+
+    def cluster(self, *args, **kw):
+        args = list(args)
+        seeds = kw.pop("seeds", None)
+        if args and not np.isscalar(args[0]):
+            seeds = args.pop(0)
+        for k, v in zip(("kernel_radius", "max_iter", "cluster_tol", "convergence_tol", "evaluator"), args):
+            kw[k] = v
+        self._r = mean_shift(self._points, seeds=seeds, device=self._device, **kw)
+        return self
+
+    def getShiftedSeeds(self):
+        return self._r["shifted"]
+
+    def getClusterModes(self):
+        return self._r["modes"]
+
+    def getNumberOfPerformedIterations(self):
+        return self._r["iterations"]
+
+    def getPointToClusterIndexMap(self):
+        return self._r["labels"]
+
+    def getNumberOfClusters(self):
+        return int(self._r["offsets"].shape[0]) - 1
+
+    def getClusterToPointIndicesMap(self):
+        """per cluster, ascending seed indices"""
+        off, mem = self._r["offsets"], self._r["members"]
+        return [mem[int(off[c]):int(off[c + 1])] for c in range(self.getNumberOfClusters())]

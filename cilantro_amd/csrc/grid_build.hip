@@ -204,7 +204,7 @@ static bool set_dims(GridDev& g, const float lo[3], const float hi[3], double ce
 }
 
 hipError_t build_grid(const float* d_xyz, const float* d_nrm, uint32_t n, hipStream_t s, GridBuildResult* out, double mean_out[3],
-                      double target_occupancy, double refined_factor) {
+                      double target_occupancy, double refined_factor, double min_cell) {
   GridDev g{};
   g.n = n; g.pts = nullptr; g.nrm = nullptr; g.pn = nullptr; g.cell_start = nullptr;
   GridStore st;      // (handed to *out on success only)
@@ -230,6 +230,8 @@ hipError_t build_grid(const float* d_xyz, const float* d_nrm, uint32_t n, hipStr
   }
   const double TARGET = target_occupancy > 0.0 ? target_occupancy : 1.0;  // points per cell for a volumetric cloud
   double cell = grid_first_cell(lo, hi, n, TARGET);
+  const bool floor_cell = min_cell > 0.0 && std::isfinite(min_cell);
+  if (floor_cell && !(cell >= min_cell)) cell = min_cell;
   if (!set_dims(g, lo, hi, cell)) return GRID_RANGE_ERROR;      // (before anything is allocated)
 
   DevBuf<uint32_t> k_in, k_out, v_in, v_out;
@@ -260,7 +262,8 @@ hipError_t build_grid(const float* d_xyz, const float* d_nrm, uint32_t n, hipStr
     const double RF = refined_factor >= 1.0 ? refined_factor : 1.0;
     if (occ <= 3.0 * TARGET * (attempt == 0 ? 1.0 : RF)) break;
     const double shrink = std::min(0.85, std::max(0.3, std::pow(2.0 * TARGET * RF / occ, 1.0 / 2.5)));
-    const double new_cell = (double)g.cell * shrink;
+    double new_cell = (double)g.cell * shrink;
+    if (floor_cell && new_cell < min_cell) new_cell = min_cell;
     GridDev probe = g;
     if (!set_dims(probe, lo, hi, new_cell)) break;
     if (probe.cell >= g.cell * 0.97f) break;  // dims / cell-count caps reached: keep the current grid

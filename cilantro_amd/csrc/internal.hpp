@@ -490,8 +490,11 @@ struct GridBuildResult {
 // Points with a non-finite coordinate keep their records at the tail of GridDev::pts (behind cell_start[n_cells]) and are in no cell.
 constexpr hipError_t GRID_RANGE_ERROR = hipErrorInvalidPitchValue;      // (a value none of build_grid's runtime calls returns)
 constexpr const char* kGridRangeMessage = "the cloud's finite coordinates span more than a single-precision grid can index (|coordinate| + 4 * extent must stay below FLT_MAX)";
+// min_cell > 0: the cell edge never goes below it, neither in the first guess nor in a refinement -- for a caller whose balls have a
+// known radius and that visits every cell of a ball (mean_shift.hip: a grid of a clustered seed set refined far below the radius would
+// make one ball millions of cells).
 hipError_t build_grid(const float* d_xyz, const float* d_nrm, uint32_t n, hipStream_t s,
-                      GridBuildResult* out, double mean_out[3], double target_occupancy, double refined_factor = 1.0);
+                      GridBuildResult* out, double mean_out[3], double target_occupancy, double refined_factor = 1.0, double min_cell = 0.0);
 // Sorts the source by the target-grid cell of T*s; writes {x,y,z,orig} records.  d_out preallocated [n].
 // Also emits the tile table of the LDS-tiled search kernel: tiles[t] = [begin,end) of <= TILE_QUERIES sorted
 // queries that share one 4x4x4-cell cube; it lives in ws (valid until the next call with it).

@@ -1,0 +1,561 @@
+// mean_shift.hip -- mean-shift clustering on the device: cilantro's MeanShift3f (clustering/mean_shift.hpp:38-124 over
+// core/common_pair_evaluators.hpp:13-79), the flow of the reference's examples/mean_shift.cpp.
+//
+// The contract (DESIGN.md section 13 has it in full; every rule cites the reference lines it restates):
+//   ball      point j is in seed i's ball iff d2_pinned(seed_i, p_j) < radius_sq (strict), radius_sq = fl(radius * radius); a point with
+//             a non-finite coordinate is in no ball                                                        mean_shift.hpp:46, :60
+//   weights   w_j = corr_weight(kind, coeff, d2_j): 1, d2_j or pinned_expf(coeff * d2_j)                   :64-66
+//   step      S = sum (double)w_j * (double)p_j, W = sum (double)w_j, new = (float)(S / W); fixed summation order, no floating-point
+//             atomics: a run is reproducible bit for bit                                                   :61-70
+//   converged d2_pinned(old, new) < fl(tol * tol); the seed takes `new` and is never examined again        :71-76
+//   empty     W == 0: the seed becomes (NaN, NaN, NaN), never converges, is never examined again; iterations = max_iter
+//   grouping  a ~ b iff d2_pinned(s_a, s_b) < fl(cluster_tol * cluster_tol); leaders = the lexicographically first maximal
+//             independent set of ~ (the reference's serial first-fit, :84-100); clusters numbered by ascending leader index;
+//             labels[i] = rank of the lowest leader ~ i; a NaN seed is a singleton
+//   modes     per cluster the f64 sum of the members' shifted seeds / size                                 :102-112
+//
+// Kernels:
+//   k_ms_shift<false>  one lane per active seed, the active list sorted once by the seeds' initial grid cell (a wave's lanes walk the
+//                      same cells): many seeds, small balls
+//   k_ms_shift<true>   one wave per active seed, the lanes stride over the x-runs of the ball's (z, y) rows, f64 partials per lane and a
+//                      fixed __shfl_down tree: few seeds whose balls hold a large part of the cloud
+//   both write the new seed and append an unconverged seed to the next active list (one integer atomicAdd per wave).
+//   k_ms_lead / k_ms_claim / k_ms_compact   one grouping round over the undecided set U: a seed of U without a lower-index ~-neighbour in
+//                      U is a leader; a wave per new leader marks every ~ seed as decided and hands it min(leader index) by an integer
+//                      atomicMin; U is compacted.  Exact; a chain of leaders needs about one round per two seeds.
+//   then ranks of the leader flags (rocPRIM scan), labels, a stable rocPRIM sort of the seed indices by label, offsets, and one wave per
+//   cluster for the mode.
+#include <hip/hip_runtime.h>
+
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+#include <algorithm>
+#include <cfloat>
+#include <chrono>
+#include <cmath>
+
+#include "../../include/cilantro_hip/c_api.h"
+#include "internal.hpp"
+#include "search_device.hpp"
+#include "stateless.hpp"
+
+namespace cilhip {
+
+namespace {
+
+constexpr int MS_THREADS = 256;
+constexpr int MS_WAVES = MS_THREADS / 64;
+constexpr uint32_t MS_UNDECIDED = 0u, MS_MEMBER = 1u, MS_LEADER = 2u;
+// form 0: one wave per seed from this estimated mean ball population on.  Measured (NOTEBOOK 2026-10-19, profiles/mean_shift_bench.json:
+// frame_1 downsampled, 15 531 seeds, time per pass wave / lane): x1.30 at an estimate of 189, x0.79 at 638 -- the crossover is near 380;
+// with fewer seeds the wave form wins earlier (1500 seeds: x0.19 at 612), so the constant errs towards the lane form only where both are fast.
+constexpr double MS_WAVE_FORM_MIN_BALL = 384.0;
+
+struct MsShift {
+  float radius_sq, conv_tol_sq;
+  int kind; float coeff;
+};
+
+thread_local cilhip_ms_stats g_ms_stats{};
+
+__device__ __forceinline__ bool ms_finite(float x, float y, float z) { return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY; }      // (false for NaN too)
+
+// the cells a ball can touch (never fewer): components.hip cc_ball_cells
+__device__ __forceinline__ void ms_ball_cells(const GridDev& g, float qx, float qy, float qz, float radius_sq, int& x0, int& x1, int& y0, int& y1, int& z0, int& z1) {
+  const float r = sqrtf(radius_sq) * 1.000001f + g.margin;
+  const float BIG = 1.0e9f;
+  x0 = max((int)floorf(fminf(fmaxf((qx - r - g.ox) * g.inv_cell, -BIG), BIG)), 0); x1 = min((int)floorf(fminf(fmaxf((qx + r - g.ox) * g.inv_cell, -BIG), BIG)), g.nx - 1);
+  y0 = max((int)floorf(fminf(fmaxf((qy - r - g.oy) * g.inv_cell, -BIG), BIG)), 0); y1 = min((int)floorf(fminf(fmaxf((qy + r - g.oy) * g.inv_cell, -BIG), BIG)), g.ny - 1);
+  z0 = max((int)floorf(fminf(fmaxf((qz - r - g.oz) * g.inv_cell, -BIG), BIG)), 0); z1 = min((int)floorf(fminf(fmaxf((qz + r - g.oz) * g.inv_cell, -BIG), BIG)), g.nz - 1);
+}
+
+__global__ __launch_bounds__(MS_THREADS) void k_ms_iota(uint32_t* __restrict__ a, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) a[i] = (uint32_t)i;
+}
+
+// points with a non-finite coordinate become (NaN, NaN, NaN): in no cell, in nobody's ball (components.hip k_cc_clean)
+__global__ __launch_bounds__(MS_THREADS) void k_ms_clean(const F3* __restrict__ xyz, size_t n, F3* __restrict__ out, unsigned int* n_finite) {
+  unsigned int cnt = 0;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    F3 p = xyz[i];
+    if (ms_finite(p.x, p.y, p.z)) ++cnt;
+    else p = F3{NAN, NAN, NAN};
+    out[i] = p;
+  }
+  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
+  if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(n_finite, cnt);
+}
+
+// the grid cell of every seed's starting position (clamped into the grid; 0 for a non-finite seed): the sort key of the first active list
+__global__ __launch_bounds__(MS_THREADS) void k_ms_seed_keys(GridDev g, const F3* __restrict__ seeds, size_t ns, uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < ns; i += (size_t)gridDim.x * blockDim.x) {
+    const F3 q = seeds[i];
+    uint32_t key = 0u;
+    if (ms_finite(q.x, q.y, q.z)) {
+      const int cx = min(max(grid_cell_coord(q.x, g.ox, g.inv_cell), 0), g.nx - 1), cy = min(max(grid_cell_coord(q.y, g.oy, g.inv_cell), 0), g.ny - 1),
+                cz = min(max(grid_cell_coord(q.z, g.oz, g.inv_cell), 0), g.nz - 1);
+      key = ((uint32_t)cz * (uint32_t)g.ny + (uint32_t)cy) * (uint32_t)g.nx + (uint32_t)cx;
+    }
+    keys[i] = key;
+    vals[i] = (uint32_t)i;
+  }
+}
+
+// One pass over the active seeds act[0 .. n_act).  WAVE: seed = wave index, otherwise seed = lane index.  have_grid == 0: every ball is
+// empty (no finite point, or radius_sq == 0).  Writes cur[i]; appends i to next[] unless it converged or became NaN.
+template <bool WAVE>
+__global__ __launch_bounds__(MS_THREADS) void k_ms_shift(GridDev g, int have_grid, MsShift m, F3* __restrict__ cur, const uint32_t* __restrict__ act, uint32_t n_act,
+                                                         uint32_t* __restrict__ next, unsigned int* cursor, unsigned int* nan_flag) {
+  const unsigned lane = threadIdx.x & 63u;
+  const size_t slot = WAVE ? (size_t)blockIdx.x * MS_WAVES + (threadIdx.x >> 6) : (size_t)blockIdx.x * MS_THREADS + threadIdx.x;
+  const bool live = slot < n_act;      // (WAVE: the same for a wave's 64 lanes)
+  const uint32_t i = live ? act[slot] : 0u;
+  F3 q{NAN, NAN, NAN};
+  if (live) q = cur[i];
+  double sx = 0.0, sy = 0.0, sz = 0.0, sw = 0.0;
+  if (live && have_grid && ms_finite(q.x, q.y, q.z)) {
+    int x0, x1, y0, y1, z0, z1;
+    ms_ball_cells(g, q.x, q.y, q.z, m.radius_sq, x0, x1, y0, y1, z0, z1);
+    if (x0 <= x1)
+      for (int z = z0; z <= z1; ++z)
+        for (int y = y0; y <= y1; ++y) {
+          const uint32_t row = ((uint32_t)z * (uint32_t)g.ny + (uint32_t)y) * (uint32_t)g.nx;
+          const uint32_t beg = g.cell_start[row + x0], end = g.cell_start[row + x1 + 1];
+          for (uint32_t k = beg + (WAVE ? lane : 0u); k < end; k += (WAVE ? 64u : 1u)) {
+            const float4 p = g.pts[k];
+            const float d2 = d2_pinned(q.x, q.y, q.z, p.x, p.y, p.z);
+            if (!(d2 < m.radius_sq)) continue;
+            const double w = (double)corr_weight(m.kind, m.coeff, d2);
+            sx += w * (double)p.x; sy += w * (double)p.y; sz += w * (double)p.z;      // (each product is exact: 24 x 24 bits)
+            sw += w;
+          }
+        }
+  }
+  if (WAVE) { sx = wave_sum(sx); sy = wave_sum(sy); sz = wave_sum(sz); sw = wave_sum(sw); }
+  bool keep = false;
+  if (live && (!WAVE || lane == 0)) {
+    const F3 nw{(float)(sx / sw), (float)(sy / sw), (float)(sz / sw)};      // sw == 0: 0 / 0 = NaN on every axis
+    cur[i] = nw;
+    if (nw.x != nw.x) *nan_flag = 1u;      // (every writer stores the same word)
+    else keep = !(d2_pinned(q.x, q.y, q.z, nw.x, nw.y, nw.z) < m.conv_tol_sq);
+  }
+  const unsigned long long b = __ballot(keep);
+  if (b) {
+    const int first = __ffsll((long long)b) - 1;
+    unsigned int base = 0;
+    if ((int)lane == first) base = atomicAdd(cursor, (unsigned int)__popcll(b));
+    base = (unsigned int)__shfl((int)base, first, 64);
+    if (keep) next[base + (unsigned int)__popcll(b & ((1ull << lane) - 1ull))] = i;
+  }
+}
+
+// ---- grouping ------------------------------------------------------------------------------------------------------------------
+// state: MS_LEADER for a non-finite seed (~ nobody: its own cluster), MS_UNDECIDED otherwise; U = the undecided seeds
+__global__ __launch_bounds__(MS_THREADS) void k_ms_group_init(const F3* __restrict__ cur, size_t ns, uint32_t* __restrict__ state, uint32_t* __restrict__ lead_of,
+                                                              uint32_t* __restrict__ U, unsigned int* cursor) {
+  const unsigned lane = threadIdx.x & 63u;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t base_i = (size_t)blockIdx.x * blockDim.x; base_i < ns; base_i += stride) {      // (wave-uniform trip count)
+    const size_t i = base_i + threadIdx.x;
+    bool und = false;
+    if (i < ns) {
+      const F3 q = cur[i];
+      und = ms_finite(q.x, q.y, q.z);
+      state[i] = und ? MS_UNDECIDED : MS_LEADER;
+      lead_of[i] = und ? NONE_U32 : (uint32_t)i;
+    }
+    const unsigned long long b = __ballot(und);
+    if (b) {
+      const int first = __ffsll((long long)b) - 1;
+      unsigned int base = 0;
+      if ((int)lane == first) base = atomicAdd(cursor, (unsigned int)__popcll(b));
+      base = (unsigned int)__shfl((int)base, first, 64);
+      if (und) U[base + (unsigned int)__popcll(b & ((1ull << lane) - 1ull))] = (uint32_t)i;
+    }
+  }
+}
+
+// a seed of U with no lower-index ~-neighbour in U becomes a leader of this round.  state[] is only READ here (k_ms_claim writes it in a
+// launch of its own), so every lane sees U as it was when the round began.  A cell's records are in ascending index (build_grid sorts
+// stably by cell), so a cell is left at the first index >= i: the lowest seed of a collapsed mode looks at one record of its cell, every
+// other one stops at the first record that is still undecided and close.
+__global__ __launch_bounds__(MS_THREADS) void k_ms_lead(GridDev g, float tol_sq, const F3* __restrict__ cur, const uint32_t* __restrict__ state, const uint32_t* __restrict__ U,
+                                                        uint32_t n_u, uint32_t* __restrict__ new_leaders, unsigned int* cursor) {
+  const unsigned lane = threadIdx.x & 63u;
+  const size_t slot = (size_t)blockIdx.x * MS_THREADS + threadIdx.x;
+  bool leader = false;
+  uint32_t i = 0u;
+  if (slot < n_u) {
+    i = U[slot];
+    leader = true;
+    const F3 q = cur[i];
+    int x0, x1, y0, y1, z0, z1;
+    ms_ball_cells(g, q.x, q.y, q.z, tol_sq, x0, x1, y0, y1, z0, z1);
+    for (int z = z0; z <= z1 && leader; ++z)
+      for (int y = y0; y <= y1 && leader; ++y) {
+        const uint32_t row = ((uint32_t)z * (uint32_t)g.ny + (uint32_t)y) * (uint32_t)g.nx;
+        for (int x = x0; x <= x1 && leader; ++x) {
+          const uint32_t beg = g.cell_start[row + x], end = g.cell_start[row + x + 1];
+          for (uint32_t k = beg; k < end; ++k) {
+            const float4 p = g.pts[k];
+            const uint32_t j = __float_as_uint(p.w);
+            if (j >= i) break;
+            if (state[j] != MS_UNDECIDED) continue;
+            if (d2_pinned(q.x, q.y, q.z, p.x, p.y, p.z) < tol_sq) { leader = false; break; }
+          }
+        }
+      }
+  }
+  const unsigned long long b = __ballot(leader);
+  if (b) {
+    const int first = __ffsll((long long)b) - 1;
+    unsigned int base = 0;
+    if ((int)lane == first) base = atomicAdd(cursor, (unsigned int)__popcll(b));
+    base = (unsigned int)__shfl((int)base, first, 64);
+    if (leader) new_leaders[base + (unsigned int)__popcll(b & ((1ull << lane) - 1ull))] = i;
+  }
+}
+
+// one wave per new leader L: every seed ~ L that is still undecided is decided now (a member), and every seed ~ L, decided in this round
+// or an earlier one, keeps the LOWEST leader index it has met (a leader elected later can have the lower index).  Two leaders are never ~
+// each other, so no leader's word is touched.  *n_leaders is the count k_ms_lead left.
+__global__ __launch_bounds__(MS_THREADS) void k_ms_claim(GridDev g, float tol_sq, const F3* __restrict__ cur, uint32_t* state, uint32_t* lead_of,
+                                                         const uint32_t* __restrict__ new_leaders, const unsigned int* n_leaders) {
+  const unsigned lane = threadIdx.x & 63u;
+  const uint32_t n_l = *n_leaders;
+  const size_t n_waves = (size_t)gridDim.x * MS_WAVES;
+  for (size_t w = (size_t)blockIdx.x * MS_WAVES + (threadIdx.x >> 6); w < n_l; w += n_waves) {
+    const uint32_t L = new_leaders[w];
+    const F3 q = cur[L];
+    if (lane == 0) { state[L] = MS_LEADER; lead_of[L] = L; }
+    int x0, x1, y0, y1, z0, z1;
+    ms_ball_cells(g, q.x, q.y, q.z, tol_sq, x0, x1, y0, y1, z0, z1);
+    if (x0 > x1) continue;
+    for (int z = z0; z <= z1; ++z)
+      for (int y = y0; y <= y1; ++y) {
+        const uint32_t row = ((uint32_t)z * (uint32_t)g.ny + (uint32_t)y) * (uint32_t)g.nx;
+        const uint32_t beg = g.cell_start[row + x0], end = g.cell_start[row + x1 + 1];
+        for (uint32_t k = beg + lane; k < end; k += 64u) {
+          const float4 p = g.pts[k];
+          const uint32_t j = __float_as_uint(p.w);
+          if (j == L || !(d2_pinned(q.x, q.y, q.z, p.x, p.y, p.z) < tol_sq)) continue;
+          if (state[j] == MS_UNDECIDED) state[j] = MS_MEMBER;      // (several leaders may store the same word)
+          atomicMin(lead_of + j, L);
+        }
+      }
+  }
+}
+
+__global__ __launch_bounds__(MS_THREADS) void k_ms_compact(const uint32_t* __restrict__ state, const uint32_t* __restrict__ U, uint32_t n_u, uint32_t* __restrict__ next,
+                                                           unsigned int* cursor) {
+  const unsigned lane = threadIdx.x & 63u;
+  const size_t slot = (size_t)blockIdx.x * MS_THREADS + threadIdx.x;
+  uint32_t i = 0u;
+  bool keep = false;
+  if (slot < n_u) { i = U[slot]; keep = state[i] == MS_UNDECIDED; }
+  const unsigned long long b = __ballot(keep);
+  if (b) {
+    const int first = __ffsll((long long)b) - 1;
+    unsigned int base = 0;
+    if ((int)lane == first) base = atomicAdd(cursor, (unsigned int)__popcll(b));
+    base = (unsigned int)__shfl((int)base, first, 64);
+    if (keep) next[base + (unsigned int)__popcll(b & ((1ull << lane) - 1ull))] = i;
+  }
+}
+
+__global__ __launch_bounds__(MS_THREADS) void k_ms_flags(const uint32_t* __restrict__ state, size_t ns, uint32_t* __restrict__ flags) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < ns; i += (size_t)gridDim.x * blockDim.x) flags[i] = state[i] == MS_LEADER ? 1u : 0u;
+}
+// rank[] = exclusive sum of the leader flags: a leader's rank is its cluster's number
+__global__ __launch_bounds__(MS_THREADS) void k_ms_labels(const uint32_t* __restrict__ lead_of, const uint32_t* __restrict__ rank, size_t ns, uint32_t* __restrict__ labels) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < ns; i += (size_t)gridDim.x * blockDim.x) labels[i] = rank[lead_of[i]];
+}
+// offsets[k] = first sorted position of label k (components.hip k_cc_offsets); offsets[n_clusters] is preset to ns
+__global__ __launch_bounds__(MS_THREADS) void k_ms_offsets(const uint32_t* __restrict__ labels_sorted, size_t ns, uint32_t* __restrict__ offsets) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < ns; i += (size_t)gridDim.x * blockDim.x) {
+    const uint32_t l = labels_sorted[i];
+    if (i == 0 || labels_sorted[i - 1] != l) offsets[l] = (uint32_t)i;
+  }
+}
+// one wave per cluster: lane l sums members l, l + 64, ... in f64, a fixed shuffle tree adds the 64 partials, lane 0 divides by the size
+__global__ __launch_bounds__(MS_THREADS) void k_ms_modes(const F3* __restrict__ cur, const uint32_t* __restrict__ members, const uint32_t* __restrict__ offsets, uint32_t n_clusters,
+                                                         F3* __restrict__ modes) {
+  const unsigned lane = threadIdx.x & 63u;
+  const size_t n_waves = (size_t)gridDim.x * MS_WAVES;
+  for (size_t c = (size_t)blockIdx.x * MS_WAVES + (threadIdx.x >> 6); c < n_clusters; c += n_waves) {
+    const uint32_t beg = offsets[c], end = offsets[c + 1];
+    double sx = 0.0, sy = 0.0, sz = 0.0;
+    for (uint32_t k = beg + lane; k < end; k += 64u) {
+      const F3 s = cur[members[k]];
+      sx += (double)s.x; sy += (double)s.y; sz += (double)s.z;
+    }
+    sx = wave_sum(sx); sy = wave_sum(sy); sz = wave_sum(sz);
+    const double size = (double)(end - beg);
+    if (lane == 0) modes[c] = F3{(float)(sx / size), (float)(sy / size), (float)(sz / size)};
+  }
+}
+
+inline int ms_blocks(size_t n) { return (int)std::min<size_t>((n + MS_THREADS - 1) / MS_THREADS, 2048) + (n == 0); }
+inline unsigned ms_launch(size_t slots, size_t per_block) { return (unsigned)((slots + per_block - 1) / per_block); }
+unsigned ms_bits(uint32_t v) {      // bits that hold 0 .. v
+  unsigned b = 1;
+  while (b < 32 && (1ull << b) <= (unsigned long long)v) ++b;
+  return b;
+}
+double ms_now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+#define MS_CK(call) ST_CK("mean_shift", call)
+// build_grid's own refusal is not a HIP failure
+#define MS_GRID(call) do { const hipError_t ms_e_ = (call); if (ms_e_ == GRID_RANGE_ERROR) return st_fail(CILHIP_ERR_UNSUPPORTED, "mean_shift", kGridRangeMessage); \
+                           if (ms_e_ != hipSuccess) return st_fail(CILHIP_ERR_HIP, "mean_shift", #call, hipGetErrorString(ms_e_)); } while (0)
+
+struct MsArgs {
+  int device, mem;
+  const float* points; size_t n;
+  const float* seeds; size_t ns;      // seeds: the caller's array, or `points` (every point is a seed)
+  cilhip_ms_params prm;
+  float *shifted, *modes;
+  uint32_t *labels, *offsets, *members;
+  size_t *n_clusters, *iterations;
+};
+
+int ms_run(const MsArgs& a) {
+  DevPool pool;
+  GridBuildResult pgrid{}, sgrid{};      // over the points; over the shifted seeds
+  StreamGuard st;      // (declared last: the stream is drained and destroyed before anything is freed)
+  if (const int open = st_open("mean_shift", a.device)) return open;
+  MS_CK(st.create());
+  hipStream_t s = st.s;
+  const size_t n = a.n, ns = a.ns;
+  const bool host = a.mem == CILHIP_MEM_HOST;
+  const dim3 block(MS_THREADS);
+  cilhip_ms_stats stats{};
+
+  // ---- the points' grid ----
+  const float radius_sq = a.prm.kernel_radius * a.prm.kernel_radius;
+  int have_grid = 0;
+  unsigned int* d_words = nullptr;      // [0] n_finite / U cursor, [1] nan flag, [2], [3] list cursors
+  MS_CK(pool.bytes(&d_words, 4 * sizeof(unsigned int)));
+  MS_CK(hipMemsetAsync(d_words, 0, 4 * sizeof(unsigned int), s));
+  unsigned int n_finite = 0;
+  if (n && radius_sq > 0.0f && a.prm.max_iter > 0) {
+    const F3* d_pts = nullptr;
+    F3* clean = nullptr;
+    MS_CK(st_stage(pool, s, a.mem, a.points, n, &d_pts));
+    MS_CK(pool.bytes(&clean, n * sizeof(F3)));
+    hipLaunchKernelGGL(k_ms_clean, dim3(ms_blocks(n)), block, 0, s, d_pts, n, clean, d_words);
+    MS_CK(hipMemcpyAsync(&n_finite, d_words, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+    MS_CK(hipStreamSynchronize(s));
+    if (n_finite) {
+      double mean[3];
+      // no cell below an eighth of the radius: a ball is at most 17 x 17 rows however dense the cloud
+      MS_GRID(build_grid(reinterpret_cast<const float*>(clean), nullptr, (uint32_t)n, s, &pgrid, mean, 2.0, 1.0, 0.125 * std::sqrt((double)radius_sq)));
+      have_grid = 1;
+    }
+  }
+
+  // ---- the seeds: shifted in place ----
+  F3* cur = reinterpret_cast<F3*>(a.shifted);
+  if (host) {
+    MS_CK(pool.bytes(&cur, ns * sizeof(F3)));
+    MS_CK(hipMemcpyAsync(cur, a.seeds, ns * sizeof(F3), hipMemcpyHostToDevice, s));
+  } else {
+    MS_CK(hipMemcpyAsync(cur, a.seeds, ns * sizeof(F3), hipMemcpyDeviceToDevice, s));
+  }
+  uint32_t *list_a = nullptr, *list_b = nullptr, *keys = nullptr, *keys_sorted = nullptr;
+  MS_CK(pool.bytes(&list_a, ns * sizeof(uint32_t)));
+  MS_CK(pool.bytes(&list_b, ns * sizeof(uint32_t)));
+  MS_CK(pool.bytes(&keys, ns * sizeof(uint32_t)));
+  MS_CK(pool.bytes(&keys_sorted, ns * sizeof(uint32_t)));
+
+  // ---- the shift passes ----
+  size_t it = 0;
+  const double t_shift0 = ms_now_ms();
+  if (a.prm.max_iter > 0) {
+    bool wave = a.prm.form == 2;
+    if (have_grid) {
+      // mean ball population: the density the points see around them (own-cell population / cell volume) times the ball's volume
+      const double cell = (double)pgrid.grid.cell, r = std::sqrt((double)radius_sq);
+      stats.est_ball = std::min((double)n_finite, pgrid.avg_occupancy / (cell * cell * cell) * (4.18879020478639 * r * r * r));
+      if (a.prm.form == 0) wave = stats.est_ball >= MS_WAVE_FORM_MIN_BALL;
+      // the first active list: the seeds in the order of their starting cells (a wave's lanes then walk the same cells)
+      hipLaunchKernelGGL(k_ms_seed_keys, dim3(ms_blocks(ns)), block, 0, s, pgrid.grid, (const F3*)cur, ns, keys, list_b);
+      size_t tmp_bytes = 0;
+      void* tmp = nullptr;
+      const unsigned bits = ms_bits((uint32_t)pgrid.n_cells);
+      MS_CK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys, keys_sorted, list_b, list_a, ns, 0u, bits, s));
+      MS_CK(pool.bytes(&tmp, tmp_bytes));
+      MS_CK(rocprim::radix_sort_pairs(tmp, tmp_bytes, keys, keys_sorted, list_b, list_a, ns, 0u, bits, s));
+    } else {
+      hipLaunchKernelGGL(k_ms_iota, dim3(ms_blocks(ns)), block, 0, s, list_a, ns);
+    }
+    stats.form_used = wave ? 2 : 1;
+    const MsShift m{radius_sq, a.prm.convergence_tol * a.prm.convergence_tol, a.prm.kernel_kind,
+                    a.prm.kernel_kind == CW_RBF ? -0.5f / (a.prm.kernel_sigma * a.prm.kernel_sigma) : 0.0f};
+    unsigned int n_act = (unsigned int)ns;
+    while (it < a.prm.max_iter && n_act > 0) {
+      MS_CK(hipMemsetAsync(d_words + 2, 0, sizeof(unsigned int), s));
+      if (wave) hipLaunchKernelGGL(k_ms_shift<true>, dim3(ms_launch(n_act, MS_WAVES)), block, 0, s, pgrid.grid, have_grid, m, cur, (const uint32_t*)list_a, (uint32_t)n_act, list_b, d_words + 2, d_words + 1);
+      else hipLaunchKernelGGL(k_ms_shift<false>, dim3(ms_launch(n_act, MS_THREADS)), block, 0, s, pgrid.grid, have_grid, m, cur, (const uint32_t*)list_a, (uint32_t)n_act, list_b, d_words + 2, d_words + 1);
+      MS_CK(hipGetLastError());
+      ++it;
+      MS_CK(hipMemcpyAsync(&n_act, d_words + 2, sizeof(unsigned int), hipMemcpyDeviceToHost, s));      // the pass's one readback
+      MS_CK(hipStreamSynchronize(s));
+      std::swap(list_a, list_b);
+    }
+    stats.passes = it;
+    if (it < a.prm.max_iter) {      // nobody is active: with a NaN seed the reference would idle through its remaining passes
+      unsigned int nan_any = 0;
+      MS_CK(hipMemcpyAsync(&nan_any, d_words + 1, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+      MS_CK(hipStreamSynchronize(s));
+      if (nan_any) it = a.prm.max_iter;
+    }
+  }
+  stats.shift_ms = ms_now_ms() - t_shift0;
+
+  // ---- grouping ----
+  const double t_group0 = ms_now_ms();
+  const float tol_sq = a.prm.cluster_tol * a.prm.cluster_tol;
+  uint32_t *state = keys, *lead_of = keys_sorted, *new_leaders = nullptr;      // (the sort keys are done with)
+  MS_CK(pool.bytes(&new_leaders, ns * sizeof(uint32_t)));
+  MS_CK(hipMemsetAsync(d_words, 0, sizeof(unsigned int), s));
+  hipLaunchKernelGGL(k_ms_group_init, dim3(ms_blocks(ns)), block, 0, s, (const F3*)cur, ns, state, lead_of, list_a, d_words);
+  unsigned int n_u = 0;
+  MS_CK(hipMemcpyAsync(&n_u, d_words, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+  MS_CK(hipStreamSynchronize(s));
+  size_t rounds = 0;
+  if (n_u) {
+    double mean[3];
+    // no cell below the tolerance: k_ms_lead visits every cell of a seed's ball, and a collapsed seed set would otherwise be refined to
+    // cells a 10^4-th of it (NOTEBOOK 2026-10-19: the grouping of the example's 1500 collapsed seeds took 7.3 s that way)
+    MS_GRID(build_grid(reinterpret_cast<const float*>(cur), nullptr, (uint32_t)ns, s, &sgrid, mean, 2.0, 1.0, std::sqrt((double)tol_sq)));
+    while (n_u > 0) {
+      MS_CK(hipMemsetAsync(d_words + 2, 0, 2 * sizeof(unsigned int), s));
+      hipLaunchKernelGGL(k_ms_lead, dim3(ms_launch(n_u, MS_THREADS)), block, 0, s, sgrid.grid, tol_sq, (const F3*)cur, (const uint32_t*)state, (const uint32_t*)list_a, (uint32_t)n_u,
+                         new_leaders, d_words + 2);
+      hipLaunchKernelGGL(k_ms_claim, dim3(std::min<unsigned>(ms_launch(n_u, MS_WAVES), 4096u)), block, 0, s, sgrid.grid, tol_sq, (const F3*)cur, state, lead_of,
+                         (const uint32_t*)new_leaders, (const unsigned int*)(d_words + 2));
+      hipLaunchKernelGGL(k_ms_compact, dim3(ms_launch(n_u, MS_THREADS)), block, 0, s, (const uint32_t*)state, (const uint32_t*)list_a, (uint32_t)n_u, list_b, d_words + 3);
+      MS_CK(hipGetLastError());
+      MS_CK(hipMemcpyAsync(&n_u, d_words + 3, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+      MS_CK(hipStreamSynchronize(s));
+      std::swap(list_a, list_b);
+      if (++rounds > ns) return st_fail(CILHIP_ERR_HIP, "mean_shift", "the grouping did not finish");      // (every round decides the lowest undecided seed: never met)
+    }
+  }
+  // cluster numbers = ranks of the leaders
+  uint32_t *flags = list_a, *rank = list_b;      // (the lists are done with)
+  hipLaunchKernelGGL(k_ms_flags, dim3(ms_blocks(ns)), block, 0, s, (const uint32_t*)state, ns, flags);
+  {
+    size_t tmp_bytes = 0;
+    void* tmp = nullptr;
+    MS_CK(rocprim::exclusive_scan(nullptr, tmp_bytes, flags, rank, 0u, ns, rocprim::plus<uint32_t>(), s));
+    MS_CK(pool.bytes(&tmp, tmp_bytes));
+    MS_CK(rocprim::exclusive_scan(tmp, tmp_bytes, flags, rank, 0u, ns, rocprim::plus<uint32_t>(), s));
+  }
+  uint32_t last[2] = {0, 0};
+  MS_CK(hipMemcpyAsync(&last[0], rank + (ns - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  MS_CK(hipMemcpyAsync(&last[1], flags + (ns - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  MS_CK(hipStreamSynchronize(s));
+  const uint32_t n_clusters = last[0] + last[1];
+  uint32_t* d_labels = a.labels;
+  if (host) MS_CK(pool.bytes(&d_labels, ns * sizeof(uint32_t)));
+  hipLaunchKernelGGL(k_ms_labels, dim3(ms_blocks(ns)), block, 0, s, (const uint32_t*)lead_of, (const uint32_t*)rank, ns, d_labels);
+  MS_CK(hipGetLastError());
+  stats.group_ms = ms_now_ms() - t_group0;      // (host clock up to the last synchronisation; the label kernel is in flight)
+  stats.rounds = rounds;
+
+  // ---- member lists and modes ----
+  if (a.offsets || a.members || a.modes) {
+    uint32_t *iota = flags, *lab_sorted = new_leaders, *d_members = a.members, *d_offsets = a.offsets;
+    F3* d_modes = reinterpret_cast<F3*>(a.modes);
+    if (host || !d_members) MS_CK(pool.bytes(&d_members, ns * sizeof(uint32_t)));
+    if (host || !d_offsets) MS_CK(pool.bytes(&d_offsets, ((size_t)n_clusters + 1) * sizeof(uint32_t)));
+    hipLaunchKernelGGL(k_ms_iota, dim3(ms_blocks(ns)), block, 0, s, iota, ns);
+    size_t tmp_bytes = 0;
+    void* tmp = nullptr;
+    const unsigned bits = ms_bits(n_clusters);
+    MS_CK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_labels, lab_sorted, iota, d_members, ns, 0u, bits, s));
+    MS_CK(pool.bytes(&tmp, tmp_bytes));
+    MS_CK(rocprim::radix_sort_pairs(tmp, tmp_bytes, d_labels, lab_sorted, iota, d_members, ns, 0u, bits, s));
+    const uint32_t ns32 = (uint32_t)ns;
+    MS_CK(hipMemcpyAsync(d_offsets + n_clusters, &ns32, sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_ms_offsets, dim3(ms_blocks(ns)), block, 0, s, (const uint32_t*)lab_sorted, ns, d_offsets);
+    if (a.modes) {
+      if (host) MS_CK(pool.bytes(&d_modes, (size_t)n_clusters * sizeof(F3)));
+      hipLaunchKernelGGL(k_ms_modes, dim3(std::min<unsigned>(ms_launch(n_clusters, MS_WAVES), 4096u)), block, 0, s, (const F3*)cur, (const uint32_t*)d_members, (const uint32_t*)d_offsets,
+                         n_clusters, d_modes);
+    }
+    MS_CK(hipGetLastError());
+    if (host && a.offsets) MS_CK(hipMemcpyAsync(a.offsets, d_offsets, ((size_t)n_clusters + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (host && a.members) MS_CK(hipMemcpyAsync(a.members, d_members, ns * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (host && a.modes) MS_CK(hipMemcpyAsync(a.modes, d_modes, (size_t)n_clusters * sizeof(F3), hipMemcpyDeviceToHost, s));
+  }
+  if (host) {
+    MS_CK(hipMemcpyAsync(a.shifted, cur, ns * sizeof(F3), hipMemcpyDeviceToHost, s));
+    MS_CK(hipMemcpyAsync(a.labels, d_labels, ns * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  }
+  MS_CK(hipStreamSynchronize(s));
+  *a.n_clusters = n_clusters;
+  *a.iterations = it;
+  g_ms_stats = stats;
+  return CILHIP_OK;
+}
+
+int ms_refuse(const char* why) { return st_fail(CILHIP_ERR_INVALID, "mean_shift", why); }
+bool ms_tolerance(float v) { return std::isfinite(v) && v >= 0.0f; }
+
+}  // namespace
+
+}  // namespace cilhip
+
+extern "C" void cilhip_ms_default_params(cilhip_ms_params* p) {
+  if (!p) return;
+  *p = cilhip_ms_params{};
+  p->convergence_tol = FLT_EPSILON;
+  p->kernel_sigma = 1.0f;
+}
+
+extern "C" int cilhip_ms_last_stats(cilhip_ms_stats* out) {
+  if (!out) return CILHIP_ERR_INVALID;
+  *out = cilhip::g_ms_stats;
+  return CILHIP_OK;
+}
+
+extern "C" int cilhip_mean_shift3f(int device, const float* points, size_t n, const float* seeds_or_null, size_t n_seeds, int mem, const cilhip_ms_params* params,
+                                   float* shifted_seeds_out, uint32_t* labels_out, float* modes_out_or_null, uint32_t* offsets_out_or_null, uint32_t* members_out_or_null,
+                                   size_t* n_clusters_out, size_t* iterations_out) {
+  using namespace cilhip;
+  if (!params) return ms_refuse("params is null");
+  if (!n_clusters_out) return ms_refuse("n_clusters_out is null");
+  if (!iterations_out) return ms_refuse("iterations_out is null");
+  if ((unsigned long long)n >= (1ull << 32)) return ms_refuse("n must be below 2^32");
+  if ((unsigned long long)n_seeds >= (1ull << 32)) return ms_refuse("n_seeds must be below 2^32");
+  if (mem != CILHIP_MEM_HOST && mem != CILHIP_MEM_DEVICE) return ms_refuse("mem: CILHIP_MEM_HOST or CILHIP_MEM_DEVICE");
+  if (n && !points) return ms_refuse("points is null");
+  if (n_seeds && !seeds_or_null) return ms_refuse("n_seeds > 0 without a seed array");
+  if (!ms_tolerance(params->kernel_radius)) return ms_refuse("kernel_radius must be finite and not negative");
+  if (!ms_tolerance(params->cluster_tol)) return ms_refuse("cluster_tol must be finite and not negative");
+  if (!ms_tolerance(params->convergence_tol)) return ms_refuse("convergence_tol must be finite and not negative");
+  if (params->kernel_kind != CW_UNITY && params->kernel_kind != CW_IDENTITY && params->kernel_kind != CW_RBF) return ms_refuse("kernel_kind: 0 (Unity), 1 (Identity) or 2 (RBF)");
+  if (params->kernel_kind == CW_RBF && !(std::isfinite(params->kernel_sigma) && params->kernel_sigma > 0.0f)) return ms_refuse("kernel_sigma must be finite and positive");
+  if (params->form < 0 || params->form > 2) return ms_refuse("form: 0 (chosen by the code), 1 (a lane per seed) or 2 (a wave per seed)");
+  const size_t ns = seeds_or_null ? n_seeds : n;
+  if (ns && !shifted_seeds_out) return ms_refuse("shifted_seeds_out is null");
+  if (ns && !labels_out) return ms_refuse("labels_out is null");
+  st_clear();
+  if (ns == 0) {      // (without touching a device)
+    *n_clusters_out = 0;
+    *iterations_out = 0;
+    if (offsets_out_or_null && mem == CILHIP_MEM_HOST) offsets_out_or_null[0] = 0;
+    return CILHIP_OK;
+  }
+  const MsArgs a{device, mem, points, n, seeds_or_null ? seeds_or_null : points, ns, *params, shifted_seeds_out, modes_out_or_null, labels_out, offsets_out_or_null,
+                 members_out_or_null, n_clusters_out, iterations_out};
+  try {
+    return ms_run(a);
+  } catch (...) {      // (out of host memory: never across the C boundary)
+    return st_fail(CILHIP_ERR_HIP, "mean_shift", "out of host memory");
+  }
+}

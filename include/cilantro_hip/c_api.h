@@ -547,6 +547,64 @@ int cilhip_connected_components_lists(int device, size_t n, const uint64_t* offs
                                       const uint32_t* seeds_or_null, size_t n_seeds, uint32_t* labels_out, uint32_t* offsets_out_or_null,
                                       uint32_t* members_out_or_null, size_t* n_segments_out);
 
+/* ---- mean-shift clustering ---------------------------------------------------------------------
+ * cilantro's MeanShift3f (clustering/mean_shift.hpp:38-124; float, 3-D, L2), the flow of examples/mean_shift.cpp.  DESIGN.md section 13
+ * is the long form; the rules, each with the reference line it restates:
+ *   1 ball      point j is in seed i's ball iff d2(seed_i, p_j) < radius_sq, strict (:60, kd_tree.hpp:251-257); d2 is the engine's pinned
+ *               ((dx*dx)+(dy*dy))+(dz*dz) in f32, radius_sq = kernel_radius * kernel_radius formed once in f32 (:46).  A point with a
+ *               non-finite coordinate is in no ball.
+ *   2 weights   w_j = 1 (kernel_kind 0, UnityWeightEvaluator), d2_j (1, IdentityWeightEvaluator) or exp(coeff * d2_j) (2, RBFKernelWeightEvaluator,
+ *               coeff = -0.5f / (sigma * sigma) in f32, the product and the exponential in the pinned f32 arithmetic of the ICP weight
+ *               evaluators) -- common_pair_evaluators.hpp:13-79, mean_shift.hpp:64-66.
+ *   3 step      S = sum (double)w_j * (double)p_j per axis (every product exact), W = sum (double)w_j, new = (float)(S / W) (:61-70).  The sums
+ *               run in a fixed order that the input alone decides; no floating-point atomics: two runs agree bit for bit.  Deviation: the
+ *               reference sums in f32 in ascending-distance order (equal distances as std::sort leaves them) and multiplies by
+ *               1.0f / total_weight.
+ *   4 converged a seed has converged when d2(old, new) < convergence_tol * convergence_tol (f32 product); it still takes `new` and is never
+ *               examined again (:71-76).  *iterations_out counts the passes performed, the one in which the last seed converged included
+ *               (:79-81); max_iter = 0 performs none: shifted = seeds.
+ *   5 empty     an empty or zero-weight ball gives 0 / 0: the seed becomes (NaN, NaN, NaN) -- the reference's 0 * inf.  It never converges
+ *               and finds nothing again, so once no other seed is active the remaining passes are not run and *iterations_out = max_iter,
+ *               the reference's count.  A seed that comes in with a non-finite coordinate behaves so from pass 1.
+ *   6 grouping  a ~ b iff d2(s_a, s_b) < cluster_tol * cluster_tol (f32 product).  Leaders: i is one iff no leader j < i has j ~ i -- the
+ *               reference's serial first-fit (:84-100).  Clusters are numbered by ascending leader index (its creation order, not a size
+ *               order); labels_out[i] = the lowest-numbered cluster whose leader is ~ i; a NaN seed is ~ nobody: a cluster of its own with
+ *               a NaN mode.  offsets_out / members_out: the clusters as CSR lists, members in ascending index.
+ *   7 modes     per cluster and axis the f64 sum of the members' shifted seeds (member k of the list in partial sum k mod 64, the 64 partials
+ *               added by a fixed tree), then (float)(sum / size).  Deviation: the reference adds in f32 along the list and multiplies by the
+ *               reciprocal (:102-112).
+ * seeds_or_null == NULL: every point is a seed (:118-124; n_seeds is ignored).  mem says where points, seeds and the five output arrays
+ * live; n_clusters_out and iterations_out are host words.  Sizes that always suffice: shifted 3 n_seeds, labels n_seeds, modes 3 n_seeds,
+ * offsets n_seeds + 1, members n_seeds.  form: which shift kernel runs -- 0: the code decides from the estimated mean ball population,
+ * 1: one lane per seed, 2: one wave per seed (the results of 1 and 2 differ only by the summation order of rule 3).
+ * CILHIP_ERR_INVALID, before the device is opened, nothing written, cilhip_last_error(NULL) naming the rule: NULL points with n > 0; n_seeds
+ * > 0 with NULL seeds; n or n_seeds >= 2^32; kernel_radius, cluster_tol or convergence_tol not finite or negative; an RBF sigma not finite
+ * and positive; unknown kernel_kind, form or mem; NULL params, n_clusters_out, iterations_out, or (with at least one seed) NULL
+ * shifted_seeds_out / labels_out.  No seed at all: CILHIP_OK, zero clusters, zero iterations, no device needed.  n == 0 with seeds is
+ * legal: every ball is empty (rule 5).
+ * Not built: 2-D, double and dynamic-dimension variants, other distance adaptors, a caller's functor as kernel evaluator, a caller-owned
+ * tree (MeanShift(const SearchTree&) is "the same points"), a sharded run. */
+typedef struct cilhip_ms_params {
+  float kernel_radius; size_t max_iter; float cluster_tol; float convergence_tol;
+  int kernel_kind;      /* 0 Unity, 1 Identity, 2 RBF over the squared distance */
+  float kernel_sigma;   /* RBF only */
+  int form;             /* 0 chosen by the code, 1 one lane per seed, 2 one wave per seed */
+} cilhip_ms_params;
+/* Unity kernel, convergence_tol = FLT_EPSILON (:41), kernel_sigma = 1, form 0; radius, max_iter and cluster_tol 0: the caller sets them */
+void cilhip_ms_default_params(cilhip_ms_params* params);
+int cilhip_mean_shift3f(int device, const float* points, size_t n, const float* seeds_or_null, size_t n_seeds, int mem, const cilhip_ms_params* params,
+                        float* shifted_seeds_out, uint32_t* labels_out, float* modes_out_or_null, uint32_t* offsets_out_or_null,
+                        uint32_t* members_out_or_null, size_t* n_clusters_out, size_t* iterations_out);
+/* What the calling thread's last successful cilhip_mean_shift3f did (bench tool, tests): the shift form that ran, the ball population the
+ * choice was made from, host wall time of the shift passes and of the grouping (each pass and round ends in a synchronisation), the
+ * passes that ran (rule 5: *iterations_out can be larger) and the grouping rounds. */
+typedef struct cilhip_ms_stats {
+  int form_used;
+  double est_ball, shift_ms, group_ms;
+  size_t passes, rounds;
+} cilhip_ms_stats;
+int cilhip_ms_last_stats(cilhip_ms_stats* out);
+
 /* ---- introspection (bench / tests) ----------------------------------------------------------- */
 typedef struct {
   int nx, ny, nz;        /* grid dims */

@@ -1,6 +1,9 @@
-// cilantro_hip/clustering.hpp -- C++ host-side mirror of cilantro's connected-component segmentation, header-only on top of the C ABI
-// (c_api.h: cilhip_connected_components3f, which states the contract):
+// cilantro_hip/clustering.hpp -- C++ host-side mirrors of cilantro's connected-component segmentation and mean-shift clustering,
+// header-only on top of the C ABI (c_api.h: cilhip_connected_components3f and cilhip_mean_shift3f, which state the contracts; DESIGN.md
+// sections 11 and 13):
 //
+//   MeanShift3f                                clustering/mean_shift.hpp:12-140 (the end of this file)
+//   Unity / Identity / RBFKernel WeightEvaluator               core/common_pair_evaluators.hpp:13-79
 //   ConnectedComponentExtraction3f             clustering/connected_component_extraction.hpp:368-428 (segment :394-422)
 //   the ClusteringBase accessors               clustering/clustering_base.hpp:60-97
 //   RadiusNeighborhoodSpecification<float>     core/nearest_neighbors.hpp (the radius is a SQUARED distance)
@@ -180,6 +183,89 @@ private:
 
   ConstPointsView points_;
   int device_;
+  ClusterToPointIndicesMap cluster_to_point_indices_map_;
+  PointToClusterIndexMap point_to_cluster_index_map_;
+};
+
+// ---- MeanShift3f -----------------------------------------------------------------------------------------------------------------
+// The three kernel evaluators the device knows (a description, evaluated on the device; a caller's functor is not supported).
+template <typename ScalarT = float, typename WeightT = ScalarT>
+struct UnityWeightEvaluator {      // :30-43
+  int kind() const { return 0; }
+  float sigma() const { return 1.0f; }
+};
+template <typename ScalarT = float, typename WeightT = ScalarT>
+struct IdentityWeightEvaluator {      // :14-27
+  int kind() const { return 1; }
+  float sigma() const { return 1.0f; }
+};
+template <typename ScalarT = float, typename WeightT = ScalarT>
+class RBFKernelWeightEvaluator {      // :46-80
+public:
+  explicit RBFKernelWeightEvaluator(ScalarT sigma = (ScalarT)1) : sigma_((float)sigma) {}
+  int kind() const { return 2; }
+  float sigma() const { return sigma_; }
+private:
+  float sigma_;
+};
+
+template <typename PointIndexT = size_t, typename ClusterIndexT = size_t>
+class MeanShift3f {
+public:
+  typedef std::vector<std::vector<PointIndexT>> ClusterToPointIndicesMap;
+  typedef std::vector<ClusterIndexT> PointToClusterIndexMap;
+
+  // (max_leaf_size: the reference's kd-tree parameter, accepted and unused)
+  explicit MeanShift3f(const ConstPointsView& points, size_t max_leaf_size = 10, int device = 0) : points_(points), device_(device) { (void)max_leaf_size; }
+
+  // :38-115 -- given seeds
+  template <class KernelEvaluatorT = UnityWeightEvaluator<float>>
+  MeanShift3f& cluster(const ConstPointsView& seeds, float kernel_radius, size_t max_iter, float cluster_tol, float convergence_tol = std::numeric_limits<float>::epsilon(),
+                       const KernelEvaluatorT& evaluator = KernelEvaluatorT()) {
+    return run(&seeds, kernel_radius, max_iter, cluster_tol, convergence_tol, evaluator.kind(), evaluator.sigma());
+  }
+  // :118-124 -- every point is a seed
+  template <class KernelEvaluatorT = UnityWeightEvaluator<float>>
+  MeanShift3f& cluster(float kernel_radius, size_t max_iter, float cluster_tol, float convergence_tol = std::numeric_limits<float>::epsilon(),
+                       const KernelEvaluatorT& evaluator = KernelEvaluatorT()) {
+    return run(nullptr, kernel_radius, max_iter, cluster_tol, convergence_tol, evaluator.kind(), evaluator.sigma());
+  }
+
+  const std::vector<float>& getShiftedSeeds() const { return shifted_seeds_; }      // xyz per seed
+  const std::vector<float>& getClusterModes() const { return cluster_modes_; }      // xyz per cluster
+  size_t getNumberOfPerformedIterations() const { return iteration_count_; }
+  const ClusterToPointIndicesMap& getClusterToPointIndicesMap() const { return cluster_to_point_indices_map_; }
+  const PointToClusterIndexMap& getPointToClusterIndexMap() const { return point_to_cluster_index_map_; }
+  size_t getNumberOfClusters() const { return cluster_to_point_indices_map_.size(); }
+  size_t getNumberOfPoints() const { return point_to_cluster_index_map_.size(); }
+
+private:
+  MeanShift3f& run(const ConstPointsView* seeds, float kernel_radius, size_t max_iter, float cluster_tol, float convergence_tol, int kind, float sigma) {
+    const size_t ns = seeds ? seeds->cols() : points_.cols();
+    cilhip_ms_params prm;
+    cilhip_ms_default_params(&prm);
+    prm.kernel_radius = kernel_radius; prm.max_iter = max_iter; prm.cluster_tol = cluster_tol; prm.convergence_tol = convergence_tol;
+    prm.kernel_kind = kind; prm.kernel_sigma = sigma;
+    std::vector<float> shifted(3 * ns + 3), modes(3 * ns + 3), no_seed(3);
+    std::vector<uint32_t> labels(ns + 1), offsets(ns + 1), members(ns + 1);
+    size_t nc = 0, iters = 0;
+    const float* sp = seeds ? (seeds->cols() ? seeds->data() : no_seed.data()) : nullptr;      // (an empty list is still a list)
+    const int rc = cilhip_mean_shift3f(device_, points_.data(), points_.cols(), sp, seeds ? ns : 0, CILHIP_MEM_HOST, &prm, shifted.data(), labels.data(), modes.data(),
+                                       offsets.data(), members.data(), &nc, &iters);
+    if (rc != CILHIP_OK) throw std::runtime_error("cilhip_mean_shift3f failed (rc " + std::to_string(rc) + "): " + cilhip_last_error(nullptr));
+    shifted_seeds_.assign(shifted.begin(), shifted.begin() + 3 * ns);
+    cluster_modes_.assign(modes.begin(), modes.begin() + 3 * nc);
+    iteration_count_ = iters;
+    cluster_to_point_indices_map_.assign(nc, std::vector<PointIndexT>());
+    for (size_t k = 0; k < nc; ++k) cluster_to_point_indices_map_[k].assign(members.begin() + offsets[k], members.begin() + offsets[k + 1]);
+    point_to_cluster_index_map_.assign(labels.begin(), labels.begin() + ns);
+    return *this;
+  }
+
+  ConstPointsView points_;
+  int device_;
+  size_t iteration_count_ = 0;
+  std::vector<float> shifted_seeds_, cluster_modes_;
   ClusterToPointIndicesMap cluster_to_point_indices_map_;
   PointToClusterIndexMap point_to_cluster_index_map_;
 };
