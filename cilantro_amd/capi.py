@@ -29,6 +29,7 @@ SYMBOLS = [
     "cilhip_plane_ransac3f", "cilhip_plane_score3f", "cilhip_plane_fit3f", "cilhip_transform_ransac3f", "cilhip_transform_score3f", "cilhip_transform_fit3f", "cilhip_knn3f", "cilhip_knn_set_tie_rule", "cilhip_normals_knn3f", "cilhip_normals_radius3f", "cilhip_radius_search3f", "cilhip_grid_downsample3f",
     "cilhip_cc_default_params", "cilhip_connected_components3f", "cilhip_connected_components_lists",
     "cilhip_ms_default_params", "cilhip_mean_shift3f", "cilhip_ms_last_stats",
+    "cilhip_depth_default_converter", "cilhip_depth_image_to_points3f", "cilhip_points_to_depth_image3f", "cilhip_points_to_index_map3f", "cilhip_set_projection",
 ]
 
 
@@ -100,6 +101,12 @@ class MsParams(C.Structure):
 class MsStats(C.Structure):
     _fields_ = [("form_used", C.c_int), ("est_ball", C.c_double), ("shift_ms", C.c_double), ("group_ms", C.c_double), ("passes", C.c_size_t), ("rounds", C.c_size_t)]
 
+
+class DepthConverter(C.Structure):
+    _fields_ = [("raw_type", C.c_int), ("scale", C.c_float), ("truncated", C.c_int), ("max_depth", C.c_float)]
+
+
+DEPTH_U16, DEPTH_F32 = 0, 1
 
 _lib = None
 
@@ -202,6 +209,13 @@ def load():
     L.cilhip_ms_default_params.restype = None
     L.cilhip_mean_shift3f.argtypes = [C.c_int, f32p, C.c_size_t, f32p, C.c_size_t, C.c_int, C.POINTER(MsParams), vp, vp, vp, vp, vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.cilhip_ms_last_stats.argtypes = [C.POINTER(MsStats)]
+    L.cilhip_depth_default_converter.argtypes = [C.POINTER(DepthConverter)]
+    L.cilhip_depth_default_converter.restype = None
+    L.cilhip_depth_image_to_points3f.argtypes = [C.c_int, vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(DepthConverter), f32p, f32p, C.c_int, C.c_int, f32p, f32p, f32p,
+                                                 C.c_size_t, C.POINTER(C.c_size_t)]
+    L.cilhip_points_to_depth_image3f.argtypes = [C.c_int, f32p, f32p, C.c_size_t, C.c_int, f32p, f32p, C.POINTER(DepthConverter), C.c_size_t, C.c_size_t, vp, vp]
+    L.cilhip_points_to_index_map3f.argtypes = [C.c_int, f32p, C.c_size_t, C.c_int, f32p, f32p, C.c_size_t, C.c_size_t, vp]
+    L.cilhip_set_projection.argtypes = [vp, f32p, C.c_size_t, C.c_size_t, f32p]
     L.cilhip_icp_sums_from_keys.argtypes = [vp, vp, f64p]
     L.cilhip_icp_order_keys.argtypes = [vp, vp, vp]
     L.cilhip_icp_sums_from_ordered_keys.argtypes = [vp, vp, vp, f64p]
@@ -248,7 +262,7 @@ def load():
     L.cilhip_get_slab_violation_state.argtypes = [vp, C.POINTER(C.c_int), vp]
     for name in SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
-        if name not in ("cilhip_destroy", "cilhip_last_error", "cilhip_icp_default_params", "cilhip_option_info", "cilhip_cc_default_params", "cilhip_ms_default_params"):
+        if name not in ("cilhip_destroy", "cilhip_last_error", "cilhip_icp_default_params", "cilhip_option_info", "cilhip_cc_default_params", "cilhip_ms_default_params", "cilhip_depth_default_converter"):
             fn.restype = C.c_int
     _lib = L
     return L

@@ -981,8 +981,54 @@ int cilhip::run_pair_search(cilhip_ctx* c, const IterArgs& a, float max_sq, cons
   return CILHIP_OK;
 }
 
+const char* cilhip::proj_conflict(const cilhip_ctx* c) {
+  if (c->search_dir != 0 || c->reciprocal) return "projective search: SECOND_TO_FIRST only (no other search direction, no reciprocity)";
+  if (c->one_to_one) return "projective search: the one-to-one filter is not available";
+  if (feat6(c)) return "projective search: feature adaptors are not available";
+  if (c->weight_fn) return "projective search: the pair-weight callback is not available";
+  if (c->index_offset || c->partial_target || c->guard_axis >= 0) return "projective search: not available on slab or target shards";
+  return nullptr;
+}
+
+int cilhip::ensure_proj_map(cilhip_ctx* c) {
+  if (c->d_proj_map) return CILHIP_OK;
+  const size_t npix = (size_t)c->proj.w * c->proj.h;
+  CK(c, c->d_proj_keys.alloc(npix));
+  CK(c, c->d_proj_map.alloc(npix));
+  const hipError_t e = launch_proj_map(c->grid.pts, c->grid.n, c->proj, c->d_proj_keys, c->d_proj_map, c->stream);
+  if (e != hipSuccess) { c->d_proj_map.reset(); c->err = std::string("projective index map: ") + hipGetErrorString(e); return CILHIP_ERR_HIP; }
+  return CILHIP_OK;
+}
+
+int cilhip_set_projection(cilhip_ctx* c, const float* K, size_t w, size_t h, const float* E) {
+  if (!c) return CILHIP_ERR_INVALID;
+  if (K) {
+    for (int i = 0; i < 9; ++i) if (!std::isfinite(K[i])) return fail(c, CILHIP_ERR_INVALID, "set_projection: the intrinsic matrix has a non-finite entry");
+    if (w == 0 || h == 0 || w >= 0xFFFFFFF0ull || h >= 0xFFFFFFF0ull || (unsigned long long)w * h >= 0xFFFFFFF0ull)
+      return fail(c, CILHIP_ERR_INVALID, "set_projection: w * h must be positive and below 2^32 - 16");
+  }
+  CK(c, hipSetDevice(c->device));
+  CK(c, hipStreamSynchronize(c->stream));      // (a search may still be reading the map)
+  c->d_proj_map.reset(); c->d_proj_keys.reset();
+  drop_matches(c);
+  c->proj_on = K != nullptr;
+  if (!K) return CILHIP_OK;
+  ProjDev& p = c->proj;
+  p = ProjDev{};
+  p.has_cam = E != nullptr;
+  if (E)      // to_cam = (R^T, -R^T t), formed in f64 from the f32 entries, rounded once (rule P1)
+    for (int r = 0; r < 3; ++r) {
+      for (int k = 0; k < 3; ++k) p.L[3 * r + k] = E[k + 4 * r];
+      p.t[r] = (float)-((double)E[0 + 4 * r] * (double)E[12] + ((double)E[1 + 4 * r] * (double)E[13] + (double)E[2 + 4 * r] * (double)E[14]));
+    }
+  for (int j = 0; j < 3; ++j) { p.k0[j] = K[0 + 3 * j]; p.k1[j] = K[1 + 3 * j]; }
+  p.w = (uint32_t)w; p.h = (uint32_t)h;
+  return CILHIP_OK;
+}
+
 int cilhip_find_correspondences(cilhip_ctx* c, const float T[16], float max_sq, size_t* n_found) {
   if (!c || !T) return CILHIP_ERR_INVALID;
+  if (c->proj_on) { if (const char* why = proj_conflict(c)) return fail(c, CILHIP_ERR_UNSUPPORTED, why); }
   CK(c, hipSetDevice(c->device));
   int rc = ensure_sorted(c, T);
   if (rc) return rc;
@@ -1013,7 +1059,11 @@ int cilhip_find_correspondences(cilhip_ctx* c, const float T[16], float max_sq, 
     return CILHIP_OK;
   }
   c->have_pairs = false;
-  if (c->ns) {
+  if (c->proj_on) {
+    rc = ensure_proj_map(c);
+    if (rc) return rc;
+    launch_proj_search(c->d_src_sorted, c->ns, c->d_state, c->grid.pts, c->proj, c->d_proj_map, max_sq, c->d_nn_pos, c->d_nn_d2, c->stream);
+  } else if (c->ns) {
     rc = launch_search(c, a);
     if (rc) return rc;
     bool again = false;      // (tie_rule 2: the search met ties and there were no order tables yet -- they exist now: once more)
@@ -1542,6 +1592,7 @@ int cilhip_icp_run_two_sets(cilhip_ctx* cp, float max_sq_point, cilhip_ctx* cl, 
   if (p->metric != CILHIP_METRIC_COMBINED) return fail(cp, CILHIP_ERR_INVALID, "icp_run (two sets): the combined metric is what takes two correspondence sets");
   if (cp->transform_mode != 0 || cl->transform_mode != 0) return fail(cp, CILHIP_ERR_UNSUPPORTED, "icp_run (two sets): rigid transforms");
   if (cp->search_dir != 0 || cl->search_dir != 0) return fail(cp, CILHIP_ERR_UNSUPPORTED, "icp_run (two sets): SECOND_TO_FIRST engines");
+  if (cp->proj_on || cl->proj_on) return fail(cp, CILHIP_ERR_UNSUPPORTED, "projective search: cilhip_icp_run_two_sets is not available");
   float T[16];
   memcpy(T, T0 ? T0 : kIdentity16, sizeof(T));
   memcpy(out->T, T, sizeof(T));

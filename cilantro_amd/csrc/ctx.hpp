@@ -32,6 +32,8 @@ struct TargetBufs {
   DevBuf<float4> d_dst_rgb_sorted;
   DevBuf<uint32_t> d_rev_pos;     // list-free loops of FIRST_TO_SECOND / BOTH: reverse matches by target position
   DevBuf<float> d_rev_d2;
+  DevBuf<unsigned long long> d_proj_keys;  // [w * h] scratch of the index map build
+  DevBuf<uint32_t> d_proj_map;    // [w * h] the target's index map under the current projection: sorted positions (null: not built; dropped with the target and by cilhip_set_projection)
 };
 // ... of the SOURCE's own grid (FIRST_TO_SECOND / BOTH) and what is laid out in its order
 struct SrcGridBufs {
@@ -202,6 +204,10 @@ struct cilhip_ctx : CtxStream, TargetBufs, SourceBufs {
   bool have_pairs = false;        // `pairs` holds the result of the last find_correspondences
   DevBuf<IcpState> d_state_id; // a state holding the identity transform (the reverse search transforms nothing)
 
+  // cilhip_set_projection: while proj_on, searches and cilhip_icp_run associate through the target's index map (projective.hip)
+  bool proj_on = false;
+  ProjDev proj{};
+
   // sharded-run state
   cilhip_icp_params run_prm{};
   bool run_active = false;
@@ -314,6 +320,8 @@ TieDev tie_dev_rev(const cilhip_ctx* c);
 int tie_prepare(cilhip_ctx* c, const char* what);
 int tie_check_pending(cilhip_ctx* c, bool* again);
 int apply_filters(cilhip_ctx* c);
+const char* proj_conflict(const cilhip_ctx* c);      // what, of the context's settings, a projection does not run with (null: nothing)
+int ensure_proj_map(cilhip_ctx* c);
 IterArgs make_iter_args(cilhip_ctx* c, float max_sq);
 int launch_search(cilhip_ctx* c, const IterArgs& a, int lanes = -1 /* -1: the option's own value when it names a lane count */);
 int run_pair_search(cilhip_ctx* c, const IterArgs& a, float max_sq, const float T_host[16]);

@@ -320,6 +320,48 @@ static int run_pair_list_loop(cilhip_ctx* c, RunSetup& r) {
   return finish_run(c, r, false, true);      // c->pairs: the last iteration's list
 }
 
+// A projection is set (cilhip_set_projection): host-paced like run_pair_list_loop -- the projective search over the target's index map
+// leaves its matches in nn_pos, the post-filter and the streaming accumulation run over them as after any search-only form, the
+// epilogue solves, and the host reads the loop state after every iteration.  No tiled or warm forms.
+static int run_projective_loop(cilhip_ctx* c, RunSetup& r) {
+  const cilhip_icp_params* p = r.p;
+  IterArgs& a = r.a;
+  SolveArgs& sa = r.sa;
+  CK(c, hipEventRecord(r.e_beg, c->stream));
+  int rc = ensure_proj_map(c);
+  if (rc) return rc;
+  c->rec_valid = false; c->lb_fresh = false;
+  c->last_fused_iters = c->last_two_pass_iters = c->last_warm_iters = 0;
+  c->iter_form.clear(); c->trace_form.clear(); c->timed_iter.clear();
+  for (int k = 0; k < 5; ++k) { c->form_ms[k] = 0.0; c->form_n[k] = 0; }
+  for (size_t it = 0; it < p->max_iter; ++it) {
+    if (c->ns) {
+      launch_proj_search(c->d_src_sorted, c->ns, c->d_state, c->grid.pts, c->proj, c->d_proj_map, p->max_sq_dist, c->d_nn_pos, c->d_nn_d2, c->stream);
+      rc = apply_filters(c);
+      if (rc) return rc;
+    }
+    ++c->last_two_pass_iters;
+    for (size_t st = 0; st < r.opt_steps; ++st) {
+      a.skip_if_inner_done = (st > 0);
+      sa.gn_last_step = (st + 1 == r.opt_steps);
+      if (c->ns) {
+        launch_iter(a, r.im, false, false, r.nb, c->stream);
+        launch_reduce_and_solve(c->d_partials, r.nb, c->d_stage, nullptr, sa, c->stream);
+      } else {
+        launch_solve(sa, c->stream);
+      }
+    }
+    rc = read_state(c, r.out);
+    if (rc) return rc;
+    if (r.out->last_delta_norm < p->conv_tol) break;   // the device sets `done` by the same test (icp_base.hpp:83)
+  }
+  c->last_acc_ms = 0.0;
+  // the last iteration's matches are in nn_pos, with the values its search formed (a post-filtered set is searched again on demand, as after the grid loop)
+  rc = finish_run(c, r, !filters_active(c), false);
+  if (rc == CILHIP_OK && c->have_nn) c->d2_stale = false;
+  return rc;
+}
+
 // FIRST_TO_SECOND / BOTH: which of the two loops
 static int run_other_directions(cilhip_ctx* c, RunSetup& r) {
   if (c->index_offset) return fail(c, CILHIP_ERR_UNSUPPORTED, "search directions other than SECOND_TO_FIRST are not available on target shards");
@@ -587,6 +629,10 @@ static int run_forward_loop(cilhip_ctx* c, RunSetup& r) {
 }
 
 static int icp_run_once(cilhip_ctx* c, const cilhip_icp_params* p, const float* T0, cilhip_icp_result* out) {
+  if (c->proj_on) {
+    if (const char* why = proj_conflict(c)) return fail(c, CILHIP_ERR_UNSUPPORTED, why);
+    if (c->transform_mode == 1) return fail(c, CILHIP_ERR_UNSUPPORTED, "projective search: the affine loop is not available");
+  }
   if (c->weight_fn && p->metric == CILHIP_METRIC_COMBINED && c->transform_mode == 0) {
     // a caller's own weight evaluators run on the host: the reference's loop step by step (search, estimate over the stored set with
     // the callback's weights, rotation() polish + compose), the combiner's loop with one engine in both roles
@@ -642,6 +688,7 @@ static int icp_run_once(cilhip_ctx* c, const cilhip_icp_params* p, const float* 
     r.sa.reduced = c->d_sums;
   }
   r.e_beg = event_at(c->ev, 0); r.e_end = event_at(c->ev, 1);
+  if (c->proj_on) return run_projective_loop(c, r);
   return c->search_dir != 0 ? run_other_directions(c, r) : run_forward_loop(c, r);
 }
 
@@ -663,6 +710,7 @@ int cilhip_icp_run(cilhip_ctx* c, const cilhip_icp_params* p, const float* T0, c
 
 int cilhip_icp_begin(cilhip_ctx* c, const cilhip_icp_params* p, const float* T0, const float* gmean) {
   if (!c || !p) return CILHIP_ERR_INVALID;
+  if (c->proj_on) return fail(c, CILHIP_ERR_UNSUPPORTED, "projective search: sharded runs (cilhip_icp_begin ..., cilhip_multi_*) are not available");
   CK(c, hipSetDevice(c->device));
   if (p->metric == CILHIP_METRIC_COMBINED && p->max_opt_iter != 1) return fail(c, CILHIP_ERR_UNSUPPORTED, "sharded runs support max_opt_iter == 1");
   if (filters_active(c)) return fail(c, CILHIP_ERR_UNSUPPORTED, "inlier_fraction / one_to_one are global filters: not available in sharded runs");

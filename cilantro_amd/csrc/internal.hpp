@@ -417,6 +417,13 @@ void launch_tie_tables_by_position(const float4* dst_sorted, uint32_t n, const u
 void launch_count_ties(const GridDev& g, const float4* src_sorted, uint32_t ns, const float T[16], float max_sq, unsigned long long* out, hipStream_t s);
 // squared distances of the stored matches under T, formed again with the search's pinned arithmetic (bit-identical to what the
 // search compared): the ICP loop does not store them, a caller of getCorrespondences() after estimate() reads them
+// projective association (projective.hip): the camera of cilhip_set_projection as the kernels take it -- to_cam = inverse extrinsics (rows of
+// the linear part, translation; has_cam = 0: the identity), rows 0 and 1 of K, the image size
+struct ProjDev { float L[9]; float t[3]; int has_cam; float k0[3], k1[3]; uint32_t w, h; };
+// map[pixel] = SORTED position of the target point rules P1-P4 name (ties in depth by ORIGINAL index), NONE_U32: empty; keys: w * h words of scratch
+hipError_t launch_proj_map(const float4* pts, uint32_t n, const ProjDev& p, unsigned long long* keys, uint32_t* map, hipStream_t s);
+void launch_proj_search(const float4* src, uint32_t ns, const IcpState* state, const float4* pts, const ProjDev& p, const uint32_t* map, float max_sq, uint32_t* nn_pos,
+                        float* nn_d2, hipStream_t s);
 void launch_fill_d2(const float4* src_sorted, const float4* dst_sorted, const uint32_t* nn_pos, const float T[16], uint32_t ns, float* nn_d2, hipStream_t s);
 void launch_residuals(const IterArgs& a, int metric, float w_p2p, float w_p2pl, float* out, hipStream_t s);
 int iter_num_blocks(uint32_t ns);

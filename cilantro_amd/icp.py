@@ -173,6 +173,12 @@ class Context:
                                                      C.byref(n) if count else None))
         return n.value if count else None
 
+    def set_projection(self, K, w=640, h=480, extrinsics=None):
+        """cilhip_set_projection: K 3x3 (None: back to the grid search), the image size, extrinsics 4x4 camera pose or None"""
+        k = None if K is None else np.ascontiguousarray(np.asarray(K, np.float32).reshape(3, 3).T).reshape(9)
+        e = None if extrinsics is None else _T_to_abi(extrinsics)
+        self._ck(self._L.cilhip_set_projection(self._h, None if k is None else k.ctypes.data, int(w), int(h), None if e is None else e.ctypes.data))
+
     def tie_count(self, T, max_sq_dist):
         """queries whose nearest target point (under T, within the radius) is not unique in the pinned f32 distance: where the
         engine's lowest-index rule and the reference's first-met rule may name different correspondences (cilhip_get_tie_count)"""
@@ -467,6 +473,47 @@ class CorrespondenceSearchHIP:
         self.require_reciprocality_ = False
         self.one_to_one_ = False
         self._corr = None
+        # correspondence_search_projective.hpp:33-40 (in force on the projective engine only)
+        self._projective = False
+        self.projection_intrinsics_ = np.array([[528, 0, 320], [0, 528, 240], [0, 0, 1]], np.float32)
+        self.projection_image_width_, self.projection_image_height_ = 640, 480
+        self.projection_extrinsics_ = np.eye(4, dtype=np.float32)
+
+    def _push_projection(self):
+        if self._projective:
+            E = self.projection_extrinsics_
+            self._ctx.set_projection(self.projection_intrinsics_, self.projection_image_width_, self.projection_image_height_,
+                                     None if np.array_equal(E, np.eye(4, dtype=np.float32)) else E)
+        self._corr = None
+        return self
+
+    def getProjectionIntrinsicMatrix(self):
+        return self.projection_intrinsics_
+
+    def setProjectionIntrinsicMatrix(self, K):
+        self.projection_intrinsics_ = np.asarray(K, np.float32).reshape(3, 3).copy()
+        return self._push_projection()
+
+    def getProjectionImageWidth(self):
+        return self.projection_image_width_
+
+    def setProjectionImageWidth(self, w):
+        self.projection_image_width_ = int(w)
+        return self._push_projection()
+
+    def getProjectionImageHeight(self):
+        return self.projection_image_height_
+
+    def setProjectionImageHeight(self, h):
+        self.projection_image_height_ = int(h)
+        return self._push_projection()
+
+    def getProjectionExtrinsicMatrix(self):
+        return self.projection_extrinsics_
+
+    def setProjectionExtrinsicMatrix(self, E):
+        self.projection_extrinsics_ = np.asarray(E, np.float32).reshape(4, 4).copy()
+        return self._push_projection()
 
     def findCorrespondences(self, tform=None):
         T = np.eye(4, dtype=np.float32) if tform is None else tform
@@ -804,6 +851,18 @@ class SimpleCombinedMetricRigidICP3f(_IterativeClosestPointBase):
     def getResiduals(self):
         return self._ctx.compute_residuals(1, float(self.point_to_point_weight_), float(self.point_to_plane_weight_),
                                            self.transform_)
+
+
+class SimpleCombinedMetricRigidProjectiveICP3f(SimpleCombinedMetricRigidICP3f):
+    """registration/icp_common_instances.hpp:208-225, :269-270: the combined-metric rigid ICP over CorrespondenceSearchProjective
+    (correspondence_search/correspondence_search_projective.hpp): the target is associated through its index map under the engine's
+    projection (defaults 528 / 320 / 240, 640 x 480, identity extrinsics)."""
+
+    def __init__(self, dst_points, dst_normals, src_points, device=0, stream=None):
+        super().__init__(dst_points, dst_normals, src_points, None, device, stream)
+        eng = self.correspondenceSearchEngine()
+        eng._projective = True
+        eng._push_projection()
 
 
 class CorrespondenceSearchCombinedMetricCombiner:

@@ -140,6 +140,17 @@ int cilhip_share_target(cilhip_ctx* ctx, cilhip_ctx* from);
  * for the grid over the source that search directions FIRST_TO_SECOND / BOTH build. */
 int cilhip_find_correspondences(cilhip_ctx* ctx, const float T[16], float max_sq_dist,
                                 size_t* n_found_or_null);
+/* Projective association (correspondence_search/correspondence_search_projective.hpp:156-209; DESIGN.md section 14.4, rules S1-S3).
+ * K: float[9] column-major intrinsics, w x h the image, extrinsics: float[16] column-major camera pose (camera to world) or NULL.
+ * While a projection is set, cilhip_find_correspondences and cilhip_icp_run (SECOND_TO_FIRST) associate through the target's index
+ * map (cilhip_points_to_index_map3f's rules under these extrinsics; built lazily, once per target and projection; dropped by
+ * cilhip_set_target, cilhip_share_target and this call): per source point q = T s, projected like a map point, matched to the map's
+ * point j at its pixel iff |q - p_j|^2 = dx^2 + (dy^2 + dz^2) < max_sq_dist (strict).  Everything that reads "the last search" works
+ * on the result.  K == NULL: back to the grid search.  Refused with CILHIP_ERR_UNSUPPORTED while a projection is set: search
+ * directions other than SECOND_TO_FIRST, reciprocity, one-to-one, feature adaptors, the pair-weight callback, sharded runs
+ * (cilhip_icp_begin ..., cilhip_multi_*, slab and target shards), cilhip_icp_run_two_sets and the affine loop.
+ * cilhip_compute_residuals is unaffected.  CILHIP_ERR_INVALID: NULL ctx, non-finite K, w * h == 0 or >= 2^32 - 16. */
+int cilhip_set_projection(cilhip_ctx* ctx, const float* K_or_null, size_t w, size_t h, const float* extrinsics_or_null);
 /* Per-source raw result of the last search, in ORIGINAL source order: nn_idx[i] = dst index or
  * 0xFFFFFFFF (none), nn_d2[i] = squared distance (undefined when none).  Either may be NULL.
  * "The last search" includes the one of the last executed iteration of cilhip_icp_run: like the reference's engine, which
@@ -604,6 +615,58 @@ typedef struct cilhip_ms_stats {
   size_t passes, rounds;
 } cilhip_ms_stats;
 int cilhip_ms_last_stats(cilhip_ms_stats* out);
+
+/* ---- depth images <-> points ------------------------------------------------------------------------------------ */
+/* core/image_point_cloud_conversions.hpp: DepthValueConverter / TruncatedDepthValueConverter (:7-51), the eight
+ * depthImageToPoints[Normals] / RGBDImagesToPoints[Normals]Colors overloads (:53-695), pointsToDepthImage /
+ * pointsColorsToRGBDImages (:697-863) and pointsToIndexMap (:865-934), for float.  DESIGN.md section 14 is the long form
+ * (rules D1-D8, P1-P5); dot3(a, b) = a0 b0 + (a1 b1 + a2 b2) and the point transform (L_r0 x + (L_r1 y + L_r2 z)) + t_r are
+ * the engine's pinned ones, every product and sum rounded to f32, no FMA.
+ * Intrinsics K: float[9], column-major (Eigen::Matrix3f::data()).  Extrinsics: float[16], column-major rigid transform
+ * (camera to world), or NULL for the identity.  mem says where ALL arrays of a call live.  Images are row-major, pixel k = y * w + x;
+ * an rgb image has 3 bytes per pixel.
+ * The converter: metric z = (1.0f / scale) * (float)raw, truncated: z < max_depth ? z : 0; back: raw = (RawT)(scale * z),
+ * truncated: 0 unless z < max_depth.  raw_type says what the depth image holds. */
+enum { CILHIP_DEPTH_U16 = 0, CILHIP_DEPTH_F32 = 1 };
+typedef struct cilhip_depth_converter {
+  int raw_type;     /* CILHIP_DEPTH_U16 | CILHIP_DEPTH_F32 */
+  float scale;      /* raw units per metric unit (1000: millimetres) */
+  int truncated;    /* 0: DepthValueConverter, 1: TruncatedDepthValueConverter */
+  float max_depth;
+} cilhip_depth_converter;
+/* U16, scale 1, not truncated, max_depth FLT_MAX */
+void cilhip_depth_default_converter(cilhip_depth_converter* conv);
+/* Depth (and rgb) image -> points (, normals) (, colours).  Camera-frame point of pixel (x, y): Kinv * (z x, z y, z), Kinv the
+ * inverse of K formed in f64 and rounded once.  Without normals a pixel gives a row iff its point's z is > 0; with
+ * want_normals iff it is an interior pixel whose own and four neighbouring points' z are > 0 (the normal:
+ * normalized(cross(P[k+w] - P[k-w], P[k+1] - P[k-1]))).  keep_invalid: all w * h rows, normals NaN where the rule gives none.
+ * Rows are in ascending pixel index.  Extrinsics are applied last (points: E * P, normals: linear(E) * n).
+ * colour = (1.0f / 255.0f) * (float)byte.  Outputs hold `capacity` rows, *n_out = the number of rows; all outputs NULL and
+ * capacity == 0: only *n_out is set; capacity < *n_out: CILHIP_ERR_INVALID, *n_out set, nothing written; capacity = w * h always
+ * suffices.  normals_out is written with want_normals, rgb_out with an rgb image.
+ * CILHIP_ERR_INVALID, before the device is opened, nothing written, cilhip_last_error(NULL) naming the rule: NULL n_out / conv / K /
+ * depth (w * h > 0); unknown mem or raw_type; scale not finite and positive; truncated with a NaN max_depth; w * h >= 2^32 - 16;
+ * K not finite or singular; capacity > 0 with xyz_out NULL, with want_normals and normals_out NULL, or with rgb and rgb_out NULL.
+ * w * h == 0: CILHIP_OK, *n_out = 0, no device needed. */
+int cilhip_depth_image_to_points3f(int device, const void* depth, const unsigned char* rgb_or_null, size_t w, size_t h, int mem,
+                                   const cilhip_depth_converter* conv, const float* K, const float* extrinsics_or_null, int keep_invalid,
+                                   int want_normals, float* xyz_out, float* normals_out, float* rgb_out, size_t capacity, size_t* n_out);
+/* Points (and colours, 3 floats per point) -> depth (and rgb) image of w x h pixels.  c = to_cam * p with to_cam the inverse of
+ * the extrinsics, (R^T, -R^T t) formed in f64 and rounded once (no extrinsics: c = p).  A point takes part iff c_z > 0 and both
+ * projections u = (1.0f / c_z) * dot3(K_row0, c), v likewise, are finite; its pixel is (llround(u), llround(v)) -- ties away
+ * from zero -- if that lies inside the image.  raw = (RawT)(scale * c_z), truncated toward zero (U16: a product that is NaN or
+ * >= 65536 skips the point); a point contributes iff raw > 0.  A pixel holds the smallest raw value that landed on it, 0 if
+ * none; its rgb is (uchar)(255.0f * colour) -- truncated, saturated to [0, 255], NaN -> 0 -- of the lowest-index point among
+ * those with that value.  depth_out: w * h values of conv->raw_type; rgb_out: 3 w h bytes, written when colours are given.
+ * CILHIP_ERR_INVALID as above, and for n >= 2^32 - 16, NULL xyz with n > 0, NULL depth_out, colours without rgb_out.
+ * w * h == 0: CILHIP_OK, no device needed; n == 0 with host arrays: the empty images, no device needed. */
+int cilhip_points_to_depth_image3f(int device, const float* xyz, const float* rgb_or_null, size_t n, int mem, const float* extrinsics_or_null,
+                                   const float* K, const cilhip_depth_converter* conv, size_t w, size_t h, void* depth_out,
+                                   unsigned char* rgb_out_or_null);
+/* Points -> index map: index_out[pixel] = the point with the smallest c_z among those that project to the pixel (projection as
+ * above), equal c_z: the lowest index -- the reference's loop run serially (:889, strict <); 0xFFFFFFFF: no point. */
+int cilhip_points_to_index_map3f(int device, const float* xyz, size_t n, int mem, const float* extrinsics_or_null, const float* K, size_t w,
+                                 size_t h, uint32_t* index_out);
 
 /* ---- introspection (bench / tests) ----------------------------------------------------------- */
 typedef struct {

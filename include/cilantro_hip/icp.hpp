@@ -245,10 +245,35 @@ public:
     return *this;
   }
 
+  // correspondence_search_projective.hpp:33-40, :211-259: the projection of the projective engine (SimpleCombinedMetricRigidProjectiveICP3f;
+  // on the kd-tree engines the values are kept and not used).  Intrinsics: 9 floats, column-major (Eigen::Matrix3f::data()).
+  const float* getProjectionIntrinsicMatrix() const { return proj_K_; }
+  CorrespondenceSearchHIP& setProjectionIntrinsicMatrix(const float* K) { std::memcpy(proj_K_, K, sizeof(proj_K_)); return pushProjection_(); }
+  size_t getProjectionImageWidth() const { return proj_w_; }
+  CorrespondenceSearchHIP& setProjectionImageWidth(size_t w) { proj_w_ = w; return pushProjection_(); }
+  size_t getProjectionImageHeight() const { return proj_h_; }
+  CorrespondenceSearchHIP& setProjectionImageHeight(size_t h) { proj_h_ = h; return pushProjection_(); }
+  const RigidTransform3f& getProjectionExtrinsicMatrix() const { return proj_E_; }
+  CorrespondenceSearchHIP& setProjectionExtrinsicMatrix(const RigidTransform3f& E) { proj_E_ = E; return pushProjection_(); }
+  void enableProjection_() { projective_ = true; pushProjection_(); }  // internal: the projective ICP class
+
   void setSourceCount_(size_t n) { capacity_ += n; }  // internal: result capacity (called with both cloud sizes)
   cilhip_ctx* context() const { return ctx_; }        // (extension)
 
 private:
+  CorrespondenceSearchHIP& pushProjection_() {
+    if (projective_) {
+      const RigidTransform3f id;
+      const bool identity = std::memcmp(proj_E_.m, id.m, sizeof(id.m)) == 0;
+      internal::check(ctx_, cilhip_set_projection(ctx_, proj_K_, proj_w_, proj_h_, identity ? nullptr : proj_E_.m), "setProjection");
+    }
+    fetched_ = false;
+    return *this;
+  }
+  bool projective_ = false;
+  float proj_K_[9] = {528.0f, 0.0f, 0.0f, 0.0f, 528.0f, 0.0f, 320.0f, 240.0f, 1.0f};
+  size_t proj_w_ = 640, proj_h_ = 480;
+  RigidTransform3f proj_E_;
   cilhip_ctx* ctx_;
   CorrespondenceSearchDirection search_dir_;
   CorrespondenceScalar max_distance_;
@@ -487,6 +512,17 @@ private:
   float point_to_point_weight_;
   float point_to_plane_weight_;
   CorrespondenceWeightEvaluator point_corr_eval_, plane_corr_eval_;
+};
+
+// icp_common_instances.hpp:208-225, :269-270: the combined-metric rigid ICP over CorrespondenceSearchProjective -- the target is
+// associated through its index map under the engine's projection (setProjection* on correspondenceSearchEngine(); defaults 528 / 320 /
+// 240, 640 x 480, identity extrinsics).  Setters inherited from the kd-tree class return that class: chain them on the object itself.
+class SimpleCombinedMetricRigidProjectiveICP3f : public SimpleCombinedMetricRigidICP3f {
+public:
+  SimpleCombinedMetricRigidProjectiveICP3f(const ConstPointsView& dst_p, const ConstPointsView& dst_n, const ConstPointsView& src_p, int device = 0)
+      : SimpleCombinedMetricRigidICP3f(dst_p, dst_n, src_p, device) {
+    correspondenceSearchEngine().enableProjection_();
+  }
 };
 
 // Affine instances (registration/icp_common_instances.hpp:255, :266): the same loop and correspondence engine with an

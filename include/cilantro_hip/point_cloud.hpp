@@ -10,6 +10,8 @@
 //   utilities/point_cloud.hpp:201-245             removeInvalidPoints / Normals / Colors / Data: host compaction, in the order the reference's remove() (:154-198) leaves
 //   utilities/point_cloud.hpp:247-290             gridDownsample / gridDownsampled (on the device: grid_downsampler.hpp); member
 //                                                 templates as in the reference, so a program that never calls them links without the library
+//   utilities/point_cloud.hpp:87-116, :463-499    the depth-image constructor, fromDepthImage / fromRGBDImages (on the device:
+//                                                 image_point_cloud_conversions.hpp); intrinsics: 9 floats, column-major
 #pragma once
 
 #include <cmath>
@@ -23,6 +25,7 @@
 #include <vector>
 
 #include "grid_downsampler.hpp"
+#include "image_point_cloud_conversions.hpp"
 
 namespace cilantro_hip {
 
@@ -34,6 +37,33 @@ public:
 
   PointCloud3f() = default;
   explicit PointCloud3f(const std::string& file_name) { fromPLYFile(file_name); }   // point_cloud.hpp:118-121
+
+  template <class DepthConverterT>                                                 // point_cloud.hpp:87-98
+  PointCloud3f(const typename DepthConverterT::RawDepth* depth_data, const DepthConverterT& depth_converter, size_t image_w, size_t image_h, const float* intrinsics,
+               bool keep_invalid = false, bool compute_normals = false) {
+    fromDepthImage(depth_data, depth_converter, image_w, image_h, intrinsics, keep_invalid, compute_normals);
+  }
+
+  // point_cloud.hpp:463-478
+  template <class DepthConverterT>
+  PointCloud3f& fromDepthImage(const typename DepthConverterT::RawDepth* depth_data, const DepthConverterT& depth_converter, size_t image_w, size_t image_h,
+                               const float* intrinsics, bool keep_invalid = false, bool compute_normals = false) {
+    colors.clear();
+    normals.clear();
+    if (compute_normals) depthImageToPointsNormals<DepthConverterT>(depth_data, depth_converter, image_w, image_h, intrinsics, points, normals, keep_invalid);
+    else depthImageToPoints<DepthConverterT>(depth_data, depth_converter, image_w, image_h, intrinsics, points, keep_invalid);
+    return *this;
+  }
+
+  // point_cloud.hpp:484-499
+  template <class DepthConverterT>
+  PointCloud3f& fromRGBDImages(const unsigned char* rgb_data, const typename DepthConverterT::RawDepth* depth_data, const DepthConverterT& depth_converter, size_t image_w,
+                               size_t image_h, const float* intrinsics, bool keep_invalid = false, bool compute_normals = false) {
+    normals.clear();
+    if (compute_normals) RGBDImagesToPointsNormalsColors<DepthConverterT>(rgb_data, depth_data, depth_converter, image_w, image_h, intrinsics, points, normals, colors, keep_invalid);
+    else RGBDImagesToPointsColors<DepthConverterT>(rgb_data, depth_data, depth_converter, image_w, image_h, intrinsics, points, colors, keep_invalid);
+    return *this;
+  }
 
   size_t size() const { return points.size() / 3; }
   bool isEmpty() const { return points.empty(); }
