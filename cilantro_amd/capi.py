@@ -29,6 +29,7 @@ SYMBOLS = [
     "cilhip_plane_ransac3f", "cilhip_plane_score3f", "cilhip_plane_fit3f", "cilhip_transform_ransac3f", "cilhip_transform_score3f", "cilhip_transform_fit3f", "cilhip_knn3f", "cilhip_knn_set_tie_rule", "cilhip_normals_knn3f", "cilhip_normals_radius3f", "cilhip_radius_search3f", "cilhip_grid_downsample3f",
     "cilhip_cc_default_params", "cilhip_connected_components3f", "cilhip_connected_components_lists",
     "cilhip_ms_default_params", "cilhip_mean_shift3f", "cilhip_ms_last_stats",
+    "cilhip_mcd_params_default", "cilhip_robust_normals_knn3f",
     "cilhip_depth_default_converter", "cilhip_depth_image_to_points3f", "cilhip_points_to_depth_image3f", "cilhip_points_to_index_map3f", "cilhip_set_projection",
 ]
 
@@ -100,6 +101,11 @@ class MsParams(C.Structure):
 
 class MsStats(C.Structure):
     _fields_ = [("form_used", C.c_int), ("est_ball", C.c_double), ("shift_ms", C.c_double), ("group_ms", C.c_double), ("passes", C.c_size_t), ("rounds", C.c_size_t)]
+
+
+class McdParams(C.Structure):
+    _fields_ = [("k", C.c_size_t), ("max_sq_dist", C.c_float), ("num_trials", C.c_int), ("num_refinements", C.c_int), ("inlier_ratio", C.c_float),
+                ("chi_square_threshold", C.c_float), ("seed", C.c_uint64)]
 
 
 class DepthConverter(C.Structure):
@@ -209,6 +215,9 @@ def load():
     L.cilhip_ms_default_params.restype = None
     L.cilhip_mean_shift3f.argtypes = [C.c_int, f32p, C.c_size_t, f32p, C.c_size_t, C.c_int, C.POINTER(MsParams), vp, vp, vp, vp, vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.cilhip_ms_last_stats.argtypes = [C.POINTER(MsStats)]
+    L.cilhip_mcd_params_default.argtypes = [C.POINTER(McdParams)]
+    L.cilhip_mcd_params_default.restype = None
+    L.cilhip_robust_normals_knn3f.argtypes = [C.c_int, f32p, C.c_size_t, C.c_int, C.POINTER(McdParams), f32p, f32p, f32p, vp, vp]
     L.cilhip_depth_default_converter.argtypes = [C.POINTER(DepthConverter)]
     L.cilhip_depth_default_converter.restype = None
     L.cilhip_depth_image_to_points3f.argtypes = [C.c_int, vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(DepthConverter), f32p, f32p, C.c_int, C.c_int, f32p, f32p, f32p,
@@ -262,7 +271,7 @@ def load():
     L.cilhip_get_slab_violation_state.argtypes = [vp, C.POINTER(C.c_int), vp]
     for name in SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
-        if name not in ("cilhip_destroy", "cilhip_last_error", "cilhip_icp_default_params", "cilhip_option_info", "cilhip_cc_default_params", "cilhip_ms_default_params", "cilhip_depth_default_converter"):
+        if name not in ("cilhip_destroy", "cilhip_last_error", "cilhip_icp_default_params", "cilhip_option_info", "cilhip_cc_default_params", "cilhip_ms_default_params", "cilhip_mcd_params_default", "cilhip_depth_default_converter"):
             fn.restype = C.c_int
     _lib = L
     return L

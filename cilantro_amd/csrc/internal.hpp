@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <functional>
 #include <string>
 #include <thread>
 
@@ -407,6 +408,12 @@ struct TieNode {          // 16 bytes: one load on the device
 // every point and its slot in the reference's permutation (device arrays [n] the caller provides); *d_nodes_out: the TieNode
 // records, breadth-first ids.
 extern int g_knn_tie_rule;      // knn.hip: cilhip_knn_set_tie_rule (k-NN lists and the KMeans kd branch)
+// knn.hip: the self-search of cilhip_knn3f(xyz, xyz, k, max_sq_dist) -- same grid, same tie rule, same lists -- stopped before the download: `consume`
+// gets the lists where the search left them and enqueues its work on `s` (it synchronises `s` itself before it returns; blocks it takes from `pool`
+// live as long as the lists).  Rows by ORIGINAL index, ascending, NONE_U32-padded behind cnt[i].  Returns what `consume` returns.
+struct KnnDeviceLists { const float* xyz; const uint32_t* idx; const uint32_t* cnt; size_t n, k; DevPool* pool; hipStream_t s; };
+typedef std::function<int(const KnnDeviceLists&)> KnnListsConsumer;
+int knn_self_lists_on_device(int device, const float* xyz, size_t n, int mem, size_t k, float max_sq_dist, const KnnListsConsumer& consume);
 hipError_t tie_order_build_device(const float* d_xyz, const float4* d_sorted, uint32_t n, hipStream_t s, uint32_t* d_leaf_by_index, uint32_t* d_slot_by_index,
                                   DevBuf<uint4>* d_nodes_out, size_t* n_nodes_out, int* max_depth_out);
 // ... and of the tree a feature adaptor's search walks (DIM = 6 / 9: points + w1 * att1 [+ w2 * att2], attributes by sorted position);

@@ -374,7 +374,7 @@ __global__ __launch_bounds__(KNN_THREADS) void k_radius_pca(KnnArgs a) {
 
 int knn_impl(int device, const float* ref_xyz, size_t n_ref, const float* query_xyz, size_t n_query, int mem, size_t k, float max_sq_dist,
              uint32_t* idx_out, float* d2_out, uint32_t* cnt_out, bool do_pca, const float* view_point, float* normals_out,
-             float* curvature_out) {
+             float* curvature_out, const KnnListsConsumer* consume = nullptr) {
   const bool radius_only = do_pca && k == 0;   // unbounded neighbourhood: moments only, no list
   if ((!ref_xyz && n_ref) || (k == 0 && !radius_only) || k > (size_t)KNN_MAX_K || n_ref > 0xFFFFFFF0ull || n_query > 0xFFFFFFF0ull) return st_fail(CILHIP_ERR_INVALID, "knn", kBadArguments);
   if (radius_only && !std::isfinite(max_sq_dist)) return st_fail(CILHIP_ERR_INVALID, "knn", "radius_sq must be finite");
@@ -421,9 +421,9 @@ int knn_impl(int device, const float* ref_xyz, size_t n_ref, const float* query_
     }
     KnnArgs a{};
     a.g = gr.grid; a.queries = d_qs; a.nq = (uint32_t)n_query; a.k = (uint32_t)k; a.radius_sq = max_sq_dist;
-    if (idx_out) { ST_CK("knn", pool.get(&d_idx, n_query * k)); a.out_idx = d_idx; }
+    if (idx_out || consume) { ST_CK("knn", pool.get(&d_idx, n_query * k)); a.out_idx = d_idx; }
     if (idx_out && d2_out) { ST_CK("knn", pool.get(&d_d2, n_query * k)); a.out_d2 = d_d2; }
-    if (cnt_out) { ST_CK("knn", pool.get(&d_cnt, n_query)); a.out_cnt = d_cnt; }
+    if (cnt_out || consume) { ST_CK("knn", pool.get(&d_cnt, n_query)); a.out_cnt = d_cnt; }
     a.do_pca = do_pca ? 1 : 0;
     if (do_pca) {
       ST_CK("knn", pool.get(&d_nrm, 3 * n_query));
@@ -470,6 +470,8 @@ int knn_impl(int device, const float* ref_xyz, size_t n_ref, const float* query_
       }
     }
     ST_CK("knn", hipGetLastError());
+    // the lists stay on the device: the consumer enqueues its own work behind the search, on the same stream, and waits for it
+    if (consume) return (*consume)(KnnDeviceLists{d_ref, d_idx, d_cnt, n_query, k, &pool, s});
     if (idx_out) ST_CK("knn", hipMemcpyAsync(idx_out, d_idx, n_query * k * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     if (idx_out && d2_out) ST_CK("knn", hipMemcpyAsync(d2_out, d_d2, n_query * k * sizeof(float), hipMemcpyDeviceToHost, s));
     if (cnt_out) ST_CK("knn", hipMemcpyAsync(cnt_out, d_cnt, n_query * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -622,6 +624,10 @@ int radius_impl(int device, const float* ref_xyz, size_t n_ref, const float* que
 }
 
 }  // namespace
+
+int knn_self_lists_on_device(int device, const float* xyz, size_t n, int mem, size_t k, float max_sq_dist, const KnnListsConsumer& consume) {
+  return knn_impl(device, xyz, n, nullptr, n, mem, k, max_sq_dist, nullptr, nullptr, nullptr, false, nullptr, nullptr, nullptr, &consume);
+}
 }  // namespace cilhip
 
 extern "C" {

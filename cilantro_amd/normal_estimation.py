@@ -9,7 +9,12 @@
     normals, curvature = ne.getNormalsAndCurvatureKNN(k)       # :72-80
     normals = ne.getNormalsKNNInRadius(k, radius)              # :189-196   (NormalEstimation squares its radius itself, :174)
 
-Radius-only neighbourhoods are supported for the normals (moments accumulated without listing the neighbours).
+    rne = RobustNormalEstimation3f(points).setViewPoint([0, 0, 0])          # NormalEstimation<float, 3, MinimumCovarianceDeterminant<float, 3>>
+    rne.covarianceMethod().setChiSquareThreshold(6.25).setNumberOfTrials(2).setNumberOfRefinements(1)   # core/covariance.hpp:185-371
+    normals = rne.getNormalsKNN(12)                                          # an outlier's normal is NaN
+
+Radius-only neighbourhoods are supported for the plain normals (moments accumulated without listing the neighbours); the robust class
+ranks a neighbour list and refuses them.
 """
 import ctypes as C
 
@@ -154,3 +159,129 @@ class NormalEstimation3f:
 
     def getCurvatureRadius(self, radius):
         return self._run_radius(self._sq(radius), True)[1]
+
+
+class MinimumCovarianceDeterminant3f:
+    """the settings of core/covariance.hpp:185-371, same names and defaults (:365-369); setSeed: the trials' draws follow from a stated
+    seed (the reference asks std::random_device), so two runs give the same bytes"""
+
+    def __init__(self):
+        self._trials, self._refinements, self._ratio, self._chi, self._seed = 6, 3, 0.75, -1.0, 0
+
+    def getNumberOfTrials(self):
+        return self._trials
+
+    def setNumberOfTrials(self, num_trials):
+        self._trials = int(num_trials)
+        return self
+
+    def getNumberOfRefinements(self):
+        return self._refinements
+
+    def setNumberOfRefinements(self, num_refinements):
+        self._refinements = int(num_refinements)
+        return self
+
+    def getInlierRatio(self):
+        return self._ratio
+
+    def setInlierRatio(self, inlier_ratio):
+        self._ratio = float(inlier_ratio)
+        return self
+
+    def getChiSquareThreshold(self):
+        return self._chi
+
+    def setChiSquareThreshold(self, chi_square_threshold):
+        self._chi = float(chi_square_threshold)
+        return self
+
+    def getSeed(self):
+        return self._seed
+
+    def setSeed(self, seed):
+        self._seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        return self
+
+
+class RobustNormalEstimation3f:
+    """NormalEstimation<float, 3, MinimumCovarianceDeterminant<float, 3>> over k-NN lists (cilhip_robust_normals_knn3f; the contract is
+    DESIGN.md section 15).  A torch device tensor as the cloud gives torch device tensors back (mem = DEVICE)."""
+
+    _RADIUS_ONLY = ("RobustNormalEstimation3f: a radius-only neighbourhood keeps no neighbour list on the device, and the MCD trials rank a "
+                    "list; use the ...KNNInRadius getters (k <= 32)")
+
+    def __init__(self, points, device=0):
+        self._L = capi.load()
+        self._points = points
+        self._device = device
+        self._vp = None
+        self._mcd = MinimumCovarianceDeterminant3f()
+
+    def covarianceMethod(self):
+        return self._mcd
+
+    def setViewPoint(self, vp):
+        self._vp = None if vp is None else np.ascontiguousarray(vp, np.float32).reshape(3)
+        return self
+
+    def getViewPoint(self):
+        return np.full(3, np.nan, np.float32) if self._vp is None else self._vp
+
+    def _run(self, k, radius_sq, want_curvature=True, want_decisions=False):
+        """-> (normals, curvature or None, subset masks or None, inlier flags or None)"""
+        p, n, mem, keep = _as_cloud(self._points)
+        prm = capi.McdParams()
+        self._L.cilhip_mcd_params_default(C.byref(prm))
+        prm.k, prm.max_sq_dist = int(k), float(radius_sq)
+        m = self._mcd
+        prm.num_trials, prm.num_refinements, prm.inlier_ratio, prm.chi_square_threshold, prm.seed = m._trials, m._refinements, m._ratio, m._chi, m._seed
+        if mem == capi.MEM_DEVICE:
+            import torch
+
+            dev = self._points.device
+            outs = [torch.zeros((max(n, 1), 3), dtype=torch.float32, device=dev), torch.zeros(max(n, 1), dtype=torch.float32, device=dev) if want_curvature else None,
+                    torch.zeros(max(n, 1), dtype=torch.int32, device=dev) if want_decisions else None, torch.zeros(max(n, 1), dtype=torch.uint8, device=dev) if want_decisions else None]
+            ptr = [None if o is None else o.data_ptr() for o in outs]
+        else:
+            outs = [np.zeros((max(n, 1), 3), np.float32), np.zeros(max(n, 1), np.float32) if want_curvature else None,
+                    np.zeros(max(n, 1), np.uint32) if want_decisions else None, np.zeros(max(n, 1), np.uint8) if want_decisions else None]
+            ptr = [None if o is None else o.ctypes.data for o in outs]
+        rc = self._L.cilhip_robust_normals_knn3f(self._device, p, n, mem, C.byref(prm), None if self._vp is None else self._vp.ctypes.data, *ptr)
+        if rc != capi.OK:
+            raise capi.CilhipError(rc, "cilhip_robust_normals_knn3f: " + self._L.cilhip_last_error(None).decode())
+        return tuple(None if o is None else o[:n] for o in outs)
+
+    def getNormalsAndCurvatureKNN(self, k):
+        return self._run(k, np.inf)[:2]
+
+    def getNormalsKNN(self, k):
+        return self._run(k, np.inf, False)[0]
+
+    def getCurvatureKNN(self, k):
+        return self._run(k, np.inf)[1]
+
+    def getNormalsAndCurvatureKNNInRadius(self, k, radius):
+        return self._run(k, NormalEstimation3f._sq(radius))[:2]
+
+    def getNormalsKNNInRadius(self, k, radius):
+        return self._run(k, NormalEstimation3f._sq(radius), False)[0]
+
+    def getCurvatureKNNInRadius(self, k, radius):
+        return self._run(k, NormalEstimation3f._sq(radius))[1]
+
+    def getSubsetMasksAndInliersKNN(self, k):
+        """the decisions behind the normals: per point the final subset (bit j: list position j is in it) and the chi-square inlier flag"""
+        return self._run(k, np.inf, False, True)[2:]
+
+    def getSubsetMasksAndInliersKNNInRadius(self, k, radius):
+        return self._run(k, NormalEstimation3f._sq(radius), False, True)[2:]
+
+    def getNormalsAndCurvatureRadius(self, radius):
+        raise ValueError(self._RADIUS_ONLY)
+
+    def getNormalsRadius(self, radius):
+        raise ValueError(self._RADIUS_ONLY)
+
+    def getCurvatureRadius(self, radius):
+        raise ValueError(self._RADIUS_ONLY)

@@ -475,6 +475,42 @@ int cilhip_normals_knn3f(int device, const float* xyz, size_t n, int mem, size_t
  * (strict) takes part; the neighbourhood is unbounded, its moments are accumulated without listing it. */
 int cilhip_normals_radius3f(int device, const float* xyz, size_t n, int mem, float radius_sq, const float* view_point,
                             float* normals_out, float* curvature_out);
+/* NormalEstimation<float, 3, MinimumCovarianceDeterminant<float, 3>>::getNormalsKNN / ...KNNInRadius (the reference's
+ * examples/robust_normal_estimation.cpp; core/covariance.hpp:185-371): per point i, over the list L[0..m) that
+ * cilhip_knn3f(xyz, xyz, k, max_sq_dist) returns for it under the process's tie rule, num_trials random elemental starts of 3 distinct
+ * list positions, each followed by num_refinements concentration steps (rank the list by Mahalanobis distance, keep the h closest,
+ * re-estimate), the trial of the smallest covariance determinant kept, then the chi-square test on the point itself.  The contract,
+ * operation by operation, is DESIGN.md section 15.1; in short
+ *   h = min(max(3, llroundf(inlier_ratio * (float)m)), m)  (covariance.hpp:317-319); m < 3: NaN row; m == 3 or h == m: the plain
+ *       covariance of the whole list, no trials (:204, :349-352) -- with inlier_ratio 1 and chi_square_threshold <= 0 the call returns
+ *       the bytes of cilhip_normals_knn3f;
+ *   trial j of point i draws its start with draw_samples(seed ^ ((uint64_t)i << 8 | j), m, 3, 1, .) (a stated seed where the reference
+ *       asks std::random_device: two runs give the same bytes);
+ *   mean and covariance of a subset: the arithmetic of cilhip_normals_knn3f (f64 sums, f32 mean, f32 centred terms and products);
+ *   ranking by q = d^T adj(C) d in f64 (det(C) times the squared Mahalanobis distance: no division, defined for the singular covariance
+ *       of a 3-point start, where it orders by distance to the plane through the start), ties by list position, NaN last;
+ *   a trial replaces the best iff its determinant is smaller (strict; NaN and inf never win); no winner: NaN row;
+ *   inlier iff chi_square_threshold <= 0 or q_0 <= (double)chi_square_threshold * det; an outlier's normal and curvature are NaN
+ *       (normal_estimation.hpp:300, :381); normal, view-point flip and curvature from the chosen covariance as cilhip_normals_knn3f.
+ * mem: where xyz AND the four outputs live.  view_point: HOST, 3 floats, NULL / non-finite: no flip.  normals_out: 3*n floats;
+ * curvature_or_null: n floats; subset_mask_or_null: n words, bit j set iff list position j is in the final subset (0 for a NaN row
+ * that is not an outlier); inlier_or_null: n bytes, 1 = inlier.  A point with a non-finite coordinate is in no list and gets a NaN row.
+ * CILHIP_ERR_INVALID, before a device is opened and with nothing written: params, xyz (n > 0) or normals_out NULL, k outside 1..32,
+ * num_trials outside 1..64, num_refinements outside 0..16, inlier_ratio not finite or <= 0, chi_square_threshold NaN, n >= 2^32 - 16,
+ * unknown mem.  Radius-only neighbourhoods keep no list (cilhip_normals_radius3f) and have no robust form. */
+typedef struct cilhip_mcd_params {
+  size_t k;                     /* list length, 1..32 */
+  float max_sq_dist;            /* only neighbours with d2 < max_sq_dist (INFINITY: none left out) */
+  int num_trials;               /* 1..64 */
+  int num_refinements;          /* 0..16 */
+  float inlier_ratio;
+  float chi_square_threshold;   /* <= 0: no point is labelled an outlier */
+  uint64_t seed;
+} cilhip_mcd_params;
+/* 6 trials, 3 refinements, ratio 0.75, threshold -1 (covariance.hpp:365-369); max_sq_dist INFINITY, k 0 (to be set), seed 0 */
+void cilhip_mcd_params_default(cilhip_mcd_params* params);
+int cilhip_robust_normals_knn3f(int device, const float* xyz, size_t n, int mem, const cilhip_mcd_params* params, const float* view_point,
+                                float* normals_out, float* curvature_or_null, uint32_t* subset_mask_or_null, uint8_t* inlier_or_null);
 
 /* ---- voxel-grid downsampling ---------------------------------------------------------------------------------- */
 /* PointsGridDownsampler<float,3> and its siblings with normals / colours (core/grid_downsampler.hpp:8-340 over
