@@ -31,6 +31,7 @@ SYMBOLS = [
     "cilhip_ms_default_params", "cilhip_mean_shift3f", "cilhip_ms_last_stats",
     "cilhip_mcd_params_default", "cilhip_robust_normals_knn3f",
     "cilhip_depth_default_converter", "cilhip_depth_image_to_points3f", "cilhip_points_to_depth_image3f", "cilhip_points_to_index_map3f", "cilhip_set_projection",
+    "cilhip_fusion_default_params", "cilhip_fuse_frame3f", "cilhip_fusion_remove_unstable3f",
 ]
 
 
@@ -113,6 +114,16 @@ class DepthConverter(C.Structure):
 
 
 DEPTH_U16, DEPTH_F32 = 0, 1
+
+
+class FusionParams(C.Structure):
+    _fields_ = [("fusion_dist_thresh", C.c_float), ("occlusion_dist_thresh", C.c_float), ("radial_factor", C.c_float), ("fuse_max_angle_deg", C.c_float),
+                ("append_min_angle_deg", C.c_float), ("free_space_max_angle_deg", C.c_float)]
+
+
+class FusionCounts(C.Structure):
+    _fields_ = [("visited", C.c_size_t), ("fused", C.c_size_t), ("appended", C.c_size_t), ("removed", C.c_size_t), ("untouched", C.c_size_t)]
+
 
 _lib = None
 
@@ -225,6 +236,11 @@ def load():
     L.cilhip_points_to_depth_image3f.argtypes = [C.c_int, f32p, f32p, C.c_size_t, C.c_int, f32p, f32p, C.POINTER(DepthConverter), C.c_size_t, C.c_size_t, vp, vp]
     L.cilhip_points_to_index_map3f.argtypes = [C.c_int, f32p, C.c_size_t, C.c_int, f32p, f32p, C.c_size_t, C.c_size_t, vp]
     L.cilhip_set_projection.argtypes = [vp, f32p, C.c_size_t, C.c_size_t, f32p]
+    L.cilhip_fusion_default_params.argtypes = [C.POINTER(FusionParams)]
+    L.cilhip_fusion_default_params.restype = None
+    L.cilhip_fuse_frame3f.argtypes = [C.c_int, f32p, f32p, f32p, f32p, C.c_size_t, C.c_size_t, f32p, f32p, f32p, C.c_size_t, C.c_int, f32p, f32p, C.c_size_t, C.c_size_t,
+                                      C.POINTER(FusionParams), C.POINTER(C.c_size_t), C.POINTER(FusionCounts)]
+    L.cilhip_fusion_remove_unstable3f.argtypes = [C.c_int, f32p, f32p, f32p, f32p, C.c_size_t, C.c_int, C.c_float, C.POINTER(C.c_size_t)]
     L.cilhip_icp_sums_from_keys.argtypes = [vp, vp, f64p]
     L.cilhip_icp_order_keys.argtypes = [vp, vp, vp]
     L.cilhip_icp_sums_from_ordered_keys.argtypes = [vp, vp, vp, f64p]
@@ -271,7 +287,7 @@ def load():
     L.cilhip_get_slab_violation_state.argtypes = [vp, C.POINTER(C.c_int), vp]
     for name in SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
-        if name not in ("cilhip_destroy", "cilhip_last_error", "cilhip_icp_default_params", "cilhip_option_info", "cilhip_cc_default_params", "cilhip_ms_default_params", "cilhip_mcd_params_default", "cilhip_depth_default_converter"):
+        if name not in ("cilhip_destroy", "cilhip_last_error", "cilhip_icp_default_params", "cilhip_option_info", "cilhip_cc_default_params", "cilhip_ms_default_params", "cilhip_mcd_params_default", "cilhip_depth_default_converter", "cilhip_fusion_default_params"):
             fn.restype = C.c_int
     _lib = L
     return L

@@ -15,7 +15,7 @@
 //                           bits), nothing like the reference's points_tmp is materialised.  COUNT: kept rows per block of 256 pixels
 //                           (ballot / popcount per wave).  One rocPRIM exclusive scan of those counts, then the same kernel again writes
 //                           every kept row at its block's offset plus its rank inside the block: rows leave in pixel order.
-//   k_ic_splat<MODE>        one lane per point: one 64-bit atomicMin on (bits(c_z) << 32) | index (index map) or (raw << 32) | index
+//   k_ic_splat<MODE>        (image_device.hpp, shared with fusion.hip) one lane per point: one 64-bit atomicMin on (bits(c_z) << 32) | index (index map) or (raw << 32) | index
 //                           (depth image) -- c_z and raw are positive, so their f32 bits order as their values do; the minimum is rule
 //                           P4 / P5 whatever the arrival order.  No floating-point atomics: two runs give the same bits.
 //   k_ic_resolve_*          one lane per pixel: key -> index / u16 / f32 / rgb
@@ -29,6 +29,7 @@
 #include <cstring>
 
 #include "../../include/cilantro_hip/c_api.h"
+#include "image_device.hpp"
 #include "internal.hpp"
 #include "stateless.hpp"
 
@@ -36,21 +37,7 @@ namespace cilhip {
 
 namespace {
 
-constexpr unsigned long long IC_LIMIT = 0xFFFFFFF0ull;      // w * h and n stay below 2^32 - 16
-constexpr unsigned long long IC_EMPTY = ~0ull;
-constexpr int IC_BLOCK = 256;
-
-struct IcConv { float scale, inv_scale, max_depth; int truncated, raw_type; };
-
-__device__ __forceinline__ float ic_dot3(float a0, float a1, float a2, float b0, float b1, float b2) {
-  return __fadd_rn(__fmul_rn(a0, b0), __fadd_rn(__fmul_rn(a1, b1), __fmul_rn(a2, b2)));
-}
-// the engine's pinned point transform: (L_r0 x + (L_r1 y + L_r2 z)) + t_r; M = rows of L, then t
-struct IcRigid { float L[9]; float t[3]; };
-__device__ __forceinline__ F3 ic_apply(const IcRigid& m, F3 p) {
-  return F3{__fadd_rn(ic_dot3(m.L[0], m.L[1], m.L[2], p.x, p.y, p.z), m.t[0]), __fadd_rn(ic_dot3(m.L[3], m.L[4], m.L[5], p.x, p.y, p.z), m.t[1]),
-            __fadd_rn(ic_dot3(m.L[6], m.L[7], m.L[8], p.x, p.y, p.z), m.t[2])};
-}
+// (IcConv, IcRigid, ic_dot3, ic_apply, ic_normalized, ic_pixel, k_ic_splat, ic_rigid, ic_to_cam: image_device.hpp, shared with fusion.hip)
 
 struct IcUnproject {
   const void* depth;            // u16 or f32, w * h
@@ -85,15 +72,10 @@ __device__ __forceinline__ F3 ic_normal(const IcUnproject& a, uint32_t x, uint32
   if (!(r.z > 0.0f && l.z > 0.0f && d.z > 0.0f && u.z > 0.0f)) return n;
   const float ax = __fsub_rn(d.x, u.x), ay = __fsub_rn(d.y, u.y), az = __fsub_rn(d.z, u.z);
   const float bx = __fsub_rn(r.x, l.x), by = __fsub_rn(r.y, l.y), bz = __fsub_rn(r.z, l.z);
-  float cx = __fsub_rn(__fmul_rn(ay, bz), __fmul_rn(az, by));
-  float cy = __fsub_rn(__fmul_rn(az, bx), __fmul_rn(ax, bz));
-  float cz = __fsub_rn(__fmul_rn(ax, by), __fmul_rn(ay, bx));
-  const float z = ic_dot3(cx, cy, cz, cx, cy, cz);
-  if (z > 0.0f) {      // (the correctly rounded f32 square root and quotients, formed in f64 as everywhere in the engine)
-    const double s = (double)(float)sqrt((double)z);
-    cx = (float)((double)cx / s); cy = (float)((double)cy / s); cz = (float)((double)cz / s);
-  }
-  return F3{cx, cy, cz};
+  const float cx = __fsub_rn(__fmul_rn(ay, bz), __fmul_rn(az, by));
+  const float cy = __fsub_rn(__fmul_rn(az, bx), __fmul_rn(ax, bz));
+  const float cz = __fsub_rn(__fmul_rn(ax, by), __fmul_rn(ay, bx));
+  return ic_normalized(F3{cx, cy, cz});
 }
 
 // One block per 256 consecutive pixels.  COUNT: block_counts[block] = kept rows of the block.  Otherwise: write the rows.
@@ -131,7 +113,7 @@ __global__ __launch_bounds__(IC_BLOCK) void k_ic_unproject(IcUnproject a) {
   if (COUNT || !keep) return;
   if (a.has_e) {      // D7
     p = ic_apply(a.e, p);
-    if (a.want_normals) n = F3{ic_dot3(a.e.L[0], a.e.L[1], a.e.L[2], n.x, n.y, n.z), ic_dot3(a.e.L[3], a.e.L[4], a.e.L[5], n.x, n.y, n.z), ic_dot3(a.e.L[6], a.e.L[7], a.e.L[8], n.x, n.y, n.z)};
+    if (a.want_normals) n = ic_linear(a.e, n);
   }
   if (a.out_p) a.out_p[row] = p;
   if (a.out_n) a.out_n[row] = n;
@@ -140,58 +122,6 @@ __global__ __launch_bounds__(IC_BLOCK) void k_ic_unproject(IcUnproject a) {
     const unsigned char* c = a.rgb + 3 * k;
     a.out_c[row] = F3{__fmul_rn(s, (float)c[0]), __fmul_rn(s, (float)c[1]), __fmul_rn(s, (float)c[2])};
   }
-}
-
-struct IcSplat {
-  const F3* xyz;
-  uint32_t n;
-  int has_cam;
-  IcRigid to_cam;
-  float k0[3], k1[3];      // rows 0 and 1 of K
-  uint32_t w, h;
-  IcConv conv;
-  unsigned long long* keys;      // [w * h], IC_EMPTY where nothing landed
-};
-
-// P3: llround of a finite u as a pixel coordinate below `limit`; -1: outside
-__device__ __forceinline__ long long ic_pixel(float u, uint32_t limit) {
-  const float r = roundf(u);      // ties away from zero
-  if (!(r >= 0.0f && r < 4294967296.0f)) return -1;      // (-0.4 rounds to -0: pixel 0)
-  const long long x = (long long)r;
-  return x < (long long)limit ? x : -1;
-}
-
-enum { IC_INDEX = 0, IC_DEPTH = 1 };
-
-template <int MODE>
-__global__ __launch_bounds__(IC_BLOCK) void k_ic_splat(IcSplat a) {
-  const size_t i = (size_t)blockIdx.x * IC_BLOCK + threadIdx.x;
-  if (i >= a.n) return;
-  F3 c = a.xyz[i];
-  if (a.has_cam) c = ic_apply(a.to_cam, c);      // P1
-  if (!(c.z > 0.0f)) return;                     // P2 (NaN ends here)
-  const float inv_z = (float)(1.0 / (double)c.z);
-  const float u = __fmul_rn(inv_z, ic_dot3(a.k0[0], a.k0[1], a.k0[2], c.x, c.y, c.z)), v = __fmul_rn(inv_z, ic_dot3(a.k1[0], a.k1[1], a.k1[2], c.x, c.y, c.z));
-  if (!(isfinite(u) && isfinite(v))) return;
-  const long long x = ic_pixel(u, a.w), y = ic_pixel(v, a.h);
-  if (x < 0 || y < 0) return;
-  uint32_t hi;
-  if (MODE == IC_INDEX) {
-    hi = (uint32_t)__float_as_int(c.z);
-  } else {       // P5
-    if (a.conv.truncated && !(c.z < a.conv.max_depth)) return;
-    const float prod = __fmul_rn(a.conv.scale, c.z);
-    if (a.conv.raw_type == CILHIP_DEPTH_U16) {
-      if (!(prod < 65536.0f)) return;      // (NaN too: no defined conversion)
-      hi = (uint32_t)prod;                 // truncation toward zero
-      if (hi == 0u) return;
-    } else {
-      if (!(prod > 0.0f)) return;
-      hi = (uint32_t)__float_as_int(prod);
-    }
-  }
-  // y < h, x < w and w * h < 2^32 - 16: the pixel is inside keys[]
-  atomicMin(&a.keys[(size_t)y * a.w + (size_t)x], ((unsigned long long)hi << 32) | (unsigned long long)(uint32_t)i);
 }
 
 __global__ __launch_bounds__(IC_BLOCK) void k_ic_resolve_index(const unsigned long long* __restrict__ keys, size_t npix, uint32_t* __restrict__ out) {
@@ -222,13 +152,7 @@ __global__ __launch_bounds__(IC_BLOCK) void k_ic_resolve_depth(const unsigned lo
   }
 }
 
-inline unsigned ic_blocks(size_t n) { return (unsigned)((n + IC_BLOCK - 1) / IC_BLOCK); }      // (n < 2^32: below the grid limit)
-
 // ---- host side of the rules ------------------------------------------------------------------------------------------
-bool ic_all_finite(const float* a, int n) {
-  for (int i = 0; i < n; ++i) if (!std::isfinite(a[i])) return false;
-  return true;
-}
 // D2: the inverse of the column-major f32 K, formed in f64, every entry rounded once; row-major out.  false: singular
 bool ic_invert(const float* K, float out[9]) {
   double m[3][3];
@@ -242,21 +166,6 @@ bool ic_invert(const float* K, float out[9]) {
   for (int i = 0; i < 9; ++i) { out[i] = (float)inv[i]; if (!std::isfinite(out[i])) return false; }
   return true;
 }
-IcRigid ic_rigid(const float* E) {      // column-major 4x4 -> rows of the linear part, translation
-  IcRigid m{};
-  for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) m.L[3 * r + c] = E[r + 4 * c]; m.t[r] = E[r + 12]; }
-  return m;
-}
-// P1: to_cam = (R^T, -R^T t), formed in f64 from the f32 entries, rounded once
-IcRigid ic_to_cam(const float* E) {
-  IcRigid m{};
-  for (int r = 0; r < 3; ++r) {
-    for (int c = 0; c < 3; ++c) m.L[3 * r + c] = E[c + 4 * r];
-    m.t[r] = (float)-((double)E[0 + 4 * r] * (double)E[12] + ((double)E[1 + 4 * r] * (double)E[13] + (double)E[2 + 4 * r] * (double)E[14]));
-  }
-  return m;
-}
-
 // the converter's rules; null: fine
 const char* ic_conv_rule(const cilhip_depth_converter* c) {
   if (!c) return "the depth converter is null";

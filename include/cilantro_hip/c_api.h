@@ -704,6 +704,58 @@ int cilhip_points_to_depth_image3f(int device, const float* xyz, const float* rg
 int cilhip_points_to_index_map3f(int device, const float* xyz, size_t n, int mem, const float* extrinsics_or_null, const float* K, size_t w,
                                  size_t h, uint32_t* index_out);
 
+/* ---- map fusion of registered depth frames (stateless; the "Map" step of examples/fusion.cpp:147-236) ------------------------
+ * A surfel model -- points, normals, colours and one confidence per point -- takes in one frame (points, normals and colours in
+ * the CAMERA frame, as fromRGBDImages gives them) seen from cam_pose: model points the frame confirms are averaged with it by
+ * confidence, surface the model has not seen is appended, model points in observed free space are removed.  DESIGN.md section 16
+ * has the contract in full (rules F1-F9, compared bit for bit with tests/_fusion_refs.py); in short, with the rounding conventions of
+ * the image conversions above (dot3, the pinned transform, no FMA, correctly rounded quotients and square roots):
+ *   F1  model map = index map of model_xyz under extrinsics cam_pose (c = to_cam p, nc = linear(to_cam) n: model_t, :152, :156);
+ *       frame map = index map of frame_xyz without extrinsics (:158)
+ *   F2  interior pixels 1 <= x <= w - 2, 1 <= y <= h - 2 in ascending k = y w + x (:172-173; none for w < 3 or h < 3); a pixel
+ *       whose frame entry is empty does nothing (:177).  f, m: the two maps' entries at the pixel
+ *   F3  fz = frame_xyz[f].z, mz = c_m.z (:182-184); rw = pinned_expf(radial_factor * (dx dx + dy dy)), dx = (float)x - K02,
+ *       dy = (float)y - K12 (:185-186); ang(v) = (float)acos((double)min(1.0f, max(-1.0f, v))) (std::min / std::max as written:
+ *       NaN becomes -1), compared in f64 against T(deg) = ((double)deg * M_PI) / 180.0; a = ang(dot3(nc_m, frame_normals[f]))
+ *   F4  the first that holds (:188-226): FUSE m exists, |mz - fz| < fusion_dist_thresh, a < T(fuse_max_angle_deg);
+ *       APPEND m empty and the pixel's four neighbours in the model map empty, or m exists and a > T(append_min_angle_deg);
+ *       REMOVE m exists, fz > mz + occlusion_dist_thresh, ang(-dot3(normalized(c_m), nc_m)) < T(free_space_max_angle_deg);
+ *       otherwise the pixel is untouched
+ *   F5  fuse (:194-203): g = rw / (rw + conf[m]), gc = 1.0f - g, q = cam_pose frame_xyz[f], nq = linear(cam_pose) frame_normals[f];
+ *       point and colour per component gc old + g new, normal normalized(gc n + g nq), conf[m] += g (0 / 0 gives NaN)
+ *   F6  the removed set S leaves as the reference's remove() / vec_remove do (utilities/point_cloud.hpp:154-198, fusion.cpp:8-33):
+ *       n' = n - |S| (|S| >= n: the model is cleared); a row p < n' not in S stays; the k-th smallest member of S below n' receives
+ *       the k-th LARGEST surviving row of [n', n)
+ *   F7  then rows (q, nq, frame_rgb[f], conf = rw) are appended in ascending pixel order (:229-235)
+ *   F8  *n_out = n_model - removed + appended; counts: the five populations, visited = their sum
+ * The model is edited in place: its four arrays hold `capacity` rows (xyz, normals, rgb: 3 floats per row; conf: 1), the first n_model
+ * are the model, after the call the first *n_out.  capacity = n_model + min(n_frame, w h) always suffices.  A capacity that is too
+ * small: CILHIP_ERR_INVALID, *n_out = the size needed, and NOTHING is written to the model (every decision is made in scratch before
+ * the first row changes).  mem says where all arrays live; host arrays are staged and copied back.
+ * CILHIP_ERR_INVALID before the device is opened, nothing written, cilhip_last_error(NULL) naming the rule: NULL n_out, params, K or
+ * cam_pose; a NULL model array with capacity > 0; a NULL frame array with n_frame > 0; n_model > capacity; n_model, n_frame or
+ * w h >= 2^32 - 16; unknown mem; a non-finite K, pose or parameter; a negative threshold or angle.  w h == 0 or n_frame == 0:
+ * CILHIP_OK, *n_out = n_model, no device needed. */
+typedef struct cilhip_fusion_params {
+  float fusion_dist_thresh;        /* 0.01   fusion.cpp:98 */
+  float occlusion_dist_thresh;     /* 0.025  :99 */
+  float radial_factor;             /* -0.5f / (120 * 120)  :100 */
+  float fuse_max_angle_deg;        /* 75   :192 */
+  float append_min_angle_deg;      /* 105  :211 */
+  float free_space_max_angle_deg;  /* 45   :223 */
+} cilhip_fusion_params;
+void cilhip_fusion_default_params(cilhip_fusion_params* params);
+typedef struct cilhip_fusion_counts { size_t visited, fused, appended, removed, untouched; } cilhip_fusion_counts;
+int cilhip_fuse_frame3f(int device, float* model_xyz, float* model_normals, float* model_rgb, float* model_conf, size_t n_model, size_t capacity,
+                        const float* frame_xyz, const float* frame_normals, const float* frame_rgb, size_t n_frame, int mem,
+                        const float* cam_pose /* float[16] column-major, camera to world */, const float* K, size_t w, size_t h,
+                        const cilhip_fusion_params* params, size_t* n_out, cilhip_fusion_counts* counts_or_null);
+/* F9, cleanup_callback (fusion.cpp:51-59): S = {i : conf[i] < conf_thresh} (a NaN confidence stays) leaves by F6; in place, *n_out rows
+ * remain.  CILHIP_ERR_INVALID: NULL n_out, a NULL array with n_model > 0, n_model >= 2^32 - 16, unknown mem.  n_model == 0: CILHIP_OK,
+ * no device needed. */
+int cilhip_fusion_remove_unstable3f(int device, float* model_xyz, float* model_normals, float* model_rgb, float* model_conf, size_t n_model, int mem,
+                                    float conf_thresh, size_t* n_out);
+
 /* ---- introspection (bench / tests) ----------------------------------------------------------- */
 typedef struct {
   int nx, ny, nz;        /* grid dims */
