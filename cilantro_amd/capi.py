@@ -32,6 +32,8 @@ SYMBOLS = [
     "cilhip_mcd_params_default", "cilhip_robust_normals_knn3f",
     "cilhip_depth_default_converter", "cilhip_depth_image_to_points3f", "cilhip_points_to_depth_image3f", "cilhip_points_to_index_map3f", "cilhip_set_projection",
     "cilhip_fusion_default_params", "cilhip_fuse_frame3f", "cilhip_fusion_remove_unstable3f",
+    "cilhip_warp_default_params", "cilhip_warp_field_create", "cilhip_warp_field_destroy", "cilhip_warp_field_estimate3f", "cilhip_warp_field_resample3f",
+    "cilhip_transform_points_per_point3f", "cilhip_warp_field_icp_run",
 ]
 
 
@@ -124,6 +126,17 @@ class FusionParams(C.Structure):
 class FusionCounts(C.Structure):
     _fields_ = [("visited", C.c_size_t), ("fused", C.c_size_t), ("appended", C.c_size_t), ("removed", C.c_size_t), ("untouched", C.c_size_t)]
 
+
+class WarpParams(C.Structure):
+    _fields_ = [("w_p2p", C.c_float), ("w_p2pl", C.c_float), ("w_reg", C.c_float), ("huber_boundary", C.c_float), ("max_gn_iter", C.c_size_t), ("gn_conv_tol", C.c_float),
+                ("max_cg_iter", C.c_size_t), ("cg_conv_tol", C.c_float)]
+
+
+class WarpStats(C.Structure):
+    _fields_ = [("gn_iterations", C.c_int), ("converged", C.c_int), ("cg_iterations_total", C.c_uint), ("last_cg_residual_norm2", C.c_float), ("max_delta_sq", C.c_float)]
+
+
+WARP_UNITY, WARP_RBF = 0, 1
 
 _lib = None
 
@@ -241,6 +254,15 @@ def load():
     L.cilhip_fuse_frame3f.argtypes = [C.c_int, f32p, f32p, f32p, f32p, C.c_size_t, C.c_size_t, f32p, f32p, f32p, C.c_size_t, C.c_int, f32p, f32p, C.c_size_t, C.c_size_t,
                                       C.POINTER(FusionParams), C.POINTER(C.c_size_t), C.POINTER(FusionCounts)]
     L.cilhip_fusion_remove_unstable3f.argtypes = [C.c_int, f32p, f32p, f32p, f32p, C.c_size_t, C.c_int, C.c_float, C.POINTER(C.c_size_t)]
+    L.cilhip_warp_default_params.argtypes = [C.POINTER(WarpParams)]
+    L.cilhip_warp_default_params.restype = None
+    L.cilhip_warp_field_create.argtypes = [C.c_int, C.c_size_t, C.c_size_t, vp, f32p, C.c_size_t, C.c_int, C.c_float, vp, f32p, C.c_size_t, C.c_int, C.c_float, C.c_int, C.POINTER(vp)]
+    L.cilhip_warp_field_destroy.argtypes = [vp]
+    L.cilhip_warp_field_destroy.restype = None
+    L.cilhip_warp_field_estimate3f.argtypes = [vp, f32p, f32p, C.c_size_t, f32p, vp, C.c_int, C.POINTER(WarpParams), f32p, C.POINTER(WarpStats)]
+    L.cilhip_warp_field_resample3f.argtypes = [vp, f32p, f32p, C.c_int]
+    L.cilhip_transform_points_per_point3f.argtypes = [C.c_int, f32p, f32p, C.c_size_t, C.c_int, f32p]
+    L.cilhip_warp_field_icp_run.argtypes = [vp, vp, C.POINTER(WarpParams), C.c_size_t, C.c_float, C.c_float, f32p, f32p, f32p, C.POINTER(IcpResult)]
     L.cilhip_icp_sums_from_keys.argtypes = [vp, vp, f64p]
     L.cilhip_icp_order_keys.argtypes = [vp, vp, vp]
     L.cilhip_icp_sums_from_ordered_keys.argtypes = [vp, vp, vp, f64p]
@@ -287,7 +309,7 @@ def load():
     L.cilhip_get_slab_violation_state.argtypes = [vp, C.POINTER(C.c_int), vp]
     for name in SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
-        if name not in ("cilhip_destroy", "cilhip_last_error", "cilhip_icp_default_params", "cilhip_option_info", "cilhip_cc_default_params", "cilhip_ms_default_params", "cilhip_mcd_params_default", "cilhip_depth_default_converter", "cilhip_fusion_default_params"):
+        if name not in ("cilhip_destroy", "cilhip_last_error", "cilhip_icp_default_params", "cilhip_option_info", "cilhip_cc_default_params", "cilhip_ms_default_params", "cilhip_mcd_params_default", "cilhip_depth_default_converter", "cilhip_fusion_default_params", "cilhip_warp_default_params", "cilhip_warp_field_destroy"):
             fn.restype = C.c_int
     _lib = L
     return L

@@ -981,3 +981,247 @@ class SimpleCombinedMetricAffineICP3f(SimpleCombinedMetricRigidICP3f):
     def __init__(self, dst_points, dst_normals, src_points, src_normals=None, device=0, stream=None):
         super().__init__(dst_points, dst_normals, src_points, None, device, stream)
         self._ctx.set_option("transform_mode", 1)
+
+
+# ---- non-rigid ICP on a warp field -------------------------------------------------------------------------
+def _warp_kernel(ev):
+    """a stock control / regularisation evaluator -> (kernel code, sigma) of cilhip_warp_field_create"""
+    kind = getattr(ev, "kind", None)
+    if kind == 0:
+        return capi.WARP_UNITY, 1.0
+    if kind == 2:
+        return capi.WARP_RBF, float(ev.sigma)
+    raise capi.CilhipError(capi.ERR_UNSUPPORTED, "warp field weights: UnityWeightEvaluator or RBFKernelWeightEvaluator (on the squared distance)")
+
+
+def _as_lists(neighborhoods, n):
+    """a neighbourhood set as cilhip_knn3f writes it, (indices (n, k) padded with 0xFFFFFFFF or -1, squared distances (n, k)): what
+    KDTree3f.kNNSearch returns (its third element, the counts, is not needed)"""
+    idx, d2 = neighborhoods[0], neighborhoods[1]
+    idx = np.ascontiguousarray(np.where(np.asarray(idx).astype(np.int64) < 0, capi.NONE_IDX, np.asarray(idx).astype(np.int64)).astype(np.uint32)).reshape(n, -1)
+    d2 = np.ascontiguousarray(d2, np.float32).reshape(n, -1)
+    if idx.shape != d2.shape:
+        raise ValueError("a neighbourhood set's indices and distances differ in shape")
+    return idx, d2
+
+
+def _Ts_to_abi(T):
+    return np.ascontiguousarray(np.asarray(T, np.float32).reshape(-1, 4, 4).transpose(0, 2, 1)).reshape(-1)
+
+
+def _Ts_from_abi(buf, n):
+    return np.asarray(buf, np.float32).reshape(n, 4, 4).transpose(0, 2, 1).copy()
+
+
+class WarpField:
+    """RAII wrapper of cilhip_warp_field: the graph between `n_src` source points and `n_ctrl` control nodes, with the solver's scratch."""
+
+    def __init__(self, n_src, n_ctrl, src_to_ctrl, ctrl_evaluator, regularization, reg_evaluator, device=0):
+        self._L = capi.load()
+        self.n_src, self.n_ctrl = int(n_src), int(n_ctrl)
+        ci, cd = _as_lists(src_to_ctrl, self.n_src)
+        ri, rd = _as_lists(regularization, self.n_ctrl)
+        ck, cs = _warp_kernel(ctrl_evaluator)
+        rk, rs = _warp_kernel(reg_evaluator)
+        h = C.c_void_p()
+        rc = self._L.cilhip_warp_field_create(int(device), self.n_src, self.n_ctrl, ci.ctypes.data, cd.ctypes.data, ci.shape[1], ck, cs, ri.ctypes.data, rd.ctypes.data,
+                                              ri.shape[1], rk, rs, capi.MEM_HOST, C.byref(h))
+        if rc != capi.OK:
+            raise capi.CilhipError(rc, self._L.cilhip_last_error(None).decode())
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.cilhip_warp_field_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ck(self, rc):
+        if rc != capi.OK:
+            raise capi.CilhipError(rc, self._L.cilhip_last_error(None).decode())
+
+    def estimate(self, dst_points, dst_normals, warped_src_points, nn_idx, params):
+        """one estimateSparseWarpFieldCombinedMetric call -> (control transforms (n_ctrl, 4, 4), capi.WarpStats)"""
+        d = np.ascontiguousarray(dst_points, np.float32).reshape(-1, 3)
+        n = None if dst_normals is None else np.ascontiguousarray(dst_normals, np.float32).reshape(-1, 3)
+        s = np.ascontiguousarray(warped_src_points, np.float32).reshape(self.n_src, 3)
+        nn = np.ascontiguousarray(nn_idx, np.uint32).reshape(self.n_src)
+        out = np.zeros(16 * self.n_ctrl, np.float32)
+        st = capi.WarpStats()
+        self._ck(self._L.cilhip_warp_field_estimate3f(self._h, d.ctypes.data, None if n is None else n.ctypes.data, len(d), s.ctypes.data, nn.ctypes.data, capi.MEM_HOST,
+                                                      C.byref(params), out.ctypes.data, C.byref(st)))
+        return _Ts_from_abi(out, self.n_ctrl), st
+
+    def resample(self, ctrl_transforms):
+        """resampleTransforms over the field's own lists -> (n_src, 4, 4)"""
+        t = _Ts_to_abi(ctrl_transforms)
+        if len(t) != 16 * self.n_ctrl:
+            raise ValueError("one transform per control node is needed")
+        out = np.zeros(16 * self.n_src, np.float32)
+        self._ck(self._L.cilhip_warp_field_resample3f(self._h, t.ctypes.data, out.ctypes.data, capi.MEM_HOST))
+        return _Ts_from_abi(out, self.n_src)
+
+
+def transformPoints(transforms, points, device=0):
+    """transformPoints with one transform per point (also PointCloud3f::transformed(TransformSet)): (n, 4, 4), (n, 3) -> (n, 3)"""
+    p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    t = _Ts_to_abi(transforms)
+    if len(t) != 16 * len(p):
+        raise ValueError("one transform per point is needed")
+    out = np.zeros_like(p)
+    L = capi.load()
+    rc = L.cilhip_transform_points_per_point3f(int(device), t.ctypes.data, p.ctypes.data, len(p), capi.MEM_HOST, out.ctypes.data)
+    if rc != capi.OK:
+        raise capi.CilhipError(rc, L.cilhip_last_error(None).decode())
+    return out
+
+
+def resampleTransforms(old_transforms, new_to_old_map, weight_evaluator=None, device=0):
+    """registration/warp_field_utilities.hpp:14-48, the list overload: per new point the old transforms blended with weights
+    eval(squared distance), through rotation(); the identity where the weights sum to 0"""
+    old = np.asarray(old_transforms, np.float32).reshape(-1, 4, 4)
+    idx, d2 = new_to_old_map[0], new_to_old_map[1]
+    n_new = len(np.asarray(idx))
+    ev = UnityWeightEvaluator() if weight_evaluator is None else weight_evaluator
+    self_lists = (np.arange(len(old), dtype=np.uint32).reshape(-1, 1), np.zeros((len(old), 1), np.float32))
+    wf = WarpField(n_new, len(old), (idx, d2), ev, self_lists, UnityWeightEvaluator(), device)
+    try:
+        return wf.resample(old)
+    finally:
+        wf.close()
+
+
+class SimpleCombinedMetricSparseRigidWarpFieldICP3f:
+    """registration/icp_common_instances.hpp (SimpleCombinedMetricSparseRigidWarpFieldICP3f) over CombinedMetricSparseWarpFieldICP
+    (icp_warp_field_combined_metric_sparse.hpp); defaults :67-74.  Neighbourhood sets are (indices (n, k), squared distances (n, k))
+    pairs as the k-NN mirrors return them.  Unity correspondence weights; control and regularisation weights Unity or RBF."""
+
+    def __init__(self, dst_points, dst_normals, src_points, src_to_ctrl_neighborhoods, num_ctrl_nodes, ctrl_regularization_neighborhoods, device=0, stream=None):
+        self._device = int(device)
+        self._ctx = Context(device, stream)
+        self._engine = CorrespondenceSearchHIP(self._ctx)
+        self._src = np.ascontiguousarray(src_points, np.float32).reshape(-1, 3)
+        self._ctx.set_target(dst_points, dst_normals)
+        self._ctx.set_source(self._src)
+        self._ctrl_lists, self._reg_lists, self.num_ctrl_nodes_ = src_to_ctrl_neighborhoods, ctrl_regularization_neighborhoods, int(num_ctrl_nodes)
+        self._control_eval, self._reg_eval = RBFKernelWeightEvaluator(), RBFKernelWeightEvaluator()
+        self._params = capi.WarpParams()
+        self._ctx._L.cilhip_warp_default_params(C.byref(self._params))
+        self.max_iterations_, self.convergence_tol_ = 15, np.float32(1e-5)      # icp_base.hpp:24-25
+        self.iterations_, self.last_delta_norm_, self.last_ncorr_ = 0, np.float32(np.inf), 0
+        self.transform_init_ = np.tile(np.eye(4, dtype=np.float32), (self.num_ctrl_nodes_, 1, 1))
+        self.transform_ = self.transform_init_.copy()
+        self.transform_dense_ = np.tile(np.eye(4, dtype=np.float32), (len(self._src), 1, 1))
+        self._field, self._field_key = None, None
+
+    def correspondenceSearchEngine(self):
+        return self._engine
+
+    def controlWeightEvaluator(self):
+        return self._control_eval
+
+    def regularizationWeightEvaluator(self):
+        return self._reg_eval
+
+    def _set(self, name, value):
+        setattr(self._params, name, value)
+        return self
+
+    def getPointToPointMetricWeight(self): return self._params.w_p2p
+    def setPointToPointMetricWeight(self, w): return self._set("w_p2p", float(w))
+    def getPointToPlaneMetricWeight(self): return self._params.w_p2pl
+    def setPointToPlaneMetricWeight(self, w): return self._set("w_p2pl", float(w))
+    def getStiffnessRegularizationWeight(self): return self._params.w_reg
+    def setStiffnessRegularizationWeight(self, w): return self._set("w_reg", float(w))
+    def getMaxNumberOfGaussNewtonIterations(self): return self._params.max_gn_iter
+    def setMaxNumberOfGaussNewtonIterations(self, n): return self._set("max_gn_iter", int(n))
+    def getGaussNewtonConvergenceTolerance(self): return self._params.gn_conv_tol
+    def setGaussNewtonConvergenceTolerance(self, tol): return self._set("gn_conv_tol", float(tol))
+    def getMaxNumberOfConjugateGradientIterations(self): return self._params.max_cg_iter
+    def setMaxNumberOfConjugateGradientIterations(self, n): return self._set("max_cg_iter", int(n))
+    def getConjugateGradientConvergenceTolerance(self): return self._params.cg_conv_tol
+    def setConjugateGradientConvergenceTolerance(self, tol): return self._set("cg_conv_tol", float(tol))
+    def getHuberLossBoundary(self): return self._params.huber_boundary
+    def setHuberLossBoundary(self, b): return self._set("huber_boundary", float(b))
+
+    def getMaxNumberOfIterations(self): return self.max_iterations_
+
+    def setMaxNumberOfIterations(self, n):
+        self.max_iterations_ = int(n)
+        return self
+
+    def getConvergenceTolerance(self): return self.convergence_tol_
+
+    def setConvergenceTolerance(self, tol):
+        self.convergence_tol_ = np.float32(tol)
+        return self
+
+    def getInitialTransform(self): return self.transform_init_
+
+    def setInitialTransform(self, T):
+        self.transform_init_ = np.asarray(T, np.float32).reshape(self.num_ctrl_nodes_, 4, 4).copy()
+        return self
+
+    def getNumberOfPerformedIterations(self): return self.iterations_
+    def getLastUpdateNorm(self): return self.last_delta_norm_
+    def hasConverged(self): return bool(self.last_delta_norm_ < self.convergence_tol_)
+    def getTransform(self): return self.transform_
+    def getDenseWarpField(self): return self.transform_dense_
+
+    def _warp_field(self):
+        key = (_warp_kernel(self._control_eval), _warp_kernel(self._reg_eval))
+        if self._field is None or key != self._field_key:      # (the weights belong to the graph: a new sigma is a new graph)
+            if self._field is not None:
+                self._field.close()
+            self._field = WarpField(len(self._src), self.num_ctrl_nodes_, self._ctrl_lists, self._control_eval, self._reg_lists, self._reg_eval, self._device)
+            self._field_key = key
+        return self._field
+
+    def estimate(self, max_iter=None, conv_tol=None):
+        if max_iter is not None:
+            self.max_iterations_ = int(max_iter)
+        if conv_tol is not None:
+            self.convergence_tol_ = np.float32(conv_tol)
+        wf = self._warp_field()
+        t0 = _Ts_to_abi(self.transform_init_)
+        ctrl, dense, res = np.zeros(16 * self.num_ctrl_nodes_, np.float32), np.zeros(16 * len(self._src), np.float32), capi.IcpResult()
+        self._ctx._ck(self._ctx._L.cilhip_warp_field_icp_run(self._ctx._h, wf._h, C.byref(self._params), self.max_iterations_, float(self.convergence_tol_),
+                                                           float(self._engine.max_distance_), t0.ctypes.data, ctrl.ctypes.data, dense.ctypes.data, C.byref(res)))
+        self._engine._corr = None
+        self.transform_, self.transform_dense_ = _Ts_from_abi(ctrl, self.num_ctrl_nodes_), _Ts_from_abi(dense, len(self._src))
+        self.iterations_, self.last_delta_norm_, self.last_ncorr_ = int(res.iterations), np.float32(res.last_delta_norm), int(res.last_ncorr)
+        return self
+
+    def getResiduals(self):
+        """icp_warp_field_combined_metric_sparse.hpp:243-263: per source point, against the nearest target point of its WARPED position,
+        w_p2p |d - q|^2 + w_p2pl (n . (d - q))^2 -- the context's residual path on the warped cloud (the context keeps the original source)"""
+        warped = transformPoints(self.transform_dense_, self._src, self._device)
+        self._ctx.set_source(warped)
+        try:
+            return self._ctx.compute_residuals(capi.METRIC_COMBINED, float(self._params.w_p2p), float(self._params.w_p2pl), np.eye(4, dtype=np.float32))
+        finally:
+            self._ctx.set_source(self._src)
+
+
+class SimpleCombinedMetricDenseRigidWarpFieldICP3f(SimpleCombinedMetricSparseRigidWarpFieldICP3f):
+    """SimpleCombinedMetricDenseRigidWarpFieldICP3f (icp_warp_field_combined_metric_dense.hpp): every source point is its own control node.
+    A thin mirror over the sparse entry with the lists ctrl_idx[i] = i, k_ctrl = 1 and Unity control weights: w = total = 1, so every
+    row of the sparse system is, term for term, the dense estimator's (warp_field_estimation.hpp:369-716; tests/test_warp_refs_cpu.py pins
+    the two systems against each other).  The dense code path is not ported separately."""
+
+    def __init__(self, dst_points, dst_normals, src_points, regularization_neighborhoods, device=0, stream=None):
+        n = len(np.asarray(src_points).reshape(-1, 3))
+        own = (np.arange(n, dtype=np.uint32).reshape(n, 1), np.zeros((n, 1), np.float32))
+        super().__init__(dst_points, dst_normals, src_points, own, n, regularization_neighborhoods, device, stream)
+        self._control_eval = UnityWeightEvaluator()
+
+    def controlWeightEvaluator(self):
+        raise AttributeError("the dense warp field has no control weights")
+
+    def getDenseWarpField(self):
+        return self.transform_

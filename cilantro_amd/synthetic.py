@@ -77,3 +77,24 @@ def make_pair(n_dst, n_src=None, with_normals=True, noise=0.05, perturb=0.3, src
         "dst": np.ascontiguousarray(dst), "dst_n": dst_n, "src": np.ascontiguousarray(src),
         "T_true": T_true, "h": h, "max_sq_dist": np.float32((2.0 * h) ** 2),
     }
+
+
+def make_surface(n, seed=45, extent=1.0):
+    """n points of a curved height field over [0, extent)^2 with unit normals (analytic, pointing to +z): float32 (n, 3), (n, 3)."""
+    u = uniform01(seed, 2 * n).reshape(n, 2).astype(np.float64) * extent
+    x, y = u[:, 0], u[:, 1]
+    k1, k2 = 2.0 * np.pi * 0.8 / extent, 2.0 * np.pi * 0.6 / extent
+    z = 0.12 * extent * np.sin(k1 * x) * np.cos(k2 * y) + 0.05 * extent * np.cos(1.7 * k1 * x + 0.9 * k2 * y)
+    zx = 0.12 * extent * k1 * np.cos(k1 * x) * np.cos(k2 * y) - 0.05 * extent * 1.7 * k1 * np.sin(1.7 * k1 * x + 0.9 * k2 * y)
+    zy = -0.12 * extent * k2 * np.sin(k1 * x) * np.sin(k2 * y) - 0.05 * extent * 0.9 * k2 * np.sin(1.7 * k1 * x + 0.9 * k2 * y)
+    nrm = np.stack([-zx, -zy, np.ones(n)], 1)
+    nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+    return np.ascontiguousarray(np.stack([x, y, z], 1), np.float32), np.ascontiguousarray(nrm, np.float32)
+
+
+def bend(points, amplitude=0.004, extent=1.0):
+    """points moved by a smooth, low-frequency displacement field of at most ~amplitude per axis (float32 in, float32 out)."""
+    p = np.asarray(points, np.float64)
+    k = 2.0 * np.pi / extent
+    d = np.stack([np.sin(0.7 * k * p[:, 1] + 0.3), np.cos(0.6 * k * p[:, 0] - 0.2), np.sin(0.5 * k * (p[:, 0] + p[:, 1]) + 0.9)], 1)
+    return np.ascontiguousarray(p + amplitude * d, np.float32)

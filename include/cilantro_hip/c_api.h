@@ -756,6 +756,76 @@ int cilhip_fuse_frame3f(int device, float* model_xyz, float* model_normals, floa
 int cilhip_fusion_remove_unstable3f(int device, float* model_xyz, float* model_normals, float* model_rgb, float* model_conf, size_t n_model, int mem,
                                     float conf_thresh, size_t* n_out);
 
+/* ---- non-rigid registration on a sparse warp field (rigid 3-D transforms, float) ---------------------------------------------
+ * estimateSparseWarpFieldCombinedMetric (registration/warp_field_estimation.hpp:1388-1846), resampleTransforms
+ * (registration/warp_field_utilities.hpp:14-48), transformPoints with one transform per point, and the loop of
+ * CombinedMetricSparseWarpFieldICP (icp_base.hpp:68-87 over icp_warp_field_combined_metric_sparse.hpp:202-240), the flow of
+ * examples/non_rigid_icp.cpp.  DESIGN.md section 17 has the contract; in short:
+ *   graph     n_ctrl control nodes; per source point a list of k_ctrl nodes and squared distances, per node a list of k_reg nodes
+ *             (itself first), both in the layout cilhip_knn3f writes: idx[n * k] padded with 0xFFFFFFFF, d2[n * k].  Weights
+ *             w = eval(d2): kernel 0 = Unity (1), 1 = RBF on the squared distance, pinned_expf((-0.5f / (sigma * sigma)) * d2).
+ *             total_i = the weights of point i summed in list order (:1456-1465).  Row i of the regularisation lists, entries
+ *             j >= 1, gives the arc (first entry, entry j) with weight sqrt(w_reg) * sqrt(eval(d2)); both directions are kept when
+ *             both rows list the pair; the lower node index comes first (:1748).  A row whose first entry is padding gives no arc.
+ *   unknowns  (a, b, c, t) per node, blended per source point by w / total; rotation Rz(c) Ry(b) Rx(a) (computeRotationTerms, :38-89)
+ *   rows      per matched source point three point rows (w_p2p > 0) and one plane row (w_p2pl > 0) with unity correspondence
+ *             weights; total_i == 0: rows of zeros (:1687-1690); per arc six sqrtHuberLoss rows (:10-36, :1750-1802)
+ *   solve     per Gauss-Newton step (A^T A) delta = A^T b by Eigen's Jacobi-preconditioned conjugate_gradient() from x0 = 0, matrix
+ *             free; vectors in f32, every dot product and gather accumulated in f64 in a fixed order (no floating-point atomics:
+ *             two runs give the same bits); tforms += delta; converged when max over nodes |delta_node|^2 < gn_conv_tol^2 (:1819-1829)
+ *   output    per node Rz(c) Ry(b) Rx(a) through rotation() (the closest rotation), translation t; 4 x 4 column-major
+ *   no data   no match in nn_idx, or w_p2p <= 0 and w_p2pl <= 0: identity transforms, converged = 0, gn_iterations = 0 (:1427-1433)
+ * cilhip_warp_field_create builds the graph once per (source, control graph) pair (mem: where the four list arrays live); the handle
+ * also owns the solver's scratch and is used by one thread at a time.  estimate3f: src_xyz is the ALREADY WARPED source, nn_idx the
+ * target index per source point (0xFFFFFFFF or any value >= n_dst: none); mem says where dst_xyz, dst_normals (may be NULL when
+ * w_p2pl == 0), src_xyz, nn_idx and ctrl_transforms_out live.  resample3f: the dense field T_i = sum_j w_ij T_j / total_i through
+ * rotation(), the identity where total_i == 0.  cilhip_transform_points_per_point3f: out_i = ((L0 x + L1 y) + L2 z) + t of T_i,
+ * every operation rounded once.
+ * CILHIP_ERR_INVALID (CILHIP_ERR_UNSUPPORTED for an unknown kernel code) before a device is touched, nothing written,
+ * cilhip_last_error(NULL) naming the rule: a NULL pointer; n_src == 0 or n_ctrl == 0; k_ctrl or k_reg outside 1 .. 32;
+ * n_src * k_ctrl >= 2^32 - 16 or n_ctrl * k_reg >= 2^28 - 1; a non-finite sigma, or sigma == 0 with the RBF kernel; a list index >= n_ctrl
+ * that is not 0xFFFFFFFF (lists in device memory: checked after the device is opened); unknown mem; a non-finite parameter, a negative
+ * weight, huber_boundary <= 0, an iteration limit >= 2^32 - 16; NULL dst_normals with w_p2pl > 0 and n_dst > 0. */
+typedef struct cilhip_warp_field cilhip_warp_field;
+typedef struct cilhip_warp_params {
+  float w_p2p;             /* 0     icp_warp_field_combined_metric_sparse.hpp:67 */
+  float w_p2pl;            /* 1     :68 */
+  float w_reg;             /* 1     :69 (stiffness) */
+  float huber_boundary;    /* 1e-4  warp_field_estimation.hpp:1411 */
+  size_t max_gn_iter;      /* 10    :1412 */
+  float gn_conv_tol;       /* 1e-5  :1413 */
+  size_t max_cg_iter;      /* 1000  :1414 */
+  float cg_conv_tol;       /* 1e-5  :1415 */
+} cilhip_warp_params;
+typedef struct cilhip_warp_stats {
+  int gn_iterations, converged;
+  unsigned cg_iterations_total;     /* Eigen's iterations() summed over the Gauss-Newton steps */
+  float last_cg_residual_norm2;     /* |A^T b - A^T A delta|^2 of the last step's recurrence */
+  float max_delta_sq;
+} cilhip_warp_stats;
+void cilhip_warp_default_params(cilhip_warp_params* params);
+int cilhip_warp_field_create(int device, size_t n_src, size_t n_ctrl, const uint32_t* ctrl_idx, const float* ctrl_d2, size_t k_ctrl, int ctrl_kernel,
+                             float ctrl_sigma, const uint32_t* reg_idx, const float* reg_d2, size_t k_reg, int reg_kernel, float reg_sigma, int mem,
+                             cilhip_warp_field** out);
+void cilhip_warp_field_destroy(cilhip_warp_field* field);
+int cilhip_warp_field_estimate3f(cilhip_warp_field* field, const float* dst_xyz, const float* dst_normals, size_t n_dst, const float* src_xyz,
+                                 const uint32_t* nn_idx, int mem, const cilhip_warp_params* params, float* ctrl_transforms_out /* n_ctrl * 16 */,
+                                 cilhip_warp_stats* stats_or_null);
+int cilhip_warp_field_resample3f(cilhip_warp_field* field, const float* ctrl_T /* n_ctrl * 16 */, float* dense_T_out /* n_src * 16 */, int mem);
+int cilhip_transform_points_per_point3f(int device, const float* T /* n * 16 */, const float* xyz, size_t n, int mem, float* out);
+/* The loop.  The context holds the target (with normals when w_p2pl > 0) and the ORIGINAL source, of the field's n_src points, on the
+ * field's device.  Per iteration: the dense field warps the source on the device, the context searches the warped cloud under the identity
+ * (max_sq_dist as in cilhip_find_correspondences), the estimator runs on the device-resident matches, T_ctrl[i] = T_iter[i] * T_ctrl[i],
+ * the field is resampled, last_delta_norm = sqrt(max_i(|R_iter,i - I|_F^2 + |t_iter,i|^2)); stops after max_iter iterations or when
+ * last_delta_norm < conv_tol.  ctrl_T0_or_null, ctrl_T_out (n_ctrl * 16) and dense_T_out_or_null (n_src * 16) are HOST arrays.  out->T
+ * is the identity (a warp field has no single transform), out->last_ncorr the last search's count.  Afterwards the context's source is
+ * the caller's again (restored by cilhip_set_source: optional source normals and colour features have to be set again) and it holds no
+ * correspondence set.  CILHIP_ERR_INVALID: a NULL pointer, a parameter rule of above, no target or source, sizes or devices that differ,
+ * w_p2pl > 0 without target normals.  CILHIP_ERR_UNSUPPORTED: a projection set on the context, a search direction other than
+ * SECOND_TO_FIRST, post-filters, correspondence weight evaluators, a feature adaptor, a target shard. */
+int cilhip_warp_field_icp_run(cilhip_ctx* ctx, cilhip_warp_field* field, const cilhip_warp_params* params, size_t max_iter, float conv_tol,
+                              float max_sq_dist, const float* ctrl_T0_or_null, float* ctrl_T_out, float* dense_T_out_or_null, cilhip_icp_result* out);
+
 /* ---- introspection (bench / tests) ----------------------------------------------------------- */
 typedef struct {
   int nx, ny, nz;        /* grid dims */

@@ -93,6 +93,17 @@ struct Correspondence {  // core/correspondence.hpp:9-52
 template <typename ScalarT, typename IndexT = size_t>
 using CorrespondenceSet = std::vector<Correspondence<ScalarT, IndexT>>;
 
+// core/nearest_neighbors.hpp:7-47 (what the k-NN mirrors of normal_estimation.hpp return and the warp-field classes below take)
+struct Neighbor {
+  size_t index;
+  float value;
+};
+typedef std::vector<Neighbor> Neighborhood;
+typedef std::vector<Neighborhood> NeighborhoodSet;
+
+// core/space_transformations.hpp: TransformSet<RigidTransform3f>, one transform per point or control node
+typedef std::vector<RigidTransform3f> RigidTransformSet3f;
+
 namespace internal {
 struct CtxDeleter {
   void operator()(cilhip_ctx* c) const { cilhip_destroy(c); }
@@ -704,6 +715,186 @@ public:
   SimpleCombinedMetricAffineICP3f(const ConstPointsView& dst_p, const ConstPointsView& dst_n, const ConstPointsView& src_p,
                                   const ConstPointsView& /*src_n*/, int device = 0)
       : SimpleCombinedMetricAffineICP3f(dst_p, dst_n, src_p, device) {}
+};
+
+// ---- non-rigid ICP on a warp field -------------------------------------------------------------------------
+// core/common_pair_evaluators.hpp:30-80: the control / regularisation weight of the warp-field classes, Unity or RBF on the squared
+// distance (the classes' default, RBFKernelWeightEvaluator<float, float, true>)
+class WarpWeightEvaluator {
+public:
+  enum Kind { Unity = 0, RBFKernel = 1 };
+  WarpWeightEvaluator(Kind kind = RBFKernel, float sigma = 1.0f) : kind_(kind), sigma_(sigma) {}
+  inline WarpWeightEvaluator& setKind(Kind k) { kind_ = k; return *this; }
+  inline WarpWeightEvaluator& setSigma(float sigma) { sigma_ = sigma; return *this; }
+  inline Kind kind() const { return kind_; }
+  inline float sigma() const { return sigma_; }
+
+private:
+  Kind kind_;
+  float sigma_;
+};
+
+namespace internal {
+struct WarpFieldDeleter {
+  void operator()(cilhip_warp_field* f) const { cilhip_warp_field_destroy(f); }
+};
+using WarpFieldPtr = std::unique_ptr<cilhip_warp_field, WarpFieldDeleter>;
+
+inline void check_stateless(int rc, const char* what) {
+  if (rc == CILHIP_OK) return;
+  const std::string msg = std::string(what) + ": " + cilhip_last_error(nullptr);
+  if (rc == CILHIP_ERR_UNSUPPORTED || rc == CILHIP_ERR_INVALID) throw std::invalid_argument(msg);
+  throw std::runtime_error(msg);
+}
+
+// a NeighborhoodSet as the padded rows cilhip_knn3f writes (k = the longest list)
+inline size_t to_lists(const NeighborhoodSet& nh, std::vector<uint32_t>& idx, std::vector<float>& d2) {
+  size_t k = 1;
+  for (const auto& l : nh) k = l.size() > k ? l.size() : k;
+  idx.assign(nh.size() * k ? nh.size() * k : 1, 0xFFFFFFFFu);
+  d2.assign(idx.size(), 0.0f);
+  for (size_t i = 0; i < nh.size(); ++i)
+    for (size_t j = 0; j < nh[i].size(); ++j) { idx[i * k + j] = (uint32_t)nh[i][j].index; d2[i * k + j] = nh[i][j].value; }
+  return k;
+}
+
+inline WarpFieldPtr make_warp_field(int device, size_t n_src, size_t n_ctrl, const NeighborhoodSet& ctrl, const WarpWeightEvaluator& ce, const NeighborhoodSet& reg,
+                                    const WarpWeightEvaluator& re) {
+  if (ctrl.size() != n_src || reg.size() != n_ctrl) throw std::invalid_argument("warp field: one control list per point and one regularisation list per control node are needed");
+  std::vector<uint32_t> ci, ri;
+  std::vector<float> cd, rd;
+  const size_t kc = to_lists(ctrl, ci, cd), kr = to_lists(reg, ri, rd);
+  cilhip_warp_field* f = nullptr;
+  check_stateless(cilhip_warp_field_create(device, n_src, n_ctrl, ci.data(), cd.data(), kc, (int)ce.kind(), ce.sigma(), ri.data(), rd.data(), kr, (int)re.kind(), re.sigma(),
+                                           CILHIP_MEM_HOST, &f), "warp_field_create");
+  return WarpFieldPtr(f);
+}
+}  // namespace internal
+
+// transformPoints with one transform per point (core/space_transformations.hpp; PointCloud3f::transformed(TransformSet) in point_cloud.hpp)
+inline std::vector<float> transformPoints(const RigidTransformSet3f& tforms, const ConstPointsView& points, int device = 0) {
+  if (tforms.size() != points.cols()) throw std::invalid_argument("transformPoints: one transform per point is needed");
+  std::vector<float> out(3 * points.cols());
+  static_assert(sizeof(RigidTransform3f) == 16 * sizeof(float), "RigidTransform3f is 16 packed floats");
+  internal::check_stateless(cilhip_transform_points_per_point3f(device, tforms.empty() ? nullptr : tforms[0].m, points.data(), points.cols(), CILHIP_MEM_HOST, out.data()),
+                            "transformPoints");
+  return out;
+}
+
+// registration/warp_field_utilities.hpp:14-48, the list overload
+inline RigidTransformSet3f resampleTransforms(const RigidTransformSet3f& old_transforms, const NeighborhoodSet& new_to_old_map,
+                                              const WarpWeightEvaluator& weight_evaluator = WarpWeightEvaluator(WarpWeightEvaluator::Unity), int device = 0) {
+  RigidTransformSet3f out(new_to_old_map.size());
+  if (out.empty() || old_transforms.empty()) return out;
+  NeighborhoodSet self(old_transforms.size());
+  for (size_t i = 0; i < self.size(); ++i) self[i].push_back(Neighbor{i, 0.0f});
+  internal::WarpFieldPtr f = internal::make_warp_field(device, out.size(), old_transforms.size(), new_to_old_map, weight_evaluator, self, WarpWeightEvaluator(WarpWeightEvaluator::Unity));
+  internal::check_stateless(cilhip_warp_field_resample3f(f.get(), old_transforms[0].m, out[0].m, CILHIP_MEM_HOST), "resampleTransforms");
+  return out;
+}
+
+// registration/icp_warp_field_combined_metric_sparse.hpp + icp_common_instances.hpp: SimpleCombinedMetricSparseRigidWarpFieldICP3f.
+// Unity correspondence weights; control and regularisation weights Unity or RBF (default RBF, the example sets only sigma).
+class SimpleCombinedMetricSparseRigidWarpFieldICP3f {
+public:
+  using Transform = RigidTransformSet3f;
+  using CorrespondenceSearchEngine = CorrespondenceSearchHIP;
+  using ResidualVector = std::vector<float>;
+
+  SimpleCombinedMetricSparseRigidWarpFieldICP3f(const ConstPointsView& dst_p, const ConstPointsView& dst_n, const ConstPointsView& src_p,
+                                                const NeighborhoodSet& src_to_ctrl_neighborhoods, size_t num_ctrl_nodes,
+                                                const NeighborhoodSet& ctrl_regularization_neighborhoods, int device = 0)
+      : device_(device), ctx_(internal::make_ctx(device)), engine_(ctx_.get()), src_(src_p.data(), src_p.data() + 3 * src_p.cols()),
+        ctrl_lists_(src_to_ctrl_neighborhoods), reg_lists_(ctrl_regularization_neighborhoods), num_ctrl_nodes_(num_ctrl_nodes),
+        transform_init_(num_ctrl_nodes), transform_(num_ctrl_nodes), transform_dense_(src_p.cols()) {
+    cilhip_warp_default_params(&prm_);
+    internal::check(ctx_.get(), cilhip_set_target(ctx_.get(), dst_p.data(), dst_n.data(), dst_p.cols(), CILHIP_MEM_HOST), "set_target");
+    internal::check(ctx_.get(), cilhip_set_source(ctx_.get(), src_.data(), src_p.cols(), CILHIP_MEM_HOST), "set_source");
+  }
+
+  inline CorrespondenceSearchEngine& correspondenceSearchEngine() { return engine_; }
+  inline WarpWeightEvaluator& controlWeightEvaluator() { return control_eval_; }
+  inline WarpWeightEvaluator& regularizationWeightEvaluator() { return reg_eval_; }
+
+  inline float getPointToPointMetricWeight() const { return prm_.w_p2p; }
+  inline SimpleCombinedMetricSparseRigidWarpFieldICP3f& setPointToPointMetricWeight(float w) { prm_.w_p2p = w; return *this; }
+  inline float getPointToPlaneMetricWeight() const { return prm_.w_p2pl; }
+  inline SimpleCombinedMetricSparseRigidWarpFieldICP3f& setPointToPlaneMetricWeight(float w) { prm_.w_p2pl = w; return *this; }
+  inline float getStiffnessRegularizationWeight() const { return prm_.w_reg; }
+  inline SimpleCombinedMetricSparseRigidWarpFieldICP3f& setStiffnessRegularizationWeight(float w) { prm_.w_reg = w; return *this; }
+  inline size_t getMaxNumberOfGaussNewtonIterations() const { return prm_.max_gn_iter; }
+  inline SimpleCombinedMetricSparseRigidWarpFieldICP3f& setMaxNumberOfGaussNewtonIterations(size_t n) { prm_.max_gn_iter = n; return *this; }
+  inline float getGaussNewtonConvergenceTolerance() const { return prm_.gn_conv_tol; }
+  inline SimpleCombinedMetricSparseRigidWarpFieldICP3f& setGaussNewtonConvergenceTolerance(float tol) { prm_.gn_conv_tol = tol; return *this; }
+  inline size_t getMaxNumberOfConjugateGradientIterations() const { return prm_.max_cg_iter; }
+  inline SimpleCombinedMetricSparseRigidWarpFieldICP3f& setMaxNumberOfConjugateGradientIterations(size_t n) { prm_.max_cg_iter = n; return *this; }
+  inline float getConjugateGradientConvergenceTolerance() const { return prm_.cg_conv_tol; }
+  inline SimpleCombinedMetricSparseRigidWarpFieldICP3f& setConjugateGradientConvergenceTolerance(float tol) { prm_.cg_conv_tol = tol; return *this; }
+  inline float getHuberLossBoundary() const { return prm_.huber_boundary; }
+  inline SimpleCombinedMetricSparseRigidWarpFieldICP3f& setHuberLossBoundary(float b) { prm_.huber_boundary = b; return *this; }
+
+  inline size_t getMaxNumberOfIterations() const { return max_iterations_; }
+  inline SimpleCombinedMetricSparseRigidWarpFieldICP3f& setMaxNumberOfIterations(size_t n) { max_iterations_ = n; return *this; }
+  inline float getConvergenceTolerance() const { return convergence_tol_; }
+  inline SimpleCombinedMetricSparseRigidWarpFieldICP3f& setConvergenceTolerance(float tol) { convergence_tol_ = tol; return *this; }
+  inline const Transform& getInitialTransform() const { return transform_init_; }
+  inline SimpleCombinedMetricSparseRigidWarpFieldICP3f& setInitialTransform(const Transform& t) {
+    if (t.size() != num_ctrl_nodes_) throw std::invalid_argument("setInitialTransform: one transform per control node is needed");
+    transform_init_ = t;
+    return *this;
+  }
+  inline size_t getNumberOfPerformedIterations() const { return iterations_; }
+  inline float getLastUpdateNorm() const { return last_delta_norm_; }
+  inline bool hasConverged() const { return last_delta_norm_ < convergence_tol_; }
+  inline const Transform& getTransform() const { return transform_; }              // the control nodes' transforms
+  inline const Transform& getDenseWarpField() const { return transform_dense_; }   // one per source point
+  inline size_t getNumberOfLastCorrespondences() const { return last_ncorr_; }      // (extension)
+
+  SimpleCombinedMetricSparseRigidWarpFieldICP3f& estimate() {
+    // (the weights belong to the graph: built here, with the sigmas set so far)
+    internal::WarpFieldPtr f = internal::make_warp_field(device_, src_.size() / 3, num_ctrl_nodes_, ctrl_lists_, control_eval_, reg_lists_, reg_eval_);
+    cilhip_icp_result r;
+    internal::check(ctx_.get(), cilhip_warp_field_icp_run(ctx_.get(), f.get(), &prm_, max_iterations_, convergence_tol_, engine_.getMaxDistance(),
+                                                         transform_init_.empty() ? nullptr : transform_init_[0].m, transform_.empty() ? nullptr : transform_[0].m,
+                                                         transform_dense_.empty() ? nullptr : transform_dense_[0].m, &r), "estimate");
+    engine_.invalidateFetched();
+    iterations_ = r.iterations;
+    last_delta_norm_ = r.last_delta_norm;
+    last_ncorr_ = r.last_ncorr;
+    return *this;
+  }
+  inline SimpleCombinedMetricSparseRigidWarpFieldICP3f& estimate(size_t max_iter, float conv_tol) {
+    max_iterations_ = max_iter;
+    convergence_tol_ = conv_tol;
+    return estimate();
+  }
+
+  // icp_warp_field_combined_metric_sparse.hpp:243-263: the context's residual path on the warped cloud (the context keeps the original source)
+  ResidualVector getResiduals() {
+    const size_t n = src_.size() / 3;
+    const std::vector<float> warped = transformPoints(transform_dense_, ConstPointsView(src_.data(), n), device_);
+    std::vector<float> res(n ? n : 1);
+    static const float I16[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    internal::check(ctx_.get(), cilhip_set_source(ctx_.get(), warped.data(), n, CILHIP_MEM_HOST), "set_source");
+    const int rc = cilhip_compute_residuals(ctx_.get(), CILHIP_METRIC_COMBINED, prm_.w_p2p, prm_.w_p2pl, I16, res.data(), CILHIP_MEM_HOST);
+    internal::check(ctx_.get(), cilhip_set_source(ctx_.get(), src_.data(), n, CILHIP_MEM_HOST), "set_source");
+    internal::check(ctx_.get(), rc, "getResiduals");
+    res.resize(n);
+    return res;
+  }
+
+private:
+  int device_;
+  internal::CtxPtr ctx_;
+  CorrespondenceSearchEngine engine_;
+  std::vector<float> src_;
+  NeighborhoodSet ctrl_lists_, reg_lists_;
+  size_t num_ctrl_nodes_;
+  WarpWeightEvaluator control_eval_, reg_eval_;
+  cilhip_warp_params prm_;
+  size_t max_iterations_ = 15, iterations_ = 0, last_ncorr_ = 0;      // icp_base.hpp:24-25
+  float convergence_tol_ = 1e-5f, last_delta_norm_ = std::numeric_limits<float>::infinity();
+  Transform transform_init_, transform_, transform_dense_;
 };
 
 #ifdef CILANTRO_HIP_HAVE_EIGEN

@@ -23,13 +23,7 @@
 
 namespace cilantro_hip {
 
-// core/nearest_neighbors.hpp:7-47
-struct Neighbor {
-  size_t index;
-  float value;
-};
-typedef std::vector<Neighbor> Neighborhood;
-typedef std::vector<Neighborhood> NeighborhoodSet;
+// (Neighbor / Neighborhood / NeighborhoodSet, core/nearest_neighbors.hpp:7-47: icp.hpp, which the warp-field classes share them with)
 
 class KDTree3f {
 public:

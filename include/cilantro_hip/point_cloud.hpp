@@ -10,6 +10,7 @@
 //   utilities/point_cloud.hpp:201-245             removeInvalidPoints / Normals / Colors / Data: host compaction, in the order the reference's remove() (:154-198) leaves
 //   utilities/point_cloud.hpp:247-290             gridDownsample / gridDownsampled (on the device: grid_downsampler.hpp); member
 //                                                 templates as in the reference, so a program that never calls them links without the library
+//   utilities/point_cloud.hpp:445-457             transformed(TransformSet): one rigid transform per point (on the device: icp.hpp transformPoints)
 //   utilities/point_cloud.hpp:87-116, :463-499    the depth-image constructor, fromDepthImage / fromRGBDImages (on the device:
 //                                                 image_point_cloud_conversions.hpp); intrinsics: 9 floats, column-major
 #pragma once
@@ -82,6 +83,21 @@ public:
     PointCloud3f res = gridDownsampled<GridPointScalarT>(bin_size, min_points_in_bin, parallel);
     points.swap(res.points); normals.swap(res.normals); colors.swap(res.colors);
     return *this;
+  }
+
+  // point_cloud.hpp:445-457 with a TransformSet: one rigid transform per point, on the device (examples/non_rigid_icp.cpp:154); normals
+  // turn with the linear part.  A member template like the ones above: a program that never calls it links without the library
+  template <class TransformSetT = RigidTransformSet3f>
+  PointCloud3f transformed(const TransformSetT& tforms, int device = 0) const {
+    PointCloud3f cloud;
+    cloud.points = transformPoints(tforms, ConstPointsView(points), device);
+    if (hasNormals()) {
+      TransformSetT linear(tforms);
+      for (auto& t : linear) t.translation(0) = t.translation(1) = t.translation(2) = 0.0f;
+      cloud.normals = transformPoints(linear, ConstPointsView(normals), device);
+    }
+    if (hasColors()) cloud.colors = colors;
+    return cloud;
   }
 
   // point_cloud.hpp:268-290
