@@ -34,6 +34,8 @@ SYMBOLS = [
     "cilhip_fusion_default_params", "cilhip_fuse_frame3f", "cilhip_fusion_remove_unstable3f",
     "cilhip_warp_default_params", "cilhip_warp_field_create", "cilhip_warp_field_destroy", "cilhip_warp_field_estimate3f", "cilhip_warp_field_resample3f",
     "cilhip_transform_points_per_point3f", "cilhip_warp_field_icp_run",
+    "cilhip_nn_graph_matrix", "cilhip_sparse_from_csr", "cilhip_sparse_info", "cilhip_sparse_get", "cilhip_sparse_destroy",
+    "cilhip_spectral_default_params", "cilhip_spectral_embedding", "cilhip_kmeans_nd",
 ]
 
 
@@ -137,6 +139,17 @@ class WarpStats(C.Structure):
 
 
 WARP_UNITY, WARP_RBF = 0, 1
+
+
+class SpectralParams(C.Structure):
+    _fields_ = [("max_num_clusters", C.c_size_t), ("estimate_num_clusters", C.c_int), ("laplacian_type", C.c_int), ("max_outer", C.c_size_t), ("degree", C.c_int),
+                ("guard", C.c_int)]
+
+
+class SpectralResult(C.Structure):
+    _fields_ = [("num_clusters", C.c_size_t), ("num_eigenvalues", C.c_size_t), ("n_converged", C.c_size_t), ("outer_iterations", C.c_size_t), ("block_products", C.c_size_t),
+                ("max_residual", C.c_double), ("wall_ms", C.c_double)]
+
 
 _lib = None
 
@@ -263,6 +276,16 @@ def load():
     L.cilhip_warp_field_resample3f.argtypes = [vp, f32p, f32p, C.c_int]
     L.cilhip_transform_points_per_point3f.argtypes = [C.c_int, f32p, f32p, C.c_size_t, C.c_int, f32p]
     L.cilhip_warp_field_icp_run.argtypes = [vp, vp, C.POINTER(WarpParams), C.c_size_t, C.c_float, C.c_float, f32p, f32p, f32p, C.POINTER(IcpResult)]
+    L.cilhip_nn_graph_matrix.argtypes = [C.c_int, C.c_size_t, vp, vp, f32p, C.c_size_t, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.POINTER(vp)]
+    L.cilhip_sparse_from_csr.argtypes = [C.c_int, C.c_size_t, vp, vp, f32p, C.c_int, C.POINTER(vp)]
+    L.cilhip_sparse_info.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.cilhip_sparse_get.argtypes = [vp, vp, vp, f32p, C.c_int]
+    L.cilhip_sparse_destroy.argtypes = [vp]
+    L.cilhip_sparse_destroy.restype = None
+    L.cilhip_spectral_default_params.argtypes = [C.POINTER(SpectralParams)]
+    L.cilhip_spectral_default_params.restype = None
+    L.cilhip_spectral_embedding.argtypes = [vp, C.POINTER(SpectralParams), f32p, f32p, C.c_int, C.POINTER(SpectralResult)]
+    L.cilhip_kmeans_nd.argtypes = [C.c_int, f32p, C.c_size_t, C.c_size_t, C.c_int, f32p, C.c_size_t, C.c_size_t, C.c_float, vp, C.POINTER(C.c_size_t)]
     L.cilhip_icp_sums_from_keys.argtypes = [vp, vp, f64p]
     L.cilhip_icp_order_keys.argtypes = [vp, vp, vp]
     L.cilhip_icp_sums_from_ordered_keys.argtypes = [vp, vp, vp, f64p]
@@ -309,7 +332,8 @@ def load():
     L.cilhip_get_slab_violation_state.argtypes = [vp, C.POINTER(C.c_int), vp]
     for name in SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
-        if name not in ("cilhip_destroy", "cilhip_last_error", "cilhip_icp_default_params", "cilhip_option_info", "cilhip_cc_default_params", "cilhip_ms_default_params", "cilhip_mcd_params_default", "cilhip_depth_default_converter", "cilhip_fusion_default_params", "cilhip_warp_default_params", "cilhip_warp_field_destroy"):
+        if name not in ("cilhip_destroy", "cilhip_last_error", "cilhip_icp_default_params", "cilhip_option_info", "cilhip_cc_default_params", "cilhip_ms_default_params", "cilhip_mcd_params_default", "cilhip_depth_default_converter", "cilhip_fusion_default_params", "cilhip_warp_default_params", "cilhip_warp_field_destroy", "cilhip_sparse_destroy",
+                        "cilhip_spectral_default_params"):
             fn.restype = C.c_int
     _lib = L
     return L

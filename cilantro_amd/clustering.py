@@ -1,6 +1,8 @@
 """Python mirrors of cilantro's KMeans3f (clustering/kmeans.hpp), ConnectedComponentExtraction3f
-(clustering/connected_component_extraction.hpp; second part of this file) and MeanShift3f (clustering/mean_shift.hpp; last part) on top
-of the C ABI (cilhip_kmeans3f, cilhip_connected_components3f, cilhip_mean_shift3f).
+(clustering/connected_component_extraction.hpp; second part of this file), MeanShift3f (clustering/mean_shift.hpp; third part) and
+SpectralClustering with KMeansXf and the sparse nearest-neighbour graph matrix (clustering/spectral_clustering.hpp; last part) on top
+of the C ABI (cilhip_kmeans3f, cilhip_connected_components3f, cilhip_mean_shift3f, cilhip_nn_graph_matrix / cilhip_spectral_embedding /
+cilhip_kmeans_nd).
 
     km = KMeans3f(points)
     km.cluster(initial_centroids, max_iter=100, tol=eps)      # kmeans.hpp:24-30
@@ -437,3 +439,244 @@ class MeanShift3f:
         """per cluster, ascending seed indices"""
         off, mem = self._r["offsets"], self._r["members"]
         return [mem[int(off[c]):int(off[c + 1])] for c in range(self.getNumberOfClusters())]
+
+
+# ---- SpectralClustering (clustering/spectral_clustering.hpp) ---------------------------------------------------------------------
+# The contract is stated in include/cilantro_hip/c_api.h (rules S1-S6) and DESIGN.md section 18.  There is no CPU path.
+class GraphLaplacianType:
+    """spectral_clustering.hpp:44"""
+
+    UNNORMALIZED, NORMALIZED_SYMMETRIC, NORMALIZED_RANDOM_WALK = 0, 1, 2
+
+
+def _ptr(a):
+    return None if a is None else (a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data)
+
+
+class SparseMatrix:
+    """owner of a cilhip_sparse handle (a CSR matrix on the device); close() or the garbage collector frees it"""
+
+    def __init__(self, handle, device):
+        self._L, self._h, self.device = capi.load(), handle, device
+
+    @classmethod
+    def from_csr(cls, n, offsets, columns, values, device=0):
+        """cilhip_sparse_from_csr: numpy arrays, or device tensors (int64 offsets, int32 columns, float32 values)"""
+        L = capi.load()
+        if hasattr(values, "is_cuda") and values.is_cuda:
+            import torch
+
+            if values.device.index is not None:
+                device = values.device.index
+            off, col, val = offsets.to(torch.int64).contiguous(), columns.to(torch.int32).contiguous(), values.to(torch.float32).contiguous()
+            torch.cuda.synchronize(values.device)
+            mem = capi.MEM_DEVICE
+        else:
+            off, col, val = np.ascontiguousarray(offsets, np.uint64), np.ascontiguousarray(columns, np.uint32), np.ascontiguousarray(values, np.float32)
+            col, val = (col if col.size else np.zeros(1, np.uint32)), (val if val.size else np.zeros(1, np.float32))
+            mem = capi.MEM_HOST
+        if len(off) != n + 1:
+            raise ValueError("offsets must have n + 1 entries")
+        h = C.c_void_p()
+        rc = L.cilhip_sparse_from_csr(int(device), int(n), _ptr(off), _ptr(col), _ptr(val), mem, C.byref(h))
+        if rc != capi.OK:
+            raise capi.CilhipError(rc, "cilhip_sparse_from_csr: " + L.cilhip_last_error(None).decode())
+        return cls(h, int(device))
+
+    @classmethod
+    def from_dense(cls, dense, device=0):
+        """a dense affinity matrix, converted to CSR on the host (the entries that are not zero)"""
+        a = np.asarray(dense.cpu() if hasattr(dense, "cpu") else dense, np.float32)
+        if a.ndim != 2 or a.shape[0] != a.shape[1]:
+            raise ValueError("a dense affinity matrix is square")
+        rows, cols = np.nonzero(a)
+        off = np.concatenate(([0], np.cumsum(np.bincount(rows, minlength=a.shape[0])))).astype(np.uint64)
+        return cls.from_csr(a.shape[0], off, cols.astype(np.uint32), a[rows, cols], device)
+
+    def info(self):
+        """-> (n, nnz, longest row)"""
+        v = [C.c_size_t(0) for _ in range(3)]
+        self._L.cilhip_sparse_info(self._h, *[C.byref(x) for x in v])
+        return tuple(int(x.value) for x in v)
+
+    def get(self, on_device=False):
+        """cilhip_sparse_get -> (offsets[n + 1], columns[nnz], values[nnz]): numpy (uint64, uint32, float32) or device tensors (int64, int32, float32)"""
+        n, nnz, _ = self.info()
+        if on_device:
+            import torch
+
+            dev = torch.device("cuda", self.device)
+            out = [torch.empty(n + 1, dtype=torch.int64, device=dev), torch.empty(max(nnz, 1), dtype=torch.int32, device=dev), torch.empty(max(nnz, 1), dtype=torch.float32, device=dev)]
+            torch.cuda.synchronize(dev)
+        else:
+            out = [np.empty(n + 1, np.uint64), np.empty(max(nnz, 1), np.uint32), np.empty(max(nnz, 1), np.float32)]
+        rc = self._L.cilhip_sparse_get(self._h, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), capi.MEM_DEVICE if on_device else capi.MEM_HOST)
+        if rc != capi.OK:
+            raise capi.CilhipError(rc, "cilhip_sparse_get: " + self._L.cilhip_last_error(None).decode())
+        return out[0], out[1][:nnz], out[2][:nnz]
+
+    def close(self):
+        if self._h:
+            self._L.cilhip_sparse_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+def nn_graph_sparse_matrix(neighbors, evaluator=None, force_symmetry=False, duplicates=0, device=0):
+    """getNNGraphFunctionValueSparseMatrix (nearest_neighbor_graph_utilities.hpp:89-118; duplicates=1: the dense variant's assignment rule,
+    :63-87) -> SparseMatrix.  neighbors: (idx[n, k], d2[n, k]) as KDTree3f.kNNSearch returns them (-1 or 0xFFFFFFFF pads a short list) or
+    (offsets[n + 1], idx, d2) as radiusSearch does; numpy arrays or device tensors.  The first entry of a list, the point itself, is kept."""
+    L = capi.load()
+    ev = evaluator if evaluator is not None else UnityWeightEvaluator()
+    offsets = None
+    if len(neighbors) == 3 and np.ndim(neighbors[1]) == 1:
+        offsets, idx, d2 = neighbors
+    else:
+        idx, d2 = neighbors[0], neighbors[1]
+    on_device = hasattr(idx, "is_cuda") and idx.is_cuda
+    if on_device:
+        import torch
+
+        if idx.device.index is not None:
+            device = idx.device.index
+        ix = idx.to(torch.int32).contiguous()
+        dd = None if d2 is None else d2.to(device=idx.device, dtype=torch.float32).contiguous()
+        off = None if offsets is None else offsets.to(device=idx.device, dtype=torch.int64).contiguous()
+        torch.cuda.synchronize(idx.device)
+        shape, mem = tuple(ix.shape), capi.MEM_DEVICE
+    else:
+        ix = np.ascontiguousarray(np.asarray(idx).astype(np.int64) & 0xFFFFFFFF, np.uint32)
+        dd = None if d2 is None else np.ascontiguousarray(d2, np.float32)
+        off = None if offsets is None else np.ascontiguousarray(offsets, np.uint64)
+        shape, mem = ix.shape, capi.MEM_HOST
+    if off is None:
+        if len(shape) != 2:
+            raise ValueError("a k-NN list is an n x k array")
+        n, k_or_total = int(shape[0]), int(shape[1])
+    else:
+        n, k_or_total = len(off) - 1, int(np.prod(shape))
+        if not on_device and ix.size == 0:
+            ix, dd = np.zeros(1, np.uint32), (None if dd is None else np.zeros(1, np.float32))
+    h = C.c_void_p()
+    rc = L.cilhip_nn_graph_matrix(int(device), n, _ptr(off), _ptr(ix), _ptr(dd), k_or_total, mem, int(ev.kind), C.c_float(ev.sigma), int(bool(force_symmetry)), int(duplicates),
+                                  C.byref(h))
+    if rc != capi.OK:
+        raise capi.CilhipError(rc, "cilhip_nn_graph_matrix: " + L.cilhip_last_error(None).decode())
+    return SparseMatrix(h, int(device))
+
+
+def spectral_embedding(affinities, max_num_clusters, estimate_num_clusters=False, laplacian_type=GraphLaplacianType.NORMALIZED_RANDOM_WALK, on_device=False, max_outer=None,
+                       degree=None, guard=None, raise_unconverged=True):
+    """cilhip_spectral_embedding -> (embedded[n, num_clusters] f32, eigenvalues[nev] f32, result dict).  Raises when the solver gave up
+    (n_converged < num_eigenvalues after max_outer iterations) unless raise_unconverged is False."""
+    L = capi.load()
+    n = affinities.info()[0]
+    prm = capi.SpectralParams()
+    L.cilhip_spectral_default_params(C.byref(prm))
+    prm.max_num_clusters, prm.estimate_num_clusters, prm.laplacian_type = int(max_num_clusters), int(bool(estimate_num_clusters)), int(laplacian_type)
+    for key, v in (("max_outer", max_outer), ("degree", degree), ("guard", guard)):
+        if v is not None:
+            setattr(prm, key, int(v))
+    room = max(min(int(max_num_clusters), 16), 2)
+    if on_device:
+        import torch
+
+        dev = torch.device("cuda", affinities.device)
+        emb = torch.empty((n, room), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+    else:
+        emb = np.empty((n, room), np.float32)
+    ev = np.zeros(room + 1, np.float32)
+    res = capi.SpectralResult()
+    rc = L.cilhip_spectral_embedding(affinities._h, C.byref(prm), _ptr(emb), ev.ctypes.data, capi.MEM_DEVICE if on_device else capi.MEM_HOST, C.byref(res))
+    if rc != capi.OK:
+        raise capi.CilhipError(rc, "cilhip_spectral_embedding: " + L.cilhip_last_error(None).decode())
+    info = {k: getattr(res, k) for k, _ in capi.SpectralResult._fields_}
+    if raise_unconverged and res.n_converged < res.num_eigenvalues:
+        raise capi.CilhipError(capi.ERR_UNSUPPORTED, "cilhip_spectral_embedding: %d of %d eigenpairs converged in %d outer iterations (largest residual %.3g)"
+                               % (res.n_converged, res.num_eigenvalues, res.outer_iterations, res.max_residual))
+    nc = int(res.num_clusters)
+    flat = emb.reshape(-1)[: n * nc]      # (point-major n x num_clusters at the start of the buffer)
+    return flat.reshape(n, nc), ev[: res.num_eigenvalues].copy(), info
+
+
+class KMeansXf(KMeans3f):
+    """KMeans<float, Dynamic> (kmeans.hpp:67-194), brute-force branch, 1 <= dim <= 16 (cilhip_kmeans_nd, rule S6).  data: n x dim, a numpy
+    array or a device tensor.  use_kd_tree is accepted and changes nothing: the kd-tree branch is not built in D dimensions."""
+
+    def cluster(self, centroids_or_k, max_iter=100, tol=float(np.finfo(np.float32).eps), use_kd_tree=False, seed=None):
+        x = self._data
+        on_device = hasattr(x, "is_cuda") and x.is_cuda
+        if on_device:
+            import torch
+
+            x = x.to(torch.float32).contiguous()
+            device = x.device.index if x.device.index is not None else self._device
+            torch.cuda.synchronize(x.device)
+        else:
+            x, device = np.ascontiguousarray(x, np.float32), self._device
+        if x.ndim != 2:
+            raise ValueError("the points are an n x dim array")
+        n, dim = int(x.shape[0]), int(x.shape[1])
+        if np.isscalar(centroids_or_k):
+            k = max(1, min(int(centroids_or_k), n))
+            idx = np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+            cent = np.ascontiguousarray((x[torch.as_tensor(idx, device=x.device)].cpu().numpy() if on_device else x[idx]), np.float32)
+        else:
+            cent = np.ascontiguousarray(centroids_or_k.cpu() if hasattr(centroids_or_k, "cpu") else centroids_or_k, np.float32).reshape(-1, dim).copy()
+        if on_device:
+            labels = torch.zeros(n, dtype=torch.int32, device=x.device)
+            torch.cuda.synchronize(x.device)
+        else:
+            labels = np.zeros(n, np.uint32)
+        iters = C.c_size_t(0)
+        rc = self._L.cilhip_kmeans_nd(int(device), _ptr(x), n, dim, capi.MEM_DEVICE if on_device else capi.MEM_HOST, cent.ctypes.data, len(cent), int(max_iter), C.c_float(tol),
+                                      _ptr(labels), C.byref(iters))
+        if rc != capi.OK:
+            raise capi.CilhipError(rc, "cilhip_kmeans_nd: " + self._L.cilhip_last_error(None).decode())
+        self.cluster_centroids_ = cent
+        self.point_to_cluster_index_map_ = (labels.cpu().numpy() if on_device else labels).astype(np.int64)
+        self.iteration_count_ = int(iters.value)
+        return self
+
+
+class SpectralClustering(KMeansXf):
+    """SpectralClustering<float, Dynamic> (spectral_clustering.hpp:316-416): the Laplacian embedding of an affinity matrix, then k-means
+    on the embedded points with num_clusters centroids.
+
+        sc = SpectralClustering(affinities, 4, True, GraphLaplacianType.NORMALIZED_RANDOM_WALK)
+    affinities: a SparseMatrix (nn_graph_sparse_matrix), a CSR triple (offsets, columns, values) or a dense square array (converted to CSR
+    on the host).  The reference starts k-means from random points (std::random_device): `seed` seeds that draw, or
+    initial_centroid_indices names the points.  kmeans_use_kd_tree is accepted and changes nothing (KMeansXf)."""
+
+    def __init__(self, affinities, max_num_clusters, estimate_num_clusters=False, laplacian_type=GraphLaplacianType.NORMALIZED_RANDOM_WALK, kmeans_max_iter=100,
+                 kmeans_conv_tol=float(np.finfo(np.float32).eps), kmeans_use_kd_tree=False, seed=None, initial_centroid_indices=None, device=0):
+        own = not isinstance(affinities, SparseMatrix)
+        if own:
+            if isinstance(affinities, (tuple, list)) and len(affinities) == 3:
+                affinities = SparseMatrix.from_csr(len(affinities[0]) - 1, affinities[0], affinities[1], affinities[2], device)
+            else:
+                affinities = SparseMatrix.from_dense(affinities, device)
+        try:
+            self.embedded_points_, self.computed_eigenvalues_, self.embedding_info_ = spectral_embedding(affinities, max_num_clusters, estimate_num_clusters, laplacian_type)
+        finally:
+            if own:
+                affinities.close()
+        super().__init__(self.embedded_points_, affinities.device)
+        k = self.embedded_points_.shape[1]
+        if initial_centroid_indices is not None:
+            start = self.embedded_points_[np.asarray(initial_centroid_indices, np.int64)[:k]]
+        else:
+            start = k
+        self.cluster(start, kmeans_max_iter, kmeans_conv_tol, kmeans_use_kd_tree, seed)
+
+    def getEmbeddedPoints(self):
+        """n x num_clusters (the reference's dim x n, column-major: the same bytes)"""
+        return self.embedded_points_
+
+    def getComputedEigenValues(self):
+        return self.computed_eigenvalues_
+
+    def getEmbeddingDimension(self):
+        return int(self.embedded_points_.shape[1])

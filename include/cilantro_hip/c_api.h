@@ -1169,6 +1169,87 @@ int cilhip_debug_counters(cilhip_ctx* ctx, uint32_t out[2]);
  * "nothing leaked" can be checked exactly, without reading the device's free memory (which other processes move). */
 int cilhip_debug_live_allocations(unsigned long long out[2]);
 
+/* ---- spectral clustering: sparse affinities, Laplacian embedding, k-means in D dimensions ---------------------------------------- */
+/* clustering/spectral_clustering.hpp (computeLaplacianSpectralEmbedding, sparse input, :191-312; SpectralClustering :398-416) with
+ * utilities/nearest_neighbor_graph_utilities.hpp:63-118 in front of it and KMeans<float, Dynamic> (kmeans.hpp:67-194) behind it, for
+ * float.  DESIGN.md section 18 is the long form; tests/_spectral_refs.py restates every rule in numpy.
+ *   S1 graph     a neighbour list (of cilhip_knn3f: idx[n*k] padded with 0xFFFFFFFF and d2[n*k], offsets == NULL, k_or_total = k; or CSR
+ *                lists as cilhip_radius_search3f returns them: offsets[n + 1], idx, d2, k_or_total = offsets[n]) becomes the sparse matrix
+ *                of getNNGraphFunctionValueSparseMatrix (:89-118).  Entry e of point i's list with neighbour j = idx[e] (the first entry, the
+ *                point itself, is KEPT, as in the reference) gives val = 1 (kernel_kind 0), d2[e] (1) or exp(coeff * d2[e]) (2, coeff =
+ *                -0.5f / (sigma * sigma), the pinned f32 arithmetic of cilhip_ms_params) and M(j, i) = val; with force_symmetry also M(i, j)
+ *                = val.  duplicates = 0: values that fall on one (row, column) are SUMMED (setFromTriplets: a mutual pair carries 2 val and
+ *                the self entry 2 val; the sum runs in the order (i, e) of the contributing list entries, which for two terms is order-free).
+ *                duplicates = 1: the dense variant's rule (:63-87), assignment -- the contribution with the largest (i, e) stays.  The build
+ *                runs on the device (count, scan, fill, per-row sort, merge) with integer atomics only: the result does not depend on
+ *                scheduling.  The matrix: CSR, columns strictly ascending per row, f32 values, uint64 offsets.
+ *                CILHIP_ERR_INVALID (cilhip_last_error(NULL) names the rule, *out untouched): NULL idx or out; NULL d2 unless kernel_kind is 0;
+ *                n == 0 or n >= 2^32 - 16; k == 0 or n * k >= 2^32 in the k-NN layout; unknown kernel_kind, mem or duplicates; an RBF sigma
+ *                not finite and positive; and, found on the device, an index >= n that is not the padding, offsets that are not ascending or
+ *                whose last entry is not k_or_total.
+ *   S2 operator  W is taken as symmetric (the caller's promise, as in the reference).  d_i = the f64 sum of row i in column order
+ *                (deviation: the reference sums in f32).  laplacian_type 0 UNNORMALIZED: A = D - W, spectrum in [0, 2 max d]; 1
+ *                NORMALIZED_SYMMETRIC: A = I - D^-1/2 W D^-1/2, spectrum in [0, 2]; 2 NORMALIZED_RANDOM_WALK: (D - W) v = lambda D v with
+ *                v^T D v = 1 (:276-309), computed as the symmetric form's u with v = D^-1/2 u.  A degree that is not finite and positive
+ *                under a normalised type: CILHIP_ERR_INVALID.  Solver storage and arithmetic are f64, the matrix stays f32; there is no
+ *                floating-point atomic anywhere.
+ *   S3 sizes     max_num_clusters == 0 or >= n: 2 clusters, estimation off (:406-412).  nev = estimate ? min(max + 1, n - 1) : max
+ *                (:198-200).  max_num_clusters > 16: CILHIP_ERR_UNSUPPORTED.  n < 3: CILHIP_ERR_INVALID.
+ *   S4 solver    Chebyshev-filtered subspace iteration on a block of b = min(nev + max(guard, nev / 2), n) columns, guard = 3: a start block
+ *                from a counter-based hash of (row, column), then per outer iteration a Rayleigh-Ritz step (Ritz values theta ascending)
+ *                and, unless every one of the first nev Ritz pairs passes Spectra's test (3rd_party/Spectra/HermEigsBase.h:152-167 with the
+ *                float literals of spectral_clustering.hpp:202) on its TRUE residual in f64,
+ *                    ||A x - theta x||_2 < 1e-7f * max(pow(FLT_EPSILON, 2/3), |theta|)      (x of unit length),
+ *                a filter of degree `degree` (24) that damps [largest Ritz value of the block, the upper bound of S2], scaled at the lowest
+ *                Ritz value by the three-term recurrence, and CholQR2.  After max_outer (1000) iterations without acceptance the call still
+ *                returns CILHIP_OK, with n_converged < num_eigenvalues in the result (the reference doubles max_iter for ever).
+ *   S5 output    eigenvalues rounded to f32, negative ones set to 0 (:225-228); with estimation num_clusters =
+ *                estimateNumberOfClustersEigengap (:46-68, literally, f32 on the rounded values); the embedding is the first num_clusters
+ *                vectors, point-major n x num_clusters f32 (the reference's column-major dim x n); NORMALIZED_SYMMETRIC divides each point's
+ *                vector by its f32 norm (ascending f32 sum of squares, sqrtf) when 1 / norm is finite (:269-272).  Addition: each vector's
+ *                sign makes its largest-magnitude component (f64, before the type's scaling; lowest index among equals) positive.  Two runs
+ *                agree bit for bit; vectors inside a repeated eigenvalue's space are whatever the iteration gives.
+ *   S6 k-means   cilhip_kmeans_nd: cilhip_kmeans3f's rules (brute-force branch, the empty-cluster repair with its quirk) in 1 <= dim <= 16
+ *                dimensions, k <= 256.  Distance: the f32 sum ((d0 d0 + d1 d1) + d2 d2) + ... in ascending coordinate order, no FMA;
+ *                assignment: strict '<' over ascending cluster index; cluster sums: f64, the points in chunks of ceil(n / min(256,
+ *                ceil(n / 256))) consecutive indices, ascending inside a chunk, the chunks' partial sums added in ascending order; centroid
+ *                = (float)(sum / count) (deviation: the reference sums in f32).  centroids: HOST dim * k floats, in and out; mem: where x
+ *                and labels_out live.
+ * embedded_out: n * num_clusters floats where `mem` says (room for n * max_num_clusters always suffices); eigenvalues_out: HOST, nev floats
+ * (room for max_num_clusters + 1).  Not built: double, 2-D and dense-input device paths, the kd-tree branch of the D-dimensional k-means,
+ * a sharded run, a check of W's symmetry, multidimensional scaling. */
+typedef struct cilhip_sparse cilhip_sparse;
+int cilhip_nn_graph_matrix(int device, size_t n, const uint64_t* offsets_or_null, const uint32_t* idx, const float* d2, size_t k_or_total, int mem,
+                           int kernel_kind, float kernel_sigma, int force_symmetry, int duplicates, cilhip_sparse** out);
+/* a caller's CSR matrix (n x n; mem: where the three arrays live).  CILHIP_ERR_INVALID: a NULL array, n == 0 or >= 2^32 - 16, offsets[0] != 0
+ * or descending, columns of a row not strictly ascending (unsorted or duplicate), a column >= n, a value that is not finite. */
+int cilhip_sparse_from_csr(int device, size_t n, const uint64_t* offsets, const uint32_t* columns, const float* values, int mem, cilhip_sparse** out);
+/* any of the three may be NULL */
+int cilhip_sparse_info(const cilhip_sparse* m, size_t* n_out, size_t* nnz_out, size_t* longest_row_out);
+/* copy-out: offsets n + 1, columns nnz, values nnz, each where `mem` says, each optional */
+int cilhip_sparse_get(const cilhip_sparse* m, uint64_t* offsets_out, uint32_t* columns_out, float* values_out, int mem);
+void cilhip_sparse_destroy(cilhip_sparse* m);
+
+typedef struct cilhip_spectral_params {
+  size_t max_num_clusters;
+  int estimate_num_clusters;
+  int laplacian_type;      /* 0 UNNORMALIZED, 1 NORMALIZED_SYMMETRIC, 2 NORMALIZED_RANDOM_WALK */
+  size_t max_outer;        /* S4: outer iterations before the call gives up */
+  int degree;              /* S4: degree of the filter, 2 .. 512 */
+  int guard;               /* S4: guard columns, 1 .. 15 */
+} cilhip_spectral_params;
+typedef struct cilhip_spectral_result {
+  size_t num_clusters, num_eigenvalues, n_converged, outer_iterations, block_products;
+  double max_residual;     /* the largest true residual among the first num_eigenvalues Ritz pairs at the end */
+  double wall_ms;
+} cilhip_spectral_result;
+/* max_num_clusters 2, no estimation, NORMALIZED_RANDOM_WALK (:401), max_outer 1000, degree 24, guard 3 */
+void cilhip_spectral_default_params(cilhip_spectral_params* params);
+int cilhip_spectral_embedding(const cilhip_sparse* W, const cilhip_spectral_params* params, float* embedded_out, float* eigenvalues_out, int mem,
+                              cilhip_spectral_result* result);
+int cilhip_kmeans_nd(int device, const float* x, size_t n, size_t dim, int mem, float* centroids, size_t k, size_t max_iter, float tol,
+                     uint32_t* labels_out, size_t* iterations_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,10 @@
 // header-only on top of the C ABI (c_api.h: cilhip_connected_components3f and cilhip_mean_shift3f, which state the contracts; DESIGN.md
 // sections 11 and 13):
 //
-//   MeanShift3f                                clustering/mean_shift.hpp:12-140 (the end of this file)
+//   SpectralClusteringXf / 2f / 3f, KMeansXf, getNNGraphFunctionValueSparseMatrix, estimateNumberOfClustersEigengap, GraphLaplacianType
+//                                              clustering/spectral_clustering.hpp, kmeans.hpp:67-194, utilities/nearest_neighbor_graph_utilities.hpp:89-118
+//                                              (the end of this file; cilhip_nn_graph_matrix, cilhip_spectral_embedding, cilhip_kmeans_nd)
+//   MeanShift3f                                clustering/mean_shift.hpp:12-140 (before that)
 //   Unity / Identity / RBFKernel WeightEvaluator               core/common_pair_evaluators.hpp:13-79
 //   ConnectedComponentExtraction3f             clustering/connected_component_extraction.hpp:368-428 (segment :394-422)
 //   the ClusteringBase accessors               clustering/clustering_base.hpp:60-97
@@ -269,5 +272,204 @@ private:
   ClusterToPointIndicesMap cluster_to_point_indices_map_;
   PointToClusterIndexMap point_to_cluster_index_map_;
 };
+
+// ---- SpectralClustering (clustering/spectral_clustering.hpp; c_api.h rules S1-S6) ---------------------------
+enum struct GraphLaplacianType { UNNORMALIZED, NORMALIZED_SYMMETRIC, NORMALIZED_RANDOM_WALK };      // :44
+
+// :46-68, literally
+template <class VectorT>
+size_t estimateNumberOfClustersEigengap(const VectorT& eigenvalues, size_t max_num_clusters) {
+  typedef typename VectorT::value_type ScalarT;
+  const size_t rows = eigenvalues.size();
+  ScalarT min_val = std::numeric_limits<ScalarT>::infinity();
+  ScalarT max_val = -std::numeric_limits<ScalarT>::infinity();
+  ScalarT max_diff = eigenvalues[0];
+  size_t max_ind = 0;
+  for (size_t i = 0; i + 1 < rows; i++) {
+    ScalarT diff = eigenvalues[i + 1] - eigenvalues[i];
+    if (diff > max_diff) {
+      max_diff = diff;
+      max_ind = i;
+    }
+    if (eigenvalues[i] < min_val) min_val = eigenvalues[i];
+    if (eigenvalues[i] > max_val) max_val = eigenvalues[i];
+  }
+  if (eigenvalues[rows - 1] < min_val) min_val = eigenvalues[rows - 1];
+  if (eigenvalues[rows - 1] > max_val) max_val = eigenvalues[rows - 1];
+  if (max_val - min_val < std::numeric_limits<ScalarT>::epsilon()) return max_num_clusters;
+  return max_ind + 1;
+}
+
+// a sparse affinity matrix on the device (the owner of a cilhip_sparse handle): the place of Eigen::SparseMatrix<float> in the reference
+class SparseAffinities {
+public:
+  SparseAffinities() = default;
+  explicit SparseAffinities(cilhip_sparse* h) : h_(h) {}
+  SparseAffinities(const SparseAffinities&) = delete;
+  SparseAffinities& operator=(const SparseAffinities&) = delete;
+  SparseAffinities(SparseAffinities&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  SparseAffinities& operator=(SparseAffinities&& o) noexcept {
+    if (this != &o) { cilhip_sparse_destroy(h_); h_ = o.h_; o.h_ = nullptr; }
+    return *this;
+  }
+  ~SparseAffinities() { cilhip_sparse_destroy(h_); }
+  // a CSR matrix of the caller's: columns strictly ascending per row
+  static SparseAffinities fromCSR(size_t n, const std::vector<uint64_t>& offsets, const std::vector<uint32_t>& columns, const std::vector<float>& values, int device = 0) {
+    if (offsets.size() != n + 1 || columns.size() != values.size()) throw std::invalid_argument("SparseAffinities: offsets need n + 1 entries, columns and values one per entry");
+    const uint32_t no_col = 0;
+    const float no_val = 0.0f;
+    cilhip_sparse* h = nullptr;
+    const int rc = cilhip_sparse_from_csr(device, n, offsets.data(), columns.empty() ? &no_col : columns.data(), values.empty() ? &no_val : values.data(), CILHIP_MEM_HOST, &h);
+    if (rc != CILHIP_OK) throw std::runtime_error("cilhip_sparse_from_csr failed (rc " + std::to_string(rc) + "): " + cilhip_last_error(nullptr));
+    return SparseAffinities(h);
+  }
+  const cilhip_sparse* handle() const { return h_; }
+  size_t rows() const { size_t n = 0; if (h_) cilhip_sparse_info(h_, &n, nullptr, nullptr); return n; }
+  size_t cols() const { return rows(); }
+  size_t nonZeros() const { size_t z = 0; if (h_) cilhip_sparse_info(h_, nullptr, &z, nullptr); return z; }
+
+private:
+  cilhip_sparse* h_ = nullptr;
+};
+
+// utilities/nearest_neighbor_graph_utilities.hpp:89-118 (the first entry of a list, the point itself, is kept; duplicates summed)
+template <class PairEvaluatorT = UnityWeightEvaluator<float>>
+SparseAffinities getNNGraphFunctionValueSparseMatrix(const NeighborhoodSet& adj_list, const PairEvaluatorT& evaluator = PairEvaluatorT(), bool force_symmetry = false,
+                                                     int device = 0) {
+  std::vector<uint64_t> off(adj_list.size() + 1, 0);
+  for (size_t i = 0; i < adj_list.size(); ++i) off[i + 1] = off[i] + adj_list[i].size();
+  std::vector<uint32_t> idx((size_t)off.back() + 1);
+  std::vector<float> d2((size_t)off.back() + 1);
+  for (size_t i = 0; i < adj_list.size(); ++i)
+    for (size_t j = 0; j < adj_list[i].size(); ++j) {
+      if (adj_list[i][j].index >= adj_list.size()) throw std::invalid_argument("getNNGraphFunctionValueSparseMatrix: a neighbour index is not below the number of lists");
+      idx[(size_t)off[i] + j] = (uint32_t)adj_list[i][j].index;
+      d2[(size_t)off[i] + j] = adj_list[i][j].value;
+    }
+  cilhip_sparse* h = nullptr;
+  const int rc = cilhip_nn_graph_matrix(device, adj_list.size(), off.data(), idx.data(), d2.data(), (size_t)off.back(), CILHIP_MEM_HOST, evaluator.kind(), evaluator.sigma(),
+                                        force_symmetry ? 1 : 0, 0, &h);
+  if (rc != CILHIP_OK) throw std::runtime_error("cilhip_nn_graph_matrix failed (rc " + std::to_string(rc) + "): " + cilhip_last_error(nullptr));
+  return SparseAffinities(h);
+}
+
+// KMeans<float, Dynamic> (kmeans.hpp:67-194), brute-force branch, 1 <= dim <= 16.  The points are a non-owning dim x n column-major view
+// (point-major floats); use_kd_tree is accepted and changes nothing (the kd-tree branch is not built in D dimensions).
+template <typename PointIndexT = size_t, typename ClusterIndexT = size_t>
+class KMeansXf {
+public:
+  typedef std::vector<std::vector<PointIndexT>> ClusterToPointIndicesMap;
+  typedef std::vector<ClusterIndexT> PointToClusterIndexMap;
+
+  KMeansXf() = default;
+  KMeansXf(const float* data, size_t num_points, size_t dim, int device = 0) : data_(data), n_(num_points), dim_(dim), device_(device) {}
+
+  // kmeans.hpp:24-30
+  KMeansXf& cluster(const std::vector<float>& centroids, size_t max_iter = 100, float tol = std::numeric_limits<float>::epsilon(), bool use_kd_tree = false) {
+    (void)use_kd_tree;
+    if (dim_ == 0 || centroids.size() % dim_ != 0) throw std::invalid_argument("KMeansXf: the centroids are dim floats each");
+    cluster_centroids_ = centroids;
+    const size_t k = centroids.size() / dim_;
+    std::vector<uint32_t> labels(n_ + 1);
+    const int rc = cilhip_kmeans_nd(device_, data_, n_, dim_, CILHIP_MEM_HOST, cluster_centroids_.data(), k, max_iter, tol, labels.data(), &iteration_count_);
+    if (rc != CILHIP_OK) throw std::runtime_error("cilhip_kmeans_nd failed (rc " + std::to_string(rc) + "): " + cilhip_last_error(nullptr));
+    point_to_cluster_index_map_.assign(labels.begin(), labels.begin() + n_);
+    cluster_to_point_indices_map_.assign(k, std::vector<PointIndexT>());
+    for (size_t i = 0; i < n_; ++i) cluster_to_point_indices_map_[labels[i]].push_back((PointIndexT)i);
+    return *this;
+  }
+  // the centroids start at the given points (the reference draws them with std::random_device, :32-53)
+  KMeansXf& cluster(const std::vector<size_t>& initial_centroid_indices, size_t max_iter = 100, float tol = std::numeric_limits<float>::epsilon(), bool use_kd_tree = false) {
+    std::vector<float> c;
+    for (size_t i : initial_centroid_indices) {
+      if (i >= n_) throw std::invalid_argument("KMeansXf: an initial centroid index is not below the number of points");
+      c.insert(c.end(), data_ + i * dim_, data_ + (i + 1) * dim_);
+    }
+    return cluster(c, max_iter, tol, use_kd_tree);
+  }
+
+  const std::vector<float>& getClusterCentroids() const { return cluster_centroids_; }      // dim floats per cluster
+  size_t getNumberOfPerformedIterations() const { return iteration_count_; }
+  const ClusterToPointIndicesMap& getClusterToPointIndicesMap() const { return cluster_to_point_indices_map_; }
+  const PointToClusterIndexMap& getPointToClusterIndexMap() const { return point_to_cluster_index_map_; }
+  size_t getNumberOfClusters() const { return cluster_to_point_indices_map_.size(); }
+  size_t getNumberOfPoints() const { return point_to_cluster_index_map_.size(); }
+
+protected:
+  const float* data_ = nullptr;
+  size_t n_ = 0, dim_ = 0;
+  int device_ = 0;
+  size_t iteration_count_ = 0;
+  std::vector<float> cluster_centroids_;
+  ClusterToPointIndicesMap cluster_to_point_indices_map_;
+  PointToClusterIndexMap point_to_cluster_index_map_;
+};
+
+// spectral_clustering.hpp:316-416, sparse input.  EigenDim > 0: the number of clusters (:377-391); EigenDim = -1 (Eigen::Dynamic): set at
+// run time, optionally estimated from the eigenvalues (:397-416).  The reference starts k-means from random points; here from
+// `initial_centroid_indices`, or from num_clusters points spread evenly over the index range when the list is empty.
+template <ptrdiff_t EigenDim = -1, typename PointIndexT = size_t, typename ClusterIndexT = size_t>
+class SpectralClustering : public KMeansXf<PointIndexT, ClusterIndexT> {
+  typedef KMeansXf<PointIndexT, ClusterIndexT> Clusterer;
+
+public:
+  enum { EmbeddingDimension = EigenDim };
+
+  // compile-time number of clusters
+  explicit SpectralClustering(const SparseAffinities& affinities, const GraphLaplacianType& laplacian_type = GraphLaplacianType::NORMALIZED_RANDOM_WALK,
+                              size_t kmeans_max_iter = 100, float kmeans_conv_tol = std::numeric_limits<float>::epsilon(), bool kmeans_use_kd_tree = false,
+                              const std::vector<size_t>& initial_centroid_indices = std::vector<size_t>()) {
+    static_assert(EigenDim > 0, "this constructor takes the number of clusters from EigenDim");
+    run(affinities, (size_t)EigenDim, false, laplacian_type, kmeans_max_iter, kmeans_conv_tol, kmeans_use_kd_tree, initial_centroid_indices);
+  }
+  // run-time number of clusters
+  SpectralClustering(const SparseAffinities& affinities, size_t max_num_clusters, bool estimate_num_clusters = false,
+                     const GraphLaplacianType& laplacian_type = GraphLaplacianType::NORMALIZED_RANDOM_WALK, size_t kmeans_max_iter = 100,
+                     float kmeans_conv_tol = std::numeric_limits<float>::epsilon(), bool kmeans_use_kd_tree = false,
+                     const std::vector<size_t>& initial_centroid_indices = std::vector<size_t>()) {
+    static_assert(EigenDim == -1, "this constructor belongs to the dynamic-dimension class");
+    run(affinities, max_num_clusters, estimate_num_clusters, laplacian_type, kmeans_max_iter, kmeans_conv_tol, kmeans_use_kd_tree, initial_centroid_indices);
+  }
+
+  // spectral_embedding_base.hpp: dim floats per point (the reference's dim x n, column-major)
+  const std::vector<float>& getEmbeddedPoints() const { return embedded_points_; }
+  const std::vector<float>& getComputedEigenValues() const { return computed_eigenvalues_; }
+  size_t getEmbeddingDimension() const { return this->dim_; }
+  const cilhip_spectral_result& getSolverResult() const { return result_; }
+
+private:
+  void run(const SparseAffinities& affinities, size_t max_num_clusters, bool estimate, const GraphLaplacianType& type, size_t max_iter, float tol, bool use_kd_tree,
+           const std::vector<size_t>& start) {
+    if (!affinities.handle()) throw std::invalid_argument("SpectralClustering: the affinity matrix is empty");
+    const size_t n = affinities.rows();
+    cilhip_spectral_params prm;
+    cilhip_spectral_default_params(&prm);
+    prm.max_num_clusters = max_num_clusters; prm.estimate_num_clusters = estimate ? 1 : 0; prm.laplacian_type = (int)type;
+    const size_t room = max_num_clusters >= 2 && max_num_clusters <= 16 ? max_num_clusters : 2;
+    embedded_points_.assign(n * room + 1, 0.0f);
+    computed_eigenvalues_.assign(room + 1, 0.0f);
+    const int rc = cilhip_spectral_embedding(affinities.handle(), &prm, embedded_points_.data(), computed_eigenvalues_.data(), CILHIP_MEM_HOST, &result_);
+    if (rc != CILHIP_OK) throw std::runtime_error("cilhip_spectral_embedding failed (rc " + std::to_string(rc) + "): " + cilhip_last_error(nullptr));
+    if (result_.n_converged < result_.num_eigenvalues)
+      throw std::runtime_error("cilhip_spectral_embedding: " + std::to_string(result_.n_converged) + " of " + std::to_string(result_.num_eigenvalues) + " eigenpairs converged");
+    const size_t k = result_.num_clusters;
+    embedded_points_.resize(n * k);
+    computed_eigenvalues_.resize(result_.num_eigenvalues);
+    this->data_ = embedded_points_.data(); this->n_ = n; this->dim_ = k;
+    std::vector<size_t> idx(start.begin(), start.begin() + (start.size() < k ? start.size() : k));
+    if (idx.size() < k) { idx.clear(); for (size_t c = 0; c < k; ++c) idx.push_back(c * n / k); }
+    Clusterer::cluster(idx, max_iter, tol, use_kd_tree);
+  }
+
+  std::vector<float> embedded_points_, computed_eigenvalues_;
+  cilhip_spectral_result result_{};
+};
+
+template <typename PointIndexT = size_t, typename ClusterIndexT = size_t>
+using SpectralClustering2f = SpectralClustering<2, PointIndexT, ClusterIndexT>;
+template <typename PointIndexT = size_t, typename ClusterIndexT = size_t>
+using SpectralClustering3f = SpectralClustering<3, PointIndexT, ClusterIndexT>;
+template <typename PointIndexT = size_t, typename ClusterIndexT = size_t>
+using SpectralClusteringXf = SpectralClustering<-1, PointIndexT, ClusterIndexT>;
 
 }  // namespace cilantro_hip
