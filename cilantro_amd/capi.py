@@ -36,6 +36,7 @@ SYMBOLS = [
     "cilhip_transform_points_per_point3f", "cilhip_warp_field_icp_run",
     "cilhip_nn_graph_matrix", "cilhip_sparse_from_csr", "cilhip_sparse_info", "cilhip_sparse_get", "cilhip_sparse_destroy",
     "cilhip_spectral_default_params", "cilhip_spectral_embedding", "cilhip_kmeans_nd",
+    "cilhip_mds_default_params", "cilhip_mds_embedding", "cilhip_mds_apply", "cilhip_pca_fit", "cilhip_pca_project", "cilhip_pca_reconstruct",
 ]
 
 
@@ -149,6 +150,15 @@ class SpectralParams(C.Structure):
 class SpectralResult(C.Structure):
     _fields_ = [("num_clusters", C.c_size_t), ("num_eigenvalues", C.c_size_t), ("n_converged", C.c_size_t), ("outer_iterations", C.c_size_t), ("block_products", C.c_size_t),
                 ("max_residual", C.c_double), ("wall_ms", C.c_double)]
+
+
+class MdsParams(C.Structure):
+    _fields_ = [("max_dim", C.c_size_t), ("estimate_dim", C.c_int), ("distances_are_squared", C.c_int), ("max_outer", C.c_size_t), ("degree", C.c_int), ("guard", C.c_int)]
+
+
+class MdsResult(C.Structure):
+    _fields_ = [("dim", C.c_size_t), ("num_eigenvalues", C.c_size_t), ("n_converged", C.c_size_t), ("outer_iterations", C.c_size_t), ("block_products", C.c_size_t),
+                ("locked", C.c_size_t), ("max_residual", C.c_double), ("wall_ms", C.c_double)]
 
 
 _lib = None
@@ -286,6 +296,13 @@ def load():
     L.cilhip_spectral_default_params.restype = None
     L.cilhip_spectral_embedding.argtypes = [vp, C.POINTER(SpectralParams), f32p, f32p, C.c_int, C.POINTER(SpectralResult)]
     L.cilhip_kmeans_nd.argtypes = [C.c_int, f32p, C.c_size_t, C.c_size_t, C.c_int, f32p, C.c_size_t, C.c_size_t, C.c_float, vp, C.POINTER(C.c_size_t)]
+    L.cilhip_mds_default_params.argtypes = [C.POINTER(MdsParams)]
+    L.cilhip_mds_default_params.restype = None
+    L.cilhip_mds_embedding.argtypes = [C.c_int, f32p, C.c_size_t, C.c_int, C.POINTER(MdsParams), f32p, f32p, C.POINTER(MdsResult)]
+    L.cilhip_mds_apply.argtypes = [C.c_int, f32p, C.c_size_t, C.c_int, C.c_int, f64p, C.c_size_t, f64p, C.POINTER(C.c_double)]
+    L.cilhip_pca_fit.argtypes = [C.c_int, f32p, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.c_int, f32p, f32p, f32p, f32p, C.POINTER(C.c_int)]
+    L.cilhip_pca_project.argtypes = [C.c_int, f32p, C.c_size_t, C.c_size_t, C.c_int, f32p, f32p, C.c_size_t, f32p]
+    L.cilhip_pca_reconstruct.argtypes = [C.c_int, f32p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, f32p, f32p, f32p]
     L.cilhip_icp_sums_from_keys.argtypes = [vp, vp, f64p]
     L.cilhip_icp_order_keys.argtypes = [vp, vp, vp]
     L.cilhip_icp_sums_from_ordered_keys.argtypes = [vp, vp, vp, f64p]
@@ -333,7 +350,7 @@ def load():
     for name in SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
         if name not in ("cilhip_destroy", "cilhip_last_error", "cilhip_icp_default_params", "cilhip_option_info", "cilhip_cc_default_params", "cilhip_ms_default_params", "cilhip_mcd_params_default", "cilhip_depth_default_converter", "cilhip_fusion_default_params", "cilhip_warp_default_params", "cilhip_warp_field_destroy", "cilhip_sparse_destroy",
-                        "cilhip_spectral_default_params"):
+                        "cilhip_spectral_default_params", "cilhip_mds_default_params"):
             fn.restype = C.c_int
     _lib = L
     return L

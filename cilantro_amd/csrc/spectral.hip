@@ -1,9 +1,9 @@
 // spectral.hip -- SpectralClustering<float> on the device (the rules S1-S6 are stated in c_api.h):
 //   S1  neighbour lists -> sparse affinity matrix (getNNGraphFunctionValueSparseMatrix)      k_graph_*: count, scan, fill, sort, merge
 //   S2  the Laplacian as an operator that is never assembled                                  k_degrees, k_block_product
-//   S4  Chebyshev-filtered subspace iteration, matrix-free, f64                                k_block_product (the hot path), k_gram_stage1 /
-//       k_stage2 (b x b products: fixed-shape two-stage sums), k_block_mul (X S, Y R^-1), k_residual_stage1; small dense work: small_sym.hpp
-//   S5  signs, scaling, rounding                                                               k_sign_stage1 / 2, k_epilogue
+//   S4  Chebyshev-filtered subspace iteration, matrix-free, f64                                k_block_product (the hot path); the b x b products,
+//       block updates, residuals, CholQR2 and the recurrence: subspace_device.hpp (shared with mds.hip); small dense work: small_sym.hpp
+//   S5  signs, scaling, rounding                                                               k_sign_stage1 / 2 (subspace_device.hpp), k_epilogue
 //   S6  k-means in D dimensions                                                                k_nd_assign, k_nd_sums, k_nd_farthest
 // Every sum runs in an order the input alone decides and the only atomics are integer ones: two runs agree bit for bit.
 #include "../../include/cilantro_hip/c_api.h"
@@ -11,6 +11,7 @@
 #include "search_device.hpp"
 #include "small_sym.hpp"
 #include "stateless.hpp"
+#include "subspace_device.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -38,15 +39,7 @@ using cilhip::CW_IDENTITY;
 using cilhip::CW_RBF;
 using cilhip::CW_UNITY;
 
-constexpr int SP_THREADS = 256;
-constexpr uint32_t SP_NONE = 0xFFFFFFFFu;
-constexpr int SP_MAX_B = 32;                 // columns of the block: nev <= 17, guard <= 15
-constexpr int SP_PARTIAL_BLOCKS = 256;       // stage-1 blocks of every two-stage sum
-constexpr size_t SP_MAX_N = 0xFFFFFFF0ull;
 enum { SP_ERR_INDEX = 1u, SP_ERR_OFFSETS = 2u, SP_ERR_ORDER = 4u, SP_ERR_VALUE = 8u };
-
-// one lane per row or element, grid-stride: at most one block per CU
-inline unsigned sp_grid(size_t work, unsigned cap = 256) { return (unsigned)std::min<size_t>(std::max<size_t>((work + SP_THREADS - 1) / SP_THREADS, 1), cap); }
 
 // ---- S1: the graph builder ----------------------------------------------------------------------------------------------------------
 struct SpEnt { uint64_t ord; uint32_t col; float val; };      // ord = (source list i) << 32 | position in that list
@@ -217,120 +210,6 @@ __global__ __launch_bounds__(SP_THREADS) void k_block_product(OpDev A, const dou
   }
 }
 
-// ---- S4: the b x b products, the block updates, the residuals ------------------------------------------------------------------------
-// stage 1 of C = X^T Y: block B owns the rows [B rows_per_block, (B + 1) rows_per_block) and sums them in ascending order, 32 rows at a
-// time through LDS; partial[B][b * b].  The shape depends on n and b alone.
-constexpr int GR_TILE = 32;
-__global__ __launch_bounds__(SP_THREADS) void k_gram_stage1(const double* __restrict__ X, const double* __restrict__ Y, uint32_t n, int b, uint32_t rows_per_block,
-                                                            double* __restrict__ partial) {
-  __shared__ double sx[GR_TILE * SP_MAX_B], sy[GR_TILE * SP_MAX_B];
-  const int t = threadIdx.x, bb = b * b;
-  const uint64_t r0 = std::min<uint64_t>((uint64_t)blockIdx.x * rows_per_block, n), r1 = std::min<uint64_t>(r0 + rows_per_block, n);
-  double acc[4] = {0.0, 0.0, 0.0, 0.0};
-  for (uint64_t base = r0; base < r1; base += GR_TILE) {
-    const int cnt = (int)std::min<uint64_t>(GR_TILE, r1 - base);
-    for (int u = t; u < cnt * b; u += SP_THREADS) { sx[u] = X[base * b + u]; sy[u] = Y[base * b + u]; }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int e = t + SP_THREADS * q;
-      if (e < bb) {
-        const int i = e / b, j = e - i * b;
-        double a = acc[q];
-        for (int rr = 0; rr < cnt; ++rr) a = fma(sx[rr * b + i], sy[rr * b + j], a);
-        acc[q] = a;
-      }
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int e = t + SP_THREADS * q;
-    if (e < bb) partial[(size_t)blockIdx.x * bb + e] = acc[q];
-  }
-}
-
-// stage 2 of every two-stage sum: out[e] = partial[0][e] + partial[1][e] + ... in ascending block order
-__global__ __launch_bounds__(SP_THREADS) void k_stage2(const double* __restrict__ partial, int blocks, int width, double* __restrict__ out) {
-  for (int e = threadIdx.x; e < width; e += SP_THREADS) {
-    double a = 0.0;
-    for (int B = 0; B < blocks; ++B) a += partial[(size_t)B * width + e];
-    out[e] = a;
-  }
-}
-
-// Out = X S (S: b x b, row-major); Out must not be X
-__global__ __launch_bounds__(SP_THREADS) void k_block_mul(const double* __restrict__ X, const double* __restrict__ S, double* __restrict__ Out, uint64_t total, int b) {
-  __shared__ double sS[SP_MAX_B * SP_MAX_B];
-  for (int u = threadIdx.x; u < b * b; u += SP_THREADS) sS[u] = S[u];
-  __syncthreads();
-  for (uint64_t o = (uint64_t)blockIdx.x * SP_THREADS + threadIdx.x; o < total; o += (uint64_t)gridDim.x * SP_THREADS) {
-    const uint64_t r = o / b;
-    const int c = (int)(o - r * b);
-    double a = 0.0;
-    for (int k = 0; k < b; ++k) a = fma(X[r * b + k], sS[k * b + c], a);
-    Out[o] = a;
-  }
-}
-
-// stage 1 of the squared residual norms ||AX_c - theta_c X_c||^2: lane (rl, c) sums the rows rl, rl + rpb, ... of the block's range for
-// column c, the rpb sums of a column are added in ascending rl; partial[B][b]
-__global__ __launch_bounds__(SP_THREADS) void k_residual_stage1(const double* __restrict__ X, const double* __restrict__ AX, const double* __restrict__ theta, uint32_t n, int b,
-                                                                uint32_t rows_per_block, double* __restrict__ partial) {
-  __shared__ double part[SP_THREADS];
-  const int t = threadIdx.x, rpb = SP_THREADS / b, rl = t / b, c = t - rl * b;
-  const uint64_t r0 = std::min<uint64_t>((uint64_t)blockIdx.x * rows_per_block, n), r1 = std::min<uint64_t>(r0 + rows_per_block, n);
-  double acc = 0.0;
-  if (rl < rpb) {
-    const double th = theta[c];
-    for (uint64_t r = r0 + rl; r < r1; r += rpb) {
-      const double d = AX[r * b + c] - th * X[r * b + c];
-      acc = fma(d, d, acc);
-    }
-  }
-  part[t] = acc;
-  __syncthreads();
-  if (t < b) {
-    double a = 0.0;
-    for (int u = 0; u < rpb; ++u) a += part[u * b + t];
-    partial[(size_t)blockIdx.x * b + t] = a;
-  }
-}
-
-// S5's sign rule, stage 1: per block and column the largest |x| of the block's rows, the lowest row among equals, and x there
-struct SignRec { double mag, value; uint32_t row; uint32_t pad; };
-__global__ __launch_bounds__(SP_THREADS) void k_sign_stage1(const double* __restrict__ X, uint32_t n, int b, uint32_t rows_per_block, SignRec* __restrict__ partial) {
-  __shared__ SignRec part[SP_THREADS];
-  const int t = threadIdx.x, rpb = SP_THREADS / b, rl = t / b, c = t - rl * b;
-  const uint64_t r0 = std::min<uint64_t>((uint64_t)blockIdx.x * rows_per_block, n), r1 = std::min<uint64_t>(r0 + rows_per_block, n);
-  SignRec best{-1.0, 0.0, SP_NONE, 0u};
-  if (rl < rpb)
-    for (uint64_t r = r0 + rl; r < r1; r += rpb) {
-      const double v = X[r * b + c], m = fabs(v);
-      if (m > best.mag) best = SignRec{m, v, (uint32_t)r, 0u};      // (ascending rows: the first one stays)
-    }
-  part[t] = best;
-  __syncthreads();
-  if (t < b) {
-    SignRec a = part[t];
-    for (int u = 1; u < rpb; ++u) {
-      const SignRec o = part[u * b + t];
-      if (o.mag > a.mag || (o.mag == a.mag && o.row < a.row)) a = o;
-    }
-    partial[(size_t)blockIdx.x * b + t] = a;
-  }
-}
-__global__ void k_sign_stage2(const SignRec* __restrict__ partial, int blocks, int b, double* __restrict__ sign) {
-  const int c = threadIdx.x;
-  if (c >= b) return;
-  SignRec a = partial[c];
-  for (int B = 1; B < blocks; ++B) {
-    const SignRec o = partial[(size_t)B * b + c];
-    if (o.mag > a.mag || (o.mag == a.mag && o.row < a.row)) a = o;
-  }
-  sign[c] = a.value < 0.0 ? -1.0 : 1.0;
-}
-
 // S5: the first nc vectors, signed, (random walk) scaled by d^-1/2, rounded to f32, (symmetric) each point's vector divided by its norm
 __global__ __launch_bounds__(SP_THREADS) void k_epilogue(const double* __restrict__ X, const double* __restrict__ sign, const double* __restrict__ s, uint32_t n, int b, int nc,
                                                          int type, float* __restrict__ out) {
@@ -352,18 +231,6 @@ __global__ __launch_bounds__(SP_THREADS) void k_epilogue(const double* __restric
 #pragma unroll
     for (int c = 0; c < SP_MAX_B; ++c)
       if (c < nc) out[r * nc + c] = type == 1 ? __fmul_rn(v[c], f) : v[c];
-  }
-}
-
-// the start block: a counter-based hash of (row, column) (splitmix64's finaliser), uniform in [-1, 1)
-__global__ __launch_bounds__(SP_THREADS) void k_start_block(double* __restrict__ X, uint64_t total, int b) {
-  for (uint64_t o = (uint64_t)blockIdx.x * SP_THREADS + threadIdx.x; o < total; o += (uint64_t)gridDim.x * SP_THREADS) {
-    const uint64_t r = o / b, c = o - r * b;
-    uint64_t z = (r * 64u + c + 1u) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    X[o] = (double)(z >> 11) * (1.0 / 4503599627370496.0) - 1.0;      // 2^-52: [0, 2) - 1
   }
 }
 
@@ -443,13 +310,6 @@ const char* sp_error_text(unsigned int e) {
          : (e & SP_ERR_INDEX) ? "an index is not below n"
          : (e & SP_ERR_ORDER) ? "the columns of a row must be strictly ascending (unsorted or duplicate columns)"
                               : "a value is not finite";
-}
-
-// shape of a two-stage sum over n rows
-struct TwoStage { int blocks; uint32_t rows_per_block; };
-inline TwoStage two_stage(size_t n) {
-  const size_t nb = std::min<size_t>(SP_PARTIAL_BLOCKS, std::max<size_t>((n + 63) / 64, 1));
-  return TwoStage{(int)nb, (uint32_t)((n + nb - 1) / nb)};
 }
 
 int graph_impl(int device, size_t n, const uint64_t* offsets, const uint32_t* idx, const float* d2, size_t k_or_total, int mem, int kind, float sigma, int sym, int duplicates,
@@ -566,17 +426,10 @@ size_t eigengap(const float* ev, size_t count, size_t max_num_clusters) {
   return max_ind + 1;
 }
 
-struct Solver {
-  const char* F = "spectral_embedding";
+struct Solver : SubspaceOps {
   const cilhip_sparse* W;
-  hipStream_t s;
   OpDev A{};
-  int b = 0, split = 1;
-  size_t n = 0;
-  TwoStage ts{};
-  double* small = nullptr;      // [0, 1024) a b x b matrix, [1024, 1056) theta, [1056, 1088) signs
-  double* out = nullptr;        // [1024] result of a two-stage sum
-  double* partial = nullptr;    // [SP_PARTIAL_BLOCKS * 1024]
+  int split = 1;
   size_t products = 0;
 
   int product(const double* X, const double* Z, double* Y, double alpha, double c, double beta) {
@@ -587,50 +440,6 @@ struct Solver {
     else hipLaunchKernelGGL(k_block_product<1>, dim3(grid), dim3(SP_THREADS), 0, s, A, X, Z, Y, alpha, c, beta);
     ST_CK(F, hipGetLastError());
     ++products;
-    return CILHIP_OK;
-  }
-  // host[b * b] = X^T Y
-  int gram(const double* X, const double* Y, double* host) {
-    hipLaunchKernelGGL(k_gram_stage1, dim3(ts.blocks), dim3(SP_THREADS), 0, s, X, Y, (uint32_t)n, b, ts.rows_per_block, partial);
-    hipLaunchKernelGGL(k_stage2, dim3(1), dim3(SP_THREADS), 0, s, (const double*)partial, ts.blocks, b * b, out);
-    ST_CK(F, hipGetLastError());
-    ST_CK(F, hipMemcpyAsync(host, out, (size_t)b * b * sizeof(double), hipMemcpyDeviceToHost, s));
-    ST_CK(F, hipStreamSynchronize(s));
-    return CILHIP_OK;
-  }
-  // Out = X M (M: host b x b)
-  int mul(const double* X, const double* M, double* Out) {
-    ST_CK(F, hipMemcpyAsync(small, M, (size_t)b * b * sizeof(double), hipMemcpyHostToDevice, s));
-    ST_CK(F, hipStreamSynchronize(s));      // (M is the caller's stack)
-    hipLaunchKernelGGL(k_block_mul, dim3(sp_grid(n * b, 2048)), dim3(SP_THREADS), 0, s, X, (const double*)small, Out, (uint64_t)n * b, b);
-    ST_CK(F, hipGetLastError());
-    return CILHIP_OK;
-  }
-  // CholQR2 with the columns scaled to unit length first (the filter leaves columns of very different lengths); *X and *T swap
-  int orthonormalise(double** X, double** T) {
-    double G[SP_MAX_B * SP_MAX_B], R[SP_MAX_B * SP_MAX_B], Ri[SP_MAX_B * SP_MAX_B], dd[SP_MAX_B];
-    int passes = 2;
-    for (int pass = 0; pass < passes; ++pass) {
-      if (const int rc = gram(*X, *X, G)) return rc;
-      for (int i = 0; i < b; ++i) { const double g = G[i * b + i]; dd[i] = (g > 0.0 && std::isfinite(g)) ? std::sqrt(g) : 1.0; }
-      for (int i = 0; i < b; ++i)
-        for (int j = 0; j < b; ++j) G[i * b + j] = 0.5 * (G[i * b + j] + G[j * b + i]) / (dd[i] * dd[j]);
-      for (int i = 0; i < b; ++i)
-        for (int j = 0; j < i; ++j) G[i * b + j] = G[j * b + i];
-      double shift = 0.0;
-      for (int attempt = 0; !cilhip::sym_cholesky(G, b, R); ++attempt) {      // (nearly dependent columns: shifted CholQR, one more pass)
-        if (attempt == 8) return cilhip::st_fail(CILHIP_ERR_HIP, F, "the block lost its rank");
-        const double add = shift == 0.0 ? 1e-13 * b : shift * 99.0;
-        for (int i = 0; i < b; ++i) G[i * b + i] += add;
-        shift += add;
-        if (passes < 4) passes = pass + 3 > 4 ? 4 : pass + 3;
-      }
-      cilhip::upper_inverse(R, b, Ri);
-      for (int i = 0; i < b; ++i)
-        for (int j = 0; j < b; ++j) Ri[i * b + j] /= dd[i];
-      if (const int rc = mul(*X, Ri, *T)) return rc;
-      std::swap(*X, *T);
-    }
     return CILHIP_OK;
   }
 };
@@ -718,18 +527,8 @@ int embedding_impl(const cilhip_sparse* W, const cilhip_spectral_params& prm, si
     if (!(a < ub)) a = a0 + 0.5 * (ub - a0);
     if (ub > a0 && a > a0 && a < ub) {
       const double e = 0.5 * (ub - a), c = 0.5 * (ub + a);
-      double sigma = e / (a0 - c);
-      const double sigma1 = sigma;
-      double *Yp = X, *Yc = T1, *Yn = T2;
-      if (const int rc = so.product(Yp, nullptr, Yc, sigma1 / e, c, 0.0)) return rc;
-      for (int i = 2; i <= prm.degree; ++i) {
-        const double sigma2 = 1.0 / (2.0 / sigma1 - sigma);
-        if (const int rc = so.product(Yc, Yp, Yn, 2.0 * sigma2 / e, c, -sigma * sigma2)) return rc;
-        double* const old = Yp;
-        Yp = Yc; Yc = Yn; Yn = old;
-        sigma = sigma2;
-      }
-      X = Yc; T1 = Yp; T2 = Yn;
+      auto product = [&](const double* Xi, const double* Zi, double* Yo, double alpha, double cc, double beta) { return so.product(Xi, Zi, Yo, alpha, cc, beta); };
+      if (const int rc = cheb_filter(product, e, c, a0, prm.degree, X, T1, T2)) return rc;
     }
     if (const int rc = so.orthonormalise(&X, &T1)) return rc;
   }
@@ -830,10 +629,6 @@ int kmeans_nd_impl(const float* x, size_t n, int D, int mem, float* centroids, s
   ST_CK(F, hipStreamSynchronize(s));
   if (iterations_out) *iterations_out = iter;
   return CILHIP_OK;
-}
-
-template <class Fn> int sp_guard(const char* family, Fn&& fn) {
-  try { return fn(); } catch (const std::bad_alloc&) { return cilhip::st_fail(CILHIP_ERR_HIP, family, "out of host memory"); } catch (...) { return cilhip::st_fail(CILHIP_ERR_HIP, family, "unexpected exception"); }
 }
 
 }  // namespace

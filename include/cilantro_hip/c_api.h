@@ -1217,7 +1217,7 @@ int cilhip_debug_live_allocations(unsigned long long out[2]);
  *                and labels_out live.
  * embedded_out: n * num_clusters floats where `mem` says (room for n * max_num_clusters always suffices); eigenvalues_out: HOST, nev floats
  * (room for max_num_clusters + 1).  Not built: double, 2-D and dense-input device paths, the kd-tree branch of the D-dimensional k-means,
- * a sharded run, a check of W's symmetry, multidimensional scaling. */
+ * a sharded run, a check of W's symmetry. */
 typedef struct cilhip_sparse cilhip_sparse;
 int cilhip_nn_graph_matrix(int device, size_t n, const uint64_t* offsets_or_null, const uint32_t* idx, const float* d2, size_t k_or_total, int mem,
                            int kernel_kind, float kernel_sigma, int force_symmetry, int duplicates, cilhip_sparse** out);
@@ -1249,6 +1249,83 @@ int cilhip_spectral_embedding(const cilhip_sparse* W, const cilhip_spectral_para
                               cilhip_spectral_result* result);
 int cilhip_kmeans_nd(int device, const float* x, size_t n, size_t dim, int mem, float* centroids, size_t k, size_t max_iter, float tol,
                      uint32_t* labels_out, size_t* iterations_out);
+
+/* ---- multidimensional scaling and principal component analysis ------------------------------------------------------------------------ */
+/* utilities/multidimensional_scaling.hpp (computeDistancePreservingSpectralEmbedding :34-83, MultidimensionalScaling :86-120) for float: the
+ * classical (Torgerson) embedding of n points from their n x n distance matrix.  DESIGN.md section 19 is the long form;
+ * tests/_mds_refs.py restates every rule in numpy.
+ *   M1 input     D: n x n f32, row-major, leading dimension n, where `mem` says.  Symmetry is the caller's promise, as in the reference;
+ *                whether D or its transpose is applied is unspecified (the reference's column-major matrix is the same bytes).
+ *                distances_are_squared == 0: Dhat_ij = d * d as one f32 product (array().square() in ScalarT, :57); otherwise Dhat = D.
+ *                CILHIP_ERR_INVALID (cilhip_last_error(NULL) names the rule, the outputs untouched): a NULL pointer; n < 3 or n >= 2^32 - 16;
+ *                unknown mem; degree outside [1, 512], guard outside [1, 15], max_outer == 0; and, found on the device in the pass that
+ *                forms the column means, an entry of Dhat that is not finite.  Argument errors are refused before any device call.
+ *   M2 operator  B = -1/2 J Dhat J, J = I - 1 1^T / n, is applied in f64 and never formed: with r_i the mean of column i of Dhat and g the
+ *                mean of r, (B x)_i = -1/2 (sum_j Dhat_ji x_j - r_i sum_j x_j - sum_j r_j x_j + g sum_j x_j).  The sum over j runs in
+ *                chunks of max(128, ceil(n / 64)) consecutive rows, ascending inside a chunk, the chunks' sums added in ascending order; the
+ *                two moments of x (sum_j x_j, sum_j r_j x_j) in the fixed two-stage shape of S4's residual sums (DESIGN.md 19.1 spells it
+ *                out); g: ascending i on the host.  The order depends on n and the block width alone.  No floating-point atomic.
+ *   M3 sizes     max_dim == 0 or >= n: dimension 2, estimation off (:110-118).  nev = estimate ? min(max_dim + 1, n - 1) : max_dim (:41-42).
+ *                max_dim > 16: CILHIP_ERR_UNSUPPORTED.
+ *   M4 solver    the nev eigenpairs of LARGEST MAGNITUDE, ordered by descending |theta| (Spectra's LargestMagn for selection and sort,
+ *                :65-66), each accepted by Spectra's test (3rd_party/Spectra/HermEigsBase.h:152-167 with the float literal of :44) on its
+ *                TRUE residual in f64,
+ *                    ||B x - theta x||_2 < 1e-7f * max(pow(FLT_EPSILON, 2/3), |theta|)      (x of unit length).
+ *                Subspace iteration on a block of b = min(nev + max(guard, nev / 2), n) columns from S4's start block: per outer iteration
+ *                a Rayleigh-Ritz step on the unlocked columns (Ritz pairs by descending magnitude), locking of the leading pairs that pass
+ *                the test, and on the rest a filter that damps [-e, e] (e: the smallest magnitude of the block) and is 1 at the first
+ *                unlocked magnitude, of a degree <= `degree` (24) chosen so that its gain stays within 1e6 down to the lowest wanted
+ *                magnitude and within 1e10 up to the largest locked one; then two projections against the locked vectors and CholQR2.
+ *                After max_outer (1000) iterations without acceptance the call still returns CILHIP_OK, with n_converged < num_eigenvalues
+ *                (the reference doubles max_iter for ever).  That is what a request for a pair inside the rounding noise of exactly
+ *                low-rank data gets (estimate_dim with max_dim >= the rank).
+ *   M5 output    eigenvalues rounded to f32, negative ones set to 0 in place (:70-73: the order stays the magnitude order); with estimation
+ *                dim = estimateEmbeddingDimensionEigengap (:10-31, literally, f32 on the clamped values); the embedding is point-major
+ *                n x dim f32 (the reference's column-major dim x n), sqrtf(ev[c]) * (float)(sign_c * x_ic) (:79-80).  Addition: sign_c makes
+ *                the largest-magnitude component of the f64 vector positive (lowest index among equals).  Two runs agree bit for bit;
+ *                vectors inside a repeated eigenvalue's space are whatever the iteration gives.
+ * embedded_out: n * dim floats where `mem` says (room for n * max_dim -- n * 2 when M3 falls back -- always suffices); eigenvalues_out: HOST,
+ * nev floats (room for max_dim + 1).  Not built: double, a sharded run, a check of D's symmetry. */
+typedef struct cilhip_mds_params {
+  size_t max_dim;
+  int estimate_dim;
+  int distances_are_squared;
+  size_t max_outer;        /* M4: outer iterations before the call gives up */
+  int degree;              /* M4: largest degree of the filter, 1 .. 512 */
+  int guard;               /* M4: guard columns, 1 .. 15 */
+} cilhip_mds_params;
+typedef struct cilhip_mds_result {
+  size_t dim, num_eigenvalues, n_converged, outer_iterations, block_products, locked;
+  double max_residual;     /* the largest true residual among the num_eigenvalues Ritz pairs at the end */
+  double wall_ms;
+} cilhip_mds_result;
+/* max_dim 2, no estimation, squared distances (:97, :109), max_outer 1000, degree 24, guard 3 */
+void cilhip_mds_default_params(cilhip_mds_params* params);
+int cilhip_mds_embedding(int device, const float* D, size_t n, int mem, const cilhip_mds_params* params, float* embedded_out, float* eigenvalues_out,
+                         cilhip_mds_result* result);
+/* The operator of M2 alone: y = B x for a row-major n x b f64 block (1 <= b <= 32; x and y_out where `mem` says, like D), in the order M2
+ * states.  product_ms_out (optional): device time of the product itself, without the pass that forms the column means. */
+int cilhip_mds_apply(int device, const float* D, size_t n, int mem, int distances_are_squared, const double* x, size_t b, double* y_out, double* product_ms_out);
+
+/* core/principal_component_analysis.hpp with core/covariance.hpp:31-180 for float.  x: n points of `dim` coordinates, point-major (the
+ * reference's column-major dim x n), 1 <= dim <= 16, where `mem` says; subset_or_null: n_subset uint32 indices into x (the subset
+ * constructor; where `mem` says), an index >= n is found on the device: CILHIP_ERR_INVALID.  count = n_subset, or n without a subset.
+ *   P1 mean        f64 coordinate sums -- the sample in chunks of ceil(count / min(256, ceil(count / 64))) consecutive entries, ascending
+ *                  inside a chunk, the chunks' sums added in ascending order -- and mean = (float)(sum / count) (deviation: the reference
+ *                  sums in f32, covariance.hpp:64-68).
+ *   P2 covariance  tmp = x - mean in f32 (:73); the products tmp_a tmp_c and their sums in f64, the same order; cov = (float)(sum / (count - 1)).
+ *   P3 small       count < 2 (min_sample_size_, :35-39): mean, covariance, eigenvalues and eigenvectors are all NaN, *valid_out = 0, CILHIP_OK.
+ *   P4 eigen       cyclic Jacobi in f64 on the f32 covariance, eigenvalues descending (principal_component_analysis.hpp:76-84), outputs f32.
+ *                  eigenvectors_out[c * dim + k]: component k of vector c (the reference's column-major matrix).  Addition: vectors
+ *                  0 .. dim - 2 get M5's sign rule, the last one the sign that makes the determinant positive (:79-82).
+ *   P5 maps        project: out[i][t] = (float) sum_k V[t][k] * (x[i][k] - mean[k]), t < target_dim <= dim (:46-49): the difference in f32,
+ *                  products and the ascending sum in f64.  reconstruct: out[i][k] = (float)(sum_{t < source_dim} V[t][k] y[i][t] + mean[k])
+ *                  in f64 (:59-62).  target_dim / source_dim outside [1, dim]: CILHIP_ERR_INVALID.  mean and eigenvectors: HOST.
+ * mean_out dim, cov_out dim * dim (row-major), eigenvalues_out dim, eigenvectors_out dim * dim: HOST. */
+int cilhip_pca_fit(int device, const float* x, size_t n, size_t dim, const uint32_t* subset_or_null, size_t n_subset, int mem, float* mean_out, float* cov_out,
+                   float* eigenvalues_out, float* eigenvectors_out, int* valid_out);
+int cilhip_pca_project(int device, const float* x, size_t m, size_t dim, int mem, const float* mean, const float* eigenvectors, size_t target_dim, float* out);
+int cilhip_pca_reconstruct(int device, const float* y, size_t m, size_t source_dim, size_t dim, int mem, const float* mean, const float* eigenvectors, float* out);
 
 #ifdef __cplusplus
 }
