@@ -18,9 +18,7 @@
 #include <cstdlib>
 #include <utility>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
+#include "device_prims.hpp"
 #include "internal.hpp"
 #include "rank_update.hpp"
 
@@ -545,10 +543,11 @@ static hipError_t ensure_ws(PairSet& p, size_t ncand, size_t nd, size_t ns, size
 static hipError_t scan_flags_ws(PairSet& p, const uint32_t* flags, uint32_t* offs, uint32_t n, uint32_t* total_out, hipStream_t s) {
   *total_out = 0;
   if (n == 0) return hipSuccess;
+  const auto scan = prim_exclusive_sum(flags, offs, (size_t)n, s);
   size_t tmp_bytes = 0;
-  HIP_TRY(rocprim::exclusive_scan(nullptr, tmp_bytes, flags, offs, 0u, (size_t)n, rocprim::plus<uint32_t>(), s));
+  HIP_TRY(scan(nullptr, tmp_bytes));
   HIP_TRY(ensure_ws(p, p.ws_cand, 0, 0, tmp_bytes ? tmp_bytes : 16));
-  HIP_TRY(rocprim::exclusive_scan(p.ws[14], tmp_bytes, flags, offs, 0u, (size_t)n, rocprim::plus<uint32_t>(), s));
+  HIP_TRY(scan(p.ws[14], tmp_bytes));
   uint32_t last_off = 0, last_flag = 0;
   HIP_TRY(hipMemcpyAsync(&last_off, offs + (n - 1), 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(&last_flag, flags + (n - 1), 4, hipMemcpyDeviceToHost, s));
@@ -579,7 +578,7 @@ hipError_t find_pairs(const FeatSpec& feat, const GridDev& g, const GridDev& sgr
   if (nd == 0 || ns == 0) return hipSuccess;   // kd_tree_utilities.hpp:16-19: an empty side gives no correspondences
   const unsigned end_bit = 32u + bits_for_u32(nd);            // keys = first << 32 | second, first < nd; the invalid key (all ones) still sorts last
   size_t sort_bytes = 0;
-  HIP_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, ncand, 0u, end_bit, s));
+  HIP_TRY(prim_sort_pairs((unsigned long long*)nullptr, (unsigned long long*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, ncand, 0u, end_bit, s)(nullptr, sort_bytes));
   HIP_TRY(ensure_ws(out, ncand, nd, ns, sort_bytes ? sort_bytes : 16));
   uint32_t* rev_pos = (uint32_t*)out.ws[REV_POS].get(); float* rev_d2 = (float*)out.ws[REV_D2].get();
   unsigned long long *keys_in = (unsigned long long*)out.ws[KEYS_IN].get(), *keys_out = (unsigned long long*)out.ws[KEYS_OUT].get();
@@ -644,7 +643,7 @@ hipError_t find_pairs(const FeatSpec& feat, const GridDev& g, const GridDev& sgr
     if (direction == 2)
       hipLaunchKernelGGL(k_cand_forward, dim3(nblk(ns)), dim3(256), 0, s, g.pts, nd, src_sorted, ns, fwd_pos, fwd_d2, keys_in, slots_in, c_posd, c_poss,
                          c_d2);
-    if ((e = rocprim::radix_sort_pairs(out.ws[TMP], sort_bytes, keys_in, keys_out, slots_in, slots_out, ncand, 0u, end_bit, s)) != hipSuccess) break;
+    if ((e = prim_sort_pairs(keys_in, keys_out, slots_in, slots_out, ncand, 0u, end_bit, s)(out.ws[TMP], sort_bytes)) != hipSuccess) break;
     // 3. union / intersection / plain, then ordered compaction
     hipLaunchKernelGGL(k_mark, dim3(nblk(ncand)), dim3(256), 0, s, keys_out, (uint32_t)ncand, direction == 2 ? (reciprocal ? 2 : 1) : 0, flags);
     uint32_t m = 0;

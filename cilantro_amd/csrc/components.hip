@@ -33,14 +33,13 @@
 // entry still naming itself.  Path halving only ever replaces a non-root's parent by one of its ancestors.
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_radix_sort.hpp>
-
 #include <algorithm>
 #include <cmath>
 #include <string>
 #include <vector>
 
 #include "../../include/cilantro_hip/c_api.h"
+#include "device_prims.hpp"
 #include "internal.hpp"
 #include "stateless.hpp"
 
@@ -124,10 +123,6 @@ __device__ __forceinline__ bool cc_similar(const CcClauses& c, const F3* __restr
     return c.angle_inclusive ? v <= lim : v < lim;
   }
   return true;
-}
-
-__global__ __launch_bounds__(CC_THREADS) void k_cc_init(uint32_t* __restrict__ a, size_t n) {      // a[i] = i: every point its own root
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) a[i] = (uint32_t)i;
 }
 
 // points with a non-finite coordinate become (NaN, NaN, NaN): such a record sits in the grid's first (empty) cell, is inside nobody's
@@ -249,20 +244,7 @@ __global__ __launch_bounds__(CC_THREADS) void k_cc_labels(const uint32_t* __rest
   }
 }
 
-// offsets[k] = first sorted position of label k; offsets[n_kept] (preset to n) = the first unlabelled point's
-__global__ __launch_bounds__(CC_THREADS) void k_cc_offsets(const uint32_t* __restrict__ labels_sorted, size_t n, uint32_t* __restrict__ offsets) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const uint32_t l = labels_sorted[i];
-    if (i == 0 || labels_sorted[i - 1] != l) offsets[l] = (uint32_t)i;
-  }
-}
-
 inline int cc_blocks(size_t n) { return (int)std::min<size_t>((n + CC_THREADS - 1) / CC_THREADS, 2048) + (n == 0); }
-unsigned cc_bits(uint32_t v) {      // bits that hold 0 .. v
-  unsigned b = 1;
-  while (b < 32 && (1ull << b) <= (unsigned long long)v) ++b;
-  return b;
-}
 
 struct CcOut {
   int mem;
@@ -302,13 +284,7 @@ int cc_finish(const CcOut& o, DevPool& pool, hipStream_t s, uint32_t* parent) {
   hipLaunchKernelGGL(k_cc_sizes, grid, block, 0, s, (const uint32_t*)root, n, count);
   hipLaunchKernelGGL(k_cc_keys, grid, block, 0, s, (const uint32_t*)root, (const uint32_t*)count, (const uint32_t*)seeded, n, o.min_size, o.max_size, keys, n_kept_d);
   ST_CK("connected_components", hipGetLastError());
-  {
-    size_t tmp_bytes = 0;
-    void* tmp = nullptr;
-    ST_CK("connected_components", rocprim::radix_sort_keys(nullptr, tmp_bytes, keys, keys_sorted, n, 0u, 64u, s));
-    ST_CK("connected_components", pool.bytes(&tmp, tmp_bytes));
-    ST_CK("connected_components", rocprim::radix_sort_keys(tmp, tmp_bytes, keys, keys_sorted, n, 0u, 64u, s));
-  }
+  ST_CK("connected_components", prim_run(pool, prim_sort_keys(keys, keys_sorted, n, 0u, 64u, s)));
   unsigned int n_kept = 0;      // the one host round trip of the chain
   ST_CK("connected_components", hipMemcpyAsync(&n_kept, n_kept_d, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
   ST_CK("connected_components", hipStreamSynchronize(s));
@@ -326,16 +302,7 @@ int cc_finish(const CcOut& o, DevPool& pool, hipStream_t s, uint32_t* parent) {
     uint32_t *iota = root, *lab_sorted = reinterpret_cast<uint32_t*>(keys), *d_members = o.members, *d_offsets = o.offsets;      // (roots and unsorted keys are done with)
     if (host || !d_members) ST_CK("connected_components", pool.bytes(&d_members, n * sizeof(uint32_t)));
     if (host || !d_offsets) ST_CK("connected_components", pool.bytes(&d_offsets, ((size_t)n_kept + 1) * sizeof(uint32_t)));
-    hipLaunchKernelGGL(k_cc_init, grid, block, 0, s, iota, n);
-    size_t tmp_bytes = 0;
-    void* tmp = nullptr;
-    const unsigned bits = cc_bits(n_kept);
-    ST_CK("connected_components", rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_labels, lab_sorted, iota, d_members, n, 0u, bits, s));
-    ST_CK("connected_components", pool.bytes(&tmp, tmp_bytes));
-    ST_CK("connected_components", rocprim::radix_sort_pairs(tmp, tmp_bytes, d_labels, lab_sorted, iota, d_members, n, 0u, bits, s));
-    const uint32_t n32 = (uint32_t)n;
-    ST_CK("connected_components", hipMemcpyAsync(d_offsets + n_kept, &n32, sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_cc_offsets, grid, block, 0, s, (const uint32_t*)lab_sorted, n, d_offsets);
+    ST_CK("connected_components", group_by_label(pool, s, d_labels, n, (uint32_t)n_kept, iota, lab_sorted, d_members, d_offsets));
     ST_CK("connected_components", hipGetLastError());
     if (host && o.offsets) ST_CK("connected_components", hipMemcpyAsync(o.offsets, d_offsets, ((size_t)n_kept + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     if (host && o.members) ST_CK("connected_components", hipMemcpyAsync(o.members, d_members, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -359,7 +326,7 @@ int cc_run_fused(int device, const float* xyz, const float* nrm, const float* rg
     if (src[k]) ST_CK("connected_components", st_stage(pool, s, o.mem, src[k], n, &d_in[k]));
   uint32_t* parent = nullptr;
   ST_CK("connected_components", pool.bytes(&parent, n * sizeof(uint32_t)));
-  hipLaunchKernelGGL(k_cc_init, dim3(cc_blocks(n)), dim3(CC_THREADS), 0, s, parent, n);
+  hipLaunchKernelGGL(k_iota<uint32_t>, dim3(cc_blocks(n)), dim3(CC_THREADS), 0, s, parent, n);      // every point its own root
   if (cl.radius_sq > 0.0f) {
     F3* clean = nullptr;
     unsigned int *d_fin = nullptr, n_finite = 0;
@@ -403,7 +370,7 @@ int cc_run_lists(int device, const uint64_t* offsets, const uint32_t* idx, const
   }
   uint32_t* parent = nullptr;
   ST_CK("connected_components", pool.bytes(&parent, n * sizeof(uint32_t)));
-  hipLaunchKernelGGL(k_cc_init, dim3(cc_blocks(n)), dim3(CC_THREADS), 0, s, parent, n);
+  hipLaunchKernelGGL(k_iota<uint32_t>, dim3(cc_blocks(n)), dim3(CC_THREADS), 0, s, parent, n);      // every point its own root
   hipLaunchKernelGGL(k_cc_hook_lists, dim3((unsigned)((n + CC_THREADS - 1) / CC_THREADS)), dim3(CC_THREADS), 0, s, d_off, d_idx, d_keep, (unsigned long long)n_entries, (uint32_t)n,
                      skip_first ? 1u : 0u, parent);
   ST_CK("connected_components", hipGetLastError());

@@ -22,14 +22,12 @@
 // Every decision is in scratch before the first model row changes.  No floating-point atomics: two runs give the same bits.
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 
 #include "../../include/cilantro_hip/c_api.h"
+#include "device_prims.hpp"
 #include "image_device.hpp"
 #include "internal.hpp"
 #include "search_device.hpp"
@@ -109,29 +107,15 @@ __device__ __forceinline__ unsigned char fu_decision(const FuArgs& a, size_t k) 
   return FU_UNTOUCHED;
 }
 
-// rows of the block before this lane among those with `flag`, and the block's total in *total
-__device__ __forceinline__ uint32_t fu_rank(bool flag, uint32_t* total) {
-  __shared__ uint32_t s_cnt[IC_BLOCK / 64];
-  const unsigned long long mask = __ballot(flag);
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  __syncthreads();      // (a second call: the first one's readers are done)
-  if (lane == 0) s_cnt[wave] = (uint32_t)__popcll(mask);
-  __syncthreads();
-  uint32_t before = (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-  for (uint32_t v = 0; v < wave; ++v) before += s_cnt[v];
-  *total = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-  return before;
-}
-
 __global__ __launch_bounds__(IC_BLOCK) void k_fu_decide(FuArgs a) {
   const size_t k = (size_t)blockIdx.x * IC_BLOCK + threadIdx.x;
   const unsigned char d = fu_decision(a, k);
   if (k < a.npix) a.decision[k] = d;
   FuCount c;
-  (void)fu_rank(d == FU_FUSE, &c.fused);
-  (void)fu_rank(d == FU_APPEND, &c.appended);
-  (void)fu_rank(d == FU_REMOVE, &c.removed);
-  (void)fu_rank(d == FU_UNTOUCHED, &c.untouched);
+  (void)block_rank<IC_BLOCK>(d == FU_FUSE, &c.fused);
+  (void)block_rank<IC_BLOCK>(d == FU_APPEND, &c.appended);
+  (void)block_rank<IC_BLOCK>(d == FU_REMOVE, &c.removed);
+  (void)block_rank<IC_BLOCK>(d == FU_UNTOUCHED, &c.untouched);
   if (threadIdx.x == 0) a.block_counts[blockIdx.x] = c;
 }
 
@@ -140,7 +124,7 @@ __global__ __launch_bounds__(IC_BLOCK) void k_fu_fuse(FuArgs a) {
   const size_t k = (size_t)blockIdx.x * IC_BLOCK + threadIdx.x;
   const unsigned char d = k < a.npix ? a.decision[k] : (unsigned char)FU_NONE;
   uint32_t total;
-  const uint32_t rank = fu_rank(d == FU_REMOVE, &total);
+  const uint32_t rank = block_rank<IC_BLOCK>(d == FU_REMOVE, &total);
   if (d != FU_FUSE && d != FU_REMOVE) return;
   const uint32_t m = (uint32_t)a.keys_m[k];      // (< n_model: k_fu_decide checked it)
   if (d == FU_REMOVE) {
@@ -166,7 +150,7 @@ __global__ __launch_bounds__(IC_BLOCK) void k_fu_append(FuArgs a, size_t capacit
   const size_t k = (size_t)blockIdx.x * IC_BLOCK + threadIdx.x;
   const unsigned char d = k < a.npix ? a.decision[k] : (unsigned char)FU_NONE;
   uint32_t total;
-  const uint32_t rank = fu_rank(d == FU_APPEND, &total);
+  const uint32_t rank = block_rank<IC_BLOCK>(d == FU_APPEND, &total);
   if (d != FU_APPEND) return;
   const size_t row = (size_t)a.n_after_remove + a.block_counts[blockIdx.x].appended + rank;
   if (row >= capacity) return;      // (the host compared the total with the capacity before this launch)
@@ -203,7 +187,7 @@ __global__ __launch_bounds__(IC_BLOCK) void k_fu_unstable(const float* __restric
   const size_t i = (size_t)blockIdx.x * IC_BLOCK + threadIdx.x;
   const bool out = i < n && conf[i] < thresh;
   uint32_t total;
-  const uint32_t rank = fu_rank(out, &total);
+  const uint32_t rank = block_rank<IC_BLOCK>(out, &total);
   if (COUNT) { if (threadIdx.x == 0) block_counts[blockIdx.x] = total; return; }
   if (out) S[(size_t)block_counts[blockIdx.x] + rank] = (uint32_t)i;
 }
@@ -211,14 +195,10 @@ __global__ __launch_bounds__(IC_BLOCK) void k_fu_unstable(const float* __restric
 // F6 on the device: S (cnt members, `sorted` or not) leaves the n rows of m; returns through ST_CK's convention
 int fu_remove_rows(const char* F, DevPool& pool, hipStream_t s, uint32_t* S, uint32_t cnt, bool sorted, uint32_t n, const FuModel& m) {
   if (cnt == 0 || cnt >= n) return CILHIP_OK;      // (nothing leaves / the model is cleared: no row moves)
-  size_t tmp_bytes = 0;
-  void* tmp = nullptr;
   if (!sorted) {
     uint32_t* sorted_S = nullptr;
     ST_CK(F, pool.get(&sorted_S, cnt));
-    ST_CK(F, rocprim::radix_sort_keys(nullptr, tmp_bytes, S, sorted_S, (size_t)cnt, 0, 32, s));
-    ST_CK(F, pool.bytes(&tmp, tmp_bytes));
-    ST_CK(F, rocprim::radix_sort_keys(tmp, tmp_bytes, S, sorted_S, (size_t)cnt, 0, 32, s));
+    ST_CK(F, prim_run(pool, prim_sort_keys(S, sorted_S, (size_t)cnt, 0, 32, s)));
     S = sorted_S;
   }
   uint32_t *gone = nullptr, *gone_before = nullptr;
@@ -227,10 +207,7 @@ int fu_remove_rows(const char* F, DevPool& pool, hipStream_t s, uint32_t* S, uin
   ST_CK(F, hipMemsetAsync(gone, 0, (size_t)cnt * sizeof(uint32_t), s));
   hipLaunchKernelGGL(k_fu_tail, dim3(ic_blocks(cnt)), dim3(IC_BLOCK), 0, s, (const uint32_t*)S, cnt, n, gone);
   ST_CK(F, hipGetLastError());
-  tmp_bytes = 0;
-  ST_CK(F, rocprim::exclusive_scan(nullptr, tmp_bytes, gone, gone_before, 0u, (size_t)cnt, rocprim::plus<uint32_t>(), s));
-  ST_CK(F, pool.bytes(&tmp, tmp_bytes));
-  ST_CK(F, rocprim::exclusive_scan(tmp, tmp_bytes, gone, gone_before, 0u, (size_t)cnt, rocprim::plus<uint32_t>(), s));
+  ST_CK(F, prim_run(pool, prim_exclusive_sum(gone, gone_before, (size_t)cnt, s)));
   hipLaunchKernelGGL(k_fu_move, dim3(ic_blocks(cnt)), dim3(IC_BLOCK), 0, s, (const uint32_t*)S, cnt, n, (const uint32_t*)gone, (const uint32_t*)gone_before, m);
   ST_CK(F, hipGetLastError());
   return CILHIP_OK;
@@ -317,11 +294,7 @@ int fu_run(const FuCall& c, int device) {
   ST_CK(F, hipMemsetAsync(a.block_counts + nblocks, 0, sizeof(FuCount), s));
   hipLaunchKernelGGL(k_fu_decide, dim3(nblocks), dim3(IC_BLOCK), 0, s, a);
   ST_CK(F, hipGetLastError());
-  size_t tmp_bytes = 0;
-  void* tmp = nullptr;
-  ST_CK(F, rocprim::exclusive_scan(nullptr, tmp_bytes, a.block_counts, a.block_counts, FuCount{0, 0, 0, 0}, (size_t)nblocks + 1, FuPlus(), s));
-  ST_CK(F, pool.bytes(&tmp, tmp_bytes));
-  ST_CK(F, rocprim::exclusive_scan(tmp, tmp_bytes, a.block_counts, a.block_counts, FuCount{0, 0, 0, 0}, (size_t)nblocks + 1, FuPlus(), s));
+  ST_CK(F, prim_run(pool, prim_exclusive_scan(a.block_counts, a.block_counts, FuCount{0, 0, 0, 0}, (size_t)nblocks + 1, FuPlus(), s)));
   FuCount total{};
   ST_CK(F, hipMemcpyAsync(&total, a.block_counts + nblocks, sizeof(FuCount), hipMemcpyDeviceToHost, s));
   ST_CK(F, hipStreamSynchronize(s));
@@ -361,11 +334,7 @@ int fu_run_unstable(int device, float* xyz, float* nrm, float* rgb, float* conf,
   ST_CK(F, hipMemsetAsync(counts + nblocks, 0, sizeof(uint32_t), s));
   hipLaunchKernelGGL((k_fu_unstable<true>), dim3(nblocks), dim3(IC_BLOCK), 0, s, (const float*)m.conf, (uint32_t)n, thresh, counts, (uint32_t*)nullptr);
   ST_CK(F, hipGetLastError());
-  size_t tmp_bytes = 0;
-  void* tmp = nullptr;
-  ST_CK(F, rocprim::exclusive_scan(nullptr, tmp_bytes, counts, counts, 0u, (size_t)nblocks + 1, rocprim::plus<uint32_t>(), s));
-  ST_CK(F, pool.bytes(&tmp, tmp_bytes));
-  ST_CK(F, rocprim::exclusive_scan(tmp, tmp_bytes, counts, counts, 0u, (size_t)nblocks + 1, rocprim::plus<uint32_t>(), s));
+  ST_CK(F, prim_run(pool, prim_exclusive_sum(counts, counts, (size_t)nblocks + 1, s)));
   uint32_t total = 0;
   ST_CK(F, hipMemcpyAsync(&total, counts + nblocks, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   ST_CK(F, hipStreamSynchronize(s));

@@ -13,14 +13,11 @@
 
 #include <cstring>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/iterator/reverse_iterator.hpp>
-
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
+#include "device_prims.hpp"
 #include "grid_policy.hpp"
 #include "internal.hpp"
 
@@ -142,17 +139,21 @@ __global__ void k_run_starts(const uint32_t* __restrict__ keys_sorted, uint32_t 
   if (blockIdx.x == 0 && threadIdx.x == 0 && (n == 0 || keys_sorted[n - 1] != ncells)) cell_start[ncells] = n;
 }
 static inline int grid_blocks(uint32_t n);
+// a rocPRIM call (device_prims.hpp) in a temporary block of its own, freed once the stream has run it
+template <class Op> static hipError_t run_and_wait(Op op, hipStream_t s) {
+  size_t tmp_bytes = 0;
+  HIP_TRY(op(nullptr, tmp_bytes));
+  DevBuf<unsigned char> tmp;
+  HIP_TRY(tmp.alloc(tmp_bytes));
+  hipError_t e = op(tmp.get(), tmp_bytes);
+  hipError_t e2 = hipStreamSynchronize(s);
+  return e != hipSuccess ? e : e2;
+}
 static hipError_t cell_start_table(const uint32_t* keys_sorted, uint32_t n, uint32_t ncells, uint32_t* cell_start, hipStream_t s) {
   HIP_TRY(hipMemsetAsync(cell_start, 0xFF, ((size_t)ncells + 1) * sizeof(uint32_t), s));
   hipLaunchKernelGGL(k_run_starts, dim3(grid_blocks(n)), dim3(256), 0, s, keys_sorted, n, ncells, cell_start);
   auto rit = rocprim::make_reverse_iterator(cell_start + (size_t)ncells + 1);
-  size_t tmp_bytes = 0;
-  HIP_TRY(rocprim::inclusive_scan(nullptr, tmp_bytes, rit, rit, (size_t)ncells + 1, rocprim::minimum<uint32_t>(), s));
-  DevBuf<unsigned char> tmp;
-  HIP_TRY(tmp.alloc(tmp_bytes));
-  hipError_t e = rocprim::inclusive_scan(tmp.get(), tmp_bytes, rit, rit, (size_t)ncells + 1, rocprim::minimum<uint32_t>(), s);
-  hipError_t e2 = hipStreamSynchronize(s);
-  return e != hipSuccess ? e : e2;
+  return run_and_wait(prim_inclusive_scan(rit, rit, (size_t)ncells + 1, rocprim::minimum<uint32_t>(), s), s);
 }
 
 __global__ void k_gather(const float* __restrict__ xyz, const float* __restrict__ nrm, const uint32_t* __restrict__ perm,
@@ -176,16 +177,6 @@ __global__ void k_occupancy(const uint32_t* __restrict__ cell_start, uint32_t nc
 }
 
 static inline int grid_blocks(uint32_t n) { return (int)std::min<uint32_t>((n + 255) / 256, 8192u) + (n == 0); }
-
-static hipError_t sort_pairs(uint32_t* k_in, uint32_t* k_out, uint32_t* v_in, uint32_t* v_out, uint32_t n, unsigned bits, hipStream_t s) {
-  size_t tmp_bytes = 0;
-  HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, k_in, k_out, v_in, v_out, (size_t)n, 0u, bits, s));
-  DevBuf<unsigned char> tmp;
-  HIP_TRY(tmp.alloc(tmp_bytes));
-  hipError_t e = rocprim::radix_sort_pairs(tmp.get(), tmp_bytes, k_in, k_out, v_in, v_out, (size_t)n, 0u, bits, s);
-  hipError_t e2 = hipStreamSynchronize(s);
-  return e != hipSuccess ? e : e2;
-}
 
 static unsigned bits_for(uint32_t ncells) {
   unsigned b = 1;
@@ -247,7 +238,7 @@ hipError_t build_grid(const float* d_xyz, const float* d_nrm, uint32_t n, hipStr
     HIP_TRY(st.cell_start.alloc(ncells + 1));
     uint32_t* const cs = st.cell_start;
     hipLaunchKernelGGL(k_cell_keys, dim3(grid_blocks(n)), dim3(256), 0, s, d_xyz, n, g, k_in.get(), v_in.get());
-    HIP_TRY(sort_pairs(k_in, k_out, v_in, v_out, n, bits_for((uint32_t)ncells + 1u), s));      // (+ 1: the key of the points without a cell)
+    HIP_TRY(run_and_wait(prim_sort_pairs(k_in.get(), k_out.get(), v_in.get(), v_out.get(), (size_t)n, 0u, bits_for((uint32_t)ncells + 1u), s), s));      // (+ 1: the key of the points without a cell)
     HIP_TRY(cell_start_table(k_out, n, (uint32_t)ncells, cs, s));
     HIP_TRY(hipMemsetAsync(d_occ, 0, sizeof(double), s));
     hipLaunchKernelGGL(k_occupancy, dim3(grid_blocks((uint32_t)ncells)), dim3(256), 0, s, cs, (uint32_t)ncells, d_occ.get());
@@ -368,8 +359,8 @@ hipError_t sort_source(const float* d_xyz, uint32_t n, const GridDev& g, const f
   // one slab of scratch: 4 key / value arrays, 3 per-cube arrays, the temporaries of the sort and of the scan
   uint32_t* nul = nullptr;
   size_t sort_tmp = 0, scan_tmp = 0;
-  HIP_TRY(rocprim::radix_sort_pairs(nullptr, sort_tmp, nul, nul, nul, nul, (size_t)n, 0u, bits, s));
-  HIP_TRY(rocprim::exclusive_scan(nullptr, scan_tmp, nul, nul, 0u, (size_t)ncubes + 1, rocprim::plus<uint32_t>(), s));
+  HIP_TRY(prim_sort_pairs(nul, nul, nul, nul, (size_t)n, 0u, bits, s)(nullptr, sort_tmp));
+  HIP_TRY(prim_exclusive_sum(nul, nul, (size_t)ncubes + 1, s)(nullptr, scan_tmp));
   auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const size_t arr = up((size_t)n * 4), carr = up(((size_t)ncubes + 1) * 4);
   const size_t need = 4 * arr + 3 * carr + up(sort_tmp ? sort_tmp : 16) + up(scan_tmp ? scan_tmp : 16);
@@ -386,14 +377,14 @@ hipError_t sort_source(const float* d_xyz, uint32_t n, const GridDev& g, const f
   for (int i = 0; i < 16; ++i) tf.m[i] = T[i];
   do {
     hipLaunchKernelGGL(k_cube_keys_tf, dim3(grid_blocks(n)), dim3(256), 0, s, d_xyz, n, g, tf, k_in, v_in);
-    if ((e = rocprim::radix_sort_pairs(tmp_sort, sort_tmp, k_in, k_out, v_in, v_out, (size_t)n, 0u, bits, s)) != hipSuccess) break;
+    if ((e = prim_sort_pairs(k_in, k_out, v_in, v_out, (size_t)n, 0u, bits, s)(tmp_sort, sort_tmp)) != hipSuccess) break;
     hipLaunchKernelGGL(k_gather, dim3(grid_blocks(n)), dim3(256), 0, s, d_xyz, (const float*)nullptr, v_out, n, d_out, (float4*)nullptr);
     // cube_start[] over the sorted cube ids, then the tile table
     hipLaunchKernelGGL(k_shift_keys, dim3(grid_blocks(n)), dim3(256), 0, s, k_out, n, k_in);
     hipLaunchKernelGGL(k_cell_start, dim3(grid_blocks(n + 1)), dim3(256), 0, s, k_in, n, ncubes, cube_start);
     if ((e = hipMemsetAsync(tcount, 0, ((size_t)ncubes + 1) * 4, s)) != hipSuccess) break;
     hipLaunchKernelGGL(k_tile_counts, dim3(grid_blocks(ncubes)), dim3(256), 0, s, cube_start, ncubes, tcount);
-    if ((e = rocprim::exclusive_scan(tmp_scan, scan_tmp, tcount, toff, 0u, (size_t)ncubes + 1, rocprim::plus<uint32_t>(), s)) != hipSuccess) break;
+    if ((e = prim_exclusive_sum(tcount, toff, (size_t)ncubes + 1, s)(tmp_scan, scan_tmp)) != hipSuccess) break;
     uint32_t ntiles = 0;
     if ((e = hipMemcpyAsync(&ntiles, toff + ncubes, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) break;
     if ((e = hipStreamSynchronize(s)) != hipSuccess) break;

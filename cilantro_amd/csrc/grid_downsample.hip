@@ -24,9 +24,6 @@
 //                    chain fed from lane broadcasts (v_readlane) -- it waits on add latency, not on memory
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -34,6 +31,7 @@
 #include <vector>
 
 #include "../../include/cilantro_hip/c_api.h"
+#include "device_prims.hpp"
 #include "internal.hpp"
 #include "stateless.hpp"
 
@@ -301,26 +299,21 @@ int gd_sort_and_fold(const GdCall& c, DevPool& pool, hipStream_t s, const F3* d_
   ST_CK("grid_downsample", pool.bytes(&k_in, n * sizeof(KeyT))); ST_CK("grid_downsample", pool.bytes(&k_out, n * sizeof(KeyT)));
   ST_CK("grid_downsample", pool.bytes(&v_in, (n + 1) * sizeof(uint32_t))); ST_CK("grid_downsample", pool.bytes(&v_out, n * sizeof(uint32_t)));
   hipLaunchKernelGGL((k_gd_keys<KeyT>), dim3(gd_blocks(n)), dim3(256), 0, s, d_xyz, n, pk, k_in, v_in);
-  {
-    size_t tmp_bytes = 0;
-    void* tmp = nullptr;
-    ST_CK("grid_downsample", rocprim::radix_sort_pairs(nullptr, tmp_bytes, k_in, k_out, v_in, v_out, n, 0u, end_bit, s));
-    ST_CK("grid_downsample", pool.bytes(&tmp, tmp_bytes));
-    ST_CK("grid_downsample", rocprim::radix_sort_pairs(tmp, tmp_bytes, k_in, k_out, v_in, v_out, n, 0u, end_bit, s));
-  }
+  ST_CK("grid_downsample", prim_run(pool, prim_sort_pairs(k_in, k_out, v_in, v_out, n, 0u, end_bit, s)));
   // the first m sorted positions are the points that have a bin
   uint32_t* bin_of = reinterpret_cast<uint32_t*>(k_in);      // (the unsorted keys are done with)
   hipLaunchKernelGGL((k_gd_heads<KeyT>), dim3(gd_blocks(m)), dim3(256), 0, s, (const KeyT*)k_out, m, bin_of);
-  void* scan_tmp = nullptr;
+  void* scan_tmp = nullptr;      // one block for every scan below: the larger of the two requests
   size_t scan_bytes = 0;
+  const auto bin_scan = prim_inclusive_sum(bin_of, bin_of, m, s);
   {
     size_t b1 = 0, b2 = 0;
-    ST_CK("grid_downsample", rocprim::inclusive_scan(nullptr, b1, bin_of, bin_of, m, rocprim::plus<uint32_t>(), s));
-    ST_CK("grid_downsample", rocprim::exclusive_scan(nullptr, b2, bin_of, bin_of, 0u, n + 1, rocprim::plus<uint32_t>(), s));
+    ST_CK("grid_downsample", bin_scan(nullptr, b1));
+    ST_CK("grid_downsample", prim_exclusive_sum(bin_of, bin_of, n + 1, s)(nullptr, b2));
     scan_bytes = std::max(b1, b2);
     ST_CK("grid_downsample", pool.bytes(&scan_tmp, scan_bytes));
   }
-  ST_CK("grid_downsample", rocprim::inclusive_scan(scan_tmp, scan_bytes, bin_of, bin_of, m, rocprim::plus<uint32_t>(), s));
+  ST_CK("grid_downsample", bin_scan(scan_tmp, scan_bytes));
   uint32_t nbins = 0;
   ST_CK("grid_downsample", hipMemcpyAsync(&nbins, bin_of + (m - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   ST_CK("grid_downsample", hipStreamSynchronize(s));
@@ -332,13 +325,13 @@ int gd_sort_and_fold(const GdCall& c, DevPool& pool, hipStream_t s, const F3* d_
   uint32_t rows = 0;
   if (c.bin_order == 1) {
     hipLaunchKernelGGL(k_gd_keep, dim3(gd_blocks((size_t)nbins + 1)), dim3(256), 0, s, (const uint32_t*)start, nbins, min_pts, slot);
-    ST_CK("grid_downsample", rocprim::exclusive_scan(scan_tmp, scan_bytes, slot, slot, 0u, (size_t)nbins + 1, rocprim::plus<uint32_t>(), s));
+    ST_CK("grid_downsample", prim_exclusive_sum(slot, slot, (size_t)nbins + 1, s)(scan_tmp, scan_bytes));
     ST_CK("grid_downsample", hipMemcpyAsync(&rows, slot + nbins, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   } else {
     uint32_t* mark = v_in;      // (the unsorted indices are done with; n + 1 entries)
     ST_CK("grid_downsample", hipMemsetAsync(mark, 0, (n + 1) * sizeof(uint32_t), s));
     hipLaunchKernelGGL(k_gd_mark, dim3(gd_blocks(nbins)), dim3(256), 0, s, (const uint32_t*)start, (const uint32_t*)v_out, nbins, min_pts, mark);
-    ST_CK("grid_downsample", rocprim::exclusive_scan(scan_tmp, scan_bytes, mark, mark, 0u, n + 1, rocprim::plus<uint32_t>(), s));
+    ST_CK("grid_downsample", prim_exclusive_sum(mark, mark, n + 1, s)(scan_tmp, scan_bytes));
     hipLaunchKernelGGL(k_gd_slots, dim3(gd_blocks(nbins)), dim3(256), 0, s, (const uint32_t*)start, (const uint32_t*)v_out, nbins, (const uint32_t*)mark, slot);
     ST_CK("grid_downsample", hipMemcpyAsync(&rows, mark + n, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   }

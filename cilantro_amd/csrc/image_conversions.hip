@@ -21,14 +21,13 @@
 //   k_ic_resolve_*          one lane per pixel: key -> index / u16 / f32 / rgb
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_scan.hpp>
-
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 
 #include "../../include/cilantro_hip/c_api.h"
+#include "device_prims.hpp"
 #include "image_device.hpp"
 #include "internal.hpp"
 #include "stateless.hpp"
@@ -97,17 +96,12 @@ __global__ __launch_bounds__(IC_BLOCK) void k_ic_unproject(IcUnproject a) {
   }
   size_t row = k;
   if (!a.keep_invalid) {
-    const unsigned long long mask = __ballot(keep);
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    __shared__ uint32_t s_cnt[IC_BLOCK / 64];
-    if (lane == 0) s_cnt[wave] = (uint32_t)__popcll(mask);
-    __syncthreads();
+    uint32_t total;
+    const uint32_t before = block_rank<IC_BLOCK>(keep, &total);
     if (COUNT) {
-      if (threadIdx.x == 0) a.block_counts[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+      if (threadIdx.x == 0) a.block_counts[blockIdx.x] = total;
       return;
     }
-    uint32_t before = (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-    for (uint32_t v = 0; v < wave; ++v) before += s_cnt[v];
     row = (size_t)a.block_offs[blockIdx.x] + before;
   }
   if (COUNT || !keep) return;
@@ -220,11 +214,7 @@ int ic_run_to_points(const IcToPoints& c, int device) {
     a.block_counts = counts;
     hipLaunchKernelGGL((k_ic_unproject<true>), dim3(nblocks), dim3(IC_BLOCK), 0, s, a);
     ST_CK(F, hipGetLastError());
-    size_t tmp_bytes = 0;
-    void* tmp = nullptr;
-    ST_CK(F, rocprim::exclusive_scan(nullptr, tmp_bytes, counts, counts, 0u, (size_t)nblocks + 1, rocprim::plus<uint32_t>(), s));
-    ST_CK(F, pool.bytes(&tmp, tmp_bytes));
-    ST_CK(F, rocprim::exclusive_scan(tmp, tmp_bytes, counts, counts, 0u, (size_t)nblocks + 1, rocprim::plus<uint32_t>(), s));
+    ST_CK(F, prim_run(pool, prim_exclusive_sum(counts, counts, (size_t)nblocks + 1, s)));
     uint32_t total = 0;
     ST_CK(F, hipMemcpyAsync(&total, counts + nblocks, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     ST_CK(F, hipStreamSynchronize(s));

@@ -20,11 +20,11 @@
 // from ALL points at exactly that distance, first met first.  Rule 0: lowest index (the keys' own order).
 // Queries are processed in target-grid cell order (neighbouring lanes scan the same cells).
 #include "../../include/cilantro_hip/c_api.h"
+#include "device_prims.hpp"
 #include "internal.hpp"
 #include "stateless.hpp"
 
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
 #include <cmath>
@@ -587,11 +587,12 @@ int radius_impl(int device, const float* ref_xyz, size_t n_ref, const float* que
     hipLaunchKernelGGL((k_radius_lists<false>), dim3(nblk), dim3(KNN_THREADS), 0, s, gr.grid, (const float4*)d_qs, (uint32_t)n_query, radius_sq, d_cnt,
                        (unsigned long long*)nullptr);
     {  // counts -> offsets (exclusive scan over n_query + 1 entries: the last one is the total), in place
+      const auto scan = prim_exclusive_sum(d_cnt, d_cnt, n_query + 1, s);
       size_t tmp_bytes = 0;
-      ST_CK("radius_search", rocprim::exclusive_scan(nullptr, tmp_bytes, d_cnt, d_cnt, 0ull, n_query + 1, rocprim::plus<unsigned long long>(), s));
+      ST_CK("radius_search", scan(nullptr, tmp_bytes));
       DevBuf<unsigned char> d_tmp;
       ST_CK("radius_search", d_tmp.alloc(tmp_bytes));
-      ST_CK("radius_search", rocprim::exclusive_scan(d_tmp.get(), tmp_bytes, d_cnt, d_cnt, 0ull, n_query + 1, rocprim::plus<unsigned long long>(), s));
+      ST_CK("radius_search", scan(d_tmp.get(), tmp_bytes));
     }
     ST_CK("radius_search", hipMemcpyAsync(offsets_out, d_cnt, (n_query + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     ST_CK("radius_search", hipStreamSynchronize(s));
@@ -605,11 +606,9 @@ int radius_impl(int device, const float* ref_xyz, size_t n_ref, const float* que
       ST_CK("radius_search", pool.get(&d_off32, n_query + 1));
       hipLaunchKernelGGL(k_offsets32, dim3(256), dim3(256), 0, s, (const unsigned long long*)d_cnt, (uint32_t)(n_query + 1), d_off32);
       {
-        size_t tmp_bytes = 0;
-        ST_CK("radius_search", rocprim::segmented_radix_sort_keys(nullptr, tmp_bytes, d_keys, d_keys2, (unsigned int)total, (unsigned int)n_query, d_off32, d_off32 + 1, 0, 64, s));
-        void* d_tmp = nullptr;
-        ST_CK("radius_search", pool.bytes(&d_tmp, tmp_bytes));
-        ST_CK("radius_search", rocprim::segmented_radix_sort_keys(d_tmp, tmp_bytes, d_keys, d_keys2, (unsigned int)total, (unsigned int)n_query, d_off32, d_off32 + 1, 0, 64, s));
+        ST_CK("radius_search", prim_run(pool, [&](void* tmp, size_t& bytes) {
+          return rocprim::segmented_radix_sort_keys(tmp, bytes, d_keys, d_keys2, (unsigned int)total, (unsigned int)n_query, d_off32, d_off32 + 1, 0, 64, s);
+        }));
       }
       ST_CK("radius_search", pool.get(&d_idx, total));
       if (d2_out) ST_CK("radius_search", pool.get(&d_d2, total));

@@ -27,15 +27,13 @@
 //   cluster for the mode.
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
 #include <algorithm>
 #include <cfloat>
 #include <chrono>
 #include <cmath>
 
 #include "../../include/cilantro_hip/c_api.h"
+#include "device_prims.hpp"
 #include "internal.hpp"
 #include "search_device.hpp"
 #include "stateless.hpp"
@@ -68,10 +66,6 @@ __device__ __forceinline__ void ms_ball_cells(const GridDev& g, float qx, float 
   x0 = max((int)floorf(fminf(fmaxf((qx - r - g.ox) * g.inv_cell, -BIG), BIG)), 0); x1 = min((int)floorf(fminf(fmaxf((qx + r - g.ox) * g.inv_cell, -BIG), BIG)), g.nx - 1);
   y0 = max((int)floorf(fminf(fmaxf((qy - r - g.oy) * g.inv_cell, -BIG), BIG)), 0); y1 = min((int)floorf(fminf(fmaxf((qy + r - g.oy) * g.inv_cell, -BIG), BIG)), g.ny - 1);
   z0 = max((int)floorf(fminf(fmaxf((qz - r - g.oz) * g.inv_cell, -BIG), BIG)), 0); z1 = min((int)floorf(fminf(fmaxf((qz + r - g.oz) * g.inv_cell, -BIG), BIG)), g.nz - 1);
-}
-
-__global__ __launch_bounds__(MS_THREADS) void k_ms_iota(uint32_t* __restrict__ a, size_t n) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) a[i] = (uint32_t)i;
 }
 
 // points with a non-finite coordinate become (NaN, NaN, NaN): in no cell, in nobody's ball (components.hip k_cc_clean)
@@ -140,21 +134,14 @@ __global__ __launch_bounds__(MS_THREADS) void k_ms_shift(GridDev g, int have_gri
     if (nw.x != nw.x) *nan_flag = 1u;      // (every writer stores the same word)
     else keep = !(d2_pinned(q.x, q.y, q.z, nw.x, nw.y, nw.z) < m.conv_tol_sq);
   }
-  const unsigned long long b = __ballot(keep);
-  if (b) {
-    const int first = __ffsll((long long)b) - 1;
-    unsigned int base = 0;
-    if ((int)lane == first) base = atomicAdd(cursor, (unsigned int)__popcll(b));
-    base = (unsigned int)__shfl((int)base, first, 64);
-    if (keep) next[base + (unsigned int)__popcll(b & ((1ull << lane) - 1ull))] = i;
-  }
+  const unsigned int at = wave_append(keep, cursor);
+  if (keep) next[at] = i;
 }
 
 // ---- grouping ------------------------------------------------------------------------------------------------------------------
 // state: MS_LEADER for a non-finite seed (~ nobody: its own cluster), MS_UNDECIDED otherwise; U = the undecided seeds
 __global__ __launch_bounds__(MS_THREADS) void k_ms_group_init(const F3* __restrict__ cur, size_t ns, uint32_t* __restrict__ state, uint32_t* __restrict__ lead_of,
                                                               uint32_t* __restrict__ U, unsigned int* cursor) {
-  const unsigned lane = threadIdx.x & 63u;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t base_i = (size_t)blockIdx.x * blockDim.x; base_i < ns; base_i += stride) {      // (wave-uniform trip count)
     const size_t i = base_i + threadIdx.x;
@@ -165,14 +152,8 @@ __global__ __launch_bounds__(MS_THREADS) void k_ms_group_init(const F3* __restri
       state[i] = und ? MS_UNDECIDED : MS_LEADER;
       lead_of[i] = und ? NONE_U32 : (uint32_t)i;
     }
-    const unsigned long long b = __ballot(und);
-    if (b) {
-      const int first = __ffsll((long long)b) - 1;
-      unsigned int base = 0;
-      if ((int)lane == first) base = atomicAdd(cursor, (unsigned int)__popcll(b));
-      base = (unsigned int)__shfl((int)base, first, 64);
-      if (und) U[base + (unsigned int)__popcll(b & ((1ull << lane) - 1ull))] = (uint32_t)i;
-    }
+    const unsigned int at = wave_append(und, cursor);
+    if (und) U[at] = (uint32_t)i;
   }
 }
 
@@ -182,7 +163,6 @@ __global__ __launch_bounds__(MS_THREADS) void k_ms_group_init(const F3* __restri
 // other one stops at the first record that is still undecided and close.
 __global__ __launch_bounds__(MS_THREADS) void k_ms_lead(GridDev g, float tol_sq, const F3* __restrict__ cur, const uint32_t* __restrict__ state, const uint32_t* __restrict__ U,
                                                         uint32_t n_u, uint32_t* __restrict__ new_leaders, unsigned int* cursor) {
-  const unsigned lane = threadIdx.x & 63u;
   const size_t slot = (size_t)blockIdx.x * MS_THREADS + threadIdx.x;
   bool leader = false;
   uint32_t i = 0u;
@@ -207,14 +187,8 @@ __global__ __launch_bounds__(MS_THREADS) void k_ms_lead(GridDev g, float tol_sq,
         }
       }
   }
-  const unsigned long long b = __ballot(leader);
-  if (b) {
-    const int first = __ffsll((long long)b) - 1;
-    unsigned int base = 0;
-    if ((int)lane == first) base = atomicAdd(cursor, (unsigned int)__popcll(b));
-    base = (unsigned int)__shfl((int)base, first, 64);
-    if (leader) new_leaders[base + (unsigned int)__popcll(b & ((1ull << lane) - 1ull))] = i;
-  }
+  const unsigned int at = wave_append(leader, cursor);
+  if (leader) new_leaders[at] = i;
 }
 
 // one wave per new leader L: every seed ~ L that is still undecided is decided now (a member), and every seed ~ L, decided in this round
@@ -249,19 +223,12 @@ __global__ __launch_bounds__(MS_THREADS) void k_ms_claim(GridDev g, float tol_sq
 
 __global__ __launch_bounds__(MS_THREADS) void k_ms_compact(const uint32_t* __restrict__ state, const uint32_t* __restrict__ U, uint32_t n_u, uint32_t* __restrict__ next,
                                                            unsigned int* cursor) {
-  const unsigned lane = threadIdx.x & 63u;
   const size_t slot = (size_t)blockIdx.x * MS_THREADS + threadIdx.x;
   uint32_t i = 0u;
   bool keep = false;
   if (slot < n_u) { i = U[slot]; keep = state[i] == MS_UNDECIDED; }
-  const unsigned long long b = __ballot(keep);
-  if (b) {
-    const int first = __ffsll((long long)b) - 1;
-    unsigned int base = 0;
-    if ((int)lane == first) base = atomicAdd(cursor, (unsigned int)__popcll(b));
-    base = (unsigned int)__shfl((int)base, first, 64);
-    if (keep) next[base + (unsigned int)__popcll(b & ((1ull << lane) - 1ull))] = i;
-  }
+  const unsigned int at = wave_append(keep, cursor);
+  if (keep) next[at] = i;
 }
 
 __global__ __launch_bounds__(MS_THREADS) void k_ms_flags(const uint32_t* __restrict__ state, size_t ns, uint32_t* __restrict__ flags) {
@@ -270,13 +237,6 @@ __global__ __launch_bounds__(MS_THREADS) void k_ms_flags(const uint32_t* __restr
 // rank[] = exclusive sum of the leader flags: a leader's rank is its cluster's number
 __global__ __launch_bounds__(MS_THREADS) void k_ms_labels(const uint32_t* __restrict__ lead_of, const uint32_t* __restrict__ rank, size_t ns, uint32_t* __restrict__ labels) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < ns; i += (size_t)gridDim.x * blockDim.x) labels[i] = rank[lead_of[i]];
-}
-// offsets[k] = first sorted position of label k (components.hip k_cc_offsets); offsets[n_clusters] is preset to ns
-__global__ __launch_bounds__(MS_THREADS) void k_ms_offsets(const uint32_t* __restrict__ labels_sorted, size_t ns, uint32_t* __restrict__ offsets) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < ns; i += (size_t)gridDim.x * blockDim.x) {
-    const uint32_t l = labels_sorted[i];
-    if (i == 0 || labels_sorted[i - 1] != l) offsets[l] = (uint32_t)i;
-  }
 }
 // one wave per cluster: lane l sums members l, l + 64, ... in f64, a fixed shuffle tree adds the 64 partials, lane 0 divides by the size
 __global__ __launch_bounds__(MS_THREADS) void k_ms_modes(const F3* __restrict__ cur, const uint32_t* __restrict__ members, const uint32_t* __restrict__ offsets, uint32_t n_clusters,
@@ -298,11 +258,6 @@ __global__ __launch_bounds__(MS_THREADS) void k_ms_modes(const F3* __restrict__ 
 
 inline int ms_blocks(size_t n) { return (int)std::min<size_t>((n + MS_THREADS - 1) / MS_THREADS, 2048) + (n == 0); }
 inline unsigned ms_launch(size_t slots, size_t per_block) { return (unsigned)((slots + per_block - 1) / per_block); }
-unsigned ms_bits(uint32_t v) {      // bits that hold 0 .. v
-  unsigned b = 1;
-  while (b < 32 && (1ull << b) <= (unsigned long long)v) ++b;
-  return b;
-}
 double ms_now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 #define MS_CK(call) ST_CK("mean_shift", call)
@@ -381,14 +336,9 @@ int ms_run(const MsArgs& a) {
       if (a.prm.form == 0) wave = stats.est_ball >= MS_WAVE_FORM_MIN_BALL;
       // the first active list: the seeds in the order of their starting cells (a wave's lanes then walk the same cells)
       hipLaunchKernelGGL(k_ms_seed_keys, dim3(ms_blocks(ns)), block, 0, s, pgrid.grid, (const F3*)cur, ns, keys, list_b);
-      size_t tmp_bytes = 0;
-      void* tmp = nullptr;
-      const unsigned bits = ms_bits((uint32_t)pgrid.n_cells);
-      MS_CK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys, keys_sorted, list_b, list_a, ns, 0u, bits, s));
-      MS_CK(pool.bytes(&tmp, tmp_bytes));
-      MS_CK(rocprim::radix_sort_pairs(tmp, tmp_bytes, keys, keys_sorted, list_b, list_a, ns, 0u, bits, s));
+      MS_CK(prim_run(pool, prim_sort_pairs(keys, keys_sorted, list_b, list_a, ns, 0u, key_bits((uint32_t)pgrid.n_cells), s)));
     } else {
-      hipLaunchKernelGGL(k_ms_iota, dim3(ms_blocks(ns)), block, 0, s, list_a, ns);
+      hipLaunchKernelGGL(k_iota<uint32_t>, dim3(ms_blocks(ns)), block, 0, s, list_a, ns);
     }
     stats.form_used = wave ? 2 : 1;
     const MsShift m{radius_sq, a.prm.convergence_tol * a.prm.convergence_tol, a.prm.kernel_kind,
@@ -447,13 +397,7 @@ int ms_run(const MsArgs& a) {
   // cluster numbers = ranks of the leaders
   uint32_t *flags = list_a, *rank = list_b;      // (the lists are done with)
   hipLaunchKernelGGL(k_ms_flags, dim3(ms_blocks(ns)), block, 0, s, (const uint32_t*)state, ns, flags);
-  {
-    size_t tmp_bytes = 0;
-    void* tmp = nullptr;
-    MS_CK(rocprim::exclusive_scan(nullptr, tmp_bytes, flags, rank, 0u, ns, rocprim::plus<uint32_t>(), s));
-    MS_CK(pool.bytes(&tmp, tmp_bytes));
-    MS_CK(rocprim::exclusive_scan(tmp, tmp_bytes, flags, rank, 0u, ns, rocprim::plus<uint32_t>(), s));
-  }
+  MS_CK(prim_run(pool, prim_exclusive_sum(flags, rank, ns, s)));
   uint32_t last[2] = {0, 0};
   MS_CK(hipMemcpyAsync(&last[0], rank + (ns - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   MS_CK(hipMemcpyAsync(&last[1], flags + (ns - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -472,16 +416,7 @@ int ms_run(const MsArgs& a) {
     F3* d_modes = reinterpret_cast<F3*>(a.modes);
     if (host || !d_members) MS_CK(pool.bytes(&d_members, ns * sizeof(uint32_t)));
     if (host || !d_offsets) MS_CK(pool.bytes(&d_offsets, ((size_t)n_clusters + 1) * sizeof(uint32_t)));
-    hipLaunchKernelGGL(k_ms_iota, dim3(ms_blocks(ns)), block, 0, s, iota, ns);
-    size_t tmp_bytes = 0;
-    void* tmp = nullptr;
-    const unsigned bits = ms_bits(n_clusters);
-    MS_CK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_labels, lab_sorted, iota, d_members, ns, 0u, bits, s));
-    MS_CK(pool.bytes(&tmp, tmp_bytes));
-    MS_CK(rocprim::radix_sort_pairs(tmp, tmp_bytes, d_labels, lab_sorted, iota, d_members, ns, 0u, bits, s));
-    const uint32_t ns32 = (uint32_t)ns;
-    MS_CK(hipMemcpyAsync(d_offsets + n_clusters, &ns32, sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_ms_offsets, dim3(ms_blocks(ns)), block, 0, s, (const uint32_t*)lab_sorted, ns, d_offsets);
+    MS_CK(group_by_label(pool, s, d_labels, ns, n_clusters, iota, lab_sorted, d_members, d_offsets));
     if (a.modes) {
       if (host) MS_CK(pool.bytes(&d_modes, (size_t)n_clusters * sizeof(F3)));
       hipLaunchKernelGGL(k_ms_modes, dim3(std::min<unsigned>(ms_launch(n_clusters, MS_WAVES), 4096u)), block, 0, s, (const F3*)cur, (const uint32_t*)d_members, (const uint32_t*)d_offsets,

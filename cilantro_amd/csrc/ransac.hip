@@ -16,6 +16,7 @@
 // the same plane.  Model fit: f32 per-term arithmetic, f64 accumulation in a fixed order (bitwise
 // reproducible), f64 Jacobi eigen-solve (solve.hpp) in place of Eigen's f32 SelfAdjointEigenSolver.
 #include "../../include/cilantro_hip/c_api.h"
+#include "device_prims.hpp"
 #include "ransac_sampling.hpp"
 #include "solve.hpp"
 #include "stateless.hpp"
@@ -280,22 +281,12 @@ __global__ __launch_bounds__(RS_THREADS) void k_chunk_counts(const float* __rest
   if (threadIdx.x == 0) counts[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 
-__global__ void k_scan_counts(uint32_t* counts, int nblocks, RansacState* st) {   // one lane; nblocks <= 1024
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    uint32_t run = 0;
-    for (int g = 0; g < nblocks; ++g) { const uint32_t c = counts[g]; counts[g] = run; run += c; }
-    st->n_inliers = run;
-  }
-}
-
 __global__ __launch_bounds__(RS_THREADS) void k_write_final(const float* __restrict__ xyz, uint32_t n, uint32_t chunk, float thr,
                                                             const RansacState* __restrict__ st, const uint32_t* __restrict__ offsets,
                                                             float* __restrict__ residuals, uint32_t* __restrict__ inliers) {
   const float n0 = st->best[0], n1 = st->best[1], n2 = st->best[2], off = st->best[3];
   const size_t lo = (size_t)blockIdx.x * chunk, hi = lo + chunk < n ? lo + chunk : n;
-  __shared__ uint32_t wave_cnt[RS_THREADS / 64];
   uint32_t run = offsets ? offsets[blockIdx.x] : 0;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (size_t b = lo; b < hi; b += RS_THREADS) {
     const size_t i = b + threadIdx.x;
     bool in = false;
@@ -305,14 +296,10 @@ __global__ __launch_bounds__(RS_THREADS) void k_write_final(const float* __restr
       in = r <= thr;
     }
     if (inliers) {   // block-uniform
-      const unsigned long long bal = __ballot(in);
-      if (lane == 0) wave_cnt[wave] = (uint32_t)__popcll(bal);
-      __syncthreads();
-      uint32_t before = 0, total = 0;
-      for (int w = 0; w < RS_THREADS / 64; ++w) { before += w < wave ? wave_cnt[w] : 0; total += wave_cnt[w]; }
-      if (in) inliers[run + before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = (uint32_t)i;
+      uint32_t total;
+      const uint32_t rank = block_rank<RS_THREADS>(in, &total);
+      if (in) inliers[run + rank] = (uint32_t)i;
       run += total;
-      __syncthreads();
     }
   }
 }
@@ -410,7 +397,7 @@ int cilhip_plane_ransac3f(int device, const float* xyz, size_t n, int mem, const
       const uint32_t chunk = (uint32_t)(((n + mb - 1) / mb + RS_THREADS - 1) / RS_THREADS * RS_THREADS);
       const int cb = (int)((n + chunk - 1) / chunk);
       hipLaunchKernelGGL(k_chunk_counts, dim3(cb), dim3(RS_THREADS), 0, b.s, b.xyz, (uint32_t)n, chunk, max_residual, b.st, b.chunk_counts);
-      hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(64), 0, b.s, b.chunk_counts, cb, b.st);
+      hipLaunchKernelGGL(k_scan_counts<uint32_t>, dim3(1), dim3(64), 0, b.s, b.chunk_counts, cb, &b.st->n_inliers);
       if (residuals_out) ST_CK("plane_ransac", b.pool.get(&b.residuals, n));
       if (inliers_out) ST_CK("plane_ransac", b.pool.get(&b.inliers, n));
       if (residuals_out || inliers_out)

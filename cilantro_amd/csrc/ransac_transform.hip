@@ -19,6 +19,7 @@
 // moments (products of f32 coordinates are exact in f64), f64 SVD -- Eigen's JacobiSVD<Matrix3f> round-off is "parity
 // unpinned" (Eigen is absent from the build container), as for every estimator of this engine.
 #include "../../include/cilantro_hip/c_api.h"
+#include "device_prims.hpp"
 #include "ransac_sampling.hpp"
 #include "solve.hpp"
 #include "stateless.hpp"
@@ -208,23 +209,13 @@ __global__ __launch_bounds__(TR_THREADS) void k_tchunk_counts(const float* __res
   if (threadIdx.x == 0) counts[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 
-__global__ void k_tscan_counts(uint32_t* counts, int nblocks, TState* st) {   // one lane; nblocks <= 1024
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    uint32_t run = 0;
-    for (int g = 0; g < nblocks; ++g) { const uint32_t c = counts[g]; counts[g] = run; run += c; }
-    st->n_inliers = run;
-  }
-}
-
 __global__ __launch_bounds__(TR_THREADS) void k_twrite_final(const float* __restrict__ dst, const float* __restrict__ src, uint32_t n, uint32_t chunk,
                                                              float thr_sq, const TState* __restrict__ st, const uint32_t* __restrict__ offsets,
                                                              float* __restrict__ residuals, uint32_t* __restrict__ inliers) {
   float M[12];
   for (int i = 0; i < 12; ++i) M[i] = st->best[i];
   const size_t lo = (size_t)blockIdx.x * chunk, hi = lo + chunk < n ? lo + chunk : n;
-  __shared__ uint32_t wave_cnt[TR_THREADS / 64];
   uint32_t run = offsets ? offsets[blockIdx.x] : 0;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (size_t b = lo; b < hi; b += TR_THREADS) {
     const size_t i = b + threadIdx.x;
     bool in = false;
@@ -236,14 +227,10 @@ __global__ __launch_bounds__(TR_THREADS) void k_twrite_final(const float* __rest
       in = st->have_model && r2 <= thr_sq;
     }
     if (inliers) {   // block-uniform
-      const unsigned long long bal = __ballot(in);
-      if (lane == 0) wave_cnt[wave] = (uint32_t)__popcll(bal);
-      __syncthreads();
-      uint32_t before = 0, total = 0;
-      for (int w = 0; w < TR_THREADS / 64; ++w) { before += w < wave ? wave_cnt[w] : 0; total += wave_cnt[w]; }
-      if (in) inliers[run + before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = (uint32_t)i;
+      uint32_t total;
+      const uint32_t rank = block_rank<TR_THREADS>(in, &total);
+      if (in) inliers[run + rank] = (uint32_t)i;
       run += total;
-      __syncthreads();
     }
   }
 }
@@ -360,7 +347,7 @@ int cilhip_transform_ransac3f(int device, const float* dst_xyz, const float* src
         hipLaunchKernelGGL(k_tmoments_finish, dim3(1), dim3(64), 0, b.s, b.dpartial, mb, b.st);
       }
       hipLaunchKernelGGL(k_tchunk_counts, dim3(cb), dim3(TR_THREADS), 0, b.s, b.dst, b.src, (uint32_t)n, chunk, thr_sq, b.st, b.chunk_counts);
-      hipLaunchKernelGGL(k_tscan_counts, dim3(1), dim3(64), 0, b.s, b.chunk_counts, cb, b.st);
+      hipLaunchKernelGGL(k_scan_counts<uint32_t>, dim3(1), dim3(64), 0, b.s, b.chunk_counts, cb, &b.st->n_inliers);
       if (residuals_out) ST_CK("transform_ransac", b.pool.get(&b.residuals, n));
       if (inliers_out) ST_CK("transform_ransac", b.pool.get(&b.inliers, n));
       if (residuals_out || inliers_out)

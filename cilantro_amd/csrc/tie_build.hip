@@ -19,11 +19,11 @@
 //
 // Node ids are breadth-first here (the host build numbers depth-first per worker): ids are labels -- tie_before() follows parent links
 // -- so the tables agree with the host's up to that relabelling; tests/test_gpu_tie_rule.py compares slot for slot and path for path.
+#include "device_prims.hpp"
 #include "internal.hpp"
 
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_reduce_by_key.hpp>
-#include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
 #include <algorithm>
@@ -597,8 +597,8 @@ hipError_t build_impl(const float* d_xyz, const float4* d_sorted, const float4* 
     const size_t run_cap = 4 * (size_t)act_cap + 4;
     {      // scratch of the scans / the reduction: the largest request
       size_t b1 = 0, b2 = 0, b3 = 0;
-      TB_TRY(rocprim::exclusive_scan(nullptr, b1, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), s));
-      TB_TRY(rocprim::exclusive_scan(nullptr, b2, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, 2 * (size_t)act_cap + 1, rocprim::plus<uint32_t>(), s));
+      TB_TRY(prim_exclusive_sum((uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)n + 1, s)(nullptr, b1));
+      TB_TRY(prim_exclusive_sum((uint32_t*)nullptr, (uint32_t*)nullptr, 2 * (size_t)act_cap + 1, s)(nullptr, b2));
       auto vals = rocprim::make_transform_iterator((const R*)nullptr, ToMM<DIM>());
       TB_TRY(rocprim::reduce_by_key(nullptr, b3, (uint32_t*)nullptr, vals, (size_t)n, (uint32_t*)nullptr, (M*)nullptr, (uint32_t*)nullptr, MMOp<DIM>(), rocprim::equal_to<uint32_t>(), s));
       tmp_bytes = std::max(b1, std::max(b2, b3));
@@ -650,19 +650,19 @@ hipError_t build_impl(const float* d_xyz, const float4* d_sorted, const float4* 
       hipLaunchKernelGGL((k_decide<DIM>), dim3(ga), dim3(TB), 0, s, cur, (const uint32_t*)cnt_cur);
       // planeSplit, first pass: recA -> recB
       hipLaunchKernelGGL((k_flags<DIM, 1>), dim3(gp), dim3(TB), 0, s, (const R*)recA, (const uint32_t*)node_of, (const A*)cur, n, flags);
-      { size_t b = tmp_bytes; TB_TRY(rocprim::exclusive_scan(tmp, b, flags, S, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), s)); }
+      TB_TRY(prim_exclusive_sum(flags, S, (size_t)n + 1, s)(tmp, tmp_bytes));
       hipLaunchKernelGGL((k_ranks<DIM, 1>), dim3(gp), dim3(TB), 0, s, (const uint32_t*)flags, (const uint32_t*)S, (const uint32_t*)node_of, cur, n, posF, posU);
       hipLaunchKernelGGL((k_scatter<DIM, 1>), dim3(gp), dim3(TB), 0, s, (const R*)recA, recB, (const uint32_t*)flags, (const uint32_t*)S, (const uint32_t*)node_of, (const A*)cur, n,
                          (const uint32_t*)posF, (const uint32_t*)posU);
       // second pass: recB -> recA
       hipLaunchKernelGGL((k_flags<DIM, 2>), dim3(gp), dim3(TB), 0, s, (const R*)recB, (const uint32_t*)node_of, (const A*)cur, n, flags);
-      { size_t b = tmp_bytes; TB_TRY(rocprim::exclusive_scan(tmp, b, flags, S, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), s)); }
+      TB_TRY(prim_exclusive_sum(flags, S, (size_t)n + 1, s)(tmp, tmp_bytes));
       hipLaunchKernelGGL((k_ranks<DIM, 2>), dim3(gp), dim3(TB), 0, s, (const uint32_t*)flags, (const uint32_t*)S, (const uint32_t*)node_of, cur, n, posF, posU);
       hipLaunchKernelGGL((k_scatter<DIM, 2>), dim3(gp), dim3(TB), 0, s, (const R*)recB, recA, (const uint32_t*)flags, (const uint32_t*)S, (const uint32_t*)node_of, (const A*)cur, n,
                          (const uint32_t*)posF, (const uint32_t*)posU);
       // children
       hipLaunchKernelGGL((k_children<DIM>), dim3(ga), dim3(TB), 0, s, cur, (const uint32_t*)cnt_cur, internal);
-      { size_t b = tmp_bytes; TB_TRY(rocprim::exclusive_scan(tmp, b, internal, iscan, 0u, 2 * (size_t)na + 1, rocprim::plus<uint32_t>(), s)); }
+      TB_TRY(prim_exclusive_sum(internal, iscan, 2 * (size_t)na + 1, s)(tmp, tmp_bytes));
       hipLaunchKernelGGL((k_child_keys<DIM>), dim3(gp), dim3(TB), 0, s, (const uint32_t*)node_of, (const A*)cur, n, keys);
       {
         auto vals = rocprim::make_transform_iterator((const R*)recA, ToMM<DIM>());

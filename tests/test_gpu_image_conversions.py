@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 F = np.float32
 HERE = os.path.dirname(os.path.abspath(__file__))
 E_SMALL = R.small_E()
-SHAPES = [(1, 1), (2, 5), (5, 2), (3, 3), (67, 5), (130, 3), (64, 64)]
+SHAPES = [(1, 1), (2, 5), (5, 2), (3, 3), (67, 5), (130, 3), (64, 64), (27, 19)]      # 27 x 19 = 513: two full blocks of 256 pixels and one pixel
 
 
 @pytest.fixture(scope="module")
