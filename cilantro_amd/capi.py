@@ -37,6 +37,8 @@ SYMBOLS = [
     "cilhip_nn_graph_matrix", "cilhip_sparse_from_csr", "cilhip_sparse_info", "cilhip_sparse_get", "cilhip_sparse_destroy",
     "cilhip_spectral_default_params", "cilhip_spectral_embedding", "cilhip_kmeans_nd",
     "cilhip_mds_default_params", "cilhip_mds_embedding", "cilhip_mds_apply", "cilhip_pca_fit", "cilhip_pca_project", "cilhip_pca_reconstruct",
+    "cilhip_convex_hull_create", "cilhip_convex_hull_get", "cilhip_convex_hull_destroy", "cilhip_polytope_signed_distances", "cilhip_polytopes_interior_mask",
+    "cilhip_polytopes_interior_indices",
 ]
 
 
@@ -159,6 +161,12 @@ class MdsParams(C.Structure):
 class MdsResult(C.Structure):
     _fields_ = [("dim", C.c_size_t), ("num_eigenvalues", C.c_size_t), ("n_converged", C.c_size_t), ("outer_iterations", C.c_size_t), ("block_products", C.c_size_t),
                 ("locked", C.c_size_t), ("max_residual", C.c_double), ("wall_ms", C.c_double)]
+
+
+class HullInfo(C.Structure):
+    _fields_ = [("dim", C.c_int), ("is_empty", C.c_int), ("n_vertices", C.c_size_t), ("n_facets", C.c_size_t), ("n_facet_indices", C.c_size_t), ("n_vertex_facets", C.c_size_t),
+                ("n_halfspaces", C.c_size_t), ("area", C.c_double), ("volume", C.c_double), ("interior_point", C.c_float * 3), ("rounds", C.c_size_t), ("n_nonfinite", C.c_size_t),
+                ("survivors_first_round", C.c_size_t), ("plane_tests", C.c_ulonglong), ("facet_tile", C.c_size_t), ("cull_ms", C.c_double)]
 
 
 _lib = None
@@ -303,6 +311,13 @@ def load():
     L.cilhip_pca_fit.argtypes = [C.c_int, f32p, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.c_int, f32p, f32p, f32p, f32p, C.POINTER(C.c_int)]
     L.cilhip_pca_project.argtypes = [C.c_int, f32p, C.c_size_t, C.c_size_t, C.c_int, f32p, f32p, C.c_size_t, f32p]
     L.cilhip_pca_reconstruct.argtypes = [C.c_int, f32p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, f32p, f32p, f32p]
+    L.cilhip_convex_hull_create.argtypes = [C.c_int, f32p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_double, C.POINTER(vp), C.POINTER(HullInfo)]
+    L.cilhip_convex_hull_get.argtypes = [vp, vp, f32p, f32p, vp, vp, vp, vp, vp, vp]
+    L.cilhip_convex_hull_destroy.argtypes = [vp]
+    L.cilhip_convex_hull_destroy.restype = None
+    L.cilhip_polytope_signed_distances.argtypes = [C.c_int, f32p, C.c_size_t, f32p, C.c_size_t, C.c_size_t, C.c_int, f32p]
+    L.cilhip_polytopes_interior_mask.argtypes = [C.c_int, f32p, vp, C.c_size_t, f32p, C.c_size_t, C.c_size_t, C.c_int, C.c_float, vp]
+    L.cilhip_polytopes_interior_indices.argtypes = [C.c_int, f32p, vp, C.c_size_t, f32p, C.c_size_t, C.c_size_t, C.c_int, C.c_float, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.cilhip_icp_sums_from_keys.argtypes = [vp, vp, f64p]
     L.cilhip_icp_order_keys.argtypes = [vp, vp, vp]
     L.cilhip_icp_sums_from_ordered_keys.argtypes = [vp, vp, vp, f64p]
@@ -350,7 +365,7 @@ def load():
     for name in SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
         if name not in ("cilhip_destroy", "cilhip_last_error", "cilhip_icp_default_params", "cilhip_option_info", "cilhip_cc_default_params", "cilhip_ms_default_params", "cilhip_mcd_params_default", "cilhip_depth_default_converter", "cilhip_fusion_default_params", "cilhip_warp_default_params", "cilhip_warp_field_destroy", "cilhip_sparse_destroy",
-                        "cilhip_spectral_default_params", "cilhip_mds_default_params"):
+                        "cilhip_spectral_default_params", "cilhip_mds_default_params", "cilhip_convex_hull_destroy"):
             fn.restype = C.c_int
     _lib = L
     return L

@@ -1327,6 +1327,70 @@ int cilhip_pca_fit(int device, const float* x, size_t n, size_t dim, const uint3
 int cilhip_pca_project(int device, const float* x, size_t m, size_t dim, int mem, const float* mean, const float* eigenvectors, size_t target_dim, float* out);
 int cilhip_pca_reconstruct(int device, const float* y, size_t m, size_t source_dim, size_t dim, int mem, const float* mean, const float* eigenvectors, float* out);
 
+/* spatial/convex_polytope.hpp, convex_hull_utilities.hpp:570-740 (convexHullFromPoints) for float in 2 and 3 dimensions.
+ * Qhull is not ported: the device finds the extreme points among n (filter and refine), a plain-C++ builder orders them (csrc/hull_host.hpp).
+ * points: n rows of `dim` floats where `mem` says.
+ *   H1 arithmetic  every plane is f64 on the f32 coordinates: nrm = normalise((b - a) x (c - a)), off = -nrm . a (2-D: the edge's outward
+ *                  normal); d(p) = nrm . p + off, positive outside.
+ *   H2 band        tol = max(merge_tol, 2^-44 M), M the largest finite |coordinate|.  Outside iff d > tol.  Points within the band of the
+ *                  boundary (face interiors, edges, duplicates of a vertex) are not vertices; of exact duplicates the lowest index is.
+ *   H3 input       non-finite rows are ignored and counted.  Fewer than dim + 1 finite points, or no simplex of height > tol
+ *                  (convex_hull_utilities.hpp:582-628): the reference's empty polytope -- is_empty, no vertices, no facets, the two
+ *                  placeholder halfspaces (1, 0, .., 1) and (-1, 0, .., 1), area = volume = 0, a NaN interior point -- and CILHIP_OK.
+ *   H4 order       vertex_point_indices ascend; vertices are those rows, copied.  A facet lists vertex-list indices counter-clockwise seen
+ *                  from outside, its smallest first (2-D: the edge (v0, v1) with the interior on its left, as it is); facets are sorted
+ *                  lexicographically.  Triangles whose opposite vertices lie within tol of each other's plane merge into their boundary
+ *                  polygon; simplicial_facets = 1 lists each polygon as the fan (v0, vi, vi+1) from its smallest vertex.  Halfspace k is
+ *                  (nrm, off) of facet k rounded to f32 (a polygon: of its fan triangle with the smallest sorted index triple), so
+ *                  nrm . x + off <= 0 inside (convex_polytope.hpp:109-115).  facet_neighbors[j] of facet k: the facet across the edge
+ *                  (v_j, v_j+1 mod m) (2-D: the other edge at v_j).  vertex_facets ascend.  interior_point: the f32 mean of the vertices,
+ *                  summed in order (:238).  area / volume (f64, Qhull's meaning: perimeter / enclosed area in 2-D): the facets' areas, the
+ *                  signed simplex volumes from the interior point, both summed in facet order.
+ *   H5 repeatable  every array and `info` agree bit for bit between two runs.
+ * Refused with CILHIP_ERR_INVALID before a device is opened (cilhip_last_error(NULL) names the rule): a NULL points / out / info, dim outside
+ * {2, 3}, n >= 2^32 - 16, an unknown mem, a negative or non-finite merge_tol.  n == 0: the empty polytope, no device needed.
+ * Not built (CILHIP_ERR_UNSUPPORTED where a call could ask): the halfspace constructor's vertex enumeration, intersectionWith,
+ * SpaceRegion::complement / relativeComplement / getVolume (they need the QP of convex_hull_utilities.hpp:12-193 and a dual hull), double,
+ * dimension above 3, hulls of lower-dimensional input beyond FlatConvexHull3f. */
+typedef struct cilhip_hull cilhip_hull;
+typedef struct cilhip_hull_info {
+  int dim, is_empty;
+  size_t n_vertices, n_facets, n_facet_indices, n_vertex_facets;
+  size_t n_halfspaces;                 /* n_facets, or the 2 placeholders of the empty polytope */
+  double area, volume;
+  float interior_point[3];
+  size_t rounds;                       /* cull launches */
+  size_t n_nonfinite;
+  size_t survivors_first_round;        /* points still outside the seed hull after the first cull */
+  unsigned long long plane_tests;      /* sum over the rounds of survivors x facets */
+  size_t facet_tile;                   /* facets per LDS tile of the cull kernel */
+  double cull_ms;                      /* device time of the cull kernels by events; 0 unless CILHIP_HULL_TIMING=1 is set (see below) */
+} cilhip_hull_info;
+int cilhip_convex_hull_create(int device, const float* points, size_t n, size_t dim, int mem, int simplicial_facets, double merge_tol, cilhip_hull** out,
+                              cilhip_hull_info* info);
+/* HOST arrays, any NULL one is skipped: vertex_point_indices n_vertices; vertices n_vertices x dim; halfspaces n_halfspaces columns of dim + 1
+ * (column k contiguous); facet_offsets n_facets + 1; facet_indices and facet_neighbors n_facet_indices; vertex_facet_offsets n_vertices + 1;
+ * vertex_facets n_vertex_facets; survivors_per_round `rounds` entries. */
+int cilhip_convex_hull_get(const cilhip_hull* hull, uint32_t* vertex_point_indices, float* vertices, float* halfspaces, uint32_t* facet_offsets, uint32_t* facet_indices,
+                           uint32_t* facet_neighbors, uint32_t* vertex_facet_offsets, uint32_t* vertex_facets, uint64_t* survivors_per_round);
+void cilhip_convex_hull_destroy(cilhip_hull* hull);
+/* CILHIP_HULL_TIMING=1 in the environment makes create() time its cull kernels with device events (info.cull_ms; 0 otherwise). */
+
+/* Containment (convex_polytope.hpp:109-141, space_region.hpp:208-234).  halfspaces: HOST, the polytopes' columns of dim + 1 floats one after
+ * the other; poly_offsets: HOST, n_polytopes + 1 column offsets ascending from 0.  points (n rows of dim floats) and the output where `mem` says.
+ *   Q1  v = ((h0 x + h1 y) + h2 z) + h3 in f32, left to right, no contraction (2-D: (h0 x + h1 y) + h2)
+ *   Q2  inside a polytope iff no column has v > -offset (a point leaves at its first failing column); inside the region iff inside any
+ *       polytope.  No columns: contains everything.  The empty polytope's placeholders contain nothing.
+ * signed_distances: out[k * n + i] = v of column k at point i.  interior_mask: n bytes, 0 / 1.  interior_indices: ascending indices; *n_out
+ * (HOST) always gets the count; capacity == 0 only counts; a capacity below the count is CILHIP_ERR_INVALID and writes nothing
+ * (the rules of cilhip_grid_downsample3f).  n == 0 needs no device.  Refused: NULL arrays, dim outside {2, 3}, n >= 2^32 - 16, an unknown
+ * mem, poly_offsets that do not ascend from 0, a NaN offset. */
+int cilhip_polytope_signed_distances(int device, const float* halfspaces, size_t n_facets, const float* points, size_t n, size_t dim, int mem, float* out);
+int cilhip_polytopes_interior_mask(int device, const float* halfspaces, const uint32_t* poly_offsets, size_t n_polytopes, const float* points, size_t n, size_t dim, int mem,
+                                   float offset, uint8_t* mask_out);
+int cilhip_polytopes_interior_indices(int device, const float* halfspaces, const uint32_t* poly_offsets, size_t n_polytopes, const float* points, size_t n, size_t dim, int mem,
+                                      float offset, uint32_t* indices_out, size_t capacity, size_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif
