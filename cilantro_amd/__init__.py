@@ -1,0 +1,13 @@
+"""cilantro_amd: Python mirrors of the cilantro classes over libcilantro_hip.so.  Each family lives in its own module; the names below are
+also reachable from the package itself (resolved on first use, so importing the package loads nothing)."""
+
+_KD_TREE = ("KDTree", "KDTree2f", "KDTreeXf", "KNNNeighborhoodSpecification", "KNNInRadiusNeighborhoodSpecification")
+__all__ = list(_KD_TREE)
+
+
+def __getattr__(name):
+    if name in _KD_TREE:
+        from . import kd_tree
+
+        return getattr(kd_tree, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

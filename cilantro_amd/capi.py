@@ -39,6 +39,7 @@ SYMBOLS = [
     "cilhip_mds_default_params", "cilhip_mds_embedding", "cilhip_mds_apply", "cilhip_pca_fit", "cilhip_pca_project", "cilhip_pca_reconstruct",
     "cilhip_convex_hull_create", "cilhip_convex_hull_get", "cilhip_convex_hull_destroy", "cilhip_polytope_signed_distances", "cilhip_polytopes_interior_mask",
     "cilhip_polytopes_interior_indices",
+    "cilhip_knn_nd", "cilhip_radius_search_nd",
 ]
 
 
@@ -318,6 +319,8 @@ def load():
     L.cilhip_polytope_signed_distances.argtypes = [C.c_int, f32p, C.c_size_t, f32p, C.c_size_t, C.c_size_t, C.c_int, f32p]
     L.cilhip_polytopes_interior_mask.argtypes = [C.c_int, f32p, vp, C.c_size_t, f32p, C.c_size_t, C.c_size_t, C.c_int, C.c_float, vp]
     L.cilhip_polytopes_interior_indices.argtypes = [C.c_int, f32p, vp, C.c_size_t, f32p, C.c_size_t, C.c_size_t, C.c_int, C.c_float, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.cilhip_knn_nd.argtypes = [C.c_int, f32p, C.c_size_t, f32p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_float, vp, vp, vp]
+    L.cilhip_radius_search_nd.argtypes = [C.c_int, f32p, C.c_size_t, f32p, C.c_size_t, C.c_size_t, C.c_int, C.c_float, vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.cilhip_icp_sums_from_keys.argtypes = [vp, vp, f64p]
     L.cilhip_icp_order_keys.argtypes = [vp, vp, vp]
     L.cilhip_icp_sums_from_ordered_keys.argtypes = [vp, vp, vp, f64p]

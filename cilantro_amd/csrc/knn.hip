@@ -22,10 +22,10 @@
 #include "../../include/cilantro_hip/c_api.h"
 #include "device_prims.hpp"
 #include "internal.hpp"
+#include "knn_lists.hpp"
 #include "stateless.hpp"
 
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_segmented_radix_sort.hpp>
 
 #include <cmath>
 #include <cstring>
@@ -36,8 +36,7 @@ int g_knn_tie_rule = 2;      // cilhip_knn_set_tie_rule (k-NN lists; kmeans.hip:
 
 namespace {
 
-constexpr int KNN_THREADS = 256;
-constexpr int KNN_MAX_K = 32;
+// (KNN_THREADS, KNN_MAX_K and the per-lane list KList: knn_lists.hpp)
 constexpr float KNN_SHRINK = 0.99999905f;   // 1 - 2^-20, as in the 1-NN path
 
 struct KnnArgs {
@@ -67,28 +66,6 @@ __device__ __forceinline__ float d2_pinned(float qx, float qy, float qz, float p
   return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
 }
 __device__ __forceinline__ float gap(float q, float lo, float hi, float margin) { return fmaxf(fmaxf(lo - q, q - hi) - margin, 0.0f); }
-
-// per-lane sorted list of the k best keys, column `tid` of lists[k][KNN_THREADS]
-struct KList {
-  unsigned long long* col;   // &lists[threadIdx.x]
-  uint32_t k, cnt;
-  unsigned long long worst;  // a candidate enters iff key < worst
-  unsigned long long none_key;
-  uint32_t tie_bits;         // bits of the distance at which a candidate last fell off (or stayed out of) a FULL list while an entry at exactly that
-                             // distance stayed in: the k-th place is tied iff this is the final k-th distance (the k-th distance only shrinks)
-  __device__ __forceinline__ float worst_d2() const { return __uint_as_float((uint32_t)(worst >> 32)); }
-  __device__ __forceinline__ void insert(unsigned long long key) {
-    if (key >= worst) { if (cnt == k && (uint32_t)(key >> 32) == (uint32_t)(worst >> 32)) tie_bits = (uint32_t)(key >> 32); return; }
-    const bool full = cnt == k;
-    const unsigned long long out = full ? col[(size_t)(k - 1) * KNN_THREADS] : 0ull;
-    uint32_t j = cnt < k ? cnt : k - 1;
-    while (j > 0 && col[(size_t)(j - 1) * KNN_THREADS] > key) { col[(size_t)j * KNN_THREADS] = col[(size_t)(j - 1) * KNN_THREADS]; --j; }
-    col[(size_t)j * KNN_THREADS] = key;
-    if (cnt < k) ++cnt;
-    worst = cnt < k ? none_key : col[(size_t)(k - 1) * KNN_THREADS];
-    if (full && (uint32_t)(out >> 32) == (uint32_t)(worst >> 32)) tie_bits = (uint32_t)(out >> 32);
-  }
-};
 
 __device__ __forceinline__ void scan_run(const float4* __restrict__ pts, uint32_t beg, uint32_t end, float qx, float qy, float qz, KList& L, bool by_pos) {
   if (beg >= end) return;
@@ -529,17 +506,6 @@ __global__ __launch_bounds__(KNN_THREADS) void k_radius_lists(GridDev g, const f
   if (!FILL) counts_or_offsets[orig] = cnt;
 }
 
-__global__ void k_unpack_radius(const unsigned long long* __restrict__ keys, size_t total, uint32_t* __restrict__ idx, float* __restrict__ d2) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const unsigned long long k = keys[i];
-    idx[i] = (uint32_t)k;
-    if (d2) d2[i] = __uint_as_float((uint32_t)(k >> 32));
-  }
-}
-__global__ void k_offsets32(const unsigned long long* __restrict__ off64, uint32_t n, uint32_t* __restrict__ off32) {
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) off32[i] = (uint32_t)off64[i];
-}
-
 int radius_impl(int device, const float* ref_xyz, size_t n_ref, const float* query_xyz, size_t n_query, int mem, float radius_sq,
                 uint64_t* offsets_out, uint32_t* idx_out, float* d2_out, size_t capacity, size_t* total_out) {
   if ((!ref_xyz && n_ref) || !offsets_out || n_ref > 0xFFFFFFF0ull || n_query > 0xFFFFFFF0ull || !std::isfinite(radius_sq)) return st_fail(CILHIP_ERR_INVALID, "radius_search", kBadArguments);
@@ -549,12 +515,11 @@ int radius_impl(int device, const float* ref_xyz, size_t n_ref, const float* que
   if (self) n_query = n_ref;
   if (total_out) *total_out = 0;
   DevPool pool;
-  float *d_ref = nullptr, *d_q = nullptr, *d_d2 = nullptr;
+  float *d_ref = nullptr, *d_q = nullptr;
   float4* d_qs = nullptr;
   uint2* d_tiles = nullptr;
   float4* d_tc = nullptr;
-  unsigned long long *d_cnt = nullptr, *d_keys = nullptr, *d_keys2 = nullptr;
-  uint32_t *d_off32 = nullptr, *d_idx = nullptr;
+  unsigned long long *d_cnt = nullptr, *d_keys = nullptr;
   GridBuildResult gr{};
   SortWorkspace sort_ws;
   StreamGuard s;      // (declared last: drained and destroyed before anything is freed)
@@ -601,22 +566,8 @@ int radius_impl(int device, const float* ref_xyz, size_t n_ref, const float* que
     if (idx_out && capacity >= total && total > 0) {
       if (total > 0xFFFFFFF0ull) return st_fail(CILHIP_ERR_UNSUPPORTED, "radius_search", "the lists hold more than 2^32 - 16 entries together");   // one segmented sort call takes 32-bit sizes
       ST_CK("radius_search", pool.get(&d_keys, total));
-      ST_CK("radius_search", pool.get(&d_keys2, total));
       hipLaunchKernelGGL((k_radius_lists<true>), dim3(nblk), dim3(KNN_THREADS), 0, s, gr.grid, (const float4*)d_qs, (uint32_t)n_query, radius_sq, d_cnt, d_keys);
-      ST_CK("radius_search", pool.get(&d_off32, n_query + 1));
-      hipLaunchKernelGGL(k_offsets32, dim3(256), dim3(256), 0, s, (const unsigned long long*)d_cnt, (uint32_t)(n_query + 1), d_off32);
-      {
-        ST_CK("radius_search", prim_run(pool, [&](void* tmp, size_t& bytes) {
-          return rocprim::segmented_radix_sort_keys(tmp, bytes, d_keys, d_keys2, (unsigned int)total, (unsigned int)n_query, d_off32, d_off32 + 1, 0, 64, s);
-        }));
-      }
-      ST_CK("radius_search", pool.get(&d_idx, total));
-      if (d2_out) ST_CK("radius_search", pool.get(&d_d2, total));
-      hipLaunchKernelGGL(k_unpack_radius, dim3(2048), dim3(256), 0, s, (const unsigned long long*)d_keys2, total, d_idx, d_d2);
-      ST_CK("radius_search", hipGetLastError());
-      ST_CK("radius_search", hipMemcpyAsync(idx_out, d_idx, total * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-      if (d2_out) ST_CK("radius_search", hipMemcpyAsync(d2_out, d_d2, total * sizeof(float), hipMemcpyDeviceToHost, s));
-      ST_CK("radius_search", hipStreamSynchronize(s));
+      if (const int rc = radius_sort_unpack("radius_search", pool, s, d_cnt, n_query, total, d_keys, idx_out, d2_out)) return rc;
     }
   }
   return CILHIP_OK;

@@ -1391,6 +1391,36 @@ int cilhip_polytopes_interior_mask(int device, const float* halfspaces, const ui
 int cilhip_polytopes_interior_indices(int device, const float* halfspaces, const uint32_t* poly_offsets, size_t n_polytopes, const float* points, size_t n, size_t dim, int mem,
                                       float offset, uint32_t* indices_out, size_t capacity, size_t* n_out);
 
+/* ---- exact neighbour search in 1 to 16 dimensions ------------------------------------------------------------------------------------- */
+/* KDTree<float, EigenDim, L2> for EigenDim != 3 (core/kd_tree.hpp:144-406: KDTree2f, KDTreeXf): kNNSearch, kNNInRadiusSearch and
+ * radiusSearch over n x dim float points, exhaustively (csrc/knn_nd.hip).  DESIGN.md section 21 is the long form.
+ * ref / query_or_null: point-major n x dim floats (the layout of cilhip_kmeans_nd), where `mem` says; query_or_null == NULL: the reference
+ * points are the queries (n_query is ignored; every finite point finds itself first, at distance 0).  The outputs are HOST arrays with the
+ * shapes, padding (0xFFFFFFFF / +inf), NULL rules (d2_out, counts_out, total_out_or_null may be NULL) and the two-call capacity protocol of
+ * cilhip_knn3f and cilhip_radius_search3f.
+ *   N1 distance    nanoflann's L2_Adaptor::evalMetric (nanoflann.hpp:570-604) in f32, every operation rounded, nothing contracted: with
+ *                  s_i = (q_i - p_i)^2, r = 0; for each full group of four coordinates r = r + (((s_d + s_d+1) + s_d+2) + s_d+3); for the
+ *                  0 to 3 coordinates left over, one at a time, r = r + s_d.  dim = 3: the d2 of cilhip_knn3f bit for bit; dim = 6:
+ *                  (g0 + s4) + s5, never g0 + (s4 + s5).
+ *   N2 acceptance  a candidate enters iff d2 < max_sq_dist (strict; INFINITY: plain k-NN) and d2 is finite: a reference row with a
+ *                  non-finite coordinate is in no list, nor is a candidate whose finite coordinates overflow d2 to +inf; a non-finite
+ *                  query gets count 0 (an empty list).
+ *   N3 order       lists ascend by (d2, index); among exactly equal distances the lowest reference index wins, inside a list and at its
+ *                  k-th place (cilhip_knn3f under tie rule 0).  cilhip_knn_set_tie_rule does not apply.  A stated deviation: the
+ *                  reference's KDTreeXf names whichever equal candidate its traversal meets first.
+ *   N4 sizes       1 <= dim <= 16, 1 <= k <= 32 (k > n_ref: padded rows); n_ref, n_query < 2^32 - 16; the radius lists hold at most
+ *                  2^32 - 16 entries together (else CILHIP_ERR_UNSUPPORTED, as in 3-D).  CILHIP_ERR_UNSUPPORTED: dim > 16, k > 32.
+ *                  CILHIP_ERR_INVALID: ref NULL with n_ref > 0, idx_out NULL (k-NN), offsets_out NULL (radius), dim == 0, k == 0, a NaN
+ *                  max_sq_dist, a radius_sq that is not finite, an unknown mem, a size at or above 2^32 - 16.  All of these are refused
+ *                  before a device is opened and leave the outputs untouched; cilhip_last_error(NULL) names the rule.  n_ref == 0,
+ *                  n_query == 0 or a bound <= 0: empty lists / count 0, no device needed.
+ *   N5 radius      every reference point with d2 < radius_sq, ascending by (d2, index); radius_sq <= 0: empty lists.
+ *   N6 repeatable  two runs agree bit for bit. */
+int cilhip_knn_nd(int device, const float* ref, size_t n_ref, const float* query_or_null, size_t n_query, size_t dim, int mem, size_t k, float max_sq_dist,
+                  uint32_t* idx_out, float* d2_out, uint32_t* counts_out);
+int cilhip_radius_search_nd(int device, const float* ref, size_t n_ref, const float* query_or_null, size_t n_query, size_t dim, int mem, float radius_sq,
+                            uint64_t* offsets_out, uint32_t* idx_out, float* d2_out, size_t capacity, size_t* total_out_or_null);
+
 #ifdef __cplusplus
 }
 #endif

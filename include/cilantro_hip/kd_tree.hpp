@@ -1,0 +1,126 @@
+// cilantro_hip/kd_tree.hpp -- C++ host-side mirrors of cilantro's dimension-generic KDTree (core/kd_tree.hpp:144-406), header-only on top
+// of the C ABI (c_api.h: cilhip_knn_nd, cilhip_radius_search_nd):
+//
+//   KDTreeXf     KDTree<float, Eigen::Dynamic, KDTreeDistanceAdaptors::L2>     any dimension from 1 to 16, taken from the view
+//   KDTree2f     KDTree<float, 2, KDTreeDistanceAdaptors::L2>
+//
+// kNNSearch, kNNInRadiusSearch, radiusSearch, nearestNeighborSearch and search(queries, specification): same names and argument meaning as
+// the reference -- radii are SQUARED distances.  A point set is a non-owning view of a dim x n column-major float matrix (the reference's
+// ConstVectorSetMatrixMap: one point after the other).  The search is exhaustive and exact; lists ascend by (distance, index), so among
+// exactly equal distances the lowest index is named (the reference: whichever its traversal meets first).  KDTree3f
+// (normal_estimation.hpp) keeps the 3-D grid path.  No CPU fallback: a failing C-ABI call throws.
+#pragma once
+
+#include <cstdint>
+#include <limits>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "c_api.h"
+#include "clustering.hpp"
+#include "icp.hpp"
+
+namespace cilantro_hip {
+
+// core/data_containers.hpp:73-122: non-owning view of a dim x n column-major float matrix
+struct ConstDataView {
+  const float* data_ = nullptr;
+  size_t rows_ = 0, cols_ = 0;
+  ConstDataView() = default;
+  ConstDataView(const float* d, size_t dim, size_t n) : data_(d), rows_(dim), cols_(n) {}
+  ConstDataView(const std::vector<float>& v, size_t dim) : data_(v.data()), rows_(dim), cols_(dim ? v.size() / dim : 0) {}
+  const float* data() const { return data_; }
+  size_t rows() const { return rows_; }
+  size_t cols() const { return cols_; }
+};
+
+// core/nearest_neighbors.hpp:49-77
+struct KNNNeighborhoodSpecification {
+  size_t maxNumberOfNeighbors;
+  explicit KNNNeighborhoodSpecification(size_t k = 0) : maxNumberOfNeighbors(k) {}
+};
+template <typename ScalarT = float>
+struct KNNInRadiusNeighborhoodSpecification {
+  size_t maxNumberOfNeighbors;
+  ScalarT radius;
+  KNNInRadiusNeighborhoodSpecification(size_t k = 0, ScalarT radius_sq = (ScalarT)0) : maxNumberOfNeighbors(k), radius(radius_sq) {}
+};
+
+class KDTreeXf {
+public:
+  explicit KDTreeXf(const ConstDataView& points, int device = 0) : points_(points), device_(device) {}
+
+  NeighborhoodSet kNNSearch(const ConstDataView& queries, size_t k) const { return knn(queries, k, std::numeric_limits<float>::infinity()); }
+  NeighborhoodSet kNNInRadiusSearch(const ConstDataView& queries, size_t k, float radius) const { return knn(queries, k, radius); }
+  // one query point (dim floats)
+  Neighborhood kNNInRadiusSearch(const float* query, size_t k, float radius) const { return knn(ConstDataView(query, points_.rows(), 1), k, radius)[0]; }
+  Neighborhood kNNSearch(const float* query, size_t k) const { return kNNInRadiusSearch(query, k, std::numeric_limits<float>::infinity()); }
+  // the nearest point of every query; a query without one (a non-finite query, an empty tree) is left out of the set's list
+  NeighborhoodSet nearestNeighborSearch(const ConstDataView& queries) const { return kNNSearch(queries, 1); }
+
+  // every neighbour with squared distance < radius, ascending by (distance, index)
+  NeighborhoodSet radiusSearch(const ConstDataView& queries, float radius) const {
+    check(queries);
+    const size_t nq = queries.cols();
+    std::vector<uint64_t> off(nq + 1, 0);
+    size_t total = 0;
+    int rc = cilhip_radius_search_nd(device_, points_.data(), points_.cols(), queries.data(), nq, points_.rows(), CILHIP_MEM_HOST, radius, off.data(), nullptr, nullptr, 0, &total);
+    if (rc != CILHIP_OK) fail("cilhip_radius_search_nd", rc);
+    std::vector<uint32_t> idx(total ? total : 1);
+    std::vector<float> d2(total ? total : 1);
+    if (total) {
+      rc = cilhip_radius_search_nd(device_, points_.data(), points_.cols(), queries.data(), nq, points_.rows(), CILHIP_MEM_HOST, radius, off.data(), idx.data(), d2.data(), total,
+                                   &total);
+      if (rc != CILHIP_OK) fail("cilhip_radius_search_nd", rc);
+    }
+    NeighborhoodSet out(nq);
+    for (size_t i = 0; i < nq; ++i) {
+      out[i].resize((size_t)(off[i + 1] - off[i]));
+      for (size_t j = 0; j < out[i].size(); ++j) out[i][j] = Neighbor{(size_t)idx[off[i] + j], d2[off[i] + j]};
+    }
+    return out;
+  }
+
+  // kd_tree.hpp:320-388: dispatch on the neighbourhood specification
+  NeighborhoodSet search(const ConstDataView& queries, const KNNNeighborhoodSpecification& nh) const { return kNNSearch(queries, nh.maxNumberOfNeighbors); }
+  NeighborhoodSet search(const ConstDataView& queries, const KNNInRadiusNeighborhoodSpecification<float>& nh) const {
+    return kNNInRadiusSearch(queries, nh.maxNumberOfNeighbors, nh.radius);
+  }
+  NeighborhoodSet search(const ConstDataView& queries, const RadiusNeighborhoodSpecification<float>& nh) const { return radiusSearch(queries, nh.radius); }
+
+  const ConstDataView& getPointsMatrixMap() const { return points_; }
+
+private:
+  static void fail(const char* what, int rc) { throw std::runtime_error(std::string(what) + " failed (rc " + std::to_string(rc) + "): " + cilhip_last_error(nullptr)); }
+  void check(const ConstDataView& queries) const {
+    if (queries.rows() != points_.rows()) throw std::invalid_argument("KDTree: the queries' dimension is not the tree's");
+  }
+  NeighborhoodSet knn(const ConstDataView& queries, size_t k, float radius) const {
+    check(queries);
+    const size_t nq = queries.cols();
+    std::vector<uint32_t> idx(nq * k ? nq * k : 1), cnt(nq ? nq : 1);
+    std::vector<float> d2(nq * k ? nq * k : 1);
+    const int rc = cilhip_knn_nd(device_, points_.data(), points_.cols(), queries.data(), nq, points_.rows(), CILHIP_MEM_HOST, k, radius, idx.data(), d2.data(), cnt.data());
+    if (rc != CILHIP_OK) fail("cilhip_knn_nd", rc);
+    NeighborhoodSet out(nq);
+    for (size_t i = 0; i < nq; ++i) {
+      out[i].resize(cnt[i]);
+      for (size_t j = 0; j < cnt[i]; ++j) out[i][j] = Neighbor{(size_t)idx[i * k + j], d2[i * k + j]};
+    }
+    return out;
+  }
+  ConstDataView points_;
+  int device_;
+};
+
+class KDTree2f : public KDTreeXf {
+public:
+  explicit KDTree2f(const ConstDataView& points, int device = 0) : KDTreeXf(points, device) {
+    if (points.rows() != 2) throw std::invalid_argument("KDTree2f: the points are not 2-D");
+  }
+  // n points as x0 y0 x1 y1 ...
+  KDTree2f(const float* xy, size_t n, int device = 0) : KDTreeXf(ConstDataView(xy, 2, n), device) {}
+};
+
+}  // namespace cilantro_hip
