@@ -600,7 +600,8 @@ int kmeans_nd_impl(const float* x, size_t n, int D, int mem, float* centroids, s
       ST_CK(F, hipGetLastError());
       ST_CK(F, hipMemcpyAsync(&best, d_best, sizeof(best), hipMemcpyDeviceToHost, s));
       ST_CK(F, hipStreamSynchronize(s));
-      if (best == 0) continue;      // (no member anywhere: n < k)
+      if (best == 0) continue;      // (never taken, n < k included: the counts add up to n >= 1, so the donor -- the largest -- has a member,
+                                    // and a member's key ends in 0xFFFFFFFF - i >= 16; kept so that an empty key can never become the index mi)
       const uint32_t mi = 0xFFFFFFFFu - (uint32_t)(best & 0xFFFFFFFFull);
       float p[ND_MAX_DIM];
       hipLaunchKernelGGL(k_nd_set_label, dim3(1), dim3(64), 0, s, d_lab, mi, (uint32_t)i);

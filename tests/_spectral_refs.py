@@ -228,14 +228,29 @@ def nd_sums(x, lab, k):
         xs, ls = x[lo:lo + rows].astype(F64), lab[lo:lo + rows]
         for c in range(k):
             m = xs[ls == c]
-            part = np.cumsum(m, axis=0)[-1] if len(m) else np.zeros(D)
+            with np.errstate(invalid="ignore"):      # (+inf and -inf members: NaN, as IEEE has it)
+                part = np.cumsum(m, axis=0)[-1] if len(m) else np.zeros(D)
             sums[c] = sums[c] + part
             counts[c] = counts[c] + len(m)
     return sums, counts      # (a block past the end adds an exact zero)
 
 
-def kmeans_nd(x, centroids, max_iter=100, tol=FLT_EPS):
-    """KMeans<float, Dynamic>::cluster_ (kmeans.hpp:67-194), brute-force branch -> (centroids, labels, iterations)"""
+def nd_farthest(dist):
+    """the repair's choice among the donor's members, the entry's rule (k_nd_farthest ranks by the distance's bit pattern, then by
+    0xFFFFFFFF - index): a NaN distance above +inf above every number, among equal ranks and values the lowest position.  (A distance
+    is a sum of squares: never negative.  The reference's `dist > max_dist` from -1, kmeans.hpp:150-167, never accepts a NaN and
+    leaves max_dist_ind uninitialised when every distance is one.) -> position in dist"""
+    dist = np.asarray(dist, F32)
+    rank = np.where(np.isnan(dist), 2, np.where(dist == np.inf, 1, 0))
+    top = np.flatnonzero(rank == rank.max())
+    if rank.max() == 0:
+        top = top[dist[top] == dist[top].max()]
+    return int(top[0])
+
+
+def kmeans_nd(x, centroids, max_iter=100, tol=FLT_EPS, trace=None):
+    """KMeans<float, Dynamic>::cluster_ (kmeans.hpp:67-194), brute-force branch -> (centroids, labels, iterations).  trace: a list that
+    receives one record per repair, (iteration, empty cluster, donor cluster, moved point)"""
     x = np.ascontiguousarray(x, F32)
     cent = np.ascontiguousarray(centroids, F32).copy()
     k, D = cent.shape
@@ -250,26 +265,30 @@ def kmeans_nd(x, centroids, max_iter=100, tol=FLT_EPS):
             break
         old = cent.copy()
         sums, counts = nd_sums(x, lab, k)
-        for i in range(k):      # :134-176
-            if counts[i] != 0:
-                continue
-            mx = int(np.argmax(counts))      # (the first largest)
-            oc = (sums[mx] / counts[mx]).astype(F32)
-            members = np.flatnonzero(lab == mx)
-            dist = nd_dist(x[members], oc)
-            mi = members[int(np.argmax(dist))]      # (the first farthest: the lowest index)
-            lab[mi] = i
-            sums[mx] -= x[mi].astype(F64)
-            counts[mx] -= 1
-            counts[i] += 1      # (:171-175: the point is not added to cluster i's sum)
-        with np.errstate(invalid="ignore", divide="ignore"):
+        with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+            for i in range(k):      # :134-176
+                if counts[i] != 0:
+                    continue
+                mx = int(np.argmax(counts))      # (the first largest)
+                oc = (sums[mx] / counts[mx]).astype(F32)
+                members = np.flatnonzero(lab == mx)
+                mi = members[nd_farthest(nd_dist(x[members], oc))]
+                if trace is not None:
+                    trace.append((it, i, mx, int(mi)))
+                lab[mi] = i
+                sums[mx] -= x[mi].astype(F64)
+                counts[mx] -= 1
+                counts[i] += 1      # (:171-175: the point is not added to cluster i's sum)
             cent = (sums / counts[:, None]).astype(F32)
-        it += 1
-        if tol > 0:
-            d = (cent - old).astype(F32)
-            sq = d[:, 0] * d[:, 0]
-            for t in range(1, D):
-                sq = (sq + d[:, t] * d[:, t]).astype(F32)
-            if sq.max() < tol_sq:
-                break
+            it += 1
+            if tol > 0:
+                d = (cent - old).astype(F32)
+                sq = d[:, 0] * d[:, 0]
+                for t in range(1, D):
+                    sq = (sq + d[:, t] * d[:, t]).astype(F32)
+                # cilhip_kmeans3f's rule: the largest squared move is taken with `sq > max` from 0, so a NaN move (a centroid that is NaN,
+                # or infinite twice running) does not count.  (Eigen's maxCoeff, :187, leaves what a NaN does to the implementation.)
+                moved = sq[~np.isnan(sq)]
+                if (moved.max() if len(moved) else F32(0)) < tol_sq:
+                    break
     return cent, lab, it

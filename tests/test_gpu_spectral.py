@@ -314,12 +314,12 @@ def _kmeans_case(x, start, max_iter=100, tol=R.FLT_EPS):
     print("k-means", x.shape, "iterations", km.getNumberOfPerformedIterations(), want_it, "labels differing", int((km.getPointToClusterIndexMap() != want_l).sum()),
           "centroid ulps", _ulps(km.getClusterCentroids()[ok], want_c[ok]).max())
     assert (km.getPointToClusterIndexMap() == want_l).all() and km.getNumberOfPerformedIterations() == want_it
-    assert (np.isfinite(km.getClusterCentroids()) == ok).all() and (_ulps(km.getClusterCentroids()[ok], want_c[ok]) <= 1.0).all()
+    assert (np.isfinite(km.getClusterCentroids()) == ok).all() and (km.getClusterCentroids().view(np.uint32)[ok] == want_c.view(np.uint32)[ok]).all()
     return km
 
 
 def test_kmeans_nd_on_a_five_dimensional_embedding():
-    """335 x 5 (blobs5's embedding): label for label against the restatement, centroids within 1 ulp; a start that empties a cluster.
+    """335 x 5 (blobs5's embedding): label for label against the restatement, finite centroids bit for bit; a start that empties a cluster.
     Measured on an MI355X (first run, here and at 70 000 x 7): no label differs, centroids 0 ulp apart, equal iteration counts."""
     E, _, info = embed("blobs5", R.NORMALIZED_RANDOM_WALK, 5, True)
     assert E.shape == (335, 5)
