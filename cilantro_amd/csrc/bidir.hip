@@ -46,7 +46,7 @@ __global__ void k_transform_original(const float* __restrict__ src_xyz, uint32_t
   }
 }
 
-// the same under a transform the HOST holds (the order tables of the tree the reference builds over the transformed source: c_api.hip)
+// the same under a transform the HOST holds (the order tables of the tree the reference builds over the transformed source: tie_tables.hip)
 __global__ void k_transform_original_T(const float* __restrict__ src_xyz, uint32_t ns, TfDev Tf, float* __restrict__ out) {
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < ns; i += gridDim.x * blockDim.x) {
     float qx, qy, qz;

@@ -1,11 +1,13 @@
-// c_api.hip -- the C ABI of libcilantro_hip.so (declared in include/cilantro_hip/c_api.h), but for the ICP loop drivers (icp_loop.hip).
+// c_api.hip -- the C ABI of libcilantro_hip.so (declared in include/cilantro_hip/c_api.h): contexts and their stream, the clouds a context
+// holds and the buffers built on demand over them (ensure_*), the option entry points, timing and diagnostic getters, a single
+// correspondence search and the calls that read the stored set back.  The rest of the ABI by what a call touches: tie_tables.hip,
+// estimate.hip, shard_keys.hip, icp_loop.hip (the loop drivers).
 // Host-side orchestration only: owns device buffers + stream, enqueues the kernels of kernels.hip /
 // grid_build.hip.  No CPU compute fallback exists: without a usable HIP device every call fails.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstddef>
-#include <cstdio>
 #include <cstring>
 #include <new>
 
@@ -18,17 +20,6 @@ hipStream_t ctx_stream(const cilhip_ctx* c) { return c->stream; }
 double ctx_wait_us(const cilhip_ctx* c) { return c->wait_us; }
 }  // namespace cilhip
 
-// ---- what a context lets go of, and when (ctx.hpp: the groups).  A shared target array is only let go of: its last holder frees it.
-static void drop_src_grid(cilhip_ctx* c) {
-  static_cast<SrcGridBufs&>(*c) = SrcGridBufs{};
-  c->src_grid = GridDev{}; c->has_src_grid = false;
-}
-static void drop_feat_tie_tables(cilhip_ctx* c) {      // (one target under one set of feature options; never shared)
-  c->d_tief_leaf_slot.reset(); c->d_tief_nodes.reset();
-}
-static void drop_tie_tables(cilhip_ctx* c) {      // (they describe ONE target)
-  c->d_tie_leaf_slot.reset(); c->d_tie_nodes.reset();
-}
 // everything a context holds of its target: grid arrays, the tables built on top of them, the per-target buffers of the filters and
 // the reverse searches, the colours that were set for it
 static void release_target(cilhip_ctx* c) {
@@ -78,8 +69,7 @@ static void free_source(cilhip_ctx* c) {
   c->rev_tie_valid = false; c->rev_tie_aware = false;      // (the reverse order tables described this source under one transform)
   c->src3_valid = false; c->lb_fresh = false; c->rec_valid = false;
   c->d_tiles = nullptr; c->d_tile_center = nullptr; c->ntiles = 0;
-  c->has_source = false; c->src_sorted = false; drop_matches(c); c->ns = 0;
-  c->have_pairs = false; c->pairs.count = 0;   // a pair list refers to the source / target it was found on
+  c->has_source = false; c->src_sorted = false; drop_correspondences(c); c->ns = 0;
   c->policy.far_mode = true;
   c->policy.warm_banned = false;
 }
@@ -109,166 +99,42 @@ int cilhip_synchronize(cilhip_ctx* c) {
   return CILHIP_OK;
 }
 
-// ---- the options of a context, as a table a C caller can enumerate and check at compile time (enum cilhip_option in c_api.h):
-// id, key, default, admissible range, one line of documentation, how to read the current value back.  cilhip_set_option() below
-// validates and applies; the table is what tests/test_capi_symbols.py walks (every option documented, accepted with its default,
-// readable, exercised by a test).  Long-form documentation: c_api.h above cilhip_set_option.
-namespace {
-struct OptionRow { cilhip_option_info_t info; double (*get)(const cilhip_ctx*); };
-#define OPT(ID, KEY, DEF, LO, HI, DOC, EXPR) {{ID, KEY, DEF, LO, HI, DOC}, [](const cilhip_ctx* c) -> double { return (double)(EXPR); }}
-const OptionRow g_options[] = {
-  OPT(CILHIP_OPT_FUSED, "fused", 0, 0, 1, "1 = one per-lane search+accumulate kernel per iteration; 0 = search kernel + streaming accumulation (or the LDS tiles)", c->fused),
-  OPT(CILHIP_OPT_INLIER_FRACTION, "inlier_fraction", 1, 0, 1, "CorrespondenceSearchKDTree::setInlierFraction: keep that fraction of the correspondences, nearest first", c->inlier_fraction),
-  OPT(CILHIP_OPT_ONE_TO_ONE, "one_to_one", 0, 0, 1, "setOneToOne: a target point keeps only its nearest source point", c->one_to_one),
-  OPT(CILHIP_OPT_TILED, "tiled", 1, 0, 2, "LDS-tiled search: 0 = never, 1 = when the cloud fills the chip with full tiles, 2 = always", c->tiled),
-  OPT(CILHIP_OPT_WARM_START, "warm_start", 1, 0, 2, "warm-started iterations (margin proof): 0 = never, 1 = when the loop is near alignment, 2 = from the second iteration on", c->warm_start),
-  OPT(CILHIP_OPT_WARM_FORECAST, "warm_forecast", 1, 0, 1, "the cold kernels' forecast gates the warm-started form (0: the step alone; tests)", c->warm_forecast),
-  OPT(CILHIP_OPT_FUSED_EPILOGUE, "fused_epilogue", 0, 0, 1, "stage-1 reduction + epilogue as one launch behind a device-scope fence (bitwise equal, measured slower; A/B)", c->fused_epilogue),
-  OPT(CILHIP_OPT_GROUP_SEARCH, "group_search", -1, -1, 64, "lanes per query of the cooperative global-memory search: -1 = the loop decides, 0 = never, 4 / 8 / 16 / 32 / 64", c->group_lanes),
-  OPT(CILHIP_OPT_TIE_RULE, "tie_rule", 2, 0, 2, "exactly equidistant nearest points: 0 = lowest index, 1 = the reference's kd-tree order (tables up front), 2 = the same, tables when a tie is first met", c->tie_rule),
-  OPT(CILHIP_OPT_WARM_EXTRA_FRACTION, "warm_extra_fraction", 0.0625, 1e-9, 1, "room (fraction of a cell) of the ball a warm-started iteration searches a listed query in", c->warm_extra),
-  OPT(CILHIP_OPT_PAIR_RECORDS, "pair_records", 1, 0, 1, "streaming accumulation gathers a match's point and normal from one 32-byte record (A/B)", c->pair_records),
-  OPT(CILHIP_OPT_TILE_RECORDS, "tile_records", 1, 0, 1, "the accumulating tile kernel writes the warm-started form's match records itself (A/B)", c->tile_records),
-  OPT(CILHIP_OPT_WARM_ENTER_FRACTION, "warm_enter_fraction", 0.15, 1e-9, 1e9, "the warm-started form is entered once an update moves no source point by more than this fraction of a cell", c->warm_enter),
-  OPT(CILHIP_OPT_POINT_WEIGHT_EVALUATOR, "point_weight_evaluator", 0, 0, 2, "combined metric, point-to-point terms: 0 = UnityWeightEvaluator, 1 = DistanceEvaluator, 2 = RBFKernelWeightEvaluator", c->cw_point_kind),
-  OPT(CILHIP_OPT_PLANE_WEIGHT_EVALUATOR, "plane_weight_evaluator", 0, 0, 2, "combined metric, point-to-plane terms: 0 = Unity, 1 = Identity (distance), 2 = RBF kernel", c->cw_plane_kind),
-  OPT(CILHIP_OPT_POINT_WEIGHT_SIGMA, "point_weight_sigma", 1, 1e-30, 1e30, "sigma of the RBF evaluator of the point-to-point terms", c->cw_point_sigma),
-  OPT(CILHIP_OPT_PLANE_WEIGHT_SIGMA, "plane_weight_sigma", 1, 1e-30, 1e30, "sigma of the RBF evaluator of the point-to-plane terms", c->cw_plane_sigma),
-  OPT(CILHIP_OPT_TILE_ACCUMULATION, "tile_accumulation", 1, 0, 2, "first Gauss-Newton step accumulated inside the LDS tiles: 0 = never, 1 = unless the source is far from alignment, 2 = always", (c->tile_acc ? (c->tile_acc_adaptive ? 1 : 2) : 0)),
-  OPT(CILHIP_OPT_SEARCH_DIRECTION, "search_direction", 0, 0, 2, "CorrespondenceSearchDirection: 0 = SECOND_TO_FIRST, 1 = FIRST_TO_SECOND, 2 = BOTH", c->search_dir),
-  OPT(CILHIP_OPT_FEATURE_NORMAL_WEIGHT, "feature_normal_weight", 0, 0, 1e30, "PointNormalFeaturesAdaptor's normal weight (> 0: the search runs on 6-D features)", c->normal_weight),
-  OPT(CILHIP_OPT_FEATURE_KIND, "feature_kind", 0, 0, 2, "second feature block: 0 = normals (follow the transform), 1 = colours (do not), 2 = normals + colours (9-D)", c->feature_kind),
-  OPT(CILHIP_OPT_FEATURE_COLOR_WEIGHT, "feature_color_weight", 0, 0, 1e30, "PointNormalColorFeaturesAdaptor's colour weight (feature_kind 2)", c->color_weight),
-  OPT(CILHIP_OPT_SYMMETRIC_METRIC, "symmetric_metric", 1, 0, 1, "source normals, when set, switch the combined metric to the symmetric objective", c->symmetric),
-  OPT(CILHIP_OPT_TRANSFORM_MODE, "transform_mode", 0, 0, 1, "ICP instance family: 0 = rigid, 1 = affine", c->transform_mode),
-  OPT(CILHIP_OPT_REQUIRE_RECIPROCALITY, "require_reciprocality", 0, 0, 1, "setRequireReciprocality (search_direction BOTH)", c->reciprocal),
-  OPT(CILHIP_OPT_CELL_OCCUPANCY, "cell_occupancy", 1, 1e-3, 1e6, "target points per grid cell the next cilhip_set_target aims at", c->cell_occupancy),
-  OPT(CILHIP_OPT_REFINED_OCCUPANCY_FACTOR, "refined_occupancy_factor", 3, 1, 64, "how much denser than that a grid that had to be refined (surface, clusters) may stay", c->refined_occupancy),
-  OPT(CILHIP_OPT_KERNEL_TIMING, "kernel_timing", 0, 0, 1, "hipEvents around the search / accumulation kernels (cilhip_enable_kernel_timing)", c->kernel_timing),
-  OPT(CILHIP_OPT_KERNEL_TIMING_STRIDE, "kernel_timing_stride", 1, 1, 4096, "with kernel timing on: iterations 0..2 and every stride-th one carry events", c->timing_stride),
-  OPT(CILHIP_OPT_REVERSE_WARM_START, "reverse_warm_start", 1, 0, 1, "device-resident FIRST_TO_SECOND / BOTH loops: reverse searches after the first start from the previous reverse matches (margin test over the source; A/B)", c->reverse_warm),
-  OPT(CILHIP_OPT_FEATURE_WARM_START, "feature_warm_start", 1, 0, 1, "feature adaptors (SECOND_TO_FIRST loops): searches warm-started from the previous matches once the loop moves little (margin test with the feature distance; A/B)", c->feat_warm),
-  OPT(CILHIP_OPT_AFFINE_DEVICE_LOOP, "affine_device_loop", 1, 0, 1, "affine classes: 1 = device-resident loop (one-pass moments, solve in the epilogue kernel), 0 = host-driven loop (three passes + host solve; A/B)", c->affine_device_loop),
-};
-#undef OPT
-constexpr int N_OPTIONS = (int)(sizeof(g_options) / sizeof(g_options[0]));
-static_assert(N_OPTIONS == CILHIP_OPT_COUNT, "one table row per enum cilhip_option value, in the enum's order");
-}  // namespace
+// ---- the options of a context: the table a C caller can enumerate and check at compile time (enum cilhip_option in c_api.h) is
+// ctx_options.hpp's, one row per option; it is also what tests/test_capi_symbols.py walks (every option documented, accepted with its
+// default, readable, exercised by a test).
+static const OptionRow* option_row(const char* key) {
+  for (const OptionRow& r : kOptionRows) if (!strcmp(key, r.info.key)) return &r;
+  return nullptr;
+}
+// a row's admissible range holds for every key (a mistyped "tiled" = 3 would otherwise run some other form); the row adds what a range cannot say
+static int store_option(cilhip_ctx* c, const OptionRow* row, double value) {
+  if (value != value) return fail(c, CILHIP_ERR_INVALID, "set_option: the value is not a number");
+  if (!row) return fail(c, CILHIP_ERR_INVALID, "set_option: unknown key");
+  if (!(value >= row->info.min_value && value <= row->info.max_value))
+    return fail(c, CILHIP_ERR_INVALID, "set_option: value outside the option's [min_value, max_value] (cilhip_option_info)");
+  unsigned stale = 0;
+  if (const char* refusal = row->set(*c, value, &stale)) return fail(c, CILHIP_ERR_INVALID, refusal);
+  apply_stale(c, stale);
+  return CILHIP_OK;
+}
 
 int cilhip_option_count(void) { return N_OPTIONS; }
-const cilhip_option_info_t* cilhip_option_info(int id) { return (id >= 0 && id < N_OPTIONS) ? &g_options[id].info : nullptr; }
+const cilhip_option_info_t* cilhip_option_info(int id) { return (id >= 0 && id < N_OPTIONS) ? &kOptionRows[id].info : nullptr; }
 int cilhip_set_option_id(cilhip_ctx* c, cilhip_option id, double value) {
   if (!c) return CILHIP_ERR_INVALID;
   if ((int)id < 0 || (int)id >= N_OPTIONS) return fail(c, CILHIP_ERR_INVALID, "set_option_id: unknown option");
-  return cilhip_set_option(c, g_options[(int)id].info.key, value);
+  return store_option(c, &kOptionRows[(int)id], value);
 }
 int cilhip_get_option(cilhip_ctx* c, const char* key, double* value) {
   if (!c || !key || !value) return CILHIP_ERR_INVALID;
-  for (int i = 0; i < N_OPTIONS; ++i)
-    if (!strcmp(key, g_options[i].info.key)) { *value = g_options[i].get(c); return CILHIP_OK; }
-  return fail(c, CILHIP_ERR_INVALID, "get_option: unknown key");
+  const OptionRow* row = option_row(key);
+  if (!row) return fail(c, CILHIP_ERR_INVALID, "get_option: unknown key");
+  *value = row->get(*c);
+  return CILHIP_OK;
 }
-
 int cilhip_set_option(cilhip_ctx* c, const char* key, double value) {
   if (!c || !key) return CILHIP_ERR_INVALID;
-  if (value != value) return fail(c, CILHIP_ERR_INVALID, "set_option: the value is not a number");
-  // every row's admissible range holds for every key (a mistyped "tiled" = 3 would otherwise run some other form); the rows
-  // below only add what a range cannot say (the discrete values of group_search, tie_rule, ...)
-  for (int i = 0; i < N_OPTIONS; ++i)
-    if (!strcmp(key, g_options[i].info.key) && !(value >= g_options[i].info.min_value && value <= g_options[i].info.max_value))
-      return fail(c, CILHIP_ERR_INVALID, "set_option: value outside the option's [min_value, max_value] (cilhip_option_info)");
-  if (!strcmp(key, "fused")) { c->fused = value != 0.0; return CILHIP_OK; }
-  // (a finished run's set that has not been searched again yet -- cilhip_get_last_matches_origin 2 -- would be filtered with the
-  //  NEW values: a changed post-filter drops it; a set already in memory is what its search left, whatever is set afterwards)
-  if (!strcmp(key, "inlier_fraction")) { if (c->inlier_fraction != value && c->pending_matches) drop_matches(c); c->inlier_fraction = value; return CILHIP_OK; }
-  if (!strcmp(key, "one_to_one")) { if (c->one_to_one != (value != 0.0) && c->pending_matches) drop_matches(c); c->one_to_one = value != 0.0; return CILHIP_OK; }
-  if (!strcmp(key, "tiled")) { c->tiled = (int)value; return CILHIP_OK; }
-  if (!strcmp(key, "warm_start")) { c->warm_start = (int)value; return CILHIP_OK; }
-  if (!strcmp(key, "warm_forecast")) { c->warm_forecast = value != 0.0; return CILHIP_OK; }
-  if (!strcmp(key, "fused_epilogue")) { c->fused_epilogue = value != 0.0; return CILHIP_OK; }
-  if (!strcmp(key, "reverse_warm_start")) { c->reverse_warm = value != 0.0; return CILHIP_OK; }
-  if (!strcmp(key, "feature_warm_start")) { c->feat_warm = value != 0.0; return CILHIP_OK; }
-  if (!strcmp(key, "affine_device_loop")) { c->affine_device_loop = value != 0.0; return CILHIP_OK; }
-  if (!strcmp(key, "group_search")) {
-    if (value != -1.0 && value != 0.0 && value != 4.0 && value != 8.0 && value != 16.0 && value != 32.0 && value != 64.0)
-      return fail(c, CILHIP_ERR_INVALID, "group_search: -1 (the loop decides), 0 (never), or 4, 8, 16, 32, 64 lanes per query");
-    c->group_lanes = (int)value;
-    return CILHIP_OK;
-  }
-  if (!strcmp(key, "tie_rule")) {
-    if (value != 0.0 && value != 1.0 && value != 2.0)
-      return fail(c, CILHIP_ERR_INVALID, "tie_rule: 0 (lowest index), 1 (the reference's kd-tree order, tables built up front) or 2 (the same, tables built when a tie is first met)");
-    if (((int)value != 0) != (c->tie_rule != 0)) drop_matches(c);
-    c->tie_rule = (int)value;
-    return CILHIP_OK;
-  }
-  if (!strcmp(key, "warm_extra_fraction")) {
-    if (!(value > 0.0 && value <= 1.0)) return fail(c, CILHIP_ERR_INVALID, "warm_extra_fraction: in (0, 1]");
-    c->warm_extra = (float)value;
-    return CILHIP_OK;
-  }
-  if (!strcmp(key, "pair_records")) { c->pair_records = value != 0.0; return CILHIP_OK; }
-  if (!strcmp(key, "tile_records")) { c->tile_records = value != 0.0; return CILHIP_OK; }
-  if (!strcmp(key, "warm_enter_fraction")) {
-    if (!(value > 0.0)) return fail(c, CILHIP_ERR_INVALID, "warm_enter_fraction: > 0 (fraction of a grid cell)");
-    c->warm_enter = (float)value;
-    return CILHIP_OK;
-  }
-  if (!strcmp(key, "point_weight_evaluator") || !strcmp(key, "plane_weight_evaluator")) {
-    if (value != 0.0 && value != 1.0 && value != 2.0) return fail(c, CILHIP_ERR_INVALID, "weight evaluator: 0 = Unity, 1 = Identity, 2 = RBF kernel");
-    (key[1] == 'o' ? c->cw_point_kind : c->cw_plane_kind) = (int)value;
-    return CILHIP_OK;
-  }
-  if (!strcmp(key, "point_weight_sigma") || !strcmp(key, "plane_weight_sigma")) {
-    if (!(value > 0.0)) return fail(c, CILHIP_ERR_INVALID, "weight evaluator sigma must be positive");
-    (key[1] == 'o' ? c->cw_point_sigma : c->cw_plane_sigma) = (float)value;
-    return CILHIP_OK;
-  }
-  if (!strcmp(key, "tile_accumulation")) { c->tile_acc = value != 0.0; c->tile_acc_adaptive = value != 2.0; return CILHIP_OK; }
-  if (!strcmp(key, "search_direction")) {
-    if (value != 0.0 && value != 1.0 && value != 2.0) return fail(c, CILHIP_ERR_INVALID, "search_direction: 0 = SECOND_TO_FIRST, 1 = FIRST_TO_SECOND, 2 = BOTH");
-    c->search_dir = (int)value; drop_matches(c); c->have_pairs = false;
-    return CILHIP_OK;
-  }
-  if (!strcmp(key, "feature_normal_weight")) {
-    if (!(value >= 0.0)) return fail(c, CILHIP_ERR_INVALID, "feature_normal_weight: >= 0 (0 = plain point features)");
-    if (c->normal_weight != (float)value) drop_feat_tie_tables(c);
-    c->normal_weight = (float)value; drop_matches(c); c->have_pairs = false;
-    return CILHIP_OK;
-  }
-  if (!strcmp(key, "feature_kind")) {
-    if (value != 0.0 && value != 1.0 && value != 2.0)
-      return fail(c, CILHIP_ERR_INVALID, "feature_kind: 0 = normals (follow the transform), 1 = colours (do not), 2 = normals + colours (9-D)");
-    if ((int)value != c->feature_kind) { drop_src_grid(c); drop_feat_tie_tables(c); }      // (the source's grid carries the feature vectors of the reverse searches)
-    c->feature_kind = (int)value; drop_matches(c); c->have_pairs = false;
-    return CILHIP_OK;
-  }
-  if (!strcmp(key, "feature_color_weight")) {
-    if (!(value >= 0.0)) return fail(c, CILHIP_ERR_INVALID, "feature_color_weight: >= 0");
-    if (c->color_weight != (float)value) drop_feat_tie_tables(c);
-    c->color_weight = (float)value; drop_matches(c); c->have_pairs = false;
-    return CILHIP_OK;
-  }
-  if (!strcmp(key, "symmetric_metric")) { c->symmetric = value != 0.0; return CILHIP_OK; }
-  if (!strcmp(key, "transform_mode")) {
-    if (value != 0.0 && value != 1.0) return fail(c, CILHIP_ERR_INVALID, "transform_mode: 0 = rigid, 1 = affine");
-    c->transform_mode = (int)value;
-    return CILHIP_OK;
-  }
-  if (!strcmp(key, "require_reciprocality")) { c->reciprocal = value != 0.0; drop_matches(c); c->have_pairs = false; return CILHIP_OK; }
-  if (!strcmp(key, "cell_occupancy")) { c->cell_occupancy = value; return CILHIP_OK; }
-  if (!strcmp(key, "refined_occupancy_factor")) {
-    if (!(value >= 1.0 && value <= 64.0)) return fail(c, CILHIP_ERR_INVALID, "refined_occupancy_factor: in [1, 64]");
-    c->refined_occupancy = value;
-    return CILHIP_OK;
-  }
-  if (!strcmp(key, "kernel_timing")) { c->kernel_timing = value != 0.0; return CILHIP_OK; }
-  if (!strcmp(key, "kernel_timing_stride")) {
-    if (!(value >= 1.0 && value <= 4096.0)) return fail(c, CILHIP_ERR_INVALID, "kernel_timing_stride: 1 .. 4096");
-    c->timing_stride = (int)value;
-    return CILHIP_OK;
-  }
-  return fail(c, CILHIP_ERR_INVALID, "set_option: unknown key");
+  return store_option(c, option_row(key), value);
 }
 
 int cilhip_debug_counters(cilhip_ctx* c, uint32_t out[2]) {
@@ -384,8 +250,7 @@ int cilhip_set_target(cilhip_ctx* c, const float* xyz, const float* nrm, size_t 
   c->partial_target = false;      // (a new target stands for itself until cilhip_set_shard_info says otherwise)
   c->has_target = true;
   c->src_sorted = false;  // source order is tied to the target grid
-  drop_matches(c);
-  c->have_pairs = false; c->pairs.count = 0;
+  drop_correspondences(c);
   c->policy.far_mode = true;
   c->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return CILHIP_OK;
@@ -410,11 +275,10 @@ int cilhip_share_target(cilhip_ctx* c, cilhip_ctx* from) {
   for (int i = 0; i < 3; ++i) c->dst_mean[i] = from->dst_mean[i];
   c->index_offset = from->index_offset; c->partial_target = from->partial_target;
   c->d_inv_perm = from->d_inv_perm; c->d_safe2 = from->d_safe2;
-  c->d_tie_leaf_slot = from->d_tie_leaf_slot; c->d_tie_nodes = from->d_tie_nodes;
+  c->d_tie_leaf_slot = from->d_tie_leaf_slot; c->d_tie_nodes = from->d_tie_nodes; c->tie_max_depth = from->tie_max_depth;
   c->policy.warm_banned = false;
   c->src_sorted = false;  // source order is tied to the target grid
-  drop_matches(c);
-  c->have_pairs = false; c->pairs.count = 0;
+  drop_correspondences(c);
   c->policy.far_mode = true;
   return CILHIP_OK;
 }
@@ -454,7 +318,7 @@ int cilhip_set_source_normals(cilhip_ctx* c, const float* nrm, int mem) {
   CK(c, hipSetDevice(c->device));
   c->d_src_nrm.reset();
   c->d_src_nrm_sorted.reset();
-  c->have_pairs = false; c->pairs.count = 0;
+  c->have_pairs = false;
   drop_src_grid(c);      // (it carries the feature vectors of the reverse searches)
   if (!nrm) return CILHIP_OK;                              // back to the 3-cloud (non-symmetric) form
   int rc = upload(c, nrm, 3 * (size_t)c->ns, mem, c->d_src_nrm);
@@ -466,8 +330,7 @@ int cilhip_set_source_normals(cilhip_ctx* c, const float* nrm, int mem) {
   }
   CK(c, c->d_src_nrm_sorted.alloc(c->ns));
   c->src_sorted = false;                                   // the sorted copy is (re)built with the next sort
-  drop_matches(c);
-  c->have_pairs = false; c->pairs.count = 0;
+  drop_correspondences(c);
   return CILHIP_OK;
 }
 
@@ -488,8 +351,7 @@ int cilhip_set_color_features(cilhip_ctx* c, const float* dst_rgb, const float* 
   c->src_sorted = false;                                   // the source's sorted copy is (re)built with the next sort
   drop_src_grid(c);      // (it carries the features of the reverse searches)
   drop_feat_tie_tables(c);      // (the colours are coordinates of the feature tree)
-  drop_matches(c);
-  c->have_pairs = false; c->pairs.count = 0;
+  drop_correspondences(c);
   return CILHIP_OK;
 }
 
@@ -548,7 +410,7 @@ int cilhip::ensure_sorted(cilhip_ctx* c, const float T[16]) {
     memcpy(c->sort_T, T, sizeof(c->sort_T));
     c->src_sorted = true;
     c->src3_valid = false; c->rec_valid = false; c->lb_fresh = false;     // (per sorted order)
-    drop_matches(c);
+    drop_matches(c);      // (the matches alone: a pair list carries its own views of the source)
   }
   return CILHIP_OK;
 }
@@ -592,236 +454,12 @@ void cilhip::set_warm_args(const cilhip_ctx* c, IterArgs& wa) {
   wa.warm_rec_n = reinterpret_cast<F3*>(c->d_warm_rec + cap);
   wa.warm_src3 = wa.warm_rec_n + cap;
 }
-// The per-pair weights of the combined-metric classes (PointToPoint/PointToPlaneCorrWeightEvaluatorT of
-// icp_single_transform_combined_metric.hpp:11-14; the point-to-point class has none): evaluator(corr.value) times the
-// metric weight, in f32.  RBF coefficient as common_pair_evaluators.hpp:53.
-static CorrWeights corr_weights_of(const cilhip_ctx* c, bool combined_metric, float w_p2p, float w_p2pl) {
-  CorrWeights w{};
-  w.enabled = (combined_metric && weighted(c)) ? 1 : 0;
-  w.point_kind = c->cw_point_kind; w.plane_kind = c->cw_plane_kind;
-  w.point_coeff = -0.5f / (c->cw_point_sigma * c->cw_point_sigma);
-  w.plane_coeff = -0.5f / (c->cw_plane_sigma * c->cw_plane_sigma);
-  w.w_p2p = w_p2p; w.w_p2pl = w_p2pl;
-  // (a caller's own evaluators: prepare_pair_weights() has put the weights of the stored correspondences into the tables)
-  if (w.enabled && c->weight_fn) { w.point_table = c->d_wtab; w.plane_table = c->d_wtab + c->d_wtab.capacity() / 2; }
-  return w;
-}
-CorrWeights cilhip::corr_weights_of(const cilhip_ctx* c, const cilhip_icp_params* p) {
-  return corr_weights_of(c, p->metric == CILHIP_METRIC_COMBINED, p->w_p2p, p->w_p2pl);
-}
 // k_self_nn's nearest-other-point table (4 B per target point, 0.5 ms at 10M): built by the first warm-capable run on a target
 int cilhip::ensure_safe2(cilhip_ctx* c) {
   if (c->d_safe2) return CILHIP_OK;
   CK(c, c->d_safe2.alloc(c->grid.n));
   launch_self_nn(c->grid, c->d_safe2, c->stream);
   return CILHIP_OK;
-}
-
-// ---- option "tie_rule": the reference's order among exactly equidistant nearest points ------------------------------------------
-// When the option is in force for a context's searches: the order is the reference's kd-tree over the TARGET POINTS: it covers the
-// SECOND_TO_FIRST matches (also the forward half of BOTH) under rigid and affine transforms.  Feature adaptors search another
-// space (nanoflann's DIM = 6 / 9 tree: tie_feat_on below), the reverse matches of FIRST_TO_SECOND / BOTH a tree over the transformed
-// SOURCE that the reference rebuilds every iteration (rev_tie_aware); the feature adaptors' reverse searches keep the lowest index
-// (tie_rule 2) or are refused (tie_rule 1, the explicit request).  An
-// index shard of a target (cilhip_set_shard_info) notices and counts ties like any context, but never builds tables from its own points:
-// the order belongs to the WHOLE target's tree -- whoever owns the shards loads it (cilhip_load_tie_order with the global indices) and
-// runs the two-key protocol between them (cilhip_icp_order_keys).  (The predicate itself: tie_mode_on, ctx.hpp.)
-// ... and over 6-D / 9-D features: the forward (SECOND_TO_FIRST) search of a whole target follows the reference's DIM = 6 / 9 tree
-// (its order tables: tie_order_build_device_features; tie_settle<true> / tie_before_nd on the device)
-static bool tie_feat_on(const cilhip_ctx* c) { return c->tie_rule != 0 && feat6(c) && c->search_dir == 0 && !c->partial_target && !c->index_offset; }
-static TieDev tie_dev_of(const cilhip_ctx* c) {
-  TieDev t{};
-  if (feat6(c)) {
-    t.mode = tie_feat_on(c) ? 1 : 0;
-    t.leaf_slot = t.mode ? c->d_tief_leaf_slot : nullptr;
-    t.nodes = c->d_tief_nodes;
-    t.counters = c->d_tie_counters;
-    return t;
-  }
-  t.mode = tie_mode_on(c) ? 1 : 0;
-  t.leaf_slot = t.mode ? c->d_tie_leaf_slot : nullptr;
-  t.nodes = c->d_tie_nodes;
-  t.counters = c->d_tie_counters;
-  return t;
-}
-// Order tables by this target's ORIGINAL (local) index -> device, by sorted position.
-static int load_tie_tables(cilhip_ctx* c, const uint32_t* leaf_by_index, const uint32_t* slot_by_index, const cilhip::TieNode* nodes, size_t n_nodes) {
-  static_assert(sizeof(cilhip::TieNode) == sizeof(uint4), "TieNode is read as one 16-byte record");
-  CK(c, hipSetDevice(c->device));
-  drop_tie_tables(c);
-  const size_t n = c->grid.n;
-  DevBuf<uint32_t> d_leaf, d_slot;
-  // (d_tie_leaf_slot != null is the "tables loaded" flag: nothing may be left half set when an allocation fails)
-  hipError_t e = c->d_tie_leaf_slot.alloc(n);
-  if (e == hipSuccess) e = c->d_tie_nodes.alloc(n_nodes);
-  if (e == hipSuccess) e = d_leaf.alloc(n);
-  if (e == hipSuccess) e = d_slot.alloc(n);
-  if (e == hipSuccess && n) {
-    e = hipMemcpyAsync(d_leaf, leaf_by_index, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_slot, slot_by_index, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && n_nodes) e = hipMemcpyAsync(c->d_tie_nodes, nodes, n_nodes * sizeof(uint4), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) { launch_tie_tables_by_position(c->grid.pts, c->grid.n, d_leaf, d_slot, c->d_tie_leaf_slot, c->stream); e = hipGetLastError(); }
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      // (the host arrays and the two staging buffers live on this frame)
-  if (e != hipSuccess) { drop_tie_tables(c); c->err = std::string("tie_rule: loading the order tables: ") + hipGetErrorString(e); return CILHIP_ERR_HIP; }
-  c->tie_max_depth = 0;
-  for (size_t k = 0; k < n_nodes; ++k) c->tie_max_depth = std::max(c->tie_max_depth, (int)(nodes[k].info >> 3));
-  return CILHIP_OK;
-}
-// The order tables of a tree over this context's target, built on the device (tie_build.hip): `build` fills leaf and slot by original
-// index and the nodes; the tables by sorted position go to *leaf_slot.  On failure the caller drops what *leaf_slot holds.
-template <class Build>
-static hipError_t build_target_order_tables(cilhip_ctx* c, SharedBuf<uint2>& leaf_slot, SharedBuf<uint4>& nodes, Build build) {
-  const uint32_t n = c->grid.n;
-  DevBuf<uint32_t> d_leaf, d_slot;
-  DevBuf<uint4> d_nodes;
-  hipError_t e = d_leaf.alloc(n);
-  if (e == hipSuccess) e = d_slot.alloc(n);
-  if (e == hipSuccess) e = leaf_slot.alloc(n);
-  if (e == hipSuccess) e = build(d_leaf.get(), d_slot.get(), &d_nodes);
-  if (e == hipSuccess && !d_nodes) e = d_nodes.alloc(1);      // (an empty target)
-  if (e == hipSuccess && n) { launch_tie_tables_by_position(c->grid.pts, n, d_leaf, d_slot, leaf_slot, c->stream); e = hipGetLastError(); }
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e == hipSuccess) e = nodes.adopt(std::move(d_nodes));
-  return e;
-}
-// The tables of THIS context's target, from the grid's own records.
-static int build_tie_tables(cilhip_ctx* c) {
-  if (c->d_tie_leaf_slot || !c->has_target) return CILHIP_OK;
-  const auto t0 = std::chrono::steady_clock::now();
-  CK(c, hipSetDevice(c->device));
-  drop_tie_tables(c);
-  size_t n_nodes = 0;
-  int depth = 0;
-  const hipError_t e = build_target_order_tables(c, c->d_tie_leaf_slot, c->d_tie_nodes, [&](uint32_t* leaf, uint32_t* slot, DevBuf<uint4>* nodes) {
-    return tie_order_build_device(nullptr, c->grid.pts, c->grid.n, c->stream, leaf, slot, nodes, &n_nodes, &depth); });
-  if (e != hipSuccess) {
-    drop_tie_tables(c);
-    c->err = std::string("tie_rule: building the order tables: ") + hipGetErrorString(e);
-    return CILHIP_ERR_HIP;
-  }
-  c->tie_max_depth = depth;
-  c->tie_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  ++c->tie_builds;
-  return CILHIP_OK;
-}
-// the counters of the searches since the last launch_init_state (a host round trip)
-static int read_tie_counters(cilhip_ctx* c, unsigned int out[4]) {
-  CK(c, hipMemcpyAsync(out, c->d_tie_counters, 4 * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
-  CK(c, hipStreamSynchronize(c->stream));
-  return CILHIP_OK;
-}
-// The reverse matches' order (FIRST_TO_SECOND / BOTH): what k_reverse_search is handed.  Without valid tables it counts the tied target
-// points (counters[3]) and keeps the lowest source index.
-TieDev cilhip::tie_dev_rev(const cilhip_ctx* c) {
-  TieDev t{};
-  t.mode = tie_mode_on(c) ? 1 : 0;
-  t.leaf_slot = (t.mode && c->rev_tie_valid) ? c->d_rev_tie_leaf_slot : nullptr;
-  t.nodes = c->d_rev_tie_nodes;
-  t.counters = c->d_tie_counters;
-  return t;
-}
-// The order tables of the tree the reference builds over the source transformed by T (src_points_trans = transform_ * src, the engine's
-// pinned f32 expression; correspondence_search_kd_tree.hpp:185-222), by position in the source grid.  Device work per search: the
-// transform of the source (its original order) and tie_order_build_device over it (2 ms for a 110k-point frame, 25 ms at 10M).
-static int build_rev_tie_tables(cilhip_ctx* c, const float T[16]) {
-  if (c->rev_tie_valid && memcmp(c->rev_tie_T, T, sizeof(c->rev_tie_T)) == 0) return CILHIP_OK;
-  c->rev_tie_valid = false;
-  const uint32_t n = c->ns;
-  if (!c->has_src_grid || n == 0) return CILHIP_OK;
-  CK(c, hipSetDevice(c->device));
-  DevBuf<float> d_q;
-  DevBuf<uint32_t> d_leaf, d_slot;
-  DevBuf<uint4> d_nodes;
-  size_t n_nodes = 0;
-  hipError_t e = d_q.alloc((size_t)n * 3);
-  if (e == hipSuccess) e = d_leaf.alloc(n);
-  if (e == hipSuccess) e = d_slot.alloc(n);
-  if (e == hipSuccess && !c->d_rev_tie_leaf_slot) e = c->d_rev_tie_leaf_slot.alloc(n);
-  if (e == hipSuccess) { launch_transform_original_host_T(c->d_src_xyz, n, T, d_q, c->stream); e = hipGetLastError(); }      // q = fl(T s), the engine's pinned expression
-  if (e == hipSuccess) e = tie_order_build_device(d_q, nullptr, n, c->stream, d_leaf, d_slot, &d_nodes, &n_nodes, nullptr);
-  if (e == hipSuccess) {
-    c->d_rev_tie_nodes = std::move(d_nodes);
-    launch_tie_tables_by_position(c->src_grid.pts, n, d_leaf, d_slot, c->d_rev_tie_leaf_slot, c->stream);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) { c->err = std::string("tie_rule: the transformed source's order tables: ") + hipGetErrorString(e); return CILHIP_ERR_HIP; }
-  memcpy(c->rev_tie_T, T, sizeof(c->rev_tie_T));
-  c->rev_tie_valid = true;
-  ++c->rev_tie_builds;
-  return CILHIP_OK;
-}
-// tie_rule 1: the tables before the first search; refusals of the explicit request (see tie_mode_on)
-// The order tables of the tree the reference's feature adaptor searches (DIM = 6: points + weighted normals or colours; 9: + colours), for
-// this target under the CURRENT feature options, built on the device (tie_build.hip).
-static int build_feat_tie_tables(cilhip_ctx* c) {
-  if (c->d_tief_leaf_slot || !c->has_target) return CILHIP_OK;
-  CK(c, hipSetDevice(c->device));
-  { const int rc = ensure_feature_arrays(c); if (rc) return rc; }
-  const FeatSpec f = feat_spec_of(c);
-  const int dim = c->feature_kind == 2 ? 9 : 6;
-  if (!f.dst || (dim == 9 && !f.dst2)) return fail(c, CILHIP_ERR_INVALID, "tie_rule: the target's feature attributes (normals / colours) are not set");
-  size_t n_nodes = 0;
-  const hipError_t e = build_target_order_tables(c, c->d_tief_leaf_slot, c->d_tief_nodes, [&](uint32_t* leaf, uint32_t* slot, DevBuf<uint4>* nodes) {
-    return tie_order_build_device_features(dim, c->grid.pts, f.dst, f.w, f.dst2, f.w2, c->grid.n, c->stream, leaf, slot, nodes, &n_nodes, nullptr); });
-  if (e != hipSuccess) {
-    drop_feat_tie_tables(c);
-    c->err = std::string("tie_rule: building the feature tree's order tables: ") + hipGetErrorString(e);
-    return CILHIP_ERR_HIP;
-  }
-  ++c->tief_builds;
-  return CILHIP_OK;
-}
-int cilhip::tie_prepare(cilhip_ctx* c, const char* what) {
-  c->tie_counters_fresh = false;      // (a new search / run: whatever the host holds of the counters is history)
-  if (c->tie_rule == 1 && ((feat6(c) && !tie_feat_on(c)) || (!feat6(c) && c->partial_target && !c->d_tie_leaf_slot))) {
-    c->err = std::string(what) + ": tie_rule = 1 covers the SECOND_TO_FIRST search (point features: every direction) on a whole target, or on shards of a point-feature target with the whole target's order loaded (tie_rule = 2 applies the reference's order where it is defined)";
-    return CILHIP_ERR_UNSUPPORTED;
-  }
-  if (c->tie_rule == 1 && tie_feat_on(c) && c->ns && c->grid.n) return build_feat_tie_tables(c);
-  if (c->tie_rule == 1 && c->search_dir != 0) c->rev_tie_aware = true;
-  if (c->tie_rule == 0) c->rev_tie_aware = false;
-  if (c->tie_rule == 1 && tie_mode_on(c) && !c->partial_target && c->search_dir != 1 && c->ns && c->grid.n) return build_tie_tables(c);
-  return CILHIP_OK;
-}
-// After a search / run: did it meet ties without tables (tie_rule 2)?  Then the tables are built and *again says: run it once more.
-int cilhip::tie_check_pending(cilhip_ctx* c, bool* again) {
-  *again = false;
-  if (tie_feat_on(c)) {      // a feature search: its forward matches counted tied queries while the feature tree's tables were not there
-    if (c->d_tief_leaf_slot || !c->ns || !c->grid.n) return CILHIP_OK;
-    unsigned int cnt[4];
-    if (c->tie_counters_fresh) memcpy(cnt, c->tie_counters_host, sizeof(cnt));
-    else { const int rc = read_tie_counters(c, cnt); if (rc) return rc; }
-    c->tie_counters_fresh = false;
-    if (cnt[0] == 0u) return CILHIP_OK;
-    *again = true;
-    CK(c, hipMemsetAsync(c->d_tie_counters, 0, 4 * sizeof(unsigned int), c->stream));
-    return build_feat_tie_tables(c);
-  }
-  if (!tie_mode_on(c) || c->partial_target || !c->ns || !c->grid.n) return CILHIP_OK;      // (a part of a target: its caller loads the whole cloud's order)
-  const bool fwd_open = !c->d_tie_leaf_slot && c->search_dir != 1;      // (forward matches: SECOND_TO_FIRST, the forward half of BOTH)
-  const bool rev_open = !c->rev_tie_aware && c->search_dir != 0;
-  if (!fwd_open && !rev_open) return CILHIP_OK;
-  unsigned int cnt[4];
-  if (c->tie_counters_fresh) {      // (a run's read_state has just brought them over with the loop state: no second round trip)
-    memcpy(cnt, c->tie_counters_host, sizeof(cnt));
-  } else {
-    const int rc = read_tie_counters(c, cnt);
-    if (rc) return rc;
-  }
-  c->tie_counters_fresh = false;
-  // Forward matches: any tie, the tables are built once per target.  Reverse matches: the tables cost a host tree build PER SEARCH (0.25 s
-  // at 10M points against an iteration of a millisecond), so the automatic rule pays it for clouds that tie systematically -- duplicated
-  // points, lattices: at least 16 tied target points and one in 100 000 -- and not for the isolated coincidence of two f32 distances in a
-  // large random cloud (about one target point in ten million): those keep the lowest source index and stay counted
-  // (cilhip_get_tie_rule_stats); tie_rule 1 follows the reference for every one of them.
-  const bool fwd = fwd_open && cnt[0] != 0u, rev = rev_open && cnt[3] >= 16u && (unsigned long long)cnt[3] * 100000ull >= (unsigned long long)c->grid.n;
-  if (!fwd && !rev) return CILHIP_OK;
-  *again = true;
-  CK(c, hipMemsetAsync(c->d_tie_counters, 0, 4 * sizeof(unsigned int), c->stream));      // (the repeated search counts afresh)
-  if (rev) c->rev_tie_aware = true;      // (the tables themselves: per search, under its transform -- run_pair_search)
-  return fwd ? build_tie_tables(c) : CILHIP_OK;
 }
 
 // filterCorrespondencesFraction then filterCorrespondencesOneToOne on the stored matches
@@ -1010,7 +648,7 @@ int cilhip_set_projection(cilhip_ctx* c, const float* K, size_t w, size_t h, con
   CK(c, hipSetDevice(c->device));
   CK(c, hipStreamSynchronize(c->stream));      // (a search may still be reading the map)
   c->d_proj_map.reset(); c->d_proj_keys.reset();
-  drop_matches(c);
+  drop_matches(c);      // (the matches alone: a projection never runs with the pair-list directions)
   c->proj_on = K != nullptr;
   if (!K) return CILHIP_OK;
   ProjDev& p = c->proj;
@@ -1111,7 +749,7 @@ static int scatter_to_original(cilhip_ctx* c) {
 // The correspondence set of the last executed iteration of cilhip_icp_run, when the loop's kernels did not leave it in memory
 // (post-filters, pair-list directions, feature search, forms that store no matches): searched again under the transform that
 // iteration searched under.  The search is exact and deterministic: the same set.
-static int materialize_pending(cilhip_ctx* c) {
+int cilhip::materialize_pending(cilhip_ctx* c) {
   if (!c->pending_matches) return ensure_d2(c);      // (matches a loop left in place: their distances are formed now, if not yet)
   float T[16];
   memcpy(T, c->nn_T, sizeof(T));
@@ -1140,109 +778,6 @@ int cilhip_get_matches_transform(cilhip_ctx* c, float T[16]) {
   if (!c || !T) return CILHIP_ERR_INVALID;
   if (!c->have_nn && !c->have_pairs && !c->pending_matches) return fail(c, CILHIP_ERR_INVALID, "get_matches_transform: no search has been run");
   memcpy(T, c->nn_T, sizeof(c->nn_T));
-  return CILHIP_OK;
-}
-
-int cilhip_get_tie_count(cilhip_ctx* c, const float T[16], float max_sq, size_t* n_ties) {
-  if (!c || !T || !n_ties) return CILHIP_ERR_INVALID;
-  CK(c, hipSetDevice(c->device));
-  const int rc = ensure_sorted(c, T);
-  if (rc) return rc;
-  launch_count_ties(c->grid, c->d_src_sorted, c->ns, T, max_sq, c->d_count, c->stream);
-  unsigned long long v = 0;
-  CK(c, hipMemcpyAsync(&v, c->d_count, sizeof(v), hipMemcpyDeviceToHost, c->stream));
-  CK(c, hipStreamSynchronize(c->stream));
-  CK(c, hipGetLastError());
-  *n_ties = (size_t)v;
-  return CILHIP_OK;
-}
-
-struct cilhip_tie_order { std::vector<uint32_t> leaf, slot; std::vector<cilhip::TieNode> nodes; uint32_t n = 0; int max_depth = 0; };
-int cilhip_tie_order_create(const float* xyz, size_t n, cilhip_tie_order** out) {
-  if (!out || (n && !xyz) || n >= 0xFFFFFFF0ull) return CILHIP_ERR_INVALID;
-  *out = nullptr;
-  int ndev = 0, dev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipGetDevice(&dev) != hipSuccess) return CILHIP_ERR_NO_DEVICE;      // (built on the device: no CPU fallback)
-  cilhip_tie_order* o = nullptr;
-  DevBuf<float> d_xyz;
-  DevBuf<uint32_t> d_leaf, d_slot;
-  DevBuf<uint4> d_nodes;
-  size_t n_nodes = 0;
-  StreamGuard s;      // (declared last: drained and destroyed before the buffers go)
-  hipError_t e = hipSuccess;
-  int rc = CILHIP_OK;
-  try {
-    o = new cilhip_tie_order();
-    o->n = (uint32_t)n;
-    o->leaf.assign(n, 0u); o->slot.assign(n, 0u);
-    if (n) {
-      e = s.create();
-      if (e == hipSuccess) e = d_xyz.alloc(n * 3);
-      if (e == hipSuccess) e = d_leaf.alloc(n);
-      if (e == hipSuccess) e = d_slot.alloc(n);
-      if (e == hipSuccess) e = hipMemcpyAsync(d_xyz, xyz, n * 3 * sizeof(float), hipMemcpyHostToDevice, s);
-      if (e == hipSuccess) e = tie_order_build_device(d_xyz, nullptr, (uint32_t)n, s, d_leaf, d_slot, &d_nodes, &n_nodes, &o->max_depth);
-      if (e == hipSuccess) { o->nodes.resize(n_nodes); e = hipMemcpyAsync(o->nodes.data(), d_nodes, n_nodes * sizeof(uint4), hipMemcpyDeviceToHost, s); }
-      if (e == hipSuccess) e = hipMemcpyAsync(o->leaf.data(), d_leaf, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-      if (e == hipSuccess) e = hipMemcpyAsync(o->slot.data(), d_slot, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-      if (e == hipSuccess) e = hipStreamSynchronize(s);
-    }
-  } catch (...) { rc = CILHIP_ERR_HIP; }      // (out of host memory: never across the C boundary)
-  if (e != hipSuccess) rc = CILHIP_ERR_HIP;
-  if (rc != CILHIP_OK) { delete o; return rc; }
-  *out = o;
-  return CILHIP_OK;
-}
-void cilhip_tie_order_destroy(cilhip_tie_order* order) { delete order; }
-int cilhip_tie_order_tables(const cilhip_tie_order* o, uint32_t* leaf_by_index, uint32_t* slot_by_index, void* nodes_out, size_t nodes_cap, size_t* n_nodes, int* max_depth) {
-  if (!o) return CILHIP_ERR_INVALID;
-  if (leaf_by_index && o->n) memcpy(leaf_by_index, o->leaf.data(), (size_t)o->n * sizeof(uint32_t));
-  if (slot_by_index && o->n) memcpy(slot_by_index, o->slot.data(), (size_t)o->n * sizeof(uint32_t));
-  if (nodes_out && nodes_cap) memcpy(nodes_out, o->nodes.data(), std::min(nodes_cap, o->nodes.size()) * sizeof(cilhip::TieNode));
-  if (n_nodes) *n_nodes = o->nodes.size();
-  if (max_depth) *max_depth = o->max_depth;
-  return CILHIP_OK;
-}
-int cilhip_load_tie_order(cilhip_ctx* c, const cilhip_tie_order* order, const uint32_t* global_index) {
-  if (!c || !order) return CILHIP_ERR_INVALID;
-  if (!c->has_target) return fail(c, CILHIP_ERR_INVALID, "load_tie_order: set_target first");
-  const uint32_t n = c->grid.n, N = order->n;
-  if (n == 0) return load_tie_tables(c, nullptr, nullptr, order->nodes.data(), order->nodes.size());      // (a shard without target points)
-  if (!global_index) {
-    if (n != N) return fail(c, CILHIP_ERR_INVALID, "load_tie_order: the order was built for a cloud of another size (pass global_index for a part of it)");
-    return load_tie_tables(c, order->leaf.data(), order->slot.data(), order->nodes.data(), order->nodes.size());
-  }
-  try {
-    std::vector<uint32_t> leaf(n ? n : 1), slot(n ? n : 1);
-    for (uint32_t i = 0; i < n; ++i) {
-      if (global_index[i] >= N) return fail(c, CILHIP_ERR_INVALID, "load_tie_order: global index out of range");
-      leaf[i] = order->leaf[global_index[i]]; slot[i] = order->slot[global_index[i]];
-    }
-    return load_tie_tables(c, leaf.data(), slot.data(), order->nodes.data(), order->nodes.size());
-  } catch (...) { return fail(c, CILHIP_ERR_HIP, "load_tie_order: out of host memory"); }
-}
-int cilhip_build_tie_order(cilhip_ctx* c) {
-  if (!c) return CILHIP_ERR_INVALID;
-  if (!c->has_target) return fail(c, CILHIP_ERR_INVALID, "build_tie_order: set_target first");
-  if (c->partial_target) return fail(c, CILHIP_ERR_INVALID, "build_tie_order: this context holds a PART of a target (cilhip_set_shard_info): the order is the whole cloud's -- cilhip_tie_order_create + cilhip_load_tie_order");
-  return build_tie_tables(c);
-}
-int cilhip_get_tie_order_info(cilhip_ctx* c, cilhip_tie_order_info* out) {
-  if (!c || !out) return CILHIP_ERR_INVALID;
-  CK(c, hipSetDevice(c->device));
-  unsigned int cnt[4];
-  { const int rc = read_tie_counters(c, cnt); if (rc) return rc; }
-  out->loaded = (feat6(c) ? c->d_tief_leaf_slot != nullptr : c->d_tie_leaf_slot != nullptr) ? 1 : 0; out->builds = c->tie_builds + c->tief_builds; out->build_ms = c->tie_build_ms; out->pending = cnt[0];
-  return CILHIP_OK;
-}
-
-int cilhip_get_tie_rule_stats(cilhip_ctx* c, size_t* tied_queries, size_t* repointed) {
-  if (!c) return CILHIP_ERR_INVALID;
-  CK(c, hipSetDevice(c->device));
-  unsigned int cnt[4];
-  { const int rc = read_tie_counters(c, cnt); if (rc) return rc; }
-  if (tied_queries) *tied_queries = (size_t)cnt[1] + (size_t)cnt[0] + (size_t)cnt[3];      // (settled from tables + met without them, forward and reverse)
-  if (repointed) *repointed = (size_t)cnt[2];
   return CILHIP_OK;
 }
 
@@ -1332,415 +867,6 @@ static int get_correspondences_impl(cilhip_ctx* c, uint64_t* i1, uint64_t* i2, f
   return CILHIP_OK;
 }
 
-static void pack_T(const double L[9], const double t[3], float T[16]) {
-  for (int i = 0; i < 16; ++i) T[i] = 0.f;
-  T[15] = 1.f;
-  for (int r = 0; r < 3; ++r) { for (int cc = 0; cc < 3; ++cc) T[cc * 4 + r] = (float)L[r * 3 + cc]; T[12 + r] = (float)t[r]; }
-}
-
-// ---- a caller's own weight evaluators -----------------------------------------------------------------------------------------
-// The reference's combined-metric classes take their evaluators as template arguments (icp_single_transform_combined_metric.hpp:10-14)
-// and the estimators call them per correspondence: evaluator(corr.indexInFirst, corr.indexInSecond, corr.value)
-// (transform_estimation.hpp:303, :332, :432, :453).  A functor cannot cross a C boundary onto the device; with a callback set, every
-// estimate brings the stored correspondence set to the host, lets the callback fill both weights of every pair, and the accumulation
-// pass reads them from tables (CorrWeights::point_table) instead of evaluating a kind.  Stored order: ascending source index
-// (SECOND_TO_FIRST), or the pair list's (first, second).
-static int prepare_pair_weights_impl(cilhip_ctx* c);
-static int prepare_pair_weights(cilhip_ctx* c) {
-  if (!c->weight_fn) return CILHIP_OK;
-  // (host vectors of the size of the correspondence set: an allocation failure must not cross the C boundary; neither may whatever a
-  //  C++ callback lets escape)
-  try {
-    return prepare_pair_weights_impl(c);
-  } catch (const std::bad_alloc&) {
-    return fail(c, CILHIP_ERR_HIP, "pair-weight callback: out of host memory for the correspondence set");
-  } catch (...) {
-    return fail(c, CILHIP_ERR_INVALID, "pair-weight callback: an exception escaped the callback");
-  }
-}
-static int prepare_pair_weights_impl(cilhip_ctx* c) {
-  const bool pairs = c->have_pairs;
-  const size_t slots = pairs ? c->pairs.count : c->ns;      // stream positions
-  if (2 * slots > c->d_wtab.capacity() || !c->d_wtab || !c->d_wtab_in) {
-    c->d_wtab.reset(); c->d_wtab_in.reset();
-    const size_t cap = slots ? slots : 1;
-    CK(c, c->d_wtab.alloc(2 * cap));
-    CK(c, c->d_wtab_in.alloc(2 * cap));
-  }
-  const size_t half = c->d_wtab.capacity() / 2;      // the plane weights' table follows the point weights' (corr_weights_of)
-  if (slots == 0) return CILHIP_OK;
-  std::vector<uint64_t> i1(slots), i2(slots);
-  std::vector<float> val(slots), wq(slots, 0.0f), wl(slots, 0.0f);
-  size_t cnt = 0;
-  if (pairs) {
-    std::vector<uint32_t> f(slots), sc(slots);
-    CK(c, hipMemcpyAsync(f.data(), c->pairs.first, slots * 4, hipMemcpyDeviceToHost, c->stream));
-    CK(c, hipMemcpyAsync(sc.data(), c->pairs.second, slots * 4, hipMemcpyDeviceToHost, c->stream));
-    CK(c, hipMemcpyAsync(val.data(), c->pairs.d2, slots * 4, hipMemcpyDeviceToHost, c->stream));
-    CK(c, hipStreamSynchronize(c->stream));
-    for (size_t k = 0; k < slots; ++k) { i1[k] = f[k]; i2[k] = sc[k]; }
-    cnt = slots;
-  } else {
-    std::vector<uint32_t> idx(slots);
-    std::vector<float> d2(slots);
-    const int rc = cilhip_get_nn(c, idx.data(), d2.data(), CILHIP_MEM_HOST);
-    if (rc) return rc;
-    for (size_t i = 0; i < slots; ++i)
-      if (idx[i] != NONE_U32) { i1[cnt] = idx[i]; i2[cnt] = i; val[cnt] = d2[i]; ++cnt; }
-  }
-  if (cnt) c->weight_fn(c->weight_user, i1.data(), i2.data(), val.data(), cnt, wq.data(), wl.data());
-  if (pairs) {
-    CK(c, hipMemcpyAsync(c->d_wtab, wq.data(), slots * 4, hipMemcpyHostToDevice, c->stream));
-    CK(c, hipMemcpyAsync(c->d_wtab + half, wl.data(), slots * 4, hipMemcpyHostToDevice, c->stream));
-  } else {
-    // by original source index (unmatched: 0, never read), then into the sorted order the pass streams over
-    std::vector<float> oq(slots, 0.0f), ol(slots, 0.0f);
-    for (size_t k = 0; k < cnt; ++k) { oq[i2[k]] = wq[k]; ol[i2[k]] = wl[k]; }
-    CK(c, hipMemcpyAsync(c->d_wtab_in, oq.data(), slots * 4, hipMemcpyHostToDevice, c->stream));
-    CK(c, hipMemcpyAsync(c->d_wtab_in + half, ol.data(), slots * 4, hipMemcpyHostToDevice, c->stream));
-    launch_gather1_by_w(c->d_src_sorted, c->d_wtab_in, (uint32_t)slots, c->d_wtab, c->stream);
-    launch_gather1_by_w(c->d_src_sorted, c->d_wtab_in + half, (uint32_t)slots, c->d_wtab + half, c->stream);
-  }
-  CK(c, hipStreamSynchronize(c->stream));      // (the host vectors go out of scope)
-  return CILHIP_OK;
-}
-
-// Accumulate over the stored matches (transform = nn_T) and bring the reduced sums to the host.
-static int accumulate_stored(cilhip_ctx* c, int metric, const double innerL[9], const double innert[3], double sums[SUMS_MAX],
-                             const CorrWeights* cw = nullptr) {
-  IcpState hs;
-  launch_init_state(c->d_state, c->nn_T, c->src_mean, c->stream);
-  if (innerL) {
-    CK(c, hipMemcpyAsync(&hs, c->d_state, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
-    CK(c, hipStreamSynchronize(c->stream));
-    for (int i = 0; i < 9; ++i) { hs.innerL[i] = (float)innerL[i]; hs.dLd[i] = innerL[i]; }
-    for (int i = 0; i < 3; ++i) { hs.innert[i] = (float)innert[i]; hs.dtd[i] = innert[i]; }
-    CK(c, hipMemcpyAsync(c->d_state, &hs, sizeof(hs), hipMemcpyHostToDevice, c->stream));
-  }
-  IterArgs a = make_iter_args(c, 0.0f);
-  if (cw) a.cw = *cw;
-  // (a pair list -- FIRST_TO_SECOND / BOTH -- carries its own view of the source, per pair)
-  if (c->have_pairs) {
-    a.src = c->pairs.src_view; a.ns = c->pairs.count; a.nn_pos = c->pairs.posd; a.nn_d2 = c->pairs.d2;
-    a.src_nrm = (c->d_src_nrm && c->symmetric) ? c->pairs.nrm_view : nullptr;
-  }
-  const int nb = iter_num_blocks(a.ns);
-  for (int i = 0; i < SUMS_MAX; ++i) sums[i] = 0.0;
-  if (a.ns == 0) return CILHIP_OK;
-  const int grc = ensure_partial_rows(c, (size_t)nb);
-  if (grc) return grc;
-  a.partials = c->d_partials;
-  launch_iter(a, metric, false, false, nb, c->stream);
-  launch_reduce_partials(c->d_partials, nb, c->d_stage, c->d_sums, c->stream);
-  CK(c, hipGetLastError());
-  CK(c, hipMemcpyAsync(sums, c->d_sums, SUMS_MAX * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  CK(c, hipStreamSynchronize(c->stream));
-  return CILHIP_OK;
-}
-
-int cilhip_estimate_point_to_point(cilhip_ctx* c, float dT[16], double* sums_out, int* ok) {
-  if (!c || !dT) return CILHIP_ERR_INVALID;
-  { const int prc = materialize_pending(c); if (prc) return prc; }
-  if (!c->have_nn) return fail(c, CILHIP_ERR_INVALID, "estimate: run find_correspondences first");
-  CK(c, hipSetDevice(c->device));
-  double sums[SUMS_MAX];
-  int rc = accumulate_stored(c, IM_KABSCH, nullptr, nullptr, sums);
-  if (rc) return rc;
-  double L[9], t[3];
-  kabsch_from_sums(sums, L, t);
-  pack_T(L, t, dT);
-  if (sums_out) memcpy(sums_out, sums, 16 * sizeof(double));
-  if (ok) *ok = sums[0] >= 3.0;
-  return CILHIP_OK;
-}
-
-int cilhip_estimate_combined(cilhip_ctx* c, float w_p2p, float w_p2pl, size_t max_iter, float conv_tol, float dT[16],
-                             double* AtA_out, double* Atb_out, int* converged) {
-  if (!c || !dT) return CILHIP_ERR_INVALID;
-  { const int prc = materialize_pending(c); if (prc) return prc; }
-  if (!c->have_nn && !c->have_pairs) return fail(c, CILHIP_ERR_INVALID, "estimate: run find_correspondences first");
-  CK(c, hipSetDevice(c->device));
-  { const int wrc = prepare_pair_weights(c); if (wrc) return wrc; }
-  double L[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0};
-  memcpy(dT, kIdentity16, sizeof(kIdentity16));
-  if (converged) *converged = 0;
-  if (AtA_out) for (int i = 0; i < 36; ++i) AtA_out[i] = 0.0;
-  if (Atb_out) for (int i = 0; i < 6; ++i) Atb_out[i] = 0.0;
-  const bool wp = w_p2p > 0.0f, wl = w_p2pl > 0.0f;
-  if (!wp && !wl) return CILHIP_OK;                      // transform_estimation.hpp:264-272
-  if (wl && !c->has_normals) return CILHIP_OK;           // dst_p.cols() != dst_n.cols() -> identity, false
-  const int metric = (wp && wl) ? IM_BOTH : (wl ? IM_PLANE : IM_POINT);
-  float smt[3];
-  transform_point(c->nn_T, c->src_mean[0], c->src_mean[1], c->src_mean[2], smt[0], smt[1], smt[2]);
-  int conv = 0;
-  const CorrWeights cw = corr_weights_of(c, true, w_p2p, w_p2pl);
-  if (max_iter == 0) {      // the loop body never runs; "no usable terms" (no correspondences) still means identity (:264-272)
-    double sums[SUMS_MAX];
-    const int rc = accumulate_stored(c, metric, L, t, sums, &cw);
-    if (rc) return rc;
-    if (!(sums[0] > 0.0)) return CILHIP_OK;
-  }
-  for (size_t it = 0; it < max_iter; ++it) {
-    double sums[SUMS_MAX];
-    int rc = accumulate_stored(c, metric, L, t, sums, &cw);
-    if (rc) return rc;
-    if (!(sums[0] > 0.0)) return CILHIP_OK;              // no correspondences: identity
-    double AtA[36], Atb[6], dth[6];
-    if (cw.enabled) gn_normal_equations(sums, wp ? 1.0 : 0.0, wl ? 1.0 : 0.0, AtA, Atb, true);   // (metric weights inside the per-pair weights)
-    else gn_normal_equations(sums, wp ? (double)w_p2p : 0.0, wl ? (double)w_p2pl : 0.0, AtA, Atb);
-    if (it == 0) {
-      if (AtA_out) memcpy(AtA_out, AtA, sizeof(AtA));
-      if (Atb_out) memcpy(Atb_out, Atb, sizeof(Atb));
-    }
-    ldlt6_solve(AtA, Atb, dth);
-    rigid_gn_update(dth, L, t);
-    double nrm = 0.0;
-    for (int i = 0; i < 6; ++i) nrm += dth[i] * dth[i];
-    if (std::sqrt(nrm) < (double)conv_tol) { conv = 1; break; }
-  }
-  double tt[3];
-  for (int r = 0; r < 3; ++r)
-    tt[r] = t[r] - (L[r * 3] * (double)smt[0] + L[r * 3 + 1] * (double)smt[1] + L[r * 3 + 2] * (double)smt[2]) + (double)c->dst_mean[r];
-  pack_T(L, tt, dT);
-  if (converged) *converged = conv;
-  return CILHIP_OK;
-}
-
-// ---- two correspondence sets in one combined-metric estimate: CorrespondenceSearchCombinedMetricCombiner -------------
-// (registration/correspondence_search_combined_metric_combiner.hpp:8-81: the point-to-point terms read one engine's
-//  correspondences, the point-to-plane terms another's -- other radius, features, filters -- over the same two clouds.)
-// Each context accumulates its own block of the sums over its own stored matches (the point block, slots [28, 44), on
-// c_point; the plane block, slots [0, 28), on c_plane); the normal equations are assembled from the two.
-static int combined_two_sets_step(cilhip_ctx* cp, cilhip_ctx* cl, bool wp, bool wl, float w_p2p, float w_p2pl, const double L[9], const double t[3],
-                                  double sums[SUMS_MAX], bool* weighted_out) {
-  CorrWeights cwp = corr_weights_of(cp, true, w_p2p, w_p2pl), cwl = corr_weights_of(cl, true, w_p2p, w_p2pl);
-  const bool any = cwp.enabled || cwl.enabled;      // (some evaluator is not Unity: both blocks then carry their metric weight per pair)
-  cwp.enabled = cwl.enabled = any ? 1 : 0;
-  *weighted_out = any;
-  for (int i = 0; i < SUMS_MAX; ++i) sums[i] = 0.0;
-  double s1[SUMS_MAX], s2[SUMS_MAX];
-  if (wp) {
-    CK(cp, hipSetDevice(cp->device));
-    const int rc = accumulate_stored(cp, IM_POINT, L, t, s1, &cwp);
-    if (rc) return rc;
-    for (int i = 28; i < 44; ++i) sums[i] = s1[i];
-    if (!(s1[0] > 0.0)) sums[43] = 0.0;
-  }
-  if (wl) {
-    CK(cl, hipSetDevice(cl->device));
-    const int rc = accumulate_stored(cl, IM_PLANE, L, t, s2, &cwl);
-    if (rc) { if (cl != cp) cp->err = cl->err; return rc; }
-    for (int i = 0; i < 28; ++i) sums[i] = s2[i];
-  }
-  // slot 0 = the plane set's count; the point set's count travels in slot 43 (sum of the unit weights) -- keep a copy where
-  // the caller can tell "no point correspondences" from "no plane correspondences"
-  sums[44] = wp ? s1[0] : 0.0;
-  return CILHIP_OK;
-}
-
-int cilhip_estimate_combined_two_sets(cilhip_ctx* cp, cilhip_ctx* cl, float w_p2p, float w_p2pl, size_t max_iter, float conv_tol, float dT[16],
-                                      int* converged) {
-  if (!cp || !cl || !dT) return CILHIP_ERR_INVALID;
-  static_assert(SUMS_MAX >= 45, "slot 44 carries the point set's count");
-  { int prc = materialize_pending(cp); if (prc) return prc; prc = materialize_pending(cl); if (prc) { cp->err = cl->err; return prc; } }
-  if (!cp->have_nn || !cl->have_nn)
-    return fail(cp, CILHIP_ERR_INVALID, "estimate (two sets): both engines need stored SECOND_TO_FIRST correspondences (find_correspondences first)");
-  if (memcmp(cp->nn_T, cl->nn_T, sizeof(cp->nn_T)) != 0) return fail(cp, CILHIP_ERR_INVALID, "estimate (two sets): the two engines searched under different transforms");
-  if (cp->ns != cl->ns || cp->grid.n != cl->grid.n) return fail(cp, CILHIP_ERR_INVALID, "estimate (two sets): the two engines hold different clouds");
-  { int wrc = prepare_pair_weights(cp); if (wrc) return wrc; if (cl != cp) { wrc = prepare_pair_weights(cl); if (wrc) { cp->err = cl->err; return wrc; } } }
-  double L[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0};
-  memcpy(dT, kIdentity16, sizeof(kIdentity16));
-  if (converged) *converged = 0;
-  bool wp = w_p2p > 0.0f, wl = w_p2pl > 0.0f;
-  if (!wp && !wl) return CILHIP_OK;                      // transform_estimation.hpp:264-272
-  float smt[3];
-  transform_point(cp->nn_T, cp->src_mean[0], cp->src_mean[1], cp->src_mean[2], smt[0], smt[1], smt[2]);
-  int conv = 0;
-  const size_t steps = max_iter ? max_iter : 1;          // (max_iter 0: one pass for the "no usable terms" test only)
-  for (size_t it = 0; it < steps; ++it) {
-    double sums[SUMS_MAX];
-    bool weighted_sums = false;
-    const int rc = combined_two_sets_step(cp, cl, wp, wl, w_p2p, w_p2pl, L, t, sums, &weighted_sums);
-    if (rc) return rc;
-    const bool has_p2p = wp && sums[44] > 0.0, has_p2pl = wl && sums[0] > 0.0;     // :264-267
-    if ((!has_p2p && !has_p2pl) || (has_p2pl && !cl->has_normals)) return CILHIP_OK;   // :269-272: identity, false
-    if (max_iter == 0) break;
-    double AtA[36], Atb[6], dth[6];
-    if (weighted_sums) gn_normal_equations(sums, has_p2p ? 1.0 : 0.0, has_p2pl ? 1.0 : 0.0, AtA, Atb, true);
-    else gn_normal_equations(sums, has_p2p ? (double)w_p2p : 0.0, has_p2pl ? (double)w_p2pl : 0.0, AtA, Atb, true);
-    ldlt6_solve(AtA, Atb, dth);
-    rigid_gn_update(dth, L, t);
-    double nrm = 0.0;
-    for (int i = 0; i < 6; ++i) nrm += dth[i] * dth[i];
-    if (std::sqrt(nrm) < (double)conv_tol) { conv = 1; break; }
-  }
-  double tt[3];
-  for (int r = 0; r < 3; ++r)
-    tt[r] = t[r] - (L[r * 3] * (double)smt[0] + L[r * 3 + 1] * (double)smt[1] + L[r * 3 + 2] * (double)smt[2]) + (double)cp->dst_mean[r];
-  pack_T(L, tt, dT);
-  if (converged) *converged = conv;
-  return CILHIP_OK;
-}
-
-// CombinedMetricSingleTransformICP over a Combiner (icp_single_transform_combined_metric.hpp:169-217 with the engine of
-// correspondence_search_combined_metric_combiner.hpp): per iteration both engines search under the current transform (each with
-// its own radius and options), the estimator reads the two sets, the instance class composes and tests the update norm.
-// Host-driven: a few synchronisations per iteration -- this is the reference's thin combination class, not the hot path.
-int cilhip_icp_run_two_sets(cilhip_ctx* cp, float max_sq_point, cilhip_ctx* cl, float max_sq_plane, const cilhip_icp_params* p, const float* T0,
-                            cilhip_icp_result* out) {
-  if (!cp || !cl || !p || !out) return CILHIP_ERR_INVALID;
-  if (p->metric != CILHIP_METRIC_COMBINED) return fail(cp, CILHIP_ERR_INVALID, "icp_run (two sets): the combined metric is what takes two correspondence sets");
-  if (cp->transform_mode != 0 || cl->transform_mode != 0) return fail(cp, CILHIP_ERR_UNSUPPORTED, "icp_run (two sets): rigid transforms");
-  if (cp->search_dir != 0 || cl->search_dir != 0) return fail(cp, CILHIP_ERR_UNSUPPORTED, "icp_run (two sets): SECOND_TO_FIRST engines");
-  if (cp->proj_on || cl->proj_on) return fail(cp, CILHIP_ERR_UNSUPPORTED, "projective search: cilhip_icp_run_two_sets is not available");
-  float T[16];
-  memcpy(T, T0 ? T0 : kIdentity16, sizeof(T));
-  memcpy(out->T, T, sizeof(T));
-  out->iterations = 0; out->last_delta_norm = INFINITY; out->last_ncorr = 0;
-  for (size_t it = 0; it < p->max_iter; ++it) {
-    size_t n1 = 0, n2 = 0;
-    int rc = cilhip_find_correspondences(cp, T, max_sq_point, &n1);
-    if (rc) return rc;
-    if (cl != cp) { rc = cilhip_find_correspondences(cl, T, max_sq_plane, &n2); if (rc) { cp->err = cl->err; return rc; } } else n2 = n1;
-    float dT[16];
-    int conv = 0;
-    rc = cilhip_estimate_combined_two_sets(cp, cl, p->w_p2p, p->w_p2pl, p->max_opt_iter, p->opt_conv_tol, dT, &conv);
-    if (rc) return rc;
-    double L[9], t[3];
-    for (int r = 0; r < 3; ++r) { for (int k = 0; k < 3; ++k) L[r * 3 + k] = (double)dT[k * 4 + r]; t[r] = (double)dT[12 + r]; }
-    float Tn[16];
-    const float delta = compose_update(L, t, T, Tn);      // rotation() polish, transform_ = tform_iter * transform_, update norm (:207-216)
-    memcpy(T, Tn, sizeof(T));
-    out->iterations = it + 1; out->last_delta_norm = delta; out->last_ncorr = n1 > n2 ? n1 : n2;
-    if (delta < p->conv_tol) break;                       // icp_base.hpp:83
-  }
-  memcpy(out->T, T, sizeof(T));
-  return CILHIP_OK;
-}
-
-// ---- affine variants: SimpleCombinedMetricAffineICP3f / SimplePointToPointMetricAffineICP3f ---------------------------
-// Moments of the 12-unknown normal equations over the stored correspondences (matches or pair list), three streaming
-// passes on the device, one copy to the host.
-static int affine_accumulate(cilhip_ctx* c, bool centered, bool plane, double sums[3 * SUMS_MAX], const CorrWeights* cw = nullptr) {
-  for (int i = 0; i < 3 * SUMS_MAX; ++i) sums[i] = 0.0;
-  launch_init_state(c->d_state, c->nn_T, c->src_mean, c->stream);
-  IterArgs a = make_iter_args(c, 0.0f);
-  if (cw) a.cw = *cw;
-  // (a pair list carries its own values, per pair)
-  if (c->have_pairs) { a.src = c->pairs.src_view; a.ns = c->pairs.count; a.nn_pos = c->pairs.posd; a.nn_d2 = c->pairs.d2; }
-  a.src_nrm = nullptr;   // (the symmetric metric exists for the rigid classes only)
-  a.no_centering = centered ? 0 : 1;
-  if (a.ns == 0) return CILHIP_OK;
-  const int nb = iter_num_blocks(a.ns);
-  const int grc = ensure_partial_rows(c, (size_t)nb);
-  if (grc) return grc;
-  a.partials = c->d_partials;
-  const int passes[3] = {IM_AFF0, IM_AFF1, IM_AFF2};
-  const int np = plane ? 3 : 1;
-  for (int k = 0; k < np; ++k) {
-    launch_iter(a, passes[k], false, false, nb, c->stream);
-    launch_reduce_partials(c->d_partials, nb, c->d_stage, c->d_sums + k * SUMS_MAX, c->stream);
-  }
-  CK(c, hipGetLastError());
-  CK(c, hipMemcpyAsync(sums, c->d_sums, (size_t)np * SUMS_MAX * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  CK(c, hipStreamSynchronize(c->stream));
-  return CILHIP_OK;
-}
-
-int cilhip_estimate_affine(cilhip_ctx* c, float w_p2p, float w_p2pl, int centered, float dT[16], double* AtA_out,
-                           double* Atb_out, size_t* n_corr, int* ok) {
-  if (!c || !dT) return CILHIP_ERR_INVALID;
-  { const int prc = materialize_pending(c); if (prc) return prc; }
-  if (!c->have_nn && !c->have_pairs) return fail(c, CILHIP_ERR_INVALID, "estimate: run find_correspondences first");
-  CK(c, hipSetDevice(c->device));
-  memcpy(dT, kIdentity16, sizeof(kIdentity16));
-  if (ok) *ok = 0;
-  if (n_corr) *n_corr = 0;
-  if (AtA_out) for (int i = 0; i < 144; ++i) AtA_out[i] = 0.0;
-  if (Atb_out) for (int i = 0; i < 12; ++i) Atb_out[i] = 0.0;
-  const bool wp = w_p2p > 0.0f, wl = w_p2pl > 0.0f;
-  if (!wp && !wl) return CILHIP_OK;                      // transform_estimation.hpp:400-409
-  if (wl && !c->has_normals) return CILHIP_OK;           // dst_p.cols() != dst_n.cols() -> identity, false
-  double sums[3 * SUMS_MAX];
-  // weight evaluators (the combined-metric class only: `centered` distinguishes it from the point-to-point class here)
-  if (centered) { const int wrc = prepare_pair_weights(c); if (wrc) return wrc; }
-  const CorrWeights cw = corr_weights_of(c, centered != 0, w_p2p, w_p2pl);
-  const int rc = affine_accumulate(c, centered != 0, wl, sums, &cw);
-  if (rc) return rc;
-  const double n = sums[0];
-  if (n_corr) *n_corr = (size_t)n;
-  if (!(n > 0.0)) return CILHIP_OK;                      // no correspondences: identity, false
-  double AtA[144], Atb[12], th[12];
-  if (cw.enabled) affine_normal_equations(sums, sums + SUMS_MAX, sums + 2 * SUMS_MAX, wp ? 1.0 : 0.0, wl ? 1.0 : 0.0, AtA, Atb, true);      // (metric weights inside the per-pair weights)
-  else affine_normal_equations(sums, sums + SUMS_MAX, sums + 2 * SUMS_MAX, wp ? (double)w_p2p : 0.0, wl ? (double)w_p2pl : 0.0, AtA, Atb);
-  if (AtA_out) memcpy(AtA_out, AtA, sizeof(AtA));
-  if (Atb_out) memcpy(Atb_out, Atb, sizeof(Atb));
-  ldlt_solve_n(12, AtA, Atb, th);                        // :468 AtA.ldlt().solve(Atb)
-  double L[9], t[3];
-  for (int i = 0; i < 9; ++i) L[i] = th[i];              // :470-472 row-major linear part, then the translation
-  for (int i = 0; i < 3; ++i) t[i] = th[9 + i];
-  if (centered) {                                        // :473 tform = t_dst * tform * t_src
-    float smt[3];
-    transform_point(c->nn_T, c->src_mean[0], c->src_mean[1], c->src_mean[2], smt[0], smt[1], smt[2]);
-    for (int r = 0; r < 3; ++r)
-      t[r] = t[r] - (L[r * 3] * (double)smt[0] + L[r * 3 + 1] * (double)smt[1] + L[r * 3 + 2] * (double)smt[2]) + (double)c->dst_mean[r];
-  }
-  pack_T(L, t, dT);
-  if (ok) *ok = ((wp ? 1.0 : 0.0) + (wl ? 1.0 : 0.0)) * n >= 4.0;
-  return CILHIP_OK;
-}
-
-// icp_base.hpp:68-87 with the affine updateEstimate() (icp_single_transform_point_to_point_metric.hpp:46-65,
-// icp_single_transform_combined_metric.hpp:173-217 without the rotation() polish): host-driven, one 12x12 solve per iteration.
-int cilhip::icp_run_affine(cilhip_ctx* c, const cilhip_icp_params* p, const float* T0, cilhip_icp_result* out) {
-  float T[16];
-  memcpy(T, T0 ? T0 : kIdentity16, sizeof(T));
-  float delta = INFINITY;
-  size_t it = 0, ncorr = 0;
-  hipEvent_t e_beg = event_at(c->ev, 0), e_end = event_at(c->ev, 1);
-  CK(c, hipEventRecord(e_beg, c->stream));
-  while (it < p->max_iter) {
-    int rc = cilhip_find_correspondences(c, T, p->max_sq_dist, nullptr);
-    if (rc) return rc;
-    float dT[16];
-    if (p->metric == CILHIP_METRIC_POINT_TO_POINT) rc = cilhip_estimate_affine(c, 1.0f, 0.0f, 0, dT, nullptr, nullptr, &ncorr, nullptr);
-    else rc = cilhip_estimate_affine(c, p->w_p2p, p->w_p2pl, 1, dT, nullptr, nullptr, &ncorr, nullptr);
-    if (rc) return rc;
-    float Tn[16] = {0};
-    Tn[15] = 1.0f;                                       // transform_ = tform_iter * transform_ (f32, Eigen affine product)
-    for (int r = 0; r < 3; ++r) {
-      for (int cc = 0; cc < 3; ++cc) Tn[cc * 4 + r] = dT[0 * 4 + r] * T[cc * 4 + 0] + dT[1 * 4 + r] * T[cc * 4 + 1] + dT[2 * 4 + r] * T[cc * 4 + 2];
-      Tn[12 + r] = (dT[0 * 4 + r] * T[12] + dT[1 * 4 + r] * T[13] + dT[2 * 4 + r] * T[14]) + dT[12 + r];
-    }
-    memcpy(T, Tn, sizeof(T));
-    float dn = 0.0f;
-    for (int r = 0; r < 3; ++r)
-      for (int cc = 0; cc < 3; ++cc) { const float v = dT[cc * 4 + r] - (r == cc ? 1.0f : 0.0f); dn += v * v; }
-    for (int r = 0; r < 3; ++r) dn += dT[12 + r] * dT[12 + r];
-    delta = std::sqrt(dn);
-    ++it;
-    if (delta < p->conv_tol) break;
-  }
-  CK(c, hipEventRecord(e_end, c->stream));
-  CK(c, hipStreamSynchronize(c->stream));
-  memcpy(out->T, T, sizeof(T));
-  out->iterations = it;
-  out->last_delta_norm = delta;
-  out->last_ncorr = ncorr;
-  // (the last iteration's cilhip_find_correspondences left the set it estimated from: what getCorrespondences() returns)
-  if (it == 0) { drop_matches(c); c->have_pairs = false; } else c->matches_origin = 1;
-  float ms = 0.f;
-  CK(c, hipEventElapsedTime(&ms, e_beg, e_end));
-  c->last_loop_ms = ms; c->last_search_ms = 0.0; c->last_acc_ms = 0.0; c->last_search_launches = 0;
-  return CILHIP_OK;
-}
-
-int cilhip_set_pair_weight_callback(cilhip_ctx* c, cilhip_pair_weight_fn fn, void* user) {
-  if (!c) return CILHIP_ERR_INVALID;
-  c->weight_fn = fn; c->weight_user = fn ? user : nullptr;
-  return CILHIP_OK;
-}
-
 void cilhip_icp_default_params(cilhip_icp_params* p) {
   if (!p) return;
   p->metric = CILHIP_METRIC_COMBINED;
@@ -1748,160 +874,6 @@ void cilhip_icp_default_params(cilhip_icp_params* p) {
   p->max_iter = 15; p->conv_tol = 1e-5f;
   p->max_opt_iter = 1; p->opt_conv_tol = 1e-5f;
   p->max_sq_dist = 0.01f * 0.01f;
-}
-
-int cilhip_set_shard_info(cilhip_ctx* c, uint64_t target_index_offset, const float* dst_mean, const float* src_mean) {
-  if (!c) return CILHIP_ERR_INVALID;
-  if (target_index_offset + (c->has_target ? c->grid.n : 0) > 0xFFFFFFFFull) return fail(c, CILHIP_ERR_INVALID, "global target indices must fit 32 bits");
-  c->index_offset = (uint32_t)target_index_offset;
-  c->partial_target = target_index_offset != 0 || dst_mean != nullptr;      // (the whole cloud's mean handed in: this target is a part of it)
-  if (dst_mean) memcpy(c->dst_mean, dst_mean, sizeof(c->dst_mean));
-  if (src_mean) memcpy(c->src_mean, src_mean, sizeof(c->src_mean));
-  return CILHIP_OK;
-}
-
-int cilhip_set_slab_guard(cilhip_ctx* c, int axis, float slack, const float center[3], const float half_extent[3], const float T_part[16]) {
-  if (!c) return CILHIP_ERR_INVALID;
-  if (axis < 0) { c->guard_axis = -1; return CILHIP_OK; }
-  if (axis > 2 || !center || !half_extent || !T_part || !(slack >= 0.0f)) return fail(c, CILHIP_ERR_INVALID, "set_slab_guard: axis 0..2, slack >= 0, box and transform required");
-  c->guard_axis = axis; c->guard_slack = slack;
-  memcpy(c->guard_center, center, sizeof(c->guard_center)); memcpy(c->guard_half, half_extent, sizeof(c->guard_half));
-  memcpy(c->guard_T, T_part, sizeof(c->guard_T));
-  return CILHIP_OK;
-}
-
-int cilhip_get_slab_violation(cilhip_ctx* c, int* out) {
-  if (!c || !out) return CILHIP_ERR_INVALID;
-  CK(c, hipSetDevice(c->device));
-  int v = 0;
-  CK(c, hipMemcpyAsync(&v, reinterpret_cast<const char*>(c->d_state.get()) + offsetof(IcpState, slab_violation), sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  CK(c, hipStreamSynchronize(c->stream));
-  *out = v;
-  return CILHIP_OK;
-}
-
-int cilhip_get_slab_violation_state(cilhip_ctx* c, int* violated, cilhip_icp_result* at) {
-  if (!c || !violated) return CILHIP_ERR_INVALID;
-  CK(c, hipSetDevice(c->device));
-  IcpState hs;
-  CK(c, hipMemcpyAsync(&hs, c->d_state, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
-  CK(c, hipStreamSynchronize(c->stream));
-  *violated = hs.slab_violation;
-  if (at) {
-    memcpy(at->T, hs.slab_violation ? hs.violation_T : hs.T, sizeof(hs.T));
-    at->iterations = (size_t)(hs.slab_violation ? hs.violation_iter : hs.iterations);
-    at->last_delta_norm = hs.slab_violation ? hs.violation_delta : hs.delta;
-    at->last_ncorr = (size_t)(hs.slab_violation ? hs.violation_ncorr : hs.ncorr);
-  }
-  return CILHIP_OK;
-}
-
-int cilhip_icp_partial_keys(cilhip_ctx* c, uint64_t* keys_dev) {
-  if (!c || !keys_dev) return CILHIP_ERR_INVALID;
-  if (!c->run_active) return fail(c, CILHIP_ERR_INVALID, "icp_begin first");
-  CK(c, hipSetDevice(c->device));
-  IterArgs a = make_iter_args(c, c->run_prm.max_sq_dist);
-  if (c->ns) {
-    if (c->grid.n == 0) CK(c, hipMemsetAsync(c->d_nn_pos, 0xFF, (size_t)c->ns * sizeof(uint32_t), c->stream));      // (a shard without target points: every key "none")
-    else if (use_tiled(c)) launch_search_tiled(a, IM_NONE, c->d_tiles, c->d_tile_center, c->d_tile_box, c->ntiles, c->stream);
-    else launch_iter(a, IM_NONE, true, true, iter_num_blocks(c->ns), c->stream);
-    launch_pack_keys(c->d_src_sorted, c->grid.pts, c->d_nn_pos, c->d_nn_d2, c->ns, c->index_offset,
-                     reinterpret_cast<unsigned long long*>(keys_dev), c->stream);
-  }
-  CK(c, hipGetLastError());
-  return CILHIP_OK;
-}
-
-// the sums over the matches a key exchange has just selected into nn_pos / nn_d2 (select: enqueues that selection)
-template <class Select>
-static int sums_of_selected(cilhip_ctx* c, double* sums_dev, Select select) {
-  const int im = iter_metric_of(c, &c->run_prm);
-  IterArgs a = make_iter_args(c, c->run_prm.max_sq_dist);
-  a.cw = corr_weights_of(c, &c->run_prm);
-  const int nb = iter_num_blocks(c->ns);
-  if (c->ns && c->grid.n) {
-    select();
-    launch_iter(a, im, false, false, nb, c->stream);
-    launch_reduce_partials(c->d_partials, nb, c->d_stage, sums_dev, c->stream);
-  } else {
-    CK(c, hipMemsetAsync(sums_dev, 0, SUMS_MAX * sizeof(double), c->stream));
-  }
-  CK(c, hipGetLastError());
-  return CILHIP_OK;
-}
-
-int cilhip_icp_sums_from_keys(cilhip_ctx* c, const uint64_t* keys_dev, double* sums_dev) {
-  if (!c || !keys_dev || !sums_dev) return CILHIP_ERR_INVALID;
-  if (!c->run_active) return fail(c, CILHIP_ERR_INVALID, "icp_begin first");
-  CK(c, hipSetDevice(c->device));
-  if (!c->d_inv_perm) {
-    CK(c, c->d_inv_perm.alloc(c->grid.n));
-    launch_inv_perm(c->grid.pts, c->grid.n, c->d_inv_perm, c->stream);
-  }
-  return sums_of_selected(c, sums_dev, [&] {
-    launch_keys_to_pos(c->d_src_sorted, reinterpret_cast<const unsigned long long*>(keys_dev), c->d_inv_perm, c->ns,
-                       c->index_offset, c->grid.n, c->d_nn_pos, c->d_nn_d2, c->stream,
-                       (tie_mode_on(c) && !c->d_tie_leaf_slot) ? c->d_tie_counters : nullptr); });
-}
-
-// The reference's tie order across target shards (extract.hip: tie_rank): after the MIN all-reduce of cilhip_icp_partial_keys' keys,
-//   cilhip_icp_order_keys(ctx, win_keys_dev, order_keys_dev)   order_keys_dev[i] = where this shard's match of source point i comes in
-//                                                              the query's traversal of the WHOLE target's tree, if it is at the
-//                                                              winning distance; 0x7fff...f otherwise
-//   all-reduce(MIN, 64-bit) of order_keys_dev                  -> the first-met point of the whole target
-//   cilhip_icp_sums_from_ordered_keys(ctx, win_keys_dev, order_keys_dev, sums_dev)   accumulates the pairs whose key came back
-// Needs the whole target's order tables on every shard (cilhip_load_tie_order with the shard's global indices).
-int cilhip_icp_order_keys(cilhip_ctx* c, const uint64_t* win_keys_dev, uint64_t* order_keys_dev) {
-  if (!c || !win_keys_dev || !order_keys_dev) return CILHIP_ERR_INVALID;
-  if (!c->run_active) return fail(c, CILHIP_ERR_INVALID, "icp_begin first");
-  if (!c->d_tie_leaf_slot) return fail(c, CILHIP_ERR_INVALID, "icp_order_keys: load the whole target's tie order first (cilhip_load_tie_order)");
-  if (c->tie_max_depth > 58) return fail(c, CILHIP_ERR_UNSUPPORTED, "icp_order_keys: the order tree is deeper than the 58 levels a traversal key holds");
-  CK(c, hipSetDevice(c->device));
-  if (!c->d_own_order) CK(c, c->d_own_order.alloc(c->ns));
-  TieDev t = tie_dev_of(c);
-  launch_order_keys(c->d_src_sorted, c->d_state, reinterpret_cast<const unsigned long long*>(win_keys_dev), c->d_nn_pos, c->d_nn_d2, c->ns, t,
-                    c->d_own_order, reinterpret_cast<unsigned long long*>(order_keys_dev), c->stream);
-  CK(c, hipGetLastError());
-  return CILHIP_OK;
-}
-
-int cilhip_icp_sums_from_ordered_keys(cilhip_ctx* c, const uint64_t* win_keys_dev, const uint64_t* order_keys_dev, double* sums_dev) {
-  if (!c || !win_keys_dev || !order_keys_dev || !sums_dev) return CILHIP_ERR_INVALID;
-  if (!c->run_active) return fail(c, CILHIP_ERR_INVALID, "icp_begin first");
-  if (!c->d_own_order) return fail(c, CILHIP_ERR_INVALID, "icp_sums_from_ordered_keys: cilhip_icp_order_keys first");
-  CK(c, hipSetDevice(c->device));
-  return sums_of_selected(c, sums_dev, [&] {
-    launch_select_ordered(c->d_src_sorted, c->d_own_order, reinterpret_cast<const unsigned long long*>(order_keys_dev),
-                          reinterpret_cast<const unsigned long long*>(win_keys_dev), c->ns, c->d_nn_pos, c->d_nn_d2, c->stream); });
-}
-
-int cilhip_compute_residuals(cilhip_ctx* c, int metric, float w_p2p, float w_p2pl, const float T[16], float* out, int mem) {
-  if (!c || !T || !out) return CILHIP_ERR_INVALID;
-  CK(c, hipSetDevice(c->device));
-  if (metric != 0 && !c->has_normals) return fail(c, CILHIP_ERR_INVALID, "compute_residuals: combined metric needs target normals");
-  int rc = ensure_sorted(c, T);
-  if (rc) return rc;
-  c->tie_counters_fresh = false;
-  rc = (c->tie_rule == 1 && tie_mode_on(c) && c->ns && c->grid.n) ? build_tie_tables(c) : CILHIP_OK;
-  if (rc) return rc;
-  launch_init_state(c->d_state, T, c->src_mean, c->stream, nullptr, 0, nullptr, nullptr, c->d_tie_counters);
-  IterArgs a = make_iter_args(c, 3.402823466e+38f);
-  DevBuf<float> staging;      // (host output: the residuals are formed on the device first)
-  if (mem != CILHIP_MEM_DEVICE) CK(c, staging.alloc(c->ns));
-  float* d_out = mem != CILHIP_MEM_DEVICE ? staging.get() : out;
-  launch_residuals(a, metric, w_p2p, w_p2pl, d_out, c->stream);
-  CK(c, hipGetLastError());
-  if (metric != 0) {      // (the point-to-plane term reads the matched point's normal: which of two equidistant points matters)
-    bool again = false;
-    rc = tie_check_pending(c, &again);
-    if (rc) return rc;
-    if (again) { a = make_iter_args(c, 3.402823466e+38f); launch_residuals(a, metric, w_p2p, w_p2pl, d_out, c->stream); CK(c, hipGetLastError()); }
-  }
-  if (mem != CILHIP_MEM_DEVICE) {
-    if (c->ns) CK(c, hipMemcpyAsync(out, d_out, (size_t)c->ns * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    CK(c, hipStreamSynchronize(c->stream));
-  }
-  return CILHIP_OK;
 }
 
 int cilhip_get_grid_info(cilhip_ctx* c, cilhip_grid_info* o) {

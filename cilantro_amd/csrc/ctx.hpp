@@ -1,5 +1,7 @@
-// ctx.hpp -- the context behind the C ABI (struct cilhip_ctx) and what the two host-only translation units share: c_api.hip (entry
-// points, buffers, single searches and estimates) and icp_loop.hip (the ICP loop drivers).  No kernel translation unit includes it.
+// ctx.hpp -- the context behind the C ABI (struct cilhip_ctx) and what the host-only translation units share: c_api.hip (contexts,
+// clouds, options, diagnostics, single searches and what they leave), tie_tables.hip (the order tables),
+// estimate.hip (the estimates over a stored set), shard_keys.hip (the key exchange of sharded runs) and icp_loop.hip (the ICP loop
+// drivers).  No kernel translation unit includes it.
 #pragma once
 
 #include "../../include/cilantro_hip/c_api.h"
@@ -9,13 +11,14 @@
 #include <string>
 #include <vector>
 
+#include "ctx_options.hpp"
 #include "internal.hpp"
 #include "loop_policy.hpp"
 
 using namespace cilhip;
 
 // What a context owns on the device, grouped by the event that releases it: a group is let go of by assigning an empty one
-// (c_api.hip: release_target, free_source, drop_src_grid).  Everything else the context owns lives as long as it does.
+// (c_api.hip: release_target, free_source; below: drop_src_grid).  Everything else the context owns lives as long as it does.
 // (declared first, destroyed last: the context's own stream outlives every buffer its work used)
 struct CtxStream { StreamGuard own_stream; };
 // ... of the TARGET.  Shareable members are what cilhip_share_target hands to a borrower, buffer by buffer.
@@ -26,6 +29,7 @@ struct TargetBufs {
   SharedBuf<uint4> d_tief_nodes;  // feature options they were built under (dropped with any of them); TieNode::info with four dimension bits
   SharedBuf<uint2> d_tie_leaf_slot;  // [grid.n] the order tables by sorted target position (null: not loaded)
   SharedBuf<uint4> d_tie_nodes;
+  int tie_max_depth = 0;          // ... and the depth of that order tree (the traversal keys hold 58 levels): set, shared and dropped with the tables
   SharedBuf<float> d_safe2;  // [grid.n] k_self_nn's table for the warm-started iteration; built with the target
   DevBuf<unsigned long long> d_winner;  // [n_target]
   DevBuf<float> d_dst_rgb;        // colour features, original order (they belong to the target they were set for)
@@ -66,7 +70,7 @@ struct SourceBufs : SrcGridBufs {
   DevBuf<uint32_t> d_src_inv;     // ... original -> sorted source position (per sorted order)
 };
 
-struct cilhip_ctx : CtxStream, TargetBufs, SourceBufs {
+struct cilhip_ctx : CtxStream, TargetBufs, SourceBufs, CtxOptions {      // (CtxOptions: every field an option sets, ctx_options.hpp)
   ~cilhip_ctx();                  // (below: events and the pinned feedback block)
   int device = 0;
   hipStream_t stream = nullptr;
@@ -102,38 +106,19 @@ struct cilhip_ctx : CtxStream, TargetBufs, SourceBufs {
   std::vector<unsigned char> trace_form;  // form of every iteration enqueued by the last run, timed or not (cilhip_get_last_run_trace)
   double form_ms[5] = {0, 0, 0, 0, 0};    // ... and the kernel time summed per form
   int form_n[5] = {0, 0, 0, 0, 0};
-  int warm_start = 1;             // option "warm_start": 0 = never, 1 = when the device reports the source near alignment, 2 = from the second iteration on
   DevBuf<uint32_t> d_dbg;                   // [2] cilhip_debug_counters scratch
   DevBuf<uint4> d_trace;                    // [RUN_TRACE_CAP] per-iteration loop state of the last run, written by the epilogue (cilhip_get_last_run_trace)
   uint32_t ntiles = 0;
-  int tiled = 1;                  // 0: per-lane global-memory search; 1: LDS-tiled search when the cloud is large enough; 2: always tiled
   bool src_sorted = false;
   float sort_T[16];
   float src_mean[3] = {0, 0, 0};
   bool rec_valid = false;         // the records describe the last executed iteration's matches (inside a run)
   bool src3_valid = false;        // the 12-byte source copy matches d_src_sorted (rewritten after a re-sort)
   bool lb_fresh = false;          // ... and they belong to the search that left nn_pos (inside a run)
-  bool warm_forecast = true;      // option "warm_forecast": the cold kernels' count of the queries a warm-started iteration would have to search gates the form
-  // option "tie_rule": which of several EXACTLY equidistant nearest target points a correspondence names.  0 = the lowest target index;
-  // 1 = the one the reference's kd-tree traversal meets first, order tables built before the first search; 2 (default) = the same
-  // choice, the tables built when a search first MEETS a tie (that search / run is then executed again): a target that never ties never
-  // pays for a tree.  The device resolves ties inside its search kernels (TieDev, kernels.hip: tie_settle).
-  int tie_rule = 2;
   int tief_builds = 0;
   unsigned int* d_tie_counters = nullptr;        // [4] TieDev::counters
   DevBuf<unsigned int> d_ticket;              // [1] k_reduce_solve's ticket (zero between launches)
-  // option "group_search": the global-memory search with SEVERAL lanes per query (k_search_group: small clouds and sources far from
-  // alignment, where one lane per query leaves the chip idle behind chains of dependent trips).  -1 (default) = the ICP loop decides per
-  // iteration (cold iterations of clouds the tiles do not take: always for clouds below the warm-started form's floor, from the
-  // kernels' own forecast above it); 0 = never; 4 .. 64 = that many lanes in every global-memory search.
-  int group_lanes = -1;
   double wait_us = 0.0;                          // time spent waiting for the device to publish loop state (wait_published), accumulated: not enqueue work
-  bool feat_warm = true;                         // option "feature_warm_start": the feature adaptors' forward search warm-started from the previous matches once the loop moves little (feat_warm.hip)
-  bool affine_device_loop = true;                // option "affine_device_loop": the affine classes' loop device-resident (one-pass moments on the matrix cores, 12-unknown
-                                                 // solve in the epilogue kernel) whenever nothing needs the stored set per iteration; 0 = the host-driven loop (A/B)
-  bool fused_epilogue = false;                   // option "fused_epilogue": stage-1 reduction + epilogue in ONE launch (the last of the 32 stage-1 blocks runs the
-                                                 // epilogue).  Bitwise the same results, measured SLOWER: 0.129 -> 0.136 ms per iteration at 10M, 0.037 -> 0.044 at 1M --
-                                                 // a device-scope fence costs more on this eight-L2 part than the kernel boundary it removes (NOTEBOOK.md): off
   unsigned int tie_counters_host[4] = {0, 0, 0, 0};      // ... as read together with the loop state at the end of a run (read_state: one synchronisation for both)
   bool tie_counters_fresh = false;
   double tie_build_ms = 0.0;                     // host time of the last table build (tree + upload)
@@ -145,14 +130,8 @@ struct cilhip_ctx : CtxStream, TargetBufs, SourceBufs {
   bool rev_tie_valid = false;
   float rev_tie_T[16];
   int rev_tie_builds = 0;
-  float warm_extra = 0.0625f;     // option "warm_extra_fraction"
-  bool pair_records = true;       // option "pair_records": the streaming accumulation gathers a match's point and normal from one 32-byte record (GridDev::pn)
   void* rank_comm = nullptr; int rank_comm_size = 0; DevBuf<double> d_rank_sums;      // cilhip_rank_comm_*: this process' rank in an RCCL communicator
-  bool tile_records = true;       // option "tile_records": the accumulating tile kernel writes the warm-started form's match records itself
-  float warm_enter = 0.15f;       // option "warm_enter_fraction": the bar a run starts with, as a fraction of a grid cell
   float src_center[3] = {0, 0, 0}, src_half[3] = {0, 0, 0};   // bounding box of the source (source coordinates): the epilogue's bound on how far a query moves per update
-  int cw_point_kind = 0, cw_plane_kind = 0;     // correspondence weight evaluators (CW_*), combined metric
-  float cw_point_sigma = 1.0f, cw_plane_sigma = 1.0f;
   cilhip_pair_weight_fn weight_fn = nullptr;    // a caller's own evaluators (cilhip_set_pair_weight_callback): the estimates call them on the host
   void* weight_user = nullptr;
   DevBuf<float> d_wtab;           // [2 * cap]: capacity() / 2 entries per table;  point / plane weights by stream position (CorrWeights::point_table / plane_table)
@@ -172,35 +151,15 @@ struct cilhip_ctx : CtxStream, TargetBufs, SourceBufs {
   DevBuf<double> d_partials;      // rows of SUMS_MAX doubles (ensure_partial_rows)
   DevBuf<double> d_stage;      // [REDUCE_STAGE_DOUBLES] stage-1 rows of the cross-block reduction
   DevBuf<double> d_sums;       // [3 * SUMS_MAX] (the affine estimator reduces three passes before one copy to the host)
-  bool tile_acc_adaptive = true;  // choose one pass / two passes per iteration from the device's feedback (option "tile_accumulation" = 2: always one pass)
-  bool tile_acc = true;           // accumulate inside the LDS tiles of the search when the engine allows it (option "tile_accumulation", A/B)
-  bool fused = false;             // true: search+accumulate in one kernel; false: search kernel + streaming accumulate kernel (faster: the search runs at 2x the occupancy)
-  double cell_occupancy = 1.0;    // target points per grid cell (takes effect at the next set_target)
-  double refined_occupancy = 3.0; // option "refined_occupancy_factor": how much denser than that a REFINED grid (surface-like / clustered target) may stay
   DevBuf<unsigned long long> d_count;
-
-  // engine post-filters (correspondence_search_kd_tree.hpp:224-225)
-  double inlier_fraction = 1.0;
-  bool one_to_one = false;
-  int tie_max_depth = 0;                   // depth of the loaded order tree (the traversal keys hold 58 levels)
   DevBuf<unsigned char> d_sel_state;
 
-  // other search directions (correspondence_search_kd_tree.hpp:185-222): the correspondence set is a pair list
-  int search_dir = 0;             // 0 = SECOND_TO_FIRST (default), 1 = FIRST_TO_SECOND, 2 = BOTH
-  bool reciprocal = false;        // require_reciprocality_ (BOTH only)
-  int transform_mode = 0;         // 0 = rigid (Isometry), 1 = affine: which ICP instance family cilhip_icp_run mirrors
-  float normal_weight = 0.0f;     // > 0: the correspondence search runs on 6-D features (point, weight * v)
-  int feature_kind = 0;           // option "feature_kind": 0 = v = normals, following the transform (PointNormalFeaturesAdaptor);
-                                  // 1 = v = colours, untouched by it (PointColorFeaturesAdaptor; cilhip_set_color_features)
-  float color_weight = 0.0f;             // option "feature_color_weight" (feature_kind 2: the 9-D adaptor's colour weight)
   bool dst_rgb_sorted_ok = false;
   float src_nrm0[3] = {0, 0, 0};  // the first source normal (the affine feature adaptor's normal weight is |w n_0|, adaptors.hpp:113-114)
   float feat_M[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};              // L^-T of the transform being searched under (affine adaptor)
-  bool symmetric = true;          // source normals, when set, also switch the combined metric to the symmetric objective
   PairSet pairs;
   GridDev src_grid{};             // grid over the source in SOURCE coordinates (built on the first FIRST_TO_SECOND / BOTH search of a source)
   bool has_src_grid = false;
-  bool reverse_warm = true;       // option "reverse_warm_start": the device-resident FIRST_TO_SECOND / BOTH loops start every reverse search but the first from the previous matches
   bool have_pairs = false;        // `pairs` holds the result of the last find_correspondences
   DevBuf<IcpState> d_state_id; // a state holding the identity transform (the reverse search transforms nothing)
 
@@ -216,9 +175,7 @@ struct cilhip_ctx : CtxStream, TargetBufs, SourceBufs {
   float run_src_mean[3] = {0, 0, 0};
 
   // timing
-  bool kernel_timing = false;
-  int timing_stride = 1;          // option "kernel_timing_stride": with kernel timing on, iterations 0..2 and every stride-th one carry events
-  std::vector<unsigned int> timed_iter;      // the iterations of the last run that did
+  std::vector<unsigned int> timed_iter;      // the iterations of the last run that carried events (options "kernel_timing", "kernel_timing_stride")
   std::vector<float> timed_ms;               // ... and the kernel time of each (cilhip_get_last_iteration_timing)
   double last_loop_ms = 0.0, last_search_ms = 0.0, last_acc_ms = 0.0;
   int last_search_launches = 0;
@@ -292,20 +249,43 @@ inline bool tile_accumulation(const cilhip_ctx* c) {
   return c->tile_acc && use_tiled(c) && !filters_active(c) && !weighted(c) && !feat6(c) && !(c->d_src_nrm && c->symmetric) && !c->fused;
 }
 
-// option "tie_rule" is in force for this context's point searches (c_api.hip: the order tables)
+// option "tie_rule" is in force for this context's point searches (tie_tables.hip: the order tables)
 inline bool tie_mode_on(const cilhip_ctx* c) { return c->tie_rule != 0 && !feat6(c); }
 
 // c->fused is honoured as ONE per-lane search+accumulate kernel only by the plain engine (post-filters and feature adaptors need the stored set)
 inline bool lane_fused(const cilhip_ctx* c) { return c->fused && !filters_active(c) && !feat6(c); }
-// the stored correspondence set (matches or pair list) no longer describes anything a caller may read
+// ---- what a context lets go of, and when.  A shared target array is only let go of: its last holder frees it.
+// the stored matches no longer describe anything a caller may read
 inline void drop_matches(cilhip_ctx* c) { c->have_nn = false; c->d2_stale = false; c->pending_matches = false; c->matches_origin = 0; }
+// ... nor does the pair list (it refers to the source / target and the options it was found under).  pairs.count stays as it is: it is
+// read behind have_pairs only, or straight after the search that wrote it
+inline void drop_correspondences(cilhip_ctx* c) { drop_matches(c); c->have_pairs = false; }
+inline void drop_src_grid(cilhip_ctx* c) {
+  static_cast<SrcGridBufs&>(*c) = SrcGridBufs{};
+  c->src_grid = GridDev{}; c->has_src_grid = false;
+}
+inline void drop_feat_tie_tables(cilhip_ctx* c) {      // (one target under one set of feature options; never shared)
+  c->d_tief_leaf_slot.reset(); c->d_tief_nodes.reset();
+}
+inline void drop_tie_tables(cilhip_ctx* c) {      // (they describe ONE target)
+  c->d_tie_leaf_slot.reset(); c->d_tie_nodes.reset(); c->tie_max_depth = 0;
+}
+// what a newly stored option value made stale (ctx_options.hpp: the STALE_* events a table row reports)
+inline void apply_stale(cilhip_ctx* c, unsigned stale) {
+  if (stale & STALE_SRC_GRID) drop_src_grid(c);
+  if (stale & STALE_FEAT_ORDER) drop_feat_tie_tables(c);
+  if ((stale & STALE_MATCHES) || ((stale & STALE_PENDING_MATCHES) && c->pending_matches)) drop_matches(c);
+  if (stale & STALE_CORRESPONDENCES) drop_correspondences(c);
+}
 // event i of a list that grows on demand (c->ev: run / kernel events, c->ev_acc: the two-pass iterations' accumulation)
 inline hipEvent_t event_at(std::vector<hipEvent_t>& v, size_t i) {
   while (v.size() <= i) { hipEvent_t e; (void)hipEventCreate(&e); v.push_back(e); }
   return v[i];
 }
 
-// ---- helpers of c_api.hip the loop drivers call (iter_metric_of: the other way round)
+// ---- helpers the host units call across files: c_api.hip (ensure_*, set_warm_args, filters, projection, searches,
+// materialize_pending), tie_tables.hip (tie_*, build_*tie_tables), estimate.hip (corr_weights_of, use_stored_set,
+// icp_run_affine), icp_loop.hip (iter_metric_of)
 int ensure_sorted(cilhip_ctx* c, const float T[16]);
 int ensure_partial_rows(cilhip_ctx* c, size_t rows);      // d_partials holds at least `rows` rows of SUMS_MAX doubles (callers re-read c->d_partials)
 int ensure_warm_buffers(cilhip_ctx* c);
@@ -316,7 +296,10 @@ int ensure_reverse_buffers(cilhip_ctx* c);
 void set_warm_args(const cilhip_ctx* c, IterArgs& wa);
 CorrWeights corr_weights_of(const cilhip_ctx* c, const cilhip_icp_params* p);
 FeatSpec feat_spec_of(const cilhip_ctx* c);
+TieDev tie_dev_of(const cilhip_ctx* c);
 TieDev tie_dev_rev(const cilhip_ctx* c);
+int build_tie_tables(cilhip_ctx* c);
+int build_rev_tie_tables(cilhip_ctx* c, const float T[16]);
 int tie_prepare(cilhip_ctx* c, const char* what);
 int tie_check_pending(cilhip_ctx* c, bool* again);
 int apply_filters(cilhip_ctx* c);
@@ -325,6 +308,8 @@ int ensure_proj_map(cilhip_ctx* c);
 IterArgs make_iter_args(cilhip_ctx* c, float max_sq);
 int launch_search(cilhip_ctx* c, const IterArgs& a, int lanes = -1 /* -1: the option's own value when it names a lane count */);
 int run_pair_search(cilhip_ctx* c, const IterArgs& a, float max_sq, const float T_host[16]);
+int materialize_pending(cilhip_ctx* c);
+void use_stored_set(const cilhip_ctx* c, IterArgs& a, bool symmetric_normals);      // the pair list's own views, for the accumulating kernels
 int icp_run_affine(cilhip_ctx* c, const cilhip_icp_params* p, const float* T0, cilhip_icp_result* out);
 int iter_metric_of(const cilhip_ctx* c, const cilhip_icp_params* p);      // (icp_loop.hip)
 }  // namespace cilhip

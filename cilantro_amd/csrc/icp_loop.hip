@@ -1,6 +1,6 @@
 // icp_loop.hip -- the ICP loop drivers of the C ABI (c_api.h): cilhip_icp_run, the building blocks of sharded runs (cilhip_icp_begin /
 // _partial_sums / _apply_sums / _state) and the ranked loop over an RCCL communicator.  Host control flow only, no kernels; the
-// form an iteration takes is decided in loop_policy.hpp, the context and the helpers of c_api.hip these loops call are in ctx.hpp.
+// form an iteration takes is decided in loop_policy.hpp, the context and the helpers of the other host units these loops call are in ctx.hpp.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -103,7 +103,7 @@ static int read_state(cilhip_ctx* c, cilhip_icp_result* out, float* Tprev = null
 // it in nn_pos (the squared distances are formed again with the search's pinned arithmetic); pairs: c->pairs holds it;
 // otherwise it is searched again when somebody asks (materialize_pending).
 static void finish_run_matches(cilhip_ctx* c, const cilhip_icp_params* p, size_t iterations, const float Tprev[16], bool stored, bool pairs) {
-  drop_matches(c); c->have_pairs = false;
+  drop_correspondences(c);
   if (iterations == 0) return;
   memcpy(c->nn_T, Tprev, sizeof(c->nn_T));
   if (pairs) { c->have_pairs = true; c->matches_origin = 1; return; }
@@ -290,8 +290,7 @@ static int run_pair_list_loop(cilhip_ctx* c, RunSetup& r) {
     int rc = run_pair_search(c, r.a, p->max_sq_dist, it == 0 ? r.Ti : r.out->T);
     if (rc) return rc;
     IterArgs pa = r.a;
-    pa.nn_d2 = c->pairs.d2;  // (per pair: corr.value -- the 6-D distance under a feature adaptor -- for the weight evaluators)
-    pa.src = c->pairs.src_view; pa.src_nrm = (c->d_src_nrm && c->symmetric) ? c->pairs.nrm_view : nullptr; pa.ns = c->pairs.count; pa.nn_pos = c->pairs.posd;
+    use_stored_set(c, pa, true);  // (nn_d2 per pair: corr.value -- the 6-D distance under a feature adaptor -- for the weight evaluators)
     const int pnb = iter_num_blocks(pa.ns);
     rc = ensure_partial_rows(c, (size_t)pnb);
     if (rc) return rc;

@@ -467,7 +467,7 @@ struct PairSet {
 // feat (optional, w > 0): the reverse matches are the nearest 6-D FEATURES (feat->src in the source grid's order, feat->dst by target position)
 // rev_tie (option "tie_rule" for these matches): the reference searches a kd-tree over the TRANSFORMED SOURCE, rebuilt every iteration
 // (correspondence_search_kd_tree.hpp:185-222): leaf_slot = that tree's order tables by position in the source grid, valid for the state's
-// transform only (built per search: c_api.hip build_rev_tie_tables); null = count the tied target points (counters[3]) and keep the lowest source index
+// transform only (built per search: tie_tables.hip build_rev_tie_tables); null = count the tied target points (counters[3]) and keep the lowest source index
 // warm_src_safe2 (plain point features only): rev_pos holds the PREVIOUS iteration's reverse matches, the table is k_self_nn's over the source grid -- k_reverse_warm
 // settles every target point whose old match passes the margin test without a search and searches the rest (the same exact result)
 // fused (with warm_src_safe2): the first Gauss-Newton step's sums over the reverse matches accumulated in the same kernel (rows of SUMS_MAX doubles, one per block:

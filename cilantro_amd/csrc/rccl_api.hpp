@@ -1,5 +1,5 @@
 // rccl_api.hpp -- RCCL opened at run time (dlopen): libcilantro_hip.so itself does not depend on it.  The entry points the
-// multi-device loop (multi.hip) and the rank communicator (c_api.hip: cilhip_rank_comm_*) call, with rccl.h's enum values.
+// multi-device loop (multi.hip) and the rank communicator (icp_loop.hip: cilhip_rank_comm_*) call, with rccl.h's enum values.
 #pragma once
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>

@@ -25,3 +25,10 @@ g++ -O2 -std=c++17 -I"$ROOT/include" "$HERE/test_ply.cpp" -o "$HERE/bin/test_ply
 # the example program (compile check; run it on a GPU box with a PLY file)
 g++ -O2 -std=c++17 -I"$ROOT/include" "$ROOT/examples/rigid_icp.cpp" -o "$HERE/bin/example_rigid_icp" \
     -L"$ROOT/cilantro_amd/lib" -lcilantro_hip -Wl,-rpath,"$ROOT/cilantro_amd/lib" -Wl,-rpath,/opt/rocm/lib -L/opt/rocm/lib -lamdhip64
+# host-only sweep of the option table (csrc/ctx_options.hpp behind cilhip_set_option / cilhip_get_option: a context constructed on the host
+# takes both without a device), once plainly and once under the address and undefined-behaviour sanitizers (hipcc: ctx.hpp pulls in the HIP runtime API)
+for v in "" "_san"; do
+SAN=""; [ -n "$v" ] && SAN="-g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all"
+/opt/rocm/bin/hipcc -O1 -std=c++17 -ffp-contract=off --offload-arch=gfx950 $SAN "$HERE/test_ctx_options.cpp" -o "$HERE/bin/test_ctx_options$v" \
+    -L"$ROOT/cilantro_amd/lib" -lcilantro_hip -Wl,-rpath,"$ROOT/cilantro_amd/lib" -Wl,-rpath,/opt/rocm/lib
+done

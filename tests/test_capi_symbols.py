@@ -10,6 +10,13 @@ from cilantro_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "cilantro_hip", "c_api.h")
+OPTIONS_HPP = os.path.join(ROOT, "cilantro_amd", "csrc", "ctx_options.hpp")
+
+
+def table_keys():
+    """the quoted key of every row of the option table (that a table key is accepted with its default and any other key refused:
+    the sweep of tests/test_cpp_host_api.py::test_option_table_sweep_on_host)"""
+    return sorted(set(re.findall(r'CILHIP_(?:FIELD|ROW)\(CILHIP_OPT_[A-Z_0-9]+, "([a-z_0-9]+)"', open(OPTIONS_HPP).read())))
 
 
 def declared_symbols():
@@ -69,12 +76,9 @@ def test_product_never_imports_the_oracle():
 
 
 def test_every_option_key_is_documented_in_the_header():
-    """cilhip_set_option's keys (cilantro_amd/csrc/c_api.hip) all appear, quoted, in include/cilantro_hip/c_api.h"""
-    import re
-
-    src = open(os.path.join(ROOT, "cilantro_amd", "csrc", "c_api.hip")).read()
+    """cilhip_set_option's keys (the rows of cilantro_amd/csrc/ctx_options.hpp) all appear, quoted, in include/cilantro_hip/c_api.h"""
     hdr = open(os.path.join(ROOT, "include", "cilantro_hip", "c_api.h")).read()
-    keys = sorted(set(re.findall(r'strcmp\(key, "([a-z_0-9]+)"\)', src)))
+    keys = table_keys()
     assert len(keys) >= 15
     missing = [k for k in keys if '"%s"' % k not in hdr]
     assert not missing, missing
@@ -93,9 +97,7 @@ def test_option_table_documents_every_option(hip_lib):
     for i, (o, n) in enumerate(zip(opts, names)):
         assert o["id"] == i and n == "CILHIP_OPT_" + o["key"].upper(), (i, o["key"], n)
         assert len(o["doc"]) >= 20 and o["min"] <= o["default"] <= o["max"], o
-    src = open(os.path.join(ROOT, "cilantro_amd", "csrc", "c_api.hip")).read()
-    keys = sorted(set(re.findall(r'strcmp\(key, "([a-z_0-9]+)"\)', src)))
-    assert sorted(o["key"] for o in opts) == keys
+    assert sorted(o["key"] for o in opts) == table_keys()
     assert hip_lib.cilhip_option_info(-1) is None or not hip_lib.cilhip_option_info(-1)
     assert not hip_lib.cilhip_option_info(len(opts))
     # named by a test (or, for the dev-only A/B switches, by a dev tool)

@@ -94,3 +94,32 @@ def test_ransac_sampling_on_host(hip_lib, orc):
         subprocess.check_call(["bash", os.path.join(ROOT, "tests", "cpp", "build.sh")])
     out = subprocess.run([binp], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and "ALL OK" in out.stdout, out.stdout + out.stderr
+
+
+def test_option_table_sweep_on_host(hip_lib, orc):
+    """cilantro_amd/csrc/ctx_options.hpp holds every context option once (fields, default, range, how a value is stored, what it makes
+    stale); cilhip_set_option / cilhip_get_option work on a context constructed on the host.  tests/cpp/test_ctx_options.cpp sets every
+    row to {default, min, max, min - 1, max + 1, midpoint, 0.5, 1.5, 2.5, 3, 5, 16, 1e-10, NaN}, by key and by id, plus keys and ids the
+    table does not hold, each on a fresh context with a stored set of every kind, and prints return code, the read-back of all options
+    (as what differs from a fresh context's, which the first line holds in full), the four stored-set flags and the error text, the
+    two ways of setting on one line where they agree in everything: byte for byte tests/golden/option_sweep.txt, recorded from the same program against
+    the library as it was before the table moved -- once plainly, once under the address and undefined-behaviour sanitizers.  No GPU."""
+    want = open(os.path.join(ROOT, "tests", "golden", "option_sweep.txt"), "rb").read()
+    lines = want.decode().splitlines()
+    from cilantro_amd import capi
+
+    keys = [o["key"] for o in capi.options()]
+    # what "accepted keys" means, by behaviour: every table key takes its default, a key absent from the table is refused
+    for k in keys:
+        first = next(ln for ln in lines if ln.startswith("key+id %s = " % k))      # (the first value of a row is its default)
+        assert "-> rc 0 | - |" in first and first.endswith("| "), first
+    assert lines[0].startswith("fresh ") and [kv.split("=")[0] for kv in lines[0].split()[1:]] == keys
+    assert any(ln.startswith("key no_such_option = 1 -> rc -1 |") and ln.endswith("set_option: unknown key") for ln in lines)
+    assert len(lines) == 14 * len(keys) + 4 and sum("-> rc -1 |" in ln for ln in lines) > 150
+    for name in ("test_ctx_options", "test_ctx_options_san"):
+        binp = os.path.join(ROOT, "tests", "cpp", "bin", name)
+        if not os.path.exists(binp):
+            subprocess.check_call(["bash", os.path.join(ROOT, "tests", "cpp", "build.sh")])
+        out = subprocess.run([binp], capture_output=True, timeout=120)
+        assert out.returncode == 0 and not out.stderr, out.stderr[-2000:]
+        assert out.stdout == want, name

@@ -403,6 +403,40 @@ def test_target_shards_follow_the_reference_s_order_across_shards(Context, orc):
     _report("tie_rule_target_shards.json", out)
 
 
+def test_a_shared_target_carries_its_order_tables_and_their_depth(Context):
+    """cilhip_share_target hands a borrower the lender's order tables together with the depth of their tree (cilhip_icp_order_keys refuses
+    a tree deeper than the 58 levels a traversal key holds, by that depth): on a 4 096-point lattice target -- every query at a cube
+    centre has 8 exactly equidistant corners -- the borrower's traversal keys are the lender's, key for key."""
+    import torch
+
+    D, N, S, r2, n_tied = _lattice(16)
+    assert len(D) == 4096
+    lender = Context(); lender.set_target(D, N); lender.set_source(S); lender.build_tie_order()
+    borrower = Context(); borrower.share_target(lender); borrower.set_source(S)
+    assert lender.tie_order_info()["loaded"] and borrower.tie_order_info()["loaded"]
+    p = _icp_params(lender, r2, 2)
+    NONE = 0x7FFFFFFFFFFFFFFF
+    got = []
+    for c in (lender, borrower):
+        keys = torch.full((len(S),), NONE, dtype=torch.int64, device="cuda:0"); okeys = torch.full_like(keys, NONE)
+        torch.cuda.synchronize()
+        c.icp_begin(p, np.eye(4, dtype=np.float32))
+        c.icp_partial_keys(keys.data_ptr())
+        c.icp_order_keys(keys.data_ptr(), okeys.data_ptr())
+        c.synchronize()
+        got.append((keys.cpu().numpy(), okeys.cpu().numpy()))
+    assert np.array_equal(got[0][0], got[1][0]) and np.array_equal(got[0][1], got[1][1])
+    ordered = got[0][1] != NONE
+    assert int(ordered.sum()) >= n_tied and len(np.unique(got[0][1][ordered])) >= 2      # (every tied query has a key, and the keys order something: not one constant)
+    # the lender goes first: the tables are the borrower's now, depth included
+    lender.close()
+    keys = torch.full((len(S),), NONE, dtype=torch.int64, device="cuda:0"); okeys = torch.full_like(keys, NONE)
+    torch.cuda.synchronize()
+    borrower.icp_begin(p, np.eye(4, dtype=np.float32)); borrower.icp_partial_keys(keys.data_ptr()); borrower.icp_order_keys(keys.data_ptr(), okeys.data_ptr()); borrower.synchronize()
+    assert np.array_equal(okeys.cpu().numpy(), got[0][1])
+    borrower.close()
+
+
 def test_other_search_directions_follow_the_tree_over_the_transformed_source(Context, orc):
     """FIRST_TO_SECOND / BOTH: the reference searches a kd-tree built over the TRANSFORMED source, a new one per iteration
     (correspondence_search_kd_tree.hpp:185-222): among source points exactly equidistant from a target point it returns the one THAT tree's
