@@ -2,7 +2,8 @@
 also reachable from the package itself (resolved on first use, so importing the package loads nothing)."""
 
 _KD_TREE = ("KDTree", "KDTree2f", "KDTreeXf", "KNNNeighborhoodSpecification", "KNNInRadiusNeighborhoodSpecification")
-__all__ = list(_KD_TREE)
+_MEAN_SHIFT = ("MeanShift3f", "MeanShift2f", "MeanShiftXf", "mean_shift", "mean_shift_nd")
+__all__ = list(_KD_TREE + _MEAN_SHIFT)
 
 
 def __getattr__(name):
@@ -10,4 +11,8 @@ def __getattr__(name):
         from . import kd_tree
 
         return getattr(kd_tree, name)
+    if name in _MEAN_SHIFT:
+        from . import clustering
+
+        return getattr(clustering, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -40,6 +40,7 @@ SYMBOLS = [
     "cilhip_convex_hull_create", "cilhip_convex_hull_get", "cilhip_convex_hull_destroy", "cilhip_polytope_signed_distances", "cilhip_polytopes_interior_mask",
     "cilhip_polytopes_interior_indices",
     "cilhip_knn_nd", "cilhip_radius_search_nd",
+    "cilhip_mean_shift_nd", "cilhip_msn_last_stats",
 ]
 
 
@@ -110,6 +111,10 @@ class MsParams(C.Structure):
 
 class MsStats(C.Structure):
     _fields_ = [("form_used", C.c_int), ("est_ball", C.c_double), ("shift_ms", C.c_double), ("group_ms", C.c_double), ("passes", C.c_size_t), ("rounds", C.c_size_t)]
+
+
+class MsnStats(C.Structure):
+    _fields_ = [("passes", C.c_size_t), ("rounds", C.c_size_t), ("slices_first", C.c_size_t), ("slices_last", C.c_size_t), ("shift_ms", C.c_double), ("group_ms", C.c_double)]
 
 
 class McdParams(C.Structure):
@@ -271,6 +276,9 @@ def load():
     L.cilhip_ms_default_params.restype = None
     L.cilhip_mean_shift3f.argtypes = [C.c_int, f32p, C.c_size_t, f32p, C.c_size_t, C.c_int, C.POINTER(MsParams), vp, vp, vp, vp, vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.cilhip_ms_last_stats.argtypes = [C.POINTER(MsStats)]
+    L.cilhip_mean_shift_nd.argtypes = [C.c_int, f32p, C.c_size_t, C.c_size_t, f32p, C.c_size_t, C.c_int, C.POINTER(MsParams), vp, vp, vp, vp, vp, C.POINTER(C.c_size_t),
+                                       C.POINTER(C.c_size_t)]
+    L.cilhip_msn_last_stats.argtypes = [C.POINTER(MsnStats)]
     L.cilhip_mcd_params_default.argtypes = [C.POINTER(McdParams)]
     L.cilhip_mcd_params_default.restype = None
     L.cilhip_robust_normals_knn3f.argtypes = [C.c_int, f32p, C.c_size_t, C.c_int, C.POINTER(McdParams), f32p, f32p, f32p, vp, vp]

@@ -1,7 +1,7 @@
 """Python mirrors of cilantro's KMeans3f (clustering/kmeans.hpp), ConnectedComponentExtraction3f
-(clustering/connected_component_extraction.hpp; second part of this file), MeanShift3f (clustering/mean_shift.hpp; third part) and
-SpectralClustering with KMeansXf and the sparse nearest-neighbour graph matrix (clustering/spectral_clustering.hpp; last part) on top
-of the C ABI (cilhip_kmeans3f, cilhip_connected_components3f, cilhip_mean_shift3f, cilhip_nn_graph_matrix / cilhip_spectral_embedding /
+(clustering/connected_component_extraction.hpp; second part of this file), MeanShift3f / MeanShift2f / MeanShiftXf
+(clustering/mean_shift.hpp; third part) and SpectralClustering with KMeansXf and the sparse nearest-neighbour graph matrix (clustering/spectral_clustering.hpp; last part) on top
+of the C ABI (cilhip_kmeans3f, cilhip_connected_components3f, cilhip_mean_shift3f, cilhip_mean_shift_nd, cilhip_nn_graph_matrix / cilhip_spectral_embedding /
 cilhip_kmeans_nd).
 
     km = KMeans3f(points)
@@ -439,6 +439,99 @@ class MeanShift3f:
         """per cluster, ascending seed indices"""
         off, mem = self._r["offsets"], self._r["members"]
         return [mem[int(off[c]):int(off[c + 1])] for c in range(self.getNumberOfClusters())]
+
+
+# ---- MeanShiftXf / MeanShift2f (clustering/mean_shift.hpp:142-164) -----------------------------------------------------------------
+# The contract is stated in include/cilantro_hip/c_api.h (cilhip_mean_shift_nd, rules M1-M7) and DESIGN.md section 22.
+def _as_rows(x, what):
+    """an n x dim float32 array, numpy or device tensor -> (array, address, n, dim, on_device)"""
+    on_device = hasattr(x, "is_cuda") and x.is_cuda
+    if on_device:
+        import torch
+
+        x = x.to(torch.float32).contiguous()
+    else:
+        x = np.ascontiguousarray(x.cpu() if hasattr(x, "cpu") else x, np.float32)
+    if x.ndim != 2:
+        raise ValueError(f"{what} are an n x dim array")
+    return x, (x.data_ptr() if on_device else x.ctypes.data), int(x.shape[0]), int(x.shape[1]), on_device
+
+
+def mean_shift_nd(points, kernel_radius, max_iter, cluster_tol, convergence_tol=float(np.finfo(np.float32).eps), evaluator=None, seeds=None, device=0):
+    """cilhip_mean_shift_nd over n x dim points (1 <= dim <= 16) -> dict(shifted[ns, dim], labels[ns], modes[k, dim], offsets[k + 1],
+    members[ns], iterations, stats): cluster c is members[offsets[c]:offsets[c + 1]]; seeds=None: every point is a seed.  numpy arrays in ->
+    numpy arrays out; device tensors in -> device tensors out"""
+    L = capi.load()
+    ev = evaluator if evaluator is not None else UnityWeightEvaluator()
+    x, p, n, dim, on_device = _as_rows(points, "the points")
+    sx, sp, ns = None, None, n
+    if seeds is not None:
+        sx, sp, ns, sdim, s_dev = _as_rows(seeds, "the seeds")
+        if s_dev != on_device:
+            raise ValueError("points and seeds must live in the same memory space")
+        if sdim != dim:
+            raise ValueError("points and seeds must have the same dimension")
+        if ns == 0:      # (an empty list is still a list: a non-null pointer)
+            sx = x.new_zeros((1, max(dim, 1))) if on_device else np.zeros((1, max(dim, 1)), np.float32)
+            sp = sx.data_ptr() if on_device else sx.ctypes.data
+    prm = capi.MsParams()
+    L.cilhip_ms_default_params(C.byref(prm))
+    prm.kernel_radius, prm.max_iter, prm.cluster_tol, prm.convergence_tol = kernel_radius, int(max_iter), cluster_tol, convergence_tol
+    prm.kernel_kind, prm.kernel_sigma = int(ev.kind), float(ev.sigma)
+    if on_device:
+        import torch
+
+        dev = x.device
+        if dev.index is not None:
+            device = dev.index
+        torch.cuda.synchronize(dev)      # the call runs on a stream of its own: the inputs must be complete
+        shifted, modes = torch.empty((ns, dim), dtype=torch.float32, device=dev), torch.empty((ns, dim), dtype=torch.float32, device=dev)
+        labels, offsets, members = (torch.empty(k, dtype=torch.int32, device=dev) for k in (ns, ns + 1, ns))
+        addr = [t.data_ptr() for t in (shifted, labels, modes, offsets, members)]
+    else:
+        shifted, modes = np.empty((ns, dim), np.float32), np.empty((ns, dim), np.float32)
+        labels, offsets, members = (np.empty(k, np.uint32) for k in (ns, ns + 1, ns))
+        addr = [a.ctypes.data for a in (shifted, labels, modes, offsets, members)]
+    nc, iters = C.c_size_t(0), C.c_size_t(0)
+    rc = L.cilhip_mean_shift_nd(int(device), p, n, dim, sp, ns if seeds is not None else 0, capi.MEM_DEVICE if on_device else capi.MEM_HOST, C.byref(prm), addr[0], addr[1], addr[2],
+                                addr[3], addr[4], C.byref(nc), C.byref(iters))
+    if rc != capi.OK:
+        raise capi.CilhipError(rc, "cilhip_mean_shift_nd: " + L.cilhip_last_error(None).decode())
+    if ns == 0:
+        offsets[:1] = 0
+    st = capi.MsnStats()
+    L.cilhip_msn_last_stats(C.byref(st))
+    stats = {k: getattr(st, k) for k in ("passes", "rounds", "slices_first", "slices_last", "shift_ms", "group_ms")} if ns else {}
+    lab, off, mem_ = _cc_result([labels, offsets, members], nc.value, on_device)
+    return {"shifted": shifted, "labels": lab, "modes": modes[: nc.value], "offsets": off, "members": mem_, "iterations": int(iters.value), "stats": stats}
+
+
+class MeanShiftXf(MeanShift3f):
+    """MeanShift<float, Dynamic> (mean_shift.hpp:164): MeanShift3f's two cluster() forms and accessors over n x dim points, 1 <= dim <= 16.
+    dim, when given, is checked against the points."""
+
+    def __init__(self, points, dim=None, device=0):
+        super().__init__(points, device)
+        if getattr(points, "ndim", None) != 2 or (dim is not None and int(points.shape[1]) != int(dim)):
+            raise ValueError("the points are an n x dim array" if dim is None else f"the points are an n x {int(dim)} array")
+        self.dim = int(points.shape[1])
+
+    def cluster(self, *args, **kw):
+        args = list(args)
+        seeds = kw.pop("seeds", None)
+        if args and not np.isscalar(args[0]):
+            seeds = args.pop(0)
+        for k, v in zip(("kernel_radius", "max_iter", "cluster_tol", "convergence_tol", "evaluator"), args):
+            kw[k] = v
+        self._r = mean_shift_nd(self._points, seeds=seeds, device=self._device, **kw)
+        return self
+
+
+class MeanShift2f(MeanShiftXf):
+    """MeanShift<float, 2> (mean_shift.hpp:142)"""
+
+    def __init__(self, points, device=0):
+        super().__init__(points, 2, device)
 
 
 # ---- SpectralClustering (clustering/spectral_clustering.hpp) ---------------------------------------------------------------------

@@ -22,6 +22,7 @@
 #include "internal.hpp"
 #include "knn_lists.hpp"
 #include "knn_nd_host.hpp"
+#include "nd_device.hpp"
 #include "stateless.hpp"
 
 #include <hip/hip_runtime.h>
@@ -32,29 +33,6 @@ namespace cilhip {
 namespace {
 
 constexpr int KNN_ND_TILE = 4;      // candidates loaded and evaluated together (4 x 16 coordinates: 64 scalar registers)
-
-template <int DIM> struct NdQuery {
-  float c[DIM];
-  __device__ __forceinline__ void load(const float* __restrict__ q) {
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) c[d] = q[d];
-  }
-  // N1; p is wave-uniform
-  __device__ __forceinline__ float d2(const float* __restrict__ p) const {
-    float r = 0.0f;
-#pragma unroll
-    for (int g = 0; g + 4 <= DIM; g += 4) {
-      const float t0 = __fsub_rn(c[g], p[g]), t1 = __fsub_rn(c[g + 1], p[g + 1]), t2 = __fsub_rn(c[g + 2], p[g + 2]), t3 = __fsub_rn(c[g + 3], p[g + 3]);
-      r = __fadd_rn(r, __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(t0, t0), __fmul_rn(t1, t1)), __fmul_rn(t2, t2)), __fmul_rn(t3, t3)));
-    }
-#pragma unroll
-    for (int d = DIM & ~3; d < DIM; ++d) {
-      const float t = __fsub_rn(c[d], p[d]);
-      r = __fadd_rn(r, __fmul_rn(t, t));
-    }
-    return r;
-  }
-};
 
 __device__ __forceinline__ unsigned long long nd_key(float d2, uint32_t j) { return ((unsigned long long)__float_as_uint(d2) << 32) | j; }
 
@@ -219,13 +197,6 @@ void launch_radius_nd(hipStream_t s, const float* ref, size_t n_ref, size_t slic
   hipLaunchKernelGGL((k_radius_nd<DIM, FILL>), dim3(nd_blocks(nq), (unsigned)slices), dim3(KNN_THREADS), 0, s, ref, (uint32_t)n_ref, (uint32_t)slice, qry, (uint32_t)nq,
                      radius_sq, cnt, keys);
 }
-
-#define ND_DISPATCH(dim, CALL)                                                                                                                  \
-  switch (dim) {                                                                                                                                \
-    case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break; case 4: CALL(4); break; case 5: CALL(5); break; case 6: CALL(6); break;      \
-    case 7: CALL(7); break; case 8: CALL(8); break; case 9: CALL(9); break; case 10: CALL(10); break; case 11: CALL(11); break; case 12: CALL(12); break; \
-    case 13: CALL(13); break; case 14: CALL(14); break; case 15: CALL(15); break; default: CALL(16); break;                                          \
-  }
 
 int knn_nd_impl(int device, const float* ref, size_t n_ref, const float* query, size_t n_query, size_t dim, int mem, size_t k, float max_sq_dist, uint32_t* idx_out,
                 float* d2_out, uint32_t* counts_out) {

@@ -629,8 +629,8 @@ int cilhip_connected_components_lists(int device, size_t n, const uint64_t* offs
  * and positive; unknown kernel_kind, form or mem; NULL params, n_clusters_out, iterations_out, or (with at least one seed) NULL
  * shifted_seeds_out / labels_out.  No seed at all: CILHIP_OK, zero clusters, zero iterations, no device needed.  n == 0 with seeds is
  * legal: every ball is empty (rule 5).
- * Not built: 2-D, double and dynamic-dimension variants, other distance adaptors, a caller's functor as kernel evaluator, a caller-owned
- * tree (MeanShift(const SearchTree&) is "the same points"), a sharded run. */
+ * Not built: double, other distance adaptors, a caller's functor as kernel evaluator, a caller-owned tree (MeanShift(const SearchTree&)
+ * is "the same points"), a sharded run.  2-D and dynamic-dimension points: cilhip_mean_shift_nd below. */
 typedef struct cilhip_ms_params {
   float kernel_radius; size_t max_iter; float cluster_tol; float convergence_tol;
   int kernel_kind;      /* 0 Unity, 1 Identity, 2 RBF over the squared distance */
@@ -651,6 +651,50 @@ typedef struct cilhip_ms_stats {
   size_t passes, rounds;
 } cilhip_ms_stats;
 int cilhip_ms_last_stats(cilhip_ms_stats* out);
+
+/* ---- mean-shift clustering in 1 to 16 dimensions ---------------------------------------------------
+ * cilantro's MeanShift2f / MeanShiftXf (clustering/mean_shift.hpp:142-164 over :38-124; float, L2).  points and seeds are point-major
+ * n x dim arrays (the layout of cilhip_knn_nd).  Exhaustive: every active seed meets every point in every pass, and the grouping is a
+ * quadratic scan (DESIGN.md section 22 states the cost and the worst cases).  The rules are those of cilhip_mean_shift3f with three
+ * changes -- the distance (M1), the stated summation order (M3) and the absence of forms:
+ *   M1 ball      point j is in seed i's ball iff d2(seed_i, p_j) < radius_sq, strict.  d2 is rule N1 of cilhip_knn_nd: nanoflann's
+ *                L2_Adaptor::evalMetric in f32, in groups of four coordinates and then the tail one coordinate at a time, every operation
+ *                rounded, nothing contracted (dim = 3: the 3-D entry's d2 bit for bit).  radius_sq = kernel_radius * kernel_radius, one f32
+ *                product.  A point with a non-finite coordinate is in no ball: its d2 is NaN or +inf.
+ *   M2 weights   rule 2 above: 1, d2_j or exp(coeff * d2_j) in the pinned f32 arithmetic.
+ *   M3 step      S_a = sum (double)w_j * (double)p_ja (every product exact), W = sum (double)w_j, new_a = (float)(S_a / W).  Order: the
+ *                point stream is cut into s slices of consecutive indices (s a function of n and of the number of seeds still active,
+ *                evaluated once per pass); within a slice the sum ascends by point index from 0; the slices' sums are added in ascending
+ *                order from 0.  No floating-point atomics: two runs agree bit for bit.  Deviation from rule 3 above: the last bit of a
+ *                step may depend on how many seeds are still active, because s does; it never depends on the schedule.
+ *   M4 converged d2(old, new) < convergence_tol * convergence_tol (one f32 product, strict); the seed takes `new` and is never examined
+ *                again.  *iterations_out counts the passes performed; max_iter = 0 performs none: shifted = seeds bit for bit.
+ *   M5 empty     an empty or zero-weight ball: the seed becomes NaN on all dim axes and is never examined again.  If the loop runs out of
+ *                active seeds after any seed became NaN, *iterations_out = max_iter.  A seed that comes in with a non-finite coordinate
+ *                behaves so from pass 1.
+ *   M6 grouping  rule 6 above with M1's d2: a ~ b iff d2(s_a, s_b) < cluster_tol * cluster_tol (one f32 product, strict); leaders by the
+ *                serial first-fit; clusters numbered by ascending leader index; labels_out[i] = the lowest-numbered cluster whose leader
+ *                is ~ i; a seed with a non-finite coordinate is ~ nobody: a cluster of its own.  cluster_tol = 0: every seed is a cluster.
+ *   M7 modes     rule 7 above per axis: member k of the list in partial sum k mod 64, the 64 partials added by a fixed tree, then
+ *                (float)(sum / size).
+ * seeds_or_null == NULL: every point is a seed (n_seeds is ignored).  mem says where points, seeds and the five output arrays live;
+ * n_clusters_out and iterations_out are host words.  Sizes that always suffice: shifted dim n_seeds, labels n_seeds, modes dim n_seeds,
+ * offsets n_seeds + 1, members n_seeds.  cilhip_ms_params is the 3-D entry's; form must be 0.
+ * Refused before a device is opened, nothing written, cilhip_last_error(NULL) naming the rule -- CILHIP_ERR_INVALID: dim == 0; form != 0;
+ * n or n_seeds >= 2^32 - 16; and everything the 3-D entry refuses (NULL points with n > 0, n_seeds > 0 with NULL seeds, a tolerance or
+ * radius that is not finite or is negative, an RBF sigma not finite and positive, unknown kernel_kind or mem, NULL params,
+ * n_clusters_out, iterations_out, or with at least one seed NULL shifted_seeds_out / labels_out); CILHIP_ERR_UNSUPPORTED: dim > 16.
+ * No seed at all: CILHIP_OK, zero clusters, zero iterations, no device needed.  n == 0 with seeds is legal: M5 for every seed.
+ * Not built: double, dim > 16, other distance adaptors, a caller's functor as kernel evaluator, a pruned search for large n, a sharded
+ * run. */
+int cilhip_mean_shift_nd(int device, const float* points, size_t n, size_t dim, const float* seeds_or_null, size_t n_seeds, int mem,
+                         const cilhip_ms_params* params, float* shifted_seeds_out /* n_seeds*dim */, uint32_t* labels_out,
+                         float* modes_out_or_null /* up to n_seeds*dim */, uint32_t* offsets_out_or_null, uint32_t* members_out_or_null,
+                         size_t* n_clusters_out, size_t* iterations_out);
+/* What the calling thread's last successful cilhip_mean_shift_nd did: the shift passes that ran (M5: *iterations_out can be larger), the
+ * grouping rounds, the slice count of the first and of the last pass (M3), host wall time of the passes and of the grouping. */
+typedef struct cilhip_msn_stats { size_t passes, rounds, slices_first, slices_last; double shift_ms, group_ms; } cilhip_msn_stats;
+int cilhip_msn_last_stats(cilhip_msn_stats* out);   /* the calling thread's last successful cilhip_mean_shift_nd */
 
 /* ---- depth images <-> points ------------------------------------------------------------------------------------ */
 /* core/image_point_cloud_conversions.hpp: DepthValueConverter / TruncatedDepthValueConverter (:7-51), the eight

@@ -6,6 +6,7 @@
 //                                              clustering/spectral_clustering.hpp, kmeans.hpp:67-194, utilities/nearest_neighbor_graph_utilities.hpp:89-118
 //                                              (the end of this file; cilhip_nn_graph_matrix, cilhip_spectral_embedding, cilhip_kmeans_nd)
 //   MeanShift3f                                clustering/mean_shift.hpp:12-140 (before that)
+//   MeanShiftXf, MeanShift2f                   clustering/mean_shift.hpp:142-164, over cilhip_mean_shift_nd (c_api.h rules M1-M7)
 //   Unity / Identity / RBFKernel WeightEvaluator               core/common_pair_evaluators.hpp:13-79
 //   ConnectedComponentExtraction3f             clustering/connected_component_extraction.hpp:368-428 (segment :394-422)
 //   the ClusteringBase accessors               clustering/clustering_base.hpp:60-97
@@ -271,6 +272,93 @@ private:
   std::vector<float> shifted_seeds_, cluster_modes_;
   ClusterToPointIndicesMap cluster_to_point_indices_map_;
   PointToClusterIndexMap point_to_cluster_index_map_;
+};
+
+// core/data_containers.hpp:73-122: non-owning view of a dim x n column-major float matrix
+struct ConstDataView {
+  const float* data_ = nullptr;
+  size_t rows_ = 0, cols_ = 0;
+  ConstDataView() = default;
+  ConstDataView(const float* d, size_t dim, size_t n) : data_(d), rows_(dim), cols_(n) {}
+  ConstDataView(const std::vector<float>& v, size_t dim) : data_(v.data()), rows_(dim), cols_(dim ? v.size() / dim : 0) {}
+  const float* data() const { return data_; }
+  size_t rows() const { return rows_; }
+  size_t cols() const { return cols_; }
+};
+
+// ---- MeanShiftXf / MeanShift2f (clustering/mean_shift.hpp:142-164; c_api.h rules M1-M7) ---------------------
+// MeanShift<float, Dynamic>: MeanShift3f's interface over a dim x n view, 1 <= dim <= 16; seeds, shifted seeds and modes are dim floats each.
+template <typename PointIndexT = size_t, typename ClusterIndexT = size_t>
+class MeanShiftXf {
+public:
+  typedef std::vector<std::vector<PointIndexT>> ClusterToPointIndicesMap;
+  typedef std::vector<ClusterIndexT> PointToClusterIndexMap;
+
+  // (max_leaf_size: the reference's kd-tree parameter, accepted and unused)
+  explicit MeanShiftXf(const ConstDataView& points, size_t max_leaf_size = 10, int device = 0) : points_(points), device_(device) { (void)max_leaf_size; }
+
+  // :38-115 -- given seeds
+  template <class KernelEvaluatorT = UnityWeightEvaluator<float>>
+  MeanShiftXf& cluster(const ConstDataView& seeds, float kernel_radius, size_t max_iter, float cluster_tol, float convergence_tol = std::numeric_limits<float>::epsilon(),
+                       const KernelEvaluatorT& evaluator = KernelEvaluatorT()) {
+    if (seeds.rows() != points_.rows()) throw std::invalid_argument("MeanShiftXf: the seeds have another dimension than the points");
+    return run(&seeds, kernel_radius, max_iter, cluster_tol, convergence_tol, evaluator.kind(), evaluator.sigma());
+  }
+  // :118-124 -- every point is a seed
+  template <class KernelEvaluatorT = UnityWeightEvaluator<float>>
+  MeanShiftXf& cluster(float kernel_radius, size_t max_iter, float cluster_tol, float convergence_tol = std::numeric_limits<float>::epsilon(),
+                       const KernelEvaluatorT& evaluator = KernelEvaluatorT()) {
+    return run(nullptr, kernel_radius, max_iter, cluster_tol, convergence_tol, evaluator.kind(), evaluator.sigma());
+  }
+
+  const std::vector<float>& getShiftedSeeds() const { return shifted_seeds_; }      // dim floats per seed
+  const std::vector<float>& getClusterModes() const { return cluster_modes_; }      // dim floats per cluster
+  size_t getNumberOfPerformedIterations() const { return iteration_count_; }
+  const ClusterToPointIndicesMap& getClusterToPointIndicesMap() const { return cluster_to_point_indices_map_; }
+  const PointToClusterIndexMap& getPointToClusterIndexMap() const { return point_to_cluster_index_map_; }
+  size_t getNumberOfClusters() const { return cluster_to_point_indices_map_.size(); }
+  size_t getNumberOfPoints() const { return point_to_cluster_index_map_.size(); }
+  size_t getDimension() const { return points_.rows(); }
+
+private:
+  MeanShiftXf& run(const ConstDataView* seeds, float kernel_radius, size_t max_iter, float cluster_tol, float convergence_tol, int kind, float sigma) {
+    const size_t dim = points_.rows(), ns = seeds ? seeds->cols() : points_.cols();
+    cilhip_ms_params prm;
+    cilhip_ms_default_params(&prm);
+    prm.kernel_radius = kernel_radius; prm.max_iter = max_iter; prm.cluster_tol = cluster_tol; prm.convergence_tol = convergence_tol;
+    prm.kernel_kind = kind; prm.kernel_sigma = sigma;
+    std::vector<float> shifted(dim * ns + 1), modes(dim * ns + 1), no_seed(dim + 1);
+    std::vector<uint32_t> labels(ns + 1), offsets(ns + 1), members(ns + 1);
+    size_t nc = 0, iters = 0;
+    const float* sp = seeds ? (seeds->cols() ? seeds->data() : no_seed.data()) : nullptr;      // (an empty list is still a list)
+    const int rc = cilhip_mean_shift_nd(device_, points_.data(), points_.cols(), dim, sp, seeds ? ns : 0, CILHIP_MEM_HOST, &prm, shifted.data(), labels.data(), modes.data(),
+                                        offsets.data(), members.data(), &nc, &iters);
+    if (rc != CILHIP_OK) throw std::runtime_error("cilhip_mean_shift_nd failed (rc " + std::to_string(rc) + "): " + cilhip_last_error(nullptr));
+    shifted_seeds_.assign(shifted.begin(), shifted.begin() + dim * ns);
+    cluster_modes_.assign(modes.begin(), modes.begin() + dim * nc);
+    iteration_count_ = iters;
+    cluster_to_point_indices_map_.assign(nc, std::vector<PointIndexT>());
+    for (size_t k = 0; k < nc; ++k) cluster_to_point_indices_map_[k].assign(members.begin() + offsets[k], members.begin() + offsets[k + 1]);
+    point_to_cluster_index_map_.assign(labels.begin(), labels.begin() + ns);
+    return *this;
+  }
+
+  ConstDataView points_;
+  int device_;
+  size_t iteration_count_ = 0;
+  std::vector<float> shifted_seeds_, cluster_modes_;
+  ClusterToPointIndicesMap cluster_to_point_indices_map_;
+  PointToClusterIndexMap point_to_cluster_index_map_;
+};
+
+// MeanShift<float, 2>
+template <typename PointIndexT = size_t, typename ClusterIndexT = size_t>
+class MeanShift2f : public MeanShiftXf<PointIndexT, ClusterIndexT> {
+public:
+  explicit MeanShift2f(const ConstDataView& points, size_t max_leaf_size = 10, int device = 0) : MeanShiftXf<PointIndexT, ClusterIndexT>(points, max_leaf_size, device) {
+    if (points.rows() != 2) throw std::invalid_argument("MeanShift2f: the points are a 2 x n matrix");
+  }
+  MeanShift2f(const float* xy, size_t n, int device = 0) : MeanShiftXf<PointIndexT, ClusterIndexT>(ConstDataView(xy, 2, n), 10, device) {}
 };
 
 // ---- SpectralClustering (clustering/spectral_clustering.hpp; c_api.h rules S1-S6) ---------------------------

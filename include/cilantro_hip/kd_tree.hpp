@@ -23,17 +23,7 @@
 
 namespace cilantro_hip {
 
-// core/data_containers.hpp:73-122: non-owning view of a dim x n column-major float matrix
-struct ConstDataView {
-  const float* data_ = nullptr;
-  size_t rows_ = 0, cols_ = 0;
-  ConstDataView() = default;
-  ConstDataView(const float* d, size_t dim, size_t n) : data_(d), rows_(dim), cols_(n) {}
-  ConstDataView(const std::vector<float>& v, size_t dim) : data_(v.data()), rows_(dim), cols_(dim ? v.size() / dim : 0) {}
-  const float* data() const { return data_; }
-  size_t rows() const { return rows_; }
-  size_t cols() const { return cols_; }
-};
+// (ConstDataView, the non-owning view of a dim x n column-major float matrix: clustering.hpp)
 
 // core/nearest_neighbors.hpp:49-77
 struct KNNNeighborhoodSpecification {
