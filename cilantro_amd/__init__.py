@@ -3,7 +3,8 @@ also reachable from the package itself (resolved on first use, so importing the 
 
 _KD_TREE = ("KDTree", "KDTree2f", "KDTreeXf", "KNNNeighborhoodSpecification", "KNNInRadiusNeighborhoodSpecification")
 _MEAN_SHIFT = ("MeanShift3f", "MeanShift2f", "MeanShiftXf", "mean_shift", "mean_shift_nd")
-__all__ = list(_KD_TREE + _MEAN_SHIFT)
+_COMPONENTS_ND = ("ConnectedComponentExtraction2f", "ConnectedComponentExtractionXf", "connected_components_nd")
+__all__ = list(_KD_TREE + _MEAN_SHIFT + _COMPONENTS_ND)
 
 
 def __getattr__(name):
@@ -11,7 +12,7 @@ def __getattr__(name):
         from . import kd_tree
 
         return getattr(kd_tree, name)
-    if name in _MEAN_SHIFT:
+    if name in _MEAN_SHIFT or name in _COMPONENTS_ND:
         from . import clustering
 
         return getattr(clustering, name)

@@ -41,6 +41,7 @@ SYMBOLS = [
     "cilhip_polytopes_interior_indices",
     "cilhip_knn_nd", "cilhip_radius_search_nd",
     "cilhip_mean_shift_nd", "cilhip_msn_last_stats",
+    "cilhip_connected_components_nd", "cilhip_ccn_last_stats", "cilhip_ccn_set_pair_cap",
 ]
 
 
@@ -115,6 +116,11 @@ class MsStats(C.Structure):
 
 class MsnStats(C.Structure):
     _fields_ = [("passes", C.c_size_t), ("rounds", C.c_size_t), ("slices_first", C.c_size_t), ("slices_last", C.c_size_t), ("shift_ms", C.c_double), ("group_ms", C.c_double)]
+
+
+class CcnStats(C.Structure):
+    _fields_ = [("form_used", C.c_int), ("axis", C.c_size_t), ("tiles_total", C.c_size_t), ("tiles_tested", C.c_size_t), ("launches", C.c_size_t), ("prep_ms", C.c_double),
+                ("hook_ms", C.c_double), ("finish_ms", C.c_double)]
 
 
 class McdParams(C.Structure):
@@ -279,6 +285,11 @@ def load():
     L.cilhip_mean_shift_nd.argtypes = [C.c_int, f32p, C.c_size_t, C.c_size_t, f32p, C.c_size_t, C.c_int, C.POINTER(MsParams), vp, vp, vp, vp, vp, C.POINTER(C.c_size_t),
                                        C.POINTER(C.c_size_t)]
     L.cilhip_msn_last_stats.argtypes = [C.POINTER(MsnStats)]
+    L.cilhip_connected_components_nd.argtypes = [C.c_int, f32p, f32p, f32p, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(CcParams), C.c_int, vp, C.c_size_t, vp, vp, vp,
+                                                 C.POINTER(C.c_size_t)]
+    L.cilhip_ccn_last_stats.argtypes = [C.POINTER(CcnStats)]
+    L.cilhip_ccn_set_pair_cap.argtypes = [C.c_size_t]
+    L.cilhip_ccn_set_pair_cap.restype = None
     L.cilhip_mcd_params_default.argtypes = [C.POINTER(McdParams)]
     L.cilhip_mcd_params_default.restype = None
     L.cilhip_robust_normals_knn3f.argtypes = [C.c_int, f32p, C.c_size_t, C.c_int, C.POINTER(McdParams), f32p, f32p, f32p, vp, vp]
@@ -376,7 +387,7 @@ def load():
     for name in SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
         if name not in ("cilhip_destroy", "cilhip_last_error", "cilhip_icp_default_params", "cilhip_option_info", "cilhip_cc_default_params", "cilhip_ms_default_params", "cilhip_mcd_params_default", "cilhip_depth_default_converter", "cilhip_fusion_default_params", "cilhip_warp_default_params", "cilhip_warp_field_destroy", "cilhip_sparse_destroy",
-                        "cilhip_spectral_default_params", "cilhip_mds_default_params", "cilhip_convex_hull_destroy"):
+                        "cilhip_spectral_default_params", "cilhip_mds_default_params", "cilhip_convex_hull_destroy", "cilhip_ccn_set_pair_cap"):
             fn.restype = C.c_int
     _lib = L
     return L

@@ -1,8 +1,8 @@
-"""Python mirrors of cilantro's KMeans3f (clustering/kmeans.hpp), ConnectedComponentExtraction3f
+"""Python mirrors of cilantro's KMeans3f (clustering/kmeans.hpp), ConnectedComponentExtraction3f / 2f / Xf
 (clustering/connected_component_extraction.hpp; second part of this file), MeanShift3f / MeanShift2f / MeanShiftXf
 (clustering/mean_shift.hpp; third part) and SpectralClustering with KMeansXf and the sparse nearest-neighbour graph matrix (clustering/spectral_clustering.hpp; last part) on top
-of the C ABI (cilhip_kmeans3f, cilhip_connected_components3f, cilhip_mean_shift3f, cilhip_mean_shift_nd, cilhip_nn_graph_matrix / cilhip_spectral_embedding /
-cilhip_kmeans_nd).
+of the C ABI (cilhip_kmeans3f, cilhip_connected_components3f, cilhip_connected_components_nd, cilhip_mean_shift3f, cilhip_mean_shift_nd, cilhip_nn_graph_matrix /
+cilhip_spectral_embedding / cilhip_kmeans_nd).
 
     km = KMeans3f(points)
     km.cluster(initial_centroids, max_iter=100, tol=eps)      # kmeans.hpp:24-30
@@ -324,6 +324,99 @@ class ConnectedComponentExtraction3f:
 
     def getUnlabeledPointIndices(self):
         return self._members[int(self._offsets[-1]):]
+
+
+# ---- ConnectedComponentExtractionXf / 2f (connected_component_extraction.hpp:162-265, :394-457 for EigenDim 2 and Dynamic) -----------
+# The contract is stated in include/cilantro_hip/c_api.h (cilhip_connected_components_nd, rules C1-C5) and DESIGN.md section 23.
+def connected_components_nd(points, radius_sq, evaluator=None, min_segment_size=1, max_segment_size=SIZE_MAX, seeds=None, form=0, device=0, stats=None):
+    """cilhip_connected_components_nd over n x dim points (1 <= dim <= 16) -> (labels[n], offsets[segments + 1], members[n]) as
+    connected_components() returns them.  The evaluator's normals are n x dim, its colours n x 3.  form: 0 the code decides, 1 the
+    exhaustive triangle, 2 sweep and prune (the same words, rule C4).  stats: a dict that receives cilhip_ccn_last_stats.  numpy arrays
+    in -> numpy arrays out; device tensors in -> device tensors out"""
+    L = capi.load()
+    ev = evaluator if evaluator is not None else AlwaysTrueEvaluator()
+    x, p, n, dim, on_device = _as_rows(points, "the points")
+    ptrs, keep = [None, None], [x]
+    for k, (att, width, what) in enumerate(((ev.normals, dim, "the normals"), (ev.colors, 3, "the colours"))):
+        if att is None:
+            continue
+        ax, ap, an, adim, a_dev = _as_rows(att, what)
+        if an != n or adim != width:
+            raise ValueError("the normals are an n x dim array and the colours an n x 3 array over the points' n")
+        if a_dev != on_device:
+            raise ValueError("points, normals and colors must live in the same memory space")
+        ptrs[k] = ap
+        keep.append(ax)
+    prm = capi.CcParams()
+    L.cilhip_cc_default_params(C.byref(prm))
+    prm.radius_sq = radius_sq
+    if ev.max_distance is not None:
+        prm.use_distance, prm.max_distance = 1, ev.max_distance
+    if ev.max_angle is not None:
+        prm.use_normals, prm.max_angle, prm.angle_inclusive = 1, ev.max_angle, int(ev.angle_inclusive)
+    if ev.color_thresh is not None:
+        prm.use_colors, prm.color_thresh = 1, ev.color_thresh
+    prm.min_segment_size, prm.max_segment_size = int(min_segment_size), min(int(max_segment_size), SIZE_MAX)
+    sp, ns, skeep = _cc_seeds(seeds)
+    dev = None
+    if on_device:
+        import torch
+
+        dev = x.device
+        if dev.index is not None:
+            device = dev.index
+        torch.cuda.synchronize(dev)      # the call runs on a stream of its own: the inputs must be complete
+    outs, addr = _cc_outputs(n, on_device, dev)
+    nseg = C.c_size_t(0)
+    rc = L.cilhip_connected_components_nd(int(device), p if n else None, ptrs[0], ptrs[1], n, dim, capi.MEM_DEVICE if on_device else capi.MEM_HOST, C.byref(prm), int(form), sp, ns,
+                                          addr[0], addr[1], addr[2], C.byref(nseg))
+    if rc != capi.OK:
+        raise capi.CilhipError(rc, "cilhip_connected_components_nd: " + L.cilhip_last_error(None).decode())
+    if n == 0:
+        outs[1][:1] = 0
+    elif stats is not None:
+        st = capi.CcnStats()
+        L.cilhip_ccn_last_stats(C.byref(st))
+        stats.update({k: getattr(st, k) for k, _ in capi.CcnStats._fields_})
+    return _cc_result(outs, nseg.value, on_device)
+
+
+class ConnectedComponentExtractionXf(ConnectedComponentExtraction3f):
+    """ConnectedComponentExtraction<float, Dynamic> (connected_component_extraction.hpp:368-457): ConnectedComponentExtraction3f's
+    segment() forms and accessors over n x dim points, 1 <= dim <= 16.  dim, when given, is checked against the points.  form: see
+    connected_components_nd(); getLastStats(): what the last segment() did (cilhip_ccn_stats)."""
+
+    def __init__(self, points, dim=None, device=0, form=0):
+        super().__init__(points, device)
+        if getattr(points, "ndim", None) != 2 or (dim is not None and int(points.shape[1]) != int(dim)):
+            raise ValueError("the points are an n x dim array" if dim is None else f"the points are an n x {int(dim)} array")
+        self.dim = int(points.shape[1])
+        self._form = form
+        self._stats = {}
+
+    def segment(self, nh, *args, **kw):
+        if not isinstance(nh, RadiusNeighborhoodSpecification):
+            raise TypeError("segment() takes a RadiusNeighborhoodSpecification (other neighbourhoods: connected_components_from_lists)")
+        args = list(args)
+        seeds = kw.pop("seeds", None)
+        if args and args[0] is not None and not isinstance(args[0], AlwaysTrueEvaluator):
+            seeds = args.pop(0)      # segment(nh, seeds_ind, evaluator, min, max)
+        for k, v in zip(("evaluator", "min_segment_size", "max_segment_size"), args):
+            kw[k] = v
+        self._stats = {}
+        self._labels, self._offsets, self._members = connected_components_nd(self._points, nh.radius, kw.get("evaluator"), kw.get("min_segment_size", 1),
+                                                                             kw.get("max_segment_size", SIZE_MAX), seeds, self._form, self._device, self._stats)
+        return self
+
+    def getLastStats(self):
+        return dict(self._stats)
+
+
+class ConnectedComponentExtraction2f(ConnectedComponentExtractionXf):
+    """ConnectedComponentExtraction<float, 2>"""
+
+    def __init__(self, points, device=0, form=0):
+        super().__init__(points, 2, device, form)
 
 
 # ---- MeanShift3f (clustering/mean_shift.hpp) ------------------------------------------------------------------------------------

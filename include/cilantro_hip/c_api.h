@@ -696,6 +696,51 @@ int cilhip_mean_shift_nd(int device, const float* points, size_t n, size_t dim, 
 typedef struct cilhip_msn_stats { size_t passes, rounds, slices_first, slices_last; double shift_ms, group_ms; } cilhip_msn_stats;
 int cilhip_msn_last_stats(cilhip_msn_stats* out);   /* the calling thread's last successful cilhip_mean_shift_nd */
 
+/* ---- connected-component segmentation in 1 to 16 dimensions ------------------------------------------
+ * cilantro's ConnectedComponentExtraction<float, EigenDim>::segment with a RadiusNeighborhoodSpecification for EigenDim 2 and Dynamic
+ * (clustering/connected_component_extraction.hpp:162-265, :394-457) and the evaluator templates of core/common_pair_evaluators.hpp:92-259.
+ * points and normals are point-major n x dim arrays (the layout of cilhip_knn_nd), rgb is n x 3.  cilhip_cc_params is the 3-D entry's.
+ * No neighbour list is ever written.  DESIGN.md section 23 is the long form; the rules:
+ *   C1 graph      points i != j are joined iff d2(i, j) < radius_sq (strict, connected_component_extraction.hpp:201-204) and every selected
+ *                 clause holds.  d2 is rule N1 of cilhip_knn_nd (groups of four coordinates, then the tail, every operation rounded, nothing
+ *                 contracted; dim = 3: the 3-D entry's d2 bit for bit).  A row with a non-finite coordinate has no neighbours: its d2 is NaN
+ *                 or +inf.  Finite coordinates whose d2 overflows are not joined.  radius_sq <= 0: every point is a singleton.
+ *   C2 clauses    use_distance: d2 < max_distance (common_pair_evaluators.hpp:100, :159, :185, :243).  use_colors: exactly as in
+ *                 cilhip_connected_components3f; colours always have 3 components (:136-141).  use_normals: dot = c_0 + (c_1 + (... +
+ *                 c_{dim-1})) with c_a = n_ia * n_ja, every product and sum rounded to f32, no contraction, folded from the last axis
+ *                 (dim = 3: the 3-D entry's x x' + (y y' + z z') bit for bit); angle = (float)acos((double)dot); max_angle >= 0: angle <|
+ *                 max_angle, otherwise min(angle, (float)M_PI - angle) <| -max_angle; <| is <= when angle_inclusive != 0 (:119-121) and <
+ *                 otherwise (:162-164, :213-215, :247-249).  A dot above 1 gives NaN: not similar.  Stated deviation: Eigen's summation
+ *                 order for dynamic sizes is not restated, and nothing is checked against a compiled reference.
+ *   C3 output     everything after the edges is word for word cilhip_connected_components3f's: sizes, min / max_segment_size (:246-261),
+ *                 order by size descending then lowest member, labels (clustering_base.hpp:10-11), CSR lists with the unlabelled tail,
+ *                 seeds_or_null (a HOST array; NULL: every point is a seed; non-NULL with n_seeds == 0: no segment), mem, and n == 0
+ *                 (CILHIP_OK, zero segments) without a device.
+ *   C4 repeatable a component's root is its lowest original index whatever happened in between: two runs, and forms 1 and 2, agree on every
+ *                 output word.
+ *   C5 refusals   before a device is opened, outputs untouched, cilhip_last_error(NULL) naming the rule -- CILHIP_ERR_INVALID: dim == 0;
+ *                 form outside 0..2; n >= 2^32 - 16; and everything the 3-D entry refuses (a normals or colours clause without its array, a
+ *                 seed index >= n, n_seeds > 0 with NULL seeds, unknown mem, radius_sq not finite, NULL params / points / labels_out /
+ *                 n_segments_out); CILHIP_ERR_UNSUPPORTED: dim > 16.
+ * form: 1 the exhaustive triangle -- every pair of points is tested once; 2 sweep and prune, exact -- rows with a non-finite coordinate are
+ * set aside (singletons), the others sorted along the axis of largest finite extent (lowest axis on ties), and a tile of 256 sorted rows is
+ * not tested against a tile that lies R or more before it on that axis, R the smallest f32 with fl(R * R) >= radius_sq: rounding is
+ * monotone and N1 adds only non-negative rounded terms, so such a pair has d2 >= radius_sq; 0 the code decides (2 from n = 65 536 up: below
+ * that the sort costs more than it saves, measured on a uniform cloud).
+ * Not built: double, dim > 16, other distance adaptors, kNN neighbourhoods fused in N-D, a caller's functor (both: cilhip_knn_nd /
+ * cilhip_radius_search_nd + cilhip_connected_components_lists), a sharded run. */
+int cilhip_connected_components_nd(int device, const float* points, const float* normals_or_null, const float* rgb_or_null, size_t n, size_t dim,
+                                   int mem, const cilhip_cc_params* params, int form, const uint32_t* seeds_or_null, size_t n_seeds,
+                                   uint32_t* labels_out, uint32_t* offsets_out_or_null, uint32_t* members_out_or_null, size_t* n_segments_out);
+/* What the calling thread's last successful cilhip_connected_components_nd did: the form that ran, form 2's sweep axis, the 256 x 256 tile
+ * pairs of the triangle and those tested, the hook launches, host wall time of the preparation (staging, sort, plan), of the hook launches
+ * and of everything after them. */
+typedef struct cilhip_ccn_stats { int form_used; size_t axis, tiles_total, tiles_tested, launches; double prep_ms, hook_ms, finish_ms; } cilhip_ccn_stats;
+int cilhip_ccn_last_stats(cilhip_ccn_stats* out);   /* the calling thread's last successful call */
+/* No hook launch tests more than max_pairs_per_launch pairs (0: the default, 6e10 -- under a quarter of a second at the slowest measured N-D
+ * pair rate); per calling thread.  For tests of the cut into launches: the result does not depend on it (C4). */
+void cilhip_ccn_set_pair_cap(size_t max_pairs_per_launch);
+
 /* ---- depth images <-> points ------------------------------------------------------------------------------------ */
 /* core/image_point_cloud_conversions.hpp: DepthValueConverter / TruncatedDepthValueConverter (:7-51), the eight
  * depthImageToPoints[Normals] / RGBDImagesToPoints[Normals]Colors overloads (:53-695), pointsToDepthImage /

@@ -9,6 +9,7 @@
 //   MeanShiftXf, MeanShift2f                   clustering/mean_shift.hpp:142-164, over cilhip_mean_shift_nd (c_api.h rules M1-M7)
 //   Unity / Identity / RBFKernel WeightEvaluator               core/common_pair_evaluators.hpp:13-79
 //   ConnectedComponentExtraction3f             clustering/connected_component_extraction.hpp:368-428 (segment :394-422)
+//   ConnectedComponentExtractionXf, 2f         clustering/connected_component_extraction.hpp:368-457, over cilhip_connected_components_nd (c_api.h rules C1-C5)
 //   the ClusteringBase accessors               clustering/clustering_base.hpp:60-97
 //   RadiusNeighborhoodSpecification<float>     core/nearest_neighbors.hpp (the radius is a SQUARED distance)
 //   AlwaysTrueEvaluator and the seven proximity evaluators      core/common_pair_evaluators.hpp:84-259, constructor arguments in the reference's order
@@ -36,19 +37,41 @@ struct RadiusNeighborhoodSpecification {
   explicit RadiusNeighborhoodSpecification(ScalarT radius_sq = (ScalarT)0) : radius(radius_sq) {}
 };
 
+// core/data_containers.hpp:73-122: non-owning view of a dim x n column-major float matrix
+struct ConstDataView {
+  const float* data_ = nullptr;
+  size_t rows_ = 0, cols_ = 0;
+  ConstDataView() = default;
+  ConstDataView(const float* d, size_t dim, size_t n) : data_(d), rows_(dim), cols_(n) {}
+  ConstDataView(const std::vector<float>& v, size_t dim) : data_(v.data()), rows_(dim), cols_(dim ? v.size() / dim : 0) {}
+  const float* data() const { return data_; }
+  size_t rows() const { return rows_; }
+  size_t cols() const { return cols_; }
+};
+
 // what an evaluator asks of a pair: the clauses of cilhip_cc_params and the arrays they read
 struct PointSimilarityClauses {
   const float* normals = nullptr;
   const float* colors = nullptr;
   size_t count = 0;      // rows of the arrays (0: no array)
+  size_t normals_dim = 3;      // components of a normal: 3 (a ConstPointsView) or the rows of a ConstDataView (ConnectedComponentExtractionXf)
   bool use_distance = false, use_normals = false, use_colors = false, angle_inclusive = false;
   float max_distance = 0.0f, max_angle = 0.0f, color_thresh = 0.0f;
 };
 
 namespace detail {
-inline PointSimilarityClauses clauses(const ConstPointsView* normals, const ConstPointsView* colors, const float* dist, const float* angle, const float* color, bool inclusive) {
+// an evaluator's normals: a 3 x n view, or the N-D view of a dim x n matrix
+struct NormalsRef {
+  const float* data_;
+  size_t dim_, cols_;
+  NormalsRef(const ConstPointsView& v) : data_(v.data()), dim_(3), cols_(v.cols()) {}
+  NormalsRef(const ConstDataView& v) : data_(v.data()), dim_(v.rows()), cols_(v.cols()) {}
+  const float* data() const { return data_; }
+  size_t cols() const { return cols_; }
+};
+inline PointSimilarityClauses clauses(const NormalsRef* normals, const ConstPointsView* colors, const float* dist, const float* angle, const float* color, bool inclusive) {
   PointSimilarityClauses c;
-  if (normals) { c.normals = normals->data(); c.count = normals->cols(); }
+  if (normals) { c.normals = normals->data(); c.count = normals->cols(); c.normals_dim = normals->dim_; }
   if (colors) { c.colors = colors->data(); c.count = colors->cols(); }
   if (normals && colors && normals->cols() != colors->cols()) throw std::invalid_argument("evaluator: normals and colors differ in size");
   if (dist) { c.use_distance = true; c.max_distance = *dist; }
@@ -71,9 +94,10 @@ private:
 class NormalsProximityEvaluator {      // :106-128 -- the one class whose angle test is <= (:119-121)
 public:
   NormalsProximityEvaluator(const ConstPointsView& normals, float angle_thresh) : n_(normals), a_(angle_thresh) {}
+  NormalsProximityEvaluator(const ConstDataView& normals, float angle_thresh) : n_(normals), a_(angle_thresh) {}      // dim-component normals
   PointSimilarityClauses clauses() const { return detail::clauses(&n_, nullptr, nullptr, &a_, nullptr, true); }
 private:
-  ConstPointsView n_;
+  detail::NormalsRef n_;
   float a_;
 };
 class ColorsProximityEvaluator {      // :130-146
@@ -87,9 +111,10 @@ private:
 class PointsNormalsProximityEvaluator {      // :148-172
 public:
   PointsNormalsProximityEvaluator(const ConstPointsView& normals, float dist_thresh, float angle_thresh) : n_(normals), d_(dist_thresh), a_(angle_thresh) {}
+  PointsNormalsProximityEvaluator(const ConstDataView& normals, float dist_thresh, float angle_thresh) : n_(normals), d_(dist_thresh), a_(angle_thresh) {}
   PointSimilarityClauses clauses() const { return detail::clauses(&n_, nullptr, &d_, &a_, nullptr, false); }
 private:
-  ConstPointsView n_;
+  detail::NormalsRef n_;
   float d_, a_;
 };
 class PointsColorsProximityEvaluator {      // :174-193
@@ -104,18 +129,24 @@ class NormalsColorsProximityEvaluator {      // :195-224
 public:
   NormalsColorsProximityEvaluator(const ConstPointsView& normals, const ConstPointsView& colors, float angle_thresh, float color_thresh)
       : n_(normals), c_(colors), a_(angle_thresh), t_(color_thresh) {}
+  NormalsColorsProximityEvaluator(const ConstDataView& normals, const ConstPointsView& colors, float angle_thresh, float color_thresh)
+      : n_(normals), c_(colors), a_(angle_thresh), t_(color_thresh) {}
   PointSimilarityClauses clauses() const { return detail::clauses(&n_, &c_, nullptr, &a_, &t_, false); }
 private:
-  ConstPointsView n_, c_;
+  detail::NormalsRef n_;
+  ConstPointsView c_;
   float a_, t_;
 };
 class PointsNormalsColorsProximityEvaluator {      // :226-259
 public:
   PointsNormalsColorsProximityEvaluator(const ConstPointsView& normals, const ConstPointsView& colors, float dist_thresh, float angle_thresh, float color_thresh)
       : n_(normals), c_(colors), d_(dist_thresh), a_(angle_thresh), t_(color_thresh) {}
+  PointsNormalsColorsProximityEvaluator(const ConstDataView& normals, const ConstPointsView& colors, float dist_thresh, float angle_thresh, float color_thresh)
+      : n_(normals), c_(colors), d_(dist_thresh), a_(angle_thresh), t_(color_thresh) {}
   PointSimilarityClauses clauses() const { return detail::clauses(&n_, &c_, &d_, &a_, &t_, false); }
 private:
-  ConstPointsView n_, c_;
+  detail::NormalsRef n_;
+  ConstPointsView c_;
   float d_, a_, t_;
 };
 
@@ -154,6 +185,7 @@ private:
                                       size_t max_size) {
     const size_t n = points_.cols();
     if (c.count != 0 && c.count != n) throw std::invalid_argument("segment: the evaluator's arrays and the points differ in size");
+    if (c.use_normals && c.normals_dim != 3) throw std::invalid_argument("segment: the evaluator's normals are not 3 x n");
     cilhip_cc_params prm;
     cilhip_cc_default_params(&prm);
     prm.radius_sq = nh.radius;
@@ -189,6 +221,97 @@ private:
   int device_;
   ClusterToPointIndicesMap cluster_to_point_indices_map_;
   PointToClusterIndexMap point_to_cluster_index_map_;
+};
+
+// ---- ConnectedComponentExtractionXf / 2f (connected_component_extraction.hpp:368-457; c_api.h rules C1-C5) --------
+// ConnectedComponentExtraction<float, Dynamic>: ConnectedComponentExtraction3f's interface over a dim x n view, 1 <= dim <= 16.  An
+// evaluator's normals are a ConstDataView of dim x n, its colours a ConstPointsView (3 x n).  form: 0 the code decides, 1 the exhaustive
+// triangle, 2 sweep and prune -- the same words (rule C4).
+template <typename PointIndexT = size_t, typename ClusterIndexT = size_t>
+class ConnectedComponentExtractionXf {
+public:
+  typedef std::vector<std::vector<PointIndexT>> ClusterToPointIndicesMap;
+  typedef std::vector<ClusterIndexT> PointToClusterIndexMap;
+
+  explicit ConnectedComponentExtractionXf(const ConstDataView& points, int device = 0, int form = 0) : points_(points), device_(device), form_(form) {}
+
+  // :409-422 -- every point is a seed
+  template <class PointSimilarityEvaluator = AlwaysTrueEvaluator>
+  ConnectedComponentExtractionXf& segment(const RadiusNeighborhoodSpecification<float>& nh, const PointSimilarityEvaluator& evaluator = PointSimilarityEvaluator(),
+                                          size_t min_segment_size = 1, size_t max_segment_size = std::numeric_limits<size_t>::max()) {
+    return run(nh, nullptr, evaluator.clauses(), min_segment_size, max_segment_size);
+  }
+  // :394-407 -- only the components that hold a seed
+  template <class PointSimilarityEvaluator = AlwaysTrueEvaluator>
+  ConnectedComponentExtractionXf& segment(const RadiusNeighborhoodSpecification<float>& nh, const std::vector<PointIndexT>& seeds_ind,
+                                          const PointSimilarityEvaluator& evaluator = PointSimilarityEvaluator(), size_t min_segment_size = 1,
+                                          size_t max_segment_size = std::numeric_limits<size_t>::max()) {
+    return run(nh, &seeds_ind, evaluator.clauses(), min_segment_size, max_segment_size);
+  }
+
+  const ClusterToPointIndicesMap& getClusterToPointIndicesMap() const { return cluster_to_point_indices_map_; }
+  const PointToClusterIndexMap& getPointToClusterIndexMap() const { return point_to_cluster_index_map_; }
+  size_t getNumberOfClusters() const { return cluster_to_point_indices_map_.size(); }
+  size_t getNumberOfPoints() const { return point_to_cluster_index_map_.size(); }
+  size_t getDimension() const { return points_.rows(); }
+  std::vector<PointIndexT> getLabeledPointIndices() const { return select(true); }        // clustering_base.hpp:36-45
+  std::vector<PointIndexT> getUnlabeledPointIndices() const { return select(false); }     // :49-58
+  const cilhip_ccn_stats& getLastStats() const { return stats_; }      // what the last segment() did (zeros before one, and after one over no point)
+
+private:
+  ConnectedComponentExtractionXf& run(const RadiusNeighborhoodSpecification<float>& nh, const std::vector<PointIndexT>* seeds, const PointSimilarityClauses& c, size_t min_size,
+                                      size_t max_size) {
+    const size_t n = points_.cols(), dim = points_.rows();
+    if (c.count != 0 && c.count != n) throw std::invalid_argument("segment: the evaluator's arrays and the points differ in size");
+    if (c.use_normals && c.normals_dim != dim) throw std::invalid_argument("segment: the evaluator's normals are not dim x n");
+    cilhip_cc_params prm;
+    cilhip_cc_default_params(&prm);
+    prm.radius_sq = nh.radius;
+    prm.use_distance = c.use_distance; prm.max_distance = c.max_distance;
+    prm.use_normals = c.use_normals; prm.max_angle = c.max_angle; prm.angle_inclusive = c.angle_inclusive;
+    prm.use_colors = c.use_colors; prm.color_thresh = c.color_thresh;
+    prm.min_segment_size = min_size; prm.max_segment_size = max_size;
+    std::vector<uint32_t> seed32(seeds ? seeds->size() + 1 : 0);      // (+ 1: an empty list is still a list)
+    if (seeds)
+      for (size_t k = 0; k < seeds->size(); ++k) {
+        if ((size_t)(*seeds)[k] >= n) throw std::invalid_argument("segment: a seed index is not below the number of points");
+        seed32[k] = (uint32_t)(*seeds)[k];
+      }
+    std::vector<uint32_t> labels(n + 1), offsets(n + 1), members(n + 1);
+    size_t nseg = 0;
+    const int rc = cilhip_connected_components_nd(device_, points_.data(), c.normals, c.colors, n, dim, CILHIP_MEM_HOST, &prm, form_, seeds ? seed32.data() : nullptr,
+                                                  seeds ? seeds->size() : 0, labels.data(), offsets.data(), members.data(), &nseg);
+    if (rc != CILHIP_OK) throw std::runtime_error("cilhip_connected_components_nd failed (rc " + std::to_string(rc) + "): " + cilhip_last_error(nullptr));
+    stats_ = cilhip_ccn_stats();
+    if (n) cilhip_ccn_last_stats(&stats_);
+    cluster_to_point_indices_map_.assign(nseg, std::vector<PointIndexT>());
+    for (size_t k = 0; k < nseg; ++k) cluster_to_point_indices_map_[k].assign(members.begin() + offsets[k], members.begin() + offsets[k + 1]);
+    point_to_cluster_index_map_.assign(labels.begin(), labels.begin() + n);
+    return *this;
+  }
+  std::vector<PointIndexT> select(bool labeled) const {
+    std::vector<PointIndexT> res;
+    const size_t k = getNumberOfClusters();
+    for (size_t i = 0; i < point_to_cluster_index_map_.size(); ++i)
+      if (((size_t)point_to_cluster_index_map_[i] < k) == labeled) res.push_back((PointIndexT)i);
+    return res;
+  }
+
+  ConstDataView points_;
+  int device_, form_;
+  cilhip_ccn_stats stats_ = cilhip_ccn_stats();
+  ClusterToPointIndicesMap cluster_to_point_indices_map_;
+  PointToClusterIndexMap point_to_cluster_index_map_;
+};
+
+// ConnectedComponentExtraction<float, 2>
+template <typename PointIndexT = size_t, typename ClusterIndexT = size_t>
+class ConnectedComponentExtraction2f : public ConnectedComponentExtractionXf<PointIndexT, ClusterIndexT> {
+public:
+  explicit ConnectedComponentExtraction2f(const ConstDataView& points, int device = 0, int form = 0) : ConnectedComponentExtractionXf<PointIndexT, ClusterIndexT>(points, device, form) {
+    if (points.rows() != 2) throw std::invalid_argument("ConnectedComponentExtraction2f: the points are a 2 x n matrix");
+  }
+  ConnectedComponentExtraction2f(const float* xy, size_t n, int device = 0) : ConnectedComponentExtractionXf<PointIndexT, ClusterIndexT>(ConstDataView(xy, 2, n), device, 0) {}
 };
 
 // ---- MeanShift3f -----------------------------------------------------------------------------------------------------------------
@@ -272,18 +395,6 @@ private:
   std::vector<float> shifted_seeds_, cluster_modes_;
   ClusterToPointIndicesMap cluster_to_point_indices_map_;
   PointToClusterIndexMap point_to_cluster_index_map_;
-};
-
-// core/data_containers.hpp:73-122: non-owning view of a dim x n column-major float matrix
-struct ConstDataView {
-  const float* data_ = nullptr;
-  size_t rows_ = 0, cols_ = 0;
-  ConstDataView() = default;
-  ConstDataView(const float* d, size_t dim, size_t n) : data_(d), rows_(dim), cols_(n) {}
-  ConstDataView(const std::vector<float>& v, size_t dim) : data_(v.data()), rows_(dim), cols_(dim ? v.size() / dim : 0) {}
-  const float* data() const { return data_; }
-  size_t rows() const { return rows_; }
-  size_t cols() const { return cols_; }
 };
 
 // ---- MeanShiftXf / MeanShift2f (clustering/mean_shift.hpp:142-164; c_api.h rules M1-M7) ---------------------
