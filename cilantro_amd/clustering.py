@@ -17,8 +17,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import capi
-from .icp import _as_cloud
+from . import _abi, capi
+from .kd_tree import RadiusNeighborhoodSpecification      # noqa: F401 (its home; this module's name for it stays)
 
 
 class KMeans3f:
@@ -31,7 +31,7 @@ class KMeans3f:
         self.iteration_count_ = 0
 
     def cluster(self, centroids_or_k, max_iter=100, tol=float(np.finfo(np.float32).eps), use_kd_tree=False, seed=None):
-        p, n, mem, keep = _as_cloud(self._data)
+        p, n, mem, keep = _abi.cloud(self._data)
         if np.isscalar(centroids_or_k):
             # kmeans.hpp:32-53 draws distinct random points (std::random_device): same law, numpy generator
             k = max(1, min(int(centroids_or_k), n))
@@ -77,7 +77,7 @@ def set_pruning(on=True):
 
 def kmeans_assign(data, centroids, device=0, use_kd_tree=False):
     L = capi.load()
-    p, n, mem, keep = _as_cloud(data)
+    p, n, mem, keep = _abi.cloud(data)
     cent = np.ascontiguousarray(centroids, np.float32).reshape(-1, 3)
     labels = np.zeros(n, np.uint32)
     rc = L.cilhip_kmeans3f_assign_ex(device, p, n, mem, cent.ctypes.data, len(cent), int(bool(use_kd_tree)), labels.ctypes.data)
@@ -90,13 +90,6 @@ def kmeans_assign(data, centroids, device=0, use_kd_tree=False):
 # The contract is stated in include/cilantro_hip/c_api.h (cilhip_connected_components3f) and DESIGN.md section 11.  numpy arrays in ->
 # numpy arrays out; device tensors in -> device tensors out.  There is no CPU path: without a usable device every entry raises.
 SIZE_MAX = (1 << (8 * C.sizeof(C.c_size_t))) - 1
-
-
-class RadiusNeighborhoodSpecification:
-    """core/nearest_neighbors.hpp: the radius is the SQUARED distance, as in the reference"""
-
-    def __init__(self, radius_sq):
-        self.radius = float(radius_sq)
 
 
 class AlwaysTrueEvaluator:
@@ -172,45 +165,37 @@ def _cc_seeds(seeds):
     return keep.ctypes.data, s.size, keep
 
 
-def _cc_outputs(n, on_device, dev):
-    if on_device:
-        import torch
-
-        outs = [torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n + 1, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)]
-        return outs, [o.data_ptr() for o in outs]
-    outs = [np.empty(n, np.uint32), np.empty(n + 1, np.uint32), np.empty(n, np.uint32)]
-    return outs, [o.ctypes.data for o in outs]
-
-
-def _cc_result(outs, nseg, on_device):
+def _segments(labels, offsets, members, nseg):
     """-> (labels, offsets[nseg + 1], members[n]) as int64"""
-    labels, offsets, members = outs
-    if on_device:
-        import torch
-
-        # (uint32 words in int32 tensors: widen without the sign)
-        wide = lambda t: t.to(torch.int64) & 0xFFFFFFFF      # noqa: E731
-        return wide(labels), wide(offsets[: nseg + 1]), wide(members)
-    return labels.astype(np.int64), offsets[: nseg + 1].astype(np.int64), members.astype(np.int64)
+    return _abi.widen(labels), _abi.widen(offsets[: nseg + 1]), _abi.widen(members)
 
 
-def connected_components(points, radius_sq, evaluator=None, min_segment_size=1, max_segment_size=SIZE_MAX, seeds=None, device=0):
-    """cilhip_connected_components3f -> (labels[n], offsets[segments + 1], members[n]): segment k is members[offsets[k]:offsets[k + 1]],
-    members[offsets[-1]:] are the unlabelled points; labels[i] == segments for those"""
+def _cloud(a, what):
+    return _abi.rows(a, 3, "clouds", none_ok=True)
+
+
+def _nd_rows(a, what):
+    return _abi.rows(a, None, what, cast=True)
+
+
+def _connected_components(nd, points, radius_sq, evaluator, min_segment_size, max_segment_size, seeds, device, form=0, stats=None):
+    """the one body of connected_components() (N x 3 clouds, float32 or TypeError) and connected_components_nd() (n x dim, converted)"""
     L = capi.load()
     ev = evaluator if evaluator is not None else AlwaysTrueEvaluator()
-    p, n, mem, keep_p = _as_cloud(points)
-    ptrs, keep = [None, None], [keep_p]
-    for k, att in enumerate((ev.normals, ev.colors)):
+    take = _nd_rows if nd else _cloud
+    x = take(points, "the points")
+    ptrs, keep = [None, None], [x.keep]
+    for k, (att, width, what) in enumerate(((ev.normals, x.dim, "the normals"), (ev.colors, 3, "the colours"))):
         if att is None:
             continue
-        ap, an, amem, akeep = _as_cloud(att)
-        if an != n:
-            raise ValueError("points, normals and colors must have the same number of rows")
-        if amem != mem:
+        a = take(att, what)
+        if a.n != x.n or (nd and a.dim != width):
+            raise ValueError("the normals are an n x dim array and the colours an n x 3 array over the points' n" if nd else
+                             "points, normals and colors must have the same number of rows")
+        if a.mem != x.mem:
             raise ValueError("points, normals and colors must live in the same memory space")
-        ptrs[k] = ap
-        keep.append(akeep)
+        ptrs[k] = a.ptr
+        keep.append(a.keep)
     prm = capi.CcParams()
     L.cilhip_cc_default_params(C.byref(prm))
     prm.radius_sq = radius_sq
@@ -222,23 +207,29 @@ def connected_components(points, radius_sq, evaluator=None, min_segment_size=1, 
         prm.use_colors, prm.color_thresh = 1, ev.color_thresh
     prm.min_segment_size, prm.max_segment_size = int(min_segment_size), min(int(max_segment_size), SIZE_MAX)
     sp, ns, skeep = _cc_seeds(seeds)
-    on_device = mem == capi.MEM_DEVICE
-    dev = None
-    if on_device:
-        import torch
-
-        dev = keep_p.device
-        if dev.index is not None:
-            device = dev.index
-        torch.cuda.synchronize(dev)      # the call runs on a stream of its own: the inputs must be complete
-    outs, addr = _cc_outputs(n, on_device, dev)
+    n = x.n
+    device, dev = _abi.enter(x.keep, device)
+    outs = [_abi.empty(m, np.uint32, dev) for m in (n, n + 1, n)]
+    addr = [_abi.ptr(o) for o in outs]
     nseg = C.c_size_t(0)
-    rc = L.cilhip_connected_components3f(int(device), p, ptrs[0], ptrs[1], n, mem, C.byref(prm), sp, ns, addr[0], addr[1], addr[2], C.byref(nseg))
-    if rc != capi.OK:
-        raise capi.CilhipError(rc, "cilhip_connected_components3f: " + L.cilhip_last_error(None).decode())
+    if nd:
+        rc = L.cilhip_connected_components_nd(device, x.ptr if n else None, ptrs[0], ptrs[1], n, x.dim, x.mem, C.byref(prm), int(form), sp, ns, *addr, C.byref(nseg))
+    else:
+        rc = L.cilhip_connected_components3f(device, x.ptr, ptrs[0], ptrs[1], n, x.mem, C.byref(prm), sp, ns, *addr, C.byref(nseg))
+    _abi.check(rc, "cilhip_connected_components_nd" if nd else "cilhip_connected_components3f", L)
     if n == 0:
         outs[1][:1] = 0
-    return _cc_result(outs, nseg.value, on_device)
+    elif nd and stats is not None:
+        st = capi.CcnStats()
+        L.cilhip_ccn_last_stats(C.byref(st))
+        stats.update({k: getattr(st, k) for k, _ in capi.CcnStats._fields_})
+    return _segments(*outs, nseg.value)
+
+
+def connected_components(points, radius_sq, evaluator=None, min_segment_size=1, max_segment_size=SIZE_MAX, seeds=None, device=0):
+    """cilhip_connected_components3f -> (labels[n], offsets[segments + 1], members[n]): segment k is members[offsets[k]:offsets[k + 1]],
+    members[offsets[-1]:] are the unlabelled points; labels[i] == segments for those"""
+    return _connected_components(False, points, radius_sq, evaluator, min_segment_size, max_segment_size, seeds, device)
 
 
 def connected_components_from_lists(n, offsets, idx, keep=None, skip_first=True, symmetric=True, min_segment_size=1, max_segment_size=SIZE_MAX, seeds=None,
@@ -246,36 +237,30 @@ def connected_components_from_lists(n, offsets, idx, keep=None, skip_first=True,
     """cilhip_connected_components_lists: the reference's "given neighbours" overloads (:20-160) over CSR lists -- of cilhip_radius_search3f
     (symmetric) or cilhip_knn3f (directed: weak components; offsets = arange(n + 1) * k) -- with an optional byte mask per entry"""
     L = capi.load()
-    on_device = hasattr(idx, "is_cuda") and idx.is_cuda
-    if on_device:
+    if _abi.on_device(idx):
         import torch
 
-        dev = idx.device
-        if dev.index is not None:
-            device = dev.index
-        off = offsets.to(device=dev, dtype=torch.int64).contiguous()
+        off = offsets.to(device=idx.device, dtype=torch.int64).contiguous()
         ix = idx.to(torch.int32).contiguous() if idx.dtype != torch.int32 else idx.contiguous()
-        kp = None if keep is None else keep.to(device=dev, dtype=torch.uint8).contiguous()
-        torch.cuda.synchronize(dev)
-        a_off, a_idx, a_keep, total, mem = off.data_ptr(), ix.data_ptr(), None if kp is None else kp.data_ptr(), ix.numel(), capi.MEM_DEVICE
+        kp = None if keep is None else keep.to(device=idx.device, dtype=torch.uint8).contiguous()
+        total, mem = ix.numel(), capi.MEM_DEVICE
     else:
-        dev = None
         off = np.ascontiguousarray(offsets, np.uint64)
         ix = np.ascontiguousarray(idx, np.uint32).reshape(-1)
         kp = None if keep is None else np.ascontiguousarray(keep, np.uint8).reshape(-1)
-        a_off, a_idx, a_keep, total, mem = off.ctypes.data, ix.ctypes.data, None if kp is None else kp.ctypes.data, ix.size, capi.MEM_HOST
+        total, mem = ix.size, capi.MEM_HOST
+    device, dev = _abi.enter(ix, device)
     if len(off) != n + 1 or (kp is not None and len(kp) != total):
         raise ValueError("offsets must have n + 1 entries and keep one byte per list entry")
     sp, ns, skeep = _cc_seeds(seeds)
-    outs, addr = _cc_outputs(n, on_device, dev)
+    outs = [_abi.empty(m, np.uint32, dev) for m in (n, n + 1, n)]
     nseg = C.c_size_t(0)
-    rc = L.cilhip_connected_components_lists(int(device), n, a_off, a_idx, a_keep, total, int(bool(skip_first)), int(bool(symmetric)), mem, int(min_segment_size),
-                                             min(int(max_segment_size), SIZE_MAX), sp, ns, addr[0], addr[1], addr[2], C.byref(nseg))
-    if rc != capi.OK:
-        raise capi.CilhipError(rc, "cilhip_connected_components_lists: " + L.cilhip_last_error(None).decode())
+    rc = L.cilhip_connected_components_lists(device, n, _abi.ptr(off), _abi.ptr(ix), _abi.ptr(kp), total, int(bool(skip_first)), int(bool(symmetric)), mem,
+                                             int(min_segment_size), min(int(max_segment_size), SIZE_MAX), sp, ns, *[_abi.ptr(o) for o in outs], C.byref(nseg))
+    _abi.check(rc, "cilhip_connected_components_lists", L)
     if n == 0:
         outs[1][:1] = 0
-    return _cc_result(outs, nseg.value, on_device)
+    return _segments(*outs, nseg.value)
 
 
 class ConnectedComponentExtraction3f:
@@ -298,12 +283,13 @@ class ConnectedComponentExtraction3f:
         seeds = kw.pop("seeds", None)
         if args and args[0] is not None and not isinstance(args[0], AlwaysTrueEvaluator):
             seeds = args.pop(0)      # segment(nh, seeds_ind, evaluator, min, max)
-        names = ("evaluator", "min_segment_size", "max_segment_size")
-        for k, v in zip(names, args):
+        for k, v in zip(("evaluator", "min_segment_size", "max_segment_size"), args):
             kw[k] = v
-        self._labels, self._offsets, self._members = connected_components(self._points, nh.radius, kw.get("evaluator"), kw.get("min_segment_size", 1),
-                                                                          kw.get("max_segment_size", SIZE_MAX), seeds, self._device)
+        self._labels, self._offsets, self._members = self._components(nh.radius, kw.get("evaluator"), kw.get("min_segment_size", 1), kw.get("max_segment_size", SIZE_MAX), seeds)
         return self
+
+    def _components(self, radius_sq, evaluator, min_segment_size, max_segment_size, seeds):
+        return connected_components(self._points, radius_sq, evaluator, min_segment_size, max_segment_size, seeds, self._device)
 
     def getPointToClusterIndexMap(self):
         return self._labels
@@ -333,52 +319,7 @@ def connected_components_nd(points, radius_sq, evaluator=None, min_segment_size=
     connected_components() returns them.  The evaluator's normals are n x dim, its colours n x 3.  form: 0 the code decides, 1 the
     exhaustive triangle, 2 sweep and prune (the same words, rule C4).  stats: a dict that receives cilhip_ccn_last_stats.  numpy arrays
     in -> numpy arrays out; device tensors in -> device tensors out"""
-    L = capi.load()
-    ev = evaluator if evaluator is not None else AlwaysTrueEvaluator()
-    x, p, n, dim, on_device = _as_rows(points, "the points")
-    ptrs, keep = [None, None], [x]
-    for k, (att, width, what) in enumerate(((ev.normals, dim, "the normals"), (ev.colors, 3, "the colours"))):
-        if att is None:
-            continue
-        ax, ap, an, adim, a_dev = _as_rows(att, what)
-        if an != n or adim != width:
-            raise ValueError("the normals are an n x dim array and the colours an n x 3 array over the points' n")
-        if a_dev != on_device:
-            raise ValueError("points, normals and colors must live in the same memory space")
-        ptrs[k] = ap
-        keep.append(ax)
-    prm = capi.CcParams()
-    L.cilhip_cc_default_params(C.byref(prm))
-    prm.radius_sq = radius_sq
-    if ev.max_distance is not None:
-        prm.use_distance, prm.max_distance = 1, ev.max_distance
-    if ev.max_angle is not None:
-        prm.use_normals, prm.max_angle, prm.angle_inclusive = 1, ev.max_angle, int(ev.angle_inclusive)
-    if ev.color_thresh is not None:
-        prm.use_colors, prm.color_thresh = 1, ev.color_thresh
-    prm.min_segment_size, prm.max_segment_size = int(min_segment_size), min(int(max_segment_size), SIZE_MAX)
-    sp, ns, skeep = _cc_seeds(seeds)
-    dev = None
-    if on_device:
-        import torch
-
-        dev = x.device
-        if dev.index is not None:
-            device = dev.index
-        torch.cuda.synchronize(dev)      # the call runs on a stream of its own: the inputs must be complete
-    outs, addr = _cc_outputs(n, on_device, dev)
-    nseg = C.c_size_t(0)
-    rc = L.cilhip_connected_components_nd(int(device), p if n else None, ptrs[0], ptrs[1], n, dim, capi.MEM_DEVICE if on_device else capi.MEM_HOST, C.byref(prm), int(form), sp, ns,
-                                          addr[0], addr[1], addr[2], C.byref(nseg))
-    if rc != capi.OK:
-        raise capi.CilhipError(rc, "cilhip_connected_components_nd: " + L.cilhip_last_error(None).decode())
-    if n == 0:
-        outs[1][:1] = 0
-    elif stats is not None:
-        st = capi.CcnStats()
-        L.cilhip_ccn_last_stats(C.byref(st))
-        stats.update({k: getattr(st, k) for k, _ in capi.CcnStats._fields_})
-    return _cc_result(outs, nseg.value, on_device)
+    return _connected_components(True, points, radius_sq, evaluator, min_segment_size, max_segment_size, seeds, device, form, stats)
 
 
 class ConnectedComponentExtractionXf(ConnectedComponentExtraction3f):
@@ -394,19 +335,9 @@ class ConnectedComponentExtractionXf(ConnectedComponentExtraction3f):
         self._form = form
         self._stats = {}
 
-    def segment(self, nh, *args, **kw):
-        if not isinstance(nh, RadiusNeighborhoodSpecification):
-            raise TypeError("segment() takes a RadiusNeighborhoodSpecification (other neighbourhoods: connected_components_from_lists)")
-        args = list(args)
-        seeds = kw.pop("seeds", None)
-        if args and args[0] is not None and not isinstance(args[0], AlwaysTrueEvaluator):
-            seeds = args.pop(0)      # segment(nh, seeds_ind, evaluator, min, max)
-        for k, v in zip(("evaluator", "min_segment_size", "max_segment_size"), args):
-            kw[k] = v
+    def _components(self, radius_sq, evaluator, min_segment_size, max_segment_size, seeds):
         self._stats = {}
-        self._labels, self._offsets, self._members = connected_components_nd(self._points, nh.radius, kw.get("evaluator"), kw.get("min_segment_size", 1),
-                                                                             kw.get("max_segment_size", SIZE_MAX), seeds, self._form, self._device, self._stats)
-        return self
+        return connected_components_nd(self._points, radius_sq, evaluator, min_segment_size, max_segment_size, seeds, self._form, self._device, self._stats)
 
     def getLastStats(self):
         return dict(self._stats)
@@ -443,51 +374,57 @@ class RBFKernelWeightEvaluator(UnityWeightEvaluator):
         self.sigma = float(sigma)
 
 
-def mean_shift(points, kernel_radius, max_iter, cluster_tol, convergence_tol=float(np.finfo(np.float32).eps), evaluator=None, seeds=None, form=0, device=0):
-    """cilhip_mean_shift3f -> dict(shifted[ns, 3], labels[ns], modes[k, 3], offsets[k + 1], members[ns], iterations, stats): cluster c is
-    members[offsets[c]:offsets[c + 1]]; seeds=None: every point is a seed"""
+_MS_STATS = (("form_used", "est_ball", "shift_ms", "group_ms", "passes", "rounds"), ("passes", "rounds", "slices_first", "slices_last", "shift_ms", "group_ms"))
+
+
+def _mean_shift(nd, points, kernel_radius, max_iter, cluster_tol, convergence_tol, evaluator, seeds, device, form=None):
+    """the one body of mean_shift() (N x 3 clouds, float32 or TypeError) and mean_shift_nd() (n x dim, converted)"""
     L = capi.load()
     ev = evaluator if evaluator is not None else UnityWeightEvaluator()
-    p, n, mem, keep_p = _as_cloud(points)
+    take = _nd_rows if nd else _cloud
+    x = take(points, "the points")
+    n, dim = x.n, (x.dim if nd else 3)
     sp, ns, keep_s = None, n, None
     if seeds is not None:
-        sp, ns, smem, keep_s = _as_cloud(seeds)
-        if smem != mem:
+        s = take(seeds, "the seeds")
+        sp, ns, keep_s = s.ptr, s.n, s.keep
+        if s.mem != x.mem:
             raise ValueError("points and seeds must live in the same memory space")
-        if ns == 0:
-            sp = (np.zeros((1, 3), np.float32) if mem == capi.MEM_HOST else keep_s.new_zeros((1, 3)))
-            keep_s = sp
-            sp = sp.ctypes.data if mem == capi.MEM_HOST else sp.data_ptr()      # (an empty list is still a list: a non-null pointer)
+        if s.dim != dim:
+            raise ValueError("points and seeds must have the same dimension")
+        if ns == 0:      # (an empty list is still a list: a non-null pointer)
+            keep_s = _abi.empty((1, max(dim, 1)), np.float32, x.keep.device if x.mem == capi.MEM_DEVICE else None, zero=True)
+            sp = _abi.ptr(keep_s)
     prm = capi.MsParams()
     L.cilhip_ms_default_params(C.byref(prm))
     prm.kernel_radius, prm.max_iter, prm.cluster_tol, prm.convergence_tol = kernel_radius, int(max_iter), cluster_tol, convergence_tol
-    prm.kernel_kind, prm.kernel_sigma, prm.form = int(ev.kind), float(ev.sigma), int(form)
-    on_device = mem == capi.MEM_DEVICE
-    if on_device:
-        import torch
-
-        dev = keep_p.device
-        if dev.index is not None:
-            device = dev.index
-        torch.cuda.synchronize(dev)      # the call runs on a stream of its own: the inputs must be complete
-        shifted, modes = torch.empty((ns, 3), dtype=torch.float32, device=dev), torch.empty((ns, 3), dtype=torch.float32, device=dev)
-        labels, offsets, members = (torch.empty(k, dtype=torch.int32, device=dev) for k in (ns, ns + 1, ns))
-        addr = [t.data_ptr() for t in (shifted, labels, modes, offsets, members)]
-    else:
-        shifted, modes = np.empty((ns, 3), np.float32), np.empty((ns, 3), np.float32)
-        labels, offsets, members = (np.empty(k, np.uint32) for k in (ns, ns + 1, ns))
-        addr = [a.ctypes.data for a in (shifted, labels, modes, offsets, members)]
+    prm.kernel_kind, prm.kernel_sigma = int(ev.kind), float(ev.sigma)
+    if form is not None:
+        prm.form = int(form)
+    device, dev = _abi.enter(x.keep, device)
+    shifted, modes = _abi.empty((ns, dim), np.float32, dev), _abi.empty((ns, dim), np.float32, dev)
+    labels, offsets, members = (_abi.empty(m, np.uint32, dev) for m in (ns, ns + 1, ns))
     nc, iters = C.c_size_t(0), C.c_size_t(0)
-    rc = L.cilhip_mean_shift3f(int(device), p, n, sp, ns if seeds is not None else 0, mem, C.byref(prm), addr[0], addr[1], addr[2], addr[3], addr[4], C.byref(nc), C.byref(iters))
-    if rc != capi.OK:
-        raise capi.CilhipError(rc, "cilhip_mean_shift3f: " + L.cilhip_last_error(None).decode())
+    outs = [_abi.ptr(o) for o in (shifted, labels, modes, offsets, members)] + [C.byref(nc), C.byref(iters)]
+    n_seeds = ns if seeds is not None else 0
+    if nd:
+        rc = L.cilhip_mean_shift_nd(device, x.ptr, n, dim, sp, n_seeds, x.mem, C.byref(prm), *outs)
+    else:
+        rc = L.cilhip_mean_shift3f(device, x.ptr, n, sp, n_seeds, x.mem, C.byref(prm), *outs)
+    _abi.check(rc, "cilhip_mean_shift_nd" if nd else "cilhip_mean_shift3f", L)
     if ns == 0:
         offsets[:1] = 0
-    st = capi.MsStats()
-    L.cilhip_ms_last_stats(C.byref(st))
-    stats = {"form_used": st.form_used, "est_ball": st.est_ball, "shift_ms": st.shift_ms, "group_ms": st.group_ms, "passes": st.passes, "rounds": st.rounds} if ns else {}
-    lab, off, mem_ = _cc_result([labels, offsets, members], nc.value, on_device)
+    st = capi.MsnStats() if nd else capi.MsStats()
+    (L.cilhip_msn_last_stats if nd else L.cilhip_ms_last_stats)(C.byref(st))
+    stats = {k: getattr(st, k) for k in _MS_STATS[nd]} if ns else {}
+    lab, off, mem_ = _segments(labels, offsets, members, nc.value)
     return {"shifted": shifted, "labels": lab, "modes": modes[: nc.value], "offsets": off, "members": mem_, "iterations": int(iters.value), "stats": stats}
+
+
+def mean_shift(points, kernel_radius, max_iter, cluster_tol, convergence_tol=float(np.finfo(np.float32).eps), evaluator=None, seeds=None, form=0, device=0):
+    """cilhip_mean_shift3f -> dict(shifted[ns, 3], labels[ns], modes[k, 3], offsets[k + 1], members[ns], iterations, stats): cluster c is
+    members[offsets[c]:offsets[c + 1]]; seeds=None: every point is a seed"""
+    return _mean_shift(False, points, kernel_radius, max_iter, cluster_tol, convergence_tol, evaluator, seeds, device, form)
 
 
 class MeanShift3f:
@@ -510,8 +447,10 @@ class MeanShift3f:
             seeds = args.pop(0)
         for k, v in zip(("kernel_radius", "max_iter", "cluster_tol", "convergence_tol", "evaluator"), args):
             kw[k] = v
-        self._r = mean_shift(self._points, seeds=seeds, device=self._device, **kw)
+        self._r = self._mean_shift(self._points, seeds=seeds, device=self._device, **kw)
         return self
+
+    _mean_shift = staticmethod(mean_shift)
 
     def getShiftedSeeds(self):
         return self._r["shifted"]
@@ -536,67 +475,11 @@ class MeanShift3f:
 
 # ---- MeanShiftXf / MeanShift2f (clustering/mean_shift.hpp:142-164) -----------------------------------------------------------------
 # The contract is stated in include/cilantro_hip/c_api.h (cilhip_mean_shift_nd, rules M1-M7) and DESIGN.md section 22.
-def _as_rows(x, what):
-    """an n x dim float32 array, numpy or device tensor -> (array, address, n, dim, on_device)"""
-    on_device = hasattr(x, "is_cuda") and x.is_cuda
-    if on_device:
-        import torch
-
-        x = x.to(torch.float32).contiguous()
-    else:
-        x = np.ascontiguousarray(x.cpu() if hasattr(x, "cpu") else x, np.float32)
-    if x.ndim != 2:
-        raise ValueError(f"{what} are an n x dim array")
-    return x, (x.data_ptr() if on_device else x.ctypes.data), int(x.shape[0]), int(x.shape[1]), on_device
-
-
 def mean_shift_nd(points, kernel_radius, max_iter, cluster_tol, convergence_tol=float(np.finfo(np.float32).eps), evaluator=None, seeds=None, device=0):
     """cilhip_mean_shift_nd over n x dim points (1 <= dim <= 16) -> dict(shifted[ns, dim], labels[ns], modes[k, dim], offsets[k + 1],
     members[ns], iterations, stats): cluster c is members[offsets[c]:offsets[c + 1]]; seeds=None: every point is a seed.  numpy arrays in ->
     numpy arrays out; device tensors in -> device tensors out"""
-    L = capi.load()
-    ev = evaluator if evaluator is not None else UnityWeightEvaluator()
-    x, p, n, dim, on_device = _as_rows(points, "the points")
-    sx, sp, ns = None, None, n
-    if seeds is not None:
-        sx, sp, ns, sdim, s_dev = _as_rows(seeds, "the seeds")
-        if s_dev != on_device:
-            raise ValueError("points and seeds must live in the same memory space")
-        if sdim != dim:
-            raise ValueError("points and seeds must have the same dimension")
-        if ns == 0:      # (an empty list is still a list: a non-null pointer)
-            sx = x.new_zeros((1, max(dim, 1))) if on_device else np.zeros((1, max(dim, 1)), np.float32)
-            sp = sx.data_ptr() if on_device else sx.ctypes.data
-    prm = capi.MsParams()
-    L.cilhip_ms_default_params(C.byref(prm))
-    prm.kernel_radius, prm.max_iter, prm.cluster_tol, prm.convergence_tol = kernel_radius, int(max_iter), cluster_tol, convergence_tol
-    prm.kernel_kind, prm.kernel_sigma = int(ev.kind), float(ev.sigma)
-    if on_device:
-        import torch
-
-        dev = x.device
-        if dev.index is not None:
-            device = dev.index
-        torch.cuda.synchronize(dev)      # the call runs on a stream of its own: the inputs must be complete
-        shifted, modes = torch.empty((ns, dim), dtype=torch.float32, device=dev), torch.empty((ns, dim), dtype=torch.float32, device=dev)
-        labels, offsets, members = (torch.empty(k, dtype=torch.int32, device=dev) for k in (ns, ns + 1, ns))
-        addr = [t.data_ptr() for t in (shifted, labels, modes, offsets, members)]
-    else:
-        shifted, modes = np.empty((ns, dim), np.float32), np.empty((ns, dim), np.float32)
-        labels, offsets, members = (np.empty(k, np.uint32) for k in (ns, ns + 1, ns))
-        addr = [a.ctypes.data for a in (shifted, labels, modes, offsets, members)]
-    nc, iters = C.c_size_t(0), C.c_size_t(0)
-    rc = L.cilhip_mean_shift_nd(int(device), p, n, dim, sp, ns if seeds is not None else 0, capi.MEM_DEVICE if on_device else capi.MEM_HOST, C.byref(prm), addr[0], addr[1], addr[2],
-                                addr[3], addr[4], C.byref(nc), C.byref(iters))
-    if rc != capi.OK:
-        raise capi.CilhipError(rc, "cilhip_mean_shift_nd: " + L.cilhip_last_error(None).decode())
-    if ns == 0:
-        offsets[:1] = 0
-    st = capi.MsnStats()
-    L.cilhip_msn_last_stats(C.byref(st))
-    stats = {k: getattr(st, k) for k in ("passes", "rounds", "slices_first", "slices_last", "shift_ms", "group_ms")} if ns else {}
-    lab, off, mem_ = _cc_result([labels, offsets, members], nc.value, on_device)
-    return {"shifted": shifted, "labels": lab, "modes": modes[: nc.value], "offsets": off, "members": mem_, "iterations": int(iters.value), "stats": stats}
+    return _mean_shift(True, points, kernel_radius, max_iter, cluster_tol, convergence_tol, evaluator, seeds, device)
 
 
 class MeanShiftXf(MeanShift3f):
@@ -609,15 +492,7 @@ class MeanShiftXf(MeanShift3f):
             raise ValueError("the points are an n x dim array" if dim is None else f"the points are an n x {int(dim)} array")
         self.dim = int(points.shape[1])
 
-    def cluster(self, *args, **kw):
-        args = list(args)
-        seeds = kw.pop("seeds", None)
-        if args and not np.isscalar(args[0]):
-            seeds = args.pop(0)
-        for k, v in zip(("kernel_radius", "max_iter", "cluster_tol", "convergence_tol", "evaluator"), args):
-            kw[k] = v
-        self._r = mean_shift_nd(self._points, seeds=seeds, device=self._device, **kw)
-        return self
+    _mean_shift = staticmethod(mean_shift_nd)
 
 
 class MeanShift2f(MeanShiftXf):
@@ -635,10 +510,6 @@ class GraphLaplacianType:
     UNNORMALIZED, NORMALIZED_SYMMETRIC, NORMALIZED_RANDOM_WALK = 0, 1, 2
 
 
-def _ptr(a):
-    return None if a is None else (a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data)
-
-
 class SparseMatrix:
     """owner of a cilhip_sparse handle (a CSR matrix on the device); close() or the garbage collector frees it"""
 
@@ -649,25 +520,21 @@ class SparseMatrix:
     def from_csr(cls, n, offsets, columns, values, device=0):
         """cilhip_sparse_from_csr: numpy arrays, or device tensors (int64 offsets, int32 columns, float32 values)"""
         L = capi.load()
-        if hasattr(values, "is_cuda") and values.is_cuda:
+        if _abi.on_device(values):
             import torch
 
-            if values.device.index is not None:
-                device = values.device.index
             off, col, val = offsets.to(torch.int64).contiguous(), columns.to(torch.int32).contiguous(), values.to(torch.float32).contiguous()
-            torch.cuda.synchronize(values.device)
             mem = capi.MEM_DEVICE
         else:
             off, col, val = np.ascontiguousarray(offsets, np.uint64), np.ascontiguousarray(columns, np.uint32), np.ascontiguousarray(values, np.float32)
             col, val = (col if col.size else np.zeros(1, np.uint32)), (val if val.size else np.zeros(1, np.float32))
             mem = capi.MEM_HOST
+        device, _ = _abi.enter(val, device)
         if len(off) != n + 1:
             raise ValueError("offsets must have n + 1 entries")
         h = C.c_void_p()
-        rc = L.cilhip_sparse_from_csr(int(device), int(n), _ptr(off), _ptr(col), _ptr(val), mem, C.byref(h))
-        if rc != capi.OK:
-            raise capi.CilhipError(rc, "cilhip_sparse_from_csr: " + L.cilhip_last_error(None).decode())
-        return cls(h, int(device))
+        _abi.check(L.cilhip_sparse_from_csr(device, int(n), _abi.ptr(off), _abi.ptr(col), _abi.ptr(val), mem, C.byref(h)), "cilhip_sparse_from_csr", L)
+        return cls(h, device)
 
     @classmethod
     def from_dense(cls, dense, device=0):
@@ -688,17 +555,11 @@ class SparseMatrix:
     def get(self, on_device=False):
         """cilhip_sparse_get -> (offsets[n + 1], columns[nnz], values[nnz]): numpy (uint64, uint32, float32) or device tensors (int64, int32, float32)"""
         n, nnz, _ = self.info()
-        if on_device:
-            import torch
-
-            dev = torch.device("cuda", self.device)
-            out = [torch.empty(n + 1, dtype=torch.int64, device=dev), torch.empty(max(nnz, 1), dtype=torch.int32, device=dev), torch.empty(max(nnz, 1), dtype=torch.float32, device=dev)]
-            torch.cuda.synchronize(dev)
-        else:
-            out = [np.empty(n + 1, np.uint64), np.empty(max(nnz, 1), np.uint32), np.empty(max(nnz, 1), np.float32)]
-        rc = self._L.cilhip_sparse_get(self._h, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), capi.MEM_DEVICE if on_device else capi.MEM_HOST)
-        if rc != capi.OK:
-            raise capi.CilhipError(rc, "cilhip_sparse_get: " + self._L.cilhip_last_error(None).decode())
+        dev = f"cuda:{self.device}" if on_device else None
+        out = [_abi.empty(n + 1, np.uint64, dev), _abi.empty(max(nnz, 1), np.uint32, dev), _abi.empty(max(nnz, 1), np.float32, dev)]
+        _abi.enter(out[0], self.device)
+        rc = self._L.cilhip_sparse_get(self._h, _abi.ptr(out[0]), _abi.ptr(out[1]), _abi.ptr(out[2]), capi.MEM_DEVICE if on_device else capi.MEM_HOST)
+        _abi.check(rc, "cilhip_sparse_get", self._L)
         return out[0], out[1][:nnz], out[2][:nnz]
 
     def close(self):
@@ -720,22 +581,20 @@ def nn_graph_sparse_matrix(neighbors, evaluator=None, force_symmetry=False, dupl
         offsets, idx, d2 = neighbors
     else:
         idx, d2 = neighbors[0], neighbors[1]
-    on_device = hasattr(idx, "is_cuda") and idx.is_cuda
+    on_device = _abi.on_device(idx)
     if on_device:
         import torch
 
-        if idx.device.index is not None:
-            device = idx.device.index
         ix = idx.to(torch.int32).contiguous()
         dd = None if d2 is None else d2.to(device=idx.device, dtype=torch.float32).contiguous()
         off = None if offsets is None else offsets.to(device=idx.device, dtype=torch.int64).contiguous()
-        torch.cuda.synchronize(idx.device)
         shape, mem = tuple(ix.shape), capi.MEM_DEVICE
     else:
         ix = np.ascontiguousarray(np.asarray(idx).astype(np.int64) & 0xFFFFFFFF, np.uint32)
         dd = None if d2 is None else np.ascontiguousarray(d2, np.float32)
         off = None if offsets is None else np.ascontiguousarray(offsets, np.uint64)
         shape, mem = ix.shape, capi.MEM_HOST
+    device, _ = _abi.enter(ix, device)
     if off is None:
         if len(shape) != 2:
             raise ValueError("a k-NN list is an n x k array")
@@ -745,11 +604,10 @@ def nn_graph_sparse_matrix(neighbors, evaluator=None, force_symmetry=False, dupl
         if not on_device and ix.size == 0:
             ix, dd = np.zeros(1, np.uint32), (None if dd is None else np.zeros(1, np.float32))
     h = C.c_void_p()
-    rc = L.cilhip_nn_graph_matrix(int(device), n, _ptr(off), _ptr(ix), _ptr(dd), k_or_total, mem, int(ev.kind), C.c_float(ev.sigma), int(bool(force_symmetry)), int(duplicates),
+    rc = L.cilhip_nn_graph_matrix(device, n, _abi.ptr(off), _abi.ptr(ix), _abi.ptr(dd), k_or_total, mem, int(ev.kind), C.c_float(ev.sigma), int(bool(force_symmetry)), int(duplicates),
                                   C.byref(h))
-    if rc != capi.OK:
-        raise capi.CilhipError(rc, "cilhip_nn_graph_matrix: " + L.cilhip_last_error(None).decode())
-    return SparseMatrix(h, int(device))
+    _abi.check(rc, "cilhip_nn_graph_matrix", L)
+    return SparseMatrix(h, device)
 
 
 def spectral_embedding(affinities, max_num_clusters, estimate_num_clusters=False, laplacian_type=GraphLaplacianType.NORMALIZED_RANDOM_WALK, on_device=False, max_outer=None,
@@ -765,19 +623,12 @@ def spectral_embedding(affinities, max_num_clusters, estimate_num_clusters=False
         if v is not None:
             setattr(prm, key, int(v))
     room = max(min(int(max_num_clusters), 16), 2)
-    if on_device:
-        import torch
-
-        dev = torch.device("cuda", affinities.device)
-        emb = torch.empty((n, room), dtype=torch.float32, device=dev)
-        torch.cuda.synchronize(dev)
-    else:
-        emb = np.empty((n, room), np.float32)
+    emb = _abi.empty((n, room), np.float32, f"cuda:{affinities.device}" if on_device else None)
+    _abi.enter(emb, affinities.device)
     ev = np.zeros(room + 1, np.float32)
     res = capi.SpectralResult()
-    rc = L.cilhip_spectral_embedding(affinities._h, C.byref(prm), _ptr(emb), ev.ctypes.data, capi.MEM_DEVICE if on_device else capi.MEM_HOST, C.byref(res))
-    if rc != capi.OK:
-        raise capi.CilhipError(rc, "cilhip_spectral_embedding: " + L.cilhip_last_error(None).decode())
+    rc = L.cilhip_spectral_embedding(affinities._h, C.byref(prm), _abi.ptr(emb), ev.ctypes.data, capi.MEM_DEVICE if on_device else capi.MEM_HOST, C.byref(res))
+    _abi.check(rc, "cilhip_spectral_embedding", L)
     info = {k: getattr(res, k) for k, _ in capi.SpectralResult._fields_}
     if raise_unconverged and res.n_converged < res.num_eigenvalues:
         raise capi.CilhipError(capi.ERR_UNSUPPORTED, "cilhip_spectral_embedding: %d of %d eigenpairs converged in %d outer iterations (largest residual %.3g)"
@@ -792,37 +643,26 @@ class KMeansXf(KMeans3f):
     array or a device tensor.  use_kd_tree is accepted and changes nothing: the kd-tree branch is not built in D dimensions."""
 
     def cluster(self, centroids_or_k, max_iter=100, tol=float(np.finfo(np.float32).eps), use_kd_tree=False, seed=None):
-        x = self._data
-        on_device = hasattr(x, "is_cuda") and x.is_cuda
-        if on_device:
-            import torch
-
-            x = x.to(torch.float32).contiguous()
-            device = x.device.index if x.device.index is not None else self._device
-            torch.cuda.synchronize(x.device)
-        else:
-            x, device = np.ascontiguousarray(x, np.float32), self._device
-        if x.ndim != 2:
-            raise ValueError("the points are an n x dim array")
-        n, dim = int(x.shape[0]), int(x.shape[1])
+        r = _nd_rows(self._data, "the points")
+        x, n, dim = r.keep, r.n, r.dim
+        device, dev = _abi.enter(x, self._device)
         if np.isscalar(centroids_or_k):
             k = max(1, min(int(centroids_or_k), n))
             idx = np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
-            cent = np.ascontiguousarray((x[torch.as_tensor(idx, device=x.device)].cpu().numpy() if on_device else x[idx]), np.float32)
+            if dev is not None:
+                import torch
+
+                idx = torch.as_tensor(idx, device=dev)
+            cent = np.ascontiguousarray(x[idx].cpu().numpy() if dev is not None else x[idx], np.float32)
         else:
             cent = np.ascontiguousarray(centroids_or_k.cpu() if hasattr(centroids_or_k, "cpu") else centroids_or_k, np.float32).reshape(-1, dim).copy()
-        if on_device:
-            labels = torch.zeros(n, dtype=torch.int32, device=x.device)
-            torch.cuda.synchronize(x.device)
-        else:
-            labels = np.zeros(n, np.uint32)
+        labels = _abi.empty(n, np.uint32, dev, zero=True)
+        _abi.enter(labels, device)      # (the zeros are torch's work too)
         iters = C.c_size_t(0)
-        rc = self._L.cilhip_kmeans_nd(int(device), _ptr(x), n, dim, capi.MEM_DEVICE if on_device else capi.MEM_HOST, cent.ctypes.data, len(cent), int(max_iter), C.c_float(tol),
-                                      _ptr(labels), C.byref(iters))
-        if rc != capi.OK:
-            raise capi.CilhipError(rc, "cilhip_kmeans_nd: " + self._L.cilhip_last_error(None).decode())
+        rc = self._L.cilhip_kmeans_nd(device, r.ptr, n, dim, r.mem, cent.ctypes.data, len(cent), int(max_iter), C.c_float(tol), _abi.ptr(labels), C.byref(iters))
+        _abi.check(rc, "cilhip_kmeans_nd", self._L)
         self.cluster_centroids_ = cent
-        self.point_to_cluster_index_map_ = (labels.cpu().numpy() if on_device else labels).astype(np.int64)
+        self.point_to_cluster_index_map_ = (labels.cpu().numpy() if dev is not None else labels).astype(np.int64)
         self.iteration_count_ = int(iters.value)
         return self
 

@@ -23,7 +23,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .icp import _as_cloud
+from ._abi import cloud as _as_cloud
 
 
 def scale_exponent(maxabs_all, n_all):

@@ -16,9 +16,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import capi
-from .icp import _as_cloud
-from .image_conversions import _ck, _K, _E
+from . import _abi, capi
+from ._abi import check as _ck, cloud as _as_cloud
 
 COUNT_NAMES = ("visited", "fused", "appended", "removed", "untouched")
 
@@ -58,17 +57,11 @@ def fuse_frame(model, n_model, frame, cam_pose, K, w, h, params=None, device=0):
                 raise ValueError("the model arrays must be contiguous float32 arrays (edited in place)")
     if len(set(mem + fmem)) != 1 or len(set(cap + (conf_rows,))) != 1 or len(set(nf)) != 1:
         raise ValueError("the model's arrays must share one capacity, the frame's one size, and all must live in the same memory space")
-    if mem[0] == capi.MEM_DEVICE:
-        import torch
-
-        dev = keep_m[0].device
-        if dev.index is not None:
-            device = dev.index
-        torch.cuda.synchronize(dev)      # the call runs on a stream of its own: the inputs must be complete
+    device, _ = _abi.enter(keep_m[0], device)
     p = params if params is not None else default_params()
     n_out, counts = C.c_size_t(0), capi.FusionCounts()
-    pose, k = _E(cam_pose), _K(K)
-    _ck(L.cilhip_fuse_frame3f(int(device), mp[0], mp[1], mp[2], conf_ptr, int(n_model), cap[0], fp[0], fp[1], fp[2], nf[0], mem[0], pose.ctypes.data, k.ctypes.data,
+    pose, k = _abi.colmajor(cam_pose, 4), _abi.colmajor(K, 3)
+    _ck(L.cilhip_fuse_frame3f(device, mp[0], mp[1], mp[2], conf_ptr, int(n_model), cap[0], fp[0], fp[1], fp[2], nf[0], mem[0], pose.ctypes.data, k.ctypes.data,
                               int(w), int(h), C.byref(p), C.byref(n_out), C.byref(counts)), "cilhip_fuse_frame3f")
     return n_out.value, _counts(counts)
 
@@ -133,9 +126,7 @@ class SurfelMap3f:
         """cleanup_callback (fusion.cpp:51-59): points whose confidence is below conf_thresh leave, in the order remove() leaves"""
         if self._n == 0:
             return self
-        import torch
-
-        torch.cuda.synchronize(self._arrays[0].device)
+        _abi.enter(self._arrays[0], self.device)
         n_out = C.c_size_t(0)
         a = self._arrays
         _ck(capi.load().cilhip_fusion_remove_unstable3f(self.device, a[0].data_ptr(), a[1].data_ptr(), a[2].data_ptr(), a[3].data_ptr(), self._n, capi.MEM_DEVICE,

@@ -14,57 +14,33 @@ import ctypes as C
 
 import numpy as np
 
-from . import capi
-from .icp import _as_cloud
+from . import _abi, capi
 
 
 def _run(points, normals, colors, bin_size, min_points_in_bin, parallel, want_counts, device):
     """-> (points, normals or None, colors or None, counts or None), every array cut to the number of bins"""
     L = capi.load()
-    p, n, mem, keep_p = _as_cloud(points)
+    p, n, mem, keep_p = _abi.cloud(points)
     ptrs, keep = [None, None], [keep_p]
     for k, att in enumerate((normals, colors)):
         if att is None:
             continue
-        ap, an, amem, akeep = _as_cloud(att)
+        ap, an, amem, akeep = _abi.cloud(att)
         if an != n:
             raise ValueError("points, normals and colors must have the same number of rows")
         if amem != mem:
             raise ValueError("points, normals and colors must live in the same memory space")
         ptrs[k] = ap
         keep.append(akeep)
-    on_device = mem == capi.MEM_DEVICE
-    if on_device:
-        import torch
-
-        dev = keep_p.device
-        if dev.index is not None:
-            device = dev.index
-        torch.cuda.synchronize(dev)      # the call runs on a stream of its own: the inputs must be complete
-        new = lambda cols, dt: torch.empty((n, cols) if cols else (n,), dtype=dt, device=dev)      # noqa: E731
-        outs = [new(3, torch.float32), None if normals is None else new(3, torch.float32), None if colors is None else new(3, torch.float32),
-                new(0, torch.int32) if want_counts else None]
-        addr = [None if o is None else o.data_ptr() for o in outs]
-    else:
-        outs = [np.empty((n, 3), np.float32), None if normals is None else np.empty((n, 3), np.float32),
-                None if colors is None else np.empty((n, 3), np.float32), np.empty(n, np.uint32) if want_counts else None]
-        addr = [None if o is None else o.ctypes.data for o in outs]
+    device, dev = _abi.enter(keep_p, device)
+    outs = [_abi.empty((n, 3), np.float32, dev), None if normals is None else _abi.empty((n, 3), np.float32, dev),
+            None if colors is None else _abi.empty((n, 3), np.float32, dev), _abi.empty(n, np.uint32, dev) if want_counts else None]
     rows = C.c_size_t(0)
     # capacity = n always suffices: one call, no counting call before it
-    rc = L.cilhip_grid_downsample3f(int(device), p, ptrs[0], ptrs[1], n, mem, C.c_float(bin_size), int(min_points_in_bin), 1 if parallel else 0,
-                                    addr[0], addr[1], addr[2], addr[3], n, C.byref(rows))
-    if rc != capi.OK:
-        raise capi.CilhipError(rc, "cilhip_grid_downsample3f: " + L.cilhip_last_error(None).decode())
-    m = rows.value
-    cut = []
-    for o in outs:
-        if o is None:
-            cut.append(None)
-        elif on_device:
-            cut.append(o[:m].clone() if 2 * m < n else o[:m])      # (do not keep an input-sized buffer alive behind a small result)
-        else:
-            cut.append(o[:m].copy() if 2 * m < n else o[:m])
-    return tuple(cut)
+    rc = L.cilhip_grid_downsample3f(device, p, ptrs[0], ptrs[1], n, mem, C.c_float(bin_size), int(min_points_in_bin), 1 if parallel else 0,
+                                    *[_abi.ptr(o) for o in outs], n, C.byref(rows))
+    _abi.check(rc, "cilhip_grid_downsample3f", L)
+    return tuple(_abi.cut(o, rows.value, n) for o in outs)
 
 
 def grid_downsample(points, bin_size, normals=None, colors=None, min_points_in_bin=1, parallel=True, device=0):

@@ -23,7 +23,8 @@ from enum import Enum
 
 import numpy as np
 
-from . import capi
+from . import _abi, capi
+from ._abi import T_from_abi as _T_from_abi, T_to_abi as _T_to_abi, cloud as _as_cloud, is_torch as _is_torch      # noqa: F401 (kept names)
 
 
 class CorrespondenceSearchDirection(Enum):  # core/correspondence.hpp:7
@@ -32,40 +33,6 @@ class CorrespondenceSearchDirection(Enum):  # core/correspondence.hpp:7
     BOTH = 2
 
 
-def _is_torch(x):
-    return type(x).__module__.startswith("torch")
-
-
-def _as_cloud(x):
-    """-> (pointer, n, mem, keepalive)"""
-    if x is None:
-        return None, 0, capi.MEM_HOST, None
-    if _is_torch(x):
-        import torch
-
-        t = x
-        if t.dtype != torch.float32:
-            raise TypeError("clouds must be float32")
-        t = t.contiguous()
-        if t.dim() != 2 or t.shape[1] != 3:
-            raise ValueError("clouds must have shape (N, 3)")
-        if t.is_cuda:
-            return t.data_ptr(), t.shape[0], capi.MEM_DEVICE, t
-        a = t.numpy()
-        return a.ctypes.data, a.shape[0], capi.MEM_HOST, a
-    a = np.ascontiguousarray(x, dtype=np.float32)
-    if a.ndim != 2 or a.shape[1] != 3:
-        raise ValueError("clouds must have shape (N, 3)")
-    return a.ctypes.data, a.shape[0], capi.MEM_HOST, a
-
-
-def _T_to_abi(T):
-    a = np.ascontiguousarray(np.asarray(T, dtype=np.float32).reshape(4, 4).T).reshape(16)
-    return a
-
-
-def _T_from_abi(buf):
-    return np.array(buf, dtype=np.float32).reshape(4, 4).T.copy()
 
 
 class Context:
@@ -1026,8 +993,7 @@ class WarpField:
         h = C.c_void_p()
         rc = self._L.cilhip_warp_field_create(int(device), self.n_src, self.n_ctrl, ci.ctypes.data, cd.ctypes.data, ci.shape[1], ck, cs, ri.ctypes.data, rd.ctypes.data,
                                               ri.shape[1], rk, rs, capi.MEM_HOST, C.byref(h))
-        if rc != capi.OK:
-            raise capi.CilhipError(rc, self._L.cilhip_last_error(None).decode())
+        _abi.check(rc, None, self._L)
         self._h = h
 
     def close(self):
@@ -1042,8 +1008,7 @@ class WarpField:
             pass
 
     def _ck(self, rc):
-        if rc != capi.OK:
-            raise capi.CilhipError(rc, self._L.cilhip_last_error(None).decode())
+        _abi.check(rc, None, self._L)
 
     def estimate(self, dst_points, dst_normals, warped_src_points, nn_idx, params):
         """one estimateSparseWarpFieldCombinedMetric call -> (control transforms (n_ctrl, 4, 4), capi.WarpStats)"""
@@ -1076,8 +1041,7 @@ def transformPoints(transforms, points, device=0):
     out = np.zeros_like(p)
     L = capi.load()
     rc = L.cilhip_transform_points_per_point3f(int(device), t.ctypes.data, p.ctypes.data, len(p), capi.MEM_HOST, out.ctypes.data)
-    if rc != capi.OK:
-        raise capi.CilhipError(rc, L.cilhip_last_error(None).decode())
+    _abi.check(rc, None, L)
     return out
 
 

@@ -16,8 +16,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import capi
-from .icp import _as_cloud, _is_torch
+from . import _abi, capi
+from ._abi import check as _ck, ptr as _ptr
 
 EMPTY = 0xFFFFFFFF
 
@@ -47,26 +47,9 @@ def _conv(conv, raw_type):
     return capi.DepthConverter(raw_type, conv.scale, 1 if conv.truncated else 0, conv.max_depth)
 
 
-def _K(K):
-    return np.ascontiguousarray(np.asarray(K, np.float32).reshape(3, 3).T).reshape(9)
-
-
-def _E(E):
-    return None if E is None else np.ascontiguousarray(np.asarray(E, np.float32).reshape(4, 4).T).reshape(16)
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data
-
-
-def _ck(rc, name):
-    if rc != capi.OK:
-        raise capi.CilhipError(rc, name + ": " + capi.load().cilhip_last_error(None).decode())
-
-
 def _image(img, what):
-    """-> (pointer, shape, mem, keepalive, raw_type or None, torch device or None)"""
-    if _is_torch(img):
+    """-> (pointer, shape, mem, keepalive, raw_type or None)"""
+    if _abi.is_torch(img):
         import torch
 
         t = img.contiguous()
@@ -76,105 +59,71 @@ def _image(img, what):
         if t.dtype not in names:
             raise TypeError(what + ": uint16 / int16 / float32 depth, uint8 rgb")
         if t.is_cuda:
-            return t.data_ptr(), tuple(t.shape), capi.MEM_DEVICE, t, names[t.dtype], t.device
+            return _ptr(t), tuple(t.shape), capi.MEM_DEVICE, t, names[t.dtype]
         img = t.numpy()
     a = np.ascontiguousarray(img)
     if a.dtype == np.int16:      # (uint16 bits, as a CUDA int16 tensor carries them)
         a = a.view(np.uint16)
     if a.dtype == np.uint8:
-        return a.ctypes.data, a.shape, capi.MEM_HOST, a, None, None
+        return _ptr(a), a.shape, capi.MEM_HOST, a, None
     if a.dtype not in (np.uint16, np.float32):
         raise TypeError(what + ": a depth image is uint16 or float32")
-    return a.ctypes.data, a.shape, capi.MEM_HOST, a, capi.DEPTH_U16 if a.dtype == np.uint16 else capi.DEPTH_F32, None
+    return _ptr(a), a.shape, capi.MEM_HOST, a, capi.DEPTH_U16 if a.dtype == np.uint16 else capi.DEPTH_F32
 
 
 def depth_image_to_points(depth, conv, K, extrinsics=None, rgb=None, keep_invalid=False, want_normals=False, device=0):
     """cilhip_depth_image_to_points3f -> (points, normals or None, colors or None), every array cut to the number of rows"""
     L = capi.load()
-    dp, shape, mem, keep_d, raw_type, dev = _image(depth, "depth")
+    dp, shape, mem, keep_d, raw_type = _image(depth, "depth")
     if raw_type is None or len(shape) != 2:
         raise ValueError("depth must be an (h, w) image of uint16 or float32")
     h, w = shape
     cp, keep_c = None, None
     if rgb is not None:
-        cp, cshape, cmem, keep_c, craw, _ = _image(rgb, "rgb")
+        cp, cshape, cmem, keep_c, craw = _image(rgb, "rgb")
         if craw is not None or tuple(cshape) != (h, w, 3):
             raise ValueError("rgb must be an (h, w, 3) image of uint8")
         if cmem != mem:
             raise ValueError("depth and rgb must live in the same memory space")
     n = w * h
-    on_device = mem == capi.MEM_DEVICE
-    if on_device:
-        import torch
-
-        if dev.index is not None:
-            device = dev.index
-        torch.cuda.synchronize(dev)      # the call runs on a stream of its own: the inputs must be complete
-        outs = [torch.empty((n, 3), dtype=torch.float32, device=dev) if use else None for use in (True, want_normals, rgb is not None)]
-        addr = [None if o is None else o.data_ptr() for o in outs]
-    else:
-        outs = [np.empty((n, 3), np.float32) if use else None for use in (True, want_normals, rgb is not None)]
-        addr = [_ptr(o) for o in outs]
+    device, dev = _abi.enter(keep_d, device)
+    outs = [_abi.empty((n, 3), np.float32, dev) if use else None for use in (True, want_normals, rgb is not None)]
     rows = C.c_size_t(0)
-    c, k, e = _conv(conv, raw_type), _K(K), _E(extrinsics)
-    _ck(L.cilhip_depth_image_to_points3f(int(device), dp, cp, w, h, mem, C.byref(c), _ptr(k), _ptr(e), 1 if keep_invalid else 0, 1 if want_normals else 0,
-                                         addr[0], addr[1], addr[2], n, C.byref(rows)), "cilhip_depth_image_to_points3f")
-    m = rows.value
-    cut = lambda o: None if o is None else ((o[:m].clone() if on_device else o[:m].copy()) if 2 * m < n else o[:m])      # noqa: E731
-    return tuple(cut(o) for o in outs)
+    c, k, e = _conv(conv, raw_type), _abi.colmajor(K, 3), _abi.colmajor(extrinsics, 4)
+    _ck(L.cilhip_depth_image_to_points3f(device, dp, cp, w, h, mem, C.byref(c), _ptr(k), _ptr(e), 1 if keep_invalid else 0, 1 if want_normals else 0,
+                                         *[_ptr(o) for o in outs], n, C.byref(rows)), "cilhip_depth_image_to_points3f", L)
+    return tuple(_abi.cut(o, rows.value, n) for o in outs)
 
 
 def points_to_depth_image(points, K, conv, w, h, extrinsics=None, colors=None, raw_type=np.uint16, device=0):
     """cilhip_points_to_depth_image3f -> (depth (h, w) of raw_type, rgb (h, w, 3) uint8 or None)"""
     L = capi.load()
-    p, n, mem, keep_p = _as_cloud(points)
+    p, n, mem, keep_p = _abi.cloud(points)
     cp, keep_c = None, None
     if colors is not None:
-        cp, cn, cmem, keep_c = _as_cloud(colors)
+        cp, cn, cmem, keep_c = _abi.cloud(colors)
         if cn != n or cmem != mem:
             raise ValueError("points and colors must have the same number of rows and live in the same memory space")
     raw = capi.DEPTH_U16 if np.dtype(raw_type) == np.uint16 else capi.DEPTH_F32
     if np.dtype(raw_type) not in (np.dtype(np.uint16), np.dtype(np.float32)):
         raise TypeError("raw_type: numpy.uint16 or numpy.float32")
     w, h = int(w), int(h)
-    if mem == capi.MEM_DEVICE:
-        import torch
-
-        dev = keep_p.device
-        if dev.index is not None:
-            device = dev.index
-        torch.cuda.synchronize(dev)
-        depth = torch.empty((h, w), dtype=torch.int16 if raw == capi.DEPTH_U16 else torch.float32, device=dev)      # (uint16 bits)
-        rgb = None if colors is None else torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
-        addr = [depth.data_ptr(), None if rgb is None else rgb.data_ptr()]
-    else:
-        depth = np.empty((h, w), raw_type)
-        rgb = None if colors is None else np.empty((h, w, 3), np.uint8)
-        addr = [depth.ctypes.data, _ptr(rgb)]
-    c, k, e = _conv(conv, raw), _K(K), _E(extrinsics)
-    _ck(L.cilhip_points_to_depth_image3f(int(device), p, cp, n, mem, _ptr(e), _ptr(k), C.byref(c), w, h, addr[0], addr[1]), "cilhip_points_to_depth_image3f")
+    device, dev = _abi.enter(keep_p, device)
+    depth = _abi.empty((h, w), raw_type, dev)
+    rgb = None if colors is None else _abi.empty((h, w, 3), np.uint8, dev)
+    c, k, e = _conv(conv, raw), _abi.colmajor(K, 3), _abi.colmajor(extrinsics, 4)
+    _ck(L.cilhip_points_to_depth_image3f(device, p, cp, n, mem, _ptr(e), _ptr(k), C.byref(c), w, h, _ptr(depth), _ptr(rgb)), "cilhip_points_to_depth_image3f", L)
     return depth, rgb
 
 
 def points_to_index_map(points, K, w, h, extrinsics=None, device=0):
     """cilhip_points_to_index_map3f -> (h, w) uint32 (a CUDA input gives an int32 tensor of the same bits), EMPTY where no point lands"""
     L = capi.load()
-    p, n, mem, keep_p = _as_cloud(points)
+    p, n, mem, keep_p = _abi.cloud(points)
     w, h = int(w), int(h)
-    if mem == capi.MEM_DEVICE:
-        import torch
-
-        dev = keep_p.device
-        if dev.index is not None:
-            device = dev.index
-        torch.cuda.synchronize(dev)
-        out = torch.empty((h, w), dtype=torch.int32, device=dev)
-        addr = out.data_ptr()
-    else:
-        out = np.empty((h, w), np.uint32)
-        addr = out.ctypes.data
-    k, e = _K(K), _E(extrinsics)
-    _ck(L.cilhip_points_to_index_map3f(int(device), p, n, mem, _ptr(e), _ptr(k), w, h, addr), "cilhip_points_to_index_map3f")
+    device, dev = _abi.enter(keep_p, device)
+    out = _abi.empty((h, w), np.uint32, dev)
+    _ck(L.cilhip_points_to_index_map3f(device, p, n, mem, _ptr(_abi.colmajor(extrinsics, 4)), _ptr(_abi.colmajor(K, 3)), w, h, _ptr(out)), "cilhip_points_to_index_map3f", L)
     return out
 
 

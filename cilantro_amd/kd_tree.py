@@ -15,10 +15,16 @@ import ctypes as C
 
 import numpy as np
 
-from . import capi
-from .clustering import RadiusNeighborhoodSpecification
+from . import _abi, capi
 
 MAX_DIM = 16
+
+
+class RadiusNeighborhoodSpecification:
+    """core/nearest_neighbors.hpp: the radius is the SQUARED distance, as in the reference"""
+
+    def __init__(self, radius_sq):
+        self.radius = float(radius_sq)
 
 
 class KNNNeighborhoodSpecification:
@@ -34,27 +40,6 @@ class KNNInRadiusNeighborhoodSpecification:
     def __init__(self, k, radius_sq):
         self.maxNumberOfNeighbors = int(k)
         self.radius = float(radius_sq)
-
-
-def _as_points(x, dim):
-    """-> (pointer, n, mem, keepalive) of an n x dim float32 array or tensor"""
-    if hasattr(x, "is_cuda"):
-        import torch
-
-        if x.dtype != torch.float32:
-            raise TypeError("points must be float32")
-        t = x.contiguous()
-        if t.dim() != 2 or t.shape[1] != dim:
-            raise ValueError(f"points must have shape (N, {dim})")
-        if t.is_cuda:
-            torch.cuda.synchronize(t.device)
-            return t.data_ptr(), int(t.shape[0]), capi.MEM_DEVICE, t
-        a = t.numpy()
-        return a.ctypes.data, a.shape[0], capi.MEM_HOST, a
-    a = np.ascontiguousarray(x, dtype=np.float32)
-    if a.ndim != 2 or a.shape[1] != dim:
-        raise ValueError(f"points must have shape (N, {dim})")
-    return a.ctypes.data, a.shape[0], capi.MEM_HOST, a
 
 
 class KDTree:
@@ -75,25 +60,26 @@ class KDTree:
     def dim(self):
         return self._dim
 
-    def _fail(self, rc, what):
-        raise capi.CilhipError(rc, f"{what}: {self._L.cilhip_last_error(None).decode()}")
+    def _rows(self, x):
+        r = _abi.rows(x, self._dim)
+        _abi.enter(r.keep, self._device)      # (for the synchronise alone: the call runs on self._device, as it always has)
+        return r
 
     def _both(self, queries):
-        p, n, mem, keep = _as_points(self._points, self._dim)
+        r = self._rows(self._points)
         if queries is None:
-            return p, n, None, n, mem, (keep,)
-        qp, nq, qmem, qkeep = _as_points(queries, self._dim)
-        if qmem != mem:
+            return r.ptr, r.n, None, r.n, r.mem, (r.keep,)
+        q = self._rows(queries)
+        if q.mem != r.mem:
             raise ValueError("reference points and queries must live in the same memory space")
-        return p, n, qp, nq, mem, (keep, qkeep)
+        return r.ptr, r.n, q.ptr, q.n, r.mem, (r.keep, q.keep)
 
     def _search(self, queries, k, radius_sq):
         p, n, qp, nq, mem, keep = self._both(queries)
         k = int(k)
         idx = np.zeros((nq, max(k, 0)), np.uint32); d2 = np.zeros((nq, max(k, 0)), np.float32); cnt = np.zeros(nq, np.uint32)
         rc = self._L.cilhip_knn_nd(self._device, p, n, qp, nq, self._dim, mem, k, C.c_float(radius_sq), idx.ctypes.data, d2.ctypes.data, cnt.ctypes.data)
-        if rc != capi.OK:
-            self._fail(rc, "cilhip_knn_nd")
+        _abi.check(rc, "cilhip_knn_nd", self._L)
         out = idx.astype(np.int64)
         out[idx == capi.NONE_IDX] = -1
         return out, d2, cnt.astype(np.int64)
@@ -116,14 +102,12 @@ class KDTree:
         off = np.zeros(nq + 1, np.uint64)
         total = C.c_size_t(0)
         rc = self._L.cilhip_radius_search_nd(self._device, p, n, qp, nq, self._dim, mem, C.c_float(radius), off.ctypes.data, None, None, 0, C.byref(total))
-        if rc != capi.OK:
-            self._fail(rc, "cilhip_radius_search_nd")
+        _abi.check(rc, "cilhip_radius_search_nd", self._L)
         idx = np.zeros(max(total.value, 1), np.uint32); d2 = np.zeros(max(total.value, 1), np.float32)
         if total.value:
             rc = self._L.cilhip_radius_search_nd(self._device, p, n, qp, nq, self._dim, mem, C.c_float(radius), off.ctypes.data, idx.ctypes.data, d2.ctypes.data,
                                                  total.value, C.byref(total))
-            if rc != capi.OK:
-                self._fail(rc, "cilhip_radius_search_nd")
+            _abi.check(rc, "cilhip_radius_search_nd", self._L)
         return off.astype(np.int64), idx[: total.value].astype(np.int64), d2[: total.value]
 
     def search(self, queries, nh):

@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .icp import _as_cloud
+from ._abi import cloud as _as_cloud
 
 
 class PlaneRANSACEstimator3f:

@@ -11,26 +11,21 @@ import ctypes as C
 
 import numpy as np
 
-from . import capi
-from .clustering import _ptr
+from . import _abi, capi
+from ._abi import ptr as _ptr
 
 
 def _matrix(distances, device):
     """-> (the array to hand over, n, mem, device)"""
-    if hasattr(distances, "is_cuda") and distances.is_cuda:
+    if _abi.on_device(distances):
         import torch
 
-        if distances.device.index is not None:
-            device = distances.device.index
-        d = distances.to(torch.float32).contiguous()
-        torch.cuda.synchronize(distances.device)
-        mem = capi.MEM_DEVICE
+        d, mem = distances.to(torch.float32).contiguous(), capi.MEM_DEVICE
     else:
-        d = np.ascontiguousarray(distances.cpu() if hasattr(distances, "cpu") else distances, np.float32)
-        mem = capi.MEM_HOST
+        d, mem = np.ascontiguousarray(distances.cpu() if hasattr(distances, "cpu") else distances, np.float32), capi.MEM_HOST
     if d.ndim != 2 or d.shape[0] != d.shape[1]:
         raise ValueError("a distance matrix is square")
-    return d, int(d.shape[0]), mem, int(device)
+    return d, int(d.shape[0]), mem, _abi.enter(d, device)[0]
 
 
 def mds_embedding(distances, max_dim=2, estimate_dim=False, distances_are_squared=True, device=0, max_outer=None, degree=None, guard=None, raise_unconverged=True):
@@ -45,18 +40,11 @@ def mds_embedding(distances, max_dim=2, estimate_dim=False, distances_are_square
         if v is not None:
             setattr(prm, key, int(v))
     room = max(min(int(max_dim), 16), 2)
-    if mem == capi.MEM_DEVICE:
-        import torch
-
-        emb = torch.empty((n, room), dtype=torch.float32, device=d.device)
-        torch.cuda.synchronize(d.device)
-    else:
-        emb = np.empty((n, room), np.float32)
+    emb = _abi.empty((n, room), np.float32, d.device if mem == capi.MEM_DEVICE else None)
     ev = np.zeros(room + 1, np.float32)
     res = capi.MdsResult()
     rc = L.cilhip_mds_embedding(device, _ptr(d), n, mem, C.byref(prm), _ptr(emb), ev.ctypes.data, C.byref(res))
-    if rc != capi.OK:
-        raise capi.CilhipError(rc, "cilhip_mds_embedding: " + L.cilhip_last_error(None).decode())
+    _abi.check(rc, "cilhip_mds_embedding", L)
     info = {k: getattr(res, k) for k, _ in capi.MdsResult._fields_}
     if raise_unconverged and res.n_converged < res.num_eigenvalues:
         raise capi.CilhipError(capi.ERR_UNSUPPORTED, "cilhip_mds_embedding: %d of %d eigenpairs converged in %d outer iterations (largest residual %.3g)"
@@ -75,14 +63,13 @@ def mds_apply(distances, x, distances_are_squared=True, device=0):
 
         xs = x.to(device=d.device, dtype=torch.float64).contiguous().reshape(n, -1)
         y = torch.empty_like(xs)
-        torch.cuda.synchronize(d.device)
+        _abi.enter(xs, device)
     else:
         xs = np.ascontiguousarray(x, np.float64).reshape(n, -1)
         y = np.empty_like(xs)
     ms = C.c_double(0.0)
     rc = L.cilhip_mds_apply(device, _ptr(d), n, mem, int(bool(distances_are_squared)), _ptr(xs), int(xs.shape[1]), _ptr(y), C.byref(ms))
-    if rc != capi.OK:
-        raise capi.CilhipError(rc, "cilhip_mds_apply: " + L.cilhip_last_error(None).decode())
+    _abi.check(rc, "cilhip_mds_apply", L)
     return y, ms.value
 
 

@@ -20,8 +20,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import capi
-from .icp import _as_cloud
+from . import _abi, capi
+from ._abi import cloud as _as_cloud
 
 
 def set_knn_tie_rule(rule):
@@ -236,20 +236,11 @@ class RobustNormalEstimation3f:
         prm.k, prm.max_sq_dist = int(k), float(radius_sq)
         m = self._mcd
         prm.num_trials, prm.num_refinements, prm.inlier_ratio, prm.chi_square_threshold, prm.seed = m._trials, m._refinements, m._ratio, m._chi, m._seed
-        if mem == capi.MEM_DEVICE:
-            import torch
-
-            dev = self._points.device
-            outs = [torch.zeros((max(n, 1), 3), dtype=torch.float32, device=dev), torch.zeros(max(n, 1), dtype=torch.float32, device=dev) if want_curvature else None,
-                    torch.zeros(max(n, 1), dtype=torch.int32, device=dev) if want_decisions else None, torch.zeros(max(n, 1), dtype=torch.uint8, device=dev) if want_decisions else None]
-            ptr = [None if o is None else o.data_ptr() for o in outs]
-        else:
-            outs = [np.zeros((max(n, 1), 3), np.float32), np.zeros(max(n, 1), np.float32) if want_curvature else None,
-                    np.zeros(max(n, 1), np.uint32) if want_decisions else None, np.zeros(max(n, 1), np.uint8) if want_decisions else None]
-            ptr = [None if o is None else o.ctypes.data for o in outs]
-        rc = self._L.cilhip_robust_normals_knn3f(self._device, p, n, mem, C.byref(prm), None if self._vp is None else self._vp.ctypes.data, *ptr)
-        if rc != capi.OK:
-            raise capi.CilhipError(rc, "cilhip_robust_normals_knn3f: " + self._L.cilhip_last_error(None).decode())
+        dev, rows = (self._points.device if mem == capi.MEM_DEVICE else None), max(n, 1)
+        outs = [_abi.empty(shape, dt, dev, zero=True) if use else None for shape, dt, use in (((rows, 3), np.float32, True), (rows, np.float32, want_curvature),
+                                                                                            (rows, np.uint32, want_decisions), (rows, np.uint8, want_decisions))]
+        rc = self._L.cilhip_robust_normals_knn3f(self._device, p, n, mem, C.byref(prm), None if self._vp is None else self._vp.ctypes.data, *[_abi.ptr(o) for o in outs])
+        _abi.check(rc, "cilhip_robust_normals_knn3f", self._L)
         return tuple(None if o is None else o[:n] for o in outs)
 
     def getNormalsAndCurvatureKNN(self, k):

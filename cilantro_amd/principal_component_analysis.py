@@ -12,32 +12,16 @@ import ctypes as C
 
 import numpy as np
 
-from . import capi
-from .clustering import _ptr
-
-
-def _points(x, device, width=None):
-    if hasattr(x, "is_cuda") and x.is_cuda:
-        import torch
-
-        if x.device.index is not None:
-            device = x.device.index
-        p = x.to(torch.float32).contiguous()
-        torch.cuda.synchronize(x.device)
-        mem = capi.MEM_DEVICE
-    else:
-        p = np.ascontiguousarray(x.cpu() if hasattr(x, "cpu") else x, np.float32)
-        mem = capi.MEM_HOST
-    if p.ndim != 2 or (width is not None and p.shape[1] != width):
-        raise ValueError("points are an n x dim array")
-    return p, mem, int(device)
+from . import _abi, capi
+from ._abi import ptr as _ptr
 
 
 class PrincipalComponentAnalysis:
     def __init__(self, data, subset=None, device=0):
         self._L = capi.load()
-        p, mem, self._device = _points(data, device)
-        n, D = int(p.shape[0]), int(p.shape[1])
+        r = _abi.rows(data, what="points", cast=True)
+        p, n, D, mem = r.keep, r.n, r.dim, r.mem
+        self._device, _ = _abi.enter(p, device)
         sub, n_sub = None, 0
         if subset is not None:
             if mem == capi.MEM_DEVICE:
@@ -45,7 +29,7 @@ class PrincipalComponentAnalysis:
 
                 sub = subset if hasattr(subset, "is_cuda") else torch.as_tensor(np.asarray(subset, np.int64))
                 sub = sub.to(device=p.device, dtype=torch.int32).contiguous()      # (the low 32 bits: uint32 indices)
-                torch.cuda.synchronize(p.device)
+                _abi.enter(sub, device)
                 n_sub = int(sub.numel())
             else:
                 sub = np.ascontiguousarray(np.asarray(subset, np.int64) & 0xFFFFFFFF, np.uint32)
@@ -57,8 +41,7 @@ class PrincipalComponentAnalysis:
         valid = C.c_int(0)
         rc = self._L.cilhip_pca_fit(self._device, _ptr(p), n, D, _ptr(sub), n_sub, mem, self.mean_.ctypes.data, self.covariance_.ctypes.data, self.eigenvalues_.ctypes.data,
                                     self._vectors.ctypes.data, C.byref(valid))
-        if rc != capi.OK:
-            raise capi.CilhipError(rc, "cilhip_pca_fit: " + self._L.cilhip_last_error(None).decode())
+        _abi.check(rc, "cilhip_pca_fit", self._L)
         self.valid_ = bool(valid.value)
         self._dim = D
 
@@ -79,21 +62,15 @@ class PrincipalComponentAnalysis:
         return self._vectors.T
 
     def _map(self, points, other, reconstruct):
-        p, mem, device = _points(points, self._device, other if reconstruct else self._dim)
-        m, out_w = int(p.shape[0]), (self._dim if reconstruct else int(other))
-        if mem == capi.MEM_DEVICE:
-            import torch
-
-            out = torch.empty((m, out_w), dtype=torch.float32, device=p.device)
-            torch.cuda.synchronize(p.device)
-        else:
-            out = np.empty((m, out_w), np.float32)
+        r = _abi.rows(points, other if reconstruct else self._dim, "points", cast=True)
+        p, m, mem = r.ptr, r.n, r.mem
+        device, dev = _abi.enter(r.keep, self._device)
+        out = _abi.empty((m, self._dim if reconstruct else int(other)), np.float32, dev)
         if reconstruct:
-            rc = self._L.cilhip_pca_reconstruct(device, _ptr(p), m, int(other), self._dim, mem, self.mean_.ctypes.data, self._vectors.ctypes.data, _ptr(out))
+            rc = self._L.cilhip_pca_reconstruct(device, p, m, int(other), self._dim, mem, self.mean_.ctypes.data, self._vectors.ctypes.data, _ptr(out))
         else:
-            rc = self._L.cilhip_pca_project(device, _ptr(p), m, self._dim, mem, self.mean_.ctypes.data, self._vectors.ctypes.data, int(other), _ptr(out))
-        if rc != capi.OK:
-            raise capi.CilhipError(rc, ("cilhip_pca_reconstruct: " if reconstruct else "cilhip_pca_project: ") + self._L.cilhip_last_error(None).decode())
+            rc = self._L.cilhip_pca_project(device, p, m, self._dim, mem, self.mean_.ctypes.data, self._vectors.ctypes.data, int(other), _ptr(out))
+        _abi.check(rc, "cilhip_pca_reconstruct" if reconstruct else "cilhip_pca_project", self._L)
         return out
 
     def project(self, points, target_dim):

@@ -17,47 +17,34 @@ import ctypes as C
 
 import numpy as np
 
-from . import capi
-from .clustering import _ptr
-from .principal_component_analysis import PrincipalComponentAnalysis, _points
+from . import _abi, capi
+from ._abi import ptr as _ptr
+from .principal_component_analysis import PrincipalComponentAnalysis
 
 NOT_BUILT = "not built: it needs the QP of convex_hull_utilities.hpp:12-193 and a dual hull"
 
 
-def _fail(L, rc, what):
-    raise capi.CilhipError(rc, what + ": " + L.cilhip_last_error(None).decode())
-
-
 def _query(L, kind, hs_cols, poly_offsets, points, dim, offset, device):
     """hs_cols: F x (dim + 1) f32 (one halfspace per row: the C layout); kind: 'dist' | 'mask' | 'idx'"""
-    p, mem, device = _points(points, device, dim)
-    n = int(p.shape[0])
-    on_device = mem == capi.MEM_DEVICE
-    if on_device:
-        import torch
-
-        def empty(shape, dt):
-            return torch.empty(shape, dtype=dt, device=p.device)
+    r = _abi.rows(points, dim, "points", cast=True)
+    p, n, mem = r.ptr, r.n, r.mem
+    device, dev = _abi.enter(r.keep, device)
     hs_cols = np.ascontiguousarray(hs_cols, np.float32)
     po = np.ascontiguousarray(poly_offsets, np.uint32)
     if kind == "dist":
         F = int(hs_cols.shape[0])
-        out = empty((F, n), torch.float32) if on_device else np.empty((F, n), np.float32)
-        rc = L.cilhip_polytope_signed_distances(device, hs_cols.ctypes.data, F, _ptr(p), n, dim, mem, _ptr(out))
-        if rc != capi.OK:
-            _fail(L, rc, "cilhip_polytope_signed_distances")
+        out = _abi.empty((F, n), np.float32, dev)
+        _abi.check(L.cilhip_polytope_signed_distances(device, hs_cols.ctypes.data, F, p, n, dim, mem, _ptr(out)), "cilhip_polytope_signed_distances", L)
         return out
     if kind == "mask":
-        out = empty((n,), torch.uint8) if on_device else np.empty(n, np.uint8)
-        rc = L.cilhip_polytopes_interior_mask(device, hs_cols.ctypes.data, po.ctypes.data, len(po) - 1, _ptr(p), n, dim, mem, C.c_float(offset), _ptr(out))
-        if rc != capi.OK:
-            _fail(L, rc, "cilhip_polytopes_interior_mask")
-        return out.bool() if on_device else out.astype(bool)
-    out = empty((max(n, 1),), torch.int32) if on_device else np.empty(max(n, 1), np.uint32)
+        out = _abi.empty(n, np.uint8, dev)
+        rc = L.cilhip_polytopes_interior_mask(device, hs_cols.ctypes.data, po.ctypes.data, len(po) - 1, p, n, dim, mem, C.c_float(offset), _ptr(out))
+        _abi.check(rc, "cilhip_polytopes_interior_mask", L)
+        return out.bool() if dev is not None else out.astype(bool)
+    out = _abi.empty(max(n, 1), np.uint32, dev)
     count = C.c_size_t(0)
-    rc = L.cilhip_polytopes_interior_indices(device, hs_cols.ctypes.data, po.ctypes.data, len(po) - 1, _ptr(p), n, dim, mem, C.c_float(offset), _ptr(out), max(n, 1), C.byref(count))
-    if rc != capi.OK:
-        _fail(L, rc, "cilhip_polytopes_interior_indices")
+    rc = L.cilhip_polytopes_interior_indices(device, hs_cols.ctypes.data, po.ctypes.data, len(po) - 1, p, n, dim, mem, C.c_float(offset), _ptr(out), max(n, 1), C.byref(count))
+    _abi.check(rc, "cilhip_polytopes_interior_indices", L)
     return out[:count.value]
 
 
@@ -83,12 +70,12 @@ class ConvexPolytope:
         if points is None:      # the default constructor: the empty polytope (:14-25), no device needed
             p, mem, n = np.zeros((1, self.dim_), np.float32), capi.MEM_HOST, 0
         else:
-            p, mem, self._device = _points(points, device, self.dim_)
-            n = int(p.shape[0])
+            r = _abi.rows(points, self.dim_, "points", cast=True)
+            p, mem, n = r.keep, r.mem, r.n
+            self._device, _ = _abi.enter(p, device)
         h, info = C.c_void_p(), capi.HullInfo()
         rc = self._L.cilhip_convex_hull_create(self._device, _ptr(p), n, self.dim_, mem, int(bool(simplicial_facets)), float(merge_tol), C.byref(h), C.byref(info))
-        if rc != capi.OK:
-            _fail(self._L, rc, "cilhip_convex_hull_create")
+        _abi.check(rc, "cilhip_convex_hull_create", self._L)
         try:
             d, V, Fh = self.dim_, info.n_vertices, info.n_halfspaces
             self.vertex_point_indices_ = np.zeros(V, np.uint32)
@@ -99,8 +86,7 @@ class ConvexPolytope:
             self.survivors_per_round_ = np.zeros(info.rounds, np.uint64)
             rc = self._L.cilhip_convex_hull_get(h, _ptr(self.vertex_point_indices_), _ptr(self.vertices_), _ptr(self._hs), _ptr(fo), _ptr(fi), _ptr(fn), _ptr(vo), _ptr(vf),
                                                 _ptr(self.survivors_per_round_))
-            if rc != capi.OK:
-                _fail(self._L, rc, "cilhip_convex_hull_get")
+            _abi.check(rc, "cilhip_convex_hull_get", self._L)
         finally:
             self._L.cilhip_convex_hull_destroy(h)
         self.is_empty_ = bool(info.is_empty)
