@@ -4,7 +4,7 @@
 // examples/connected_component_extraction.cpp.
 //
 // The contract (DESIGN.md section 11 has it in full; every rule cites the reference lines it restates):
-//   graph     i ~ j (i != j) iff d2(i, j) < radius_sq (strict; d2 = ((dx*dx)+(dy*dy))+(dz*dz), knn.hip's d2_pinned) and the
+//   graph     i ~ j (i != j) iff d2(i, j) < radius_sq (strict; d2 = ((dx*dx)+(dy*dy))+(dz*dz), search_device.hpp's d2_pinned) and the
 //             similarity clauses hold                                                   connected_component_extraction.hpp:201-204
 //   clauses   distance: d2 < max_distance                                               common_pair_evaluators.hpp:100, :159, :185, :243
 //             colours:  |c_i - c_j|^2 < fl(color_thresh * color_thresh); |v|^2 = x*x + (y*y + z*z)      :136-141
@@ -19,8 +19,9 @@
 //
 // The reference runs a serial stack flood fill per seed.  Here: a lock-free union-find over the uniform grid of grid_build.hip, no
 // neighbour list is ever written.
-//   k_cc_hook      one lane per point in grid-cell order (neighbouring lanes of a wave scan the same cells); scans the cells the ball
-//                  overlaps (the bounds of knn.hip's k_radius_pca) and, for every candidate with a SMALLER original index inside the
+//   k_points_clean (grid_ball.hpp) a point with a non-finite coordinate becomes (NaN, NaN, NaN): in no cell, nobody's neighbour
+//   k_cc_hook      one lane per point in grid-cell order (neighbouring lanes of a wave scan the same cells); walks the cells the ball
+//                  can touch (grid_ball.hpp: ball_cells, ball_rows) and, for every candidate with a SMALLER original index inside the
 //                  radius that is not already under the same root and passes the clauses, unites the two.  parent[] is over ORIGINAL
 //                  indices; a link is atomicCAS(&parent[hi], hi, lo) with hi > lo, made only on a true root.
 //   k_cc_flatten   a launch of its own: root[i] = find(i).  The larger root always goes under the smaller one, so a component's root
@@ -43,25 +44,13 @@
 #include "../../include/cilantro_hip/c_api.h"
 #include "components_device.hpp"      // the union-find and cc_finish, shared with components_nd.hip
 #include "device_prims.hpp"
+#include "grid_ball.hpp"      // ball_cells / ball_rows, the points-clean step; d2_pinned and query_is_finite (search_device.hpp)
 #include "internal.hpp"
 #include "stateless.hpp"
 
 namespace cilhip {
 
 namespace {
-
-// the cells a ball can touch (never fewer): knn.hip ball_cells
-__device__ __forceinline__ void cc_ball_cells(const GridDev& g, float qx, float qy, float qz, float radius_sq, int& x0, int& x1, int& y0, int& y1, int& z0, int& z1) {
-  const float r = sqrtf(radius_sq) * 1.000001f + g.margin;
-  const float BIG = 1.0e9f;
-  x0 = max((int)floorf(fminf(fmaxf((qx - r - g.ox) * g.inv_cell, -BIG), BIG)), 0); x1 = min((int)floorf(fminf(fmaxf((qx + r - g.ox) * g.inv_cell, -BIG), BIG)), g.nx - 1);
-  y0 = max((int)floorf(fminf(fmaxf((qy - r - g.oy) * g.inv_cell, -BIG), BIG)), 0); y1 = min((int)floorf(fminf(fmaxf((qy + r - g.oy) * g.inv_cell, -BIG), BIG)), g.ny - 1);
-  z0 = max((int)floorf(fminf(fmaxf((qz - r - g.oz) * g.inv_cell, -BIG), BIG)), 0); z1 = min((int)floorf(fminf(fmaxf((qz + r - g.oz) * g.inv_cell, -BIG), BIG)), g.nz - 1);
-}
-__device__ __forceinline__ float cc_d2(float qx, float qy, float qz, float px, float py, float pz) {      // knn.hip d2_pinned
-  const float dx = __fsub_rn(qx, px), dy = __fsub_rn(qy, py), dz = __fsub_rn(qz, pz);
-  return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-}
 
 // the evaluator classes' operator() (common_pair_evaluators.hpp:100, :116-123, :139-141, :158-166, :184-187, :209-217, :242-251)
 __device__ __forceinline__ bool cc_similar(const CcClauses& c, const F3* __restrict__ nrm, const F3* __restrict__ rgb, uint32_t i, uint32_t j, float d2) {
@@ -84,46 +73,23 @@ __device__ __forceinline__ bool cc_similar(const CcClauses& c, const F3* __restr
   return true;
 }
 
-// points with a non-finite coordinate become (NaN, NaN, NaN): such a record sits in the grid's first (empty) cell, is inside nobody's
-// radius (its d2 is NaN) and searches nothing itself; an infinite coordinate never reaches the grid's bounding box
-__global__ __launch_bounds__(CC_THREADS) void k_cc_clean(const F3* __restrict__ xyz, size_t n, F3* __restrict__ out, unsigned int* n_finite) {
-  unsigned int cnt = 0;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    F3 p = xyz[i];
-    if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) ++cnt;
-    else p = F3{NAN, NAN, NAN};
-    out[i] = p;
-  }
-  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
-  if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(n_finite, cnt);
-}
-
 __global__ __launch_bounds__(CC_THREADS) void k_cc_hook(GridDev g, CcClauses c, const F3* __restrict__ nrm, const F3* __restrict__ rgb, uint32_t* parent) {
   const size_t pos = (size_t)blockIdx.x * CC_THREADS + threadIdx.x;
   if (pos >= g.n) return;
   const float4 q = g.pts[pos];
   const uint32_t i = __float_as_uint(q.w);
-  if (!(fabsf(q.x) < INFINITY && fabsf(q.y) < INFINITY && fabsf(q.z) < INFINITY)) return;      // (false for NaN too)
-  int x0, x1, y0, y1, z0, z1;
-  cc_ball_cells(g, q.x, q.y, q.z, c.radius_sq, x0, x1, y0, y1, z0, z1);
-  if (x0 > x1) return;
+  if (!query_is_finite(q.x, q.y, q.z)) return;
   uint32_t ri = i;      // an ancestor of i (its root when last looked at)
-  for (int z = z0; z <= z1; ++z)
-    for (int y = y0; y <= y1; ++y) {
-      const uint32_t row = ((uint32_t)z * (uint32_t)g.ny + (uint32_t)y) * (uint32_t)g.nx;
-      const uint32_t beg = g.cell_start[row + x0], end = g.cell_start[row + x1 + 1];
-      for (uint32_t k = beg; k < end; ++k) {
-        const float4 p = g.pts[k];
-        const uint32_t j = __float_as_uint(p.w);
-        if (j >= i) continue;      // every undirected edge once, from its larger end (and never the point itself)
-        const float d2 = cc_d2(q.x, q.y, q.z, p.x, p.y, p.z);
-        if (!(d2 < c.radius_sq)) continue;
-        ri = cc_find(parent, ri);
-        if (cc_find(parent, j) == ri) continue;      // already one component: no clause arithmetic, no gathers
-        if (!cc_similar(c, nrm, rgb, i, j, d2)) continue;
-        ri = cc_unite(parent, ri, j);
-      }
-    }
+  ball_rows(g, ball_cells(g, q.x, q.y, q.z, c.radius_sq), 0u, 1u, [&](const float4& p) {
+    const uint32_t j = __float_as_uint(p.w);
+    if (j >= i) return;      // every undirected edge once, from its larger end (and never the point itself)
+    const float d2 = d2_pinned(q.x, q.y, q.z, p.x, p.y, p.z);
+    if (!(d2 < c.radius_sq)) return;
+    ri = cc_find(parent, ri);
+    if (cc_find(parent, j) == ri) return;      // already one component: no clause arithmetic, no gathers
+    if (!cc_similar(c, nrm, rgb, i, j, d2)) return;
+    ri = cc_unite(parent, ri, j);
+  });
 }
 
 // the "given neighbours" overloads (connected_component_extraction.hpp:20-160): CSR lists instead of a search.  One lane per list.
@@ -156,16 +122,11 @@ int cc_run_fused(int device, const float* xyz, const float* nrm, const float* rg
     if (src[k]) ST_CK("connected_components", st_stage(pool, s, o.mem, src[k], n, &d_in[k]));
   uint32_t* parent = nullptr;
   ST_CK("connected_components", pool.bytes(&parent, n * sizeof(uint32_t)));
-  hipLaunchKernelGGL(k_iota<uint32_t>, dim3(cc_blocks(n)), dim3(CC_THREADS), 0, s, parent, n);      // every point its own root
+  hipLaunchKernelGGL(k_iota<uint32_t>, dim3(prim_blocks(n)), dim3(PRIM_THREADS), 0, s, parent, n);      // every point its own root
   if (cl.radius_sq > 0.0f) {
     F3* clean = nullptr;
-    unsigned int *d_fin = nullptr, n_finite = 0;
-    ST_CK("connected_components", pool.bytes(&clean, n * sizeof(F3)));
-    ST_CK("connected_components", pool.bytes(&d_fin, sizeof(unsigned int)));
-    ST_CK("connected_components", hipMemsetAsync(d_fin, 0, sizeof(unsigned int), s));
-    hipLaunchKernelGGL(k_cc_clean, dim3(cc_blocks(n)), dim3(CC_THREADS), 0, s, d_in[0], n, clean, d_fin);
-    ST_CK("connected_components", hipMemcpyAsync(&n_finite, d_fin, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
-    ST_CK("connected_components", hipStreamSynchronize(s));
+    unsigned int n_finite = 0;
+    ST_CK("connected_components", clean_points(pool, s, d_in[0], n, &clean, &n_finite));
     if (n_finite > 1) {      // (otherwise nobody has a neighbour)
       double mean[3];
       ST_CK("connected_components", build_grid(reinterpret_cast<const float*>(clean), nullptr, (uint32_t)n, s, &grid, mean, 2.0));
@@ -200,7 +161,7 @@ int cc_run_lists(int device, const uint64_t* offsets, const uint32_t* idx, const
   }
   uint32_t* parent = nullptr;
   ST_CK("connected_components", pool.bytes(&parent, n * sizeof(uint32_t)));
-  hipLaunchKernelGGL(k_iota<uint32_t>, dim3(cc_blocks(n)), dim3(CC_THREADS), 0, s, parent, n);      // every point its own root
+  hipLaunchKernelGGL(k_iota<uint32_t>, dim3(prim_blocks(n)), dim3(PRIM_THREADS), 0, s, parent, n);      // every point its own root
   hipLaunchKernelGGL(k_cc_hook_lists, dim3((unsigned)((n + CC_THREADS - 1) / CC_THREADS)), dim3(CC_THREADS), 0, s, d_off, d_idx, d_keep, (unsigned long long)n_entries, (uint32_t)n,
                      skip_first ? 1u : 0u, parent);
   ST_CK("connected_components", hipGetLastError());

@@ -128,7 +128,7 @@ __global__ __launch_bounds__(CC_THREADS) void k_cc_labels(const uint32_t* __rest
   }
 }
 
-inline int cc_blocks(size_t n) { return (int)std::min<size_t>((n + CC_THREADS - 1) / CC_THREADS, 2048) + (n == 0); }
+static_assert(CC_THREADS == PRIM_THREADS, "the grid-stride kernels here are launched with prim_blocks() blocks");
 
 struct CcOut {
   int mem;
@@ -143,7 +143,7 @@ struct CcOut {
 // everything after the hook step: parent[] (device, over original indices) -> the caller's outputs
 inline int cc_finish(const CcOut& o, DevPool& pool, hipStream_t s, uint32_t* parent) {
   const size_t n = o.n;
-  const dim3 grid(cc_blocks(n)), block(CC_THREADS);
+  const dim3 grid(prim_blocks(n)), block(CC_THREADS);
   uint32_t *root = nullptr, *count = nullptr, *seeded = nullptr, *rank = nullptr;
   unsigned long long *keys = nullptr, *keys_sorted = nullptr;
   unsigned int* n_kept_d = nullptr;
@@ -160,7 +160,7 @@ inline int cc_finish(const CcOut& o, DevPool& pool, hipStream_t s, uint32_t* par
     ST_CK("connected_components", hipMemsetAsync(seeded, 0, n * sizeof(uint32_t), s));
     if (o.n_seeds) {
       ST_CK("connected_components", hipMemcpyAsync(d_seeds, o.seeds, o.n_seeds * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-      hipLaunchKernelGGL(k_cc_mark_seeds, dim3(cc_blocks(o.n_seeds)), block, 0, s, (const uint32_t*)root, (const uint32_t*)d_seeds, o.n_seeds, seeded);
+      hipLaunchKernelGGL(k_cc_mark_seeds, dim3(prim_blocks(o.n_seeds)), block, 0, s, (const uint32_t*)root, (const uint32_t*)d_seeds, o.n_seeds, seeded);
     }
   }
   ST_CK("connected_components", hipMemsetAsync(count, 0, n * sizeof(uint32_t), s));
@@ -174,7 +174,7 @@ inline int cc_finish(const CcOut& o, DevPool& pool, hipStream_t s, uint32_t* par
   ST_CK("connected_components", hipStreamSynchronize(s));
   rank = count;      // (the sizes are in the keys now)
   ST_CK("connected_components", hipMemsetAsync(rank, 0xFF, n * sizeof(uint32_t), s));
-  hipLaunchKernelGGL(k_cc_rank, dim3(cc_blocks(n_kept)), block, 0, s, (const unsigned long long*)keys_sorted, (uint32_t)n_kept, rank);
+  hipLaunchKernelGGL(k_cc_rank, dim3(prim_blocks(n_kept)), block, 0, s, (const unsigned long long*)keys_sorted, (uint32_t)n_kept, rank);
   const bool host = o.mem == CILHIP_MEM_HOST;
   uint32_t* d_labels = o.labels;
   if (host) ST_CK("connected_components", pool.bytes(&d_labels, n * sizeof(uint32_t)));

@@ -25,7 +25,6 @@
 // Roots are not cached in LDS next to the column tile: not built, not measured.
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <cmath>
 #include <vector>
 
@@ -175,8 +174,6 @@ __global__ __launch_bounds__(CCN_THREADS) void k_ccn_gather(const float* __restr
   }
 }
 
-double ccn_now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 #define CCN_CK(call) ST_CK("connected_components_nd", call)
 
 struct CcnArgs {
@@ -200,7 +197,7 @@ template <int DIM> int ccn_run(const CcnArgs& a) {
   cilhip_ccn_stats stats{};
   stats.form_used = a.form;
 
-  const double t0 = ccn_now_ms();
+  const double t0 = st_now_ms();
   const float *d_pts = nullptr, *d_nrm = nullptr;
   const F3* d_rgb = nullptr;
   CCN_CK(st_stage(pool, s, a.out.mem, a.points, n * DIM, &d_pts));
@@ -208,7 +205,7 @@ template <int DIM> int ccn_run(const CcnArgs& a) {
   if (a.cl.use_colors) CCN_CK(st_stage(pool, s, a.out.mem, a.rgb, n, &d_rgb));
   uint32_t* parent = nullptr;
   CCN_CK(pool.get(&parent, n));
-  hipLaunchKernelGGL(k_iota<uint32_t>, dim3(cc_blocks(n)), dim3(CC_THREADS), 0, s, parent, n);      // every point its own root
+  hipLaunchKernelGGL(k_iota<uint32_t>, dim3(prim_blocks(n)), dim3(CC_THREADS), 0, s, parent, n);      // every point its own root
   CCN_CK(hipGetLastError());
 
   // ---- the point stream and its plan ----
@@ -223,7 +220,7 @@ template <int DIM> int ccn_run(const CcnArgs& a) {
     CCN_CK(pool.get(&d_words, 2 * DIM + 1));
     CCN_CK(hipMemsetAsync(d_words, 0xFF, DIM * sizeof(unsigned int), s));
     CCN_CK(hipMemsetAsync(d_words + DIM, 0, (DIM + 1) * sizeof(unsigned int), s));
-    hipLaunchKernelGGL(k_ccn_extent<DIM>, dim3(cc_blocks(n)), block, 0, s, d_pts, n, d_words);
+    hipLaunchKernelGGL(k_ccn_extent<DIM>, dim3(prim_blocks(n)), block, 0, s, d_pts, n, d_words);
     CCN_CK(hipGetLastError());
     CCN_CK(hipMemcpyAsync(words, d_words, sizeof(words), hipMemcpyDeviceToHost, s));
     CCN_CK(hipStreamSynchronize(s));
@@ -240,11 +237,11 @@ template <int DIM> int ccn_run(const CcnArgs& a) {
       CCN_CK(pool.get(&order, n));
       CCN_CK(pool.get(&sorted, m * DIM));
       CCN_CK(pool.get(&d_lim, 2 * tiles));
-      hipLaunchKernelGGL(k_ccn_sort_keys<DIM>, dim3(cc_blocks(n)), block, 0, s, d_pts, n, (uint32_t)axis, keys);
-      hipLaunchKernelGGL(k_iota<uint32_t>, dim3(cc_blocks(n)), dim3(CC_THREADS), 0, s, iota, n);
+      hipLaunchKernelGGL(k_ccn_sort_keys<DIM>, dim3(prim_blocks(n)), block, 0, s, d_pts, n, (uint32_t)axis, keys);
+      hipLaunchKernelGGL(k_iota<uint32_t>, dim3(prim_blocks(n)), dim3(CC_THREADS), 0, s, iota, n);
       CCN_CK(hipGetLastError());
       CCN_CK(prim_run(pool, prim_sort_pairs(keys, keys_sorted, iota, order, n, 0u, 32u, s)));      // stable: the dropped rows are the last n - m
-      hipLaunchKernelGGL(k_ccn_gather<DIM>, dim3(cc_blocks(m)), block, 0, s, d_pts, (const uint32_t*)order, (uint32_t)m, (uint32_t)axis, sorted, d_lim, d_lim + tiles);
+      hipLaunchKernelGGL(k_ccn_gather<DIM>, dim3(prim_blocks(m)), block, 0, s, d_pts, (const uint32_t*)order, (uint32_t)m, (uint32_t)axis, sorted, d_lim, d_lim + tiles);
       CCN_CK(hipGetLastError());
       tile_lim.resize(2 * tiles);
       CCN_CK(hipMemcpyAsync(tile_lim.data(), d_lim, 2 * tiles * sizeof(float), hipMemcpyDeviceToHost, s));
@@ -259,7 +256,7 @@ template <int DIM> int ccn_run(const CcnArgs& a) {
   stats.tiles_total = (size_t)plan.total;
   stats.tiles_tested = (size_t)plan.tested;
   CCN_CK(hipStreamSynchronize(s));
-  const double t1 = ccn_now_ms();
+  const double t1 = st_now_ms();
   stats.prep_ms = t1 - t0;
 
   // ---- the hook launches ----
@@ -281,11 +278,11 @@ template <int DIM> int ccn_run(const CcnArgs& a) {
     stats.launches = (size_t)launches;
     CCN_CK(hipStreamSynchronize(s));
   }
-  const double t2 = ccn_now_ms();
+  const double t2 = st_now_ms();
   stats.hook_ms = t2 - t1;
 
   if (const int rc = cc_finish(a.out, pool, s, parent)) return rc;
-  stats.finish_ms = ccn_now_ms() - t2;
+  stats.finish_ms = st_now_ms() - t2;
   g_ccn_stats = stats;
   return CILHIP_OK;
 }

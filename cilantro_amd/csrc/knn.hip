@@ -19,8 +19,14 @@
 // POSITIONS in the keys, every group of equal distances inside a list is ordered by tie_before(), and a tied k-th place is refilled
 // from ALL points at exactly that distance, first met first.  Rule 0: lowest index (the keys' own order).
 // Queries are processed in target-grid cell order (neighbouring lanes scan the same cells).
+// Kernels:
+//   k_knn                 the k-NN search above, with the neighbourhood PCA when normals are asked for
+//   k_radius_pca          radius normals: the moments of every point inside the ball, two passes, nothing listed
+//   k_radius_lists<FILL>  KDTree::radiusSearch as lists: a count pass, then a fill pass (radius_sort_unpack of knn_lists.hpp sorts them)
+//   the two radius kernels visit the cells a ball can touch through grid_ball.hpp (ball_cells, ball_rows: its order is their summation order)
 #include "../../include/cilantro_hip/c_api.h"
 #include "device_prims.hpp"
+#include "grid_ball.hpp"      // the radius forms' walk over a ball's cells; d2_pinned, query_is_finite and axis_gap (search_device.hpp)
 #include "internal.hpp"
 #include "knn_lists.hpp"
 #include "stateless.hpp"
@@ -61,12 +67,6 @@ struct KnnArgs {
   int by_pos;
 };
 
-__device__ __forceinline__ float d2_pinned(float qx, float qy, float qz, float px, float py, float pz) {
-  const float dx = __fsub_rn(qx, px), dy = __fsub_rn(qy, py), dz = __fsub_rn(qz, pz);
-  return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-}
-__device__ __forceinline__ float gap(float q, float lo, float hi, float margin) { return fmaxf(fmaxf(lo - q, q - hi) - margin, 0.0f); }
-
 __device__ __forceinline__ void scan_run(const float4* __restrict__ pts, uint32_t beg, uint32_t end, float qx, float qy, float qz, KList& L, bool by_pos) {
   if (beg >= end) return;
   const uint32_t last = end - 1;
@@ -102,7 +102,7 @@ __global__ __launch_bounds__(KNN_THREADS) void k_knn(KnnArgs a) {
   const int cx = (int)floorf(fminf(fmaxf((qx - g.ox) * g.inv_cell, -BIG), BIG));
   const int cy = (int)floorf(fminf(fmaxf((qy - g.oy) * g.inv_cell, -BIG), BIG));
   const int cz = (int)floorf(fminf(fmaxf((qz - g.oz) * g.inv_cell, -BIG), BIG));
-  const bool finite = fabsf(qx) < INFINITY && fabsf(qy) < INFINITY && fabsf(qz) < INFINITY;   // false for NaN too
+  const bool finite = query_is_finite(qx, qy, qz);
   // start at the first shell that can touch the grid (queries far outside would otherwise walk empty shells)
   int s0 = 0;
   s0 = max(s0, max(-cx, cx - (g.nx - 1)));
@@ -116,31 +116,31 @@ __global__ __launch_bounds__(KNN_THREADS) void k_knn(KnnArgs a) {
       for (int z = z0; z <= z1; ++z) {
         const bool zface = (z == cz - s) || (z == cz + s);
         const float zl = g.oz + (float)z * g.cell;
-        const float gz = gap(qz, zl, zl + g.cell, g.margin);
+        const float gz = axis_gap(qz, zl, zl + g.cell, g.margin);
         const float gz2 = gz * gz;
         if (gz2 * KNN_SHRINK > L.worst_d2()) continue;
         for (int y = y0; y <= y1; ++y) {
           const bool face = zface || (y == cy - s) || (y == cy + s);
           const float yl = g.oy + (float)y * g.cell;
-          const float gy = gap(qy, yl, yl + g.cell, g.margin);
+          const float gy = axis_gap(qy, yl, yl + g.cell, g.margin);
           const float gyz2 = gz2 + gy * gy;
           if (gyz2 * KNN_SHRINK > L.worst_d2()) continue;
           const uint32_t row = ((uint32_t)z * (uint32_t)g.ny + (uint32_t)y) * (uint32_t)g.nx;
           if (face) {
             const int xa = max(xlo, 0), xb = min(xhi, g.nx - 1);
             if (xa <= xb) {
-              const float gx = gap(qx, g.ox + (float)xa * g.cell, g.ox + (float)(xb + 1) * g.cell, g.margin);
+              const float gx = axis_gap(qx, g.ox + (float)xa * g.cell, g.ox + (float)(xb + 1) * g.cell, g.margin);
               if ((gyz2 + gx * gx) * KNN_SHRINK <= L.worst_d2()) scan_run(g.pts, g.cell_start[row + xa], g.cell_start[row + xb + 1], qx, qy, qz, L, by_pos);
             }
           } else {
             if (xlo >= 0 && xlo < g.nx) {
               const float xl = g.ox + (float)xlo * g.cell;
-              const float gx = gap(qx, xl, xl + g.cell, g.margin);
+              const float gx = axis_gap(qx, xl, xl + g.cell, g.margin);
               if ((gyz2 + gx * gx) * KNN_SHRINK <= L.worst_d2()) scan_run(g.pts, g.cell_start[row + xlo], g.cell_start[row + xlo + 1], qx, qy, qz, L, by_pos);
             }
             if (xhi >= 0 && xhi < g.nx && xhi != xlo) {
               const float xl = g.ox + (float)xhi * g.cell;
-              const float gx = gap(qx, xl, xl + g.cell, g.margin);
+              const float gx = axis_gap(qx, xl, xl + g.cell, g.margin);
               if ((gyz2 + gx * gx) * KNN_SHRINK <= L.worst_d2()) scan_run(g.pts, g.cell_start[row + xhi], g.cell_start[row + xhi + 1], qx, qy, qz, L, by_pos);
             }
           }
@@ -182,11 +182,11 @@ __global__ __launch_bounds__(KNN_THREADS) void k_knn(KnnArgs a) {
             const int z0 = max(cz - s, 0), z1 = min(cz + s, g.nz - 1), y0 = max(cy - s, 0), y1 = min(cy + s, g.ny - 1);
             for (int z = z0; z <= z1; ++z) {
               const float zl = g.oz + (float)z * g.cell;
-              const float az = gap(qz, zl, zl + g.cell, g.margin);
+              const float az = axis_gap(qz, zl, zl + g.cell, g.margin);
               for (int y = y0; y <= y1; ++y) {
                 const bool face = (z == cz - s) || (z == cz + s) || (y == cy - s) || (y == cy + s);
                 const float yl = g.oy + (float)y * g.cell;
-                const float ay = gap(qy, yl, yl + g.cell, g.margin);
+                const float ay = axis_gap(qy, yl, yl + g.cell, g.margin);
                 if ((az * az + ay * ay) * KNN_SHRINK > bd) continue;
                 const uint32_t row = ((uint32_t)z * (uint32_t)g.ny + (uint32_t)y) * (uint32_t)g.nx;
                 uint32_t rb[2] = {0, 0}, re[2] = {0, 0};
@@ -296,33 +296,21 @@ __global__ __launch_bounds__(KNN_THREADS) void k_radius_pca(KnnArgs a) {
   const float qx = q4.x, qy = q4.y, qz = q4.z;
   const uint32_t orig = __float_as_uint(q4.w);
   float n0 = NAN, n1 = NAN, n2 = NAN, curv = NAN;
-  const bool finite = fabsf(qx) < INFINITY && fabsf(qy) < INFINITY && fabsf(qz) < INFINITY;
-  if (finite && g.n > 0 && a.radius_sq > 0.0f) {
-    const float r = sqrtf(a.radius_sq) * 1.000001f + g.margin;   // cells the ball can touch (never fewer)
-    const float BIG = 1.0e9f;
-    const int x0 = max((int)floorf(fminf(fmaxf((qx - r - g.ox) * g.inv_cell, -BIG), BIG)), 0), x1 = min((int)floorf(fminf(fmaxf((qx + r - g.ox) * g.inv_cell, -BIG), BIG)), g.nx - 1);
-    const int y0 = max((int)floorf(fminf(fmaxf((qy - r - g.oy) * g.inv_cell, -BIG), BIG)), 0), y1 = min((int)floorf(fminf(fmaxf((qy + r - g.oy) * g.inv_cell, -BIG), BIG)), g.ny - 1);
-    const int z0 = max((int)floorf(fminf(fmaxf((qz - r - g.oz) * g.inv_cell, -BIG), BIG)), 0), z1 = min((int)floorf(fminf(fmaxf((qz + r - g.oz) * g.inv_cell, -BIG), BIG)), g.nz - 1);
+  if (query_is_finite(qx, qy, qz) && g.n > 0 && a.radius_sq > 0.0f) {
+    const BallCells cells = ball_cells(g, qx, qy, qz, a.radius_sq);
     double s0 = 0.0, s1 = 0.0, s2 = 0.0, cnt = 0.0;
     float m0 = 0.f, m1 = 0.f, m2 = 0.f;
     double cs[6] = {0, 0, 0, 0, 0, 0};
-    for (int pass = 0; pass < 2; ++pass) {
-      if (x0 <= x1)
-        for (int z = z0; z <= z1; ++z)
-          for (int y = y0; y <= y1; ++y) {
-            const uint32_t row = ((uint32_t)z * (uint32_t)g.ny + (uint32_t)y) * (uint32_t)g.nx;
-            const uint32_t beg = g.cell_start[row + x0], end = g.cell_start[row + x1 + 1];
-            for (uint32_t j = beg; j < end; ++j) {
-              const float4 p = g.pts[j];
-              if (!(d2_pinned(qx, qy, qz, p.x, p.y, p.z) < a.radius_sq)) continue;
-              if (pass == 0) { s0 += (double)p.x; s1 += (double)p.y; s2 += (double)p.z; cnt += 1.0; }
-              else {
-                const float t0 = __fsub_rn(p.x, m0), t1 = __fsub_rn(p.y, m1), t2 = __fsub_rn(p.z, m2);
-                cs[0] += (double)__fmul_rn(t0, t0); cs[1] += (double)__fmul_rn(t0, t1); cs[2] += (double)__fmul_rn(t0, t2);
-                cs[3] += (double)__fmul_rn(t1, t1); cs[4] += (double)__fmul_rn(t1, t2); cs[5] += (double)__fmul_rn(t2, t2);
-              }
-            }
-          }
+    for (int pass = 0; pass < 2; ++pass) {      // the sums of both passes: in ball_rows' order
+      ball_rows(g, cells, 0u, 1u, [&](const float4& p) {
+        if (!(d2_pinned(qx, qy, qz, p.x, p.y, p.z) < a.radius_sq)) return;
+        if (pass == 0) { s0 += (double)p.x; s1 += (double)p.y; s2 += (double)p.z; cnt += 1.0; }
+        else {
+          const float t0 = __fsub_rn(p.x, m0), t1 = __fsub_rn(p.y, m1), t2 = __fsub_rn(p.z, m2);
+          cs[0] += (double)__fmul_rn(t0, t0); cs[1] += (double)__fmul_rn(t0, t1); cs[2] += (double)__fmul_rn(t0, t2);
+          cs[3] += (double)__fmul_rn(t1, t1); cs[4] += (double)__fmul_rn(t1, t2); cs[5] += (double)__fmul_rn(t2, t2);
+        }
+      });
       if (pass == 0) {
         if (cnt < 3.0) break;
         m0 = (float)(s0 / cnt); m1 = (float)(s1 / cnt); m2 = (float)(s2 / cnt);
@@ -383,8 +371,7 @@ int knn_impl(int device, const float* ref_xyz, size_t n_ref, const float* query_
     // ~k/4 points per cell: the k-th neighbour then normally lies inside the 3x3x3 block of cells
     {
       const hipError_t eg = build_grid(d_ref, nullptr, (uint32_t)n_ref, s, &gr, mean, std::max(1.0, (double)k / 4.0));
-      if (eg == GRID_RANGE_ERROR) return st_fail(CILHIP_ERR_UNSUPPORTED, "grid", kGridRangeMessage);
-      ST_CK("knn", eg);
+      GRID_CK("grid", "knn", eg);
     }   // (radius-only: 1 point per cell)
     // queries in target-grid cell order (identity transform)
     ST_CK("knn", pool.get(&d_qs, n_query));
@@ -465,15 +452,6 @@ int knn_impl(int device, const float* ref_xyz, size_t n_ref, const float* query_
 // per query, ascending by distance.  The reference orders equal distances as std::sort leaves them (unspecified); here
 // ties are ordered by index.  Three passes over the cells a query's ball can touch: count, then -- after a prefix sum of
 // the counts in the callers' query order -- fill packed (d2, index) keys, then one segmented radix sort of all lists.
-__device__ __forceinline__ void ball_cells(const GridDev& g, float qx, float qy, float qz, float radius_sq, int& x0, int& x1, int& y0, int& y1,
-                                           int& z0, int& z1) {
-  const float r = sqrtf(radius_sq) * 1.000001f + g.margin;   // cells the ball can touch (never fewer)
-  const float BIG = 1.0e9f;
-  x0 = max((int)floorf(fminf(fmaxf((qx - r - g.ox) * g.inv_cell, -BIG), BIG)), 0); x1 = min((int)floorf(fminf(fmaxf((qx + r - g.ox) * g.inv_cell, -BIG), BIG)), g.nx - 1);
-  y0 = max((int)floorf(fminf(fmaxf((qy - r - g.oy) * g.inv_cell, -BIG), BIG)), 0); y1 = min((int)floorf(fminf(fmaxf((qy + r - g.oy) * g.inv_cell, -BIG), BIG)), g.ny - 1);
-  z0 = max((int)floorf(fminf(fmaxf((qz - r - g.oz) * g.inv_cell, -BIG), BIG)), 0); z1 = min((int)floorf(fminf(fmaxf((qz + r - g.oz) * g.inv_cell, -BIG), BIG)), g.nz - 1);
-}
-
 // FILL = false: counts[orig] = neighbours of the query; FILL = true: keys[offsets[orig] + j] = (bits(d2) << 32) | index
 template <bool FILL>
 __global__ __launch_bounds__(KNN_THREADS) void k_radius_lists(GridDev g, const float4* __restrict__ queries, uint32_t nq, float radius_sq,
@@ -485,24 +463,13 @@ __global__ __launch_bounds__(KNN_THREADS) void k_radius_lists(GridDev g, const f
   const uint32_t orig = __float_as_uint(q4.w);
   unsigned long long cnt = 0;
   const unsigned long long base = FILL ? counts_or_offsets[orig] : 0ull;
-  const bool finite = fabsf(qx) < INFINITY && fabsf(qy) < INFINITY && fabsf(qz) < INFINITY;
-  if (finite && g.n > 0 && radius_sq > 0.0f) {
-    int x0, x1, y0, y1, z0, z1;
-    ball_cells(g, qx, qy, qz, radius_sq, x0, x1, y0, y1, z0, z1);
-    if (x0 <= x1)
-      for (int z = z0; z <= z1; ++z)
-        for (int y = y0; y <= y1; ++y) {
-          const uint32_t row = ((uint32_t)z * (uint32_t)g.ny + (uint32_t)y) * (uint32_t)g.nx;
-          const uint32_t beg = g.cell_start[row + x0], end = g.cell_start[row + x1 + 1];
-          for (uint32_t j = beg; j < end; ++j) {
-            const float4 p = g.pts[j];
-            const float d2 = d2_pinned(qx, qy, qz, p.x, p.y, p.z);
-            if (!(d2 < radius_sq)) continue;
-            if (FILL) keys[base + cnt] = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned long long)__float_as_uint(p.w);
-            ++cnt;
-          }
-        }
-  }
+  if (query_is_finite(qx, qy, qz) && g.n > 0 && radius_sq > 0.0f)
+    ball_rows(g, ball_cells(g, qx, qy, qz, radius_sq), 0u, 1u, [&](const float4& p) {
+      const float d2 = d2_pinned(qx, qy, qz, p.x, p.y, p.z);
+      if (!(d2 < radius_sq)) return;
+      if (FILL) keys[base + cnt] = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned long long)__float_as_uint(p.w);
+      ++cnt;
+    });
   if (!FILL) counts_or_offsets[orig] = cnt;
 }
 
@@ -534,8 +501,7 @@ int radius_impl(int device, const float* ref_xyz, size_t n_ref, const float* que
     double mean[3];
     {
       const hipError_t eg = build_grid(d_ref, nullptr, (uint32_t)n_ref, s, &gr, mean, 2.0);
-      if (eg == GRID_RANGE_ERROR) return st_fail(CILHIP_ERR_UNSUPPORTED, "grid", kGridRangeMessage);
-      ST_CK("radius_search", eg);
+      GRID_CK("grid", "radius_search", eg);
     }
     ST_CK("radius_search", pool.get(&d_qs, n_query));
     {

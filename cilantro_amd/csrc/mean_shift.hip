@@ -14,79 +14,50 @@
 //             labels[i] = rank of the lowest leader ~ i; a NaN seed is a singleton
 //   modes     per cluster the f64 sum of the members' shifted seeds / size                                 :102-112
 //
-// Kernels:
+// Kernels (every walk over a ball's cells is grid_ball.hpp's: ball_cells, ball_rows):
+//   k_points_clean     (grid_ball.hpp) a point with a non-finite coordinate becomes (NaN, NaN, NaN): in no cell, in nobody's ball
+//   k_ms_seed_keys     the seeds' starting cells: the sort keys of the first active list
 //   k_ms_shift<false>  one lane per active seed, the active list sorted once by the seeds' initial grid cell (a wave's lanes walk the
 //                      same cells): many seeds, small balls
 //   k_ms_shift<true>   one wave per active seed, the lanes stride over the x-runs of the ball's (z, y) rows, f64 partials per lane and a
 //                      fixed __shfl_down tree: few seeds whose balls hold a large part of the cloud
 //   both write the new seed and append an unconverged seed to the next active list (one integer atomicAdd per wave).
-//   k_ms_lead / k_ms_claim / k_ms_compact   one grouping round over the undecided set U: a seed of U without a lower-index ~-neighbour in
-//                      U is a leader; a wave per new leader marks every ~ seed as decided and hands it min(leader index) by an integer
-//                      atomicMin; U is compacted.  Exact; a chain of leaders needs about one round per two seeds.
-//   then ranks of the leader flags (rocPRIM scan), labels, a stable rocPRIM sort of the seed indices by label, offsets, and one wave per
-//   cluster for the mode.
+//   k_ms_group_init / k_ms_lead / k_ms_claim / k_ms_compact   the grouping: U = the finite seeds; per round a seed of U without a
+//                      lower-index ~-neighbour in U is a leader (k_ms_lead walks its ball cell by cell and leaves early); a wave per new
+//                      leader marks every ~ seed as decided and hands it min(leader index) by an integer atomicMin; U is compacted.
+//                      Exact; a chain of leaders needs about one round per two seeds.
+//   then ms_finish (mean_shift_device.hpp, shared with mean_shift_nd.hip): k_ms_leader_flags, their ranks (rocPRIM scan), k_ms_labels, a
+//   stable rocPRIM sort of the seed indices by label, offsets, and k_ms_modes<3>, one wave per cluster.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cfloat>
-#include <chrono>
 #include <cmath>
 
 #include "../../include/cilantro_hip/c_api.h"
 #include "device_prims.hpp"
+#include "grid_ball.hpp"      // ball_cells / ball_rows, the points-clean step; d2_pinned and query_is_finite (search_device.hpp)
 #include "internal.hpp"
-#include "search_device.hpp"
+#include "mean_shift_device.hpp"      // what mean_shift_nd.hip shares: MsArgs, MsShift, the state words, ms_finish
 #include "stateless.hpp"
 
 namespace cilhip {
 
 namespace {
 
-constexpr int MS_THREADS = 256;
-constexpr int MS_WAVES = MS_THREADS / 64;
-constexpr uint32_t MS_UNDECIDED = 0u, MS_MEMBER = 1u, MS_LEADER = 2u;
 // form 0: one wave per seed from this estimated mean ball population on.  Measured (NOTEBOOK 2026-10-19, profiles/mean_shift_bench.json:
 // frame_1 downsampled, 15 531 seeds, time per pass wave / lane): x1.30 at an estimate of 189, x0.79 at 638 -- the crossover is near 380;
 // with fewer seeds the wave form wins earlier (1500 seeds: x0.19 at 612), so the constant errs towards the lane form only where both are fast.
 constexpr double MS_WAVE_FORM_MIN_BALL = 384.0;
 
-struct MsShift {
-  float radius_sq, conv_tol_sq;
-  int kind; float coeff;
-};
-
 thread_local cilhip_ms_stats g_ms_stats{};
-
-__device__ __forceinline__ bool ms_finite(float x, float y, float z) { return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY; }      // (false for NaN too)
-
-// the cells a ball can touch (never fewer): components.hip cc_ball_cells
-__device__ __forceinline__ void ms_ball_cells(const GridDev& g, float qx, float qy, float qz, float radius_sq, int& x0, int& x1, int& y0, int& y1, int& z0, int& z1) {
-  const float r = sqrtf(radius_sq) * 1.000001f + g.margin;
-  const float BIG = 1.0e9f;
-  x0 = max((int)floorf(fminf(fmaxf((qx - r - g.ox) * g.inv_cell, -BIG), BIG)), 0); x1 = min((int)floorf(fminf(fmaxf((qx + r - g.ox) * g.inv_cell, -BIG), BIG)), g.nx - 1);
-  y0 = max((int)floorf(fminf(fmaxf((qy - r - g.oy) * g.inv_cell, -BIG), BIG)), 0); y1 = min((int)floorf(fminf(fmaxf((qy + r - g.oy) * g.inv_cell, -BIG), BIG)), g.ny - 1);
-  z0 = max((int)floorf(fminf(fmaxf((qz - r - g.oz) * g.inv_cell, -BIG), BIG)), 0); z1 = min((int)floorf(fminf(fmaxf((qz + r - g.oz) * g.inv_cell, -BIG), BIG)), g.nz - 1);
-}
-
-// points with a non-finite coordinate become (NaN, NaN, NaN): in no cell, in nobody's ball (components.hip k_cc_clean)
-__global__ __launch_bounds__(MS_THREADS) void k_ms_clean(const F3* __restrict__ xyz, size_t n, F3* __restrict__ out, unsigned int* n_finite) {
-  unsigned int cnt = 0;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    F3 p = xyz[i];
-    if (ms_finite(p.x, p.y, p.z)) ++cnt;
-    else p = F3{NAN, NAN, NAN};
-    out[i] = p;
-  }
-  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
-  if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(n_finite, cnt);
-}
 
 // the grid cell of every seed's starting position (clamped into the grid; 0 for a non-finite seed): the sort key of the first active list
 __global__ __launch_bounds__(MS_THREADS) void k_ms_seed_keys(GridDev g, const F3* __restrict__ seeds, size_t ns, uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < ns; i += (size_t)gridDim.x * blockDim.x) {
     const F3 q = seeds[i];
     uint32_t key = 0u;
-    if (ms_finite(q.x, q.y, q.z)) {
+    if (query_is_finite(q.x, q.y, q.z)) {
       const int cx = min(max(grid_cell_coord(q.x, g.ox, g.inv_cell), 0), g.nx - 1), cy = min(max(grid_cell_coord(q.y, g.oy, g.inv_cell), 0), g.ny - 1),
                 cz = min(max(grid_cell_coord(q.z, g.oz, g.inv_cell), 0), g.nz - 1);
       key = ((uint32_t)cz * (uint32_t)g.ny + (uint32_t)cy) * (uint32_t)g.nx + (uint32_t)cx;
@@ -108,24 +79,14 @@ __global__ __launch_bounds__(MS_THREADS) void k_ms_shift(GridDev g, int have_gri
   F3 q{NAN, NAN, NAN};
   if (live) q = cur[i];
   double sx = 0.0, sy = 0.0, sz = 0.0, sw = 0.0;
-  if (live && have_grid && ms_finite(q.x, q.y, q.z)) {
-    int x0, x1, y0, y1, z0, z1;
-    ms_ball_cells(g, q.x, q.y, q.z, m.radius_sq, x0, x1, y0, y1, z0, z1);
-    if (x0 <= x1)
-      for (int z = z0; z <= z1; ++z)
-        for (int y = y0; y <= y1; ++y) {
-          const uint32_t row = ((uint32_t)z * (uint32_t)g.ny + (uint32_t)y) * (uint32_t)g.nx;
-          const uint32_t beg = g.cell_start[row + x0], end = g.cell_start[row + x1 + 1];
-          for (uint32_t k = beg + (WAVE ? lane : 0u); k < end; k += (WAVE ? 64u : 1u)) {
-            const float4 p = g.pts[k];
-            const float d2 = d2_pinned(q.x, q.y, q.z, p.x, p.y, p.z);
-            if (!(d2 < m.radius_sq)) continue;
-            const double w = (double)corr_weight(m.kind, m.coeff, d2);
-            sx += w * (double)p.x; sy += w * (double)p.y; sz += w * (double)p.z;      // (each product is exact: 24 x 24 bits)
-            sw += w;
-          }
-        }
-  }
+  if (live && have_grid && query_is_finite(q.x, q.y, q.z))      // the step's fixed summation order: ball_rows' (per lane when WAVE)
+    ball_rows(g, ball_cells(g, q.x, q.y, q.z, m.radius_sq), WAVE ? lane : 0u, WAVE ? 64u : 1u, [&](const float4& p) {
+      const float d2 = d2_pinned(q.x, q.y, q.z, p.x, p.y, p.z);
+      if (!(d2 < m.radius_sq)) return;
+      const double w = (double)corr_weight(m.kind, m.coeff, d2);
+      sx += w * (double)p.x; sy += w * (double)p.y; sz += w * (double)p.z;      // (each product is exact: 24 x 24 bits)
+      sw += w;
+    });
   if (WAVE) { sx = wave_sum(sx); sy = wave_sum(sy); sz = wave_sum(sz); sw = wave_sum(sw); }
   bool keep = false;
   if (live && (!WAVE || lane == 0)) {
@@ -148,7 +109,7 @@ __global__ __launch_bounds__(MS_THREADS) void k_ms_group_init(const F3* __restri
     bool und = false;
     if (i < ns) {
       const F3 q = cur[i];
-      und = ms_finite(q.x, q.y, q.z);
+      und = query_is_finite(q.x, q.y, q.z);
       state[i] = und ? MS_UNDECIDED : MS_LEADER;
       lead_of[i] = und ? NONE_U32 : (uint32_t)i;
     }
@@ -170,12 +131,11 @@ __global__ __launch_bounds__(MS_THREADS) void k_ms_lead(GridDev g, float tol_sq,
     i = U[slot];
     leader = true;
     const F3 q = cur[i];
-    int x0, x1, y0, y1, z0, z1;
-    ms_ball_cells(g, q.x, q.y, q.z, tol_sq, x0, x1, y0, y1, z0, z1);
-    for (int z = z0; z <= z1 && leader; ++z)
-      for (int y = y0; y <= y1 && leader; ++y) {
+    const BallCells b = ball_cells(g, q.x, q.y, q.z, tol_sq);      // (walked cell by cell, with the two early exits: not ball_rows)
+    for (int z = b.z0; z <= b.z1 && leader; ++z)
+      for (int y = b.y0; y <= b.y1 && leader; ++y) {
         const uint32_t row = ((uint32_t)z * (uint32_t)g.ny + (uint32_t)y) * (uint32_t)g.nx;
-        for (int x = x0; x <= x1 && leader; ++x) {
+        for (int x = b.x0; x <= b.x1 && leader; ++x) {
           const uint32_t beg = g.cell_start[row + x], end = g.cell_start[row + x + 1];
           for (uint32_t k = beg; k < end; ++k) {
             const float4 p = g.pts[k];
@@ -203,21 +163,12 @@ __global__ __launch_bounds__(MS_THREADS) void k_ms_claim(GridDev g, float tol_sq
     const uint32_t L = new_leaders[w];
     const F3 q = cur[L];
     if (lane == 0) { state[L] = MS_LEADER; lead_of[L] = L; }
-    int x0, x1, y0, y1, z0, z1;
-    ms_ball_cells(g, q.x, q.y, q.z, tol_sq, x0, x1, y0, y1, z0, z1);
-    if (x0 > x1) continue;
-    for (int z = z0; z <= z1; ++z)
-      for (int y = y0; y <= y1; ++y) {
-        const uint32_t row = ((uint32_t)z * (uint32_t)g.ny + (uint32_t)y) * (uint32_t)g.nx;
-        const uint32_t beg = g.cell_start[row + x0], end = g.cell_start[row + x1 + 1];
-        for (uint32_t k = beg + lane; k < end; k += 64u) {
-          const float4 p = g.pts[k];
-          const uint32_t j = __float_as_uint(p.w);
-          if (j == L || !(d2_pinned(q.x, q.y, q.z, p.x, p.y, p.z) < tol_sq)) continue;
-          if (state[j] == MS_UNDECIDED) state[j] = MS_MEMBER;      // (several leaders may store the same word)
-          atomicMin(lead_of + j, L);
-        }
-      }
+    ball_rows(g, ball_cells(g, q.x, q.y, q.z, tol_sq), lane, 64u, [&](const float4& p) {
+      const uint32_t j = __float_as_uint(p.w);
+      if (j == L || !(d2_pinned(q.x, q.y, q.z, p.x, p.y, p.z) < tol_sq)) return;
+      if (state[j] == MS_UNDECIDED) state[j] = MS_MEMBER;      // (several leaders may store the same word)
+      atomicMin(lead_of + j, L);
+    });
   }
 }
 
@@ -231,49 +182,7 @@ __global__ __launch_bounds__(MS_THREADS) void k_ms_compact(const uint32_t* __res
   if (keep) next[at] = i;
 }
 
-__global__ __launch_bounds__(MS_THREADS) void k_ms_flags(const uint32_t* __restrict__ state, size_t ns, uint32_t* __restrict__ flags) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < ns; i += (size_t)gridDim.x * blockDim.x) flags[i] = state[i] == MS_LEADER ? 1u : 0u;
-}
-// rank[] = exclusive sum of the leader flags: a leader's rank is its cluster's number
-__global__ __launch_bounds__(MS_THREADS) void k_ms_labels(const uint32_t* __restrict__ lead_of, const uint32_t* __restrict__ rank, size_t ns, uint32_t* __restrict__ labels) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < ns; i += (size_t)gridDim.x * blockDim.x) labels[i] = rank[lead_of[i]];
-}
-// one wave per cluster: lane l sums members l, l + 64, ... in f64, a fixed shuffle tree adds the 64 partials, lane 0 divides by the size
-__global__ __launch_bounds__(MS_THREADS) void k_ms_modes(const F3* __restrict__ cur, const uint32_t* __restrict__ members, const uint32_t* __restrict__ offsets, uint32_t n_clusters,
-                                                         F3* __restrict__ modes) {
-  const unsigned lane = threadIdx.x & 63u;
-  const size_t n_waves = (size_t)gridDim.x * MS_WAVES;
-  for (size_t c = (size_t)blockIdx.x * MS_WAVES + (threadIdx.x >> 6); c < n_clusters; c += n_waves) {
-    const uint32_t beg = offsets[c], end = offsets[c + 1];
-    double sx = 0.0, sy = 0.0, sz = 0.0;
-    for (uint32_t k = beg + lane; k < end; k += 64u) {
-      const F3 s = cur[members[k]];
-      sx += (double)s.x; sy += (double)s.y; sz += (double)s.z;
-    }
-    sx = wave_sum(sx); sy = wave_sum(sy); sz = wave_sum(sz);
-    const double size = (double)(end - beg);
-    if (lane == 0) modes[c] = F3{(float)(sx / size), (float)(sy / size), (float)(sz / size)};
-  }
-}
-
-inline int ms_blocks(size_t n) { return (int)std::min<size_t>((n + MS_THREADS - 1) / MS_THREADS, 2048) + (n == 0); }
-inline unsigned ms_launch(size_t slots, size_t per_block) { return (unsigned)((slots + per_block - 1) / per_block); }
-double ms_now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 #define MS_CK(call) ST_CK("mean_shift", call)
-// build_grid's own refusal is not a HIP failure
-#define MS_GRID(call) do { const hipError_t ms_e_ = (call); if (ms_e_ == GRID_RANGE_ERROR) return st_fail(CILHIP_ERR_UNSUPPORTED, "mean_shift", kGridRangeMessage); \
-                           if (ms_e_ != hipSuccess) return st_fail(CILHIP_ERR_HIP, "mean_shift", #call, hipGetErrorString(ms_e_)); } while (0)
-
-struct MsArgs {
-  int device, mem;
-  const float* points; size_t n;
-  const float* seeds; size_t ns;      // seeds: the caller's array, or `points` (every point is a seed)
-  cilhip_ms_params prm;
-  float *shifted, *modes;
-  uint32_t *labels, *offsets, *members;
-  size_t *n_clusters, *iterations;
-};
 
 int ms_run(const MsArgs& a) {
   DevPool pool;
@@ -290,7 +199,7 @@ int ms_run(const MsArgs& a) {
   // ---- the points' grid ----
   const float radius_sq = a.prm.kernel_radius * a.prm.kernel_radius;
   int have_grid = 0;
-  unsigned int* d_words = nullptr;      // [0] n_finite / U cursor, [1] nan flag, [2], [3] list cursors
+  unsigned int* d_words = nullptr;      // [0] U cursor, [1] nan flag, [2], [3] list cursors
   MS_CK(pool.bytes(&d_words, 4 * sizeof(unsigned int)));
   MS_CK(hipMemsetAsync(d_words, 0, 4 * sizeof(unsigned int), s));
   unsigned int n_finite = 0;
@@ -298,14 +207,11 @@ int ms_run(const MsArgs& a) {
     const F3* d_pts = nullptr;
     F3* clean = nullptr;
     MS_CK(st_stage(pool, s, a.mem, a.points, n, &d_pts));
-    MS_CK(pool.bytes(&clean, n * sizeof(F3)));
-    hipLaunchKernelGGL(k_ms_clean, dim3(ms_blocks(n)), block, 0, s, d_pts, n, clean, d_words);
-    MS_CK(hipMemcpyAsync(&n_finite, d_words, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
-    MS_CK(hipStreamSynchronize(s));
+    MS_CK(clean_points(pool, s, d_pts, n, &clean, &n_finite));
     if (n_finite) {
       double mean[3];
       // no cell below an eighth of the radius: a ball is at most 17 x 17 rows however dense the cloud
-      MS_GRID(build_grid(reinterpret_cast<const float*>(clean), nullptr, (uint32_t)n, s, &pgrid, mean, 2.0, 1.0, 0.125 * std::sqrt((double)radius_sq)));
+      GRID_CK("mean_shift", "mean_shift", build_grid(reinterpret_cast<const float*>(clean), nullptr, (uint32_t)n, s, &pgrid, mean, 2.0, 1.0, 0.125 * std::sqrt((double)radius_sq)));
       have_grid = 1;
     }
   }
@@ -319,14 +225,14 @@ int ms_run(const MsArgs& a) {
     MS_CK(hipMemcpyAsync(cur, a.seeds, ns * sizeof(F3), hipMemcpyDeviceToDevice, s));
   }
   uint32_t *list_a = nullptr, *list_b = nullptr, *keys = nullptr, *keys_sorted = nullptr;
-  MS_CK(pool.bytes(&list_a, ns * sizeof(uint32_t)));
-  MS_CK(pool.bytes(&list_b, ns * sizeof(uint32_t)));
+  MS_CK(pool.get(&list_a, ns + 1));      // (ns + 1 words: ms_finish)
+  MS_CK(pool.get(&list_b, ns + 1));
   MS_CK(pool.bytes(&keys, ns * sizeof(uint32_t)));
   MS_CK(pool.bytes(&keys_sorted, ns * sizeof(uint32_t)));
 
   // ---- the shift passes ----
   size_t it = 0;
-  const double t_shift0 = ms_now_ms();
+  const double t_shift0 = st_now_ms();
   if (a.prm.max_iter > 0) {
     bool wave = a.prm.form == 2;
     if (have_grid) {
@@ -335,10 +241,10 @@ int ms_run(const MsArgs& a) {
       stats.est_ball = std::min((double)n_finite, pgrid.avg_occupancy / (cell * cell * cell) * (4.18879020478639 * r * r * r));
       if (a.prm.form == 0) wave = stats.est_ball >= MS_WAVE_FORM_MIN_BALL;
       // the first active list: the seeds in the order of their starting cells (a wave's lanes then walk the same cells)
-      hipLaunchKernelGGL(k_ms_seed_keys, dim3(ms_blocks(ns)), block, 0, s, pgrid.grid, (const F3*)cur, ns, keys, list_b);
+      hipLaunchKernelGGL(k_ms_seed_keys, dim3(prim_blocks(ns)), block, 0, s, pgrid.grid, (const F3*)cur, ns, keys, list_b);
       MS_CK(prim_run(pool, prim_sort_pairs(keys, keys_sorted, list_b, list_a, ns, 0u, key_bits((uint32_t)pgrid.n_cells), s)));
     } else {
-      hipLaunchKernelGGL(k_iota<uint32_t>, dim3(ms_blocks(ns)), block, 0, s, list_a, ns);
+      hipLaunchKernelGGL(k_iota<uint32_t>, dim3(prim_blocks(ns)), block, 0, s, list_a, ns);
     }
     stats.form_used = wave ? 2 : 1;
     const MsShift m{radius_sq, a.prm.convergence_tol * a.prm.convergence_tol, a.prm.kernel_kind,
@@ -362,15 +268,15 @@ int ms_run(const MsArgs& a) {
       if (nan_any) it = a.prm.max_iter;
     }
   }
-  stats.shift_ms = ms_now_ms() - t_shift0;
+  stats.shift_ms = st_now_ms() - t_shift0;
 
   // ---- grouping ----
-  const double t_group0 = ms_now_ms();
+  const double t_group0 = st_now_ms();
   const float tol_sq = a.prm.cluster_tol * a.prm.cluster_tol;
   uint32_t *state = keys, *lead_of = keys_sorted, *new_leaders = nullptr;      // (the sort keys are done with)
   MS_CK(pool.bytes(&new_leaders, ns * sizeof(uint32_t)));
   MS_CK(hipMemsetAsync(d_words, 0, sizeof(unsigned int), s));
-  hipLaunchKernelGGL(k_ms_group_init, dim3(ms_blocks(ns)), block, 0, s, (const F3*)cur, ns, state, lead_of, list_a, d_words);
+  hipLaunchKernelGGL(k_ms_group_init, dim3(prim_blocks(ns)), block, 0, s, (const F3*)cur, ns, state, lead_of, list_a, d_words);
   unsigned int n_u = 0;
   MS_CK(hipMemcpyAsync(&n_u, d_words, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
   MS_CK(hipStreamSynchronize(s));
@@ -379,7 +285,7 @@ int ms_run(const MsArgs& a) {
     double mean[3];
     // no cell below the tolerance: k_ms_lead visits every cell of a seed's ball, and a collapsed seed set would otherwise be refined to
     // cells a 10^4-th of it (NOTEBOOK 2026-10-19: the grouping of the example's 1500 collapsed seeds took 7.3 s that way)
-    MS_GRID(build_grid(reinterpret_cast<const float*>(cur), nullptr, (uint32_t)ns, s, &sgrid, mean, 2.0, 1.0, std::sqrt((double)tol_sq)));
+    GRID_CK("mean_shift", "mean_shift", build_grid(reinterpret_cast<const float*>(cur), nullptr, (uint32_t)ns, s, &sgrid, mean, 2.0, 1.0, std::sqrt((double)tol_sq)));
     while (n_u > 0) {
       MS_CK(hipMemsetAsync(d_words + 2, 0, 2 * sizeof(unsigned int), s));
       hipLaunchKernelGGL(k_ms_lead, dim3(ms_launch(n_u, MS_THREADS)), block, 0, s, sgrid.grid, tol_sq, (const F3*)cur, (const uint32_t*)state, (const uint32_t*)list_a, (uint32_t)n_u,
@@ -394,45 +300,8 @@ int ms_run(const MsArgs& a) {
       if (++rounds > ns) return st_fail(CILHIP_ERR_HIP, "mean_shift", "the grouping did not finish");      // (every round decides the lowest undecided seed: never met)
     }
   }
-  // cluster numbers = ranks of the leaders
-  uint32_t *flags = list_a, *rank = list_b;      // (the lists are done with)
-  hipLaunchKernelGGL(k_ms_flags, dim3(ms_blocks(ns)), block, 0, s, (const uint32_t*)state, ns, flags);
-  MS_CK(prim_run(pool, prim_exclusive_sum(flags, rank, ns, s)));
-  uint32_t last[2] = {0, 0};
-  MS_CK(hipMemcpyAsync(&last[0], rank + (ns - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  MS_CK(hipMemcpyAsync(&last[1], flags + (ns - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  MS_CK(hipStreamSynchronize(s));
-  const uint32_t n_clusters = last[0] + last[1];
-  uint32_t* d_labels = a.labels;
-  if (host) MS_CK(pool.bytes(&d_labels, ns * sizeof(uint32_t)));
-  hipLaunchKernelGGL(k_ms_labels, dim3(ms_blocks(ns)), block, 0, s, (const uint32_t*)lead_of, (const uint32_t*)rank, ns, d_labels);
-  MS_CK(hipGetLastError());
-  stats.group_ms = ms_now_ms() - t_group0;      // (host clock up to the last synchronisation; the label kernel is in flight)
   stats.rounds = rounds;
-
-  // ---- member lists and modes ----
-  if (a.offsets || a.members || a.modes) {
-    uint32_t *iota = flags, *lab_sorted = new_leaders, *d_members = a.members, *d_offsets = a.offsets;
-    F3* d_modes = reinterpret_cast<F3*>(a.modes);
-    if (host || !d_members) MS_CK(pool.bytes(&d_members, ns * sizeof(uint32_t)));
-    if (host || !d_offsets) MS_CK(pool.bytes(&d_offsets, ((size_t)n_clusters + 1) * sizeof(uint32_t)));
-    MS_CK(group_by_label(pool, s, d_labels, ns, n_clusters, iota, lab_sorted, d_members, d_offsets));
-    if (a.modes) {
-      if (host) MS_CK(pool.bytes(&d_modes, (size_t)n_clusters * sizeof(F3)));
-      hipLaunchKernelGGL(k_ms_modes, dim3(std::min<unsigned>(ms_launch(n_clusters, MS_WAVES), 4096u)), block, 0, s, (const F3*)cur, (const uint32_t*)d_members, (const uint32_t*)d_offsets,
-                         n_clusters, d_modes);
-    }
-    MS_CK(hipGetLastError());
-    if (host && a.offsets) MS_CK(hipMemcpyAsync(a.offsets, d_offsets, ((size_t)n_clusters + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    if (host && a.members) MS_CK(hipMemcpyAsync(a.members, d_members, ns * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    if (host && a.modes) MS_CK(hipMemcpyAsync(a.modes, d_modes, (size_t)n_clusters * sizeof(F3), hipMemcpyDeviceToHost, s));
-  }
-  if (host) {
-    MS_CK(hipMemcpyAsync(a.shifted, cur, ns * sizeof(F3), hipMemcpyDeviceToHost, s));
-    MS_CK(hipMemcpyAsync(a.labels, d_labels, ns * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  }
-  MS_CK(hipStreamSynchronize(s));
-  *a.n_clusters = n_clusters;
+  if (const int rc = ms_finish<3>("mean_shift", a, pool, s, reinterpret_cast<const float*>(cur), state, lead_of, list_a, list_b, t_group0, &stats.group_ms)) return rc;
   *a.iterations = it;
   g_ms_stats = stats;
   return CILHIP_OK;
@@ -486,7 +355,7 @@ extern "C" int cilhip_mean_shift3f(int device, const float* points, size_t n, co
     if (offsets_out_or_null && mem == CILHIP_MEM_HOST) offsets_out_or_null[0] = 0;
     return CILHIP_OK;
   }
-  const MsArgs a{device, mem, points, n, seeds_or_null ? seeds_or_null : points, ns, *params, shifted_seeds_out, modes_out_or_null, labels_out, offsets_out_or_null,
+  const MsArgs a{device, mem, points, n, 3, seeds_or_null ? seeds_or_null : points, ns, *params, shifted_seeds_out, modes_out_or_null, labels_out, offsets_out_or_null,
                  members_out_or_null, n_clusters_out, iterations_out};
   try {
     return ms_run(a);

@@ -5,10 +5,12 @@
 //   ST_CK      a HIP call that must succeed: "<family>: <call>: <hipGetErrorString>", CILHIP_ERR_HIP
 //   st_open    device count, range test, hipSetDevice
 //   st_stage   the device image of a caller's array: the caller's own pointer (CILHIP_MEM_DEVICE) or an uploaded copy the pool owns
+//   st_now_ms  the host's steady clock in milliseconds: what the *_last_stats phase times are differences of
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <string>
 #include <type_traits>
 
@@ -56,5 +58,7 @@ template <class T> hipError_t st_stage(DevPool& pool, hipStream_t s, int mem, co
   *out = d;
   return e != hipSuccess ? e : hipMemcpyAsync(d, src, n * sizeof(U), hipMemcpyHostToDevice, s);
 }
+
+inline double st_now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 }  // namespace cilhip
