@@ -10,8 +10,8 @@
 //   Unity / Identity / RBFKernel WeightEvaluator               core/common_pair_evaluators.hpp:13-79
 //   ConnectedComponentExtraction3f             clustering/connected_component_extraction.hpp:368-428 (segment :394-422)
 //   ConnectedComponentExtractionXf, 2f         clustering/connected_component_extraction.hpp:368-457, over cilhip_connected_components_nd (c_api.h rules C1-C5)
-//   the ClusteringBase accessors               clustering/clustering_base.hpp:60-97
-//   RadiusNeighborhoodSpecification<float>     core/nearest_neighbors.hpp (the radius is a SQUARED distance)
+//   the ClusteringBase accessors               clustering/clustering_base.hpp:60-97 (detail::ClusterMaps, abi.hpp: the base of all six classes)
+//   RadiusNeighborhoodSpecification<float>     core/nearest_neighbors.hpp (the radius is a SQUARED distance; abi.hpp)
 //   AlwaysTrueEvaluator and the seven proximity evaluators      core/common_pair_evaluators.hpp:84-259, constructor arguments in the reference's order
 //
 // Clouds go in as non-owning (pointer, count) views.  An evaluator here is a description of its clauses, evaluated on the device; other
@@ -26,28 +26,13 @@
 #include <string>
 #include <vector>
 
+#include "abi.hpp"
 #include "c_api.h"
 #include "icp.hpp"
 
 namespace cilantro_hip {
 
-template <typename ScalarT = float>
-struct RadiusNeighborhoodSpecification {
-  ScalarT radius;      // squared
-  explicit RadiusNeighborhoodSpecification(ScalarT radius_sq = (ScalarT)0) : radius(radius_sq) {}
-};
-
-// core/data_containers.hpp:73-122: non-owning view of a dim x n column-major float matrix
-struct ConstDataView {
-  const float* data_ = nullptr;
-  size_t rows_ = 0, cols_ = 0;
-  ConstDataView() = default;
-  ConstDataView(const float* d, size_t dim, size_t n) : data_(d), rows_(dim), cols_(n) {}
-  ConstDataView(const std::vector<float>& v, size_t dim) : data_(v.data()), rows_(dim), cols_(dim ? v.size() / dim : 0) {}
-  const float* data() const { return data_; }
-  size_t rows() const { return rows_; }
-  size_t cols() const { return cols_; }
-};
+// (RadiusNeighborhoodSpecification and ConstDataView, the non-owning view of a dim x n column-major float matrix: abi.hpp)
 
 // what an evaluator asks of a pair: the clauses of cilhip_cc_params and the arrays they read
 struct PointSimilarityClauses {
@@ -150,42 +135,41 @@ private:
   float d_, a_, t_;
 };
 
-// (a template as in the reference, where the name is an alias template: `ConnectedComponentExtraction3f<> cce(points);`)
-template <typename PointIndexT = size_t, typename ClusterIndexT = size_t>
-class ConnectedComponentExtraction3f {
+namespace detail {
+// ConnectedComponentExtraction<float, EigenDim>::segment up to and after the C call (connected_component_extraction.hpp:368-457).  Derived
+// supplies check_normals(clauses), the dimension check of an evaluator's normals, and call(...), its one entry (which throws when it fails).
+template <class Derived, class ViewT, typename PointIndexT, typename ClusterIndexT>
+class ConnectedComponentsBase : public ClusterMaps<PointIndexT, ClusterIndexT> {
 public:
-  typedef std::vector<std::vector<PointIndexT>> ClusterToPointIndicesMap;      // clustering_base.hpp:67-68
-  typedef std::vector<ClusterIndexT> PointToClusterIndexMap;
-
-  explicit ConnectedComponentExtraction3f(const ConstPointsView& points, int device = 0) : points_(points), device_(device) {}
-
   // :409-422 -- every point is a seed
   template <class PointSimilarityEvaluator = AlwaysTrueEvaluator>
-  ConnectedComponentExtraction3f& segment(const RadiusNeighborhoodSpecification<float>& nh, const PointSimilarityEvaluator& evaluator = PointSimilarityEvaluator(),
-                                          size_t min_segment_size = 1, size_t max_segment_size = std::numeric_limits<size_t>::max()) {
+  Derived& segment(const RadiusNeighborhoodSpecification<float>& nh, const PointSimilarityEvaluator& evaluator = PointSimilarityEvaluator(), size_t min_segment_size = 1,
+                   size_t max_segment_size = std::numeric_limits<size_t>::max()) {
     return run(nh, nullptr, evaluator.clauses(), min_segment_size, max_segment_size);
   }
   // :394-407 -- only the components that hold a seed
   template <class PointSimilarityEvaluator = AlwaysTrueEvaluator>
-  ConnectedComponentExtraction3f& segment(const RadiusNeighborhoodSpecification<float>& nh, const std::vector<PointIndexT>& seeds_ind,
-                                          const PointSimilarityEvaluator& evaluator = PointSimilarityEvaluator(), size_t min_segment_size = 1,
-                                          size_t max_segment_size = std::numeric_limits<size_t>::max()) {
+  Derived& segment(const RadiusNeighborhoodSpecification<float>& nh, const std::vector<PointIndexT>& seeds_ind, const PointSimilarityEvaluator& evaluator = PointSimilarityEvaluator(),
+                   size_t min_segment_size = 1, size_t max_segment_size = std::numeric_limits<size_t>::max()) {
     return run(nh, &seeds_ind, evaluator.clauses(), min_segment_size, max_segment_size);
   }
 
-  const ClusterToPointIndicesMap& getClusterToPointIndicesMap() const { return cluster_to_point_indices_map_; }
-  const PointToClusterIndexMap& getPointToClusterIndexMap() const { return point_to_cluster_index_map_; }
-  size_t getNumberOfClusters() const { return cluster_to_point_indices_map_.size(); }
-  size_t getNumberOfPoints() const { return point_to_cluster_index_map_.size(); }
-  std::vector<PointIndexT> getLabeledPointIndices() const { return select(true); }        // clustering_base.hpp:36-45
-  std::vector<PointIndexT> getUnlabeledPointIndices() const { return select(false); }     // :49-58
+  std::vector<PointIndexT> getLabeledPointIndices() const { return this->select(true); }        // clustering_base.hpp:36-45
+  std::vector<PointIndexT> getUnlabeledPointIndices() const { return this->select(false); }     // :49-58
+
+protected:
+  ConnectedComponentsBase(const ViewT& points, int device) : points_(points), device_(device) {}
+
+  // (protected for the hooks of the thin class only: not an interface for a user's subclass)
+  ViewT points_;
+  int device_;
 
 private:
-  ConnectedComponentExtraction3f& run(const RadiusNeighborhoodSpecification<float>& nh, const std::vector<PointIndexT>* seeds, const PointSimilarityClauses& c, size_t min_size,
-                                      size_t max_size) {
+  Derived& run(const RadiusNeighborhoodSpecification<float>& nh, const std::vector<PointIndexT>* seeds, const PointSimilarityClauses& c, size_t min_size, size_t max_size) {
+    Derived& self = static_cast<Derived&>(*this);
     const size_t n = points_.cols();
     if (c.count != 0 && c.count != n) throw std::invalid_argument("segment: the evaluator's arrays and the points differ in size");
-    if (c.use_normals && c.normals_dim != 3) throw std::invalid_argument("segment: the evaluator's normals are not 3 x n");
+    self.check_normals(c);
     cilhip_cc_params prm;
     cilhip_cc_default_params(&prm);
     prm.radius_sq = nh.radius;
@@ -193,34 +177,39 @@ private:
     prm.use_normals = c.use_normals; prm.max_angle = c.max_angle; prm.angle_inclusive = c.angle_inclusive;
     prm.use_colors = c.use_colors; prm.color_thresh = c.color_thresh;
     prm.min_segment_size = min_size; prm.max_segment_size = max_size;
-    std::vector<uint32_t> seed32(seeds ? seeds->size() + 1 : 0);      // (+ 1: an empty list is still a list)
+    std::vector<uint32_t> seed32(seeds ? room(seeds->size()) : 0);      // (an empty list is still a list)
     if (seeds)
       for (size_t k = 0; k < seeds->size(); ++k) {
         if ((size_t)(*seeds)[k] >= n) throw std::invalid_argument("segment: a seed index is not below the number of points");
         seed32[k] = (uint32_t)(*seeds)[k];
       }
-    std::vector<uint32_t> labels(n + 1), offsets(n + 1), members(n + 1);
+    std::vector<uint32_t> labels(room(n)), offsets(n + 1), members(room(n));
     size_t nseg = 0;
-    const int rc = cilhip_connected_components3f(device_, points_.data(), c.normals, c.colors, n, CILHIP_MEM_HOST, &prm, seeds ? seed32.data() : nullptr, seeds ? seeds->size() : 0,
-                                                 labels.data(), offsets.data(), members.data(), &nseg);
-    if (rc != CILHIP_OK) throw std::runtime_error("cilhip_connected_components3f failed (rc " + std::to_string(rc) + "): " + cilhip_last_error(nullptr));
-    cluster_to_point_indices_map_.assign(nseg, std::vector<PointIndexT>());
-    for (size_t k = 0; k < nseg; ++k) cluster_to_point_indices_map_[k].assign(members.begin() + offsets[k], members.begin() + offsets[k + 1]);
-    point_to_cluster_index_map_.assign(labels.begin(), labels.begin() + n);
-    return *this;
+    self.call(c, prm, seeds ? seed32.data() : nullptr, seeds ? seeds->size() : 0, labels.data(), offsets.data(), members.data(), &nseg);
+    this->assign_csr(labels, n, offsets, members, nseg);
+    return self;
   }
-  std::vector<PointIndexT> select(bool labeled) const {
-    std::vector<PointIndexT> res;
-    const size_t k = getNumberOfClusters();
-    for (size_t i = 0; i < point_to_cluster_index_map_.size(); ++i)
-      if (((size_t)point_to_cluster_index_map_[i] < k) == labeled) res.push_back((PointIndexT)i);
-    return res;
-  }
+};
+}  // namespace detail
 
-  ConstPointsView points_;
-  int device_;
-  ClusterToPointIndicesMap cluster_to_point_indices_map_;
-  PointToClusterIndexMap point_to_cluster_index_map_;
+// (a template as in the reference, where the name is an alias template: `ConnectedComponentExtraction3f<> cce(points);`)
+template <typename PointIndexT = size_t, typename ClusterIndexT = size_t>
+class ConnectedComponentExtraction3f : public detail::ConnectedComponentsBase<ConnectedComponentExtraction3f<PointIndexT, ClusterIndexT>, ConstPointsView, PointIndexT, ClusterIndexT> {
+  typedef detail::ConnectedComponentsBase<ConnectedComponentExtraction3f, ConstPointsView, PointIndexT, ClusterIndexT> Base;
+  friend Base;
+
+public:
+  explicit ConnectedComponentExtraction3f(const ConstPointsView& points, int device = 0) : Base(points, device) {}
+
+private:
+  void check_normals(const PointSimilarityClauses& c) const {
+    if (c.use_normals && c.normals_dim != 3) throw std::invalid_argument("segment: the evaluator's normals are not 3 x n");
+  }
+  void call(const PointSimilarityClauses& c, const cilhip_cc_params& prm, const uint32_t* seeds, size_t n_seeds, uint32_t* labels, uint32_t* offsets, uint32_t* members, size_t* nseg) {
+    detail::check(cilhip_connected_components3f(this->device_, this->points_.data(), c.normals, c.colors, this->points_.cols(), CILHIP_MEM_HOST, &prm, seeds, n_seeds, labels, offsets,
+                                                members, nseg),
+                  "cilhip_connected_components3f");
+  }
 };
 
 // ---- ConnectedComponentExtractionXf / 2f (connected_component_extraction.hpp:368-457; c_api.h rules C1-C5) --------
@@ -228,80 +217,31 @@ private:
 // evaluator's normals are a ConstDataView of dim x n, its colours a ConstPointsView (3 x n).  form: 0 the code decides, 1 the exhaustive
 // triangle, 2 sweep and prune -- the same words (rule C4).
 template <typename PointIndexT = size_t, typename ClusterIndexT = size_t>
-class ConnectedComponentExtractionXf {
+class ConnectedComponentExtractionXf : public detail::ConnectedComponentsBase<ConnectedComponentExtractionXf<PointIndexT, ClusterIndexT>, ConstDataView, PointIndexT, ClusterIndexT> {
+  typedef detail::ConnectedComponentsBase<ConnectedComponentExtractionXf, ConstDataView, PointIndexT, ClusterIndexT> Base;
+  friend Base;
+
 public:
-  typedef std::vector<std::vector<PointIndexT>> ClusterToPointIndicesMap;
-  typedef std::vector<ClusterIndexT> PointToClusterIndexMap;
+  explicit ConnectedComponentExtractionXf(const ConstDataView& points, int device = 0, int form = 0) : Base(points, device), form_(form) {}
 
-  explicit ConnectedComponentExtractionXf(const ConstDataView& points, int device = 0, int form = 0) : points_(points), device_(device), form_(form) {}
-
-  // :409-422 -- every point is a seed
-  template <class PointSimilarityEvaluator = AlwaysTrueEvaluator>
-  ConnectedComponentExtractionXf& segment(const RadiusNeighborhoodSpecification<float>& nh, const PointSimilarityEvaluator& evaluator = PointSimilarityEvaluator(),
-                                          size_t min_segment_size = 1, size_t max_segment_size = std::numeric_limits<size_t>::max()) {
-    return run(nh, nullptr, evaluator.clauses(), min_segment_size, max_segment_size);
-  }
-  // :394-407 -- only the components that hold a seed
-  template <class PointSimilarityEvaluator = AlwaysTrueEvaluator>
-  ConnectedComponentExtractionXf& segment(const RadiusNeighborhoodSpecification<float>& nh, const std::vector<PointIndexT>& seeds_ind,
-                                          const PointSimilarityEvaluator& evaluator = PointSimilarityEvaluator(), size_t min_segment_size = 1,
-                                          size_t max_segment_size = std::numeric_limits<size_t>::max()) {
-    return run(nh, &seeds_ind, evaluator.clauses(), min_segment_size, max_segment_size);
-  }
-
-  const ClusterToPointIndicesMap& getClusterToPointIndicesMap() const { return cluster_to_point_indices_map_; }
-  const PointToClusterIndexMap& getPointToClusterIndexMap() const { return point_to_cluster_index_map_; }
-  size_t getNumberOfClusters() const { return cluster_to_point_indices_map_.size(); }
-  size_t getNumberOfPoints() const { return point_to_cluster_index_map_.size(); }
-  size_t getDimension() const { return points_.rows(); }
-  std::vector<PointIndexT> getLabeledPointIndices() const { return select(true); }        // clustering_base.hpp:36-45
-  std::vector<PointIndexT> getUnlabeledPointIndices() const { return select(false); }     // :49-58
+  size_t getDimension() const { return this->points_.rows(); }
   const cilhip_ccn_stats& getLastStats() const { return stats_; }      // what the last segment() did (zeros before one, and after one over no point)
 
 private:
-  ConnectedComponentExtractionXf& run(const RadiusNeighborhoodSpecification<float>& nh, const std::vector<PointIndexT>* seeds, const PointSimilarityClauses& c, size_t min_size,
-                                      size_t max_size) {
-    const size_t n = points_.cols(), dim = points_.rows();
-    if (c.count != 0 && c.count != n) throw std::invalid_argument("segment: the evaluator's arrays and the points differ in size");
-    if (c.use_normals && c.normals_dim != dim) throw std::invalid_argument("segment: the evaluator's normals are not dim x n");
-    cilhip_cc_params prm;
-    cilhip_cc_default_params(&prm);
-    prm.radius_sq = nh.radius;
-    prm.use_distance = c.use_distance; prm.max_distance = c.max_distance;
-    prm.use_normals = c.use_normals; prm.max_angle = c.max_angle; prm.angle_inclusive = c.angle_inclusive;
-    prm.use_colors = c.use_colors; prm.color_thresh = c.color_thresh;
-    prm.min_segment_size = min_size; prm.max_segment_size = max_size;
-    std::vector<uint32_t> seed32(seeds ? seeds->size() + 1 : 0);      // (+ 1: an empty list is still a list)
-    if (seeds)
-      for (size_t k = 0; k < seeds->size(); ++k) {
-        if ((size_t)(*seeds)[k] >= n) throw std::invalid_argument("segment: a seed index is not below the number of points");
-        seed32[k] = (uint32_t)(*seeds)[k];
-      }
-    std::vector<uint32_t> labels(n + 1), offsets(n + 1), members(n + 1);
-    size_t nseg = 0;
-    const int rc = cilhip_connected_components_nd(device_, points_.data(), c.normals, c.colors, n, dim, CILHIP_MEM_HOST, &prm, form_, seeds ? seed32.data() : nullptr,
-                                                  seeds ? seeds->size() : 0, labels.data(), offsets.data(), members.data(), &nseg);
-    if (rc != CILHIP_OK) throw std::runtime_error("cilhip_connected_components_nd failed (rc " + std::to_string(rc) + "): " + cilhip_last_error(nullptr));
+  void check_normals(const PointSimilarityClauses& c) const {
+    if (c.use_normals && c.normals_dim != this->points_.rows()) throw std::invalid_argument("segment: the evaluator's normals are not dim x n");
+  }
+  void call(const PointSimilarityClauses& c, const cilhip_cc_params& prm, const uint32_t* seeds, size_t n_seeds, uint32_t* labels, uint32_t* offsets, uint32_t* members, size_t* nseg) {
+    const size_t n = this->points_.cols();
+    detail::check(cilhip_connected_components_nd(this->device_, this->points_.data(), c.normals, c.colors, n, this->points_.rows(), CILHIP_MEM_HOST, &prm, form_, seeds, n_seeds, labels,
+                                                 offsets, members, nseg),
+                  "cilhip_connected_components_nd");
     stats_ = cilhip_ccn_stats();
     if (n) cilhip_ccn_last_stats(&stats_);
-    cluster_to_point_indices_map_.assign(nseg, std::vector<PointIndexT>());
-    for (size_t k = 0; k < nseg; ++k) cluster_to_point_indices_map_[k].assign(members.begin() + offsets[k], members.begin() + offsets[k + 1]);
-    point_to_cluster_index_map_.assign(labels.begin(), labels.begin() + n);
-    return *this;
-  }
-  std::vector<PointIndexT> select(bool labeled) const {
-    std::vector<PointIndexT> res;
-    const size_t k = getNumberOfClusters();
-    for (size_t i = 0; i < point_to_cluster_index_map_.size(); ++i)
-      if (((size_t)point_to_cluster_index_map_[i] < k) == labeled) res.push_back((PointIndexT)i);
-    return res;
   }
 
-  ConstDataView points_;
-  int device_, form_;
+  int form_;
   cilhip_ccn_stats stats_ = cilhip_ccn_stats();
-  ClusterToPointIndicesMap cluster_to_point_indices_map_;
-  PointToClusterIndexMap point_to_cluster_index_map_;
 };
 
 // ConnectedComponentExtraction<float, 2>
@@ -336,130 +276,103 @@ private:
   float sigma_;
 };
 
-template <typename PointIndexT = size_t, typename ClusterIndexT = size_t>
-class MeanShift3f {
+namespace detail {
+// MeanShift<float, EigenDim>::cluster up to and after the C call (clustering/mean_shift.hpp:38-124); the dimension is the view's rows().
+// Derived supplies check_seeds(seeds), the dimension check of a seed set, and call(...), its one entry (which throws when it fails).
+template <class Derived, class ViewT, typename PointIndexT, typename ClusterIndexT>
+class MeanShiftBase : public ClusterMaps<PointIndexT, ClusterIndexT> {
 public:
-  typedef std::vector<std::vector<PointIndexT>> ClusterToPointIndicesMap;
-  typedef std::vector<ClusterIndexT> PointToClusterIndexMap;
-
-  // (max_leaf_size: the reference's kd-tree parameter, accepted and unused)
-  explicit MeanShift3f(const ConstPointsView& points, size_t max_leaf_size = 10, int device = 0) : points_(points), device_(device) { (void)max_leaf_size; }
-
   // :38-115 -- given seeds
   template <class KernelEvaluatorT = UnityWeightEvaluator<float>>
-  MeanShift3f& cluster(const ConstPointsView& seeds, float kernel_radius, size_t max_iter, float cluster_tol, float convergence_tol = std::numeric_limits<float>::epsilon(),
-                       const KernelEvaluatorT& evaluator = KernelEvaluatorT()) {
+  Derived& cluster(const ViewT& seeds, float kernel_radius, size_t max_iter, float cluster_tol, float convergence_tol = std::numeric_limits<float>::epsilon(),
+                   const KernelEvaluatorT& evaluator = KernelEvaluatorT()) {
+    static_cast<Derived&>(*this).check_seeds(seeds);
     return run(&seeds, kernel_radius, max_iter, cluster_tol, convergence_tol, evaluator.kind(), evaluator.sigma());
   }
   // :118-124 -- every point is a seed
   template <class KernelEvaluatorT = UnityWeightEvaluator<float>>
-  MeanShift3f& cluster(float kernel_radius, size_t max_iter, float cluster_tol, float convergence_tol = std::numeric_limits<float>::epsilon(),
-                       const KernelEvaluatorT& evaluator = KernelEvaluatorT()) {
+  Derived& cluster(float kernel_radius, size_t max_iter, float cluster_tol, float convergence_tol = std::numeric_limits<float>::epsilon(),
+                   const KernelEvaluatorT& evaluator = KernelEvaluatorT()) {
     return run(nullptr, kernel_radius, max_iter, cluster_tol, convergence_tol, evaluator.kind(), evaluator.sigma());
   }
 
-  const std::vector<float>& getShiftedSeeds() const { return shifted_seeds_; }      // xyz per seed
-  const std::vector<float>& getClusterModes() const { return cluster_modes_; }      // xyz per cluster
+  const std::vector<float>& getShiftedSeeds() const { return shifted_seeds_; }      // rows() floats per seed
+  const std::vector<float>& getClusterModes() const { return cluster_modes_; }      // rows() floats per cluster
   size_t getNumberOfPerformedIterations() const { return iteration_count_; }
-  const ClusterToPointIndicesMap& getClusterToPointIndicesMap() const { return cluster_to_point_indices_map_; }
-  const PointToClusterIndexMap& getPointToClusterIndexMap() const { return point_to_cluster_index_map_; }
-  size_t getNumberOfClusters() const { return cluster_to_point_indices_map_.size(); }
-  size_t getNumberOfPoints() const { return point_to_cluster_index_map_.size(); }
 
-private:
-  MeanShift3f& run(const ConstPointsView* seeds, float kernel_radius, size_t max_iter, float cluster_tol, float convergence_tol, int kind, float sigma) {
-    const size_t ns = seeds ? seeds->cols() : points_.cols();
-    cilhip_ms_params prm;
-    cilhip_ms_default_params(&prm);
-    prm.kernel_radius = kernel_radius; prm.max_iter = max_iter; prm.cluster_tol = cluster_tol; prm.convergence_tol = convergence_tol;
-    prm.kernel_kind = kind; prm.kernel_sigma = sigma;
-    std::vector<float> shifted(3 * ns + 3), modes(3 * ns + 3), no_seed(3);
-    std::vector<uint32_t> labels(ns + 1), offsets(ns + 1), members(ns + 1);
-    size_t nc = 0, iters = 0;
-    const float* sp = seeds ? (seeds->cols() ? seeds->data() : no_seed.data()) : nullptr;      // (an empty list is still a list)
-    const int rc = cilhip_mean_shift3f(device_, points_.data(), points_.cols(), sp, seeds ? ns : 0, CILHIP_MEM_HOST, &prm, shifted.data(), labels.data(), modes.data(),
-                                       offsets.data(), members.data(), &nc, &iters);
-    if (rc != CILHIP_OK) throw std::runtime_error("cilhip_mean_shift3f failed (rc " + std::to_string(rc) + "): " + cilhip_last_error(nullptr));
-    shifted_seeds_.assign(shifted.begin(), shifted.begin() + 3 * ns);
-    cluster_modes_.assign(modes.begin(), modes.begin() + 3 * nc);
-    iteration_count_ = iters;
-    cluster_to_point_indices_map_.assign(nc, std::vector<PointIndexT>());
-    for (size_t k = 0; k < nc; ++k) cluster_to_point_indices_map_[k].assign(members.begin() + offsets[k], members.begin() + offsets[k + 1]);
-    point_to_cluster_index_map_.assign(labels.begin(), labels.begin() + ns);
-    return *this;
-  }
+protected:
+  MeanShiftBase(const ViewT& points, int device) : points_(points), device_(device) {}
 
-  ConstPointsView points_;
+  // (protected for the hooks of the thin class only: not an interface for a user's subclass)
+  ViewT points_;
   int device_;
-  size_t iteration_count_ = 0;
-  std::vector<float> shifted_seeds_, cluster_modes_;
-  ClusterToPointIndicesMap cluster_to_point_indices_map_;
-  PointToClusterIndexMap point_to_cluster_index_map_;
-};
-
-// ---- MeanShiftXf / MeanShift2f (clustering/mean_shift.hpp:142-164; c_api.h rules M1-M7, DESIGN.md section 22) ---------------------
-// MeanShift<float, Dynamic>: MeanShift3f's interface over a dim x n view, 1 <= dim <= 16; seeds, shifted seeds and modes are dim floats each.
-template <typename PointIndexT = size_t, typename ClusterIndexT = size_t>
-class MeanShiftXf {
-public:
-  typedef std::vector<std::vector<PointIndexT>> ClusterToPointIndicesMap;
-  typedef std::vector<ClusterIndexT> PointToClusterIndexMap;
-
-  // (max_leaf_size: the reference's kd-tree parameter, accepted and unused)
-  explicit MeanShiftXf(const ConstDataView& points, size_t max_leaf_size = 10, int device = 0) : points_(points), device_(device) { (void)max_leaf_size; }
-
-  // :38-115 -- given seeds
-  template <class KernelEvaluatorT = UnityWeightEvaluator<float>>
-  MeanShiftXf& cluster(const ConstDataView& seeds, float kernel_radius, size_t max_iter, float cluster_tol, float convergence_tol = std::numeric_limits<float>::epsilon(),
-                       const KernelEvaluatorT& evaluator = KernelEvaluatorT()) {
-    if (seeds.rows() != points_.rows()) throw std::invalid_argument("MeanShiftXf: the seeds have another dimension than the points");
-    return run(&seeds, kernel_radius, max_iter, cluster_tol, convergence_tol, evaluator.kind(), evaluator.sigma());
-  }
-  // :118-124 -- every point is a seed
-  template <class KernelEvaluatorT = UnityWeightEvaluator<float>>
-  MeanShiftXf& cluster(float kernel_radius, size_t max_iter, float cluster_tol, float convergence_tol = std::numeric_limits<float>::epsilon(),
-                       const KernelEvaluatorT& evaluator = KernelEvaluatorT()) {
-    return run(nullptr, kernel_radius, max_iter, cluster_tol, convergence_tol, evaluator.kind(), evaluator.sigma());
-  }
-
-  const std::vector<float>& getShiftedSeeds() const { return shifted_seeds_; }      // dim floats per seed
-  const std::vector<float>& getClusterModes() const { return cluster_modes_; }      // dim floats per cluster
-  size_t getNumberOfPerformedIterations() const { return iteration_count_; }
-  const ClusterToPointIndicesMap& getClusterToPointIndicesMap() const { return cluster_to_point_indices_map_; }
-  const PointToClusterIndexMap& getPointToClusterIndexMap() const { return point_to_cluster_index_map_; }
-  size_t getNumberOfClusters() const { return cluster_to_point_indices_map_.size(); }
-  size_t getNumberOfPoints() const { return point_to_cluster_index_map_.size(); }
-  size_t getDimension() const { return points_.rows(); }
 
 private:
-  MeanShiftXf& run(const ConstDataView* seeds, float kernel_radius, size_t max_iter, float cluster_tol, float convergence_tol, int kind, float sigma) {
+  Derived& run(const ViewT* seeds, float kernel_radius, size_t max_iter, float cluster_tol, float convergence_tol, int kind, float sigma) {
+    Derived& self = static_cast<Derived&>(*this);
     const size_t dim = points_.rows(), ns = seeds ? seeds->cols() : points_.cols();
     cilhip_ms_params prm;
     cilhip_ms_default_params(&prm);
     prm.kernel_radius = kernel_radius; prm.max_iter = max_iter; prm.cluster_tol = cluster_tol; prm.convergence_tol = convergence_tol;
     prm.kernel_kind = kind; prm.kernel_sigma = sigma;
-    std::vector<float> shifted(dim * ns + 1), modes(dim * ns + 1), no_seed(dim + 1);
-    std::vector<uint32_t> labels(ns + 1), offsets(ns + 1), members(ns + 1);
+    std::vector<float> shifted(room(dim * ns)), modes(room(dim * ns)), no_seed(room(dim));
+    std::vector<uint32_t> labels(room(ns)), offsets(ns + 1), members(room(ns));
     size_t nc = 0, iters = 0;
     const float* sp = seeds ? (seeds->cols() ? seeds->data() : no_seed.data()) : nullptr;      // (an empty list is still a list)
-    const int rc = cilhip_mean_shift_nd(device_, points_.data(), points_.cols(), dim, sp, seeds ? ns : 0, CILHIP_MEM_HOST, &prm, shifted.data(), labels.data(), modes.data(),
-                                        offsets.data(), members.data(), &nc, &iters);
-    if (rc != CILHIP_OK) throw std::runtime_error("cilhip_mean_shift_nd failed (rc " + std::to_string(rc) + "): " + cilhip_last_error(nullptr));
+    self.call(sp, seeds ? ns : 0, prm, shifted.data(), labels.data(), modes.data(), offsets.data(), members.data(), &nc, &iters);
     shifted_seeds_.assign(shifted.begin(), shifted.begin() + dim * ns);
     cluster_modes_.assign(modes.begin(), modes.begin() + dim * nc);
     iteration_count_ = iters;
-    cluster_to_point_indices_map_.assign(nc, std::vector<PointIndexT>());
-    for (size_t k = 0; k < nc; ++k) cluster_to_point_indices_map_[k].assign(members.begin() + offsets[k], members.begin() + offsets[k + 1]);
-    point_to_cluster_index_map_.assign(labels.begin(), labels.begin() + ns);
-    return *this;
+    this->assign_csr(labels, ns, offsets, members, nc);
+    return self;
   }
 
-  ConstDataView points_;
-  int device_;
   size_t iteration_count_ = 0;
   std::vector<float> shifted_seeds_, cluster_modes_;
-  ClusterToPointIndicesMap cluster_to_point_indices_map_;
-  PointToClusterIndexMap point_to_cluster_index_map_;
+};
+}  // namespace detail
+
+template <typename PointIndexT = size_t, typename ClusterIndexT = size_t>
+class MeanShift3f : public detail::MeanShiftBase<MeanShift3f<PointIndexT, ClusterIndexT>, ConstPointsView, PointIndexT, ClusterIndexT> {
+  typedef detail::MeanShiftBase<MeanShift3f, ConstPointsView, PointIndexT, ClusterIndexT> Base;
+  friend Base;
+
+public:
+  // (max_leaf_size: the reference's kd-tree parameter, accepted and unused)
+  explicit MeanShift3f(const ConstPointsView& points, size_t max_leaf_size = 10, int device = 0) : Base(points, device) { (void)max_leaf_size; }
+
+private:
+  void check_seeds(const ConstPointsView&) const {}
+  void call(const float* seeds, size_t n_seeds, const cilhip_ms_params& prm, float* shifted, uint32_t* labels, float* modes, uint32_t* offsets, uint32_t* members, size_t* nc,
+            size_t* iters) {
+    detail::check(cilhip_mean_shift3f(this->device_, this->points_.data(), this->points_.cols(), seeds, n_seeds, CILHIP_MEM_HOST, &prm, shifted, labels, modes, offsets, members, nc, iters),
+                  "cilhip_mean_shift3f");
+  }
+};
+
+// ---- MeanShiftXf / MeanShift2f (clustering/mean_shift.hpp:142-164; c_api.h rules M1-M7, DESIGN.md section 22) ---------------------
+// MeanShift<float, Dynamic>: MeanShift3f's interface over a dim x n view, 1 <= dim <= 16; seeds, shifted seeds and modes are dim floats each.
+template <typename PointIndexT = size_t, typename ClusterIndexT = size_t>
+class MeanShiftXf : public detail::MeanShiftBase<MeanShiftXf<PointIndexT, ClusterIndexT>, ConstDataView, PointIndexT, ClusterIndexT> {
+  typedef detail::MeanShiftBase<MeanShiftXf, ConstDataView, PointIndexT, ClusterIndexT> Base;
+  friend Base;
+
+public:
+  // (max_leaf_size: the reference's kd-tree parameter, accepted and unused)
+  explicit MeanShiftXf(const ConstDataView& points, size_t max_leaf_size = 10, int device = 0) : Base(points, device) { (void)max_leaf_size; }
+
+  size_t getDimension() const { return this->points_.rows(); }
+
+private:
+  void check_seeds(const ConstDataView& seeds) const {
+    if (seeds.rows() != this->points_.rows()) throw std::invalid_argument("MeanShiftXf: the seeds have another dimension than the points");
+  }
+  void call(const float* seeds, size_t n_seeds, const cilhip_ms_params& prm, float* shifted, uint32_t* labels, float* modes, uint32_t* offsets, uint32_t* members, size_t* nc,
+            size_t* iters) {
+    detail::check(cilhip_mean_shift_nd(this->device_, this->points_.data(), this->points_.cols(), this->points_.rows(), seeds, n_seeds, CILHIP_MEM_HOST, &prm, shifted, labels, modes,
+                                       offsets, members, nc, iters),
+                  "cilhip_mean_shift_nd");
+  }
 };
 
 // MeanShift<float, 2>
@@ -518,8 +431,8 @@ public:
     const uint32_t no_col = 0;
     const float no_val = 0.0f;
     cilhip_sparse* h = nullptr;
-    const int rc = cilhip_sparse_from_csr(device, n, offsets.data(), columns.empty() ? &no_col : columns.data(), values.empty() ? &no_val : values.data(), CILHIP_MEM_HOST, &h);
-    if (rc != CILHIP_OK) throw std::runtime_error("cilhip_sparse_from_csr failed (rc " + std::to_string(rc) + "): " + cilhip_last_error(nullptr));
+    detail::check(cilhip_sparse_from_csr(device, n, offsets.data(), columns.empty() ? &no_col : columns.data(), values.empty() ? &no_val : values.data(), CILHIP_MEM_HOST, &h),
+                  "cilhip_sparse_from_csr");
     return SparseAffinities(h);
   }
   const cilhip_sparse* handle() const { return h_; }
@@ -537,8 +450,8 @@ SparseAffinities getNNGraphFunctionValueSparseMatrix(const NeighborhoodSet& adj_
                                                      int device = 0) {
   std::vector<uint64_t> off(adj_list.size() + 1, 0);
   for (size_t i = 0; i < adj_list.size(); ++i) off[i + 1] = off[i] + adj_list[i].size();
-  std::vector<uint32_t> idx((size_t)off.back() + 1);
-  std::vector<float> d2((size_t)off.back() + 1);
+  std::vector<uint32_t> idx(detail::room((size_t)off.back()));
+  std::vector<float> d2(detail::room((size_t)off.back()));
   for (size_t i = 0; i < adj_list.size(); ++i)
     for (size_t j = 0; j < adj_list[i].size(); ++j) {
       if (adj_list[i][j].index >= adj_list.size()) throw std::invalid_argument("getNNGraphFunctionValueSparseMatrix: a neighbour index is not below the number of lists");
@@ -546,20 +459,17 @@ SparseAffinities getNNGraphFunctionValueSparseMatrix(const NeighborhoodSet& adj_
       d2[(size_t)off[i] + j] = adj_list[i][j].value;
     }
   cilhip_sparse* h = nullptr;
-  const int rc = cilhip_nn_graph_matrix(device, adj_list.size(), off.data(), idx.data(), d2.data(), (size_t)off.back(), CILHIP_MEM_HOST, evaluator.kind(), evaluator.sigma(),
-                                        force_symmetry ? 1 : 0, 0, &h);
-  if (rc != CILHIP_OK) throw std::runtime_error("cilhip_nn_graph_matrix failed (rc " + std::to_string(rc) + "): " + cilhip_last_error(nullptr));
+  detail::check(cilhip_nn_graph_matrix(device, adj_list.size(), off.data(), idx.data(), d2.data(), (size_t)off.back(), CILHIP_MEM_HOST, evaluator.kind(), evaluator.sigma(),
+                                       force_symmetry ? 1 : 0, 0, &h),
+                "cilhip_nn_graph_matrix");
   return SparseAffinities(h);
 }
 
 // KMeans<float, Dynamic> (kmeans.hpp:67-194), brute-force branch, 1 <= dim <= 16.  The points are a non-owning dim x n column-major view
 // (point-major floats); use_kd_tree is accepted and changes nothing (the kd-tree branch is not built in D dimensions).
 template <typename PointIndexT = size_t, typename ClusterIndexT = size_t>
-class KMeansXf {
+class KMeansXf : public detail::ClusterMaps<PointIndexT, ClusterIndexT> {
 public:
-  typedef std::vector<std::vector<PointIndexT>> ClusterToPointIndicesMap;
-  typedef std::vector<ClusterIndexT> PointToClusterIndexMap;
-
   KMeansXf() = default;
   KMeansXf(const float* data, size_t num_points, size_t dim, int device = 0) : data_(data), n_(num_points), dim_(dim), device_(device) {}
 
@@ -569,12 +479,9 @@ public:
     if (dim_ == 0 || centroids.size() % dim_ != 0) throw std::invalid_argument("KMeansXf: the centroids are dim floats each");
     cluster_centroids_ = centroids;
     const size_t k = centroids.size() / dim_;
-    std::vector<uint32_t> labels(n_ + 1);
-    const int rc = cilhip_kmeans_nd(device_, data_, n_, dim_, CILHIP_MEM_HOST, cluster_centroids_.data(), k, max_iter, tol, labels.data(), &iteration_count_);
-    if (rc != CILHIP_OK) throw std::runtime_error("cilhip_kmeans_nd failed (rc " + std::to_string(rc) + "): " + cilhip_last_error(nullptr));
-    point_to_cluster_index_map_.assign(labels.begin(), labels.begin() + n_);
-    cluster_to_point_indices_map_.assign(k, std::vector<PointIndexT>());
-    for (size_t i = 0; i < n_; ++i) cluster_to_point_indices_map_[labels[i]].push_back((PointIndexT)i);
+    std::vector<uint32_t> labels(detail::room(n_));
+    detail::check(cilhip_kmeans_nd(device_, data_, n_, dim_, CILHIP_MEM_HOST, cluster_centroids_.data(), k, max_iter, tol, labels.data(), &iteration_count_), "cilhip_kmeans_nd");
+    this->assign_labels(labels, n_, k);
     return *this;
   }
   // the centroids start at the given points (the reference draws them with std::random_device, :32-53)
@@ -589,10 +496,6 @@ public:
 
   const std::vector<float>& getClusterCentroids() const { return cluster_centroids_; }      // dim floats per cluster
   size_t getNumberOfPerformedIterations() const { return iteration_count_; }
-  const ClusterToPointIndicesMap& getClusterToPointIndicesMap() const { return cluster_to_point_indices_map_; }
-  const PointToClusterIndexMap& getPointToClusterIndexMap() const { return point_to_cluster_index_map_; }
-  size_t getNumberOfClusters() const { return cluster_to_point_indices_map_.size(); }
-  size_t getNumberOfPoints() const { return point_to_cluster_index_map_.size(); }
 
 protected:
   const float* data_ = nullptr;
@@ -600,8 +503,6 @@ protected:
   int device_ = 0;
   size_t iteration_count_ = 0;
   std::vector<float> cluster_centroids_;
-  ClusterToPointIndicesMap cluster_to_point_indices_map_;
-  PointToClusterIndexMap point_to_cluster_index_map_;
 };
 
 // spectral_clustering.hpp:316-416, sparse input.  EigenDim > 0: the number of clusters (:377-391); EigenDim = -1 (Eigen::Dynamic): set at
@@ -644,11 +545,10 @@ private:
     cilhip_spectral_params prm;
     cilhip_spectral_default_params(&prm);
     prm.max_num_clusters = max_num_clusters; prm.estimate_num_clusters = estimate ? 1 : 0; prm.laplacian_type = (int)type;
-    const size_t room = max_num_clusters >= 2 && max_num_clusters <= 16 ? max_num_clusters : 2;
-    embedded_points_.assign(n * room + 1, 0.0f);
-    computed_eigenvalues_.assign(room + 1, 0.0f);
-    const int rc = cilhip_spectral_embedding(affinities.handle(), &prm, embedded_points_.data(), computed_eigenvalues_.data(), CILHIP_MEM_HOST, &result_);
-    if (rc != CILHIP_OK) throw std::runtime_error("cilhip_spectral_embedding failed (rc " + std::to_string(rc) + "): " + cilhip_last_error(nullptr));
+    const size_t width = max_num_clusters >= 2 && max_num_clusters <= 16 ? max_num_clusters : 2;
+    embedded_points_.assign(detail::room(n * width), 0.0f);
+    computed_eigenvalues_.assign(width + 1, 0.0f);      // (c_api.h: room for max_num_clusters + 1)
+    detail::check(cilhip_spectral_embedding(affinities.handle(), &prm, embedded_points_.data(), computed_eigenvalues_.data(), CILHIP_MEM_HOST, &result_), "cilhip_spectral_embedding");
     if (result_.n_converged < result_.num_eigenvalues)
       throw std::runtime_error("cilhip_spectral_embedding: " + std::to_string(result_.n_converged) + " of " + std::to_string(result_.num_eigenvalues) + " eigenpairs converged");
     const size_t k = result_.num_clusters;

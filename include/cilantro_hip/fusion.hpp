@@ -15,6 +15,7 @@
 #include <string>
 #include <vector>
 
+#include "abi.hpp"
 #include "c_api.h"
 #include "icp.hpp"
 #include "point_cloud.hpp"
@@ -43,15 +44,14 @@ public:
     const int rc = cilhip_fuse_frame3f(device_, model.points.data(), model.normals.data(), model.colors.data(), confidence.data(), n, capacity, frame.points.data(),
                                        frame.normals.data(), frame.colors.data(), nf, CILHIP_MEM_HOST, cam_pose.data(), intrinsics, image_w, image_h, &params, &n_out, &last_);
     resize(rc == CILHIP_OK ? n_out : n);
-    if (rc != CILHIP_OK) throw std::runtime_error(std::string("cilhip_fuse_frame3f failed (rc ") + std::to_string(rc) + "): " + cilhip_last_error(nullptr));
+    detail::check(rc, "cilhip_fuse_frame3f");
     return *this;
   }
 
   SurfelMap3f& removeUnstable(float conf_thresh) {
     size_t n_out = size();
-    const int rc = cilhip_fusion_remove_unstable3f(device_, model.points.data(), model.normals.data(), model.colors.data(), confidence.data(), size(), CILHIP_MEM_HOST, conf_thresh,
-                                                   &n_out);
-    if (rc != CILHIP_OK) throw std::runtime_error(std::string("cilhip_fusion_remove_unstable3f failed (rc ") + std::to_string(rc) + "): " + cilhip_last_error(nullptr));
+    detail::check(cilhip_fusion_remove_unstable3f(device_, model.points.data(), model.normals.data(), model.colors.data(), confidence.data(), size(), CILHIP_MEM_HOST, conf_thresh, &n_out),
+                  "cilhip_fusion_remove_unstable3f");
     resize(n_out);
     return *this;
   }

@@ -18,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "abi.hpp"
 #include "c_api.h"
 #include "icp.hpp"
 
@@ -35,13 +36,13 @@ protected:
   GridDownsamplerBase(const ConstPointsView& points, const float* normals, const float* colors, float bin_size, bool parallel, int device) {
     const size_t n = points.cols();
     size_t rows = 0;
-    points_.resize(3 * n + 1);
-    if (normals) normals_.resize(3 * n + 1);
-    if (colors) colors_.resize(3 * n + 1);
-    counts_.resize(n + 1);
-    const int rc = cilhip_grid_downsample3f(device, points.data(), normals, colors, n, CILHIP_MEM_HOST, bin_size, 1, parallel ? 1 : 0, points_.data(),
-                                            normals ? normals_.data() : nullptr, colors ? colors_.data() : nullptr, counts_.data(), n, &rows);
-    if (rc != CILHIP_OK) throw std::runtime_error("cilhip_grid_downsample3f failed (rc " + std::to_string(rc) + "): " + cilhip_last_error(nullptr));
+    points_.resize(room(3 * n));
+    if (normals) normals_.resize(room(3 * n));
+    if (colors) colors_.resize(room(3 * n));
+    counts_.resize(room(n));
+    check(cilhip_grid_downsample3f(device, points.data(), normals, colors, n, CILHIP_MEM_HOST, bin_size, 1, parallel ? 1 : 0, points_.data(), normals ? normals_.data() : nullptr,
+                                   colors ? colors_.data() : nullptr, counts_.data(), n, &rows),
+          "cilhip_grid_downsample3f");
     points_.resize(3 * rows);
     if (normals) normals_.resize(3 * rows);
     if (colors) colors_.resize(3 * rows);

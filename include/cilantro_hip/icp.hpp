@@ -39,6 +39,7 @@
 #include <string>
 #include <vector>
 
+#include "abi.hpp"
 #include "c_api.h"
 
 #if defined(__has_include)
@@ -50,17 +51,7 @@
 
 namespace cilantro_hip {
 
-// core/data_containers.hpp:73-122: non-owning view of a 3xN column-major float matrix
-struct ConstPointsView {
-  const float* data_ = nullptr;
-  size_t cols_ = 0;
-  ConstPointsView() = default;
-  ConstPointsView(const float* d, size_t n) : data_(d), cols_(n) {}
-  ConstPointsView(const std::vector<float>& xyz) : data_(xyz.data()), cols_(xyz.size() / 3) {}
-  const float* data() const { return data_; }
-  size_t cols() const { return cols_; }
-  static constexpr size_t rows() { return 3; }
-};
+// (ConstPointsView, the non-owning view of a 3xN column-major float matrix: abi.hpp)
 
 // core/space_transformations.hpp:54-55: Eigen::Transform<float,3,Isometry> storage (4x4 column-major)
 struct RigidTransform3f {
@@ -93,13 +84,7 @@ struct Correspondence {  // core/correspondence.hpp:9-52
 template <typename ScalarT, typename IndexT = size_t>
 using CorrespondenceSet = std::vector<Correspondence<ScalarT, IndexT>>;
 
-// core/nearest_neighbors.hpp:7-47 (what the k-NN mirrors of normal_estimation.hpp return and the warp-field classes below take)
-struct Neighbor {
-  size_t index;
-  float value;
-};
-typedef std::vector<Neighbor> Neighborhood;
-typedef std::vector<Neighborhood> NeighborhoodSet;
+// (Neighbor / Neighborhood / NeighborhoodSet, core/nearest_neighbors.hpp:7-47: abi.hpp)
 
 // core/space_transformations.hpp: TransformSet<RigidTransform3f>, one transform per point or control node
 typedef std::vector<RigidTransform3f> RigidTransformSet3f;
@@ -166,7 +151,7 @@ public:
       const size_t cap = capacity_;  // = points of both clouds (direction BOTH: up to one match per point of either)
       std::vector<uint64_t> i1, i2;
       std::vector<float> v;
-      i1.resize(cap ? cap : 1); i2.resize(cap ? cap : 1); v.resize(cap ? cap : 1);
+      i1.resize(detail::room(cap)); i2.resize(detail::room(cap)); v.resize(detail::room(cap));
       internal::check(ctx_, cilhip_get_correspondences(ctx_, i1.data(), i2.data(), v.data(), cap, &n), "getCorrespondences");
       correspondences_.resize(n);
       for (size_t k = 0; k < n; ++k) correspondences_[k] = {static_cast<size_t>(i1[k]), static_cast<size_t>(i2[k]), v[k]};
@@ -402,7 +387,7 @@ public:
 private:
   void fillParams(cilhip_icp_params& p) const { p.metric = CILHIP_METRIC_POINT_TO_POINT; }
   std::vector<float> computeResiduals() {
-    std::vector<float> res(n_src_ ? n_src_ : 1);
+    std::vector<float> res(detail::room(n_src_));
     internal::check(ctx_.get(), cilhip_compute_residuals(ctx_.get(), CILHIP_METRIC_POINT_TO_POINT, 0.f, 0.f, transform_.m, res.data(), CILHIP_MEM_HOST), "getResiduals");
     res.resize(n_src_);
     return res;
@@ -512,7 +497,7 @@ private:
     p.opt_conv_tol = optimization_convergence_tol_;
   }
   std::vector<float> computeResiduals() {
-    std::vector<float> res(n_src_ ? n_src_ : 1);
+    std::vector<float> res(detail::room(n_src_));
     internal::check(ctx_.get(), cilhip_compute_residuals(ctx_.get(), CILHIP_METRIC_COMBINED, point_to_point_weight_, point_to_plane_weight_, transform_.m, res.data(), CILHIP_MEM_HOST), "getResiduals");
     res.resize(n_src_);
     return res;
@@ -747,16 +732,7 @@ inline void check_stateless(int rc, const char* what) {
   throw std::runtime_error(msg);
 }
 
-// a NeighborhoodSet as the padded rows cilhip_knn3f writes (k = the longest list)
-inline size_t to_lists(const NeighborhoodSet& nh, std::vector<uint32_t>& idx, std::vector<float>& d2) {
-  size_t k = 1;
-  for (const auto& l : nh) k = l.size() > k ? l.size() : k;
-  idx.assign(nh.size() * k ? nh.size() * k : 1, 0xFFFFFFFFu);
-  d2.assign(idx.size(), 0.0f);
-  for (size_t i = 0; i < nh.size(); ++i)
-    for (size_t j = 0; j < nh[i].size(); ++j) { idx[i * k + j] = (uint32_t)nh[i][j].index; d2[i * k + j] = nh[i][j].value; }
-  return k;
-}
+using detail::to_lists;      // (a NeighborhoodSet as the padded rows cilhip_knn3f writes: abi.hpp)
 
 inline WarpFieldPtr make_warp_field(int device, size_t n_src, size_t n_ctrl, const NeighborhoodSet& ctrl, const WarpWeightEvaluator& ce, const NeighborhoodSet& reg,
                                     const WarpWeightEvaluator& re) {
@@ -873,7 +849,7 @@ public:
   ResidualVector getResiduals() {
     const size_t n = src_.size() / 3;
     const std::vector<float> warped = transformPoints(transform_dense_, ConstPointsView(src_.data(), n), device_);
-    std::vector<float> res(n ? n : 1);
+    std::vector<float> res(detail::room(n));
     static const float I16[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     internal::check(ctx_.get(), cilhip_set_source(ctx_.get(), warped.data(), n, CILHIP_MEM_HOST), "set_source");
     const int rc = cilhip_compute_residuals(ctx_.get(), CILHIP_METRIC_COMBINED, prm_.w_p2p, prm_.w_p2pl, I16, res.data(), CILHIP_MEM_HOST);

@@ -21,6 +21,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "abi.hpp"
 #include "c_api.h"
 #include "icp.hpp"
 
@@ -55,20 +56,16 @@ struct TruncatedDepthValueConverter {
 
 namespace detail {
 
-inline void conversions_check(int rc, const char* what) {
-  if (rc != CILHIP_OK) throw std::runtime_error(std::string(what) + " failed (rc " + std::to_string(rc) + "): " + cilhip_last_error(nullptr));
-}
-
 // the one call behind the eight image -> cloud overloads
 inline void image_to_cloud(const void* depth, const unsigned char* rgb, const cilhip_depth_converter& conv, size_t w, size_t h, const float* intrinsics,
                            const RigidTransform3f* extrinsics, std::vector<float>& points, std::vector<float>* normals, std::vector<float>* colors, bool keep_invalid,
                            int device) {
   const size_t n = w * h;
   size_t rows = 0;
-  points.resize(3 * n + 1);
-  if (normals) normals->resize(3 * n + 1);
-  if (colors) colors->resize(3 * n + 1);
-  conversions_check(cilhip_depth_image_to_points3f(device, depth, rgb, w, h, CILHIP_MEM_HOST, &conv, intrinsics, extrinsics ? extrinsics->data() : nullptr, keep_invalid ? 1 : 0,
+  points.resize(room(3 * n));
+  if (normals) normals->resize(room(3 * n));
+  if (colors) colors->resize(room(3 * n));
+  check(cilhip_depth_image_to_points3f(device, depth, rgb, w, h, CILHIP_MEM_HOST, &conv, intrinsics, extrinsics ? extrinsics->data() : nullptr, keep_invalid ? 1 : 0,
                                                    normals ? 1 : 0, points.data(), normals ? normals->data() : nullptr, colors ? colors->data() : nullptr, n, &rows),
                     "cilhip_depth_image_to_points3f");
   points.resize(3 * rows);
@@ -127,14 +124,14 @@ template <class DepthConverterT>
 void pointsToDepthImage(const ConstPointsView& points, const float* intrinsics, const DepthConverterT& depth_converter, typename DepthConverterT::RawDepth* depth_data,
                         size_t image_w, size_t image_h, int device = 0) {
   const cilhip_depth_converter c = depth_converter.abi();
-  detail::conversions_check(cilhip_points_to_depth_image3f(device, points.data(), nullptr, points.cols(), CILHIP_MEM_HOST, nullptr, intrinsics, &c, image_w, image_h, depth_data, nullptr),
+  detail::check(cilhip_points_to_depth_image3f(device, points.data(), nullptr, points.cols(), CILHIP_MEM_HOST, nullptr, intrinsics, &c, image_w, image_h, depth_data, nullptr),
                             "cilhip_points_to_depth_image3f");
 }
 template <class DepthConverterT>
 void pointsToDepthImage(const ConstPointsView& points, const RigidTransform3f& extrinsics, const float* intrinsics, const DepthConverterT& depth_converter,
                         typename DepthConverterT::RawDepth* depth_data, size_t image_w, size_t image_h, int device = 0) {
   const cilhip_depth_converter c = depth_converter.abi();
-  detail::conversions_check(cilhip_points_to_depth_image3f(device, points.data(), nullptr, points.cols(), CILHIP_MEM_HOST, extrinsics.data(), intrinsics, &c, image_w, image_h,
+  detail::check(cilhip_points_to_depth_image3f(device, points.data(), nullptr, points.cols(), CILHIP_MEM_HOST, extrinsics.data(), intrinsics, &c, image_w, image_h,
                                                            depth_data, nullptr),
                             "cilhip_points_to_depth_image3f");
 }
@@ -143,7 +140,7 @@ void pointsColorsToRGBDImages(const ConstPointsView& points, const ConstPointsVi
                               unsigned char* rgb_data, typename DepthConverterT::RawDepth* depth_data, size_t image_w, size_t image_h, int device = 0) {
   if (colors.cols() != points.cols()) throw std::invalid_argument("pointsColorsToRGBDImages: colors and points differ in size");
   const cilhip_depth_converter c = depth_converter.abi();
-  detail::conversions_check(cilhip_points_to_depth_image3f(device, points.data(), colors.data(), points.cols(), CILHIP_MEM_HOST, nullptr, intrinsics, &c, image_w, image_h,
+  detail::check(cilhip_points_to_depth_image3f(device, points.data(), colors.data(), points.cols(), CILHIP_MEM_HOST, nullptr, intrinsics, &c, image_w, image_h,
                                                            depth_data, rgb_data),
                             "cilhip_points_to_depth_image3f");
 }
@@ -153,7 +150,7 @@ void pointsColorsToRGBDImages(const ConstPointsView& points, const ConstPointsVi
                               int device = 0) {
   if (colors.cols() != points.cols()) throw std::invalid_argument("pointsColorsToRGBDImages: colors and points differ in size");
   const cilhip_depth_converter c = depth_converter.abi();
-  detail::conversions_check(cilhip_points_to_depth_image3f(device, points.data(), colors.data(), points.cols(), CILHIP_MEM_HOST, extrinsics.data(), intrinsics, &c, image_w,
+  detail::check(cilhip_points_to_depth_image3f(device, points.data(), colors.data(), points.cols(), CILHIP_MEM_HOST, extrinsics.data(), intrinsics, &c, image_w,
                                                            image_h, depth_data, rgb_data),
                             "cilhip_points_to_depth_image3f");
 }
@@ -161,8 +158,8 @@ void pointsColorsToRGBDImages(const ConstPointsView& points, const ConstPointsVi
 namespace detail {
 template <typename IndexT>
 void index_map(const ConstPointsView& points, const RigidTransform3f* extrinsics, const float* intrinsics, IndexT* index_map_data, size_t image_w, size_t image_h, int device) {
-  std::vector<uint32_t> raw(image_w * image_h + 1);
-  conversions_check(cilhip_points_to_index_map3f(device, points.data(), points.cols(), CILHIP_MEM_HOST, extrinsics ? extrinsics->data() : nullptr, intrinsics, image_w, image_h,
+  std::vector<uint32_t> raw(room(image_w * image_h));
+  check(cilhip_points_to_index_map3f(device, points.data(), points.cols(), CILHIP_MEM_HOST, extrinsics ? extrinsics->data() : nullptr, intrinsics, image_w, image_h,
                                                  raw.data()),
                     "cilhip_points_to_index_map3f");
   for (size_t k = 0; k < image_w * image_h; ++k) index_map_data[k] = raw[k] == 0xFFFFFFFFu ? std::numeric_limits<IndexT>::max() : (IndexT)raw[k];

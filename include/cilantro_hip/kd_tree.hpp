@@ -17,13 +17,14 @@
 #include <string>
 #include <vector>
 
+#include "abi.hpp"
 #include "c_api.h"
 #include "clustering.hpp"
 #include "icp.hpp"
 
 namespace cilantro_hip {
 
-// (ConstDataView, the non-owning view of a dim x n column-major float matrix: clustering.hpp)
+// (ConstDataView, the non-owning view of a dim x n column-major float matrix, and the list helpers KDTree3f shares: abi.hpp)
 
 // core/nearest_neighbors.hpp:49-77
 struct KNNNeighborhoodSpecification {
@@ -53,23 +54,9 @@ public:
   NeighborhoodSet radiusSearch(const ConstDataView& queries, float radius) const {
     check(queries);
     const size_t nq = queries.cols();
-    std::vector<uint64_t> off(nq + 1, 0);
-    size_t total = 0;
-    int rc = cilhip_radius_search_nd(device_, points_.data(), points_.cols(), queries.data(), nq, points_.rows(), CILHIP_MEM_HOST, radius, off.data(), nullptr, nullptr, 0, &total);
-    if (rc != CILHIP_OK) fail("cilhip_radius_search_nd", rc);
-    std::vector<uint32_t> idx(total ? total : 1);
-    std::vector<float> d2(total ? total : 1);
-    if (total) {
-      rc = cilhip_radius_search_nd(device_, points_.data(), points_.cols(), queries.data(), nq, points_.rows(), CILHIP_MEM_HOST, radius, off.data(), idx.data(), d2.data(), total,
-                                   &total);
-      if (rc != CILHIP_OK) fail("cilhip_radius_search_nd", rc);
-    }
-    NeighborhoodSet out(nq);
-    for (size_t i = 0; i < nq; ++i) {
-      out[i].resize((size_t)(off[i + 1] - off[i]));
-      for (size_t j = 0; j < out[i].size(); ++j) out[i][j] = Neighbor{(size_t)idx[off[i] + j], d2[off[i] + j]};
-    }
-    return out;
+    return detail::radius_lists(nq, "cilhip_radius_search_nd", [&](uint64_t* off, uint32_t* idx, float* d2, size_t capacity, size_t* total) {
+      return cilhip_radius_search_nd(device_, points_.data(), points_.cols(), queries.data(), nq, points_.rows(), CILHIP_MEM_HOST, radius, off, idx, d2, capacity, total);
+    });
   }
 
   // kd_tree.hpp:320-388: dispatch on the neighbourhood specification
@@ -82,23 +69,16 @@ public:
   const ConstDataView& getPointsMatrixMap() const { return points_; }
 
 private:
-  static void fail(const char* what, int rc) { throw std::runtime_error(std::string(what) + " failed (rc " + std::to_string(rc) + "): " + cilhip_last_error(nullptr)); }
   void check(const ConstDataView& queries) const {
     if (queries.rows() != points_.rows()) throw std::invalid_argument("KDTree: the queries' dimension is not the tree's");
   }
   NeighborhoodSet knn(const ConstDataView& queries, size_t k, float radius) const {
     check(queries);
     const size_t nq = queries.cols();
-    std::vector<uint32_t> idx(nq * k ? nq * k : 1), cnt(nq ? nq : 1);
-    std::vector<float> d2(nq * k ? nq * k : 1);
-    const int rc = cilhip_knn_nd(device_, points_.data(), points_.cols(), queries.data(), nq, points_.rows(), CILHIP_MEM_HOST, k, radius, idx.data(), d2.data(), cnt.data());
-    if (rc != CILHIP_OK) fail("cilhip_knn_nd", rc);
-    NeighborhoodSet out(nq);
-    for (size_t i = 0; i < nq; ++i) {
-      out[i].resize(cnt[i]);
-      for (size_t j = 0; j < cnt[i]; ++j) out[i][j] = Neighbor{(size_t)idx[i * k + j], d2[i * k + j]};
-    }
-    return out;
+    std::vector<uint32_t> idx(detail::room(nq * k)), cnt(detail::room(nq));
+    std::vector<float> d2(detail::room(nq * k));
+    detail::check(cilhip_knn_nd(device_, points_.data(), points_.cols(), queries.data(), nq, points_.rows(), CILHIP_MEM_HOST, k, radius, idx.data(), d2.data(), cnt.data()), "cilhip_knn_nd");
+    return detail::lists_from_rows(idx, d2, cnt, nq, k);
   }
   ConstDataView points_;
   int device_;

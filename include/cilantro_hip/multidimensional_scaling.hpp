@@ -11,6 +11,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "abi.hpp"
 #include "c_api.h"
 
 namespace cilantro_hip {
@@ -65,8 +66,7 @@ class MultidimensionalScaling {
     const size_t room = (max_dim == 0 || max_dim >= n) ? 2 : max_dim;
     embedded_points_.assign(n * room, 0.0f);
     computed_eigenvalues_.assign(room + 1, 0.0f);
-    const int rc = cilhip_mds_embedding(device, distances, n, CILHIP_MEM_HOST, &prm, embedded_points_.data(), computed_eigenvalues_.data(), &result_);
-    if (rc != CILHIP_OK) throw std::runtime_error("cilhip_mds_embedding failed (rc " + std::to_string(rc) + "): " + cilhip_last_error(nullptr));
+    detail::check(cilhip_mds_embedding(device, distances, n, CILHIP_MEM_HOST, &prm, embedded_points_.data(), computed_eigenvalues_.data(), &result_), "cilhip_mds_embedding");
     if (result_.n_converged < result_.num_eigenvalues)
       throw std::runtime_error("cilhip_mds_embedding: " + std::to_string(result_.n_converged) + " of " + std::to_string(result_.num_eigenvalues) + " eigenpairs converged");
     embedded_points_.resize(n * result_.dim);

@@ -11,6 +11,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "abi.hpp"
 #include "c_api.h"
 
 namespace cilantro_hip {
@@ -44,15 +45,13 @@ class PrincipalComponentAnalysis {
   // :46-49 -> m x target_dim, point-major
   std::vector<float> project(const float* points, size_t m, size_t target_dim) const {
     std::vector<float> out(m * target_dim);
-    const int rc = cilhip_pca_project(device_, points, m, dim_, CILHIP_MEM_HOST, mean_.data(), eigenvectors_.data(), target_dim, out.data());
-    if (rc != CILHIP_OK) throw std::runtime_error("cilhip_pca_project failed (rc " + std::to_string(rc) + "): " + cilhip_last_error(nullptr));
+    detail::check(cilhip_pca_project(device_, points, m, dim_, CILHIP_MEM_HOST, mean_.data(), eigenvectors_.data(), target_dim, out.data()), "cilhip_pca_project");
     return out;
   }
   // :59-62: m x source_dim -> m x dim
   std::vector<float> reconstruct(const float* points, size_t m, size_t source_dim) const {
     std::vector<float> out(m * dim_);
-    const int rc = cilhip_pca_reconstruct(device_, points, m, source_dim, dim_, CILHIP_MEM_HOST, mean_.data(), eigenvectors_.data(), out.data());
-    if (rc != CILHIP_OK) throw std::runtime_error("cilhip_pca_reconstruct failed (rc " + std::to_string(rc) + "): " + cilhip_last_error(nullptr));
+    detail::check(cilhip_pca_reconstruct(device_, points, m, source_dim, dim_, CILHIP_MEM_HOST, mean_.data(), eigenvectors_.data(), out.data()), "cilhip_pca_reconstruct");
     return out;
   }
 
@@ -68,8 +67,8 @@ class PrincipalComponentAnalysis {
     if (dim_ == 0 || dim_ > 16) throw std::invalid_argument("PrincipalComponentAnalysis: dim must lie in [1, 16]");
     mean_.assign(dim_, 0.0f); covariance_.assign(dim_ * dim_, 0.0f); eigenvalues_.assign(dim_, 0.0f); eigenvectors_.assign(dim_ * dim_, 0.0f);
     int valid = 0;
-    const int rc = cilhip_pca_fit(device_, points, n, dim_, subset, n_subset, CILHIP_MEM_HOST, mean_.data(), covariance_.data(), eigenvalues_.data(), eigenvectors_.data(), &valid);
-    if (rc != CILHIP_OK) throw std::runtime_error("cilhip_pca_fit failed (rc " + std::to_string(rc) + "): " + cilhip_last_error(nullptr));
+    detail::check(cilhip_pca_fit(device_, points, n, dim_, subset, n_subset, CILHIP_MEM_HOST, mean_.data(), covariance_.data(), eigenvalues_.data(), eigenvectors_.data(), &valid),
+                  "cilhip_pca_fit");
     valid_ = valid != 0;
   }
 };

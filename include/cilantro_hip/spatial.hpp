@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "abi.hpp"
 #include "c_api.h"
 #include "principal_component_analysis.hpp"
 
@@ -23,9 +24,6 @@ namespace cilantro_hip {
 
 namespace spatial_detail {
 inline const char* not_built() { return "not built: it needs the QP of convex_hull_utilities.hpp:12-193 and a dual hull"; }
-inline void check(int rc, const char* what) {
-  if (rc != CILHIP_OK) throw std::runtime_error(std::string(what) + " failed (rc " + std::to_string(rc) + "): " + cilhip_last_error(nullptr));
-}
 }  // namespace spatial_detail
 
 template <typename ScalarT = float, std::ptrdiff_t EigenDim = 3, typename IndexT = size_t>
@@ -89,20 +87,20 @@ class ConvexPolytope {
   // :117-121 -> F x n, row-major
   std::vector<float> getPointSignedDistancesFromFacets(const float* points, size_t n) const {
     std::vector<float> out(numFacets() * n);
-    spatial_detail::check(cilhip_polytope_signed_distances(device_, halfspaces_.data(), numFacets(), points, n, Dim, CILHIP_MEM_HOST, out.data()), "cilhip_polytope_signed_distances");
+    detail::check(cilhip_polytope_signed_distances(device_, halfspaces_.data(), numFacets(), points, n, Dim, CILHIP_MEM_HOST, out.data()), "cilhip_polytope_signed_distances");
     return out;
   }
   std::vector<bool> getInteriorPointsIndexMask(const float* points, size_t n, float offset = 0.0f) const {
     const uint32_t offs[2] = {0u, (uint32_t)numFacets()};
     std::vector<uint8_t> m(n);
-    spatial_detail::check(cilhip_polytopes_interior_mask(device_, halfspaces_.data(), offs, 1, points, n, Dim, CILHIP_MEM_HOST, offset, m.data()), "cilhip_polytopes_interior_mask");
+    detail::check(cilhip_polytopes_interior_mask(device_, halfspaces_.data(), offs, 1, points, n, Dim, CILHIP_MEM_HOST, offset, m.data()), "cilhip_polytopes_interior_mask");
     return std::vector<bool>(m.begin(), m.end());
   }
   template <typename IdxT = IndexT> std::vector<IdxT> getInteriorPointIndices(const float* points, size_t n, float offset = 0.0f) const {
     const uint32_t offs[2] = {0u, (uint32_t)numFacets()};
-    std::vector<uint32_t> idx(n ? n : 1);
+    std::vector<uint32_t> idx(detail::room(n));
     size_t count = 0;
-    spatial_detail::check(cilhip_polytopes_interior_indices(device_, halfspaces_.data(), offs, 1, points, n, Dim, CILHIP_MEM_HOST, offset, idx.data(), idx.size(), &count),
+    detail::check(cilhip_polytopes_interior_indices(device_, halfspaces_.data(), offs, 1, points, n, Dim, CILHIP_MEM_HOST, offset, idx.data(), idx.size(), &count),
                           "cilhip_polytopes_interior_indices");
     return std::vector<IdxT>(idx.begin(), idx.begin() + count);
   }
@@ -154,14 +152,14 @@ class ConvexPolytope {
   void build(const float* points, size_t n, bool compute_topology, bool simplicial_facets, double merge_tol) {
     const float none = 0.0f;
     cilhip_hull* h = nullptr;
-    spatial_detail::check(cilhip_convex_hull_create(device_, n ? points : &none, n, Dim, CILHIP_MEM_HOST, simplicial_facets ? 1 : 0, merge_tol, &h, &info_), "cilhip_convex_hull_create");
+    detail::check(cilhip_convex_hull_create(device_, n ? points : &none, n, Dim, CILHIP_MEM_HOST, simplicial_facets ? 1 : 0, merge_tol, &h, &info_), "cilhip_convex_hull_create");
     const size_t V = info_.n_vertices, F = info_.n_facets;
     std::vector<uint32_t> vpi(V), fo(F + 1), fi(info_.n_facet_indices), fn(info_.n_facet_indices), vo(V + 1), vf(info_.n_vertex_facets);
     vertices_.assign(V * Dim, 0.0f);
     halfspaces_.assign(info_.n_halfspaces * (Dim + 1), 0.0f);
     const int rc = cilhip_convex_hull_get(h, vpi.data(), vertices_.data(), halfspaces_.data(), fo.data(), fi.data(), fn.data(), vo.data(), vf.data(), nullptr);
     cilhip_convex_hull_destroy(h);
-    spatial_detail::check(rc, "cilhip_convex_hull_get");
+    detail::check(rc, "cilhip_convex_hull_get");
     is_empty_ = info_.is_empty != 0;
     area_ = info_.area; volume_ = info_.volume;
     interior_point_.assign(info_.interior_point, info_.interior_point + Dim);
@@ -253,16 +251,16 @@ class SpaceRegion {
     std::vector<uint32_t> offs;
     pack(hs, offs);
     std::vector<uint8_t> m(n);
-    spatial_detail::check(cilhip_polytopes_interior_mask(device_, hs.data(), offs.data(), polytopes_.size(), points, n, Dim, CILHIP_MEM_HOST, offset, m.data()), "cilhip_polytopes_interior_mask");
+    detail::check(cilhip_polytopes_interior_mask(device_, hs.data(), offs.data(), polytopes_.size(), points, n, Dim, CILHIP_MEM_HOST, offset, m.data()), "cilhip_polytopes_interior_mask");
     return std::vector<bool>(m.begin(), m.end());
   }
   template <typename IdxT = IndexT> std::vector<IdxT> getInteriorPointIndices(const float* points, size_t n, float offset = 0.0f) const {
     std::vector<float> hs;
     std::vector<uint32_t> offs;
     pack(hs, offs);
-    std::vector<uint32_t> idx(n ? n : 1);
+    std::vector<uint32_t> idx(detail::room(n));
     size_t count = 0;
-    spatial_detail::check(cilhip_polytopes_interior_indices(device_, hs.data(), offs.data(), polytopes_.size(), points, n, Dim, CILHIP_MEM_HOST, offset, idx.data(), idx.size(), &count),
+    detail::check(cilhip_polytopes_interior_indices(device_, hs.data(), offs.data(), polytopes_.size(), points, n, Dim, CILHIP_MEM_HOST, offset, idx.data(), idx.size(), &count),
                           "cilhip_polytopes_interior_indices");
     return std::vector<IdxT>(idx.begin(), idx.begin() + count);
   }
