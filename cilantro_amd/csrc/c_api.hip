@@ -207,6 +207,12 @@ int cilhip_get_last_warm_iterations(cilhip_ctx* c, int* warm_iterations) {
   return CILHIP_OK;
 }
 
+int cilhip_get_last_reverse_fused_iterations(cilhip_ctx* c, int* fused_iterations) {
+  if (!c || !fused_iterations) return CILHIP_ERR_INVALID;
+  *fused_iterations = c->last_rev_fused_iters;
+  return CILHIP_OK;
+}
+
 int cilhip_get_last_run_forms(cilhip_ctx* c, int* one_pass_iterations, int* two_pass_iterations) {
   if (!c) return CILHIP_ERR_INVALID;
   if (one_pass_iterations) *one_pass_iterations = c->last_fused_iters;

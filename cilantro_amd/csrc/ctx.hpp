@@ -101,6 +101,7 @@ struct cilhip_ctx : CtxStream, TargetBufs, SourceBufs, CtxOptions {      // (Ctx
   Feedback* d_feedback = nullptr;              // the device's address of it
   unsigned int run_tag = 0;
   int last_fused_iters = 0, last_two_pass_iters = 0, last_warm_iters = 0;
+  int last_rev_fused_iters = 0;      // run_reverse_loop: iterations whose warm-started reverse search accumulated the sums itself (k_reverse_warm<ACC>)
   int run_calls = 0;              // cilhip_icp_partial_sums calls since cilhip_icp_begin
   std::vector<unsigned char> iter_form;   // form of every timed search / one-pass launch of the last run (FORM_*), in launch order
   std::vector<unsigned char> trace_form;  // form of every iteration enqueued by the last run, timed or not (cilhip_get_last_run_trace)

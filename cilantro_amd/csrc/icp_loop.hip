@@ -232,7 +232,7 @@ static int run_reverse_loop(cilhip_ctx* c, RunSetup& r) {
   a.nn_d2 = nullptr;
   c->rec_valid = false; c->lb_fresh = false;
   c->policy.begin_run(c->warm_enter * c->grid.cell);
-  c->last_fused_iters = c->last_two_pass_iters = c->last_warm_iters = 0;
+  c->last_fused_iters = c->last_two_pass_iters = c->last_warm_iters = c->last_rev_fused_iters = 0;
   for (size_t it = 0; it < p->max_iter; ++it) {
     bool fwd_warm = false;
     const bool rev_fused = rev_fusable && it >= 1;      // (this iteration's reverse search starts from the previous matches and accumulates)
@@ -259,6 +259,7 @@ static int run_reverse_loop(cilhip_ctx* c, RunSetup& r) {
         RevFused rfu{};
         rfu.metric = im; rfu.mode = rmode; rfu.fwd_pos = c->d_nn_pos; rfu.src_inv = c->d_src_inv; rfu.grid_to_sorted = c->d_grid_to_sorted; rfu.partials = c->d_partials;
         for (int k = 0; k < 3; ++k) rfu.dst_mean[k] = a.dst_mean[k];
+        if (rev_fused) ++c->last_rev_fused_iters;
         { const TieDev rt = tie_dev_rev(c); launch_reverse_search_rigid(c->grid, c->src_grid, c->d_state, p->max_sq_dist, c->d_rev_pos, c->d_rev_d2, c->stream, feat6(c) ? &rf : nullptr, &rt, warm_tab, rev_fused ? &rfu : nullptr); }
       }
       const bool fwd_in_kernel = fwd_warm && st == 0;      // (the warm-started kernel accumulated the first step's terms itself)
@@ -330,7 +331,7 @@ static int run_projective_loop(cilhip_ctx* c, RunSetup& r) {
   int rc = ensure_proj_map(c);
   if (rc) return rc;
   c->rec_valid = false; c->lb_fresh = false;
-  c->last_fused_iters = c->last_two_pass_iters = c->last_warm_iters = 0;
+  c->last_fused_iters = c->last_two_pass_iters = c->last_warm_iters = c->last_rev_fused_iters = 0;
   c->iter_form.clear(); c->trace_form.clear(); c->timed_iter.clear();
   for (int k = 0; k < 5; ++k) { c->form_ms[k] = 0.0; c->form_n[k] = 0; }
   for (size_t it = 0; it < p->max_iter; ++it) {
@@ -592,7 +593,7 @@ static int run_forward_loop(cilhip_ctx* c, RunSetup& r) {
   }
   f.paced = ((f.tile_acc || f.wcap) && c->ns && p->max_iter > 2 && c->tile_acc_adaptive) || (f.fwcap && p->max_iter > 2);
   if (f.tile_acc && !c->tile_acc_adaptive) c->policy.far_mode = false;
-  c->last_fused_iters = c->last_two_pass_iters = c->last_warm_iters = 0;
+  c->last_fused_iters = c->last_two_pass_iters = c->last_warm_iters = c->last_rev_fused_iters = 0;
   c->rec_valid = false; c->lb_fresh = false;
   c->policy.begin_run(c->warm_enter * c->grid.cell);
   c->iter_form.clear(); c->trace_form.clear(); c->timed_iter.clear();
@@ -735,7 +736,7 @@ int cilhip_icp_begin(cilhip_ctx* c, const cilhip_icp_params* p, const float* T0,
   if (warm_capable(c) && !(c->d_src_nrm && c->symmetric)) { rc = ensure_safe2(c); if (rc) return rc; rc = ensure_warm_buffers(c); if (rc) return rc; }
   c->iter_form.clear(); c->trace_form.clear();
   for (int k = 0; k < 5; ++k) { c->form_ms[k] = 0.0; c->form_n[k] = 0; }
-  c->last_fused_iters = c->last_two_pass_iters = c->last_warm_iters = 0;    // counted per cilhip_icp_partial_sums call (cilhip_get_last_run_forms)
+  c->last_fused_iters = c->last_two_pass_iters = c->last_warm_iters = c->last_rev_fused_iters = 0;    // counted per cilhip_icp_partial_sums call (cilhip_get_last_run_forms)
   return CILHIP_OK;
 }
 

@@ -403,6 +403,13 @@ class Context:
         self._ck(self._L.cilhip_get_last_warm_iterations(self._h, C.byref(a)))
         return a.value
 
+    def last_reverse_fused_iterations(self):
+        """how many iterations of the last icp_run (device-resident FIRST_TO_SECOND / BOTH loops) took their sums from the warm-started
+        reverse search itself instead of from a separate pass over the reverse matches"""
+        a = C.c_int(0)
+        self._ck(self._L.cilhip_get_last_reverse_fused_iterations(self._h, C.byref(a)))
+        return a.value
+
     def last_matches_origin(self):
         """where get_nn / get_correspondences read from: 0 none, 3 find_correspondences, 1 kept by the last icp_run's kernels,
         2 searched again on demand under the last iteration's transform"""

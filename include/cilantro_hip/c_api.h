@@ -1041,6 +1041,10 @@ int cilhip_get_last_run_forms(cilhip_ctx* ctx, int* one_pass_iterations, int* tw
  * iteration on, near alignment, the search starts from the previous iteration's match -- a real target point, so its
  * distance from the new query bounds the search -- and usually ends inside the query's own cell; same matches. */
 int cilhip_get_last_warm_iterations(cilhip_ctx* ctx, int* warm_iterations);
+/* The device-resident FIRST_TO_SECOND / BOTH loops (no post-filter, no correspondence weight evaluators): how many iterations of the
+ * last cilhip_icp_run took their sums from the warm-started reverse search itself (option "reverse_warm_start": every iteration but the
+ * first) instead of from a separate pass over the reverse matches.  0 after any other loop.  Counted on the host. */
+int cilhip_get_last_reverse_fused_iterations(cilhip_ctx* ctx, int* fused_iterations);
 /* The last cilhip_icp_run iteration by iteration (at most the first 256, at most `cap`; written by the device's epilogue, read
  * back here): queries the search's first stage left unproven, queries a warm-started iteration had to search, the bound on
  * how far any source point moved in the iteration's update (what the warm-started form's margins are spent on), the update

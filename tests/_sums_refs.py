@@ -537,3 +537,295 @@ def pair_weights(fix, has, seed=3):
     for k, (a, b) in zip(idx[:3], ((0.0, 0.0), (0.0, 2.0), (2.0, 0.0))):
         wq[k], wp[k] = a, b
     return wq, wp
+
+
+# ---- two exact iterations: a fixture whose FIRST STEP is exact (section D of tests/test_gpu_exact_sums.py) -------------------------------
+#
+# The second iteration of a run sees lattice data again if the first one steps onto an exactly representable transform.  Target: the
+# integer lattice as above (origin (6, side + 10, 2 side + 14): under the quarter turn with its shift no stored source coordinate
+# comes near zero), normals from NORMALS, plus TWIN target points beside some occupied sites.  Source, by group (offsets in 1/16):
+#   A  site + U            matched in both iterations; every centred residual of iteration 0 is the same vector, so x* = (0, 0, 0, t)
+#                          solves every pair's equation in all four metrics, Kabsch's sigma = cov(p, p) has the identity as its polar
+#                          factor, and the step is the translation by -U / 16: T1 = T0 with that translation, to round-off in the
+#                          linear part (ABSORB says how much of it the pinned transform expression swallows)
+#   B  site + U + delta    |U + delta|^2 >= 11: unmatched at iteration 0; |delta|^2 <= 10: matched at iteration 1 with residual
+#                          -delta / 16, so Atb != 0 and T2 depends on every slot
+#   F  site + F            never matched (|F|^2 >= 11 and |F - U|^2 >= 11); sites without a source point besides (nd > n)
+#   twin targets           site + W beside some A sites, |W - U|^2 >= 11 and 0 < |W|^2 <= 10: unmatched at iteration 0; at iteration 1
+#                          their nearest source point is the A point ON the site, whose own nearest target is the site: a reverse
+#                          match that is no reciprocal duplicate (mode 2 counts it, mode 3 does not)
+# squared radius between 10/256 and 11/256.  Expected sets: iteration 0, every direction: the A pairs; iteration 1: FIRST_TO_SECOND
+# A + B + twins; BOTH the forward A + B plus the reverse non-duplicates = the twins; BOTH reciprocal A + B.
+
+TWO_STEP_U = np.array((1, 1, 1), np.int64)
+TWO_STEP_DELTAS = np.array(((2, 1, 1), (2, 2, 1), (2, 2, 0), (2, 0, 2)), np.int64)
+TWO_STEP_F = np.array((-3, -3, -3), np.int64)
+TWO_STEP_W = np.array((-2, -1, -1), np.int64)
+TWO_STEP_LARGE = 16 * 2048 * 256 + 257        # reverse_warm_blocks() capped at 2048 blocks, 17 rounds in the first of them
+TWO_STEP_SIZES = (255, 256, 257, 2048, 2049, 4097 + 255, TWO_STEP_LARGE)      # target points, twins included
+TWO_STEP_DIRECTIONS = ("first_to_second", "both", "both_reciprocal")
+GROUP_A, GROUP_B, GROUP_F = 0, 1, 2
+# a perturbation of every entry of T1's linear part that transform_points must still round away: the smallest stored coordinate is above
+# 2 (half an ulp: 2^-23), the sum of a point's coordinates below 2^11, so anything below 2^-34 disappears; the solves leave ~1e-15
+ABSORB = 2.0 ** -36
+
+_two_step_targets = {}
+_two_step_cache = {}
+
+
+def _two_step_target(nd, seed):
+    """the target of size nd (shared by every T0): sites, twins beside the first n_tw A sites, the source's groups and sites"""
+    key = (nd, seed)
+    if key in _two_step_targets:
+        return _two_step_targets[key]
+    rng = np.random.default_rng(5000 + seed)
+    n_tw = min(max(8, nd // 32), 256)
+    n_sites = nd - n_tw
+    side = cube_side(n_sites)
+    origin = np.array([6, side + 10, 2 * side + 14], np.int64)
+    n = min(int(0.55 * n_sites), 4096)
+    n_a = int(0.6 * n)
+    n_b = int(0.3 * n)
+    assert n_a >= 16 and n_a >= n_tw and n_b >= len(TWO_STEP_DELTAS) and n - n_a - n_b >= 1
+    # the source sits in the low corner of the lattice (all of it below 2^16 sites): small coordinates whatever the target's size
+    sub = side if n_sites <= 65536 else 24
+    g = np.arange(min(n_sites, (sub - 1) * (side * side + side + 1) + 1), dtype=np.int64)
+    ijk = np.stack([g // (side * side), (g // side) % side, g % side], 1)
+    cand = g[np.all(ijk < sub, 1)]
+    site_g = rng.choice(cand, n, replace=False)                          # lattice index of the site source point k sits on
+    group = np.full(n, GROUP_F, np.int64)
+    group[:n_a] = GROUP_A
+    group[n_a:n_a + n_b] = GROUP_B
+    group = group[rng.permutation(n)]
+    a_idx = np.nonzero(group == GROUP_A)[0]
+    tw_s = a_idx[rng.permutation(len(a_idx))[:n_tw]]                     # the A point on every twin's site
+    gs = np.arange(n_sites, dtype=np.int64)
+    sites = np.stack([gs // (side * side), (gs // side) % side, gs % side], 1) + origin
+    D64 = np.empty((nd, 3), np.float64)
+    perm_t = rng.permutation(nd)                                         # target index of (site j | twin j - n_sites)
+    D64[perm_t[:n_sites]] = sites
+    D64[perm_t[n_sites:]] = sites[site_g[tw_s]] + TWO_STEP_W * QUANTUM
+    N = NORMALS[rng.integers(0, len(NORMALS), nd)]
+    off = np.empty((n, 3), np.int64)
+    off[group == GROUP_A] = TWO_STEP_U
+    nb = int((group == GROUP_B).sum())
+    off[group == GROUP_B] = TWO_STEP_U + TWO_STEP_DELTAS[np.arange(nb) % len(TWO_STEP_DELTAS)]
+    off[group == GROUP_F] = TWO_STEP_F
+    c = sites[site_g].mean(0).astype(np.int64)
+    tgt = {"nd": nd, "n": n, "n_sites": n_sites, "side": side, "D": _exact32(D64), "N": np.ascontiguousarray(N), "group": group, "off": off,
+           "site_t": perm_t[site_g], "tw_t": perm_t[n_sites:], "tw_s": tw_s,
+           "dst_mean": _exact32(c + np.array([0.25, -0.25, 0.5])), "smt0": _exact32(c + np.array([-0.25, 0.5, 0.25])),
+           "r2": radius_between(np.array([10.0, 11.0]) / 256.0, 1)}
+    _two_step_targets[key] = tgt
+    return tgt
+
+
+def two_step_pair(nd, T="identity", seed=0):
+    """-> dict: D, N, S, T (= T0), T1 (T0 moved by -U/16: where iteration 0 must step to), dst_mean, src_mean, smt0 / smt1 (T0 / T1 src_mean),
+    q0 / q1 (the source under T0 / T1: q1 = q0 - U/16, on its site for A), r2, group, site_t (target index of every source point's site),
+    tw_t / tw_s (twin targets and the A point on their site), pairs0 and pairs1[direction]: (target indices, source indices)"""
+    key = (nd, T, seed)
+    if key in _two_step_cache:
+        return _two_step_cache[key]
+    tgt = _two_step_target(nd, seed)
+    Tm, Linv = fr.TRANSFORMS[T]
+    fix = dict(tgt)
+    q0 = tgt["D"].astype(np.float64)[tgt["site_t"]] + tgt["off"] * QUANTUM
+    step = TWO_STEP_U * QUANTUM
+    T1 = Tm.copy()
+    T1[:3, 3] = _exact32(Tm[:3, 3].astype(np.float64) - step)
+    fix.update({"name": f"two_step_{nd}_{T}", "tname": T, "T": Tm.copy(), "T1": T1, "q0": _exact32(q0), "q1": _exact32(q0 - step), "S": _stored(q0, T),
+                "smt1": _exact32(tgt["smt0"].astype(np.float64) - step), "src_mean": _exact32((tgt["smt0"].astype(np.float64) - Tm[:3, 3].astype(np.float64)) @ Linv.T)})
+    a = np.nonzero(tgt["group"] == GROUP_A)[0]
+    ab = np.nonzero(tgt["group"] != GROUP_F)[0]
+    fix["pairs0"] = (tgt["site_t"][a], a)
+    with_twins = (np.concatenate([tgt["site_t"][ab], tgt["tw_t"]]), np.concatenate([ab, tgt["tw_s"]]))
+    fix["pairs1"] = {"first_to_second": with_twins, "both": with_twins, "both_reciprocal": (tgt["site_t"][ab], ab)}
+    _two_step_cache[key] = fix
+    return fix
+
+
+def expected_sums_pairs(fix, metric, T, pairs):
+    """the exact sums over an explicit list of (target index, source index) pairs under T: a source point may occur in several pairs"""
+    ti, si = pairs
+    return expected_sums(metric, fix["D"], fix["N"], fix["S"][si], T, fix["dst_mean"], fix["src_mean"], ti, np.ones(len(ti), bool))
+
+
+def _site_keys(x64):
+    r = np.rint(x64).astype(np.int64)
+    return (r[:, 0] * 4096 + r[:, 1]) * 4096 + r[:, 2]
+
+
+def nearest_by_site(X, Y):
+    """for every point of X its nearest point of Y, in f64 -> (index or -1, d2, d2 of the second nearest or inf).  Only points of Y whose
+    rounded site lies in the 3 x 3 x 3 block around the rounded site of x are looked at: every point here is within 1/4 of its site, so
+    any other point is more than 1 away and x is reported as having no neighbour (-1, inf) when the block is empty -- enough wherever the
+    question is `inside a radius below 1/2`.  tests/test_sums_refs_cpu.py holds it against the full distance matrix at the small sizes."""
+    X = np.asarray(X, np.float64); Y = np.asarray(Y, np.float64)
+    ky = _site_keys(Y)
+    oy = np.argsort(ky, kind="stable")
+    kys = ky[oy]
+    lo, hi = np.rint(Y.min(0)) - 1, np.rint(Y.max(0)) + 1
+    near = np.nonzero(np.all((X >= lo - 0.5) & (X <= hi + 0.5), 1))[0]      # (the others' blocks hold no site of Y)
+    idx = np.full(len(X), -1, np.int64); d1 = np.full(len(X), np.inf); d2 = np.full(len(X), np.inf)
+    kx = _site_keys(X[near])
+    bi = np.full(len(near), -1, np.int64); b1 = np.full(len(near), np.inf); b2 = np.full(len(near), np.inf)
+    for dx in (-1, 0, 1):
+        for dy in (-1, 0, 1):
+            for dz in (-1, 0, 1):
+                k = kx + (dx * 4096 + dy) * 4096 + dz
+                beg = np.searchsorted(kys, k, "left"); end = np.searchsorted(kys, k, "right")
+                for j in range(int((end - beg).max(initial=0))):
+                    m = np.nonzero(beg + j < end)[0]
+                    c = oy[beg[m] + j]
+                    e = ((X[near[m]] - Y[c]) ** 2).sum(1)
+                    better = e < b1[m]
+                    b2[m] = np.where(better, b1[m], np.minimum(b2[m], e))
+                    bi[m] = np.where(better, c, bi[m])
+                    b1[m] = np.where(better, e, b1[m])
+    idx[near] = bi; d1[near] = b1; d2[near] = b2
+    return idx, d1, d2
+
+
+def directed_sets(fix, q, r2):
+    """-> (forward: (target, source) for every source point with a target inside the radius; reverse: the same for every target point),
+    asserting that no nearest neighbour is tied and no distance is at the radius"""
+    D64 = fix["D"].astype(np.float64); q64 = np.asarray(q, np.float64)
+    out = []
+    for X, Y in ((q64, D64), (D64, q64)):
+        idx, d1, d2 = nearest_by_site(X, Y)
+        has = d1 < float(r2)
+        assert not np.any(d1 == float(r2)) and np.all(d2[has] - d1[has] >= 1.0 / 256.0), fix["name"]
+        out.append((idx, has))
+    (fi, fh), (ri, rh) = out
+    s = np.nonzero(fh)[0]; t = np.nonzero(rh)[0]
+    return (fi[s], s), (t, ri[t])
+
+
+def _pair_set(pairs):
+    return set(zip(np.asarray(pairs[0]).tolist(), np.asarray(pairs[1]).tolist()))
+
+
+def loop_sets(fix, q, r2):
+    """the correspondence set of each direction from the two searches: FIRST_TO_SECOND the reverse matches; BOTH their union with the
+    forward ones; BOTH reciprocal the intersection -- as sets of (target, source)"""
+    fwd, rev = directed_sets(fix, q, r2)
+    f, r = _pair_set(fwd), _pair_set(rev)
+    return {"first_to_second": r, "both": f | r, "both_reciprocal": f & r, "forward": f}
+
+
+# ---- the grid the library lays over a cloud, restated (grid_policy.hpp: grid_first_cell, grid_set_dims; grid_build.hip: cell_of, a stable
+# sort by cell key) -- where a target point sits in the order the reverse kernels walk; the GPU test holds the shape against get_grid_info
+
+def grid_order(P, order=True):
+    """-> dict: nx, ny, nz, cell, origin and, with `order`, occupancy and order (sorted position -> index into P)"""
+    P = np.asarray(P, np.float32)
+    lo, hi = P.min(0), P.max(0)
+    ext = hi.astype(np.float64) - lo.astype(np.float64)
+    maxext = float(ext.max())
+    cell = float(np.cbrt(np.prod(np.maximum(ext, maxext * 1e-3)) / len(P)))
+    cell = max(cell, maxext / 2047.0)
+    f = np.float32
+    while True:
+        cf = f(cell); inv = f(1.0) / cf
+        o = lo - f(2.0) * cf
+        coord = lambda v, o_: np.floor(np.minimum(np.maximum((v - o_) * inv, f(-1.0)), f(1.0e9))).astype(np.int64)
+        for c in range(3):
+            if coord(lo[c], o[c]) < 2:
+                o[c] = lo[c] - f(2.25) * cf
+        dims = [max(int(np.floor(ext[c] / cell)) + 5, int(coord(hi[c], o[c])) + 3) for c in range(3)]
+        if dims[0] * dims[1] * dims[2] <= 2 ** 26 and max(dims) <= 2048:
+            break
+        cell *= 1.1
+    shape = {"nx": dims[0], "ny": dims[1], "nz": dims[2], "cell": float(cf), "origin": [float(v) for v in o]}
+    if not order:
+        return shape
+    cc = [np.clip(coord(P[:, c], o[c]), 0, dims[c] - 1) for c in range(3)]
+    key = (cc[2] * dims[1] + cc[1]) * dims[0] + cc[0]
+    cnt = np.bincount(key).astype(np.float64)
+    shape.update({"occupancy": float((cnt * cnt).sum() / len(P)), "order": np.argsort(key, kind="stable")})
+    return shape
+
+
+def reverse_walk_places(fix):
+    """where the A sites' and the twin target points sit in the reverse kernels' walk over the sorted target (rounds of 256, waves of 64):
+    -> dict of counts: in the last round, in lane 0 / lane 63 of a wave, for `a` and `twin`"""
+    g = grid_order(fix["D"])
+    assert g["occupancy"] <= 3.0      # (build_grid() keeps its first grid)
+    pos = np.empty(fix["nd"], np.int64)
+    pos[g["order"]] = np.arange(fix["nd"])
+    last_round = (fix["nd"] - 1) // 256
+    out = {}
+    for name, t in (("a", fix["site_t"][fix["group"] == GROUP_A]), ("twin", fix["tw_t"])):
+        p = pos[t]
+        out[name] = {"last_round": int((p // 256 == last_round).sum()), "lane0": int((p % 64 == 0).sum()), "lane63": int((p % 64 == 63).sum()),
+                     "last": int((p == fix["nd"] - 1).sum())}
+    return g, out
+
+
+# ---- the epilogue's solve, restated in f64 (epilogue.hip solve_body, solve.hpp rigid_gn_update / kabsch_from_sums / compose_update) --------
+
+METRIC_WEIGHTS = {PLANE: (0.0, 1.0), POINT: (1.0, 0.0), BOTH: (0.5, 0.25)}      # (w_p2p, w_p2pl) of the GPU test's PARAMS
+
+
+def _polar(L):
+    U, _s, Vt = np.linalg.svd(L)
+    R = U @ Vt
+    assert np.linalg.det(R) > 0.0
+    return R
+
+
+def solve_step(metric, sums, T_cur, smt, dst_mean):
+    """one outer iteration's update from the 48 sums -> (T_new as the f32 4x4 the state would hold, the step's rotation and translation in
+    f64): the Gauss-Newton metrics through gn_normal_equations and a dense solve, Kabsch through an SVD, composed as compose_update does"""
+    s = np.asarray(sums, np.float64)
+    if metric == KABSCH:
+        n = s[0]
+        mud, mus = s[1:4] / n, s[4:7] / n
+        sig = s[7:16].reshape(3, 3) / n - np.outer(mud, mus)
+        U, _s, Vt = np.linalg.svd(sig)
+        L = U @ Vt
+        assert np.linalg.det(L) > 0.0
+        t = mud - L @ mus
+    else:
+        AtA, Atb = gn_normal_equations(s, *METRIC_WEIGHTS[metric])
+        dth = np.linalg.solve(AtA, Atb)
+        a = dth[:3]
+        na = np.sqrt(a @ a)
+        u = a / na if na > 0.0 else np.zeros(3)
+        c = 1.0 / np.sqrt(1.0 + na * na)
+        sn = na * c
+        K = np.array([[0.0, -u[2], u[1]], [u[2], 0.0, -u[0]], [-u[1], u[0], 0.0]])
+        Ra = c * np.eye(3) + sn * K + (1.0 - c) * np.outer(u, u)
+        L = Ra @ Ra
+        dtd = Ra @ (c * dth[3:])
+        t = dtd - L @ np.asarray(smt, np.float64) + np.asarray(dst_mean, np.float64)
+    R = _polar(L)
+    Tc = np.asarray(T_cur, np.float32).astype(np.float64)
+    Tn = np.eye(4, dtype=np.float32)
+    Tn[:3, :3] = (R @ Tc[:3, :3]).astype(np.float32)
+    Tn[:3, 3] = (R @ Tc[:3, 3] + t).astype(np.float32)
+    return Tn, R, R @ Tc[:3, 3] + t
+
+
+def assert_exact_pairs(fix, metric, T, q, smt, pairs):
+    """assert_exact_fixture's conditions (1) to (3) over a pair list under T: q = T S and smt = T src_mean in f32 as in f64, the terms of
+    every pair in f32 as in f64, every numerator below 2^53, the used slots non-zero and apart -> (numerators, sums)"""
+    S, T = fix["S"], np.asarray(T, np.float32)
+    q32 = transform_points(T, S, np.float32); q64 = transform_points(T, S, np.float64)
+    assert q32.dtype == np.float32 and np.array_equal(q32, q) and np.array_equal(q32.astype(np.float64), q64), fix["name"]
+    m32 = transform_points(T, fix["src_mean"].reshape(1, 3), np.float32)[0]
+    assert np.array_equal(m32, smt) and np.array_equal(m32.astype(np.float64), transform_points(T, fix["src_mean"].reshape(1, 3), np.float64)[0])
+    ti, si = pairs
+    p, nv = fix["D"][ti], fix["N"][ti]
+    z32 = pair_terms(metric, p, nv, q32[si], fix["dst_mean"], m32, np.float32)
+    z64 = pair_terms(metric, p, nv, q64[si], fix["dst_mean"], m32, np.float64)
+    assert z32.dtype == np.float32 and np.array_equal(z32.astype(np.float64), z64), (fix["name"], metric)
+    _int_rows(z64, ZSCALE)
+    df = q32[si] - p
+    d2 = df[:, 0] * df[:, 0] + (df[:, 1] * df[:, 1] + df[:, 2] * df[:, 2])
+    assert np.array_equal(d2.astype(np.float64), ((q64[si] - p.astype(np.float64)) ** 2).sum(1)) and np.all(d2 < fix["r2"])
+    num, f64 = expected_sums_pairs(fix, metric, T, pairs)
+    assert all(abs(v) < (1 << 53) for v in num) and [int(v * (1 << DEN_LOG2)) for v in f64] == num
+    assert all(num[s] == 0 for s in range(NSLOTS) if s not in used_slots(metric))
+    return num, f64

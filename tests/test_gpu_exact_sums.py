@@ -36,9 +36,38 @@ C. one iteration of the device-resident loops: cilhip_icp_run(max_iter = 1, conv
    the epilogue's solve_body (epilogue.hip; no path with another solve was found) -- for the adaptive default, fused_epilogue = 1,
    search_direction 1 and 2, each with and without require_reciprocality (launch_acc_reverse), and the ranked loop with one rank
    (RANK_ROWS fold); _prove_loop says which loop and form each one took.
-Not covered: WaveRank<ACC> / k_reverse_warm -- the reverse search accumulates only from the SECOND iteration of a run on (rev_fused needs
-it >= 1, icp_loop.hip), after a step that is no longer exact; and the Kabsch moments streamed over a pair list (no host entry reads them,
-see test_stored_set_host_entries).
+D. the SECOND iteration of the reverse loops (FIRST_TO_SECOND, BOTH, BOTH reciprocal): cilhip_icp_run(max_iter = 2, conv_tol = 0) on
+   sr.two_step_pair, whose first step is exact by construction -- iteration 0 matches the A group alone, all with ONE residual, and
+   steps by -U / 16, so iteration 1 works on lattice data again (B, unmatched before, now carries the residuals; twin targets give the
+   reverse half of BOTH matches that are no reciprocal duplicates).  The reference context is handed the exact iteration-0 sums
+   (icp_begin, icp_apply_sums): it must report one iteration, |A| pairs and THE predicted T1 -- the translation bit for bit; the linear
+   part is T0's up to what the f64 solve leaves (asserted below sr.ABSORB, which tests/test_two_step_refs_cpu.py shows the pinned
+   transform expression rounds away: T1 S and T1 src_mean, evaluated here from the device's own T1, are the intended dyadic positions bit
+   for bit) -- and is then handed the exact iteration-1 sums of the direction: (T2, last_ncorr, last_delta_norm).  Every run of
+   3 directions x reverse_warm_start 1 / 0 x 4 metrics x 2 T0 returns those bytes, twice.  reverse_warm_start = 1: iteration 1 is
+   k_reverse_warm<ACC> (WaveRank<ACC>; last_reverse_fused_iterations() == 1), = 0: a full reverse search, then launch_acc_reverse
+   (== 0); both with run_reverse_loop's other proofs (_prove_loop: nothing listed, no forward form counted, BOTH's forward half cold).
+   Target sizes (twins included): one round of 256 at -1 / 0 / +1, 2,048 / 2,049 (reverse_warm_blocks: 1 -> 2 blocks), 4,352 (17 rounds
+   dealt to three blocks: 6, 6 and 5) and 16 * 2048 * 256 + 257 (the block count capped at 2,048, 17 rounds in the first block: the in-loop
+   flush() with a wave's list at RW_WCAP exactly, the pipeline's `r + gridDim.x < rounds` branch taken 16 times) against 4,096 source
+   points.  In the walk over the sorted target, A sites and twins sit in the last round and in lanes 0 and 63 of a wave, and the first
+   block's waves reach the in-loop flush() with nothing settled (test_reverse_walk_meets_a_sites_and_twins_at_its_edges, on the grid
+   shape asserted here against get_grid_info).
+   Settled or listed.  k_reverse_warm settles a target point iff it has a previous match i, m = smin sqrt(safe2[i]) 0.99999 - 2.0002 eps_q
+   is positive, 4 e (1 + 1e-5) < m^2 and e < r^2.  Here: the A sites are the only targets matched at iteration 0, and after the exact step
+   their e is 0; safe2 (k_self_nn over the source grid) is the smaller of the squared distance to the nearest other source point -- at
+   least (1 - 6/16)^2, two sites apart less the largest difference of two offsets -- and (cell - cell / 512)^2 KSHRINK of a grid
+   whose cell is cbrt(volume / ns) > 1 for a source on at most 55 % of the sites; eps_q = motion_eps_of(T1, ...) = 6e-7 (|t| +
+   sum |L| (|c| + h)) < 6e-7 * 3 * 700 = 1.3e-3.  So m > 0.5 and every A site is SETTLED (accumulated as it streams by, bidir.hip:394);
+   B's sites, the twins, F's and the empty sites have no previous match and are LISTED (searched, then accumulated at bidir.hip:349).
+   No read-out shows this: the kernel counts neither, and instrumenting it is not this module's business.
+   Limit of the design: a settled A pair has residual 0 at iteration 1 (the step removed it).  Its p, q, a, e and n entries are not zero
+   and move AtA and the Kabsch moments, so a stale q or another point's normal on a settled lane still changes T2
+   (test_second_iteration_sums_notice_a_wrong_pair); an error that only scales a settled pair's residual would not show.
+Not covered: feat_warm.hip's three-cloud accumulation; Gauss-Newton steps after the first (max_optimization_iterations > 1); per-pair
+weight callbacks in the reverse loops (they keep the separate pass by design); duplicated source points (the reverse search meets a tie
+and the loop leaves the list-free path); BOTH's warm-started forward half (three iterations and >= 65,536 source points); and the Kabsch
+moments streamed over a pair list (no host entry reads them, see test_stored_set_host_entries).
 """
 import ctypes as C
 import time
@@ -480,3 +509,105 @@ def test_one_loop_iteration_is_the_solve_of_the_exact_sums(Context, dev, n):
             ctx.close()
     print("exact sums, one loop iteration", n, cases, proof)
     _note(f"loop/{n}", {"cases": cases, "ran": proof})
+
+
+# ---- D. the second iteration of the reverse loops, after an exact step -----------------------------------------------------------------
+
+REVERSE_DIRECTIONS = (("first_to_second", (("search_direction", 1), ("require_reciprocality", 0))),
+                      ("both", (("search_direction", 2), ("require_reciprocality", 0))),
+                      ("both_reciprocal", (("search_direction", 2), ("require_reciprocality", 1))))
+
+
+def _result(res):
+    return _T_bits(res), int(res.last_ncorr), np.float32(res.last_delta_norm).tobytes()
+
+
+def _assert_first_step(st, fix, where):
+    """the state after the exact iteration-0 sums: one iteration over the A pairs, the predicted T1 -> (whether T's bits ARE T1's, the
+    largest deviation of the linear part from T0's)"""
+    na = len(fix["pairs0"][0])
+    assert int(st.iterations) == 1 and int(st.last_ncorr) == na, (where, int(st.iterations), int(st.last_ncorr), na)
+    T1 = np.array(st.T[:], np.float32).reshape(4, 4).T.copy()      # (IcpResult holds it column-major)
+    noise = float(np.abs(T1[:3, :3].astype(np.float64) - fix["T"][:3, :3].astype(np.float64)).max())
+    assert np.array_equal(T1[:3, 3], fix["T1"][:3, 3]) and np.array_equal(T1[3], np.array([0, 0, 0, 1], np.float32)), (where, T1, fix["T1"])
+    assert noise <= sr.ABSORB, (where, noise)
+    assert np.array_equal(sr.transform_points(T1, fix["S"], np.float32), fix["q1"]), (where, noise)
+    assert np.array_equal(sr.transform_points(T1, fix["src_mean"].reshape(1, 3), np.float32)[0], fix["smt1"]), (where, noise)
+    return bool(np.array_equal(T1, fix["T1"])), noise
+
+
+@pytest.mark.parametrize("nd", sr.TWO_STEP_SIZES)
+def test_second_loop_iteration_is_the_solve_of_the_exact_sums(Context, dev, nd):
+    t_all = time.perf_counter()
+    assert {m: PARAMS[m][1:] for m in sr.METRIC_WEIGHTS} == sr.METRIC_WEIGHTS
+    cases, proof, exact_T1, noise_max = {}, {}, 0, 0.0
+    run_s = []
+    fix0 = sr.two_step_pair(nd, sr.A_TRANSFORMS[0])
+    t_fix = time.perf_counter() - t_all
+    ref = _open(Context, dev, fix0, ())
+    ctx = _open(Context, dev, fix0, ())
+    # the order the reverse kernels walk the target in: the restated grid (sr.grid_order) is the library's
+    gi, shape = ctx.grid_info(), sr.grid_order(fix0["D"], order=False)
+    assert (gi.nx, gi.ny, gi.nz) == (shape["nx"], shape["ny"], shape["nz"]) and float(gi.cell) == shape["cell"], (nd, gi.nx, gi.ny, gi.nz, gi.cell, shape)
+    assert [float(v) for v in gi.origin] == shape["origin"], (nd, list(gi.origin), shape)
+    for tname in sr.A_TRANSFORMS:
+        fix = sr.two_step_pair(nd, tname)
+        assert fix["D"] is fix0["D"]
+        _load(ref, fix)
+        _load(ctx, fix)
+        r2 = fix["r2"]
+        want = {}
+        for metric in sr.METRICS:
+            exp0 = sr.expected_sums_pairs(fix, metric, fix["T"], fix["pairs0"])[1]
+            exp1 = {}
+            for d, _opts in REVERSE_DIRECTIONS:
+                if d == "both":
+                    exp1[d] = exp1["first_to_second"]      # (the same pairs by design: forward A + B and the twins)
+                    assert all(np.array_equal(x, y) for x, y in zip(fix["pairs1"][d], fix["pairs1"]["first_to_second"]))
+                else:
+                    exp1[d] = sr.expected_sums_pairs(fix, metric, fix["T1"], fix["pairs1"][d])[1]
+                ref.icp_begin(_params(ref, metric, r2, 2), fix["T"], fix["src_mean"])
+                dev.write(exp0)
+                ref.icp_apply_sums(dev.buf.data_ptr())
+                exact, noise = _assert_first_step(ref.icp_state(), fix, (nd, tname, metric))
+                exact_T1 += exact
+                noise_max = max(noise_max, noise)
+                dev.write(exp1[d])
+                ref.icp_apply_sums(dev.buf.data_ptr())
+                st = ref.icp_state()
+                assert int(st.iterations) == 2 and int(st.last_ncorr) == len(fix["pairs1"][d][0]) and float(st.last_delta_norm) > 0.0
+                want[(metric, d)] = _result(st)
+            assert want[(metric, "both")] == want[(metric, "first_to_second")] != want[(metric, "both_reciprocal")]
+        for d, opts in REVERSE_DIRECTIONS:
+            for k, v in opts:
+                ctx.set_option(k, v)
+            for rws in (1, 0):
+                ctx.set_option("reverse_warm_start", rws)
+                assert all(ctx.get_option(k) == v for k, v in opts) and ctx.get_option("reverse_warm_start") == rws
+                name = "%s, reverse_warm_start %d" % (d, rws)
+                for metric in sr.METRICS:
+                    p = _params(ctx, metric, r2, 2)
+                    got = []
+                    for _again in range(2):
+                        t0 = time.perf_counter()
+                        res = ctx.icp_run(p, fix["T"])
+                        run_s.append(time.perf_counter() - t0)
+                        assert int(res.iterations) == 2
+                        _prove_loop(ctx, REVERSE, nd)      # (the list-free reverse loop; BOTH's forward half cold)
+                        fused = ctx.last_reverse_fused_iterations()
+                        assert fused == rws, (nd, tname, name, metric, fused)      # (iteration 1: k_reverse_warm<ACC> | search + launch_acc_reverse)
+                        got.append(_result(res))
+                    assert got[0] == want[(metric, d)], (nd, tname, name, metric, got[0][1], want[(metric, d)][1])
+                    assert got[1] == got[0], (nd, tname, name, metric, "a repeated run differs")
+                    cases[name] = cases.get(name, 0) + 1
+                proof[name] = "reverse loop, iteration 1 " + ("in k_reverse_warm" if rws else "search + launch_acc_reverse")
+    ref.close()
+    ctx.close()
+    wall = time.perf_counter() - t_all
+    print("exact sums, second loop iteration", nd, cases, "T1 bit-exact in %d of %d reference steps, linear part within %.3g" % (exact_T1, 24, noise_max),
+          "%.2f s (fixture %.2f s, slowest run %.4f s)" % (wall, t_fix, max(run_s)))
+    _note(f"second/{nd}", {"cases": cases, "ran": proof, "source points": int(fix0["n"]), "pairs, iteration 0": len(fix0["pairs0"][0]),
+                           "pairs, iteration 1": {d: len(fix0["pairs1"][d][0]) for d, _o in REVERSE_DIRECTIONS},
+                           "reference steps with T1 bit-exact": exact_T1, "largest deviation of T1's linear part": noise_max,
+                           "wall s": round(wall, 3), "fixture s": round(t_fix, 3), "runs": len(run_s), "slowest run s": round(max(run_s), 5),
+                           "runs total s": round(sum(run_s), 4)})
