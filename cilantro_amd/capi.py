@@ -34,6 +34,7 @@ SYMBOLS = [
     "cilhip_fusion_default_params", "cilhip_fuse_frame3f", "cilhip_fusion_remove_unstable3f",
     "cilhip_warp_default_params", "cilhip_warp_field_create", "cilhip_warp_field_destroy", "cilhip_warp_field_estimate3f", "cilhip_warp_field_resample3f",
     "cilhip_transform_points_per_point3f", "cilhip_warp_field_icp_run",
+    "cilhip_warp_field_estimate_affine3f", "cilhip_warp_field_resample_affine3f", "cilhip_warp_field_icp_run_affine",
     "cilhip_nn_graph_matrix", "cilhip_sparse_from_csr", "cilhip_sparse_info", "cilhip_sparse_get", "cilhip_sparse_destroy",
     "cilhip_spectral_default_params", "cilhip_spectral_embedding", "cilhip_kmeans_nd",
     "cilhip_mds_default_params", "cilhip_mds_embedding", "cilhip_mds_apply", "cilhip_pca_fit", "cilhip_pca_project", "cilhip_pca_reconstruct",
@@ -314,6 +315,9 @@ def load():
     L.cilhip_warp_field_resample3f.argtypes = [vp, f32p, f32p, C.c_int]
     L.cilhip_transform_points_per_point3f.argtypes = [C.c_int, f32p, f32p, C.c_size_t, C.c_int, f32p]
     L.cilhip_warp_field_icp_run.argtypes = [vp, vp, C.POINTER(WarpParams), C.c_size_t, C.c_float, C.c_float, f32p, f32p, f32p, C.POINTER(IcpResult)]
+    L.cilhip_warp_field_estimate_affine3f.argtypes = L.cilhip_warp_field_estimate3f.argtypes
+    L.cilhip_warp_field_resample_affine3f.argtypes = L.cilhip_warp_field_resample3f.argtypes
+    L.cilhip_warp_field_icp_run_affine.argtypes = L.cilhip_warp_field_icp_run.argtypes
     L.cilhip_nn_graph_matrix.argtypes = [C.c_int, C.c_size_t, vp, vp, f32p, C.c_size_t, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.POINTER(vp)]
     L.cilhip_sparse_from_csr.argtypes = [C.c_int, C.c_size_t, vp, vp, f32p, C.c_int, C.POINTER(vp)]
     L.cilhip_sparse_info.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]

@@ -13,6 +13,11 @@
 // live in one device record, the vector updates and the convergence decision run in one 1024-thread block, and the host reads that
 // record back once per WF_CG_BATCH iterations.
 //
+// The same with AFFINE node transforms (:1859-2234): 12 unknowns per node (the 3 x 3 row-major, then t), one
+// 12-float record per source point (s_t, the normalised weights, the residuals, the normal), no polish on the way out or in the resample.
+// The kernels whose only difference is the unknown count are templates on it (NU = 6 or 12); WfRec<NU> says where a record keeps what
+// the gathers read.  The handle's scratch is sized for 6 at creation and grown on the first affine estimate.
+//
 // Set-up (cilhip_warp_field_create): the weights w_ij = eval(d2_ij), their totals in list order (:1456-1465) and the arc weights
 // sqrt(eval(d2)) on the device; the two transposes by a counting sort on the host, once per (source, control graph) pair.
 #include <hip/hip_runtime.h>
@@ -42,7 +47,14 @@ constexpr int WF_CG_BATCH = 8;          // CG iterations enqueued between two re
 constexpr int WF_ROW = 24;              // floats per source point's record
 // record layout: [0..2] dRda^T s  [3..5] dRdb^T s  [6..8] dRdc^T s  [9] point weight / total  [10..12] point residuals
 //                [13..15] n . (the three above)  [16..18] n  [19] plane weight / total  [20] plane residual  [21..23] unused
+// the affine record (section 17.4, A3), 12 floats in the same buffer: [0..2] s_t  [3] point weight / total  [4] plane weight / total
+//                [5..7] point residuals  [8..10] n  [11] plane residual
 constexpr unsigned long long WF_LIMIT = 0xFFFFFFF0ull;
+
+// where a record of NU unknowns per node keeps what the gathers read: its stride, the two normalised weights, the four residuals
+template <int NU> struct WfRec;
+template <> struct WfRec<6> { static constexpr int ROW = WF_ROW, WPT = 9, WPL = 19, BPT = 10, BPL = 20; };
+template <> struct WfRec<12> { static constexpr int ROW = 12, WPT = 3, WPL = 4, BPT = 5, BPL = 11; };
 
 struct WfScal {
   float abs_new, thr, rhs2, resid2, max_delta_sq;
@@ -175,16 +187,71 @@ __global__ void k_wf_lin_points(WfGraph g, const float* __restrict__ tf, const f
   }
 }
 
+// the affine unknowns start at the identity and a zero translation (:2004-2008): 12 per node, the 3 x 3 row-major, then t
+__global__ void k_wf_affine_start(uint32_t n_ctrl, float* __restrict__ tf) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < 12 * (size_t)n_ctrl; i += (size_t)gridDim.x * blockDim.x) {
+    const uint32_t c = (uint32_t)(i % 12);
+    tf[i] = (c == 0 || c == 4 || c == 8) ? 1.0f : 0.0f;
+  }
+}
+
+// the affine record (A2, A3; :2050-2099, :2110-2163): blend in list order, scale by the reciprocal, s_t, the residuals
+__global__ void k_wf_lin_points_affine(WfGraph g, const float* __restrict__ tf, const float* __restrict__ dst, const float* __restrict__ nrm, uint32_t n_dst,
+                                       const float* __restrict__ src, const uint32_t* __restrict__ nn, float w_pt_sqrt, float w_pl_sqrt, float* __restrict__ rows) {
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < g.n_src; i += gridDim.x * blockDim.x) {
+    float* row = rows + (size_t)i * WfRec<12>::ROW;
+    const uint32_t m = nn[i];
+    const float tot = g.total_w[i];
+    if (m >= n_dst || tot == 0.0f) {      // no correspondence, or both correspondence weights 0 (:2068-2071): a row of zeros
+#pragma unroll
+      for (int q = 0; q < WfRec<12>::ROW; ++q) row[q] = 0.0f;
+      continue;
+    }
+    float lin[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, tr[3] = {0, 0, 0};
+    for (uint32_t j = 0; j < g.k_ctrl; ++j) {
+      const size_t e = (size_t)i * g.k_ctrl + j;
+      const uint32_t id = g.ctrl_idx[e];
+      if (id == NONE_U32) continue;
+      const float w = g.ctrl_w[e];
+      const float* t12 = tf + 12 * (size_t)id;
+#pragma unroll
+      for (int c = 0; c < 9; ++c) lin[c] += w * t12[c];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) tr[c] += w * t12[9 + c];
+    }
+    const float inv = 1.0f / tot;
+#pragma unroll
+    for (int c = 0; c < 9; ++c) lin[c] *= inv;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) tr[c] *= inv;
+    const float sx = src[3 * (size_t)i], sy = src[3 * (size_t)i + 1], sz = src[3 * (size_t)i + 2];
+    float st[3], e[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      st[r] = ((lin[3 * r] * sx + lin[3 * r + 1] * sy) + lin[3 * r + 2] * sz) + tr[r];
+      e[r] = dst[3 * (size_t)m + r] - st[r];
+    }
+    float n[3] = {0.0f, 0.0f, 0.0f};
+    if (w_pl_sqrt != 0.0f) { n[0] = nrm[3 * (size_t)m]; n[1] = nrm[3 * (size_t)m + 1]; n[2] = nrm[3 * (size_t)m + 2]; }
+    row[0] = st[0]; row[1] = st[1]; row[2] = st[2];
+    row[3] = w_pt_sqrt / tot; row[4] = w_pl_sqrt / tot;
+    row[5] = w_pt_sqrt * e[0]; row[6] = w_pt_sqrt * e[1]; row[7] = w_pt_sqrt * e[2];
+    row[8] = n[0]; row[9] = n[1]; row[10] = n[2];
+    row[11] = ((n[0] * e[0] + n[1] * e[1]) + n[2] * e[2]) * w_pl_sqrt;
+  }
+}
+
+template <int NU>
 __global__ void k_wf_lin_arcs(WfGraph g, const float* __restrict__ tf, float w_reg_sqrt, float huber, float* __restrict__ arc_d, float* __restrict__ arc_b) {
   for (uint32_t a = blockIdx.x * blockDim.x + threadIdx.x; a < g.n_arcs; a += gridDim.x * blockDim.x) {
     const float w = w_reg_sqrt * g.arc_w[a];
-    const float* ts = tf + 6 * (size_t)g.arc_s[a];
-    const float* tn = tf + 6 * (size_t)g.arc_n[a];
+    const float* ts = tf + NU * (size_t)g.arc_s[a];
+    const float* tn = tf + NU * (size_t)g.arc_n[a];
 #pragma unroll
-    for (int c = 0; c < 6; ++c) {
+    for (int c = 0; c < NU; ++c) {
       const float diff = ts[c] - tn[c];
-      arc_d[6 * (size_t)a + c] = w * wf_sqrt_huber_derivative(diff, huber);
-      arc_b[6 * (size_t)a + c] = -w * wf_sqrt_huber(diff, huber);
+      arc_d[NU * (size_t)a + c] = w * wf_sqrt_huber_derivative(diff, huber);
+      arc_b[NU * (size_t)a + c] = -w * wf_sqrt_huber(diff, huber);
     }
   }
 }
@@ -201,117 +268,146 @@ __device__ __forceinline__ void wf_coefficients(const float* __restrict__ row, f
   co[3][3] = row[16] * wpl; co[3][4] = row[17] * wpl; co[3][5] = row[18] * wpl;
 }
 
+// the affine rows (A3): the linear part's coefficients carry the TRANSFORMED point s_t, as the reference writes them (:2091, :2153)
+__device__ __forceinline__ void wf_coefficients(const float* __restrict__ row, float w, float co[4][12]) {
+  const float wpt = row[3] * w, wpl = row[4] * w;
+#pragma unroll
+  for (int e = 0; e < 3; ++e) {
+#pragma unroll
+    for (int c = 0; c < 12; ++c) co[e][c] = 0.0f;
+#pragma unroll
+    for (int nz = 0; nz < 3; ++nz) co[e][3 * e + nz] = wpt * row[nz];
+    co[e][9 + e] = wpt;
+  }
+#pragma unroll
+  for (int blk = 0; blk < 3; ++blk) {
+    const float wn = wpl * row[8 + blk];
+#pragma unroll
+    for (int cur = 0; cur < 3; ++cur) co[3][3 * blk + cur] = wn * row[cur];
+    co[3][9 + blk] = wn;
+  }
+}
+
 // A^T b and diag(A^T A), one wave per control node
+template <int NU>
 __global__ void k_wf_gather_rhs(WfGraph g, const float* __restrict__ rows, const float* __restrict__ arc_d, const float* __restrict__ arc_b, float* __restrict__ atb,
                                 float* __restrict__ invdiag) {
   const uint32_t lane = threadIdx.x & 63;
   for (uint32_t node = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); node < g.n_ctrl; node += gridDim.x * (blockDim.x >> 6)) {
-    double rb[6] = {0, 0, 0, 0, 0, 0}, dg[6] = {0, 0, 0, 0, 0, 0};
+    using R = WfRec<NU>;
+    double rb[NU], dg[NU];
+#pragma unroll
+    for (int c = 0; c < NU; ++c) rb[c] = dg[c] = 0.0;
     for (uint32_t q = g.node_ptr[node] + lane; q < g.node_ptr[node + 1]; q += 64) {
       const uint32_t item = g.node_items[q];
-      const float* row = rows + (size_t)(item / g.k_ctrl) * WF_ROW;
-      float co[4][6];
+      const float* row = rows + (size_t)(item / g.k_ctrl) * R::ROW;
+      float co[4][NU];
       wf_coefficients(row, g.ctrl_w[item], co);
-      const float b[4] = {row[10], row[11], row[12], row[20]};
+      const float b[4] = {row[R::BPT], row[R::BPT + 1], row[R::BPT + 2], row[R::BPL]};
 #pragma unroll
       for (int e = 0; e < 4; ++e)
 #pragma unroll
-        for (int c = 0; c < 6; ++c) { rb[c] = fma((double)co[e][c], (double)b[e], rb[c]); dg[c] = fma((double)co[e][c], (double)co[e][c], dg[c]); }
+        for (int c = 0; c < NU; ++c) { rb[c] = fma((double)co[e][c], (double)b[e], rb[c]); dg[c] = fma((double)co[e][c], (double)co[e][c], dg[c]); }
     }
     for (uint32_t q = g.anode_ptr[node] + lane; q < g.anode_ptr[node + 1]; q += 64) {
       const uint32_t item = g.anode_items[q];
       const size_t a = item >> 1;
       const double sign = (item & 1u) ? -1.0 : 1.0;
 #pragma unroll
-      for (int c = 0; c < 6; ++c) {
-        const double d = (double)arc_d[6 * a + c];
-        rb[c] = fma(sign * d, (double)arc_b[6 * a + c], rb[c]);
+      for (int c = 0; c < NU; ++c) {
+        const double d = (double)arc_d[NU * a + c];
+        rb[c] = fma(sign * d, (double)arc_b[NU * a + c], rb[c]);
         dg[c] = fma(d, d, dg[c]);
       }
     }
 #pragma unroll
-    for (int c = 0; c < 6; ++c) { rb[c] = wf_wave_sum(rb[c]); dg[c] = wf_wave_sum(dg[c]); }
-    if (lane < 6) {
+    for (int c = 0; c < NU; ++c) { rb[c] = wf_wave_sum(rb[c]); dg[c] = wf_wave_sum(dg[c]); }
+    if (lane < NU) {
       double r = rb[0], d = dg[0];
 #pragma unroll
-      for (int c = 1; c < 6; ++c) if (lane == (uint32_t)c) { r = rb[c]; d = dg[c]; }
+      for (int c = 1; c < NU; ++c) if (lane == (uint32_t)c) { r = rb[c]; d = dg[c]; }
       const float df = (float)d;
-      atb[6 * (size_t)node + lane] = (float)r;
-      invdiag[6 * (size_t)node + lane] = df != 0.0f ? 1.0f / df : 1.0f;      // Eigen's DiagonalPreconditioner
+      atb[NU * (size_t)node + lane] = (float)r;
+      invdiag[NU * (size_t)node + lane] = df != 0.0f ? 1.0f / df : 1.0f;      // Eigen's DiagonalPreconditioner
     }
   }
 }
 
 // ---- the operator ------------------------------------------------------------------------------------------------------------------
 // pass 1: u = A p.  Lanes [0, n_src) take a source point each, lanes [n_src, n_src + n_arcs) an arc each.
+template <int NU>
 __global__ void k_wf_apply_rows(WfGraph g, const float* __restrict__ rows, const float* __restrict__ arc_d, const float* __restrict__ p, const WfScal* __restrict__ sc,
                                 float* __restrict__ u_pt, float* __restrict__ u_arc) {
   if (sc->done) return;
   const size_t total = (size_t)g.n_src + g.n_arcs;
   for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
     if (t < g.n_src) {
-      const float* row = rows + t * WF_ROW;
+      using R = WfRec<NU>;
+      const float* row = rows + t * R::ROW;
       double u[4] = {0, 0, 0, 0};
-      if (row[9] != 0.0f || row[19] != 0.0f) {
+      if (row[R::WPT] != 0.0f || row[R::WPL] != 0.0f) {
         for (uint32_t j = 0; j < g.k_ctrl; ++j) {
           const size_t e = t * g.k_ctrl + j;
           const uint32_t id = g.ctrl_idx[e];
           if (id == NONE_U32) continue;
-          float co[4][6];
+          float co[4][NU];
           wf_coefficients(row, g.ctrl_w[e], co);
-          const float* p6 = p + 6 * (size_t)id;
+          const float* p6 = p + NU * (size_t)id;
 #pragma unroll
           for (int q = 0; q < 4; ++q)
 #pragma unroll
-            for (int c = 0; c < 6; ++c) u[q] = fma((double)co[q][c], (double)p6[c], u[q]);
+            for (int c = 0; c < NU; ++c) u[q] = fma((double)co[q][c], (double)p6[c], u[q]);
         }
       }
       *reinterpret_cast<float4*>(u_pt + 4 * t) = make_float4((float)u[0], (float)u[1], (float)u[2], (float)u[3]);
     } else {
       const size_t a = t - g.n_src;
-      const float* ps = p + 6 * (size_t)g.arc_s[a];
-      const float* pn = p + 6 * (size_t)g.arc_n[a];
+      const float* ps = p + NU * (size_t)g.arc_s[a];
+      const float* pn = p + NU * (size_t)g.arc_n[a];
 #pragma unroll
-      for (int c = 0; c < 6; ++c) {
-        const double d = (double)arc_d[6 * a + c];
-        u_arc[6 * a + c] = (float)fma(d, (double)ps[c], -(d * (double)pn[c]));
+      for (int c = 0; c < NU; ++c) {
+        const double d = (double)arc_d[NU * a + c];
+        u_arc[NU * a + c] = (float)fma(d, (double)ps[c], -(d * (double)pn[c]));
       }
     }
   }
 }
 
-// pass 2: tmp = A^T u, one wave per control node; node_dot[node] = the node's six terms of p . tmp
+// pass 2: tmp = A^T u, one wave per control node; node_dot[node] = the node's NU terms of p . tmp
+template <int NU>
 __global__ void k_wf_apply_nodes(WfGraph g, const float* __restrict__ rows, const float* __restrict__ arc_d, const float* __restrict__ u_pt, const float* __restrict__ u_arc,
                                  const float* __restrict__ p, const WfScal* __restrict__ sc, float* __restrict__ tmp, double* __restrict__ node_dot) {
   if (sc->done) return;
   const uint32_t lane = threadIdx.x & 63;
   for (uint32_t node = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); node < g.n_ctrl; node += gridDim.x * (blockDim.x >> 6)) {
-    double acc[6] = {0, 0, 0, 0, 0, 0};
+    double acc[NU];
+#pragma unroll
+    for (int c = 0; c < NU; ++c) acc[c] = 0.0;
     for (uint32_t q = g.node_ptr[node] + lane; q < g.node_ptr[node + 1]; q += 64) {
       const uint32_t item = g.node_items[q];
       const size_t i = item / g.k_ctrl;
-      float co[4][6];
-      wf_coefficients(rows + i * WF_ROW, g.ctrl_w[item], co);
+      float co[4][NU];
+      wf_coefficients(rows + i * WfRec<NU>::ROW, g.ctrl_w[item], co);
       const float4 u = *reinterpret_cast<const float4*>(u_pt + 4 * i);
       const float uu[4] = {u.x, u.y, u.z, u.w};
 #pragma unroll
       for (int e = 0; e < 4; ++e)
 #pragma unroll
-        for (int c = 0; c < 6; ++c) acc[c] = fma((double)co[e][c], (double)uu[e], acc[c]);
+        for (int c = 0; c < NU; ++c) acc[c] = fma((double)co[e][c], (double)uu[e], acc[c]);
     }
     for (uint32_t q = g.anode_ptr[node] + lane; q < g.anode_ptr[node + 1]; q += 64) {
       const uint32_t item = g.anode_items[q];
       const size_t a = item >> 1;
       const double sign = (item & 1u) ? -1.0 : 1.0;
 #pragma unroll
-      for (int c = 0; c < 6; ++c) acc[c] = fma(sign * (double)arc_d[6 * a + c], (double)u_arc[6 * a + c], acc[c]);
+      for (int c = 0; c < NU; ++c) acc[c] = fma(sign * (double)arc_d[NU * a + c], (double)u_arc[NU * a + c], acc[c]);
     }
     double dot = 0.0;
 #pragma unroll
-    for (int c = 0; c < 6; ++c) {
+    for (int c = 0; c < NU; ++c) {
       const float v = (float)wf_wave_sum(acc[c]);
-      if (lane == 0) tmp[6 * (size_t)node + c] = v;
-      dot = fma((double)p[6 * (size_t)node + c], (double)v, dot);
+      if (lane == 0) tmp[NU * (size_t)node + c] = v;
+      dot = fma((double)p[NU * (size_t)node + c], (double)v, dot);
     }
     if (lane == 0) node_dot[node] = dot;
   }
@@ -382,13 +478,14 @@ __global__ __launch_bounds__(WF_CG_THREADS) void k_wf_cg_update(uint32_t n6, uin
 
 // ---- epilogue --------------------------------------------------------------------------------------------------------------------
 // tforms_vec += delta; max_delta_sq = max over the nodes of |delta_node|^2 (:1814-1824)
+template <int NU>
 __global__ __launch_bounds__(WF_CG_THREADS) void k_wf_gn_update(uint32_t n_ctrl, const float* __restrict__ x, float* __restrict__ tf, WfScal* sc) {
   __shared__ float lds[16];
   float mx = 0.0f;
   for (uint32_t node = threadIdx.x; node < n_ctrl; node += WF_CG_THREADS) {
     float d2 = 0.0f;
 #pragma unroll
-    for (int c = 0; c < 6; ++c) { const float v = x[6 * (size_t)node + c]; d2 += v * v; tf[6 * (size_t)node + c] += v; }
+    for (int c = 0; c < NU; ++c) { const float v = x[NU * (size_t)node + c]; d2 += v * v; tf[NU * (size_t)node + c] += v; }
     if (d2 > mx) mx = d2;
   }
 #pragma unroll
@@ -430,11 +527,24 @@ __global__ void k_wf_to_transforms(uint32_t n_ctrl, const float* __restrict__ tf
   }
 }
 
+// the affine unknowns are copied out as they are (:2222-2231): no rotation()
+__global__ void k_wf_to_transforms_affine(uint32_t n_ctrl, const float* __restrict__ tf, float* __restrict__ T) {
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_ctrl; i += gridDim.x * blockDim.x) {
+    const float* t12 = tf + 12 * (size_t)i;
+    float L[9];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) L[q] = t12[q];
+    wf_store_T(T + 16 * (size_t)i, L, t12[9], t12[10], t12[11]);
+  }
+}
+
 __global__ void k_wf_identity(size_t n, float* __restrict__ T) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < 16 * n; i += (size_t)gridDim.x * blockDim.x) T[i] = (i & 15) % 5 == 0 ? 1.0f : 0.0f;
 }
 
-// resampleTransforms, the list overload (warp_field_utilities.hpp:14-48), with the weights of the set-up
+// resampleTransforms, the list overload (warp_field_utilities.hpp:14-48), with the weights of the set-up; POLISH: through rotation()
+// (the Isometry mode), otherwise the blend as it is (A7)
+template <bool POLISH>
 __global__ void k_wf_resample(WfGraph g, const float* __restrict__ ctrl_T, float* __restrict__ dense_T) {
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < g.n_src; i += gridDim.x * blockDim.x) {
     float L[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, t[3] = {0, 0, 0};
@@ -459,7 +569,11 @@ __global__ void k_wf_resample(WfGraph g, const float* __restrict__ ctrl_T, float
       const float inv = 1.0f / tot;
 #pragma unroll
       for (int q = 0; q < 9; ++q) L[q] *= inv;
-      wf_polish(L, R);
+      if (POLISH) wf_polish(L, R);
+      else {
+#pragma unroll
+        for (int q = 0; q < 9; ++q) R[q] = L[q];
+      }
 #pragma unroll
       for (int q = 0; q < 3; ++q) t[q] *= inv;
     }
@@ -546,7 +660,15 @@ struct cilhip_warp_field {
   cilhip::WfGraph graph() const {
     return cilhip::WfGraph{(uint32_t)n_src, (uint32_t)n_ctrl, (uint32_t)k_ctrl, (uint32_t)n_arcs, ctrl_idx, ctrl_w, total_w, node_ptr, node_items, arc_s, arc_n, arc_w, anode_ptr, anode_items};
   }
-  float* v(int which) const { return vec.get() + (size_t)which * 6 * n_ctrl; }
+  float* v(int which, int nu = 6) const { return vec.get() + (size_t)which * nu * n_ctrl; }
+  // the solver's scratch is sized for 6 unknowns per node at creation; the first affine call grows it to 12 (contents are per call)
+  hipError_t grow(int nu) {
+    hipError_t e = vec.ensure((size_t)7 * nu * n_ctrl + n_ctrl);
+    if (e == hipSuccess) e = arc_d.ensure(nu * n_arcs);
+    if (e == hipSuccess) e = arc_b.ensure(nu * n_arcs);
+    if (e == hipSuccess) e = u_arc.ensure(nu * n_arcs);
+    return e;
+  }
 };
 
 namespace cilhip {
@@ -573,8 +695,9 @@ int wf_set_identity_dev(const char* F, hipStream_t s, float* d_T, size_t n) {
   return CILHIP_OK;
 }
 
-int wf_resample_dev(const char* F, cilhip_warp_field* wf, const float* d_ctrl_T, float* d_dense_T) {
-  hipLaunchKernelGGL(k_wf_resample, dim3(wf_blocks(wf->n_src)), dim3(WF_THREADS), 0, wf->st.s, wf->graph(), d_ctrl_T, d_dense_T);
+int wf_resample_dev(const char* F, cilhip_warp_field* wf, const float* d_ctrl_T, float* d_dense_T, WfKind kind) {
+  if (kind == WF_AFFINE) hipLaunchKernelGGL(k_wf_resample<false>, dim3(wf_blocks(wf->n_src)), dim3(WF_THREADS), 0, wf->st.s, wf->graph(), d_ctrl_T, d_dense_T);
+  else hipLaunchKernelGGL(k_wf_resample<true>, dim3(wf_blocks(wf->n_src)), dim3(WF_THREADS), 0, wf->st.s, wf->graph(), d_ctrl_T, d_dense_T);
   ST_CK(F, hipGetLastError());
   return CILHIP_OK;
 }
@@ -615,18 +738,27 @@ int wf_unsort_target_dev(const char* F, hipStream_t s, const float4* pts, const 
   return CILHIP_OK;
 }
 
-int wf_estimate_dev(const char* F, cilhip_warp_field* wf, const float* d_dst, const float* d_nrm, size_t n_dst, const float* d_src, const uint32_t* d_nn,
-                    const cilhip_warp_params& prm, float* d_T_out, cilhip_warp_stats* stats) {
+namespace {
+
+// the Gauss-Newton loop over NU unknowns per node: 6 = (a, b, c, t) of section 17.1, 12 = (L row-major, t) of section 17.4
+template <int NU>
+int wf_estimate_impl(const char* F, cilhip_warp_field* wf, const float* d_dst, const float* d_nrm, size_t n_dst, const float* d_src, const uint32_t* d_nn,
+                     const cilhip_warp_params& prm, float* d_T_out, cilhip_warp_stats* stats) {
   hipStream_t s = wf->st.s;
+  if (NU != 6) ST_CK(F, wf->grow(NU));
   const WfGraph g = wf->graph();
-  const uint32_t n6 = (uint32_t)(6 * wf->n_ctrl);
+  const uint32_t n6 = (uint32_t)(NU * wf->n_ctrl);
   cilhip_warp_stats st{0, 0, 0u, 0.0f, 0.0f};
   WfScal h{};
-  float *tf = wf->v(0), *atb = wf->v(1), *invdiag = wf->v(2), *x = wf->v(3), *r = wf->v(4), *p = wf->v(5), *tmp = wf->v(6);
+  float *tf = wf->v(0, NU), *atb = wf->v(1, NU), *invdiag = wf->v(2, NU), *x = wf->v(3, NU), *r = wf->v(4, NU), *p = wf->v(5, NU), *tmp = wf->v(6, NU);
   WfScal* sc = wf->sc.get();
   const bool has_pt = prm.w_p2p > 0.0f, has_pl = prm.w_p2pl > 0.0f;
   ST_CK(F, hipMemsetAsync(sc, 0, sizeof(WfScal), s));
-  ST_CK(F, hipMemsetAsync(tf, 0, (size_t)n6 * sizeof(float), s));
+  if (NU == 6) ST_CK(F, hipMemsetAsync(tf, 0, (size_t)n6 * sizeof(float), s));
+  else {
+    hipLaunchKernelGGL(k_wf_affine_start, dim3(wf_blocks(n6)), dim3(WF_THREADS), 0, s, g.n_ctrl, tf);
+    ST_CK(F, hipGetLastError());
+  }
   if (has_pt || has_pl) {
     hipLaunchKernelGGL(k_wf_count_matches, dim3(wf_blocks(wf->n_src)), dim3(WF_THREADS), 0, s, g.n_src, (uint32_t)n_dst, d_nn, sc);
     ST_CK(F, hipGetLastError());
@@ -644,14 +776,14 @@ int wf_estimate_dev(const char* F, cilhip_warp_field* wf, const float* d_dst, co
   const uint32_t max_cg = (uint32_t)prm.max_cg_iter;
   const unsigned row_blocks = wf_blocks(wf->n_src + wf->n_arcs), node_blocks = wf_node_blocks(wf->n_ctrl);
   while ((size_t)st.gn_iterations < prm.max_gn_iter) {
-    hipLaunchKernelGGL(k_wf_lin_points, dim3(wf_blocks(wf->n_src)), dim3(WF_THREADS), 0, s, g, (const float*)tf, d_dst, d_nrm, (uint32_t)n_dst, d_src, d_nn, w_pt_sqrt, w_pl_sqrt,
-                       wf->rows.get());
+    hipLaunchKernelGGL(NU == 6 ? k_wf_lin_points : k_wf_lin_points_affine, dim3(wf_blocks(wf->n_src)), dim3(WF_THREADS), 0, s, g, (const float*)tf, d_dst, d_nrm, (uint32_t)n_dst, d_src,
+                       d_nn, w_pt_sqrt, w_pl_sqrt, wf->rows.get());
     ST_CK(F, hipGetLastError());
     if (wf->n_arcs) {
-      hipLaunchKernelGGL(k_wf_lin_arcs, dim3(wf_blocks(wf->n_arcs)), dim3(WF_THREADS), 0, s, g, (const float*)tf, w_reg_sqrt, prm.huber_boundary, wf->arc_d.get(), wf->arc_b.get());
+      hipLaunchKernelGGL(k_wf_lin_arcs<NU>, dim3(wf_blocks(wf->n_arcs)), dim3(WF_THREADS), 0, s, g, (const float*)tf, w_reg_sqrt, prm.huber_boundary, wf->arc_d.get(), wf->arc_b.get());
       ST_CK(F, hipGetLastError());
     }
-    hipLaunchKernelGGL(k_wf_gather_rhs, dim3(node_blocks), dim3(WF_THREADS), 0, s, g, (const float*)wf->rows.get(), (const float*)wf->arc_d.get(), (const float*)wf->arc_b.get(), atb,
+    hipLaunchKernelGGL(k_wf_gather_rhs<NU>, dim3(node_blocks), dim3(WF_THREADS), 0, s, g, (const float*)wf->rows.get(), (const float*)wf->arc_d.get(), (const float*)wf->arc_b.get(), atb,
                        invdiag);
     ST_CK(F, hipGetLastError());
     hipLaunchKernelGGL(k_wf_cg_init, dim3(1), dim3(WF_CG_THREADS), 0, s, n6, (const float*)atb, (const float*)invdiag, x, r, p, sc, prm.cg_conv_tol, max_cg);
@@ -659,9 +791,9 @@ int wf_estimate_dev(const char* F, cilhip_warp_field* wf, const float* d_dst, co
     for (uint32_t launched = 0; launched < max_cg;) {
       const uint32_t batch = std::min<uint32_t>(WF_CG_BATCH, max_cg - launched);
       for (uint32_t b = 0; b < batch; ++b) {
-        hipLaunchKernelGGL(k_wf_apply_rows, dim3(row_blocks), dim3(WF_THREADS), 0, s, g, (const float*)wf->rows.get(), (const float*)wf->arc_d.get(), (const float*)p,
+        hipLaunchKernelGGL(k_wf_apply_rows<NU>, dim3(row_blocks), dim3(WF_THREADS), 0, s, g, (const float*)wf->rows.get(), (const float*)wf->arc_d.get(), (const float*)p,
                            (const WfScal*)sc, wf->u_pt.get(), wf->u_arc.get());
-        hipLaunchKernelGGL(k_wf_apply_nodes, dim3(node_blocks), dim3(WF_THREADS), 0, s, g, (const float*)wf->rows.get(), (const float*)wf->arc_d.get(), (const float*)wf->u_pt.get(),
+        hipLaunchKernelGGL(k_wf_apply_nodes<NU>, dim3(node_blocks), dim3(WF_THREADS), 0, s, g, (const float*)wf->rows.get(), (const float*)wf->arc_d.get(), (const float*)wf->u_pt.get(),
                            (const float*)wf->u_arc.get(), (const float*)p, (const WfScal*)sc, tmp, wf->node_dot.get());
         hipLaunchKernelGGL(k_wf_cg_update, dim3(1), dim3(WF_CG_THREADS), 0, s, n6, g.n_ctrl, (const double*)wf->node_dot.get(), (const float*)tmp, (const float*)invdiag, x, r, p, sc,
                            max_cg);
@@ -672,7 +804,7 @@ int wf_estimate_dev(const char* F, cilhip_warp_field* wf, const float* d_dst, co
       ST_CK(F, hipStreamSynchronize(s));
       if (h.done) break;
     }
-    hipLaunchKernelGGL(k_wf_gn_update, dim3(1), dim3(WF_CG_THREADS), 0, s, g.n_ctrl, (const float*)x, tf, sc);
+    hipLaunchKernelGGL(k_wf_gn_update<NU>, dim3(1), dim3(WF_CG_THREADS), 0, s, g.n_ctrl, (const float*)x, tf, sc);
     ST_CK(F, hipGetLastError());
     ST_CK(F, hipMemcpyAsync(&h, sc, sizeof(WfScal), hipMemcpyDeviceToHost, s));
     ST_CK(F, hipStreamSynchronize(s));
@@ -682,11 +814,19 @@ int wf_estimate_dev(const char* F, cilhip_warp_field* wf, const float* d_dst, co
     st.max_delta_sq = h.max_delta_sq;
     if (h.max_delta_sq < gn_tol_sq) { st.converged = 1; break; }
   }
-  hipLaunchKernelGGL(k_wf_to_transforms, dim3(wf_blocks(wf->n_ctrl)), dim3(WF_THREADS), 0, s, g.n_ctrl, (const float*)tf, d_T_out);
+  hipLaunchKernelGGL(NU == 6 ? k_wf_to_transforms : k_wf_to_transforms_affine, dim3(wf_blocks(wf->n_ctrl)), dim3(WF_THREADS), 0, s, g.n_ctrl, (const float*)tf, d_T_out);
   ST_CK(F, hipGetLastError());
   ST_CK(F, hipStreamSynchronize(s));
   if (stats) *stats = st;
   return CILHIP_OK;
+}
+
+}  // namespace
+
+int wf_estimate_dev(const char* F, cilhip_warp_field* wf, const float* d_dst, const float* d_nrm, size_t n_dst, const float* d_src, const uint32_t* d_nn,
+                    const cilhip_warp_params& prm, float* d_T_out, cilhip_warp_stats* stats, WfKind kind) {
+  return kind == WF_AFFINE ? wf_estimate_impl<12>(F, wf, d_dst, d_nrm, n_dst, d_src, d_nn, prm, d_T_out, stats)
+                           : wf_estimate_impl<6>(F, wf, d_dst, d_nrm, n_dst, d_src, d_nn, prm, d_T_out, stats);
 }
 
 namespace {
@@ -830,11 +970,12 @@ extern "C" void cilhip_warp_field_destroy(cilhip_warp_field* wf) {
   delete wf;
 }
 
-extern "C" int cilhip_warp_field_estimate3f(cilhip_warp_field* wf, const float* dst_xyz, const float* dst_normals, size_t n_dst, const float* src_xyz, const uint32_t* nn_idx,
-                                            int mem, const cilhip_warp_params* params, float* ctrl_transforms_out, cilhip_warp_stats* stats_or_null) {
-  using namespace cilhip;
-  constexpr const char* F = "warp_field_estimate";
-  auto refuse = [](const char* why) { return st_fail(CILHIP_ERR_INVALID, F, why); };
+namespace cilhip {
+namespace {
+
+int wf_estimate_entry(const char* F, WfKind kind, cilhip_warp_field* wf, const float* dst_xyz, const float* dst_normals, size_t n_dst, const float* src_xyz, const uint32_t* nn_idx,
+                      int mem, const cilhip_warp_params* params, float* ctrl_transforms_out, cilhip_warp_stats* stats_or_null) {
+  auto refuse = [F](const char* why) { return st_fail(CILHIP_ERR_INVALID, F, why); };
   if (!wf) return refuse("the warp field is null");
   if (!src_xyz || !nn_idx || !ctrl_transforms_out) return refuse("src_xyz, nn_idx or ctrl_transforms_out is null");
   if (mem != CILHIP_MEM_HOST && mem != CILHIP_MEM_DEVICE) return refuse("mem: CILHIP_MEM_HOST or CILHIP_MEM_DEVICE");
@@ -855,7 +996,7 @@ extern "C" int cilhip_warp_field_estimate3f(cilhip_warp_field* wf, const float* 
     float* d_T = ctrl_transforms_out;
     if (mem == CILHIP_MEM_HOST) ST_CK(F, pool.get(&d_T, 16 * wf->n_ctrl));
     cilhip_warp_stats st{};
-    if (const int rc = wf_estimate_dev(F, wf, d_dst, d_nrm, n_dst, d_src, reinterpret_cast<const uint32_t*>(d_nn), *params, d_T, &st)) return rc;
+    if (const int rc = wf_estimate_dev(F, wf, d_dst, d_nrm, n_dst, d_src, reinterpret_cast<const uint32_t*>(d_nn), *params, d_T, &st, kind)) return rc;
     if (mem == CILHIP_MEM_HOST) {
       ST_CK(F, hipMemcpyAsync(ctrl_transforms_out, d_T, 16 * wf->n_ctrl * sizeof(float), hipMemcpyDeviceToHost, s));
       ST_CK(F, hipStreamSynchronize(s));
@@ -867,10 +1008,8 @@ extern "C" int cilhip_warp_field_estimate3f(cilhip_warp_field* wf, const float* 
   }
 }
 
-extern "C" int cilhip_warp_field_resample3f(cilhip_warp_field* wf, const float* ctrl_T, float* dense_T_out, int mem) {
-  using namespace cilhip;
-  constexpr const char* F = "warp_field_resample";
-  auto refuse = [](const char* why) { return st_fail(CILHIP_ERR_INVALID, F, why); };
+int wf_resample_entry(const char* F, WfKind kind, cilhip_warp_field* wf, const float* ctrl_T, float* dense_T_out, int mem) {
+  auto refuse = [F](const char* why) { return st_fail(CILHIP_ERR_INVALID, F, why); };
   if (!wf) return refuse("the warp field is null");
   if (!ctrl_T || !dense_T_out) return refuse("ctrl_T or dense_T_out is null");
   if (mem != CILHIP_MEM_HOST && mem != CILHIP_MEM_DEVICE) return refuse("mem: CILHIP_MEM_HOST or CILHIP_MEM_DEVICE");
@@ -883,13 +1022,31 @@ extern "C" int cilhip_warp_field_resample3f(cilhip_warp_field* wf, const float* 
     ST_CK(F, st_stage(pool, s, mem, ctrl_T, 16 * wf->n_ctrl, &d_in));
     float* d_out = dense_T_out;
     if (mem == CILHIP_MEM_HOST) ST_CK(F, pool.get(&d_out, 16 * wf->n_src));
-    if (const int rc = wf_resample_dev(F, wf, d_in, d_out)) return rc;
+    if (const int rc = wf_resample_dev(F, wf, d_in, d_out, kind)) return rc;
     if (mem == CILHIP_MEM_HOST) ST_CK(F, hipMemcpyAsync(dense_T_out, d_out, 16 * wf->n_src * sizeof(float), hipMemcpyDeviceToHost, s));
     ST_CK(F, hipStreamSynchronize(s));
     return CILHIP_OK;
   } catch (...) {
     return st_fail(CILHIP_ERR_HIP, F, "out of host memory");
   }
+}
+
+}  // namespace
+}  // namespace cilhip
+
+extern "C" int cilhip_warp_field_estimate3f(cilhip_warp_field* wf, const float* dst_xyz, const float* dst_normals, size_t n_dst, const float* src_xyz, const uint32_t* nn_idx,
+                                            int mem, const cilhip_warp_params* params, float* ctrl_transforms_out, cilhip_warp_stats* stats_or_null) {
+  return cilhip::wf_estimate_entry("warp_field_estimate", cilhip::WF_RIGID, wf, dst_xyz, dst_normals, n_dst, src_xyz, nn_idx, mem, params, ctrl_transforms_out, stats_or_null);
+}
+extern "C" int cilhip_warp_field_estimate_affine3f(cilhip_warp_field* wf, const float* dst_xyz, const float* dst_normals, size_t n_dst, const float* src_xyz, const uint32_t* nn_idx,
+                                                   int mem, const cilhip_warp_params* params, float* ctrl_transforms_out, cilhip_warp_stats* stats_or_null) {
+  return cilhip::wf_estimate_entry("warp_field_estimate_affine", cilhip::WF_AFFINE, wf, dst_xyz, dst_normals, n_dst, src_xyz, nn_idx, mem, params, ctrl_transforms_out, stats_or_null);
+}
+extern "C" int cilhip_warp_field_resample3f(cilhip_warp_field* wf, const float* ctrl_T, float* dense_T_out, int mem) {
+  return cilhip::wf_resample_entry("warp_field_resample", cilhip::WF_RIGID, wf, ctrl_T, dense_T_out, mem);
+}
+extern "C" int cilhip_warp_field_resample_affine3f(cilhip_warp_field* wf, const float* ctrl_T, float* dense_T_out, int mem) {
+  return cilhip::wf_resample_entry("warp_field_resample_affine", cilhip::WF_AFFINE, wf, ctrl_T, dense_T_out, mem);
 }
 
 extern "C" int cilhip_transform_points_per_point3f(int device, const float* T, const float* xyz, size_t n, int mem, float* out) {

@@ -18,11 +18,15 @@ hipStream_t wf_stream(cilhip_warp_field* wf);
 // one argument rule shared by the estimate entry and the loop: null = the parameters are fine
 const char* wf_params_refusal(const cilhip_warp_params* p);
 
+// the node transforms of a call: rigid (section 17.1: 6 unknowns per node, output and resample through rotation()) or affine
+// (section 17.4: 12 unknowns, output and resample as they are).  The first affine estimate grows the handle's solver scratch.
+enum WfKind { WF_RIGID = 6, WF_AFFINE = 12 };
+
 // the estimator of DESIGN.md section 17 on device-resident arrays; T_out: n_ctrl * 16 floats (column-major 4 x 4).  Synchronises.
 int wf_estimate_dev(const char* family, cilhip_warp_field* wf, const float* d_dst, const float* d_nrm_or_null, size_t n_dst, const float* d_src, const uint32_t* d_nn,
-                    const cilhip_warp_params& prm, float* d_T_out, cilhip_warp_stats* stats_or_null);
+                    const cilhip_warp_params& prm, float* d_T_out, cilhip_warp_stats* stats_or_null, WfKind kind = WF_RIGID);
 // control transforms -> one transform per source point (resampleTransforms); enqueues only
-int wf_resample_dev(const char* family, cilhip_warp_field* wf, const float* d_ctrl_T, float* d_dense_T);
+int wf_resample_dev(const char* family, cilhip_warp_field* wf, const float* d_ctrl_T, float* d_dense_T, WfKind kind = WF_RIGID);
 // out[i] = T[i] * xyz[i]; enqueues only
 int wf_transform_points_dev(const char* family, hipStream_t s, const float* d_T, const float* d_xyz, size_t n, float* d_out);
 // T[i] = T_iter[i] * T[i] for the n_ctrl control transforms; *max_delta_sq = max_i |R_iter,i - I|_F^2 + |t_iter,i|^2.  Synchronises.

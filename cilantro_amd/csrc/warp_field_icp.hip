@@ -5,17 +5,21 @@
 // (cilhip_set_source, device memory) and searches it under the identity (its exact 1-NN search), the estimator runs on the
 // device-resident matches, the control transforms are composed (T_ctrl[i] = T_iter[i] * T_ctrl[i]) and resampled.  One word comes
 // back per iteration: max_i |R_iter,i - I|_F^2 + |t_iter,i|^2.  At the end the context has the caller's source again.
+// Rigid and affine node transforms (the classes at icp_common_instances.hpp:313-314 and :322-323) share the loop: the kind goes to the
+// estimator and to the resample, and nothing else differs.
 #include "ctx.hpp"
 #include "stateless.hpp"
 #include "warp_field.hpp"
 
 #include <cmath>
 
-extern "C" int cilhip_warp_field_icp_run(cilhip_ctx* c, cilhip_warp_field* wf, const cilhip_warp_params* prm, size_t max_iter, float conv_tol, float max_sq_dist,
-                                         const float* ctrl_T0_or_null, float* ctrl_T_out, float* dense_T_out_or_null, cilhip_icp_result* out) {
-  constexpr const char* F = "warp_field_icp_run";
+namespace {
+
+// one loop for both kinds of node transform: the estimator and the resample are the only steps that differ (section 17.4, A8)
+int wf_icp_run(const char* F, WfKind kind, cilhip_ctx* c, cilhip_warp_field* wf, const cilhip_warp_params* prm, size_t max_iter, float conv_tol, float max_sq_dist,
+               const float* ctrl_T0_or_null, float* ctrl_T_out, float* dense_T_out_or_null, cilhip_icp_result* out) {
   if (!c) return st_fail(CILHIP_ERR_INVALID, F, "the context is null");
-  auto refuse = [c](int code, const char* why) { st_fail(code, F, why); return fail(c, code, st_slot().c_str()); };
+  auto refuse = [c, F](int code, const char* why) { st_fail(code, F, why); return fail(c, code, st_slot().c_str()); };
   if (!wf || !ctrl_T_out || !out) return refuse(CILHIP_ERR_INVALID, "the warp field, ctrl_T_out or out is null");
   if (const char* why = wf_params_refusal(prm)) return refuse(CILHIP_ERR_INVALID, why);
   if (!std::isfinite(conv_tol) || std::isnan(max_sq_dist)) return refuse(CILHIP_ERR_INVALID, "conv_tol or max_sq_dist is not finite");
@@ -41,7 +45,7 @@ extern "C" int cilhip_warp_field_icp_run(cilhip_ctx* c, cilhip_warp_field* wf, c
   if (const int rc = wf_unsort_target_dev(F, s, c->grid.pts, c->has_normals ? c->grid.nrm : nullptr, c->grid.n, dst, nrm)) return rc;
   if (ctrl_T0_or_null) ST_CK(F, hipMemcpyAsync(T, ctrl_T0_or_null, 16 * n_ctrl * sizeof(float), hipMemcpyHostToDevice, s));
   else if (const int rc = wf_set_identity_dev(F, s, T, n_ctrl)) return rc;
-  if (const int rc = wf_resample_dev(F, wf, T, dense)) return rc;
+  if (const int rc = wf_resample_dev(F, wf, T, dense, kind)) return rc;
 
   static const float I16[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   size_t iterations = 0, ncorr = 0;
@@ -53,10 +57,10 @@ extern "C" int cilhip_warp_field_icp_run(cilhip_ctx* c, cilhip_warp_field* wf, c
     if ((rc = cilhip_set_source(c, warped, n_src, CILHIP_MEM_DEVICE))) break;
     if ((rc = cilhip_find_correspondences(c, I16, max_sq_dist, &ncorr))) break;
     if ((rc = cilhip_get_nn(c, d_nn, nullptr, CILHIP_MEM_DEVICE))) break;
-    if ((rc = wf_estimate_dev(F, wf, dst, c->has_normals ? nrm : nullptr, n_dst, warped, d_nn, *prm, T_iter, nullptr))) break;
+    if ((rc = wf_estimate_dev(F, wf, dst, c->has_normals ? nrm : nullptr, n_dst, warped, d_nn, *prm, T_iter, nullptr, kind))) break;
     float max_delta_sq = 0.0f;
     if ((rc = wf_compose_dev(F, wf, T_iter, T, &max_delta_sq))) break;
-    if ((rc = wf_resample_dev(F, wf, T, dense))) break;
+    if ((rc = wf_resample_dev(F, wf, T, dense, kind))) break;
     last_delta = std::sqrt(max_delta_sq);
     iterations++;
     if (last_delta < conv_tol) break;
@@ -72,4 +76,15 @@ extern "C" int cilhip_warp_field_icp_run(cilhip_ctx* c, cilhip_warp_field* wf, c
   for (int i = 0; i < 16; ++i) out->T[i] = I16[i];      // (a warp field has no single transform)
   out->iterations = iterations; out->last_delta_norm = last_delta; out->last_ncorr = ncorr;
   return CILHIP_OK;
+}
+
+}  // namespace
+
+extern "C" int cilhip_warp_field_icp_run(cilhip_ctx* c, cilhip_warp_field* wf, const cilhip_warp_params* prm, size_t max_iter, float conv_tol, float max_sq_dist,
+                                         const float* ctrl_T0_or_null, float* ctrl_T_out, float* dense_T_out_or_null, cilhip_icp_result* out) {
+  return wf_icp_run("warp_field_icp_run", WF_RIGID, c, wf, prm, max_iter, conv_tol, max_sq_dist, ctrl_T0_or_null, ctrl_T_out, dense_T_out_or_null, out);
+}
+extern "C" int cilhip_warp_field_icp_run_affine(cilhip_ctx* c, cilhip_warp_field* wf, const cilhip_warp_params* prm, size_t max_iter, float conv_tol, float max_sq_dist,
+                                                const float* ctrl_T0_or_null, float* ctrl_T_out, float* dense_T_out_or_null, cilhip_icp_result* out) {
+  return wf_icp_run("warp_field_icp_run_affine", WF_AFFINE, c, wf, prm, max_iter, conv_tol, max_sq_dist, ctrl_T0_or_null, ctrl_T_out, dense_T_out_or_null, out);
 }

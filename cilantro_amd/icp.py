@@ -1017,25 +1017,35 @@ class WarpField:
     def _ck(self, rc):
         _abi.check(rc, None, self._L)
 
-    def estimate(self, dst_points, dst_normals, warped_src_points, nn_idx, params):
-        """one estimateSparseWarpFieldCombinedMetric call -> (control transforms (n_ctrl, 4, 4), capi.WarpStats)"""
+    def estimate(self, dst_points, dst_normals, warped_src_points, nn_idx, params, affine=False):
+        """one estimateSparseWarpFieldCombinedMetric call -> (control transforms (n_ctrl, 4, 4), capi.WarpStats); affine: the affine
+        overload, through cilhip_warp_field_estimate_affine3f"""
+        entry = self._L.cilhip_warp_field_estimate_affine3f if affine else self._L.cilhip_warp_field_estimate3f
         d = np.ascontiguousarray(dst_points, np.float32).reshape(-1, 3)
         n = None if dst_normals is None else np.ascontiguousarray(dst_normals, np.float32).reshape(-1, 3)
         s = np.ascontiguousarray(warped_src_points, np.float32).reshape(self.n_src, 3)
         nn = np.ascontiguousarray(nn_idx, np.uint32).reshape(self.n_src)
         out = np.zeros(16 * self.n_ctrl, np.float32)
         st = capi.WarpStats()
-        self._ck(self._L.cilhip_warp_field_estimate3f(self._h, d.ctypes.data, None if n is None else n.ctypes.data, len(d), s.ctypes.data, nn.ctypes.data, capi.MEM_HOST,
-                                                      C.byref(params), out.ctypes.data, C.byref(st)))
+        self._ck(entry(self._h, d.ctypes.data, None if n is None else n.ctypes.data, len(d), s.ctypes.data, nn.ctypes.data, capi.MEM_HOST, C.byref(params), out.ctypes.data,
+                       C.byref(st)))
         return _Ts_from_abi(out, self.n_ctrl), st
 
-    def resample(self, ctrl_transforms):
-        """resampleTransforms over the field's own lists -> (n_src, 4, 4)"""
+    def estimate_affine(self, dst_points, dst_normals, warped_src_points, nn_idx, params):
+        return self.estimate(dst_points, dst_normals, warped_src_points, nn_idx, params, affine=True)
+
+    def resample_affine(self, ctrl_transforms):
+        """resampleTransforms with Mode != Isometry: the plain blend, not polished"""
+        return self.resample(ctrl_transforms, affine=True)
+
+    def resample(self, ctrl_transforms, affine=False):
+        """resampleTransforms over the field's own lists -> (n_src, 4, 4); rigid transforms go through rotation(), affine ones do not"""
+        entry = self._L.cilhip_warp_field_resample_affine3f if affine else self._L.cilhip_warp_field_resample3f
         t = _Ts_to_abi(ctrl_transforms)
         if len(t) != 16 * self.n_ctrl:
             raise ValueError("one transform per control node is needed")
         out = np.zeros(16 * self.n_src, np.float32)
-        self._ck(self._L.cilhip_warp_field_resample3f(self._h, t.ctypes.data, out.ctypes.data, capi.MEM_HOST))
+        self._ck(entry(self._h, t.ctypes.data, out.ctypes.data, capi.MEM_HOST))
         return _Ts_from_abi(out, self.n_src)
 
 
@@ -1052,9 +1062,10 @@ def transformPoints(transforms, points, device=0):
     return out
 
 
-def resampleTransforms(old_transforms, new_to_old_map, weight_evaluator=None, device=0):
+def resampleTransforms(old_transforms, new_to_old_map, weight_evaluator=None, device=0, affine=False):
     """registration/warp_field_utilities.hpp:14-48, the list overload: per new point the old transforms blended with weights
-    eval(squared distance), through rotation(); the identity where the weights sum to 0"""
+    eval(squared distance), through rotation() -- or, for affine transforms (affine=True: the reference picks by the transform's Mode),
+    as the blend stands; the identity where the weights sum to 0"""
     old = np.asarray(old_transforms, np.float32).reshape(-1, 4, 4)
     idx, d2 = new_to_old_map[0], new_to_old_map[1]
     n_new = len(np.asarray(idx))
@@ -1062,7 +1073,7 @@ def resampleTransforms(old_transforms, new_to_old_map, weight_evaluator=None, de
     self_lists = (np.arange(len(old), dtype=np.uint32).reshape(-1, 1), np.zeros((len(old), 1), np.float32))
     wf = WarpField(n_new, len(old), (idx, d2), ev, self_lists, UnityWeightEvaluator(), device)
     try:
-        return wf.resample(old)
+        return wf.resample(old, affine)
     finally:
         wf.close()
 
@@ -1071,6 +1082,8 @@ class SimpleCombinedMetricSparseRigidWarpFieldICP3f:
     """registration/icp_common_instances.hpp (SimpleCombinedMetricSparseRigidWarpFieldICP3f) over CombinedMetricSparseWarpFieldICP
     (icp_warp_field_combined_metric_sparse.hpp); defaults :67-74.  Neighbourhood sets are (indices (n, k), squared distances (n, k))
     pairs as the k-NN mirrors return them.  Unity correspondence weights; control and regularisation weights Unity or RBF."""
+
+    _affine = False      # the node transforms: the affine classes below run the same loop through cilhip_warp_field_icp_run_affine
 
     def __init__(self, dst_points, dst_normals, src_points, src_to_ctrl_neighborhoods, num_ctrl_nodes, ctrl_regularization_neighborhoods, device=0, stream=None):
         self._device = int(device)
@@ -1161,8 +1174,9 @@ class SimpleCombinedMetricSparseRigidWarpFieldICP3f:
         wf = self._warp_field()
         t0 = _Ts_to_abi(self.transform_init_)
         ctrl, dense, res = np.zeros(16 * self.num_ctrl_nodes_, np.float32), np.zeros(16 * len(self._src), np.float32), capi.IcpResult()
-        self._ctx._ck(self._ctx._L.cilhip_warp_field_icp_run(self._ctx._h, wf._h, C.byref(self._params), self.max_iterations_, float(self.convergence_tol_),
-                                                           float(self._engine.max_distance_), t0.ctypes.data, ctrl.ctypes.data, dense.ctypes.data, C.byref(res)))
+        run = self._ctx._L.cilhip_warp_field_icp_run_affine if self._affine else self._ctx._L.cilhip_warp_field_icp_run
+        self._ctx._ck(run(self._ctx._h, wf._h, C.byref(self._params), self.max_iterations_, float(self.convergence_tol_),
+                          float(self._engine.max_distance_), t0.ctypes.data, ctrl.ctypes.data, dense.ctypes.data, C.byref(res)))
         self._engine._corr = None
         self.transform_, self.transform_dense_ = _Ts_from_abi(ctrl, self.num_ctrl_nodes_), _Ts_from_abi(dense, len(self._src))
         self.iterations_, self.last_delta_norm_, self.last_ncorr_ = int(res.iterations), np.float32(res.last_delta_norm), int(res.last_ncorr)
@@ -1196,3 +1210,18 @@ class SimpleCombinedMetricDenseRigidWarpFieldICP3f(SimpleCombinedMetricSparseRig
 
     def getDenseWarpField(self):
         return self.transform_
+
+
+class SimpleCombinedMetricSparseAffineWarpFieldICP3f(SimpleCombinedMetricSparseRigidWarpFieldICP3f):
+    """registration/icp_common_instances.hpp:322-323: the same loop with affine node transforms: 12 unknowns per
+    node, no rotation() on the way out, in the resample or in the composition.  The reference's rows carry the transformed point in the
+    linear part's coefficients; that is reproduced."""
+
+    _affine = True
+
+
+class SimpleCombinedMetricDenseAffineWarpFieldICP3f(SimpleCombinedMetricDenseRigidWarpFieldICP3f):
+    """registration/icp_common_instances.hpp:293-294: every source point its own affine control node, over the sparse entry on the lists
+    ctrl_idx[i] = i, k_ctrl = 1, Unity (tests/test_warp_affine_refs_cpu.py pins the dense affine estimator's system, :856-955, against it)"""
+
+    _affine = True

@@ -915,6 +915,37 @@ int cilhip_transform_points_per_point3f(int device, const float* T /* n * 16 */,
 int cilhip_warp_field_icp_run(cilhip_ctx* ctx, cilhip_warp_field* field, const cilhip_warp_params* params, size_t max_iter, float conv_tol,
                               float max_sq_dist, const float* ctrl_T0_or_null, float* ctrl_T_out, float* dense_T_out_or_null, cilhip_icp_result* out);
 
+/* ---- the same warp field with AFFINE node transforms ------------------------------------------------------------------------
+ * estimateSparseWarpFieldCombinedMetric's affine overload (registration/warp_field_estimation.hpp:1859-2234; the dense estimator
+ * :725-1005 is the same system on the lists ctrl_idx[i] = i, k_ctrl = 1, Unity), resampleTransforms with Mode != Isometry
+ * (registration/warp_field_utilities.hpp:14-48) and the loop of SimpleCombinedMetric{Sparse,Dense}AffineWarpFieldICP3f
+ * (icp_common_instances.hpp:293-294, :322-323).  Three entries on the SAME handle, with the signatures, parameters, statistics and
+ * refusals (codes, and before a device is touched where the rigid ones are) of their rigid siblings above.  The graph, the weights,
+ * the totals, the arcs, the CG and the no-data case are those of above; DESIGN.md section 17.4 has the contract, in short:
+ *   A1 unknowns  12 per node: the 3 x 3 linear part row-major, then t (:2005-2008); the start is the identity and t = 0
+ *   A2 blend     lin = sum_j w_ij L_j, tr = sum_j w_ij t_j in f32 and list order, both then MULTIPLIED by 1 / total_i (:2050-2063);
+ *                total_i == 0: rows of zeros (:2068-2071).  s_t = ((L0 . s) + tr), the products summed left to right
+ *   A3 rows      weight = (sqrt(w_metric) / total_i) * w_ij.  Point row eq: weight * s_t[nz] at 3 eq + nz, weight at 9 + eq, right-hand
+ *                side sqrt(w_p2p) * (d - s_t)[eq] (:2084-2099).  Plane row: (weight * n[block]) * s_t[curr] at 3 block + curr,
+ *                weight * n[curr] at 9 + curr, right-hand side ((n0 e0 + n1 e1) + n2 e2) * sqrt(w_p2pl), e = d - s_t (:2145-2163).
+ *                OBSERVATION: the linear part's coefficients carry the TRANSFORMED point s_t, not s.  That is the reference as written,
+ *                in both estimators (:2091, :2153; :881, :914): the true Jacobian at the first Gauss-Newton step (s_t == s there), not
+ *                from the second on.  It is reproduced, not corrected: these entries promise the reference's iterates
+ *   A4 arcs      twelve sqrtHuberLoss rows per arc, one per unknown, otherwise as above (:2169-2193)
+ *   A5 step      tforms += delta; converged when max over nodes |delta_node|^2 (12 components) < gn_conv_tol^2 (:2204-2219)
+ *   A6 output    the linear part and t as they are, no rotation() (:2222-2231); 4 x 4 column-major, last row 0 0 0 1
+ *   A7 resample  T_i = (sum_j w_ij T_j) * (1 / total_i) in f32 and list order, not polished; the identity where total_i == 0
+ *   A8 loop      cilhip_warp_field_icp_run with A6 / A7: T_ctrl[i] = T_iter[i] * T_ctrl[i] as a plain affine product,
+ *                last_delta_norm = sqrt(max_i(|L_iter,i - I|_F^2 + |t_iter,i|^2))
+ * The first affine estimate on a handle grows its solver scratch from 6 to 12 unknowns per node; rigid calls on the same handle give
+ * the same bytes before and afterwards.  cilhip_transform_points_per_point3f serves affine transforms as it is. */
+int cilhip_warp_field_estimate_affine3f(cilhip_warp_field* field, const float* dst_xyz, const float* dst_normals, size_t n_dst, const float* src_xyz,
+                                        const uint32_t* nn_idx, int mem, const cilhip_warp_params* params, float* ctrl_transforms_out /* n_ctrl * 16 */,
+                                        cilhip_warp_stats* stats_or_null);
+int cilhip_warp_field_resample_affine3f(cilhip_warp_field* field, const float* ctrl_T /* n_ctrl * 16 */, float* dense_T_out /* n_src * 16 */, int mem);
+int cilhip_warp_field_icp_run_affine(cilhip_ctx* ctx, cilhip_warp_field* field, const cilhip_warp_params* params, size_t max_iter, float conv_tol,
+                                     float max_sq_dist, const float* ctrl_T0_or_null, float* ctrl_T_out, float* dense_T_out_or_null, cilhip_icp_result* out);
+
 /* ---- introspection (bench / tests) ----------------------------------------------------------- */
 typedef struct {
   int nx, ny, nz;        /* grid dims */

@@ -757,29 +757,46 @@ inline std::vector<float> transformPoints(const RigidTransformSet3f& tforms, con
   return out;
 }
 
-// registration/warp_field_utilities.hpp:14-48, the list overload
-inline RigidTransformSet3f resampleTransforms(const RigidTransformSet3f& old_transforms, const NeighborhoodSet& new_to_old_map,
-                                              const WarpWeightEvaluator& weight_evaluator = WarpWeightEvaluator(WarpWeightEvaluator::Unity), int device = 0) {
+namespace internal {
+inline RigidTransformSet3f resample_transforms(bool affine, const RigidTransformSet3f& old_transforms, const NeighborhoodSet& new_to_old_map, const WarpWeightEvaluator& weight_evaluator,
+                                               int device) {
   RigidTransformSet3f out(new_to_old_map.size());
   if (out.empty() || old_transforms.empty()) return out;
   NeighborhoodSet self(old_transforms.size());
   for (size_t i = 0; i < self.size(); ++i) self[i].push_back(Neighbor{i, 0.0f});
-  internal::WarpFieldPtr f = internal::make_warp_field(device, out.size(), old_transforms.size(), new_to_old_map, weight_evaluator, self, WarpWeightEvaluator(WarpWeightEvaluator::Unity));
-  internal::check_stateless(cilhip_warp_field_resample3f(f.get(), old_transforms[0].m, out[0].m, CILHIP_MEM_HOST), "resampleTransforms");
+  WarpFieldPtr f = make_warp_field(device, out.size(), old_transforms.size(), new_to_old_map, weight_evaluator, self, WarpWeightEvaluator(WarpWeightEvaluator::Unity));
+  check_stateless((affine ? cilhip_warp_field_resample_affine3f : cilhip_warp_field_resample3f)(f.get(), old_transforms[0].m, out[0].m, CILHIP_MEM_HOST),
+                  affine ? "resampleAffineTransforms" : "resampleTransforms");
   return out;
 }
+}  // namespace internal
 
-// registration/icp_warp_field_combined_metric_sparse.hpp + icp_common_instances.hpp: SimpleCombinedMetricSparseRigidWarpFieldICP3f.
-// Unity correspondence weights; control and regularisation weights Unity or RBF (default RBF, the example sets only sigma).
-class SimpleCombinedMetricSparseRigidWarpFieldICP3f {
+// registration/warp_field_utilities.hpp:14-48, the list overload: rigid transforms are blended and taken through rotation()
+inline RigidTransformSet3f resampleTransforms(const RigidTransformSet3f& old_transforms, const NeighborhoodSet& new_to_old_map,
+                                              const WarpWeightEvaluator& weight_evaluator = WarpWeightEvaluator(WarpWeightEvaluator::Unity), int device = 0) {
+  return internal::resample_transforms(false, old_transforms, new_to_old_map, weight_evaluator, device);
+}
+// the same with Mode != Isometry: the blend as it stands.  (The reference picks by the transform type; AffineTransform3f is a typedef
+// of RigidTransform3f here, so the affine overload has a name of its own.)
+typedef RigidTransformSet3f AffineTransformSet3f;
+inline AffineTransformSet3f resampleAffineTransforms(const AffineTransformSet3f& old_transforms, const NeighborhoodSet& new_to_old_map,
+                                                     const WarpWeightEvaluator& weight_evaluator = WarpWeightEvaluator(WarpWeightEvaluator::Unity), int device = 0) {
+  return internal::resample_transforms(true, old_transforms, new_to_old_map, weight_evaluator, device);
+}
+
+// registration/icp_warp_field_combined_metric_sparse.hpp: the loop class of the four warp-field instances below, written once.  Self is
+// the instance (the setters return it); Affine picks the entry -- cilhip_warp_field_icp_run or cilhip_warp_field_icp_run_affine -- and
+// nothing else.  Unity correspondence weights; control and regularisation weights Unity or RBF (default RBF, the example sets only sigma).
+namespace internal {
+template <class Self, bool Affine>
+class CombinedMetricWarpFieldICP3f {
 public:
   using Transform = RigidTransformSet3f;
   using CorrespondenceSearchEngine = CorrespondenceSearchHIP;
   using ResidualVector = std::vector<float>;
 
-  SimpleCombinedMetricSparseRigidWarpFieldICP3f(const ConstPointsView& dst_p, const ConstPointsView& dst_n, const ConstPointsView& src_p,
-                                                const NeighborhoodSet& src_to_ctrl_neighborhoods, size_t num_ctrl_nodes,
-                                                const NeighborhoodSet& ctrl_regularization_neighborhoods, int device = 0)
+  CombinedMetricWarpFieldICP3f(const ConstPointsView& dst_p, const ConstPointsView& dst_n, const ConstPointsView& src_p, const NeighborhoodSet& src_to_ctrl_neighborhoods,
+                               size_t num_ctrl_nodes, const NeighborhoodSet& ctrl_regularization_neighborhoods, int device = 0)
       : device_(device), ctx_(internal::make_ctx(device)), engine_(ctx_.get()), src_(src_p.data(), src_p.data() + 3 * src_p.cols()),
         ctrl_lists_(src_to_ctrl_neighborhoods), reg_lists_(ctrl_regularization_neighborhoods), num_ctrl_nodes_(num_ctrl_nodes),
         transform_init_(num_ctrl_nodes), transform_(num_ctrl_nodes), transform_dense_(src_p.cols()) {
@@ -793,31 +810,31 @@ public:
   inline WarpWeightEvaluator& regularizationWeightEvaluator() { return reg_eval_; }
 
   inline float getPointToPointMetricWeight() const { return prm_.w_p2p; }
-  inline SimpleCombinedMetricSparseRigidWarpFieldICP3f& setPointToPointMetricWeight(float w) { prm_.w_p2p = w; return *this; }
+  inline Self& setPointToPointMetricWeight(float w) { prm_.w_p2p = w; return self(); }
   inline float getPointToPlaneMetricWeight() const { return prm_.w_p2pl; }
-  inline SimpleCombinedMetricSparseRigidWarpFieldICP3f& setPointToPlaneMetricWeight(float w) { prm_.w_p2pl = w; return *this; }
+  inline Self& setPointToPlaneMetricWeight(float w) { prm_.w_p2pl = w; return self(); }
   inline float getStiffnessRegularizationWeight() const { return prm_.w_reg; }
-  inline SimpleCombinedMetricSparseRigidWarpFieldICP3f& setStiffnessRegularizationWeight(float w) { prm_.w_reg = w; return *this; }
+  inline Self& setStiffnessRegularizationWeight(float w) { prm_.w_reg = w; return self(); }
   inline size_t getMaxNumberOfGaussNewtonIterations() const { return prm_.max_gn_iter; }
-  inline SimpleCombinedMetricSparseRigidWarpFieldICP3f& setMaxNumberOfGaussNewtonIterations(size_t n) { prm_.max_gn_iter = n; return *this; }
+  inline Self& setMaxNumberOfGaussNewtonIterations(size_t n) { prm_.max_gn_iter = n; return self(); }
   inline float getGaussNewtonConvergenceTolerance() const { return prm_.gn_conv_tol; }
-  inline SimpleCombinedMetricSparseRigidWarpFieldICP3f& setGaussNewtonConvergenceTolerance(float tol) { prm_.gn_conv_tol = tol; return *this; }
+  inline Self& setGaussNewtonConvergenceTolerance(float tol) { prm_.gn_conv_tol = tol; return self(); }
   inline size_t getMaxNumberOfConjugateGradientIterations() const { return prm_.max_cg_iter; }
-  inline SimpleCombinedMetricSparseRigidWarpFieldICP3f& setMaxNumberOfConjugateGradientIterations(size_t n) { prm_.max_cg_iter = n; return *this; }
+  inline Self& setMaxNumberOfConjugateGradientIterations(size_t n) { prm_.max_cg_iter = n; return self(); }
   inline float getConjugateGradientConvergenceTolerance() const { return prm_.cg_conv_tol; }
-  inline SimpleCombinedMetricSparseRigidWarpFieldICP3f& setConjugateGradientConvergenceTolerance(float tol) { prm_.cg_conv_tol = tol; return *this; }
+  inline Self& setConjugateGradientConvergenceTolerance(float tol) { prm_.cg_conv_tol = tol; return self(); }
   inline float getHuberLossBoundary() const { return prm_.huber_boundary; }
-  inline SimpleCombinedMetricSparseRigidWarpFieldICP3f& setHuberLossBoundary(float b) { prm_.huber_boundary = b; return *this; }
+  inline Self& setHuberLossBoundary(float b) { prm_.huber_boundary = b; return self(); }
 
   inline size_t getMaxNumberOfIterations() const { return max_iterations_; }
-  inline SimpleCombinedMetricSparseRigidWarpFieldICP3f& setMaxNumberOfIterations(size_t n) { max_iterations_ = n; return *this; }
+  inline Self& setMaxNumberOfIterations(size_t n) { max_iterations_ = n; return self(); }
   inline float getConvergenceTolerance() const { return convergence_tol_; }
-  inline SimpleCombinedMetricSparseRigidWarpFieldICP3f& setConvergenceTolerance(float tol) { convergence_tol_ = tol; return *this; }
+  inline Self& setConvergenceTolerance(float tol) { convergence_tol_ = tol; return self(); }
   inline const Transform& getInitialTransform() const { return transform_init_; }
-  inline SimpleCombinedMetricSparseRigidWarpFieldICP3f& setInitialTransform(const Transform& t) {
+  inline Self& setInitialTransform(const Transform& t) {
     if (t.size() != num_ctrl_nodes_) throw std::invalid_argument("setInitialTransform: one transform per control node is needed");
     transform_init_ = t;
-    return *this;
+    return self();
   }
   inline size_t getNumberOfPerformedIterations() const { return iterations_; }
   inline float getLastUpdateNorm() const { return last_delta_norm_; }
@@ -826,20 +843,20 @@ public:
   inline const Transform& getDenseWarpField() const { return transform_dense_; }   // one per source point
   inline size_t getNumberOfLastCorrespondences() const { return last_ncorr_; }      // (extension)
 
-  SimpleCombinedMetricSparseRigidWarpFieldICP3f& estimate() {
+  Self& estimate() {
     // (the weights belong to the graph: built here, with the sigmas set so far)
     internal::WarpFieldPtr f = internal::make_warp_field(device_, src_.size() / 3, num_ctrl_nodes_, ctrl_lists_, control_eval_, reg_lists_, reg_eval_);
     cilhip_icp_result r;
-    internal::check(ctx_.get(), cilhip_warp_field_icp_run(ctx_.get(), f.get(), &prm_, max_iterations_, convergence_tol_, engine_.getMaxDistance(),
-                                                         transform_init_.empty() ? nullptr : transform_init_[0].m, transform_.empty() ? nullptr : transform_[0].m,
-                                                         transform_dense_.empty() ? nullptr : transform_dense_[0].m, &r), "estimate");
+    internal::check(ctx_.get(), (Affine ? cilhip_warp_field_icp_run_affine : cilhip_warp_field_icp_run)(
+                                    ctx_.get(), f.get(), &prm_, max_iterations_, convergence_tol_, engine_.getMaxDistance(), transform_init_.empty() ? nullptr : transform_init_[0].m,
+                                    transform_.empty() ? nullptr : transform_[0].m, transform_dense_.empty() ? nullptr : transform_dense_[0].m, &r), "estimate");
     engine_.invalidateFetched();
     iterations_ = r.iterations;
     last_delta_norm_ = r.last_delta_norm;
     last_ncorr_ = r.last_ncorr;
-    return *this;
+    return self();
   }
-  inline SimpleCombinedMetricSparseRigidWarpFieldICP3f& estimate(size_t max_iter, float conv_tol) {
+  inline Self& estimate(size_t max_iter, float conv_tol) {
     max_iterations_ = max_iter;
     convergence_tol_ = conv_tol;
     return estimate();
@@ -859,7 +876,8 @@ public:
     return res;
   }
 
-private:
+protected:
+  inline Self& self() { return static_cast<Self&>(*this); }
   int device_;
   internal::CtxPtr ctx_;
   CorrespondenceSearchEngine engine_;
@@ -871,6 +889,50 @@ private:
   size_t max_iterations_ = 15, iterations_ = 0, last_ncorr_ = 0;      // icp_base.hpp:24-25
   float convergence_tol_ = 1e-5f, last_delta_norm_ = std::numeric_limits<float>::infinity();
   Transform transform_init_, transform_, transform_dense_;
+};
+}  // namespace internal
+
+// icp_common_instances.hpp: the four instances.  The dense classes are the sparse loop on the lists ctrl_idx[i] = i, k_ctrl = 1 with Unity
+// control weights: w = total = 1, and every row of the sparse system is, term for term, the dense estimator's (DESIGN.md sections 17, 17.4).
+class SimpleCombinedMetricSparseRigidWarpFieldICP3f : public internal::CombinedMetricWarpFieldICP3f<SimpleCombinedMetricSparseRigidWarpFieldICP3f, false> {
+public:
+  using CombinedMetricWarpFieldICP3f::CombinedMetricWarpFieldICP3f;
+};
+// :322-323.  12 unknowns per node, no rotation() anywhere; the rows' linear part carries the transformed point, as the reference's do.
+class SimpleCombinedMetricSparseAffineWarpFieldICP3f : public internal::CombinedMetricWarpFieldICP3f<SimpleCombinedMetricSparseAffineWarpFieldICP3f, true> {
+public:
+  using Transform = AffineTransformSet3f;
+  using CombinedMetricWarpFieldICP3f::CombinedMetricWarpFieldICP3f;
+};
+
+namespace internal {
+inline NeighborhoodSet own_node_lists(size_t n) {
+  NeighborhoodSet own(n);
+  for (size_t i = 0; i < n; ++i) own[i].push_back(Neighbor{i, 0.0f});
+  return own;
+}
+template <class Self, bool Affine>
+class DenseWarpFieldICP3f : public CombinedMetricWarpFieldICP3f<Self, Affine> {
+  using Base = CombinedMetricWarpFieldICP3f<Self, Affine>;
+
+public:
+  DenseWarpFieldICP3f(const ConstPointsView& dst_p, const ConstPointsView& dst_n, const ConstPointsView& src_p, const NeighborhoodSet& regularization_neighborhoods, int device = 0)
+      : Base(dst_p, dst_n, src_p, own_node_lists(src_p.cols()), src_p.cols(), regularization_neighborhoods, device) {
+    Base::control_eval_.setKind(WarpWeightEvaluator::Unity);
+  }
+  WarpWeightEvaluator& controlWeightEvaluator() = delete;      // (the dense warp field has no control weights)
+  inline const typename Base::Transform& getDenseWarpField() const { return Base::getTransform(); }
+};
+}  // namespace internal
+
+// :284-285 and :293-294
+class SimpleCombinedMetricDenseRigidWarpFieldICP3f : public internal::DenseWarpFieldICP3f<SimpleCombinedMetricDenseRigidWarpFieldICP3f, false> {
+public:
+  using DenseWarpFieldICP3f::DenseWarpFieldICP3f;
+};
+class SimpleCombinedMetricDenseAffineWarpFieldICP3f : public internal::DenseWarpFieldICP3f<SimpleCombinedMetricDenseAffineWarpFieldICP3f, true> {
+public:
+  using DenseWarpFieldICP3f::DenseWarpFieldICP3f;
 };
 
 #ifdef CILANTRO_HIP_HAVE_EIGEN

@@ -3,7 +3,7 @@
 beside the only route that existed before it, in the same run: lists and correspondences on the host, the scipy assembly of
 tests/_warp_refs.py in f32, the explicit At At^T product, CG on the product.
 
-    python tools/warp_field_bench.py [--reps 3] [--out profiles/warp_field_bench.json] [--cases frame_1,surface_1m]
+    python tools/warp_field_bench.py [--reps 3] [--out profiles/warp_field_bench.json] [--cases frame_1,surface_1m] [--transform rigid|affine]
 
 Cases: frame_1 (tests/golden/frames_full.npz p1 with its normals) after gridDownsample(0.005), against a bent copy of itself, control
 nodes from gridDownsample(0.025) of the source, k = 4 / 8, the example's parameters (examples/non_rigid_icp.cpp:41-82); a 1M-point
@@ -17,7 +17,12 @@ and for the host route, once: assembly, product, one CG iteration (a sparse matr
 solve.  For one CG iteration the bytes it must move (the rows twice, the lists twice, u written and read, both transposed lists, the arcs'
 derivatives twice, four vectors of 6 n_ctrl) and the fraction of the 6.29 TB/s a float4 copy reaches on this part are given -- at the
 example's size the working set lies in L2 and the iteration is three dependent launches, so that fraction says nothing about the kernels
-there and the JSON says so.  No ratio is promised or asserted.  Needs a GPU."""
+there and the JSON says so.  No ratio is promised or asserted.  Needs a GPU.
+
+--transform affine times the same quantities for the affine entries (12 unknowns per node, a 12-float record per
+source point) beside the scipy route of tests/_warp_affine_refs.py, with w_reg = 1 and at most 1000 CG iterations (at the example's
+w_reg = 200 the affine system does not meet 1e-5 within the example's 500 iterations in f32), and writes them under the key "affine" of
+the same JSON file, leaving the rigid rows as they are."""
 import argparse
 import ctypes as C
 import json
@@ -50,11 +55,15 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "warp_field_bench.json"))
     ap.add_argument("--cases", default="frame_1,surface_1m")
     ap.add_argument("--host-route-max-points", type=int, default=200000, help="the scipy route is skipped above this many source points")
+    ap.add_argument("--transform", choices=("rigid", "affine"), default="rigid")
     a = ap.parse_args()
+    affine = a.transform == "affine"
+    nu = 12 if affine else 6
     import torch
 
     if not torch.cuda.is_available():
         raise SystemExit("tools/warp_field_bench.py needs a GPU: there is no CPU path to time")
+    import _warp_affine_refs as WA
     import _warp_refs as W
     from cilantro_amd import capi, grid_downsampler as gd, synthetic
     from cilantro_amd.icp import Context, WarpField, RBFKernelWeightEvaluator
@@ -98,14 +107,15 @@ def main():
         def params(**kw):
             p = capi.WarpParams()
             capi.load().cilhip_warp_default_params(C.byref(p))
-            base = dict(w_p2p=0.0, w_p2pl=1.0, w_reg=200.0, huber_boundary=1e-2, max_gn_iter=1, gn_conv_tol=5e-4, max_cg_iter=500, cg_conv_tol=1e-5)
+            base = dict(w_p2p=0.0, w_p2pl=1.0, w_reg=1.0 if affine else 200.0, huber_boundary=1e-2, max_gn_iter=1, gn_conv_tol=5e-4, max_cg_iter=1000 if affine else 500,
+                        cg_conv_tol=1e-5)
             base.update(kw)
             for k, v in base.items():
                 setattr(p, k, v)
             return p
 
         def est(p):
-            return lambda: wf.estimate(dst, dst_n, src, nn, p)
+            return lambda: wf.estimate(dst, dst_n, src, nn, p, affine=affine)
 
         # (host arrays: every call also uploads the clouds -- measured alone, below, and reported beside the times)
         def upload():
@@ -121,7 +131,8 @@ def main():
         idx = np.asarray(s2c[0])
         valid, n_arcs = int((idx >= 0).sum()), int((np.asarray(reg[0])[:, 1:] >= 0).sum())
         matched = int((nn != capi.NONE_IDX).sum())
-        cg_bytes = 2 * 96 * matched + 2 * 8 * valid + 2 * 16 * n_src + 4 * valid + 2 * 24 * n_arcs + 2 * 24 * n_arcs + 8 * n_arcs + 8 * n_arcs + 4 * 24 * n_ctrl
+        # (the record is 96 B per point, 48 B with affine transforms; an arc's derivatives and u are 4 nu B each, a vector 4 nu n_ctrl B)
+        cg_bytes = 2 * (48 if affine else 96) * matched + 2 * 8 * valid + 2 * 16 * n_src + 4 * valid + 2 * 4 * nu * n_arcs + 2 * 4 * nu * n_arcs + 8 * n_arcs + 8 * n_arcs + 4 * 4 * nu * n_ctrl
         cg_ms = (cg16 - cg8) / 8.0
         row = {"source_points": n_src, "target_points": len(dst), "control_nodes": n_ctrl, "arcs": n_arcs, "matches": matched, "create_ms": create_ms, "search_ms": search_ms,
                "upload_of_the_three_clouds_ms": upload_ms, "linearise_ms": lin_ms, "cg_iteration_ms": cg_ms, "estimate_ms": est_ms, "estimate_cg_iterations": int(st.cg_iterations_total),
@@ -130,9 +141,12 @@ def main():
         if n_src <= a.host_route_max_points:
             g = W.Graph(n_ctrl, np.where(idx < 0, W.NONE, idx).astype(np.uint32), s2c[1], W.RBF, 0.5 * res, np.where(np.asarray(reg[0]) < 0, W.NONE, reg[0]).astype(np.uint32), reg[1], W.RBF,
                         3.0 * res)
-            p = W.Params(w_p2p=0.0, w_p2pl=1.0, w_reg=200.0, huber_boundary=1e-2, max_gn_iter=1, gn_conv_tol=5e-4, max_cg_iter=500, cg_conv_tol=1e-5)
+            p = W.Params(w_p2p=0.0, w_p2pl=1.0, w_reg=1.0 if affine else 200.0, huber_boundary=1e-2, max_gn_iter=1, gn_conv_tol=5e-4, max_cg_iter=1000 if affine else 500, cg_conv_tol=1e-5)
             t0 = time.perf_counter()
-            At, b, _ = W.assemble(g, np.float32, dst, dst_n, src, nn, np.zeros(6 * n_ctrl, np.float32), p, sort=True)
+            if affine:
+                At, b, _ = WA.assemble(g, np.float32, dst, dst_n, src, nn, WA.identity_start(n_ctrl, np.float32), p, sort=True)
+            else:
+                At, b, _ = W.assemble(g, np.float32, dst, dst_n, src, nn, np.zeros(6 * n_ctrl, np.float32), p, sort=True)
             t1 = time.perf_counter()
             AtA = (At @ At.T).tocsc()
             Atb = At @ b
@@ -148,6 +162,13 @@ def main():
         wf.close()
         ctx.close()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    if affine:      # the rigid rows stay as they are: the affine ones go under a key of their own
+        kept = {}
+        if os.path.exists(a.out):
+            with open(a.out) as fh:
+                kept = json.load(fh)
+        kept["affine"] = {k: doc[k] for k in ("device", "reps", "results")}
+        doc = kept
     with open(a.out, "w") as fh:
         json.dump(doc, fh, indent=1)
         fh.write("\n")
