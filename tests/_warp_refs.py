@@ -525,3 +525,97 @@ def make_case(n_src=3000, n_dst=4000, res=0.07, k_ctrl=4, k_reg=8, amplitude=0.0
     g = Graph(len(ctrl), ctrl_idx, ctrl_d2, ctrl_kernel, cs, reg_idx, reg_d2, reg_kernel, rs)
     return dict(src=src, dst=dst, dst_n=dst_n, ctrl=ctrl, ctrl_idx=ctrl_idx, ctrl_d2=ctrl_d2, reg_idx=reg_idx, reg_d2=reg_d2, n_ctrl=len(ctrl), graph=g, ctrl_kernel=ctrl_kernel,
                 reg_kernel=reg_kernel, ctrl_sigma=cs, reg_sigma=rs, res=res, max_sq=F((0.8 * res) ** 2))
+
+
+# ---- a graph that scales: lists from a lattice, no all-pairs temporary -----------------------------------------------------------
+def d2_pairs(q, p):
+    """d2_pinned for aligned pairs: (dx dx + dy dy) + dz dz in f32, element i of q against element i of p"""
+    d = np.asarray(q, F) - np.asarray(p, F)
+    return ((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]).astype(F)
+
+
+def surface(x, y):
+    """the height field of cilantro_amd/synthetic.py make_surface (extent 1) at given x, y, f64 -> (z, unit normals)"""
+    x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+    k1, k2 = 2.0 * np.pi * 0.8, 2.0 * np.pi * 0.6
+    z = 0.12 * np.sin(k1 * x) * np.cos(k2 * y) + 0.05 * np.cos(1.7 * k1 * x + 0.9 * k2 * y)
+    zx = 0.12 * k1 * np.cos(k1 * x) * np.cos(k2 * y) - 0.05 * 1.7 * k1 * np.sin(1.7 * k1 * x + 0.9 * k2 * y)
+    zy = -0.12 * k2 * np.sin(k1 * x) * np.sin(k2 * y) - 0.05 * 0.9 * k2 * np.sin(1.7 * k1 * x + 0.9 * k2 * y)
+    n = np.stack([-zx, -zy, np.ones_like(z)], -1)
+    return z, n / np.linalg.norm(n, axis=-1, keepdims=True)
+
+
+def lattice_offsets(count):
+    """the first `count` lattice steps (dx, dy) != (0, 0) by ascending dx^2 + dy^2, then dy, then dx: the 4-neighbourhood, the diagonals, ..."""
+    r = int(np.ceil(np.sqrt(count))) + 1      # (the disc of this radius holds more than `count` steps and lies inside the window)
+    steps = sorted(((dx * dx + dy * dy, dy, dx) for dx in range(-r, r + 1) for dy in range(-r, r + 1) if dx or dy))
+    return [(dx, dy) for _, dy, dx in steps[:count]]
+
+
+def lattice_reg_lists(nx, ny, k_reg, ctrl):
+    """row i = [i, the lattice neighbours of node i in the order of lattice_offsets...], padded with NONE where the lattice ends (ragged
+    at the border); d2 through the pinned expression for the listed pairs only"""
+    n = nx * ny
+    ix, iy = np.arange(n) % nx, np.arange(n) // nx
+    idx = np.full((n, k_reg), NONE, np.uint32)
+    idx[:, 0] = np.arange(n)
+    fill = np.ones(n, np.int64)
+    for dx, dy in lattice_offsets(k_reg - 1):
+        jx, jy = ix + dx, iy + dy
+        ok = (jx >= 0) & (jx < nx) & (jy >= 0) & (jy < ny)
+        idx[np.nonzero(ok)[0], fill[ok]] = (jy * nx + jx)[ok]
+        fill[ok] += 1
+    d2 = np.zeros((n, k_reg), F)
+    live = idx != NONE
+    rows = np.broadcast_to(np.arange(n)[:, None], idx.shape)
+    d2[live] = d2_pairs(ctrl[rows[live]], ctrl[idx[live].astype(np.int64)])
+    return idx, d2
+
+
+def nearest_node_lists(ctrl, pts, k):
+    """knn_lists(ctrl, pts, k) without the all-pairs temporary: candidates from a k-d tree over the nodes, ordered by the pinned f32 d2,
+    ties by lowest index.  (The tree works in f64: it hands over k + 6 candidates, so a pair of near-equal distances that f32 orders
+    the other way is still inside.)"""
+    from scipy.spatial import cKDTree
+
+    ctrl, pts = np.asarray(ctrl, F), np.asarray(pts, F)
+    kq = min(len(ctrl), k + 6)
+    cand = cKDTree(ctrl.astype(np.float64)).query(pts.astype(np.float64), k=kq)[1].reshape(len(pts), kq).astype(np.int64)
+    dd = d2_pairs(pts[:, None, :], ctrl[cand])
+    order = np.lexsort((cand, dd), axis=1)[:, :k]
+    kk = order.shape[1]
+    idx, d2 = np.full((len(pts), k), NONE, np.uint32), np.zeros((len(pts), k), F)
+    idx[:, :kk], d2[:, :kk] = np.take_along_axis(cand, order, 1), np.take_along_axis(dd, order, 1)
+    return idx, d2
+
+
+def make_lattice_case(nx, ny, k_ctrl, k_reg, extra=0, seed=0, amplitude=0.004, ctrl_kernel=RBF, reg_kernel=RBF, jitter=0.3, unmatched_every=11):
+    """make_case's dict for an nx x ny lattice of control nodes on the same curved surface (spacing h = 1 / max(nx, ny), node i at column
+    i % nx, row i // nx), in time and memory linear in the sizes.  The lists are input data to cilhip_warp_field_create and need not be
+    a k-NN of anything: the regularisation rows are the lattice neighbourhoods (lattice_reg_lists), the control lists each source
+    point's k_ctrl nearest nodes (nearest_node_lists).  Source: the nodes moved by up to jitter h in x and y (and 0.05 h off the
+    surface), then `extra` points spread over the lattice's extent.  Target: one point per source point, 0.2 h away in x and y on the
+    surface, bent by `amplitude`, with the surface's normal; nn[i] = i except every `unmatched_every`-th from 5 on, which is NONE (the
+    correspondences are data too).  Sigmas as the example's: 0.5 h and 3 h."""
+    from cilantro_amd import synthetic
+
+    n = nx * ny
+    h = 1.0 / max(nx, ny)
+    rng = np.random.RandomState(seed)
+    gx, gy = (np.arange(n) % nx + 0.5) * h, (np.arange(n) // nx + 0.5) * h
+    ctrl = np.stack([gx, gy, surface(gx, gy)[0]], 1).astype(F)
+    sx = np.concatenate([gx + jitter * h * rng.uniform(-1, 1, n), rng.uniform(0, nx * h, extra)])
+    sy = np.concatenate([gy + jitter * h * rng.uniform(-1, 1, n), rng.uniform(0, ny * h, extra)])
+    src = np.stack([sx, sy, surface(sx, sy)[0] + 0.05 * h * rng.uniform(-1, 1, len(sx))], 1).astype(F)
+    tx, ty = sx + 0.2 * h * rng.uniform(-1, 1, len(sx)), sy + 0.2 * h * rng.uniform(-1, 1, len(sx))
+    tz, dst_n = surface(tx, ty)
+    dst = synthetic.bend(np.stack([tx, ty, tz], 1).astype(F), amplitude)
+    nn = np.arange(len(src), dtype=np.uint32)
+    if unmatched_every:
+        nn[5::unmatched_every] = NONE
+    ctrl_idx, ctrl_d2 = nearest_node_lists(ctrl, src, k_ctrl)
+    reg_idx, reg_d2 = lattice_reg_lists(nx, ny, k_reg, ctrl)
+    cs, rs = F(0.5 * h), F(3.0 * h)
+    g = Graph(n, ctrl_idx, ctrl_d2, ctrl_kernel, cs, reg_idx, reg_d2, reg_kernel, rs)
+    return dict(src=src, dst=dst, dst_n=np.ascontiguousarray(dst_n, F), ctrl=ctrl, ctrl_idx=ctrl_idx, ctrl_d2=ctrl_d2, reg_idx=reg_idx, reg_d2=reg_d2, n_ctrl=n, graph=g,
+                ctrl_kernel=ctrl_kernel, reg_kernel=reg_kernel, ctrl_sigma=cs, reg_sigma=rs, res=F(h), max_sq=F((3.0 * h) ** 2), nn=nn, nx=nx, ny=ny)

@@ -163,6 +163,35 @@ def test_resample_is_the_plain_blend(case):
     assert np.abs(A.readback(A.to_transforms(case["tf"], D)).reshape(-1) - case["tf"]).max() == 0
 
 
+@pytest.mark.parametrize("holes", [False, True])
+@pytest.mark.parametrize("dtype, tol", [(D, 1e-13), (F, 2e-6)])
+def test_lattice_graph_vectorised_assembly_equals_the_literal_loops(dtype, tol, holes):
+    """the graphs of tests/test_gpu_warp_field_edges.py (_warp_refs.make_lattice_case; tests/test_warp_refs_cpu.py pins its lists):
+    ragged rows as they come, then with NONE in the middle of both kinds of list, a row without its owner and a matched source point
+    that names no control node -- its rows are empty and its entries of b are 0 (:1924-1933, :2059-2071)"""
+    c = W.make_lattice_case(7, 5, 3, 5, extra=45, seed=3)
+    tf = A.identity_start(35, D) + (np.random.RandomState(8).standard_normal((35, 12)) * np.array([0.02] * 9 + [0.004] * 3)).reshape(-1)
+    g = c["graph"]
+    if holes:
+        ci, ri = c["ctrl_idx"].copy(), c["reg_idx"].copy()
+        ci[::3, 1] = W.NONE
+        ci[2] = W.NONE
+        ri[::4, 2] = W.NONE
+        ri[9, 0] = W.NONE
+        g = W.Graph(35, ci, c["ctrl_d2"], W.RBF, c["ctrl_sigma"], ri, c["reg_d2"], W.RBF, c["reg_sigma"])
+        assert g.total[2] == 0 and c["nn"][2] != W.NONE
+    args = (g, dtype, c["dst"], c["dst_n"], c["src"], c["nn"], tf, prm())
+    At, b, info = A.assemble(*args)
+    M, bl = A.assemble_literal(*args)
+    assert info["matches"] == 80 - 7 and info["n_reg_eq"] == 12 * len(g.arc_s) and M.shape == At.T.shape
+    assert np.abs(At.T.toarray() - M).max() <= tol * np.abs(M).max()
+    assert np.abs(b - bl).max() <= tol * max(np.abs(bl).max(), 1e-30)
+    if holes:
+        pos = int((c["nn"][:2] != W.NONE).sum())
+        rows = list(range(3 * pos, 3 * pos + 3)) + [info["n_pt_eq"] + pos]
+        assert not M[rows].any() and not bl[rows].any()
+
+
 def test_the_findings_the_gpu_cases_are_built_on():
     """On the GPU tests' pair (make_case(): 3 000 / 4 000 points, 286 nodes, 2 002 arcs), the restatements alone.
     The example's w_reg = 200 is unfit for affine solve tests: at max_cg_iter = 500, cg_conv_tol = 1e-5 the f32 restatement hits the cap

@@ -140,6 +140,96 @@ def test_estimate_reduces_the_plane_residual_and_f32_follows_f64(case):
     assert np.abs(out[F] - out[D]).max() <= 1e-3 * np.abs(out[D]).max()
 
 
+# ---- the lattice builder of tests/test_gpu_warp_field_edges.py -------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def lattice():
+    c = W.make_lattice_case(7, 5, 3, 5, extra=45, seed=3)
+    c["tf"] = (np.random.RandomState(8).standard_normal((c["n_ctrl"], 6)) * np.array([0.02, 0.02, 0.02, 0.004, 0.004, 0.004])).reshape(-1)
+    return c
+
+
+def test_lattice_case_shape(lattice):
+    c = lattice
+    assert c["n_ctrl"] == 35 and len(c["src"]) == len(c["dst"]) == len(c["dst_n"]) == 80 and c["ctrl_idx"].shape == (80, 3) and c["reg_idx"].shape == (35, 5)
+    assert np.abs(np.linalg.norm(c["dst_n"], axis=1) - 1).max() < 1e-6
+    assert (c["nn"][5::11] == W.NONE).all() and (np.delete(c["nn"], np.arange(5, 80, 11)) == np.delete(np.arange(80), np.arange(5, 80, 11))).all()
+    assert W.lattice_offsets(4) == [(0, -1), (-1, 0), (1, 0), (0, 1)] and len(set(W.lattice_offsets(31))) == 31
+    assert max(dx * dx + dy * dy for dx, dy in W.lattice_offsets(31)) == 10      # (none nearer is left out: 36 steps have a norm^2 <= 10, 28 one <= 9)
+    # the matches are real ones: the target point stands within the case's search radius of its source point
+    m = c["nn"] != W.NONE
+    assert (W.d2_pairs(c["src"][m], c["dst"][c["nn"][m]]) < c["max_sq"]).all()
+
+
+@pytest.mark.parametrize("k", [1, 3, 32])
+def test_lattice_control_lists_equal_knn_lists(k):
+    """wherever the listed distances and the first one left out are distinct, in the pinned f32 expression"""
+    c = W.make_lattice_case(20, 15, k, 2, extra=300, seed=31)
+    idx, d2 = W.knn_lists(c["ctrl"], c["src"], k)
+    full = np.sort(W.d2_pinned(c["src"], c["ctrl"]), axis=1)[:, :k + 1]
+    distinct = (np.diff(full, axis=1) > 0).all(1)
+    assert distinct.mean() > 0.9
+    assert (c["ctrl_idx"][distinct] == idx[distinct]).all() and (c["ctrl_d2"][distinct] == d2[distinct]).all()
+    assert (np.sort(c["ctrl_idx"], axis=1) == np.sort(idx, axis=1)).mean() > 0.99      # (a tie may swap two equal distances, no more)
+    small = W.make_lattice_case(2, 1, 4, 5, extra=3, seed=1)      # lists wider than the lattice: padded
+    assert (small["ctrl_idx"][:, 2:] == W.NONE).all() and (np.sort(small["ctrl_idx"][:, :2], axis=1) == [0, 1]).all() and (small["ctrl_d2"][:, 2:] == 0).all()
+
+
+def test_lattice_regularisation_rows(lattice):
+    """row i = [i, lattice neighbours..., NONE...], ragged at the border; the listed d2 are the pinned ones; where the four lattice
+    neighbours are nearer than every other node (the surface is curved) the row is knn_lists' row as a set"""
+    c = lattice
+    ri, rd = c["reg_idx"], c["reg_d2"]
+    Dm = W.d2_pinned(c["ctrl"], c["ctrl"])
+    assert (ri[:, 0] == np.arange(35)).all() and (rd[:, 0] == 0).all()
+    count = (ri != W.NONE).sum(1)
+    assert sorted(set(count)) == [3, 4, 5] and (count == 3).sum() == 4 and (count == 5).sum() == 5 * 3      # corners, edges, interior
+    knn = W.knn_lists(c["ctrl"], c["ctrl"], 5)[0]
+    same = 0
+    for i in range(35):
+        row = ri[i, :count[i]].astype(np.int64)
+        assert (ri[i, count[i]:] == W.NONE).all() and (rd[i, count[i]:] == 0).all()      # padding last
+        assert all(abs(j % 7 - i % 7) + abs(j // 7 - i // 7) == 1 for j in row[1:])
+        assert (rd[i, :count[i]] == Dm[i, row]).all()
+        others = np.setdiff1d(np.arange(35), row)
+        if count[i] == 5 and Dm[i, row].max() < Dm[i, others].min():
+            same += 1
+            assert set(row) == set(knn[i].astype(np.int64))
+    assert same >= 8
+    g = c["graph"]
+    assert len(g.arc_s) == (count - 1).sum() == 2 * (6 * 5 + 7 * 4)      # every lattice edge twice: once from either end
+
+
+@pytest.mark.parametrize("dtype, tol", [(D, 1e-13), (F, 2e-6)])
+def test_lattice_graph_vectorised_assembly_equals_the_literal_loops(lattice, dtype, tol):
+    c = lattice
+    args = (c["graph"], dtype, c["dst"], c["dst_n"], c["src"], c["nn"], c["tf"], prm())
+    At, b, info = W.assemble(*args)
+    A, bl = W.assemble_literal(*args)
+    assert info["matches"] == 80 - 7 and A.shape == At.T.shape
+    assert np.abs(At.T.toarray() - A).max() <= tol * np.abs(A).max()
+    assert np.abs(b - bl).max() <= tol * max(np.abs(bl).max(), 1e-30)
+
+
+def test_lists_with_holes_and_empty_lists_assemble_as_the_literal_loops(lattice):
+    """NONE in the middle of both kinds of list, a row without its owner, a matched source point with no control node at all: the
+    literal loops skip what is not there, the point's rows are empty and its entries of b are 0 (:1456-1465, :1593-1596, :1687-1690)"""
+    c = lattice
+    ci, ri = c["ctrl_idx"].copy(), c["reg_idx"].copy()
+    ci[::3, 1] = W.NONE
+    ci[2] = W.NONE
+    ri[::4, 2] = W.NONE
+    ri[9, 0] = W.NONE
+    g = W.Graph(35, ci, c["ctrl_d2"], W.RBF, c["ctrl_sigma"], ri, c["reg_d2"], W.RBF, c["reg_sigma"])
+    assert g.total[2] == 0 and c["nn"][2] != W.NONE and (9, 10) not in g.directed and (10, 9) in g.directed
+    args = (g, D, c["dst"], c["dst_n"], c["src"], c["nn"], c["tf"], prm())
+    At, b, info = W.assemble(*args)
+    A, bl = W.assemble_literal(*args)
+    assert np.abs(At.T.toarray() - A).max() <= 1e-13 * np.abs(A).max() and np.abs(b - bl).max() <= 1e-13 * np.abs(bl).max()
+    pos = int((c["nn"][:2] != W.NONE).sum())      # point 2's place among the matches
+    rows = list(range(3 * pos, 3 * pos + 3)) + [info["n_pt_eq"] + pos]
+    assert not A[rows].any() and not b[rows].any()
+
+
 def test_utilities(case):
     g = case["graph"]
     tf = case["tf"]
