@@ -111,7 +111,10 @@ def test_the_box_of_the_example():
     assert V[2, 0] == 1 and V[1, 1] == 1 and np.linalg.det(V.astype(F64)) > 0
 
 
-@pytest.mark.parametrize("D,n", [(1, 3), (2, 257), (3, 65537), (7, 256), (16, 255)])
+PCA_TRIP = 2048 * 256      # k_pca_project / k_pca_reconstruct: sp_grid(m, 2048) blocks of SP_THREADS = 256 lanes, a row per lane and trip
+
+
+@pytest.mark.parametrize("D,n", [(1, 3), (2, 257), (3, 65537), (7, 256), (16, 255), (3, 600001)])      # 600 001: 75 713 rows in a second trip
 def test_project_and_reconstruct(D, n):
     import torch
 
@@ -132,6 +135,11 @@ def test_project_and_reconstruct(D, n):
     err = float(np.abs(back.astype(F64) - x.astype(F64)).max())
     print(f"D {D} n {n}: round trip error {err:.3e} bound {bound:.3e}")
     assert err <= bound
+    if n > PCA_TRIP:      # a row of the last trip is as accurate as one of the first: the same bound on its own rows, the same bits as the restatement
+        last = float(np.abs(back[PCA_TRIP:].astype(F64) - x[PCA_TRIP:].astype(F64)).max())
+        print(f"rows {PCA_TRIP} .. {n - 1}: round trip error {last:.3e}")
+        assert last <= bound and y[PCA_TRIP:].tobytes() == R.project(x[PCA_TRIP:], mean, V, D).tobytes()
+        assert back[PCA_TRIP:].tobytes() == R.reconstruct(y[PCA_TRIP:], mean, V).tobytes() and np.isfinite(back[PCA_TRIP:]).all()
     with pytest.raises(capi.CilhipError):
         p.project(x, D + 1)
 
