@@ -396,3 +396,114 @@ def projective_search_literal(dst, src, T, max_sq_dist, K=None, w=640, h=480, E=
             if v < F(max_sq_dist):
                 nn[i], val[i] = index[ind], v
     return nn, val
+
+
+# ---- crafted scenes for the projective search (tests/test_gpu_projective_edges.py; pinned on the CPU in test_projective_refs_cpu.py) ----
+TIE_K = np.array([[4, 0, 3.5], [0, 4, 2.5], [0, 0, 1]], F)       # every entry dyadic: with z a power of two u and v are exact in f32
+EDGE_K = np.array([[4, 0, 0], [0, 4, 0], [0, 0, 1]], F)          # the principal point at pixel (0, 0): u = 4 x / z with no sum at all
+
+
+def tie_scene(w=8, h=6, G=64, seed=0, K=TIE_K):
+    """-> (points (w h (G + 1), 3), group (same length): the pixel whose minimal-depth group the point belongs to, -1 for the far points).
+    Per pixel G points at ONE depth (1 or 2, alternating with (x + y) % 2) on a 1/64-pixel lattice strictly inside the pixel's footprint
+    (|du|, |dv| <= 31/64; the two opposite corners always among them, so every group spans 62/64 of the footprint on both axes), and one
+    farther point at z = 4 on the centre ray, which must lose; one random permutation over the whole array, so that the index order has
+    nothing to do with where a point lies.  All arithmetic is exact: u, v are multiples of 1/64, (u - cx) z / fx of 1/256."""
+    rng = np.random.default_rng(seed)
+    K = np.asarray(K, F)
+    fx, fy, cx, cy = float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
+    pts, grp = [], []
+    for y in range(h):
+        for x in range(w):
+            z = 1.0 if (x + y) % 2 == 0 else 2.0
+            sites = np.concatenate([[0, 63 * 63 - 1], 1 + rng.choice(63 * 63 - 2, G - 2, replace=False)])      # (the two corners first)
+            du, dv = (sites % 63 - 31) / 64.0, (sites // 63 - 31) / 64.0
+            pts.append(np.stack([(x + du - cx) / fx * z, (y + dv - cy) / fy * z, np.full(G, z)], axis=1))
+            pts.append(np.array([[(x - cx) / fx * 4.0, (y - cy) / fy * 4.0, 4.0]]))
+            grp += [y * w + x] * G + [-1]
+    pts, grp = np.concatenate(pts), np.array(grp, np.int64)
+    assert np.array_equal(pts.astype(F).astype(np.float64), pts)
+    perm = rng.permutation(pts.shape[0])
+    return pts[perm].astype(F), grp[perm]
+
+
+def computed_uv(xyz, K):
+    """P2 for camera-frame points, by project()'s arithmetic -> (u, v) f32"""
+    c, K = np.asarray(xyz, F).reshape(-1, 3), np.asarray(K, F)
+    with np.errstate(all="ignore"):
+        inv_z = F(1.0) / c[:, 2]
+        return (inv_z * dot3(K[0, 0], K[0, 1], K[0, 2], c[:, 0], c[:, 1], c[:, 2]), inv_z * dot3(K[1, 0], K[1, 1], K[1, 2], c[:, 0], c[:, 1], c[:, 2]))
+
+
+def _coordinate_for(want, axis, other, z, K):
+    """the f32 coordinate on `axis` (0: x, 1: y) at depth z whose COMPUTED projection is exactly `want`, the other axis fixed at `other`;
+    searched among the neighbours of the generating formula's value, None if none of them gives it"""
+    K = np.asarray(K, F)
+    x = F((float(want) - float(K[axis, 2])) / float(K[axis, axis]) * float(z))
+    cands = [x]
+    lo = hi = x
+    for _ in range(64):
+        lo, hi = np.nextafter(lo, F(-np.inf)), np.nextafter(hi, F(np.inf))
+        cands += [lo, hi]
+    for cnd in cands:
+        p = np.array([[cnd, other, z]] if axis == 0 else [[other, cnd, z]], F)
+        if computed_uv(p, K)[axis][0] == F(want) and np.signbit(computed_uv(p, K)[axis][0]) == np.signbit(F(want)):
+            return cnd
+    return None
+
+
+def boundary_values(n):
+    """the projections rule P3 decides at the edges of an axis of n pixels"""
+    return [F(-0.5), np.nextafter(F(-0.5), F(0)), F(-0.25), F(0.5), F(1.5), F(2.5), F(n - 1), np.nextafter(F(n - 0.5), F(0)), F(n - 0.5)]
+
+
+def llround_exact(u):
+    """llround of one finite f32 by integer arithmetic on its exact value (ties away from zero)"""
+    from fractions import Fraction as Q
+
+    q = abs(Q(float(u))) + Q(1, 2)
+    r = q.numerator // q.denominator
+    return -r if float(u) < 0 else r
+
+
+def boundary_points(w, h, K=EDGE_K):
+    """-> (points, pixel): points of depth 1, 2 and 0.5 whose COMPUTED u (then v) is exactly each of boundary_values(), the other axis on
+    the centre of an inner pixel; then points the rules must reject whatever their ray: c_z of +0, -0, the smallest denormal, a negative
+    number, NaN, +inf; |u| or |v| at 2^31, the largest f32 below 2^32, 2^32, 2^40, +-inf out of a finite x; a NaN x, a NaN y, an infinite x.
+    pixel: what rule P3 gives each (llround by integer arithmetic, -1: rejected), not what project() says.
+
+    K: the sum fx x + cx z must not cancel -- with cx = 3.5, fx = 4 and u near -0.5 it is a multiple of 2^-22, and the float just above
+    -0.5 (2^-25 away) is no computed u of any point -- hence EDGE_K, whose u = 4 x / z reaches every f32."""
+    K = np.asarray(K, F)
+    pts, pix = [], []
+    col, row = min(3, w - 1), min(2, h - 1)      # the pixel the other axis stays on
+    for z in (1.0, 2.0, 0.5):
+        other_x, other_y = _coordinate_for(F(col), 0, F(0), z, K), _coordinate_for(F(row), 1, F(0), z, K)
+        for axis, n, other in ((0, w, other_y), (1, h, other_x)):
+            for want in boundary_values(n):
+                cnd = _coordinate_for(want, axis, other, z, K)
+                if cnd is None:
+                    raise ValueError(f"no point at depth {z} projects onto {want!r} on axis {axis} under this K")
+                pts.append([cnd, other, z] if axis == 0 else [other, cnd, z])
+                r = llround_exact(want)
+                pix.append(-1 if not 0 <= r < n else (row * w + r if axis == 0 else r * w + col))
+    x0, y0 = _coordinate_for(F(col), 0, F(0), 1.0, K), _coordinate_for(F(row), 1, F(0), 1.0, K)
+    for cz in (0.0, -0.0, np.finfo(F).smallest_subnormal, -1.0, np.nan, np.inf):
+        pts.append([x0, y0, cz])
+        pix.append(-1)
+    fx = float(K[0, 0])
+    big = [2.0 ** 31 / fx, (2.0 ** 32 - 256) / fx, 2.0 ** 32 / fx, 2.0 ** 40 / fx, 3e38, -(2.0 ** 32) / fx, -3e38, np.nan, np.inf, -np.inf]
+    for b in big:
+        pts += [[b, y0, 1.0], [x0, b, 1.0]]
+        pix += [-1, -1]
+    return np.array(pts, F), np.array(pix, np.int64)
+
+
+def organized_scene(offset=(1.0 / 1024, -1.0 / 2048, 1.0 / 1024)):
+    """the 67 x 45 ray-cast scene unprojected with normals: one target point per inner pixel; the source is every third target point moved
+    by a fixed dyadic offset -> (target, normals, source, K, w, h)"""
+    depth, K = raycast_scene()
+    w, h = 67, 45
+    P, N, _ = depth_to_points(depth, w, h, K, Conv(U16, 1000.0), want_normals=True)
+    src = (P[::3] + np.array(offset, F)).astype(F)
+    return P, N, src, K, w, h

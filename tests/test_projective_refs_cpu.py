@@ -193,3 +193,113 @@ def test_host_rules_by_independent_arithmetic():
     assert np.array_equal(t, np.array([f32(-(e[0][r] * e[0][3] + e[1][r] * e[1][3] + e[2][r] * e[2][3])) for r in range(3)], F))
     for c, b in ((-1.0, 0), (0.0, 0), (0.999, 254), (1.0, 255), (1.004, 255), (2.0, 255), (1e30, 255), (0.5, 127), (1 / 255, 1)):
         assert int(R.byte(np.array([c], F))[0]) == b, c
+
+
+# ---- the crafted scenes of tests/test_gpu_projective_edges.py ----------------------------------------------------------------------
+def tie_groups(pts, K=R.TIE_K, w=8, h=6):
+    """per pixel the indices of its minimal-depth group (ascending)"""
+    i, pix, c = R.project(pts, K, w, h)
+    out = []
+    for p in range(w * h):
+        mem = i[pix == p]
+        out.append(np.sort(mem[c[pix == p, 2] == c[pix == p, 2].min()]) if mem.size else mem)
+    return out
+
+
+def tie_group_span(pts, groups):
+    """the smallest extent, over the groups and the two image axes, of a group's points"""
+    return min(float(min(np.ptp(pts[g, 0]), np.ptp(pts[g, 1]))) for g in groups)
+
+
+def test_tie_scene_ties_are_decided_by_index_alone():
+    """rule P4 / S1 on a scene where the index order has nothing to do with any spatial order: 48 pixels, 64 points of bit-equal depth in
+    each, one farther point behind them"""
+    pts, grp = R.tie_scene()
+    assert pts.shape == (48 * 65, 3)
+    index = R.points_to_index_map(pts, R.TIE_K, 8, 6)
+    assert np.array_equal(index, R.points_to_index_map_literal(pts, R.TIE_K, 8, 6)) and (index != R.EMPTY).all()
+    u, v = R.computed_uv(pts, R.TIE_K)
+    assert np.array_equal(u * 64, np.rint(u * 64)) and np.array_equal(v * 64, np.rint(v * 64))      # exact multiples of 1/64
+    groups = tie_groups(pts)
+    disagree = np.zeros(3, int)
+    for p, g in enumerate(groups):
+        assert g.size >= 64 and np.array_equal(g, np.flatnonzero(grp == p))      # (the far point is in no group)
+        assert index[p] == g.min()
+        q = pts[g]
+        by_xyz, by_zyx = g[np.lexsort((q[:, 2], q[:, 1], q[:, 0]))][0], g[np.lexsort((q[:, 0], q[:, 1], q[:, 2]))][0]
+        disagree += [by_xyz != index[p], by_zyx != index[p], g.max() != index[p]]
+    print("tie scene: pixels where the first by (x, y, z), the first by (z, y, x), the highest index is not the winner:", disagree.tolist())
+    assert (disagree >= 40).all()
+    assert tie_group_span(pts, groups) == 62 / 64 / 4      # 62/64 of a pixel's footprint at z = 1
+    # the other camera of the edge tests sees the same groups in its own frame
+    pts0, grp0 = R.tie_scene(K=R.EDGE_K)
+    index0 = R.points_to_index_map(pts0, R.EDGE_K, 8, 6)
+    assert np.array_equal(index0, R.points_to_index_map_literal(pts0, R.EDGE_K, 8, 6)) and np.array_equal(grp0, grp)
+    assert all(index0[p] == np.flatnonzero(grp0 == p).min() for p in range(48))
+
+
+def test_boundary_points_land_where_rule_p3_says():
+    w, h = 8, 6
+    pts, want = R.boundary_points(w, h)
+    # the computed projections ARE the values of the list (the generating formula alone rounds some of them away), on each of the three depths
+    u, v = R.computed_uv(pts, R.EDGE_K)
+    nu, nv = len(R.boundary_values(w)), len(R.boundary_values(h))
+    for k in range(3):
+        blk = k * (nu + nv)
+        assert np.array_equal(u[blk:blk + nu], np.array(R.boundary_values(w), F)) and (v[blk:blk + nu] == 2).all()
+        assert np.array_equal(v[blk + nu:blk + nu + nv], np.array(R.boundary_values(h), F)) and (u[blk + nu:blk + nu + nv] == 3).all()
+    assert float(R.boundary_values(w)[1]) == -0.5 + 2.0 ** -25 and float(R.boundary_values(w)[7]) == 7.5 - 2.0 ** -21
+    # rule P3, literally: -0.5 out, just above it pixel 0, -0.25 -> 0, 0.5 -> 1, 1.5 -> 2, 2.5 -> 3, w - 1, just below w - 0.5 -> w - 1, w - 0.5 out
+    assert want[:nu].tolist() == [-1, 16, 16, 17, 18, 19, 23, 23, -1]
+    assert want[nu:nu + nv].tolist() == [-1, 3, 3, 11, 19, 27, 43, 43, -1]
+    assert (want[3 * (nu + nv):] == -1).all() and want.size - 3 * (nu + nv) == 6 + 20
+    i, pix, _ = R.project(pts, R.EDGE_K, w, h)
+    got = np.full(pts.shape[0], -1, np.int64)
+    got[i] = pix
+    assert np.array_equal(got, want)
+    with np.errstate(all="ignore"):
+        for k in range(pts.shape[0]):      # the serial loop, one point at a time
+            ind = R._pixel_literal(pts[k], R.EDGE_K, w, h)
+            assert (-1 if ind is None else ind) == want[k], (k, pts[k])
+    assert np.array_equal(R.points_to_index_map(pts, R.EDGE_K, w, h), R.points_to_index_map_literal(pts, R.EDGE_K, w, h))
+    # under the tie scene's own camera the float just above -0.5 is no point's projection: 4 x + 3.5 is a multiple of 2^-22 there
+    just_above = np.nextafter(F(-0.5), F(0))
+    for z in (1.0, 2.0, 0.5):
+        assert R._coordinate_for(just_above, 0, F(0), z, R.TIE_K) is None and R._coordinate_for(just_above, 0, F(0), z, R.EDGE_K) is not None
+        assert R._coordinate_for(F(-0.5), 0, F(0), z, R.TIE_K) is not None      # (the search itself works under that camera)
+        x = R._coordinate_for(F(-0.5) + F(2.0 ** -22), 0, F(0), z, R.TIE_K)      # the nearest projection above -0.5 that exists there
+        assert x is not None and R.computed_uv(np.array([[x, 0, z]], F), R.TIE_K)[0][0] == F(-0.5) + F(2.0 ** -22)
+    # the searches agree on them too, as a source and inside a target
+    dst = R.tie_scene(K=R.EDGE_K)[0]
+    for a, b in ((dst, pts), (np.concatenate([pts, dst]), dst[:200])):
+        got, lit = R.projective_search(a, b, np.eye(4, dtype=F), 3e38, R.EDGE_K, w, h), R.projective_search_literal(a, b, np.eye(4, dtype=F), 3e38, R.EDGE_K, w, h)
+        assert np.array_equal(got[0], lit[0]) and np.array_equal(got[1].view(np.uint32), lit[1].view(np.uint32))
+
+
+def test_organized_scene_projective_is_the_nearest_neighbour(orc):
+    """one target point per pixel and a source a small fixed step away from every third of them: the projective search and an exhaustive
+    nearest-neighbour search under the same radius name the same matches with the same values -- what lets a projective and a grid context be
+    compared byte for byte (tests/test_gpu_projective_edges.py)"""
+    P, N, S, K, w, h = R.organized_scene()
+    assert P.shape == N.shape == (65 * 43, 3) and S.shape[0] == 932
+    i, pix, _ = R.project(P, K, w, h)
+    assert i.size == P.shape[0] and np.unique(pix).size == P.shape[0]      # one point per pixel
+    si, spix, _ = R.project(S, K, w, h)
+    assert si.size == S.shape[0] and np.array_equal(spix, pix[::3])      # (a) every source point on its own target point's pixel
+    r2 = float(F(0.05) ** 2)
+    I = np.eye(4, dtype=F)
+    nn, val = R.projective_search(P, S, I, r2, K, w, h)
+    lit = R.projective_search_literal(P, S, I, r2, K, w, h)
+    assert np.array_equal(nn, lit[0]) and np.array_equal(val.view(np.uint32), lit[1].view(np.uint32))
+    bi, bd = orc.nn_brute(P, S, r2)
+    assert (nn != R.EMPTY).all() and np.array_equal(nn.astype(np.int64), bi) and np.array_equal(nn, np.arange(0, P.shape[0], 3))      # (b)
+    assert np.array_equal(val.view(np.uint32), bd.view(np.uint32))
+
+
+def test_the_oracle_update_accepts_an_empty_set(orc):
+    P, N, S, _, _, _ = R.organized_scene()
+    T0 = R.small_E(angles=(0.004, -0.003, 0.005), t=(0.004, -0.003, 0.002))
+    none = np.zeros(0, np.int64)
+    for metric in (0, 1):
+        T, delta = orc.icp_update(P, N, S, T0, none, none, orc.make_params(metric=metric, max_iter=1, conv_tol=0.0, max_sq_dist=1e-14))
+        assert np.array_equal(T, T0) and delta == 0.0
