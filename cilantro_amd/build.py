@@ -15,7 +15,7 @@ LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(HERE, "lib", "obj")
 LIB = os.path.join(LIBDIR, "libcilantro_hip.so")
 SOURCES = ["kernels.hip", "warm.hip", "epilogue.hip", "affine.hip", "feat_warm.hip", "extract.hip", "grid_build.hip", "grid_downsample.hip", "components.hip", "components_nd.hip", "mean_shift.hip", "mean_shift_nd.hip", "image_conversions.hip", "fusion.hip", "warp_field.hip", "warp_field_icp.hip", "spectral.hip", "mds.hip", "pca.hip", "convex_hull.hip", "polytope_query.hip", "projective.hip", "filters.hip", "kmeans.hip", "ransac.hip", "ransac_transform.hip", "knn.hip", "knn_nd.hip", "robust_normals.hip", "bidir.hip", "tie_build.hip", "c_api.hip", "tie_tables.hip", "estimate.hip", "shard_keys.hip", "icp_loop.hip", "multi.hip"]
-HEADERS = ["internal.hpp", "ctx.hpp", "ctx_options.hpp", "device_mem.hpp", "device_prims.hpp", "stateless.hpp", "ransac_sampling.hpp", "loop_policy.hpp", "grid_policy.hpp", "solve.hpp", "rccl_api.hpp", "search_device.hpp", "affine_device.hpp", "image_device.hpp", "warp_field.hpp", "small_sym.hpp", "subspace_device.hpp", "mds_host.hpp", "hull_host.hpp", "knn_lists.hpp", "knn_nd_host.hpp", "nd_device.hpp", "mean_shift_nd_host.hpp", "components_device.hpp", "components_nd_host.hpp", "grid_ball.hpp", "mean_shift_device.hpp", os.path.join("..", "..", "include", "cilantro_hip", "c_api.h")]
+HEADERS = ["internal.hpp", "ctx.hpp", "ctx_options.hpp", "device_mem.hpp", "device_prims.hpp", "stateless.hpp", "ransac_sampling.hpp", "loop_policy.hpp", "grid_policy.hpp", "solve.hpp", "rccl_api.hpp", "search_device.hpp", "rank_update.hpp", "affine_device.hpp", "image_device.hpp", "warp_field.hpp", "small_sym.hpp", "subspace_device.hpp", "mds_host.hpp", "hull_host.hpp", "knn_lists.hpp", "knn_nd_host.hpp", "nd_device.hpp", "mean_shift_nd_host.hpp", "components_device.hpp", "components_nd_host.hpp", "grid_ball.hpp", "mean_shift_device.hpp", os.path.join("..", "..", "include", "cilantro_hip", "c_api.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -ffp-contract=off: the pinned f32 expressions (d2, T*s, per-term residuals) must round exactly as
 # written on host and device; f64 accumulations use explicit fma().

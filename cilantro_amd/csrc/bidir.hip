@@ -389,7 +389,7 @@ __global__ __launch_bounds__(256) void k_reverse_warm(GridDev sg, const float4* 
     if (settled) rev_d2[jd] = e;
     const bool todo = valid && !settled;
     const unsigned long long um = __ballot(todo);
-    if (todo) wl[wcnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(um >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)um, 0u))] = jd;
+    if (todo) wl[wcnt + ballot_slot(um)] = jd;
     wcnt += (uint32_t)__popcll(um);
     if (ACC != IM_NONE) { const bool cnt = counts(jd, sp); rank.update(zb, lane, settled && cnt, qx, qy, qz, p, nv, ra.dst_mean, smt); }
   }

@@ -97,7 +97,7 @@ __global__ __launch_bounds__(256) void k_feat_warm(IterArgs a) {
     if (settled && a.nn_d2) a.nn_d2[i] = e;      // (the value the search compares: the same expression on the same operands)
     const bool todo = valid && !settled;
     const unsigned long long um = __ballot(todo);
-    if (todo) wl[wcnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(um >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)um, 0u))] = i;
+    if (todo) wl[wcnt + ballot_slot(um)] = i;
     wcnt += (uint32_t)__popcll(um);
     nlisted += (uint32_t)__popcll(um);
     if (ACC != IM_NONE) {

@@ -37,6 +37,7 @@
 //     kernel keeps per-lane f64 accumulators instead.  Fixed orders everywhere (per wave, per block, across blocks)
 //     => bitwise run-to-run reproducible (the reference's OpenMP reduction is not).
 #include "search_device.hpp"
+#include "rank_update.hpp"
 
 namespace cilhip {
 
@@ -1052,8 +1053,6 @@ __global__ __launch_bounds__(TILE_THREADS, CILHIP_TILE_WAVES_PER_SIMD) void k_se
   // matched point and its normal gathered right after the search (above) -- all of it touched by this tile a moment ago.
   // From here on nobody reads the staged points or the cell table: the point buffer becomes per-wave scratch.
   {
-    constexpr int NC = FusedZ<ACC>::NC;
-    constexpr bool DUAL = NC <= 8;        // two groups of 4 correspondences per instruction: rows/cols 0-7 and 8-15
     float z[TILE_QPT][16];
 #pragma unroll
     for (int u = 0; u < TILE_QPT - 1; ++u) {
@@ -1075,63 +1074,20 @@ __global__ __launch_bounds__(TILE_THREADS, CILHIP_TILE_WAVES_PER_SIMD) void k_se
     PHASE_CLK(4);
     const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
     float* const zb = reinterpret_cast<float*>(raw) + wave * (FUSED_WAVE_BYTES / 4);
-    typedef double double4_t __attribute__((ext_vector_type(4)));
-    double4_t acc = {0.0, 0.0, 0.0, 0.0};
+    // (layouts, matrix-core loop, tile and row: rank_update.hpp)
+    using Rank = WaveRank<ACC>;
+    typename Rank::double4_t acc = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int u = 0; u < TILE_QPT; ++u) {
-      if (DUAL) {
-        // [64 correspondences][8 floats]; the second half of the wave 16 floats further (so that the two groups an
-        // instruction reads sit on different banks)
-        float4* w4 = reinterpret_cast<float4*>(zb + lane * 8 + (lane >= 32 ? 16 : 0));
-        w4[0] = make_float4(z[u][0], z[u][1], z[u][2], z[u][3]);
-        w4[1] = make_float4(z[u][4], z[u][5], z[u][6], z[u][7]);
-      } else {
-        float2* w2 = reinterpret_cast<float2*>(zb + lane * NC);
-#pragma unroll
-        for (int c = 0; c < NC / 2; ++c) w2[c] = make_float2(z[u][2 * c], z[u][2 * c + 1]);
-      }
-      __builtin_amdgcn_wave_barrier();    // (DS operations of one wave execute in order: the reads below see the writes)
-      if (DUAL) {
-        const int comp = lane & 7, half = (lane >> 3) & 1, k4 = lane >> 4;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int qi = half * 32 + 4 * j + k4;
-          const double x = (double)zb[qi * 8 + half * 16 + comp];
-          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(x, x, acc, 0, 0, 0);
-        }
-      } else {
-        const int comp = lane & 15, k4 = lane >> 4;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-          const float f = zb[(4 * j + k4) * NC + (comp < NC ? comp : 0)];
-          const double x = comp < NC ? (double)f : 0.0;
-          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(x, x, acc, 0, 0, 0);
-        }
-      }
+      Rank::stage(zb, lane, z[u]);
+      __builtin_amdgcn_wave_barrier();    // (DS operations of one wave execute in order: the reads see the writes)
+      Rank::mfma_round(zb, lane, acc);
       __builtin_amdgcn_wave_barrier();
     }
-    // D[(lane >> 4) + 4 r][lane & 15] = acc[r]  ->  this wave's 16x16 tile in its scratch, then one fixed-order sum
-    double* const db = reinterpret_cast<double*>(raw + wave * FUSED_WAVE_BYTES);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) db[r * 64 + lane] = acc[r];
+    Rank::store_tile(raw, wave, lane, acc);      // this wave's 16x16 tile in its scratch, then one fixed-order sum
     __syncthreads();
     PHASE_CLK(5);
-    if (threadIdx.x < SUMS_MAX) {
-      int i1, j1, i2, j2;
-      const bool used = FusedZ<ACC>::slot_terms((int)threadIdx.x, i1, j1, i2, j2);
-      double v1 = 0.0, v2 = 0.0;
-      if (used) {
-        const int e1 = (i1 >> 2) * 64 + 16 * (i1 & 3) + j1, e1b = ((i1 + 8) >> 2) * 64 + 16 * ((i1 + 8) & 3) + j1 + 8;
-        const int e2 = i2 >= 0 ? (i2 >> 2) * 64 + 16 * (i2 & 3) + j2 : 0, e2b = i2 >= 0 ? ((i2 + 8) >> 2) * 64 + 16 * ((i2 + 8) & 3) + j2 + 8 : 0;
-        for (int w = 0; w < TILE_WAVES; ++w) {
-          const double* dw = reinterpret_cast<const double*>(raw + w * FUSED_WAVE_BYTES);
-          v1 += dw[e1];
-          if (DUAL) v1 += dw[e1b];
-          if (i2 >= 0) { v2 += dw[e2]; if (DUAL) v2 += dw[e2b]; }
-        }
-      }
-      a.tile_partials[(size_t)vb * SUMS_MAX + threadIdx.x] = v1 - v2;
-    }
+    Rank::template fold_row<TILE_WAVES>(raw, a.tile_partials + (size_t)vb * SUMS_MAX);
     PHASE_CLK(6);
   }
 }
@@ -1170,7 +1126,6 @@ __global__ __launch_bounds__(ITER_THREADS) void k_search_deferred(IterArgs a, co
 #pragma unroll
   for (int i = 0; i < (TR::NB > 0 ? TR::NB : 1); ++i) accB[i] = 0.0;
 
-  const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
   const uint32_t W = ntiles * (2 * TILE_WAVES), nchunks = (W + 63u) >> 6;
   // (margin keys / match records of the warm-started iterations: the generic search proves its result but keeps no bound on
   //  the other points -- "no bound known"; the warm kernel searches such a query itself and then has one)
@@ -1298,30 +1253,8 @@ __global__ __launch_bounds__(ITER_THREADS) void k_search_deferred(IterArgs a, co
     }
     __syncthreads();    // (the lists are rewritten by the next chunk)
   }
-  if (ACC != IM_NONE) {
-    __shared__ double sh[ITER_WAVES][SUMS_MAX];
-    if (has_work) {         // (block-uniform; a block that searched nothing contributes exact zeros, as the sums below would)
-      if (threadIdx.x < SUMS_MAX) {
-#pragma unroll
-        for (int w = 0; w < ITER_WAVES; ++w) sh[w][threadIdx.x] = 0.0;
-      }
-      __syncthreads();
-#pragma unroll
-      for (int k = 0; k < TR::NA; ++k) {
-        const double v = wave_sum(accA[k]);
-        if (lane == 0) sh[wave][k] = v;
-      }
-#pragma unroll
-      for (int k = 0; k < TR::NB; ++k) {
-        const double v = wave_sum(accB[k]);
-        if (lane == 0) sh[wave][28 + k] = v;
-      }
-      __syncthreads();
-    }
-    if (threadIdx.x < SUMS_MAX)
-      a.partials[(size_t)blockIdx.x * SUMS_MAX + threadIdx.x] =
-          has_work ? (sh[0][threadIdx.x] + sh[1][threadIdx.x]) + (sh[2][threadIdx.x] + sh[3][threadIdx.x]) : 0.0;
-  }
+  // (has_work, block-uniform: a block that searched nothing contributes exact zeros)
+  if (ACC != IM_NONE) fold_lane_sums<ACC>(accA, accB, a.partials + (size_t)blockIdx.x * SUMS_MAX, has_work);
 }
 
 // blocks of the clean-up pass (64 mask words = two tiles per chunk; at most 4096 blocks, then several chunks each -- a block
@@ -1649,29 +1582,7 @@ __global__ __launch_bounds__(ITER_THREADS, (METRIC == IM_NONE && SEARCH) ? 4 : 1
   }
   }
 
-  if (METRIC != IM_NONE) {
-    __shared__ double sh[ITER_WAVES][SUMS_MAX];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x < SUMS_MAX) {
-#pragma unroll
-      for (int w = 0; w < ITER_WAVES; ++w) sh[w][threadIdx.x] = 0.0;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < TR::NA; ++k) {
-      const double v = wave_sum(accA[k]);
-      if (lane == 0) sh[wave][k] = v;
-    }
-#pragma unroll
-    for (int k = 0; k < TR::NB; ++k) {
-      const double v = wave_sum(accB[k]);
-      if (lane == 0) sh[wave][28 + k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < SUMS_MAX)
-      a.partials[(size_t)vb * SUMS_MAX + threadIdx.x] =
-          (sh[0][threadIdx.x] + sh[1][threadIdx.x]) + (sh[2][threadIdx.x] + sh[3][threadIdx.x]);
-  }
+  if (METRIC != IM_NONE) fold_lane_sums<METRIC>(accA, accB, a.partials + (size_t)vb * SUMS_MAX);
 }
 
 // ---- accumulation over REVERSE matches (search directions FIRST_TO_SECOND / BOTH without post-filters) ----------------
@@ -1726,26 +1637,7 @@ __global__ __launch_bounds__(ITER_THREADS) void k_acc_reverse(IterArgs a, const 
     if (a.cw.enabled) pair_weights(a.cw, d2_pinned(qx, qy, qz, p.x, p.y, p.z), wq, wp);     // the reverse search's distance, formed again
     accumulate_pair<METRIC>(accA, accB, T, iL, it, smt, dmean, false, true, qx, qy, qz, i, p, nv, nv, wq, wp);
   }
-  __shared__ double sh[ITER_WAVES][SUMS_MAX];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x < SUMS_MAX) {
-#pragma unroll
-    for (int w = 0; w < ITER_WAVES; ++w) sh[w][threadIdx.x] = 0.0;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < TR::NA; ++k) {
-    const double v = wave_sum(accA[k]);
-    if (lane == 0) sh[wave][k] = v;
-  }
-#pragma unroll
-  for (int k = 0; k < TR::NB; ++k) {
-    const double v = wave_sum(accB[k]);
-    if (lane == 0) sh[wave][28 + k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < SUMS_MAX)
-    a.partials[(size_t)vb * SUMS_MAX + threadIdx.x] = (sh[0][threadIdx.x] + sh[1][threadIdx.x]) + (sh[2][threadIdx.x] + sh[3][threadIdx.x]);
+  fold_lane_sums<METRIC>(accA, accB, a.partials + (size_t)vb * SUMS_MAX);
 }
 
 void launch_acc_reverse(const IterArgs& a, int metric, const float4* sgrid_pts, const uint32_t* rev_pos, uint32_t nd, int mode, const uint32_t* fwd_pos,

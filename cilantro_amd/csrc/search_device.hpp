@@ -810,6 +810,10 @@ __device__ __forceinline__ double wave_sum(double v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
   return v;
 }
+// a lane's slot in a list filled in BALLOT order: the number of lanes below it that are set in `mask` (no atomics, the same list in every run)
+__device__ __forceinline__ uint32_t ballot_slot(unsigned long long mask) {
+  return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
 
 // exp() for the RBF weight evaluator in PINNED f32 arithmetic (one fixed sequence of correctly rounded operations, the same
 // in oracle/icp_oracle.c): round-to-nearest argument reduction by ln 2 (two-part constant), degree-6 polynomial, exact
@@ -852,6 +856,37 @@ struct AccTraits {
   static constexpr int NA = affine ? (METRIC == IM_AFF0 ? 35 : 30) : kabsch ? 16 : (plane ? 28 : 1);  // slots [0, NA)
   static constexpr int NB = point ? 16 : 0;                  // slots [28, 28+NB)
 };
+
+// The block's row of SUMS_MAX sums from every lane's f64 accumulators (accA: slots [0, NA), accB: slots [28, 28 + NB)): each
+// accumulator summed over its wave, the waves added in the fixed order (w0 + w1) + (w2 + w3) -- bitwise reproducible.  Every thread
+// of a block of ITER_THREADS calls this (two block-wide barriers inside).  has_work (BLOCK-UNIFORM): false for a block that
+// accumulated nothing -- exact zeros, as the sums would be, without the reduction.
+template <int METRIC>
+__device__ __forceinline__ void fold_lane_sums(const double* accA, const double* accB, double* row, const bool has_work = true) {
+  using TR = AccTraits<METRIC>;
+  static_assert(ITER_WAVES == 4, "the fixed order below names four waves");
+  __shared__ double sh[ITER_WAVES][SUMS_MAX];
+  const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+  if (has_work) {
+    if (threadIdx.x < SUMS_MAX) {
+#pragma unroll
+      for (int w = 0; w < ITER_WAVES; ++w) sh[w][threadIdx.x] = 0.0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < TR::NA; ++k) {
+      const double v = wave_sum(accA[k]);
+      if (lane == 0) sh[wave][k] = v;
+    }
+#pragma unroll
+    for (int k = 0; k < TR::NB; ++k) {
+      const double v = wave_sum(accB[k]);
+      if (lane == 0) sh[wave][28 + k] = v;
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < SUMS_MAX) row[threadIdx.x] = has_work ? (sh[0][threadIdx.x] + sh[1][threadIdx.x]) + (sh[2][threadIdx.x] + sh[3][threadIdx.x]) : 0.0;
+}
 
 // The accumulation of one matched pair (q = T*s already formed): what every accumulating kernel adds per correspondence.
 // accA / accB are the caller's per-lane f64 accumulators (slots [0, NA) and [28, 28 + NB) of a partial-sum row).

@@ -1,5 +1,6 @@
 // warm.hip -- the warm-started iteration (k_warm<metric, rec>: margin proof, list search, matrix-core accumulation) and k_self_nn's nearest-other-point table; split from kernels.hip (overview there, DESIGN.md sections 5 and 6.2).
 #include "search_device.hpp"
+#include "rank_update.hpp"
 #include "affine_device.hpp"
 
 namespace cilhip {
@@ -180,11 +181,9 @@ __global__ __launch_bounds__(WARM_THREADS, 4) void k_warm(IterArgs a) {
   unsigned long long tprev_ = wall_clock64();
   if (threadIdx.x == 0 && blockIdx.x < 4096u) g_warm_stamp[blockIdx.x][0] = tprev_;
 #endif
-  typedef double double4_t __attribute__((ext_vector_type(4)));
-  double4_t acc = {0.0, 0.0, 0.0, 0.0};
+  using Rank = WaveRank<ACC>;      // (the rigid classes' layouts, matrix-core loop and row: rank_update.hpp; AFF: affine_device.hpp)
+  typename Rank::double4_t acc = {0.0, 0.0, 0.0, 0.0};
   const AffLane afl = aff_lane((int)(threadIdx.x & 63u));
-  constexpr int NC = FusedZ<ACC>::NC;
-  constexpr bool DUAL = NC <= 8;
   constexpr bool NRM = FusedZ<ACC>::needs_normal;
 
   const uint32_t nb = gridDim.x;
@@ -219,44 +218,19 @@ __global__ __launch_bounds__(WARM_THREADS, 4) void k_warm(IterArgs a) {
     const float t2 = __fadd_rn(__fmul_rn(T[2], sn.x), __fadd_rn(__fmul_rn(T[5], sn.y), __fmul_rn(T[8], sn.z)));
     return make_float4(__fadd_rn(nd.x, t0), __fadd_rn(nd.y, t1), __fadd_rn(nd.z, t2), 0.f);
   };
-  // rank update of the wave's 16x16 tile with one round of (up to) 64 correspondences (k_search_tiled, step 5)
+  // rank update of the wave's 16x16 tile with one round of (up to) 64 correspondences (rank_update.hpp; k_search_tiled, step 5)
   // (two halves: the terms z of the wave's correspondences -> LDS; then LDS -> f64 operands -> the matrix cores.  Between them
   //  a round's streamed registers are dead, which is where the streaming loop requests the data of the round after next.)
   auto z_to_lds = [&](bool has, float qx, float qy, float qz, const float4 pm, const float4 nm) {
     if (AFF) { aff_record<NRM>(has, qx, qy, qz, pm, nm, dmn, smt, zb + lane * AFF_REC); return; }
     float z[16];
     fused_z<ACC>(has, qx, qy, qz, pm, nm, a.dst_mean, smt, z);
-    if (DUAL) {
-      float4* w4 = reinterpret_cast<float4*>(zb + lane * 8 + (lane >= 32 ? 16 : 0));
-      w4[0] = make_float4(z[0], z[1], z[2], z[3]);
-      w4[1] = make_float4(z[4], z[5], z[6], z[7]);
-    } else {
-      float2* w2 = reinterpret_cast<float2*>(zb + lane * NC);
-#pragma unroll
-      for (int c = 0; c < NC / 2; ++c) w2[c] = make_float2(z[2 * c], z[2 * c + 1]);
-    }
+    Rank::stage(zb, lane, z);
   };
   auto lds_to_mfma = [&]() {
     __builtin_amdgcn_wave_barrier();
-    if (AFF) {
-      aff_mfma_round(zb, lane, afl, acc);
-    } else if (DUAL) {
-      const int comp = lane & 7, hf = (lane >> 3) & 1, k4 = lane >> 4;
-#pragma unroll
-      for (int jj = 0; jj < 8; ++jj) {
-        const int qi = hf * 32 + 4 * jj + k4;
-        const double x = (double)zb[qi * 8 + hf * 16 + comp];
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(x, x, acc, 0, 0, 0);
-      }
-    } else {
-      const int comp = lane & 15, k4 = lane >> 4;
-#pragma unroll
-      for (int jj = 0; jj < 16; ++jj) {
-        const float f = zb[(4 * jj + k4) * NC + (comp < NC ? comp : 0)];
-        const double x = comp < NC ? (double)f : 0.0;
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(x, x, acc, 0, 0, 0);
-      }
-    }
+    if (AFF) aff_mfma_round(zb, lane, afl, acc);
+    else Rank::mfma_round(zb, lane, acc);
     __builtin_amdgcn_wave_barrier();
   };
   auto rank_update = [&](bool has, float qx, float qy, float qz, const float4 pm, const float4 nm) {
@@ -458,7 +432,7 @@ __global__ __launch_bounds__(WARM_THREADS, 4) void k_warm(IterArgs a) {
     const unsigned long long um = __ballot(todo);
     if (todo) {
       // the list entry and its bound: the squared distance to the old match if it has one inside the radius, else the radius
-      const uint32_t o = qcount + __builtin_amdgcn_mbcnt_hi((uint32_t)(um >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)um, 0u));
+      const uint32_t o = qcount + ballot_slot(um);
       wq[o] = make_float4(qx, qy, qz, __uint_as_float(i));
       wr[o] = ((REC == 2 ? !(keyv < 0.0f) : w != NONE_U32) && e_old < a.max_sq) ? e_old : a.max_sq;
     }
@@ -585,7 +559,7 @@ __global__ __launch_bounds__(WARM_THREADS, 4) void k_warm(IterArgs a) {
 #endif
       // (this round's entries are in registers: the front of the list up to b0 + 64 is free)
       if (open) {
-        const uint32_t o = nopen + __builtin_amdgcn_mbcnt_hi((uint32_t)(om >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)om, 0u));
+        const uint32_t o = nopen + ballot_slot(om);
         wq[o] = ent; wr[o] = R2;
       }
       nopen += (uint32_t)__popcll(om);
@@ -615,26 +589,9 @@ __global__ __launch_bounds__(WARM_THREADS, 4) void k_warm(IterArgs a) {
     aff_write_row<WARM_WAVES>(raw, (int)(tid_now >> 6), lane, acc, a.partials + (size_t)vb * AFF_ROW);
     return;
   }
-  double* const db = reinterpret_cast<double*>(raw + wave * FUSED_WAVE_BYTES);
-#pragma unroll
-  for (int r = 0; r < 4; ++r) db[r * 64 + lane] = acc[r];
+  Rank::store_tile(raw, wave, lane, acc);
   __syncthreads();
-  if (threadIdx.x < SUMS_MAX) {
-    int i1, j1, i2, j2;
-    const bool used = FusedZ<ACC>::slot_terms((int)threadIdx.x, i1, j1, i2, j2);
-    double v1 = 0.0, v2 = 0.0;
-    if (used) {
-      const int e1 = (i1 >> 2) * 64 + 16 * (i1 & 3) + j1, e1b = ((i1 + 8) >> 2) * 64 + 16 * ((i1 + 8) & 3) + j1 + 8;
-      const int e2 = i2 >= 0 ? (i2 >> 2) * 64 + 16 * (i2 & 3) + j2 : 0, e2b = i2 >= 0 ? ((i2 + 8) >> 2) * 64 + 16 * ((i2 + 8) & 3) + j2 + 8 : 0;
-      for (int w = 0; w < WARM_WAVES; ++w) {
-        const double* dw = reinterpret_cast<const double*>(raw + w * FUSED_WAVE_BYTES);
-        v1 += dw[e1];
-        if (DUAL) v1 += dw[e1b];
-        if (i2 >= 0) { v2 += dw[e2]; if (DUAL) v2 += dw[e2b]; }
-      }
-    }
-    a.partials[(size_t)vb * SUMS_MAX + threadIdx.x] = v1 - v2;
-  }
+  Rank::template fold_row<WARM_WAVES>(raw, a.partials + (size_t)vb * SUMS_MAX);
   WARM_CLK(5);
 #ifdef CILHIP_EXP_PHASE_CLOCKS
   if (threadIdx.x == 0 && blockIdx.x < 4096u) g_warm_stamp[blockIdx.x][1] = wall_clock64();

@@ -176,7 +176,7 @@ def test_reference_notices_every_mutation():
                 for j in range(i + 1, len(used)):
                     sw = list(base); sw[used[i]], sw[used[j]] = sw[used[j]], sw[used[i]]
                     assert sw != base, (n, metric, used[i], used[j])
-            if metric in (sr.PLANE, sr.BOTH):             # the plane vector without n_z (rank_update.hpp:20)
+            if metric in (sr.PLANE, sr.BOTH):             # the plane vector without n_z (rank_update.hpp: head comment)
                 N0 = fix["N"].copy(); N0[:, 2] = 0.0
                 assert sr.expected_sums(metric, fix["D"], N0, fix["S"], fix["T"], fix["dst_mean"], fix["src_mean"], fix["match"], has)[0] != base
 
